@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X CoTracker3 hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one ``CoTrackerPredictor.forward`` (resize -> CNN encoder -> pyramid -> all windows x 6
@@ -26,6 +26,10 @@ Prints ONE JSON line (rank 0) with the contract keys plus
   parity       -- max-abs error of THIS run's tracks / logits against the unmodified reference's CPU outputs at
                   BASELINE scale (tests/golden/scale_*.npz), next to the reference's own thread-count noise
   kernels      -- per-kernel launch counts / avg duration / achieved rate from the same HIP events
+
+--dump-outputs DIR writes what the LAST TIMED step returned to its caller as DIR/<name>.npy (float32): pred_tracks,
+pred_visibility and, where the model keeps them, the visibility / confidence logits behind the latter.  Video, weights and queries
+are seeded, so two builds of the library run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -43,6 +47,7 @@ if ROOT not in sys.path:
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 256 CU x 4 SIMD x 64 FLOP/clk x 2.4 GHz
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense f16/bf16 MFMA (v_mfma_f32_32x32x16_f16), no sparsity
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files of one dump together
 
 WORKLOADS = {
     # name: (H, W, T, grid, offline, window_len, description)
@@ -90,7 +95,29 @@ def parse():
                     help="dev/test: every rank uses cuda:0 (rank-sharded code path on a 1-GPU box; numbers are meaningless)")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32"],
                     help="Linear back end: split-half MFMA (3 f16 MFMAs per product, fp32-class accuracy) or exact-f32 MFMA")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array, DUMP_LIMIT_BYTES in all.  A set of arrays above the limit is cut down
+    by the same factor everywhere: each file then holds a fixed, seeded sample of the flattened array (ascending positions), which
+    is the same sample for every run with the same arguments.  Returns what was written, for the JSON line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy()) for k, v in arrays.items()}
+    keep = min(1.0, (DUMP_LIMIT_BYTES - 1024 * len(arrays)) / sum(a.nbytes for a in arrays.values()))  # 1 KiB: the .npy header
+    written = {}
+    for name, a in arrays.items():
+        if keep < 1.0:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": keep < 1.0}
+    return written
 
 
 def cpu_model():
@@ -539,14 +566,16 @@ def main():
     if world != args.gpus:
         if "WORLD_SIZE" in os.environ:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-        # plain `python bench.py --gpus N`: become the launcher (one rank per GPU over RCCL, rendezvous on 127.0.0.1)
+        # plain `python bench.py --gpus N`: run the launcher as a child (one rank per GPU over RCCL, rendezvous on 127.0.0.1)
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0))
             port = sock.getsockname()[1]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)]
+                                        + sys.argv[1:]).returncode)
     if args.single_device:
         local_rank = 0
     elif world > 1 and torch.cuda.device_count() < world:
@@ -712,6 +741,11 @@ def main():
         if bad:
             print(f"bench.py: timed steps {bad[:16]} differ bitwise from the first timed step", file=sys.stderr)
     kept = None
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        logits = getattr(pred.model, "last_logits", None) or ()  # CoTracker3: (visibility, confidence); CoTracker2: (visibility,)
+        dumped = dump_outputs(args.dump_outputs, {"pred_tracks": out[0], "pred_visibility": out[1],
+                                                  **dict(zip(("visibility_logits", "confidence_logits"), logits))})
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -749,7 +783,7 @@ def main():
         # day a multi-GPU node runs this line
         "all_gather_share_of_step": None if all_gather_ms is None else round(all_gather_ms / (sec_per_step * 1e3), 5),
         "all_gather_ok": None if all_gather_ms is None else bool(all_gather_ms < 0.01 * sec_per_step * 1e3),
-        "steps_bit_identical": steps_bit_identical,
+        "steps_bit_identical": steps_bit_identical, "dumped_outputs": dumped,
         "config": {"workload": desc, "name": args.workload, "points_per_gpu": n_per_rank, "frames": frames_per_step, "video": [H, W],
                    "iters": 6, "window_len": wl, "offline": bool(offline) and offline != "v2", "sharding": sharding,
                    "precision": args.precision, "weights": "seeded synthetic (no checkpoints offline)"},

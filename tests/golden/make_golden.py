@@ -1,8 +1,8 @@
 """Generate golden vectors by executing the UNMODIFIED reference on CPU fp32.
 
-Run in the build container only (needs /root/reference):
+Needs a checkout of the reference (facebookresearch/co-tracker):
 
-    python tests/golden/make_golden.py
+    COTRACKER_REFERENCE=<checkout> python tests/golden/make_golden.py
 
 The reference cannot travel to the GPU box, so its outputs are committed here
 as small .npz fixtures.  Weights are NOT stored: both sides regenerate them with
@@ -18,7 +18,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["COTRACKER_REFERENCE"])  # a checkout of facebookresearch/co-tracker
 
 from cotracker.models.core.model_utils import bilinear_sampler  # noqa: E402
 from cotracker.models.core.cotracker.cotracker3_online import CoTrackerThreeOnline, posenc  # noqa: E402

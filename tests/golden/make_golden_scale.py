@@ -1,8 +1,8 @@
 """Goldens at BASELINE.json scale: the UNMODIFIED reference on CPU fp32 at the real 384x512 model resolution.
 
-Run in the build container only (needs /root/reference):
+Needs a checkout of the reference (facebookresearch/co-tracker):
 
-    python tests/golden/make_golden_scale.py c2 c4 c3_g40 c3_g80      # any subset, in this order of cost
+    COTRACKER_REFERENCE=<checkout> python tests/golden/make_golden_scale.py c2 c4 c3_g40 c3_g80      # any subset, in this order of cost
 
 Workloads are bench.py's (same synthetic video seed 1234, same ``fill_synthetic_(seed=0)`` weights):
   c2      BASELINE configs[1]: CoTrackerPredictor(offline=True, window_len=60), 256x256, T=48, grid 20 (N=400)
@@ -30,7 +30,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["COTRACKER_REFERENCE"])  # a checkout of facebookresearch/co-tracker
 
 from cotracker.predictor import CoTrackerPredictor, CoTrackerOnlinePredictor  # noqa: E402
 

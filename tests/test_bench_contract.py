@@ -1,8 +1,13 @@
 """bench.py contract pieces that need no GPU: workload table vs BASELINE.json, the roofline object, the CPU baseline
-(numpy oracle on a bounded sample) and the PMC-traffic attachment rule."""
+(numpy oracle on a bounded sample), the PMC-traffic attachment rule and the --dump-outputs writer; on the GPU, --steps and
+--dump-outputs of a real run."""
 import json
 import os
+import subprocess
 import sys
+
+import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -113,3 +118,41 @@ def test_committed_pmc_traffic_is_tagged_with_its_workload():
     assert d["_workload"] == "c3_sliding"
     rows = [v for k, v in d.items() if k.startswith("gemm_sh")]
     assert rows and rows[0]["hbm_bytes_per_launch"] > 0 and "FETCH_SIZE x2" in rows[0]["source"]
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    import torch
+    tracks, vis = torch.arange(6000.0).reshape(1, 30, 100, 2), torch.arange(3000).reshape(1, 30, 100) % 3 == 0
+    w = bench.dump_outputs(str(tmp_path / "all"), {"pred_tracks": tracks, "pred_visibility": vis})
+    a = np.load(tmp_path / "all" / "pred_tracks.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, tracks.numpy()) and w["pred_tracks"] == {"shape": [1, 30, 100, 2], "dtype": "float32", "sampled": False}
+    assert np.array_equal(np.load(tmp_path / "all" / "pred_visibility.npy"), vis.float().numpy())
+    # above the limit: a sample of both arrays, the same one on every call, and the files together stay under the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 20000)
+    for d in ("s1", "s2"):
+        w = bench.dump_outputs(str(tmp_path / d), {"pred_tracks": tracks, "pred_visibility": vis})
+        assert w["pred_tracks"]["sampled"] and sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 20000
+    s1, s2 = np.load(tmp_path / "s1" / "pred_tracks.npy"), np.load(tmp_path / "s2" / "pred_tracks.npy")
+    assert s1.ndim == 1 and 2000 < s1.size < 6000 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+
+
+@pytest.mark.gpu
+def test_steps_and_dump_outputs_of_a_real_run(tmp_path):
+    """Two runs of the same command (each a fresh process): --steps is the number of timed steps, and the dumped outputs of the
+    last timed step are the same arrays, of the shapes a caller of the predictor receives."""
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    H, W, T, G, *_ = bench.WORKLOADS["tiny"]
+    line = lines[0]
+    assert line["steps"] == 3 and line["steps_bit_identical"]["steps_compared"] == 3 and line["steps_bit_identical"]["identical"]
+    assert sorted(line["dumped_outputs"]) == ["confidence_logits", "pred_tracks", "pred_visibility", "visibility_logits"]
+    for name in line["dumped_outputs"]:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), name
+    tracks = np.load(tmp_path / "a" / "pred_tracks.npy")
+    assert tracks.shape == (1, T, G * G, 2) and np.load(tmp_path / "a" / "pred_visibility.npy").shape == (1, T, G * G)
+    assert 0 <= tracks[..., 0].mean() < W and 0 <= tracks[..., 1].mean() < H

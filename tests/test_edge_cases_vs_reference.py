@@ -1,17 +1,12 @@
-"""The edge-case inputs of tests/test_gpu_parity.py::test_model_edge_cases_vs_torch_port, checked HERE (CPU, build container: needs
-/root/reference) between the checker that test uses -- oracle/torch_port.py -- and the imported, unmodified reference: a single
-point, a video shorter than one window, odd pyramid sizes, queries on / outside the border, queries entering in later windows with
-a ragged last window, the offline model on an odd frame count.  So the GPU test's oracle is pinned on the reference for exactly
-the inputs it is used on."""
+"""The edge-case inputs of tests/test_gpu_parity.py::test_model_edge_cases_vs_torch_port, checked HERE (CPU) between the checker
+that test uses -- oracle/torch_port.py -- and the unmodified reference, whose outputs on these inputs are stored in
+tests/golden/edge_cases.npz (tests/golden/make_golden_reference.py): a single point, a video shorter than one window, odd pyramid
+sizes, queries on / outside the border, queries entering in later windows with a ragged last window, the offline model on an odd
+frame count.  So the GPU test's oracle is pinned on the reference for exactly the inputs it is used on."""
 import copy
-import os
-import sys
 
 import pytest
 import torch
-
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "cotracker")), reason="reference checkout not present")
 
 CASES = {  # name: (H, W, T, offline, queries)
     "one_point": (64, 96, 20, False, [[0.0, 41.3, 22.7]]),
@@ -24,26 +19,21 @@ CASES = {  # name: (H, W, T, offline, queries)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
-def test_torch_port_equals_reference_on_edge_cases(case):
-    sys.path.insert(0, REF)
-    try:
-        from cotracker.models.core.cotracker.cotracker3_online import CoTrackerThreeOnline as RefOn
-        from cotracker.models.core.cotracker.cotracker3_offline import CoTrackerThreeOffline as RefOff
-    finally:
-        sys.path.remove(REF)
+def test_torch_port_equals_reference_on_edge_cases(case, golden):
+    from cotracker_amd.model import CoTrackerThreeOffline, CoTrackerThreeOnline
     from cotracker_amd.synthetic import synthetic_video
     from cotracker_amd.weights import fill_synthetic_
     from oracle import torch_port as TP
     H, W, T, offline, q = CASES[case]
     q = torch.tensor([q])
-    torch.manual_seed(0)
-    ref = (RefOff if offline else RefOn)(stride=4, corr_radius=3, window_len=8, model_resolution=(H, W)).eval()
-    fill_synthetic_(ref, seed=7)
+    g = golden("edge_cases")
+    rc, rv, rf = (torch.from_numpy(g[f"{case}_{k}"]) for k in ("coords", "vis", "conf"))
+    # the same key set as the reference's model (tests/test_boundary_vs_reference.py), so the same name-keyed weights
+    m = (CoTrackerThreeOffline if offline else CoTrackerThreeOnline)(stride=4, corr_radius=3, window_len=8, model_resolution=(H, W)).eval()
+    fill_synthetic_(m, seed=7)
     video = synthetic_video(T, H, W, seed=11)
-    with torch.no_grad():
-        rc, rv, rf, _ = ref(video, q, iters=4)
-    p = {k: v.clone() for k, v in ref.state_dict().items() if not k.startswith("fnet.")}
-    pc, pv, pf = TP.model_forward(copy.deepcopy(ref.fnet), p, video, q, iters=4, window_len=8, offline=offline)
+    p = {k: v.clone() for k, v in m.state_dict().items() if not k.startswith("fnet.")}
+    pc, pv, pf = TP.model_forward(copy.deepcopy(m.fnet), p, video, q, iters=4, window_len=8, offline=offline)
     assert torch.isfinite(rc).all()
     # same ATen kernels in the same order; what differs is blocking (the port encodes and correlates in other chunk sizes), i.e.
     # reduction order: measured 6e-5 ... 8e-5 px here, the size of the reference's own thread-count spread -- an order of

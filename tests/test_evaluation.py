@@ -1,15 +1,25 @@
-"""TAP-Vid metrics (cotracker_amd.evaluation.compute_tapvid_metrics) -- CPU.  Known-answer cases worked by hand, and,
-where the reference checkout is present (build container), agreement with the reference's own function
-(cotracker/evaluation/core/eval_utils.py:12-138) on random inputs incl. both query modes and multi-video batches."""
-import importlib.util
-import os
-
+"""TAP-Vid metrics (cotracker_amd.evaluation.compute_tapvid_metrics) -- CPU.  Known-answer cases worked by hand, and agreement
+with the reference's own function (cotracker/evaluation/core/eval_utils.py:12-138) on random inputs incl. both query modes and
+multi-video batches: its results are stored in tests/golden/tapvid_metrics.npz (tests/golden/make_golden_reference.py)."""
 import numpy as np
 import pytest
 
 from cotracker_amd.evaluation import compute_tapvid_metrics
 
-REF = "/root/reference/cotracker/evaluation/core/eval_utils.py"
+MODES = ["first", "strided"]
+GRIDS = [(8, (50, 50), [123.4, 301.7]), (5, (384, 512), None), (80, (384, 512), None), (1, (10, 20), None)]
+
+
+def metric_inputs():
+    """(query_points, gt_occluded, gt_tracks, pred_occluded, pred_tracks) of one video, then of a batch of three."""
+    r = np.random.RandomState(0)
+    for b, n, t in [(1, 7, 12), (3, 20, 9)]:
+        q = np.stack([r.randint(0, t, size=(b, n)).astype(np.float64), r.uniform(0, 255, (b, n)), r.uniform(0, 255, (b, n))], -1)
+        gt = r.uniform(0, 255, (b, n, t, 2))
+        pred = gt + r.standard_normal((b, n, t, 2)) * r.choice([0.3, 1.5, 5.0, 12.0, 30.0], size=(b, n, t, 1))
+        gt_occ = r.uniform(size=(b, n, t)) < 0.3
+        pred_occ = gt_occ ^ (r.uniform(size=(b, n, t)) < 0.2)
+        yield q, gt_occ, gt, pred_occ, pred
 
 
 def test_known_answers_first_mode():
@@ -50,37 +60,20 @@ def test_strided_mode_counts_every_frame_but_the_query():
         compute_tapvid_metrics(q, occ, gt, occ, pred, "last")
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present")
-@pytest.mark.parametrize("mode", ["first", "strided"])
-def test_agrees_with_the_reference_function(mode):
-    spec = importlib.util.spec_from_file_location("ref_eval_utils", REF)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    r = np.random.RandomState(0)
-    for b, n, t in [(1, 7, 12), (3, 20, 9)]:
-        q = np.stack([r.randint(0, t, size=(b, n)).astype(np.float64), r.uniform(0, 255, (b, n)), r.uniform(0, 255, (b, n))], -1)
-        gt = r.uniform(0, 255, (b, n, t, 2))
-        pred = gt + r.standard_normal((b, n, t, 2)) * r.choice([0.3, 1.5, 5.0, 12.0, 30.0], size=(b, n, t, 1))
-        gt_occ = r.uniform(size=(b, n, t)) < 0.3
-        pred_occ = gt_occ ^ (r.uniform(size=(b, n, t)) < 0.2)
-        a = compute_tapvid_metrics(q, gt_occ, gt, pred_occ, pred, mode)
-        e = ref.compute_tapvid_metrics(q, gt_occ, gt, pred_occ, pred, mode)
-        assert set(a) == set(e)
+@pytest.mark.parametrize("mode", MODES)
+def test_agrees_with_the_reference_function(mode, golden):
+    g = golden("tapvid_metrics")
+    for i, args in enumerate(metric_inputs()):
+        a = compute_tapvid_metrics(*args, mode)
+        e = {k.split("/")[2]: v for k, v in g.items() if k.startswith(f"{mode}/{i}/")}
+        assert e and set(a) == set(e)
         for k in e:
             np.testing.assert_allclose(a[k], e[k], rtol=0, atol=1e-12, err_msg=k)
 
 
-def test_grid_helper_matches_reference_with_center():
-    mu = "/root/reference/cotracker/models/core/model_utils.py"
-    if not os.path.exists(mu):
-        pytest.skip("reference checkout not present")
-    import sys
-    sys.path.insert(0, "/root/reference")
-    try:
-        from cotracker.models.core.model_utils import get_points_on_a_grid as ref_grid
-    finally:
-        sys.path.remove("/root/reference")
+def test_grid_helper_matches_reference_with_center(golden):
     import torch
     from cotracker_amd.predictor import get_points_on_a_grid
-    for size, extent, center in [(8, (50, 50), [123.4, 301.7]), (5, (384, 512), None), (80, (384, 512), None), (1, (10, 20), None)]:
-        assert torch.equal(get_points_on_a_grid(size, extent, center), ref_grid(size, extent, center))
+    g = golden("tapvid_metrics")
+    for i, (size, extent, center) in enumerate(GRIDS):
+        assert torch.equal(get_points_on_a_grid(size, extent, center), torch.from_numpy(g[f"grid/{i}"]))

@@ -986,7 +986,7 @@ def test_model_edge_cases_vs_torch_port(case):
     9x13, 4x6, 2x3: avg_pool floors, 7x7 taps wider than the coarsest map); queries on and outside the image border
     (border-clamped sampling everywhere); queries entering in later windows with a ragged last window; the offline model on an
     odd frame count.  The port is pinned on the imported reference FOR EXACTLY THESE INPUTS by
-    tests/test_edge_cases_vs_reference.py (CPU, build container: <= 8.4e-5 px / 8e-6 sigmoid).  Bar: 1e-3 px / 1e-4 logit."""
+    tests/test_edge_cases_vs_reference.py (CPU: <= 8.4e-5 px / 8e-6 sigmoid).  Bar: 1e-3 px / 1e-4 logit."""
     import copy
     from cotracker_amd.model import CoTrackerThreeOnline, CoTrackerThreeOffline
     from cotracker_amd.synthetic import synthetic_video

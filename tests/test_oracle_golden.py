@@ -263,28 +263,22 @@ def test_torch_port_matches_reference_goldens(golden):
     assert float((v.double() - lg(g["off_vis"])).abs().max()) < 1e-4
 
 
-def test_update_former_add_space_attn_false_matches_reference():
-    """EfficientUpdateFormer.forward(add_space_attn=False) (cotracker.py:496-502): the oracle against the imported reference
-    (build container only: /root/reference does not travel)."""
-    import os
-    import sys
-    if not os.path.isdir("/root/reference/cotracker"):
-        pytest.skip("reference checkout not present")
-    import torch
-    sys.path.insert(0, "/root/reference")
-    from cotracker.models.core.cotracker.cotracker import EfficientUpdateFormer
+# weights of the EfficientUpdateFormer in tests/golden/update_former.npz: cotracker_amd.weights.synthetic_tensor per state_dict
+# entry, heads scaled up so that the output moves by far more than the tolerance when the space attention is switched off
+UPDATE_FORMER_WEIGHTS = dict(seed=5, head_scale=50.0)
+
+
+def test_update_former_add_space_attn_false_matches_reference(golden):
+    """EfficientUpdateFormer.forward(add_space_attn=False) (cotracker.py:496-502): the oracle against what the imported reference
+    returned for the same input and weights (tests/golden/update_former.npz, tests/golden/make_golden_reference.py)."""
+    from cotracker_amd.model import CoTrackerThreeOnline
+    from cotracker_amd.weights import synthetic_tensor
     from oracle import cotracker_oracle as O
-    torch.manual_seed(0)
-    f = EfficientUpdateFormer(space_depth=3, time_depth=3, input_dim=1110, hidden_size=384, output_dim=4, mlp_ratio=4.0,
-                              num_virtual_tracks=64, add_space_attn=True, linear_layer_for_vis_conf=True).eval()
-    for _, p_ in f.named_parameters():
-        if p_.dim() > 1:
-            torch.nn.init.normal_(p_, std=0.05)
-    x = torch.randn(1, 5, 8, 1110)
-    with torch.no_grad():
-        y = f(x, add_space_attn=False).numpy()
-        y_full = f(x).numpy()
-    p = {"updateformer." + k: v.numpy() for k, v in f.state_dict().items()}
-    assert np.abs(O.update_former(x.numpy(), p, add_space_attn=False) - y).max() < 5e-5
-    assert np.abs(O.update_former(x.numpy(), p) - y_full).max() < 5e-5
+    g = golden("update_former")
+    x, y, y_full = g["x"], g["y"], g["y_full"]
+    # the reference's key set and shapes (tests/test_boundary_vs_reference.py) for input_dim=1110, hidden 384, 3 + 3 blocks, 64 virtual tracks
+    shapes = CoTrackerThreeOnline(stride=4, corr_radius=3, window_len=16, model_resolution=(64, 96)).updateformer.state_dict()
+    p = {"updateformer." + k: synthetic_tensor("updateformer." + k, v.shape, **UPDATE_FORMER_WEIGHTS).numpy() for k, v in shapes.items()}
+    assert np.abs(O.update_former(x, p, add_space_attn=False) - y).max() < 5e-5
+    assert np.abs(O.update_former(x, p) - y_full).max() < 5e-5
     assert np.abs(y - y_full).max() > 1e-2

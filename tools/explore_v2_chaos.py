@@ -1,9 +1,9 @@
 """The reference CoTracker2 at BASELINE scale (512x512, window 8, 6 iterations) with damped synthetic weights: its own 8-vs-3-thread
-spread per (head_scale, updater_scale, residual_scale) setting.  Build container only (imports /root/reference).
+spread per (head_scale, updater_scale, residual_scale) setting.  Imports the reference: COTRACKER_REFERENCE=<checkout of facebookresearch/co-tracker>.
     python tools/explore_v2_chaos.py 24 20 0.25,0.1,1.0 0.05,0.1,1.0 0.02,0.1,1.0
 """
 import sys, time, os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.environ["COTRACKER_REFERENCE"])
 import numpy as np, torch
 from cotracker.predictor import CoTrackerPredictor
 from cotracker_amd.weights import fill_synthetic_

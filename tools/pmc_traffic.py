@@ -3,7 +3,7 @@
 
     pmc_traffic.py <fetch_counter_collection.csv> <write_counter_collection.csv> <out.json> [workload]
 
-Units and corrections follow /opt/skills/guides/MI355X_MICROARCH.md, section HBM: FETCH_SIZE / WRITE_SIZE are in
+Units and corrections follow MI355X_MICROARCH.md, section HBM: FETCH_SIZE / WRITE_SIZE are in
 KiB; on gfx950 FETCH_SIZE reports one half of the bytes of wide (16 B/lane) coalesced reads -> doubled here;
 WRITE_SIZE is uncalibrated and taken as reported.  Kernel names are mapped to the names of the library's HIP-event
 recorder (bench.py "kernels"), so bench.py can attach `traffic` to its roofline objects.  Means are over ALL

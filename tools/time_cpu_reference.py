@@ -5,7 +5,7 @@ same workload, same weights, same thread count -- wall time and agreement of the
     MALLOC_MMAP_MAX_=0 MALLOC_TRIM_THRESHOLD_=68719476736 MALLOC_TOP_PAD_=1073741824 \
         python tools/time_cpu_reference.py [--frames 24] [--grid 20] [--threads 8] > profiles/r02_cpu_reference_vs_port.txt
 
-(needs /root/reference; the malloc variables are what bench.py sets for its own CPU leg, see oracle/torch_port.py)"""
+(needs COTRACKER_REFERENCE=<checkout of facebookresearch/co-tracker>; the malloc variables are what bench.py sets for its own CPU leg, see oracle/torch_port.py)"""
 import argparse
 import os
 import sys
@@ -15,7 +15,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["COTRACKER_REFERENCE"])
 
 from cotracker.predictor import CoTrackerPredictor  # noqa: E402  (the reference)
 
