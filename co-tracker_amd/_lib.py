@@ -21,10 +21,12 @@ MLP = 1536
 VIRT = 64
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH = 0, 1, 2
 ABI_VERSION = 9
+MAX_BATCH = 16  # CTK_MAX_BATCH: videos of one joint window (ctk_forward_window_batch)
 PAD_ZEROS, PAD_BORDER = 0, 1  # ctk_bilinear_sampler padding_mode
 # ctk_set_option keys (include/ctk.h)
 (OPT_GEMM_PP, OPT_GEMM_TAIL_PCT, OPT_CORR_VERSION, OPT_CORR_MAP, OPT_ATTENTION_VALU, OPT_ATTENTION_TIME_PERSISTENT,
  OPT_OVERLAP) = range(7)
+OPT_COUNT = 7
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -87,6 +89,17 @@ class AttnArgs(C.Structure):
     ]
 
 
+class AttnBatch2(C.Structure):
+    """ctk_attn_batch2: the two-level batch of ctk_attention_ex (outer strides in rows / mask bytes)."""
+    _fields_ = [("inner", C.c_int32), ("reserved", C.c_int32), ("q_os", C.c_int64), ("kv_os", C.c_int64), ("o_os", C.c_int64),
+                ("key_mask_os", C.c_int64), ("query_mask_os", C.c_int64)]
+
+
+class WindowBatch(C.Structure):
+    """ctk_window_batch: B windows of equal shape for one joint call."""
+    _fields_ = [("B", C.c_int32), ("reserved", C.c_int32), ("videos", C.POINTER(WindowArgs))]
+
+
 class FormerWeights(C.Structure):
     """ctk_former_weights: the general update former (CoTracker2)."""
     _fields_ = [
@@ -132,6 +145,9 @@ SYMBOLS = {
     "ctk_forward_window_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_forward_window": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, C.c_size_t, _fp]),
     "ctk_window_graph_create": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, C.c_size_t, _P(C.c_void_p)]),
+    "ctk_forward_window_batch_workspace_bytes": (C.c_int, [_P(WindowBatch), _P(C.c_size_t)]),
+    "ctk_forward_window_batch": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, C.c_size_t, _fp]),
+    "ctk_window_batch_graph_create": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, C.c_size_t, _P(C.c_void_p)]),
     "ctk_window_graph_launch": (C.c_int, [C.c_void_p, _fp]),
     "ctk_window_graph_nodes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "ctk_window_graph_destroy": (C.c_int, [C.c_void_p]),
@@ -173,6 +189,7 @@ SYMBOLS = {
     "ctk_layernorm": (C.c_int, [_fp, _fp, C.c_int64, _fp, _fp, C.c_float, C.c_int32, _fp]),
     "ctk_split_rows": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, _fp]),
     "ctk_attention": (C.c_int, [_P(AttnArgs), _fp]),
+    "ctk_attention_ex": (C.c_int, [_P(AttnArgs), _P(AttnBatch2), _fp]),
     "ctk_profile_enable": (C.c_int, [C.c_int]),
     "ctk_gemm_pp_mode": (None, [C.c_int]),
     "ctk_set_option": (C.c_int, [C.c_int, C.c_int]),
@@ -227,6 +244,19 @@ class option:
     def __exit__(self, *exc):
         load().ctk_set_option(self.key, self.old)
         return False
+
+
+def option_values() -> tuple:
+    """The whole option table (ctk_get_option of every key).  A captured window graph bakes in the values read while it
+    was captured (include/ctk.h), so the host models make this tuple part of their graph cache key: changing an option
+    re-captures instead of replaying a graph that still runs the old choice."""
+    lib = load()
+    v = C.c_int(0)
+    out = []
+    for k in range(OPT_COUNT):
+        check(lib.ctk_get_option(k, C.byref(v)), "ctk_get_option")
+        out.append(v.value)
+    return tuple(out)
 
 
 def check(rc: int, what: str):

@@ -13,11 +13,15 @@ int ctk_launch_corr_volume(const ctk_window_args* a, int n0, int ncount, float* 
 int ctk_launch_pyramid_split(const float* fmap, long pixels, void* out, int version, hipStream_t s);
 int ctk_launch_corr_volume_sh(const ctk_window_args* a, const void* const* fm_sh, int n0, int ncount, void* out,
                               long level_stride_halves, int version, hipStream_t s);
-int ctk_launch_virtual_init(const float* vt, int S, float* dst, hipStream_t s);
+int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream_t s);
 int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, const float* beta, float eps, void* y2, float eps2,
                           int out_split, hipStream_t s);
 int ctk_launch_heads(const float* tokens, const float* hw, const float* hb, int S, int N, float* delta, float* coords,
                      float* vis, float* conf, hipStream_t s);
+int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, float scale_x, float scale_y, void* x, int x_split,
+                              hipStream_t s);
+int ctk_launch_heads_batch(const float* tokens, const float* hw, const float* hb, const CtkBatchState& st, int B, int S, int N,
+                           hipStream_t s);
 
 namespace {
 
@@ -138,6 +142,7 @@ int gemm(const float* A, long lda, int M, WRef W, long ldw, int N, int K, float*
 bool split_mode(const ctk_model_weights* w) { return w->in_p != nullptr; }
 
 // ---- update-former workspace carve -------------------------------------------------------
+// B videos (joint window): R = B*(N+64)*S rows, the B*N*S point rows first, then the B*64*S virtual rows
 struct UfWs {
   float* tokens;  // [R,384]
   float* xn;      // [R,384]
@@ -156,8 +161,8 @@ int v2p_splits(int N) {
   return s;
 }
 
-UfWs carve_uf(int S, int N, void* base) {
-  const size_t R = (size_t)(N + CTK_VIRT) * S;
+UfWs carve_uf(int S, int N, void* base, int B = 1) {
+  const size_t R = (size_t)B * (N + CTK_VIRT) * S;
   UfWs w;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -168,25 +173,26 @@ UfWs carve_uf(int S, int N, void* base) {
   };
   w.tokens = take(R * CTK_HID);
   w.xn = take(R * CTK_HID);
-  w.xn2 = take((size_t)N * S * CTK_HID);
+  w.xn2 = take((size_t)B * N * S * CTK_HID);
   w.qkv = take(R * 3 * CTK_HID);
   w.att = take(R * CTK_HID);
   w.hid = take(R * CTK_MLP);
-  w.partial = take((size_t)v2p_splits(N) * S * CTK_HEADS * CTK_VIRT * (CTK_HEAD_DIM + 2));
+  w.partial = take((size_t)v2p_splits(N) * B * S * CTK_HEADS * CTK_VIRT * (CTK_HEAD_DIM + 2));
   w.bytes = off;
   return w;
 }
 
 int attn(const float* q, long q_ld, long q_bs, long q_is, const float* k, const float* v, long kv_ld, long kv_bs,
          long kv_is, float* out, long o_bs, long o_is, int nbatch, int n1, int n2, int splits, float* partial,
-         hipStream_t s, bool o_split, const uint8_t* key_mask = nullptr, const uint8_t* query_mask = nullptr) {
+         hipStream_t s, bool o_split, const uint8_t* key_mask = nullptr, const uint8_t* query_mask = nullptr,
+         const ctk_attn_batch2* b2 = nullptr) {
   ctk_attn_args a;
   a.key_mask = key_mask; a.query_mask = query_mask;
   a.q = q; a.q_ld = q_ld; a.q_bs = q_bs; a.q_is = q_is;
   a.k = k; a.v = v; a.kv_ld = kv_ld; a.kv_bs = kv_bs; a.kv_is = kv_is;
   a.out = out; a.o_ld = o_split ? 2 * CTK_HID : CTK_HID; a.o_bs = o_bs; a.o_is = o_is; a.o_split = o_split;
   a.nbatch = nbatch; a.n1 = n1; a.n2 = n2; a.splits = splits; a.partial = partial;
-  return ctk_attention(&a, s);
+  return ctk_attention_ex(&a, b2, s);
 }
 
 // residual MLP: x += fc2(gelu_tanh(fc1(LN(x))))  on rows [r0, r0+R)   (blocks.py:437 / cotracker.py:576)
@@ -223,6 +229,7 @@ struct FormerRef {
   bool split;                 // xn / att / hid are SH-format (split-half back end)
   hipStream_t aux;            // optional second stream (ctk_window_args.aux_stream) or null
   bool space_attn = true;     // false: add_space_attn=False (cotracker.py:496-502): the three space blocks are skipped
+  int B = 1;                  // videos of a joint window (CoTracker3 only: point_mask must be null when B > 1)
 };
 
 FormerRef former_of(const ctk_model_weights* w) {
@@ -231,19 +238,28 @@ FormerRef former_of(const ctk_model_weights* w) {
 }
 
 // EfficientUpdateFormer.forward (cotracker.py:483-531) on tokens already holding the input
-// projection in rows [0, N*S).
+// projection in rows [0, B*N*S).  B = fr.B videos share every row-wise launch: point row (b*N + j)*S + t, virtual row
+// P + (b*64 + i)*S + t.  The tracks of all videos are ONE linear batch of the time attention; the space attentions batch over
+// (video, frame) with the two outer strides N*S (point rows) and 64*S (virtual rows) -- a single level when B == 1.
 int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream_t s) {
   const FormerRef* w = &fr;
   const bool sp = fr.split;
-  const long P = (long)N * S;             // point rows
-  const long V = (long)CTK_VIRT * S;      // virtual rows
+  const int B = fr.B;
+  const long P = (long)B * N * S;             // point rows
+  const long V = (long)B * CTK_VIRT * S;      // virtual rows
+  const long PS = (long)N * S, VS = (long)CTK_VIRT * S;  // rows of one video
+  const bool joint = B > 1;
+  if (joint && fr.point_mask) return CTK_E_STATE;
+  const ctk_attn_batch2 v2p_b{S, 0, VS, PS, VS, 0, 0};   // queries / out: virtual rows, keys: point rows
+  const ctk_attn_batch2 vself_b{S, 0, VS, VS, VS, 0, 0};
+  const ctk_attn_batch2 p2v_b{S, 0, PS, VS, PS, 0, 0};   // queries / out: point rows, keys: virtual rows
   const long R = P + V;
   const long QL = 3 * CTK_HID;            // qkv leading dimension
   float* tok = ws.tokens;
   float* xn = ws.xn;
   float* qkv = ws.qkv;
   float* att = ws.att;
-  CTK_TRY(ctk_launch_virtual_init(w->virtual_tokens, S, tok + P * CTK_HID, s));  // cotracker.py:487-488
+  CTK_TRY(ctk_launch_virtual_init(w->virtual_tokens, S, tok + P * CTK_HID, B, s));  // cotracker.py:487-488
 
   for (int i = 0; i < fr.depth; ++i) {
     // ---- time attention over S for every track (incl. virtual)      cotracker.py:494-497
@@ -252,7 +268,7 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
       CTK_TRY(ctk_layernorm(tok, xn, R, nullptr, nullptr, 1e-6f, sp, s));
       CTK_TRY(gemm(xn, CTK_HID, (int)R, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(gemm(xn, CTK_HID, (int)R, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv, QL, S, 1, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, S, 1, att, S, 1, N + CTK_VIRT, S, S, 1, nullptr, s, sp));
+      CTK_TRY(attn(qkv, QL, S, 1, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, S, 1, att, S, 1, B * (N + CTK_VIRT), S, S, 1, nullptr, s, sp));
       CTK_TRY(gemm(att, CTK_HID, (int)R, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok, CTK_HID, b.bo, CTK_ACT_NONE, tok, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(mlp_block(ws, 0, R, b, s, sp));
     }
@@ -284,8 +300,8 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
       CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv + P * QL, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(gemm(xn, CTK_HID, (int)P, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       // batch = frame t; query i = virtual track (row P + i*S + t); key j = point (row j*S + t)
-      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, S, CTK_VIRT, N,
-                   v2p_splits(N), ws.partial, s, sp, fr.point_mask, nullptr));  // mask over KEYS (cotracker.py:566-569)
+      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, B * S, CTK_VIRT, N,
+                   v2p_splits(N), ws.partial, s, sp, fr.point_mask, nullptr, joint ? &v2p_b : nullptr));  // mask over KEYS (cotracker.py:566-569)
       CTK_TRY(gemm(att + P * CTK_HID, CTK_HID, (int)V, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok + P * CTK_HID, CTK_HID, b.bo, CTK_ACT_NONE,
                    tok + P * CTK_HID, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(mlp_block(ws, P, V, b, s, sp));
@@ -296,8 +312,8 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
       CTK_TRY(ctk_layernorm(tok + P * CTK_HID, xn + P * CTK_HID, V, nullptr, nullptr, 1e-6f, sp, s));
       CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv + P * QL, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + P * QL + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, S,
-                   CTK_VIRT, CTK_VIRT, 1, nullptr, s, sp));
+      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, B * S,
+                   CTK_VIRT, CTK_VIRT, 1, nullptr, s, sp, nullptr, nullptr, joint ? &vself_b : nullptr));
       CTK_TRY(gemm(att + P * CTK_HID, CTK_HID, (int)V, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok + P * CTK_HID, CTK_HID, b.bo, CTK_ACT_NONE,
                    tok + P * CTK_HID, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(mlp_block(ws, P, V, b, s, sp));
@@ -309,8 +325,8 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
       if (!side_q) CTK_TRY(gemm(ws.xn2, CTK_HID, (int)P, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));  // xn2 = norm1(points), written beside norm_context(points) above
       else CTK_TRY(side.join());  // join: q(points) is ready
       CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + P * QL + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att, 1, S, S, N, CTK_VIRT, 1, nullptr, s, sp,
-                   nullptr, fr.point_mask));  // mask over QUERIES (cotracker.py:561-564)
+      CTK_TRY(attn(qkv, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att, 1, S, B * S, N, CTK_VIRT, 1, nullptr, s, sp,
+                   nullptr, fr.point_mask, joint ? &p2v_b : nullptr));  // mask over QUERIES (cotracker.py:561-564)
       CTK_TRY(gemm(att, CTK_HID, (int)P, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok, CTK_HID, b.bo, CTK_ACT_NONE, tok, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
       CTK_TRY(mlp_block(ws, 0, P, b, s, sp));
     }
@@ -335,6 +351,7 @@ int check_weights(const ctk_model_weights* w) {
   return CTK_OK;
 }
 
+// N = point tracks of ALL videos of the call (the per-frame bias is indexed by row % S: rows are track-major in every video)
 int input_projection(int S, int N, const float* x, bool x_split, const ctk_model_weights* w, const UfWs& ws, hipStream_t s) {
   // tokens = input_transform(x + time_emb)   (cotracker3_online.py:247, cotracker.py:484)
   return gemm(x, CTK_X_LD, N * S, WRef{w->in_w, w->in_p}, CTK_X_LD, CTK_HID, CTK_X_LD, ws.tokens, CTK_HID, nullptr, CTK_ACT_NONE, nullptr, 0,
@@ -345,22 +362,25 @@ int input_projection(int S, int N, const float* x, bool x_split, const ctk_model
 struct CorrWs {
   float* vol;  // [4][chunk*S][2432]   (SH format in split mode: same bytes)
   float* h1;   // [4*chunk*S][384]     (SH format in split mode)
-  void* fm_sh[CTK_LEVELS];  // split mode: SH copy of the window's pyramid (scaled by 2^8), [S*H*W][4][2][32] halves
+  void* fm_sh[CTK_MAX_BATCH][CTK_LEVELS];  // split mode: SH copy of every video's pyramid (scaled by 2^8), [S*H*W][4][2][32] halves
   size_t bytes;
   int chunk;
   int corr_version;  // CTK_OPT_CORR_VERSION as read ONCE per entry-point call: the layout of fm_sh and the sampler kernel must agree
 };
 
-int corr_chunk_points(const ctk_window_args* a) {
-  int c = a->points_per_chunk > 0 ? a->points_per_chunk : a->N;
-  if (c > a->N) c = a->N;
-  return c;
+// points of the STACKED list (B*N) that go through the correlation stage at a time
+int corr_chunk_points(const ctk_window_args* a, int B = 1) {
+  const long all = (long)B * a->N;
+  long c = a->points_per_chunk > 0 ? a->points_per_chunk : all;
+  if (c > all) c = all;
+  return (int)c;
 }
 
-CorrWs carve_corr(const ctk_window_args* a, void* base) {
+// a = videos[0] of a joint window (the videos agree in every size)
+CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1) {
   CorrWs w;
   w.corr_version = ctk_opt(CTK_OPT_CORR_VERSION);
-  w.chunk = corr_chunk_points(a);
+  w.chunk = corr_chunk_points(a, B);
   const size_t rows = (size_t)w.chunk * a->S;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -368,35 +388,45 @@ CorrWs carve_corr(const ctk_window_args* a, void* base) {
   off += align256(rows * CTK_LEVELS * CTK_CORR_LD * sizeof(float));
   w.h1 = reinterpret_cast<float*>(p + off);
   off += align256(rows * CTK_LEVELS * CTK_HID * sizeof(float));
-  for (int l = 0; l < CTK_LEVELS; ++l) {  // always carved (the size query does not know the weights' mode): ~8 MB per frame
-    w.fm_sh[l] = p + off;
-    off += align256((size_t)a->S * (a->H[l] > 0 ? a->H[l] : 0) * (a->W[l] > 0 ? a->W[l] : 0) * CTK_C * sizeof(float));
-  }
+  for (int b = 0; b < B; ++b)
+    for (int l = 0; l < CTK_LEVELS; ++l) {  // always carved (the size query does not know the weights' mode): ~8 MB per frame
+      w.fm_sh[b][l] = p + off;
+      off += align256((size_t)a->S * (a->H[l] > 0 ? a->H[l] : 0) * (a->W[l] > 0 ? a->W[l] : 0) * CTK_C * sizeof(float));
+    }
   w.bytes = off;
   return w;
 }
 
 // split mode, once per window: SH copy of the pyramid for the correlation sampler's footprint DMA
-int prepare_pyramid_sh(const ctk_window_args* a, const CorrWs& ws, hipStream_t s) {
-  for (int l = 0; l < CTK_LEVELS; ++l) {
-    if (!a->fmaps[l]) return CTK_E_NULL;
-    if (a->H[l] <= 0 || a->W[l] <= 0) return CTK_E_SHAPE;
-    CTK_TRY(ctk_launch_pyramid_split(a->fmaps[l], (long)a->S * a->H[l] * a->W[l], ws.fm_sh[l], ws.corr_version, s));
+int prepare_pyramid_sh(const ctk_window_args* videos, const CorrWs& ws, hipStream_t s, int B = 1) {
+  for (int b = 0; b < B; ++b) {
+    const ctk_window_args* a = videos + b;
+    for (int l = 0; l < CTK_LEVELS; ++l) {
+      if (!a->fmaps[l]) return CTK_E_NULL;
+      if (a->H[l] <= 0 || a->W[l] <= 0) return CTK_E_SHAPE;
+      CTK_TRY(ctk_launch_pyramid_split(a->fmaps[l], (long)a->S * a->H[l] * a->W[l], ws.fm_sh[b][l], ws.corr_version, s));
+    }
   }
   return CTK_OK;
 }
 
-// x is f32 [N*S, CTK_X_LD] or, when x_split, the same matrix in SH format.  In split mode the hidden h1 is SH
+// x is f32 [B*N*S, CTK_X_LD] or, when x_split, the same matrix in SH format.  In split mode the hidden h1 is SH
 // (fc1's epilogue writes it, fc2 streams it) and so is the correlation volume (corr_sh.hip); the caller has run
 // prepare_pyramid_sh for this window.
-int run_corr_embed(const ctk_window_args* a, const ctk_model_weights* w, float* x, bool x_split, const CorrWs& ws, hipStream_t s) {
+// B videos (`videos[0..B)`, equal sizes): the chunk loop walks the STACKED point list g = b*N + n, so corr_mlp is one fc1 and one
+// fc2 launch per chunk over the rows of every video in it; the sampler is launched once per video that owns points of the chunk,
+// into that video's rows of the volume (its grid is already 4 workgroups per point: the single-video kernel, unchanged).
+int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights* w, float* x, bool x_split, const CorrWs& ws,
+                   hipStream_t s) {
+  const ctk_window_args* a = videos;
   const bool sp = split_mode(w);
   if (x_split && !sp) return CTK_E_SHAPE;
   if ((!w->corr_fc1_w && !w->corr_fc1_p) || !w->corr_fc1_b || (!w->corr_fc2_w && !w->corr_fc2_p) || !w->corr_fc2_b) return CTK_E_NULL;
-  hipStream_t aux = static_cast<hipStream_t>(a->aux_stream);
+  hipStream_t aux = B == 1 ? static_cast<hipStream_t>(a->aux_stream) : nullptr;  // a joint window ignores aux_stream
   const bool pipelined = sp && aux != nullptr && (overlap_mode() & 1) != 0;
-  for (int n0 = 0; n0 < a->N; n0 += ws.chunk) {
-    const int cnt = (a->N - n0 < ws.chunk) ? a->N - n0 : ws.chunk;
+  const int NT = B * a->N;
+  for (int n0 = 0; n0 < NT; n0 += ws.chunk) {
+    const int cnt = (NT - n0 < ws.chunk) ? NT - n0 : ws.chunk;
     // Software pipeline over point pieces: the sampler (VALU / LDS bound, MFMA pipe ~11 % busy) of piece j+1 runs on the
     // caller's stream while corr_mlp of piece j (MFMA bound) runs on the auxiliary stream; one workgroup of each kind
     // fits on a CU (77 KiB + 64 KiB of LDS).  Each piece has its own slice of the volume / hidden buffers.
@@ -411,8 +441,16 @@ int run_corr_embed(const ctk_window_args* a, const ctk_model_weights* w, float* 
       float* vol = ws.vol + (size_t)p0 * a->S * CTK_LEVELS * CTK_CORR_LD;
       float* h1 = ws.h1 + (size_t)p0 * a->S * CTK_LEVELS * CTK_HID;
       hipStream_t gs = s;
-      if (sp) CTK_TRY(ctk_launch_corr_volume_sh(a, ws.fm_sh, n0 + p0, pc, vol, rows * CTK_CORR_LD * 2, ws.corr_version, s));
-      else CTK_TRY(ctk_launch_corr_volume(a, n0 + p0, pc, vol, rows * CTK_CORR_LD, CTK_CORR_LD, s));
+      // stacked points [g0, g0 + pc) -> per video b: its points [m0, m0 + mc), rows (g - g0)*S + t of every level of the volume
+      const int g0 = n0 + p0;
+      for (int b = g0 / a->N; b < B && b * a->N < g0 + pc; ++b) {
+        const int lo = g0 > b * a->N ? g0 : b * a->N;
+        const int hi = g0 + pc < (b + 1) * a->N ? g0 + pc : (b + 1) * a->N;
+        const int m0 = lo - b * a->N, mc = hi - lo;
+        float* vb = vol + (size_t)(lo - g0) * a->S * CTK_CORR_LD;  // (an SH row has the bytes of an f32 row)
+        if (sp) CTK_TRY(ctk_launch_corr_volume_sh(videos + b, ws.fm_sh[b], m0, mc, vb, rows * CTK_CORR_LD * 2, ws.corr_version, s));
+        else CTK_TRY(ctk_launch_corr_volume(videos + b, m0, mc, vb, rows * CTK_CORR_LD, CTK_CORR_LD, s));
+      }
       if (pipelined && pieces > 1) {
         CTK_TRY(pipe.fork());
         gs = aux;
@@ -420,8 +458,8 @@ int run_corr_embed(const ctk_window_args* a, const ctk_model_weights* w, float* 
       // corr_mlp.fc1 + exact GELU over all 4 levels at once        cotracker3_online.py:205, blocks.py:71-72
       CTK_TRY(gemm(vol, CTK_CORR_LD, (int)(rows * CTK_LEVELS), WRef{w->corr_fc1_w, w->corr_fc1_p}, CTK_CORR_LD, CTK_HID, CTK_CORR_LD, h1, CTK_HID,
                    w->corr_fc1_b, CTK_ACT_GELU_ERF, nullptr, 0, gs, nullptr, 0, 1, 0, 0, CTK_CORR_K, sp, sp));
-      // corr_mlp.fc2, one batch per level, written into x[n*S+t][l*256 ...]   (torch.cat :209)
-      CTK_TRY(gemm(h1, CTK_HID, (int)rows, WRef{w->corr_fc2_w, w->corr_fc2_p}, CTK_HID, 256, CTK_HID, x + (long)(n0 + p0) * a->S * CTK_X_LD + CTK_X_CORR,
+      // corr_mlp.fc2, one batch per level, written into x[g*S+t][l*256 ...]   (torch.cat :209)
+      CTK_TRY(gemm(h1, CTK_HID, (int)rows, WRef{w->corr_fc2_w, w->corr_fc2_p}, CTK_HID, 256, CTK_HID, x + (long)g0 * a->S * CTK_X_LD + CTK_X_CORR,
                    CTK_X_LD, w->corr_fc2_b, CTK_ACT_NONE, nullptr, 0, gs, nullptr, 0, CTK_LEVELS, rows * CTK_HID, 256, 0, sp, x_split));
     }
     if (pipelined && pieces > 1) CTK_TRY(pipe.join());  // join before the next chunk reuses the buffers / x is consumed
@@ -434,6 +472,71 @@ int check_window(const ctk_window_args* a) {
   if (a->S <= 0 || a->N <= 0 || a->iters < 0) return CTK_E_SHAPE;
   if ((long)(a->N + CTK_VIRT) * a->S > 2000000000L / CTK_MLP * 64) return CTK_E_SHAPE;
   if (a->flags & ~CTK_WINDOW_NO_SPACE_ATTN) return CTK_E_SHAPE;  // unknown flag bits: a caller built the pre-v6 struct (no `flags`)
+  return CTK_OK;
+}
+
+// Host-only validation of a joint window: no HIP call is made before this has passed.
+int check_batch(const ctk_window_batch* bt) {
+  if (!bt) return CTK_E_NULL;
+  if (bt->B < 1 || bt->B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  if (!bt->videos) return CTK_E_NULL;
+  const ctk_window_args* a = bt->videos;
+  for (int b = 0; b < bt->B; ++b) CTK_TRY(check_window(a + b));
+  for (int b = 1; b < bt->B; ++b) {
+    const ctk_window_args* v = a + b;
+    if (v->S != a->S || v->N != a->N || v->iters != a->iters || v->flags != a->flags) return CTK_E_SHAPE;
+    if (v->scale_x != a->scale_x || v->scale_y != a->scale_y) return CTK_E_SHAPE;
+    for (int l = 0; l < CTK_LEVELS; ++l)
+      if (v->H[l] != a->H[l] || v->W[l] != a->W[l]) return CTK_E_SHAPE;
+    if ((v->point_mask == nullptr) != (a->point_mask == nullptr)) return CTK_E_NULL;
+  }
+  if ((long)bt->B * (a->N + CTK_VIRT) * a->S > 2000000000L / CTK_MLP * 64) return CTK_E_SHAPE;  // (row counts travel as int)
+  return CTK_OK;
+}
+
+size_t window_bytes(const ctk_window_args* a, int B) {
+  size_t total = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
+  total += carve_uf(a->S, a->N, nullptr, B).bytes;
+  total += carve_corr(a, nullptr, B).bytes;
+  return total;
+}
+
+// One window of B videos (validated by the caller): ctk_forward_window is the B == 1 call.
+int forward_windows(const ctk_window_args* videos, int B, const ctk_model_weights* w, void* workspace, size_t workspace_bytes,
+                    hipStream_t s) {
+  const ctk_window_args* a = videos;
+  for (int b = 0; b < B; ++b)
+    if (!videos[b].coords || !videos[b].vis || !videos[b].conf) return CTK_E_NULL;
+  if (!workspace) return CTK_E_NULL;
+  if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
+  if (window_bytes(a, B) > workspace_bytes) return CTK_E_WORKSPACE;
+  char* base = static_cast<char*>(workspace);
+  float* x = reinterpret_cast<float*>(base);
+  size_t off = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
+  const UfWs uws = carve_uf(a->S, a->N, base + off, B);
+  off += uws.bytes;
+  const CorrWs cws = carve_corr(a, base + off, B);
+  const bool sp = split_mode(w);  // split mode: the transformer input x is kept in SH format
+  CtkBatchState st{};
+  for (int b = 0; b < B; ++b) {
+    st.coords[b] = videos[b].coords; st.vis[b] = videos[b].vis; st.conf[b] = videos[b].conf;
+  }
+  if (sp && a->iters > 0) CTK_TRY(prepare_pyramid_sh(videos, cws, s, B));
+  for (int it = 0; it < a->iters; ++it) {                          // cotracker3_online.py:187
+    CTK_TRY(run_corr_embed(videos, B, w, x, sp, cws, s));          // :190-210
+    if (B == 1) CTK_TRY(ctk_assemble_tokens(a, x, sp, s));         // :212-245
+    else CTK_TRY(ctk_launch_assemble_batch(st, B, a->S, a->N, a->scale_x, a->scale_y, x, sp, s));
+    CTK_TRY(input_projection(a->S, B * a->N, x, sp, w, uws, s));   // :247 + cotracker.py:484
+    FormerRef fr = former_of(w);
+    fr.aux = B == 1 ? static_cast<hipStream_t>(a->aux_stream) : nullptr;
+    fr.space_attn = (a->flags & CTK_WINDOW_NO_SPACE_ATTN) == 0;
+    fr.B = B;
+    // (CoTracker3's point_mask acts through the sampler alone -- it zeroes the support features of not-yet-queried tracks,
+    // cotracker3_online.py:493-496 -- and the sampler is launched per video with that video's mask: fr.point_mask stays null)
+    CTK_TRY(run_transformer(a->S, a->N, fr, uws, s));              // :250
+    if (B == 1) CTK_TRY(ctk_launch_heads(uws.tokens, w->head_w, w->head_b, a->S, a->N, nullptr, a->coords, a->vis, a->conf, s));  // :252-259
+    else CTK_TRY(ctk_launch_heads_batch(uws.tokens, w->head_w, w->head_b, st, B, a->S, a->N, s));
+  }
   return CTK_OK;
 }
 
@@ -521,7 +624,7 @@ extern "C" int ctk_corr_embed(const ctk_window_args* a, const ctk_model_weights*
   const CorrWs ws = carve_corr(a, workspace);
   if (ws.bytes > workspace_bytes) return CTK_E_WORKSPACE;
   if (split_mode(w)) CTK_TRY(prepare_pyramid_sh(a, ws, static_cast<hipStream_t>(stream)));
-  return run_corr_embed(a, w, x, false, ws, static_cast<hipStream_t>(stream));
+  return run_corr_embed(a, 1, w, x, false, ws, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ctk_corr_volume_sh_workspace_bytes(const ctk_window_args* a, size_t* out_bytes) {
@@ -536,17 +639,14 @@ extern "C" int ctk_corr_volume_sh(const ctk_window_args* a, void* out, void* wor
   if (ws.bytes > workspace_bytes) return CTK_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   CTK_TRY(prepare_pyramid_sh(a, ws, s));
-  return ctk_launch_corr_volume_sh(a, ws.fm_sh, 0, a->N, out, (long)a->N * a->S * CTK_CORR_LD * 2, ws.corr_version, s);
+  return ctk_launch_corr_volume_sh(a, ws.fm_sh[0], 0, a->N, out, (long)a->N * a->S * CTK_CORR_LD * 2, ws.corr_version, s);
 }
 
 // Workspace of a whole window: x | update-former buffers | correlation buffers
 extern "C" int ctk_forward_window_workspace_bytes(const ctk_window_args* a, size_t* out_bytes) {
   if (!out_bytes) return CTK_E_NULL;
   CTK_TRY(check_window(a));
-  size_t total = align256((size_t)a->N * a->S * CTK_X_LD * sizeof(float));
-  total += carve_uf(a->S, a->N, nullptr).bytes;
-  total += carve_corr(a, nullptr).bytes;
-  *out_bytes = total;
+  *out_bytes = window_bytes(a, 1);
   return CTK_OK;
 }
 
@@ -554,31 +654,22 @@ extern "C" int ctk_forward_window(const ctk_window_args* a, const ctk_model_weig
                                   size_t workspace_bytes, void* stream) {
   CTK_TRY(check_window(a));
   CTK_TRY(check_weights(w));
-  if (!workspace || !a->coords || !a->vis || !a->conf) return CTK_E_NULL;
-  if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
-  size_t need = 0;
-  CTK_TRY(ctk_forward_window_workspace_bytes(a, &need));
-  if (need > workspace_bytes) return CTK_E_WORKSPACE;
-  char* base = static_cast<char*>(workspace);
-  float* x = reinterpret_cast<float*>(base);
-  size_t off = align256((size_t)a->N * a->S * CTK_X_LD * sizeof(float));
-  const UfWs uws = carve_uf(a->S, a->N, base + off);
-  off += uws.bytes;
-  const CorrWs cws = carve_corr(a, base + off);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool sp = split_mode(w);  // split mode: the transformer input x is kept in SH format
-  if (sp && a->iters > 0) CTK_TRY(prepare_pyramid_sh(a, cws, s));
-  for (int it = 0; it < a->iters; ++it) {                       // cotracker3_online.py:187
-    CTK_TRY(run_corr_embed(a, w, x, sp, cws, s));               // :190-210
-    CTK_TRY(ctk_assemble_tokens(a, x, sp, s));                  // :212-245
-    CTK_TRY(input_projection(a->S, a->N, x, sp, w, uws, s));    // :247 + cotracker.py:484
-    FormerRef fr = former_of(w);
-    fr.aux = static_cast<hipStream_t>(a->aux_stream);
-    fr.space_attn = (a->flags & CTK_WINDOW_NO_SPACE_ATTN) == 0;
-    CTK_TRY(run_transformer(a->S, a->N, fr, uws, s));           // :250
-    CTK_TRY(ctk_launch_heads(uws.tokens, w->head_w, w->head_b, a->S, a->N, nullptr, a->coords, a->vis, a->conf, s));  // :252-259
-  }
+  return forward_windows(a, 1, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+// ---- joint window of B videos --------------------------------------------------------------------------------
+extern "C" int ctk_forward_window_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes) {
+  if (!out_bytes) return CTK_E_NULL;
+  CTK_TRY(check_batch(batch));
+  *out_bytes = window_bytes(batch->videos, batch->B);
   return CTK_OK;
+}
+
+extern "C" int ctk_forward_window_batch(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  CTK_TRY(check_batch(batch));
+  CTK_TRY(check_weights(w));
+  return forward_windows(batch->videos, batch->B, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 // ---- hipGraph of one window (BASELINE.json configs[3]) ------------------------------------------------------
@@ -641,6 +732,21 @@ extern "C" int ctk_window_graph_create(const ctk_window_args* a, const ctk_model
   CTK_TRY(ctk_forward_window_workspace_bytes(a, &need));
   if (need > workspace_bytes) return CTK_E_WORKSPACE;
   return capture_graph([&](hipStream_t cs) { return ctk_forward_window(a, w, workspace, workspace_bytes, cs); }, out);
+}
+
+extern "C" int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
+                                             size_t workspace_bytes, ctk_window_graph** out) {
+  if (!out) return CTK_E_NULL;
+  *out = nullptr;
+  if (ctk_profile_is_on()) return CTK_E_STATE;
+  // validate before touching the capture machinery (ctk_forward_window_batch repeats these checks)
+  CTK_TRY(check_batch(batch));
+  CTK_TRY(check_weights(w));
+  if (!workspace) return CTK_E_NULL;
+  for (int b = 0; b < batch->B; ++b)
+    if (!batch->videos[b].coords || !batch->videos[b].vis || !batch->videos[b].conf) return CTK_E_NULL;
+  if (window_bytes(batch->videos, batch->B) > workspace_bytes) return CTK_E_WORKSPACE;
+  return capture_graph([&](hipStream_t cs) { return ctk_forward_window_batch(batch, w, workspace, workspace_bytes, cs); }, out);
 }
 
 // ---- CoTracker2 window driver (cotracker.py:86-173): one capture-safe call per window --------------------------

@@ -41,7 +41,20 @@ struct AttnP {
   int log2m;     // partial maxima are in the log2 domain (attention_q64_kernel) -> the merge uses exp2
   const uint8_t* kmask;  // [n2] or null: masked keys get logit -FLT_MAX (CoTracker2)
   const uint8_t* qmask;  // [n1] or null: a masked query attends uniformly
+  // Two-level batch (ctk_attention_ex; joint windows of B videos): batch b = bo * binner + bi, row(b, i) = bo * obs + bi * bs + i * is,
+  // masks of outer batch bo start at bo * km_obs / bo * qm_obs.  Single level: binner = nbatch (bo == 0 for every b) and zero outer
+  // strides, so every address is the one the single-level formula gives.  The split-K partials are indexed by the linear b.
+  int binner;
+  long q_obs, kv_obs, o_obs;
+  long km_obs, qm_obs;
 };
+
+// first row of batch b: bo * obs + bi * bs; `bo` is handed back for the masks
+__device__ __forceinline__ long batch_row(const int b, const int binner, const long bs, const long obs, int* bo_out = nullptr) {
+  const int bo = b / binner;
+  if (bo_out) *bo_out = bo;
+  return (long)bo * obs + (long)(b - bo * binner) * bs;
+}
 
 __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [2][bpw][KC*HD+BPAD]
@@ -69,7 +82,7 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
   // query row -> registers, pre-scaled
   float qr[HD];
   {
-    const float* qp = p.q + (myb * p.q_bs + myq * p.q_is) * p.q_ld + head * HD;
+    const float* qp = p.q + (batch_row(myb, p.binner, p.q_bs, p.q_obs) + myq * p.q_is) * p.q_ld + head * HD;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
       const f32x4 t = *reinterpret_cast<const f32x4*>(qp + d);
@@ -80,7 +93,10 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
 #pragma unroll
   for (int d = 0; d < HD; ++d) acc[d] = 0.0f;
   float m = -INFINITY, l = 0.0f;
-  const bool qmasked = p.qmask && !p.qmask[myq];
+  int mybo;
+  const long myorow = batch_row(myb, p.binner, p.o_bs, p.o_obs, &mybo) + myq * p.o_is;
+  const bool qmasked = p.qmask && !p.qmask[mybo * p.qm_obs + myq];
+  const uint8_t* mykmask = p.kmask ? p.kmask + mybo * p.km_obs : nullptr;
 
   const int kbeg = split * p.keys_per_split;
   const int kend = min(p.n2, kbeg + p.keys_per_split);
@@ -97,7 +113,7 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
       const int d4 = i % (HD / 4);
       const int kk = (i / (HD / 4)) % kn;
       const int bb = i / ((HD / 4) * kn);
-      const long row = ((long)(b0 + bb) * p.kv_bs + (long)(k0 + kk) * p.kv_is) * p.kv_ld + head * HD + d4 * 4;
+      const long row = (batch_row(b0 + bb, p.binner, p.kv_bs, p.kv_obs) + (long)(k0 + kk) * p.kv_is) * p.kv_ld + head * HD + d4 * 4;
       *reinterpret_cast<f32x4*>(&lk[bb * bstride + kk * HD + d4 * 4]) = *reinterpret_cast<const f32x4*>(p.k + row);
       *reinterpret_cast<f32x4*>(&lv[bb * bstride + kk * HD + d4 * 4]) = *reinterpret_cast<const f32x4*>(p.v + row);
     }
@@ -114,7 +130,7 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
           const f32x4 t = *reinterpret_cast<const f32x4*>(myk + kk * HD + d);
           dot += qr[d] * t[0] + qr[d + 1] * t[1] + qr[d + 2] * t[2] + qr[d + 3] * t[3];
         }
-        if (p.kmask && !p.kmask[k0 + kk]) dot = NEG_MAX;
+        if (mykmask && !mykmask[k0 + kk]) dot = NEG_MAX;
         if (qmasked) dot = NEG_MAX;
         cmax = fmaxf(cmax, dot);
       } else {
@@ -145,8 +161,8 @@ __global__ __launch_bounds__(64) void attention_kernel(AttnP p) {
   if (!active) return;
   if (p.splits == 1) {
     const float inv = 1.0f / l;
-    float* op = p.out + (myb * p.o_bs + myq * p.o_is) * p.o_ld + head * HD;
-    _Float16* oh = reinterpret_cast<_Float16*>(p.out) + (myb * p.o_bs + myq * p.o_is) * p.o_ld;
+    float* op = p.out + myorow * p.o_ld + head * HD;
+    _Float16* oh = reinterpret_cast<_Float16*>(p.out) + myorow * p.o_ld;
 #pragma unroll
     for (int d = 0; d < HD; d += 4) {
       f32x4 t = {acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv};
@@ -254,10 +270,15 @@ __global__ __launch_bounds__(256) void attention_kv64_kernel(AttnP p) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r32 = lane & 31, half = lane >> 5;
   const int head = blockIdx.y, b = blockIdx.z;
   unsigned char* oimg = reinterpret_cast<unsigned char*>(lds + 2 * 64 * KP + 2 * 64 * VP) + wave * OIMG_BYTES;  // SH output image of this wave
+  int bo;  // outer batch (video) of this workgroup's frame; 0 in a single-level call
+  const long kvb = batch_row(b, p.binner, p.kv_bs, p.kv_obs, &bo);
+  const long qb = batch_row(b, p.binner, p.q_bs, p.q_obs), ob = batch_row(b, p.binner, p.o_bs, p.o_obs);
+  const uint8_t* kmask = p.kmask ? p.kmask + bo * p.km_obs : nullptr;
+  const uint8_t* qmask = p.qmask ? p.qmask + bo * p.qm_obs : nullptr;
 
   for (int i = tid; i < 64 * (HD / 4); i += 256) {
     const int key = i / (HD / 4), d4 = i - key * (HD / 4);
-    const long row = ((long)b * p.kv_bs + (long)key * p.kv_is) * p.kv_ld + head * HD + d4 * 4;
+    const long row = (kvb + (long)key * p.kv_is) * p.kv_ld + head * HD + d4 * 4;
     const f32x4 kk = *reinterpret_cast<const f32x4*>(p.k + row);
     const f32x4 vv = *reinterpret_cast<const f32x4*>(p.v + row);
     f16x4 hi, lo;
@@ -278,7 +299,7 @@ __global__ __launch_bounds__(256) void attention_kv64_kernel(AttnP p) {
   f32x4 qraw[6];
   auto load_q = [&](int q0) {
     const int qi = min(q0 + r32, p.n1 - 1);
-    const float* qp = p.q + ((long)b * p.q_bs + (long)qi * p.q_is) * p.q_ld + head * HD + half * 8;
+    const float* qp = p.q + (qb + (long)qi * p.q_is) * p.q_ld + head * HD + half * 8;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       qraw[2 * j] = *reinterpret_cast<const f32x4*>(qp + 16 * j);
@@ -311,14 +332,14 @@ __global__ __launch_bounds__(256) void attention_kv64_kernel(AttnP p) {
         sacc[kt] = ctk_mma3(kh, kl, qh[j], ql[j], sacc[kt]);
       }
     }
-    if (p.kmask || p.qmask) {  // CoTracker2 masks: masked keys / every key of a masked query -> the same huge negative logit
-      const bool qm = p.qmask && !p.qmask[qi];
+    if (kmask || qmask) {  // CoTracker2 masks: masked keys / every key of a masked query -> the same huge negative logit
+      const bool qm = qmask && !qmask[qi];
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int key = 32 * kt + 8 * (e >> 2) + 4 * half + (e & 3);
-          if (qm || (p.kmask && !p.kmask[key])) sacc[kt][e] = NEG_MAX;
+          if (qm || (kmask && !kmask[key])) sacc[kt][e] = NEG_MAX;
         }
     }
     // softmax over the 64 keys of my query: 32 values here, 32 in lane ^ 32
@@ -363,10 +384,10 @@ __global__ __launch_bounds__(256) void attention_kv64_kernel(AttnP p) {
     if (p.o_split) {
       attn_store_sh_head(oacc, inv, oimg, lane, head, [&](int row) -> _Float16* {
         const int qr = q0 + row;
-        return qr < p.n1 ? reinterpret_cast<_Float16*>(p.out) + ((long)b * p.o_bs + (long)qr * p.o_is) * p.o_ld : nullptr;
+        return qr < p.n1 ? reinterpret_cast<_Float16*>(p.out) + (ob + (long)qr * p.o_is) * p.o_ld : nullptr;
       });
     } else if (q0 + r32 < p.n1) {
-      const long orow = ((long)b * p.o_bs + (long)qi * p.o_is) * p.o_ld;
+      const long orow = (ob + (long)qi * p.o_is) * p.o_ld;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -394,11 +415,16 @@ __global__ __launch_bounds__(256) void attention_q64_kernel(AttnP p) {
   static_assert((VT_PITCH * 4) % 16 == 0 && (64 * (HD + 2) * 4) % 16 == 0, "16-byte rows / slices for ds_write_b128");
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r32 = lane & 31, half = lane >> 5;
   const int split = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
+  int bo;  // outer batch (video) of this workgroup's frame; 0 in a single-level call
+  const long kvb = batch_row(b, p.binner, p.kv_bs, p.kv_obs, &bo);
+  const long qb = batch_row(b, p.binner, p.q_bs, p.q_obs), ob = batch_row(b, p.binner, p.o_bs, p.o_obs);
+  const uint8_t* kmask = p.kmask ? p.kmask + bo * p.km_obs : nullptr;
+  const uint8_t* qmask = p.qmask ? p.qmask + bo * p.qm_obs : nullptr;
 
   f16x8 qh[2][3], ql[2][3];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
-    const float* qp = p.q + ((long)b * p.q_bs + (long)(qt * 32 + r32) * p.q_is) * p.q_ld + head * HD + half * 8;
+    const float* qp = p.q + (qb + (long)(qt * 32 + r32) * p.q_is) * p.q_ld + head * HD + half * 8;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const f32x4 a = *reinterpret_cast<const f32x4*>(qp + 16 * j) * p.scale2;
@@ -409,8 +435,8 @@ __global__ __launch_bounds__(256) void attention_q64_kernel(AttnP p) {
   const int kbeg = split * p.keys_per_split;
   const int kend = min(p.n2, kbeg + p.keys_per_split);
   const int ntiles = (kend - kbeg + 31) >> 5;
-  const float* kbase = p.k + (long)b * p.kv_bs * p.kv_ld + head * HD + half * 8;
-  const float* vbase = p.v + (long)b * p.kv_bs * p.kv_ld + head * HD;
+  const float* kbase = p.k + kvb * p.kv_ld + head * HD + half * 8;
+  const float* vbase = p.v + kvb * p.kv_ld + head * HD;
   const long kstride = p.kv_is * p.kv_ld;
   const int vd0 = r32, vd1 = min(32 + r32, HD - 1);  // dims of my V^T rows (rows 48..63 of the 2nd tile: unused outputs)
 
@@ -485,14 +511,14 @@ __global__ __launch_bounds__(256) void attention_q64_kernel(AttnP p) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) sacc[qt] = ctk_mma3(kh[j], kl[j], qh[qt][j], ql[qt][j], sacc[qt]);
     }
-    if (p.kmask || p.qmask) {  // CoTracker2 masks (finite bias: a fully masked row stays a uniform softmax)
+    if (kmask || qmask) {  // CoTracker2 masks (finite bias: a fully masked row stays a uniform softmax)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int key = min(k0 + 8 * (e >> 2) + 4 * half + (e & 3), kend - 1);
-        const bool km = p.kmask && !p.kmask[key];
+        const bool km = kmask && !kmask[key];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt)
-          if (km || (p.qmask && !p.qmask[qt * 32 + r32])) sacc[qt][e] = NEG_MAX;
+          if (km || (qmask && !qmask[qt * 32 + r32])) sacc[qt][e] = NEG_MAX;
       }
     }
     if (k0 + 32 > kend) {  // ragged last tile: keys past the split's range get probability 0
@@ -582,7 +608,7 @@ __global__ __launch_bounds__(256) void attention_q64_kernel(AttnP p) {
     }
     if (p.splits == 1) {
       const float inv = 1.0f / L;
-      const long orow = ((long)b * p.o_bs + (long)qi * p.o_is) * p.o_ld;
+      const long orow = (ob + (long)qi * p.o_is) * p.o_ld;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         const f32x4 t = {o[4 * i] * inv, o[4 * i + 1] * inv, o[4 * i + 2] * inv, o[4 * i + 3] * inv};
@@ -937,13 +963,14 @@ __global__ void attention_merge_kernel(AttnP p) {
     a += w * base[s * stride + 2 + d];
   }
   const float o = a / l;
+  const long orow = batch_row(b, p.binner, p.o_bs, p.o_obs) + qi * p.o_is;
   if (p.o_split) {
-    _Float16* oh = reinterpret_cast<_Float16*>(p.out) + (b * p.o_bs + qi * p.o_is) * p.o_ld + ctk_sh_col(head * HD + d);
+    _Float16* oh = reinterpret_cast<_Float16*>(p.out) + orow * p.o_ld + ctk_sh_col(head * HD + d);
     const _Float16 hi = (_Float16)o;
     oh[0] = hi;
     oh[32] = (_Float16)(o - (float)hi);
   } else {
-    p.out[(b * p.o_bs + qi * p.o_is) * p.o_ld + head * HD + d] = o;
+    p.out[orow * p.o_ld + head * HD + d] = o;
   }
 }
 
@@ -952,9 +979,13 @@ int attn_backend() { return ctk_opt(CTK_OPT_ATTENTION_VALU); }
 
 }  // namespace
 
-extern "C" int ctk_attention(const ctk_attn_args* a, void* stream) {
+extern "C" int ctk_attention(const ctk_attn_args* a, void* stream) { return ctk_attention_ex(a, nullptr, stream); }
+
+extern "C" int ctk_attention_ex(const ctk_attn_args* a, const ctk_attn_batch2* b2, void* stream) {
   if (!a || !a->q || !a->k || !a->v || !a->out) return CTK_E_NULL;
   if (a->nbatch <= 0 || a->n1 <= 0 || a->n2 <= 0) return CTK_E_SHAPE;
+  const bool two_level = b2 != nullptr && b2->inner > 0;
+  if (two_level && (a->nbatch % b2->inner)) return CTK_E_SHAPE;
   if ((a->q_ld % 4) || (a->kv_ld % 4) || (a->o_ld % 4)) return CTK_E_ALIGN;
   if (!ctk_aligned16(a->q) || !ctk_aligned16(a->k) || !ctk_aligned16(a->v) || !ctk_aligned16(a->out)) return CTK_E_ALIGN;
   AttnP p;
@@ -969,6 +1000,9 @@ extern "C" int ctk_attention(const ctk_attn_args* a, void* stream) {
   p.partial = a->partial;
   p.kmask = a->key_mask;
   p.qmask = a->query_mask;
+  p.binner = two_level ? b2->inner : a->nbatch;
+  p.q_obs = two_level ? b2->q_os : 0; p.kv_obs = two_level ? b2->kv_os : 0; p.o_obs = two_level ? b2->o_os : 0;
+  p.km_obs = two_level ? b2->key_mask_os : 0; p.qm_obs = two_level ? b2->query_mask_os : 0;
   p.scale = 0.14433756729740643f;  // 48 ** -0.5 (blocks.py:372)
   p.scale2 = 0.14433756729740643f * 1.4426950408889634f;
   p.log2m = 0;
@@ -1007,8 +1041,10 @@ extern "C" int ctk_attention(const ctk_attn_args* a, void* stream) {
     return CTK_OK;
   }
 
-  if (mfma && a->n1 == a->n2 && p.splits == 1) {
-    // time attention (and any other square shape): one wave per (batch pair | batch, head, 32-query tile)
+  if (mfma && a->n1 == a->n2 && p.splits == 1 && !two_level) {
+    // time attention (and any other square shape): one wave per (batch pair | batch, head, 32-query tile).  Single-level batches
+    // only: the stacked token rows of a joint window keep the tracks of all videos one linear batch, so the time kernels never
+    // see a two-level batch; a two-level square shape other than 64 x 64 (not on the model's path) takes the VALU kernel below.
     p.keys_per_split = a->n2;
     p.bpw = a->n1 <= 16 ? 2 : 1;
     p.qtiles = p.bpw == 2 ? 1 : (a->n1 + 31) / 32;

@@ -15,6 +15,14 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
     if (e__ != hipSuccess) return (int)e__;    \
   } while (0)
 
+// Per-video state pointers of a joint window (ctk_forward_window_batch), handed to the row kernels BY VALUE (the library owns no
+// device memory to keep a table in): video b's coords [S,N,2] and vis / conf [S,N].
+struct CtkBatchState {
+  float* coords[CTK_MAX_BATCH];
+  float* vis[CTK_MAX_BATCH];
+  float* conf[CTK_MAX_BATCH];
+};
+
 static inline bool ctk_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // XCD-aware remap: the dispatcher places workgroup b on XCD b % 8 (observed, speed only).

@@ -101,17 +101,11 @@ __device__ __forceinline__ float assemble_value(const float* coords, const float
   return sinf(a);
 }
 
-__global__ void assemble_kernel(const float* coords, const float* vis, const float* conf, int S, int N, float scale_x,
-                                float scale_y, float* x, int x_split) {
-  constexpr int EW = CTK_X_LD - CTK_X_VIS;  // 96 columns written per row
-  constexpr int G8 = EW / 8;                // 12 column octets
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)S * N * G8;
-  if (i >= total) return;
-  const int e0 = (int)(i % G8) * 8;
-  const long row = i / G8;  // n*S + t
-  const int t = row % S;
-  const int n = row / S;
+constexpr int ASM_G8 = (CTK_X_LD - CTK_X_VIS) / 8;  // 12 column octets of the 96 columns written per row
+
+// columns e0 .. e0+7 of row `row` of x from track n, frame t of one video's state
+__device__ __forceinline__ void assemble_octet(const float* coords, const float* vis, const float* conf, int S, int N, float scale_x,
+                                               float scale_y, float* x, int x_split, long row, int t, int n, int e0) {
   f32x4 v[2];
 #pragma unroll
   for (int k = 0; k < 8; ++k) v[k >> 2][k & 3] = assemble_value(coords, vis, conf, S, N, scale_x, scale_y, t, n, e0 + k);
@@ -128,13 +122,39 @@ __global__ void assemble_kernel(const float* coords, const float* vis, const flo
   }
 }
 
+__global__ void assemble_kernel(const float* coords, const float* vis, const float* conf, int S, int N, float scale_x,
+                                float scale_y, float* x, int x_split) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)S * N * ASM_G8;
+  if (i >= total) return;
+  const int e0 = (int)(i % ASM_G8) * 8;
+  const long row = i / ASM_G8;  // n*S + t
+  const int t = row % S;
+  const int n = row / S;
+  assemble_octet(coords, vis, conf, S, N, scale_x, scale_y, x, x_split, row, t, n, e0);
+}
+
+// joint window: row = (b*N + n)*S + t of the stacked x, state of video b from the by-value table
+__global__ void assemble_batch_kernel(CtkBatchState st, int B, int S, int N, float scale_x, float scale_y, float* x, int x_split) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)B * S * N * ASM_G8;
+  if (i >= total) return;
+  const int e0 = (int)(i % ASM_G8) * 8;
+  const long row = i / ASM_G8;
+  const int t = row % S;
+  const int bn = row / S;
+  const int b = bn / N, n = bn - b * N;
+  assemble_octet(st.coords[b], st.vis[b], st.conf[b], S, N, scale_x, scale_y, x, x_split, row, t, n, e0);
+}
+
 // ---- virtual tokens: tokens[(N+v)*S + t] = virual_tracks[v]   (cotracker.py:487-488) --------
-__global__ void virtual_init_kernel(const float* vt, int S, float* dst) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // float4 index over 64*S*96
-  const long total = (long)CTK_VIRT * S * (CTK_HID / 4);
+// nv = B * 64 virtual tracks of a joint window (rows (b*64 + v)*S + t); nv = 64: one video
+__global__ void virtual_init_kernel(const float* vt, int S, float* dst, int nv) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // float4 index over nv*S*96
+  const long total = (long)nv * S * (CTK_HID / 4);
   if (i >= total) return;
   const int c4 = i % (CTK_HID / 4);
-  const int v = i / ((long)(CTK_HID / 4) * S);
+  const int v = (int)(i / ((long)(CTK_HID / 4) * S)) % CTK_VIRT;
   reinterpret_cast<f32x4*>(dst)[i] = reinterpret_cast<const f32x4*>(vt)[v * (CTK_HID / 4) + c4];
 }
 
@@ -143,12 +163,46 @@ __global__ void virtual_init_kernel(const float* vt, int S, float* dst) {
 // Round 3: a half-wave per row with 16-byte loads (a row's 32 lanes read 512 consecutive bytes per instruction), the 4 x 384 head
 // weights held in registers while the half-wave walks over its rows (they were re-read from cache for every row: 12 of the 15
 // loads), 68 -> ~35 us per launch.  Same sums up to the order of the f32 additions.
+// State of the single-video kernel / of the joint one (row = (b*N + n)*S + t over B videos, per-video pointers by value)
+struct HeadsOne {
+  float *coords, *vis, *conf;
+  __device__ __forceinline__ long rows(int S, int N) const { return (long)S * N; }
+  __device__ __forceinline__ void update(long row, int S, int N, const float (&d)[4]) const {
+    if (coords) {
+      const int t = row % S;
+      const int n = row / S;
+      const long sn = (long)t * N + n;
+      coords[sn * 2] += d[0];
+      coords[sn * 2 + 1] += d[1];
+      vis[sn] += d[2];
+      conf[sn] += d[3];
+    }
+  }
+};
+struct HeadsBatch {
+  CtkBatchState st;
+  int B;
+  __device__ __forceinline__ long rows(int S, int N) const { return (long)B * S * N; }
+  __device__ __forceinline__ void update(long row, int S, int N, const float (&d)[4]) const {
+    const int t = row % S;
+    const int bn = row / S;
+    const int b = bn / N, n = bn - b * N;
+    const long sn = (long)t * N + n;
+    float* c = st.coords[b];
+    c[sn * 2] += d[0];
+    c[sn * 2 + 1] += d[1];
+    st.vis[b][sn] += d[2];
+    st.conf[b][sn] += d[3];
+  }
+};
+
+template <class State>
 __global__ __launch_bounds__(256) void heads_kernel(const float* tokens, const float* hw, const float* hb, int S, int N,
-                                                     float* delta, float* coords, float* vis, float* conf) {
+                                                     float* delta, State state) {
   const int j = threadIdx.x & 31;
   const long hw_id = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 5;  // half-wave index
   const long nhw = ((long)gridDim.x * blockDim.x) >> 5;
-  const long rows = (long)S * N;
+  const long rows = state.rows(S, N);
   f32x4 w[4][3];
 #pragma unroll
   for (int o = 0; o < 4; ++o)
@@ -173,15 +227,7 @@ __global__ __launch_bounds__(256) void heads_kernel(const float* tokens, const f
         const f32x4 t = {d[0], d[1], d[2], d[3]};
         *reinterpret_cast<f32x4*>(delta + row * 4) = t;
       }
-      if (coords) {
-        const int t = row % S;
-        const int n = row / S;
-        const long sn = (long)t * N + n;
-        coords[sn * 2] += d[0];
-        coords[sn * 2 + 1] += d[1];
-        vis[sn] += d[2];
-        conf[sn] += d[3];
-      }
+      state.update(row, S, N, d);
     }
   }
 }
@@ -225,10 +271,10 @@ extern "C" int ctk_assemble_tokens(const ctk_window_args* a, void* x, int32_t x_
   return CTK_OK;
 }
 
-int ctk_launch_virtual_init(const float* vt, int S, float* dst, hipStream_t s) {
-  const long total = (long)CTK_VIRT * S * (CTK_HID / 4);
+int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream_t s) {
+  const long total = (long)B * CTK_VIRT * S * (CTK_HID / 4);
   CtkProfScope ps("virtual_init", 0.0, 16.0 * total, s);
-  hipLaunchKernelGGL(virtual_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, vt, S, dst);
+  hipLaunchKernelGGL(virtual_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, vt, S, dst, B * CTK_VIRT);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }
@@ -238,8 +284,33 @@ int ctk_launch_heads(const float* tokens, const float* hw, const float* hb, int 
   const long rows = (long)S * N;
   CtkProfScope ps("heads_update", 8.0 * rows * CTK_HID, 4.0 * rows * CTK_HID, s);
   const long want = (rows + 7) / 8;  // one row per half-wave at most; 2048 workgroups walk over the rest
-  hipLaunchKernelGGL(heads_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, s, tokens, hw, hb, S, N, delta, coords,
-                     vis, conf);
+  hipLaunchKernelGGL(heads_kernel<HeadsOne>, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, s, tokens, hw, hb, S, N, delta,
+                     HeadsOne{coords, vis, conf});
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+// ---- joint window (ctk_forward_window_batch, B > 1): one launch for all videos -------------------------------------------
+int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, float scale_x, float scale_y, void* x, int x_split,
+                              hipStream_t s) {
+  if (!x) return CTK_E_NULL;
+  if (B <= 0 || B > CTK_MAX_BATCH || S <= 0 || N <= 0 || !(scale_x > 0.f) || !(scale_y > 0.f)) return CTK_E_SHAPE;
+  const long total = (long)B * S * N * ASM_G8;
+  CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, s);
+  hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st, B, S, N, scale_x, scale_y,
+                     static_cast<float*>(x), x_split);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+int ctk_launch_heads_batch(const float* tokens, const float* hw, const float* hb, const CtkBatchState& st, int B, int S, int N,
+                           hipStream_t s) {
+  if (B <= 0 || B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  const long rows = (long)B * S * N;
+  CtkProfScope ps("heads_update", 8.0 * rows * CTK_HID, 4.0 * rows * CTK_HID, s);
+  const long want = (rows + 7) / 8;
+  hipLaunchKernelGGL(heads_kernel<HeadsBatch>, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, s, tokens, hw, hb, S, N,
+                     static_cast<float*>(nullptr), HeadsBatch{st, B});
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }

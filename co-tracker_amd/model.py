@@ -304,6 +304,23 @@ class CoTrackerThreeBase(nn.Module):
         self.encoder_chunk = 16  # frames per CNN call (see _encode); not a reference kwarg
         # pre-sigmoid (visibility, confidence) of the last forward, [B,T,N] each -- parity tests compare logits
         self.last_logits = None
+        # B > 1: "loop" (default) runs the B videos one after the other, each through its own window calls; "joint" runs every
+        # window / iteration chain ONCE for all B videos (ctk_forward_window_batch: one launch per Linear over B times the
+        # rows) and the encoder on the B*T frames as one frame batch.  Results are fp32-class equal to "loop", not
+        # bit-identical (include/ctk.h).  Not a reference kwarg: set it after construction, like hip_graph and precision.
+        self.batch_mode = "loop"
+
+    BATCH_MODES = ("loop", "joint")
+
+    @property
+    def batch_mode(self) -> str:
+        return getattr(self, "_batch_mode", "loop")  # (a model pickled before the attribute existed)
+
+    @batch_mode.setter
+    def batch_mode(self, mode):
+        if mode not in self.BATCH_MODES:
+            raise ValueError(f"batch_mode must be one of {self.BATCH_MODES}, got {mode!r}")
+        self._batch_mode = mode
 
     # -- weights ------------------------------------------------------------------------
     def load_state_dict(self, *args, **kwargs):
@@ -399,33 +416,60 @@ class CoTrackerThreeBase(nn.Module):
                                          "split-half (f16x3) back end (an activation left the f16 range |x| < 65504, or the "
                                          "input was non-finite); restart the stream with model.precision = 'f32'")
 
-    def _graphed_window(self, fm, support, coords, vis, conf, mask, iters, pw):
-        """Run one window through its captured hipGraph: static buffers are created (and the graph captured) on
-        first use of this (shapes, iters, weights) combination, then only refreshed in place and replayed.
-        Returns the static coords/vis/conf tensors (overwritten by the next call)."""
+    def _graphed_windows(self, reqs, iters, pw):
+        """Run one window per request -- (fm, support, coords, vis, conf, mask), one request per video -- through the captured
+        hipGraph of this (shapes, iters, weights, B) combination: static buffers are created (and the graph captured) on first
+        use, then only refreshed in place and replayed.  One request: the single-window graph (ctk_window_graph_create); several:
+        ONE graph of the joint window (ctk_window_batch_graph_create).  Returns the static (coords, vis, conf) of every video
+        (overwritten by the next call).  The option table is part of the key: a graph bakes in the options read at capture."""
+        fm, coords = reqs[0][0], reqs[0][2]
+        B = len(reqs)
         key = (tuple(tuple(f.shape) for f in fm), coords.shape[1], int(iters), id(pw), coords.device.index,
-               int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), bool(getattr(self, "_space_attn", True)))
+               int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), bool(getattr(self, "_space_attn", True)),
+               B, L.option_values())
         g = self._graphs.get(key)
         if g is None:
-            st_fm = [f.clone() for f in fm]
-            st_sup = [s_.clone() for s_ in support]
-            win = ops.Window(st_fm, st_sup, coords.clone(), vis.clone(), conf.clone(), self._scale_xy(), iters=iters,
-                             point_mask=mask.clone(), max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True))
+            wins = [ops.Window([f.clone() for f in fm_], [s_.clone() for s_ in sup_], c_.clone(), v_.clone(), f_.clone(),
+                               self._scale_xy(), iters=iters, point_mask=m_.clone(), max_corr_rows=self.max_corr_rows,
+                               space_attn=getattr(self, "_space_attn", True)) for fm_, sup_, c_, v_, f_, m_ in reqs]
             self._drop_graphs()  # one live graph per model: a new shape replaces the old one (frees its workspace)
-            g = ops.WindowGraph(win, pw)
+            g = ops.WindowGraph(wins[0], pw) if B == 1 else ops.WindowBatchGraph(wins, pw, self.max_corr_rows)
+            g.wins = wins
             self._graphs = {key: g}
         else:
-            st_fm, st_sup, c_, v_, f_, m_ = g.win.keep
-            for d, s_ in zip(st_fm, fm):
-                d.copy_(s_)
-            for d, s_ in zip(st_sup, support):
-                d.copy_(s_)
-            c_.copy_(coords)
-            v_.copy_(vis)
-            f_.copy_(conf)
-            m_.copy_(mask)
+            for win, (fm_, sup_, c_, v_, f_, m_) in zip(g.wins, reqs):
+                st_fm, st_sup, sc, sv, sf, sm = win.keep
+                for d, s_ in zip(st_fm, fm_):
+                    d.copy_(s_)
+                for d, s_ in zip(st_sup, sup_):
+                    d.copy_(s_)
+                sc.copy_(c_)
+                sv.copy_(v_)
+                sf.copy_(f_)
+                sm.copy_(m_)
         g.launch()
-        return g.win.keep[2], g.win.keep[3], g.win.keep[4]
+        return [(w_.keep[2], w_.keep[3], w_.keep[4]) for w_ in g.wins]
+
+    def _run_windows(self, reqs, iters, pw, graphed):
+        """One window per request (see _graphed_windows), all of them in ONE call when there are several (joint batch mode)."""
+        if graphed:
+            return self._graphed_windows(reqs, iters, pw)
+        wins = []
+        for fm, support, coords_init, vis_init, conf_init, mask in reqs:
+            wins.append(ops.Window(fm, support, coords_init.clone(), vis_init.clone(), conf_init.clone(), self._scale_xy(), iters=iters,
+                                   point_mask=mask, max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True)))
+        if len(wins) == 1:
+            ops.forward_window(wins[0], pw)
+        else:
+            ops.forward_windows(wins, pw, self.max_corr_rows)
+        return [(w_.keep[2], w_.keep[3], w_.keep[4]) for w_ in wins]
+
+    def _encode_batch(self, video: torch.Tensor, chunk: int) -> torch.Tensor:
+        """Joint batch mode: the frames of all B videos as ONE frame batch [B*T,3,H,W] -> features [B,T,H/4,W/4,128].  The CNN is
+        per-frame and its result does not depend on which frames share a call (tests/test_gpu_parity.py)."""
+        B, T = video.shape[:2]
+        f0 = self._encode(video.reshape(B * T, *video.shape[2:]).float(), chunk)
+        return f0.view(B, T, *f0.shape[1:])
 
     # -- shared pieces ------------------------------------------------------------------
     def _scale_xy(self):
@@ -505,7 +549,16 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             assert getattr(self, "online_ind", None) is not None, "Call model.init_video_online_processing() first."
         self._hint_now, self._overlap_hint = getattr(self, "_overlap_hint", None), None
         # streaming with the window graph (CoTrackerOnlinePredictor): deferred range check, the chunk stream stays asynchronous
-        deferred = bool(is_online and self.hip_graph and B == 1 and self.stream_range_check == "deferred")
+        joint = B > 1 and self.batch_mode == "joint"
+        deferred = bool(is_online and self.hip_graph and (B == 1 or joint) and self.stream_range_check == "deferred")
+        if joint:
+            # ONE window call per window for all B videos; one finiteness check over the stacked outputs, and a hit re-runs the
+            # whole batch on the exact-f32 back end (per-element online states restored first)
+            coords, vis, conf = self._guarded(
+                lambda prec: self._forward_joint(video, queries, iters, fmaps_chunk_size, is_online, prec),
+                self._joint_snapshot(B) if is_online else None, self._joint_restore, deferred)
+            self.last_logits = (vis, conf)
+            return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
         run = lambda b: self._guarded(  # noqa: E731
             lambda prec: self._forward_one(video[b], queries[b], iters, fmaps_chunk_size, is_online, prec),
             self._online_snapshot() if is_online else None, self._online_restore, deferred)
@@ -527,6 +580,59 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         conf = torch.stack([o[2] for o in outs])
         self.last_logits = (vis, conf)
         return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
+
+    def _joint_snapshot(self, B):
+        """The per-element online states of a joint streaming call (a list of _online_snapshot tuples; all elements start from
+        the state init_video_online_processing left)."""
+        states = self._online_batch if self._online_batch is not None else [self._online_snapshot()] * B
+        assert len(states) == B, "batch size changed between online calls"
+        return list(states)
+
+    def _joint_restore(self, states):
+        if states is not None:
+            self._online_batch = list(states)
+
+    def _forward_joint(self, video, queries, iters, chunk, is_online, precision=None):
+        """batch_mode == "joint": the B videos advance window by window in lock step (equal T, so equal window indices); every
+        window is one joint call.  Online state stays one tuple per element, swapped in around that element's host code.
+        online_feature_cache: each element then encodes through its own cache (per-video encoder calls); otherwise the B*T
+        frames go through the encoder as one frame batch."""
+        B = video.shape[0]
+        pw = self.packed(video.device, precision)
+        states = self._joint_snapshot(B) if is_online else None
+        per_element_encode = is_online and self.online_feature_cache
+        f0 = None if per_element_encode else self._encode_batch(video, chunk)
+        gens = [self._forward_gen(video[b], queries[b], chunk, is_online, None if f0 is None else f0[b]) for b in range(B)]
+        outs = self._drive(gens, lambda reqs: self._run_windows(reqs, iters, pw, bool(is_online and self.hip_graph)), states)
+        if is_online:
+            self._online_batch = states
+        return tuple(torch.stack([o[k] for o in outs]) for k in range(3))
+
+    def _drive(self, gens, run_windows, states=None):
+        """Advance the per-video generators of _forward_gen in lock step: collect one window request from each, run them with
+        run_windows(requests) -> results, hand every generator its result, until they return (coords, vis, conf).  `states`: the
+        per-element online state tuples, swapped in around every step of an element (and updated in place)."""
+        B = len(gens)
+        reqs, outs = [None] * B, [None] * B
+
+        def step(b, value):
+            if states is not None:
+                self._online_restore(states[b])
+            try:
+                reqs[b] = gens[b].send(value)
+            except StopIteration as stop:
+                reqs[b], outs[b] = None, stop.value
+            if states is not None:
+                states[b] = self._online_snapshot()
+
+        for b in range(B):
+            step(b, None)
+        while any(r is not None for r in reqs):
+            assert all(r is not None for r in reqs), "joint batch: the videos must have the same number of windows"
+            res = run_windows(reqs)
+            for b in range(B):
+                step(b, res[b])
+        return outs
 
     def _online_snapshot(self):
         return (self.online_ind, list(self.online_track_support), self.online_coords_predicted, self.online_vis_predicted,
@@ -571,12 +677,19 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         return f0
 
     def _forward_one(self, video, queries, iters, chunk, is_online, precision=None):
+        pw = self.packed(video.device, precision)
+        gen = self._forward_gen(video, queries, chunk, is_online)
+        return self._drive([gen], lambda reqs: self._run_windows(reqs, iters, pw, bool(is_online and self.hip_graph)))[0]
+
+    def _forward_gen(self, video, queries, chunk, is_online, f0=None):
+        """One video's host code as a generator: yields one request (fm, support, coords_init, vis_init, conf_init, mask) per
+        window, receives that window's (coords, vis, conf), returns (coords_pred, vis_pred, conf_pred).  f0: this video's
+        level-0 features when the caller has encoded them already (joint batch mode)."""
         T = video.shape[0]
         N = queries.shape[0]
         S = self.window_len
         step = S // 2
         dev = video.device
-        pw = self.packed(dev, precision)
         queries = queries.float()
         qframes = queries[:, 0].long()                      # cotracker3_online.py:333
         qcoords = (queries[:, 1:3] / self.stride).contiguous()  # :335-336
@@ -584,7 +697,11 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         # encoder + pyramid.  The reference pads the *video* by repeating its last frame
         # (:321-328); the encoder is per-frame, so repeating the last feature map is identical.
         pad = (S - T) if is_online else (S - T % S) % S
-        f0 = self._encode_online(video, chunk, S, step) if is_online else self._encode(video.float(), chunk)
+        if f0 is not None:
+            if is_online:  # encoded by the caller: this element's feature cache is not fed
+                self.online_f0_tail = self._online_prev_frames = None
+        else:
+            f0 = self._encode_online(video, chunk, S, step) if is_online else self._encode(video.float(), chunk)
         if pad > 0:
             f0 = torch.cat([f0, f0[-1:].expand(pad, -1, -1, -1)], dim=0).contiguous()
         pyr = ops.build_pyramid(f0, self.corr_levels)
@@ -634,15 +751,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
                 conf_init = torch.where(copy_over, fprev, conf_init).contiguous()
             mask = (qframes < ind + S).to(torch.uint8).contiguous()  # attention_mask :484, used as :493-496
             fm = pyr if is_online else [p_[ind:ind + S] for p_ in pyr]
-            if is_online and self.hip_graph:
-                coords, vis, conf = self._graphed_window(fm, support, coords_init, vis_init, conf_init, mask, iters, pw)
-            else:
-                coords = coords_init.clone()
-                vis = vis_init.clone()
-                conf = conf_init.clone()
-                win = ops.Window(fm, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=mask,
-                                 max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True))
-                ops.forward_window(win, pw)
+            coords, vis, conf = yield (fm, support, coords_init, vis_init, conf_init, mask)
             S_trim = T if is_online else min(T - ind, S)
             coords_pred[ind:ind + S] = (coords * float(self.stride))[:S_trim]
             vis_pred[ind:ind + S] = vis[:S_trim]
@@ -662,6 +771,10 @@ class CoTrackerThreeOffline(CoTrackerThreeBase):
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200):
         B, T, H, W = self._check_inputs(video, queries, is_train, add_space_attn)
         assert T >= 1
+        if B > 1 and self.batch_mode == "joint":  # one window call for all B videos, one range check over the stacked outputs
+            coords, vis, conf = self._guarded(lambda prec: self._forward_joint(video, queries, iters, fmaps_chunk_size, prec))
+            self.last_logits = (vis, conf)
+            return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
         outs = [self._guarded(lambda prec, b=b: self._forward_one(video[b], queries[b], iters, fmaps_chunk_size, prec))
                 for b in range(B)]
         vis, conf = torch.stack([o[1] for o in outs]), torch.stack([o[2] for o in outs])
@@ -669,19 +782,34 @@ class CoTrackerThreeOffline(CoTrackerThreeBase):
         return torch.stack([o[0] for o in outs]), torch.sigmoid(vis), torch.sigmoid(conf), None
 
     def _forward_one(self, video, queries, iters, chunk, precision=None):
-        T = video.shape[0]
+        pw = self.packed(video.device, precision)
+        win = self._window(self._encode(video.float(), chunk), queries, iters)
+        ops.forward_window(win, pw)
+        coords, vis, conf = win.keep[2:5]
+        return coords * float(self.stride), vis, conf
+
+    def _forward_joint(self, video, queries, iters, chunk, precision=None):
+        """batch_mode == "joint": the B*T frames through the encoder as one frame batch, then ONE window call for the B videos."""
+        B = video.shape[0]
+        pw = self.packed(video.device, precision)
+        f0 = self._encode_batch(video, chunk)
+        wins = [self._window(f0[b], queries[b], iters) for b in range(B)]
+        ops.forward_windows(wins, pw, self.max_corr_rows)
+        return (torch.stack([w_.keep[2] for w_ in wins]) * float(self.stride), torch.stack([w_.keep[3] for w_ in wins]),
+                torch.stack([w_.keep[4] for w_ in wins]))
+
+    def _window(self, f0, queries, iters):
+        """The single window over all T frames of one video: f0 = its level-0 features [T,H/4,W/4,128]."""
+        T = f0.shape[0]
         N = queries.shape[0]
-        dev = video.device
-        pw = self.packed(dev, precision)
+        dev = f0.device
         queries = queries.float()
         qframes = queries[:, 0].long()
         qcoords = (queries[:, 1:3] / self.stride).contiguous()
-        pyr = ops.build_pyramid(self._encode(video.float(), chunk), self.corr_levels)
+        pyr = ops.build_pyramid(f0, self.corr_levels)
         support = self._support(pyr, qframes.float().contiguous(), qcoords)
         coords = qcoords[None].expand(T, N, 2).contiguous()
         vis = torch.zeros(T, N, device=dev)
         conf = torch.zeros(T, N, device=dev)
-        win = ops.Window(pyr, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=None,
-                         max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True))
-        ops.forward_window(win, pw)
-        return coords * float(self.stride), vis, conf
+        return ops.Window(pyr, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=None,
+                          max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True))

@@ -57,6 +57,7 @@ class CoTracker2(nn.Module):
         self.track_feat_updater = nn.Sequential(_Lin(self.latent_dim, self.latent_dim))  # + nn.GELU() (no parameters)
         self.vis_predictor = nn.Sequential(_Lin(self.latent_dim, 1))
         self._packed = None
+        self.batch_mode = "loop"  # B > 1 is a loop over the videos; the joint batch mode of the CoTracker3 models is not available here
         self.hip_graph = False   # streaming (is_online=True): replay the captured window graph; not a reference kwarg
         self._graphs = {}
         from . import model as _m
@@ -84,6 +85,20 @@ from . import _lib as L  # noqa: E402
 from . import ops  # noqa: E402
 
 IN_LD, OUT_LD, DEPTH_V2 = 480, 192, 6  # input_dim 456 / output_dim 130 padded for the GEMM tiles
+
+
+def _v2_get_batch_mode(self) -> str:
+    return "loop"
+
+
+def _v2_set_batch_mode(self, mode):
+    if mode == "joint":
+        raise NotImplementedError("CoTracker2 (model_v2.py) stays on the loop; batch_mode=\"joint\" on a v2 model is not implemented")
+    if mode != "loop":
+        raise ValueError(f"batch_mode must be 'loop' or 'joint', got {mode!r}")
+
+
+CoTracker2.batch_mode = property(_v2_get_batch_mode, _v2_set_batch_mode)
 
 
 class PackedWeightsV2:
@@ -179,7 +194,8 @@ def _v2_forward_window(self, pyr, coords, track_feat, vis, track_mask, point_mas
 
 def _v2_graphed_window(self, pyr, coords, track_feat, vis, track_mask, point_mask, iters, pw):
     """Streaming: the whole window (iters x (5 + ~390) launches) is captured once per shape and replayed per chunk."""
-    key = (tuple(tuple(f.shape) for f in pyr), coords.shape[1], int(iters), id(pw), coords.device.index)
+    # (the option table is part of the key: a captured graph bakes in the options read at capture, include/ctk.h)
+    key = (tuple(tuple(f.shape) for f in pyr), coords.shape[1], int(iters), id(pw), coords.device.index, L.option_values())
     g = self._graphs.get(key)
     if g is None:
         if self._graphs:

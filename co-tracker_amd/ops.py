@@ -132,6 +132,37 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: int = 1
     return out
 
 
+def attention_batch2(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: int = 1, out_split: bool = False,
+                     key_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ctk_attention_ex on the operand layout of a joint window: q [Bo, N1, Bi, 384], k / v [Bo, N2, Bi, 384] (outer batch =
+    video, then the track, then the inner batch = frame) -> out [Bo, N1, Bi, 384] (or its SH form [Bo*N1*Bi, 12, 2, 32]).
+    Batch (bo, bi) attends q[bo, :, bi] over k / v[bo, :, bi]: ONE launch with inner = Bi, row strides bs = 1, is = Bi and the
+    outer strides N1*Bi (q, out) and N2*Bi (k, v) -- different for the two sides.  key_mask [Bo, N2] / query_mask [Bo, N1] uint8."""
+    _chk_f32(q, k, v)
+    Bo, N1, Bi, _ = q.shape
+    N2 = k.shape[1]
+    assert k.shape == (Bo, N2, Bi, L.HID) and v.shape == k.shape
+    out = torch.empty(Bo * N1 * Bi, L.HID // 32, 2, 32, device=q.device, dtype=torch.float16) if out_split else torch.empty_like(q)
+    a = L.AttnArgs()
+    a.q, a.q_ld, a.q_bs, a.q_is = _ptr(q), L.HID, 1, Bi
+    a.k, a.v, a.kv_ld, a.kv_bs, a.kv_is = _ptr(k), _ptr(v), L.HID, 1, Bi
+    a.out, a.o_ld, a.o_bs, a.o_is = _ptr(out), (2 * L.HID if out_split else L.HID), 1, Bi
+    a.o_split = int(out_split)
+    a.nbatch, a.n1, a.n2 = Bo * Bi, N1, N2
+    a.splits = splits
+    part = None
+    if splits > 1:
+        part = torch.empty(splits * Bo * Bi * 8 * N1 * 50, device=q.device, dtype=torch.float32)
+    a.partial = _ptr(part)
+    a.key_mask, a.query_mask = _ptr(key_mask), _ptr(query_mask)
+    b2 = L.AttnBatch2()
+    b2.inner, b2.reserved = Bi, 0
+    b2.q_os, b2.kv_os, b2.o_os = N1 * Bi, N2 * Bi, N1 * Bi
+    b2.key_mask_os, b2.query_mask_os = N2, N1
+    L.check(L.load().ctk_attention_ex(C.byref(a), C.byref(b2), _stream()), "ctk_attention_ex")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # pyramid / samplers
 # ------------------------------------------------------------------------------------------
@@ -470,6 +501,92 @@ class WindowGraph:
         torch.cuda.synchronize(win.device)          # weight packing / input copies issued so far are complete
         L.check(lib.ctk_window_graph_create(C.byref(win.args), C.byref(mw), _ptr(self.ws), self.ws.numel(), C.byref(h)),
                 "ctk_window_graph_create")
+        self._h = h
+        n = C.c_int64(0)
+        L.check(lib.ctk_window_graph_nodes(self._h, C.byref(n)), "ctk_window_graph_nodes")
+        self.nodes = n.value
+
+    def launch(self) -> None:
+        L.check(L.load().ctk_window_graph_launch(self._h, _stream()), "ctk_window_graph_launch")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.load().ctk_window_graph_destroy(h)
+            except Exception:
+                pass
+
+
+class WindowBatch:
+    """ctk_window_batch over B Windows of equal shape (S, N, iters, level sizes, scale, flags, mask presence): the
+    argument of the joint calls.  ``points_per_chunk`` counts points of the STACKED list of B*N tracks (default: what
+    ``max_corr_rows`` rows of correlation volume hold, as for one window) and is written into wins[0]'s slot of the array."""
+
+    def __init__(self, wins: Sequence[Window], max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None):
+        B = len(wins)
+        if not 1 <= B <= L.MAX_BATCH:
+            raise ValueError(f"a joint window takes 1..{L.MAX_BATCH} videos, got {B}")
+        self.wins = list(wins)
+        self.arr = (L.WindowArgs * B)()
+        for b, w_ in enumerate(wins):
+            C.memmove(C.byref(self.arr[b]), C.byref(w_.args), C.sizeof(L.WindowArgs))
+        if B > 1:
+            S, N = wins[0].S, wins[0].N
+            ppc = points_per_chunk if points_per_chunk is not None else max(1, min(B * N, max_corr_rows // S))
+            for b in range(B):
+                self.arr[b].points_per_chunk = int(ppc)
+        elif points_per_chunk is not None:
+            self.arr[0].points_per_chunk = int(points_per_chunk)
+        self.struct = L.WindowBatch(B, 0, C.cast(self.arr, C.POINTER(L.WindowArgs)))
+        self.B, self.S, self.N = B, wins[0].S, wins[0].N
+        self.device = wins[0].device
+
+    def workspace_bytes(self) -> int:
+        nbytes = C.c_size_t(0)
+        L.check(L.load().ctk_forward_window_batch_workspace_bytes(C.byref(self.struct), C.byref(nbytes)),
+                "ctk_forward_window_batch_workspace_bytes")
+        return nbytes.value
+
+
+def forward_windows(wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None) -> None:
+    """ONE joint window call for B videos (ctk_forward_window_batch): `iters` update iterations in place on every
+    win's coords / vis / conf.  One video: exactly forward_window(wins[0])."""
+    batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
+    ws = _workspace(batch.workspace_bytes(), batch.device)
+    mw = weights.struct_for(batch.S)
+    L.check(L.load().ctk_forward_window_batch(C.byref(batch.struct), C.byref(mw), _ptr(ws), ws.numel(), _stream()),
+            "ctk_forward_window_batch")
+
+
+class WindowBatchGraph:
+    """hipGraph of one joint window of B videos (ctk_window_batch_graph_create): the contract of WindowGraph -- the
+    pointers of every win's tensors, of the weights and of a private workspace are baked in, the caller refreshes the
+    tensors' contents in place and calls ``launch()``."""
+
+    def __init__(self, wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None):
+        lib = L.load()
+        self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
+        self.wins = batch.wins
+        self.weights = weights
+        self.ws = torch.empty(batch.workspace_bytes(), device=batch.device, dtype=torch.uint8)  # private: its address is baked in
+        mw = weights.struct_for(batch.S)
+        # one direct iteration first (every kernel resident before the capture), state restored afterwards -- as WindowGraph
+        state = [t_ for w_ in self.wins for t_ in w_.keep[2:5]]
+        saved = [t_.clone() for t_ in state]
+        iters = batch.arr[0].iters
+        for b in range(batch.B):
+            batch.arr[b].iters = 1
+        L.check(lib.ctk_forward_window_batch(C.byref(batch.struct), C.byref(mw), _ptr(self.ws), self.ws.numel(), _stream()),
+                "ctk_forward_window_batch")
+        for b in range(batch.B):
+            batch.arr[b].iters = iters
+        for t_, s_ in zip(state, saved):
+            t_.copy_(s_)
+        torch.cuda.synchronize(batch.device)
+        h = C.c_void_p()
+        L.check(lib.ctk_window_batch_graph_create(C.byref(batch.struct), C.byref(mw), _ptr(self.ws), self.ws.numel(), C.byref(h)),
+                "ctk_window_batch_graph_create")
         self._h = h
         n = C.c_int64(0)
         L.check(lib.ctk_window_graph_nodes(self._h, C.byref(n)), "ctk_window_graph_nodes")

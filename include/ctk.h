@@ -20,7 +20,8 @@
  *    synchronisation, no host reads of device data -> safe under stream capture.
  *  - return value: 0 ok, <0 invalid argument (CTK_E_*), >0 a hipError_t.
  *  - batch size B = 1 per call (every reference config has B = 1; the Python host
- *    loops over B).  C = 128 feature channels, hidden = 384, heads = 8 x 48,
+ *    loops over B) -- except ctk_forward_window_batch, the opt-in joint call for B videos
+ *    of equal shape.  C = 128 feature channels, hidden = 384, heads = 8 x 48,
  *    mlp = 1536, 64 virtual tracks, 4 pyramid levels, 7x7 taps -- the values fixed by
  *    cotracker/models/build_cotracker.py:31-38 and cotracker3_online.py:43-84.
  *
@@ -46,6 +47,8 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (no existing struct or symbol changed, number unchanged): + ctk_forward_window_batch, its workspace query and
+ *       ctk_window_batch_graph_create (joint windows of up to CTK_MAX_BATCH videos); + ctk_attention_ex (two-level batch).
  *   v9 (round 6): + ctk_set_option / ctk_get_option (every back-end choice of the library in one validated, atomic table; the
  *       environment variables are read ONCE when the library is loaded); - the two stream-K scratch entry points of v7 (the
  *       stream-K walk of the persistent GEMMs left the library); ctk_gemm_pp_mode(m) = ctk_set_option(CTK_OPT_GEMM_PP, m) and
@@ -171,6 +174,38 @@ int ctk_window_graph_create(const ctk_window_args* a, const ctk_model_weights* w
 int ctk_window_graph_launch(ctk_window_graph* g, void* stream);
 int ctk_window_graph_nodes(const ctk_window_graph* g, int64_t* out_nodes); /* kernel nodes captured */
 int ctk_window_graph_destroy(ctk_window_graph* g);
+
+/* ---- joint batch: ONE window call for B videos of equal shape (the reference carries B through every tensor of forward,
+ * cotracker3_online.py:294-541) ---------------------------------------------------------------------------------------
+ * videos[0..B) are B ordinary windows, each with its own pyramid, support, point_mask and coords / vis / conf state.  They
+ * must agree in S, N, iters, H, W, scale_x / scale_y, flags and in whether point_mask is given; 1 <= B <= CTK_MAX_BATCH.
+ * Anything else is CTK_E_SHAPE / CTK_E_NULL before any launch.  Inside the workspace the token rows are stacked as all
+ * point rows of all videos, then all virtual-track rows of all videos (point row (b*N + j)*S + t, virtual row
+ * B*N*S + (b*64 + i)*S + t), so every Linear, LayerNorm, time attention and MLP is ONE launch over B times the rows, the
+ * space attentions run with a two-level (video, frame) batch (ctk_attention_ex), token assembly, heads and the virtual-token
+ * broadcast are one launch for all videos, and the correlation sampler is launched per video into its rows of the chunk.
+ * points_per_chunk and aux_stream are taken from videos[0]: the chunk counts points of the STACKED list (0 = all B*N; a
+ * chunk may straddle two videos), and aux_stream is IGNORED when B > 1.
+ * B == 1 enqueues exactly the launches of ctk_forward_window(&videos[0]) and needs exactly its workspace.
+ * Joint and one-by-one results are fp32-class equal, NOT bit-identical: which GEMM kernel a row tile lands on depends on the
+ * total row count (CTK_OPT_GEMM_PP bit 5), and those kernels differ in the residual Linears' last bit.  What is exact: a
+ * video's result does not depend on the CONTENTS of the other videos of the batch, and the call is deterministic.
+ * Same contract as ctk_forward_window otherwise (caller allocates, no host synchronisation, capture-safe, both Linear back
+ * ends).  ctk_window_batch_graph_create captures one such call; the handle is a ctk_window_graph -- launch / nodes / destroy
+ * as above -- and bakes in the pointers of every videos[b], of *w and of workspace.
+ * A captured graph -- of either kind -- also bakes in the OPTION values (ctk_set_option) read while it was captured:
+ * changing an option later does not change what an existing graph runs; re-create the graph.                            */
+#define CTK_MAX_BATCH 16
+typedef struct ctk_window_batch {
+  int32_t B;
+  int32_t reserved;                 /* 0 */
+  const ctk_window_args* videos;    /* [B] */
+} ctk_window_batch;
+int ctk_forward_window_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes);
+int ctk_forward_window_batch(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
+                                  size_t workspace_bytes, ctk_window_graph** out);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
@@ -416,6 +451,22 @@ typedef struct ctk_attn_args {
   const uint8_t* query_mask; /* [n1] */
 } ctk_attn_args;
 int ctk_attention(const ctk_attn_args* a, void* stream);
+/* The same operator with a TWO-LEVEL batch: batch b = bo * inner + bi (nbatch % inner == 0) and
+ *   row(b, i) = bo * os + bi * bs + i * is,
+ * with separate outer strides (in rows) for the queries, the keys / values and the output; the masks of outer batch bo start
+ * at key_mask + bo * key_mask_os / query_mask + bo * query_mask_os (bytes).  This is the space attention of a joint window
+ * (ctk_forward_window_batch): bo = video, bi = frame, and the point rows and the virtual-track rows of a video lie
+ * N*S and 64*S rows apart.  b2 == NULL or inner <= 0 is ctk_attention(a): every address is then the one the single-level
+ * formula gives, and the results are the same bits.  `partial` is [splits, nbatch, 8, n1, 50] over the linear b, as before.
+ * 64-key, 64-query and VALU shapes run on their usual kernels; a two-level SQUARE shape other than 64 x 64 runs on the
+ * VALU kernel (the time-attention kernels take single-level batches only: stacked token rows keep the tracks of all videos
+ * one linear batch).                                                                                                     */
+typedef struct ctk_attn_batch2 {
+  int32_t inner; int32_t reserved;         /* inner batch count (frames); reserved = 0 */
+  int64_t q_os; int64_t kv_os; int64_t o_os;
+  int64_t key_mask_os; int64_t query_mask_os;
+} ctk_attn_batch2;
+int ctk_attention_ex(const ctk_attn_args* a, const ctk_attn_batch2* b2, void* stream);
 
 /* ---- opt-in kernel timing (bench.py) ------------------------------------------------
  * When enabled, every kernel launch of this library is bracketed by two HIP events recorded on

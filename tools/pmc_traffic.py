@@ -65,6 +65,7 @@ NAME_MAP = [
     (r"attention_kernel", "attention_valu"),
     (r"layernorm_kernel", "layernorm"),
     (r"assemble_kernel", "assemble_tokens"),
+    (r"assemble_batch_kernel", "assemble_tokens"),  # joint window (ctk_forward_window_batch, B > 1)
     (r"heads_kernel", "heads_update"),
     (r"split_rows_scaled_kernel", "pyramid_split"),
     (r"virtual_init_kernel", "virtual_init"),
