@@ -15,7 +15,9 @@ iterative update (correlation sampling, corr MLP, token assembly, EfficientUpdat
 Window scheduling and online state are Python glue, as in the reference.
 Inference only (``is_train`` must be False).
 """
+import copy
 import warnings
+from dataclasses import dataclass, replace
 from typing import List, Optional
 
 import torch
@@ -96,7 +98,7 @@ class _UpdateFormerParams(nn.Module):  # cotracker.py:387-462
         self.space_virtual2point_blocks = nn.ModuleList([_CrossBlock(hidden) for _ in range(depth)])
 
 
-DEFAULT_PRECISION = "f16x3"  # Linear back end of newly built models ("f16x3" | "f32"), see CoTrackerThreeBase.precision
+DEFAULT_PRECISION = "f16x3"  # Linear back end of newly built models ("f16x3" | "f32"), see TrackerBase.precision
 
 
 def sincos_time_embed(dim: int, window_len: int) -> torch.Tensor:
@@ -242,8 +244,257 @@ def tail_aliases(prev, cur, dim, step):
         return False
 
 
-class CoTrackerThreeBase(nn.Module):
+@dataclass
+class OnlineState:
+    """The online state of ONE video (the reference batches it inside its state tensors, cotracker3_online.py:163-169 /
+    cotracker.py:187-191; here every batch element owns one).  The tensors in it are never written in place -- every update
+    rebinds the field -- so a shallow copy (dataclasses.replace) is a snapshot."""
+    ind: int = 0
+    track_support: Optional[list] = None   # CoTracker3: the accumulated support features, one [N,49,128] per level
+    track_feat: Optional[torch.Tensor] = None  # CoTracker2: the accumulated track features [S,N,128]
+    coords_predicted: Optional[torch.Tensor] = None
+    vis_predicted: Optional[torch.Tensor] = None
+    conf_predicted: Optional[torch.Tensor] = None
+    f0_tail: Optional[torch.Tensor] = None      # level-0 features of the frames the NEXT chunk starts with (feature cache)
+    prev_frames: Optional[torch.Tensor] = None  # the previous chunk itself (a reference), to prove the overlap on the host
+
+    def __getstate__(self):  # pickles / deep copies: the feature cache is tied to a live allocation and rebuilt on demand
+        return {**self.__dict__, "f0_tail": None, "prev_frames": None}
+
+
+def _online_attr(field):
+    """A reference-visible ``online_*`` attribute: that field of the online state (B > 1: of the last batch element)."""
+    return property(lambda self: getattr(self._online[-1], field))
+
+
+class TrackerBase(nn.Module):
+    """What CoTrackerThreeBase and CoTracker2 (model_v2.py) share and the reference does not have: the attributes that are not
+    reference kwargs, the packed-weight and graph caches, pickling, the f16 range guard, and the forward path over B videos."""
+
+    PACKED_WEIGHTS = None  # the packed-weights class of the model family
+    BATCH_MODES = ("loop", "joint")
+
+    def __init__(self):
+        super().__init__()
+        self._packed = {}  # precision -> PACKED_WEIGHTS
+        self._hip_encoder = None  # encoder_hip.HipEncoder for the current device (repacked convolution weights)
+        # arithmetic of the Linear layers: "f16x3" = split-half MFMA (3 f16 MFMAs per product, f32 accumulate,
+        # fp32-class accuracy at 5.3x the f32-MFMA ceiling), "f32" = exact-f32 MFMA.  Not a reference kwarg.
+        self.precision = DEFAULT_PRECISION
+        # hipGraph replay of the streaming window (BASELINE.json configs[3]): with is_online=True the whole
+        # window (iters x ~190 launches) is captured once per (S, N, iters) and replayed with one graph launch
+        # per chunk.  Not a reference kwarg; CoTrackerOnlinePredictor switches it on.
+        self.hip_graph = False
+        self._graphs = {}
+        # f16 range guard of the split-half back end (include/ctk.h "numeric range"): an activation beyond +-65504
+        # becomes inf/NaN in its hi/lo halves and reaches the window state as a non-finite value (nothing on the path
+        # clamps or masks it), so every forward checks its outputs once and, on a hit, re-runs that forward on the
+        # exact-f32 MFMA back end of the same library (fp32 range, as the reference).  range_fallbacks counts hits.
+        self.range_guard = True
+        self.range_fallbacks = 0
+        # graph streaming only: "deferred" (default) examines a chunk's finiteness flag at the start of the NEXT call, so the
+        # stream of chunk calls never waits for the GPU -- a hit then raises (the chunk was already returned); "immediate" waits
+        # for the flag inside the call (one device-to-host sync per chunk) and, on a hit, restores the online state and re-runs
+        # that chunk on the exact-f32 back end before returning it -- the behaviour of every non-streaming path.
+        self.stream_range_check = "deferred"
+        self._pending_range = None
+        # "hip" (default): the CNN runs on the library's split-half implicit-GEMM convolutions (encoder_hip.py, csrc/conv_pp.hip,
+        # csrc/encoder.hip) -- fp32-class accuracy at 2.2x the speed of MIOpen's fp32 convolutions; "torch": nn.Conv2d on
+        # PyTorch-ROCm / MIOpen (the round-1/2 path, kept for A/B and for `encoder_dtype` experiments).  Not a reference kwarg.
+        self.encoder_backend = "hip"
+        self.encoder_chunk = 16  # frames per CNN call (see _encode); not a reference kwarg
+        # pre-sigmoid outputs of the last forward, [B,T,N] each -- (visibility, confidence), CoTracker2: (visibility,); parity
+        # tests compare logits
+        self.last_logits = None
+        # B > 1: "loop" (default) runs the B videos one after the other, each through its own window calls; "joint" runs every
+        # window / iteration chain ONCE for all B videos (ctk_forward_window_batch: one launch per Linear over B times the
+        # rows) and the encoder on the B*T frames as one frame batch.  Results are fp32-class equal to "loop", not
+        # bit-identical (include/ctk.h).  Not a reference kwarg: set it after construction, like hip_graph and precision.
+        self.batch_mode = "loop"
+
+    @property
+    def batch_mode(self) -> str:
+        return getattr(self, "_batch_mode", "loop")  # (a model pickled before the attribute existed)
+
+    @batch_mode.setter
+    def batch_mode(self, mode):
+        if mode not in self.BATCH_MODES:
+            raise ValueError(f"batch_mode must be one of {self.BATCH_MODES}, got {mode!r}")
+        self._batch_mode = mode
+
+    # -- weights ------------------------------------------------------------------------
+    def load_state_dict(self, *args, **kwargs):
+        self.invalidate_packed_weights()
+        return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.invalidate_packed_weights()
+        return super()._apply(fn, *args, **kwargs)
+
+    def packed(self, device, precision: Optional[str] = None):
+        precision = precision or self.precision
+        pw = self._packed.get(precision)
+        if pw is None or pw.device != device:
+            pw = self._packed[precision] = self.PACKED_WEIGHTS(self, device, precision)
+        return pw
+
+    def invalidate_packed_weights(self):
+        """Call after mutating parameters in place (e.g. weights.fill_synthetic_)."""
+        self._packed = {}
+        self._hip_encoder = None
+        self._drop_graphs()  # captured graphs hold pointers into the old packed weights
+
+    def _drop_graphs(self):
+        if getattr(self, "_graphs", None):
+            # a replay may still be in flight on the current stream: destroying the exec / freeing its private
+            # workspace under it is undefined, so drain first
+            if torch.cuda.is_available():
+                torch.cuda.current_stream().synchronize()
+            self._graphs = {}
+
+    # device-side caches (ctypes structs with raw pointers) are rebuilt on demand: keep them out of pickles / deep copies
+    # (the online state is ordinary tensors and is copied, less its feature cache: OnlineState.__getstate__)
+    _TRANSIENT = {"_packed": dict, "_graphs": dict, "_hip_encoder": type(None), "_pending_range": type(None)}
+
+    def __getstate__(self):
+        # a pending (pinned flag, cuda Event) pair cannot be pickled, and must not be lost: pickling (like deepcopy) a model in
+        # the middle of a graph stream waits for the last chunk and may raise FloatingPointError (INTEGRATION.md)
+        self._resolve_deferred_range_check()
+        st = self.__dict__.copy()
+        for k, mk in self._TRANSIENT.items():
+            if k in st:
+                st[k] = mk()
+        return st
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for k, mk in self._TRANSIENT.items():  # (a pickle of an earlier tree may hold None where this one holds {})
+            if k in self.__dict__:
+                self.__dict__[k] = mk()
+
+    def __deepcopy__(self, memo):
+        cls = self.__class__
+        # may synchronise and raise FloatingPointError (a pending deferred range check of graph streaming): do it BEFORE the
+        # half-built copy is registered in memo, so a raise leaves no partial object behind
+        self._resolve_deferred_range_check()
+        new = cls.__new__(cls)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = self._TRANSIENT[k]() if k in self._TRANSIENT else copy.deepcopy(v, memo)
+        return new
+
+    # -- f16 range guard ----------------------------------------------------------------
+    def _guarded(self, run, snapshot=None, restore=None, deferred=False):
+        """run(precision) -> (coords, vis_logit[, conf_logit]) under the f16 range guard described in __init__.
+        deferred=True (streaming): the finiteness flag of this call is copied to the host asynchronously and examined at
+        the START of the next call, so the stream of chunk calls never waits for the GPU; a hit then raises (the chunk
+        that overflowed has already been returned, and the online state is poisoned: the stream must be re-run with
+        ``precision="f32"``)."""
+        self._resolve_deferred_range_check()
+        out = run(self.precision)
+        if self.precision == "f16x3" and self.range_guard:
+            finite = torch.stack([torch.isfinite(o).all() for o in out]).all()
+            if deferred:
+                flag = torch.empty((), dtype=torch.bool, pin_memory=True)
+                flag.copy_(finite, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                self._pending_range = (flag, ev)
+                return out
+            if not bool(finite):
+                self.range_fallbacks += 1
+                warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left "
+                              "the f16 range (|x| < 65504) or the input is non-finite; re-running this forward on the "
+                              "exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
+                if snapshot is not None:  # (offline / sliding: no online state to put back before the exact-f32 re-run)
+                    restore(snapshot)
+                out = run("f32")
+        return out
+
+    def _resolve_deferred_range_check(self):
+        pending, self._pending_range = getattr(self, "_pending_range", None), None
+        if pending is not None:
+            flag, ev = pending
+            ev.synchronize()
+            if not bool(flag):
+                self.range_fallbacks += 1
+                raise FloatingPointError("cotracker_amd: the previous streaming chunk produced non-finite tracks on the "
+                                         "split-half (f16x3) back end (an activation left the f16 range |x| < 65504, or the "
+                                         "input was non-finite); restart the stream with model.precision = 'f32'")
+
+    # -- the forward path: B videos, loop or joint, offline / sliding / streaming --------
+    def _check_call(self, video, is_train):
+        if is_train:
+            raise NotImplementedError("inference-only implementation (training is out of scope)")
+        if not video.is_cuda:
+            raise RuntimeError("cotracker_amd runs on an MI355X GPU only: move the model and inputs to 'cuda'. "
+                               "There is no CPU path.")
+
+    def _online_states(self, B, T):
+        """The per-video states of a streaming call (is_online=True): one OnlineState per batch element."""
+        assert T <= self.window_len, "Online mode: video chunk must be <= window size."
+        assert getattr(self, "_online", None), "Call model.init_video_online_processing() first."
+        if len(self._online) == 1 and B > 1:  # every element starts from the state init_video_online_processing left
+            self._online = [replace(self._online[0]) for _ in range(B)]
+        assert len(self._online) == B, "batch size changed between online calls"
+        return self._online
+
+    def _track(self, video, iters, make_gens, states=None, **window_kw):
+        """The one forward path.  make_gens(group) -> one generator per video of `group` (a list of batch indices): one
+        video's host code, which yields one window request per window, receives that window's result and returns that video's
+        logits (coords, vis[, conf]).  The videos are grouped -- groups of one in "loop" mode, ONE group of B in "joint" mode --
+        and each group advances in lock step, all its requests going through one _run_windows call.  The range guard wraps one
+        group: "loop" checks every video and re-runs a hit on the exact-f32 back end on its own; "joint" checks the stacked
+        outputs once and re-runs the whole batch.  states: the OnlineStates of a streaming call (None: offline / sliding), put
+        back as they were before the re-run.  Returns forward's tuple: (coords, sigmoid of every logit ..., None)."""
+        B = video.shape[0]
+        joint = B > 1 and self.batch_mode == "joint"
+        groups = [list(range(B))] if joint else [[b] for b in range(B)]
+        graphed = bool(states is not None and self.hip_graph)
+        # streaming with the window graph (CoTrackerOnlinePredictor): deferred range check, the chunk stream stays asynchronous
+        deferred = graphed and len(groups) == 1 and self.stream_range_check == "deferred"
+        parts = []
+        for group in groups:
+            def run(precision):
+                pw = self.packed(video.device, precision)
+                outs = self._drive(make_gens(group), lambda reqs: self._run_windows(reqs, iters, pw, graphed, **window_kw))
+                return tuple(torch.stack(o) for o in zip(*outs)) if joint else outs[0]
+
+            def restore(saved):
+                for b, st in zip(group, saved):
+                    states[b] = st
+            parts.append(self._guarded(run, None if states is None else [replace(states[b]) for b in group], restore, deferred))
+        out = parts[0] if joint else tuple(torch.stack(o) for o in zip(*parts))
+        self.last_logits = out[1:]
+        return (out[0], *[torch.sigmoid(o) for o in out[1:]], None)
+
+    @staticmethod
+    def _drive(gens, run_windows):
+        """Advance the per-video generators in lock step: collect one window request from each, run them with
+        run_windows(requests) -> results, hand every generator its result, until they return."""
+        B = len(gens)
+        reqs, outs = [None] * B, [None] * B
+
+        def step(b, value):
+            try:
+                reqs[b] = gens[b].send(value)
+            except StopIteration as stop:
+                reqs[b], outs[b] = None, stop.value
+
+        for b in range(B):
+            step(b, None)
+        while any(r is not None for r in reqs):
+            assert all(r is not None for r in reqs), "joint batch: the videos must have the same number of windows"
+            res = run_windows(reqs)
+            for b in range(B):
+                step(b, res[b])
+        return outs
+
+
+class CoTrackerThreeBase(TrackerBase):
     """Constructor mirrors cotracker3_online.py:43-92."""
+
+    PACKED_WEIGHTS = PackedWeights
 
     def __init__(self, window_len=8, stride=4, corr_radius=3, corr_levels=4, num_virtual_tracks=64,
                  model_resolution=(384, 512), add_space_attn=True, linear_layer_for_vis_conf=True):
@@ -269,175 +520,34 @@ class CoTrackerThreeBase(nn.Module):
                                                 vis_conf_head=bool(linear_layer_for_vis_conf), space_attn=bool(add_space_attn))
         self.corr_mlp = _Mlp(49 * 49, 384, 256)
         self.register_buffer("time_emb", sincos_time_embed(self.input_dim, window_len))
-        self._packed = {}  # precision -> PackedWeights
-        self._hip_encoder = None  # encoder_hip.HipEncoder for the current device (repacked convolution weights)
         self.max_corr_rows = 262144  # (point,frame) rows of correlation volume resident at once (~10 GB)
-        # arithmetic of the Linear layers: "f16x3" = split-half MFMA (3 f16 MFMAs per product, f32 accumulate,
-        # fp32-class accuracy at 5.3x the f32-MFMA ceiling), "f32" = exact-f32 MFMA.  Not a reference kwarg.
-        self.precision = DEFAULT_PRECISION
-        # hipGraph replay of the streaming window (BASELINE.json configs[3]): with is_online=True the whole
-        # window (iters x ~190 launches) is captured once per (S, N, iters) and replayed with one graph launch
-        # per chunk.  Not a reference kwarg; CoTrackerOnlinePredictor switches it on.
-        self.hip_graph = False
-        self._graphs = {}
-        # f16 range guard of the split-half back end (include/ctk.h "numeric range"): an activation beyond +-65504
-        # becomes inf/NaN in its hi/lo halves and reaches the window state as a non-finite value (nothing on the path
-        # clamps or masks it), so every forward checks its outputs once and, on a hit, re-runs that forward on the
-        # exact-f32 MFMA back end of the same library (fp32 range, as the reference).  range_fallbacks counts hits.
-        self.range_guard = True
-        self.range_fallbacks = 0
-        # graph streaming only: "deferred" (default) examines a chunk's finiteness flag at the start of the NEXT call, so the
-        # stream of chunk calls never waits for the GPU -- a hit then raises (the chunk was already returned); "immediate" waits
-        # for the flag inside the call (one device-to-host sync per chunk) and, on a hit, restores the online state and re-runs
-        # that chunk on the exact-f32 back end before returning it -- the behaviour of every non-streaming path.
-        self.stream_range_check = "deferred"
         self.encoder_dtype = torch.float32  # fp32 as the reference; see tools/probe_encoder_precision.py for why not lower
-        # "hip" (default): the CNN runs on the library's split-half implicit-GEMM convolutions (encoder_hip.py, csrc/conv_pp.hip,
-        # csrc/encoder.hip) -- fp32-class accuracy at 2.2x the speed of MIOpen's fp32 convolutions; "torch": nn.Conv2d on
-        # PyTorch-ROCm / MIOpen (the round-1/2 path, kept for A/B and for `encoder_dtype` experiments).  Not a reference kwarg.
-        self.encoder_backend = "hip"
         # streaming: reuse the previous chunk's features for the overlapping frames (see _encode_online).  Not a reference
         # kwarg and OFF by default (the reference re-encodes whatever chunk it is given, predictor.py:288-290); opt in for
         # streams whose chunks are overlapping VIEWS of one resident video (see _encode_online: the overlap is proven on the host
         # by storage aliasing; bench.py --workload c4_online --feature-cache)
         self.online_feature_cache = False
-        self.encoder_chunk = 16  # frames per CNN call (see _encode); not a reference kwarg
-        # pre-sigmoid (visibility, confidence) of the last forward, [B,T,N] each -- parity tests compare logits
-        self.last_logits = None
-        # B > 1: "loop" (default) runs the B videos one after the other, each through its own window calls; "joint" runs every
-        # window / iteration chain ONCE for all B videos (ctk_forward_window_batch: one launch per Linear over B times the
-        # rows) and the encoder on the B*T frames as one frame batch.  Results are fp32-class equal to "loop", not
-        # bit-identical (include/ctk.h).  Not a reference kwarg: set it after construction, like hip_graph and precision.
-        self.batch_mode = "loop"
 
-    BATCH_MODES = ("loop", "joint")
-
-    @property
-    def batch_mode(self) -> str:
-        return getattr(self, "_batch_mode", "loop")  # (a model pickled before the attribute existed)
-
-    @batch_mode.setter
-    def batch_mode(self, mode):
-        if mode not in self.BATCH_MODES:
-            raise ValueError(f"batch_mode must be one of {self.BATCH_MODES}, got {mode!r}")
-        self._batch_mode = mode
-
-    # -- weights ------------------------------------------------------------------------
-    def load_state_dict(self, *args, **kwargs):
-        self.invalidate_packed_weights()
-        return super().load_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.invalidate_packed_weights()
-        return super()._apply(fn, *args, **kwargs)
-
-    def packed(self, device, precision: Optional[str] = None) -> PackedWeights:
-        precision = precision or self.precision
-        pw = self._packed.get(precision)
-        if pw is None or pw.device != device:
-            pw = self._packed[precision] = PackedWeights(self, device, precision)
-        return pw
-
-    def invalidate_packed_weights(self):
-        """Call after mutating parameters in place (e.g. weights.fill_synthetic_)."""
-        self._packed = {}
-        self._hip_encoder = None
-        self._drop_graphs()  # captured graphs hold pointers into the old packed weights
-
-    def _drop_graphs(self):
-        if getattr(self, "_graphs", None):
-            # a replay may still be in flight on the current stream: destroying the exec / freeing its private
-            # workspace under it is undefined, so drain first
-            if torch.cuda.is_available():
-                torch.cuda.current_stream().synchronize()
-            self._graphs = {}
-
-    # device-side caches (ctypes structs with raw pointers) are rebuilt on demand: keep them out of pickles / deep copies
-    _TRANSIENT = {"_packed": dict, "_graphs": dict, "_hip_encoder": type(None), "_pending_range": type(None), "_pending_overlap": type(None),
-                  "online_f0_tail": type(None), "_online_prev_frames": type(None), "_overlap_hint": type(None), "_hint_now": type(None)}
-
-    def __getstate__(self):
-        # a pending (pinned flag, cuda Event) pair cannot be pickled, and must not be lost: pickling (like deepcopy) a model in
-        # the middle of a graph stream waits for the last chunk and may raise FloatingPointError (INTEGRATION.md)
-        self._resolve_deferred_range_check()
-        st = self.__dict__.copy()
-        for k, mk in self._TRANSIENT.items():
-            if k in st:
-                st[k] = mk()
-        return st
-
-    def __deepcopy__(self, memo):
-        import copy
-        cls = self.__class__
-        # may synchronise and raise FloatingPointError (a pending deferred range check of graph streaming): do it BEFORE the
-        # half-built copy is registered in memo, so a raise leaves no partial object behind
-        self._resolve_deferred_range_check()
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            new.__dict__[k] = self._TRANSIENT[k]() if k in self._TRANSIENT else copy.deepcopy(v, memo)
-        return new
-
-    def _guarded(self, run, snapshot=None, restore=None, deferred=False):
-        """run(precision) -> (coords, vis_logit, conf_logit) under the f16 range guard described in __init__.
-        deferred=True (streaming): the finiteness flag of this call is copied to the host asynchronously and examined at
-        the START of the next call, so the stream of chunk calls never waits for the GPU; a hit then raises (the chunk
-        that overflowed has already been returned, and the online state is poisoned: the stream must be re-run with
-        ``precision="f32"``)."""
-        self._resolve_deferred_range_check()
-        out = run(self.precision)
-        if self.precision == "f16x3" and self.range_guard:
-            finite = torch.stack([torch.isfinite(o).all() for o in out]).all()
-            if deferred:
-                flag = torch.empty((), dtype=torch.bool, pin_memory=True)
-                flag.copy_(finite, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._pending_range = (flag, ev)
-                return out
-            if not bool(finite):
-                self.range_fallbacks += 1
-                warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left "
-                              "the f16 range (|x| < 65504) or the input is non-finite; re-running this forward on the "
-                              "exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
-                if restore is not None:
-                    restore(snapshot)
-                out = run("f32")
-        return out
-
-    def _resolve_deferred_range_check(self):
-        pending, self._pending_range = getattr(self, "_pending_range", None), None
-        if pending is not None:
-            flag, ev = pending
-            ev.synchronize()
-            if not bool(flag):
-                self.range_fallbacks += 1
-                raise FloatingPointError("cotracker_amd: the previous streaming chunk produced non-finite tracks on the "
-                                         "split-half (f16x3) back end (an activation left the f16 range |x| < 65504, or the "
-                                         "input was non-finite); restart the stream with model.precision = 'f32'")
-
-    def _graphed_windows(self, reqs, iters, pw):
-        """Run one window per request -- (fm, support, coords, vis, conf, mask), one request per video -- through the captured
-        hipGraph of this (shapes, iters, weights, B) combination: static buffers are created (and the graph captured) on first
-        use, then only refreshed in place and replayed.  One request: the single-window graph (ctk_window_graph_create); several:
-        ONE graph of the joint window (ctk_window_batch_graph_create).  Returns the static (coords, vis, conf) of every video
-        (overwritten by the next call).  The option table is part of the key: a graph bakes in the options read at capture."""
+    def _graphed_windows(self, reqs, iters, pw, space_attn):
+        """Run one window per request (see _run_windows) through the captured hipGraph of this (shapes, iters, weights, B)
+        combination: static buffers are created (and the graph captured) on first use, then only refreshed in place and
+        replayed.  One request: the single-window graph (ctk_window_graph_create); several: ONE graph of the joint window
+        (ctk_window_batch_graph_create).  Returns the static (coords, vis, conf) of every video (overwritten by the next
+        call).  The option table is part of the key: a graph bakes in the options read at capture."""
         fm, coords = reqs[0][0], reqs[0][2]
         B = len(reqs)
         key = (tuple(tuple(f.shape) for f in fm), coords.shape[1], int(iters), id(pw), coords.device.index,
-               int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), bool(getattr(self, "_space_attn", True)),
-               B, L.option_values())
+               int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), space_attn, B, L.option_values())
         g = self._graphs.get(key)
         if g is None:
             wins = [ops.Window([f.clone() for f in fm_], [s_.clone() for s_ in sup_], c_.clone(), v_.clone(), f_.clone(),
                                self._scale_xy(), iters=iters, point_mask=m_.clone(), max_corr_rows=self.max_corr_rows,
-                               space_attn=getattr(self, "_space_attn", True)) for fm_, sup_, c_, v_, f_, m_ in reqs]
+                               space_attn=space_attn) for fm_, sup_, c_, v_, f_, m_, _ in reqs]
             self._drop_graphs()  # one live graph per model: a new shape replaces the old one (frees its workspace)
             g = ops.WindowGraph(wins[0], pw) if B == 1 else ops.WindowBatchGraph(wins, pw, self.max_corr_rows)
-            g.wins = wins
             self._graphs = {key: g}
         else:
-            for win, (fm_, sup_, c_, v_, f_, m_) in zip(g.wins, reqs):
+            for win, (fm_, sup_, c_, v_, f_, m_, _) in zip(g.wins, reqs):
                 st_fm, st_sup, sc, sv, sf, sm = win.keep
                 for d, s_ in zip(st_fm, fm_):
                     d.copy_(s_)
@@ -448,28 +558,26 @@ class CoTrackerThreeBase(nn.Module):
                 sf.copy_(f_)
                 sm.copy_(m_)
         g.launch()
-        return [(w_.keep[2], w_.keep[3], w_.keep[4]) for w_ in g.wins]
+        return [w_.keep[2:5] for w_ in g.wins]
 
-    def _run_windows(self, reqs, iters, pw, graphed):
-        """One window per request (see _graphed_windows), all of them in ONE call when there are several (joint batch mode)."""
+    def _run_windows(self, reqs, iters, pw, graphed, space_attn=True):
+        """One window per request -- (fmaps, support, coords, vis, conf, point_mask or None, owned), one request per video -- all of
+        them in ONE call when there are several (joint batch mode).  The window overwrites its coords / vis / conf: a request
+        that is not `owned` hands over state it still needs (the sliding carry-over), so the window gets clones.  Returns every
+        video's (coords, vis, conf)."""
         if graphed:
-            return self._graphed_windows(reqs, iters, pw)
+            return self._graphed_windows(reqs, iters, pw, space_attn)
         wins = []
-        for fm, support, coords_init, vis_init, conf_init, mask in reqs:
-            wins.append(ops.Window(fm, support, coords_init.clone(), vis_init.clone(), conf_init.clone(), self._scale_xy(), iters=iters,
-                                   point_mask=mask, max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True)))
+        for fm, support, coords, vis, conf, mask, owned in reqs:
+            if not owned:
+                coords, vis, conf = coords.clone(), vis.clone(), conf.clone()
+            wins.append(ops.Window(fm, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=mask,
+                                   max_corr_rows=self.max_corr_rows, space_attn=space_attn))
         if len(wins) == 1:
             ops.forward_window(wins[0], pw)
         else:
             ops.forward_windows(wins, pw, self.max_corr_rows)
-        return [(w_.keep[2], w_.keep[3], w_.keep[4]) for w_ in wins]
-
-    def _encode_batch(self, video: torch.Tensor, chunk: int) -> torch.Tensor:
-        """Joint batch mode: the frames of all B videos as ONE frame batch [B*T,3,H,W] -> features [B,T,H/4,W/4,128].  The CNN is
-        per-frame and its result does not depend on which frames share a call (tests/test_gpu_parity.py)."""
-        B, T = video.shape[:2]
-        f0 = self._encode(video.reshape(B * T, *video.shape[2:]).float(), chunk)
-        return f0.view(B, T, *f0.shape[1:])
+        return [w_.keep[2:5] for w_ in wins]
 
     # -- shared pieces ------------------------------------------------------------------
     def _scale_xy(self):
@@ -503,148 +611,65 @@ class CoTrackerThreeBase(nn.Module):
             ops.normalize_to_nhwc(f.float().contiguous(), out=out[t0:t0 + step])
         return out
 
+    def _encode_batch(self, video: torch.Tensor, chunk: int) -> torch.Tensor:
+        """Joint batch mode: the frames of all B videos as ONE frame batch [B*T,3,H,W] -> features [B,T,H/4,W/4,128].  The CNN is
+        per-frame and its result does not depend on which frames share a call (tests/test_gpu_parity.py)."""
+        B, T = video.shape[:2]
+        f0 = self._encode(video.reshape(B * T, *video.shape[2:]).float(), chunk)
+        return f0.view(B, T, *f0.shape[1:])
+
+    def _split_queries(self, queries):
+        """queries [N,3] = (frame, x, y) in pixels -> query frames [N] (long), coordinates [N,2] in feature units."""
+        queries = queries.float()
+        return queries[:, 0].long(), (queries[:, 1:3] / self.stride).contiguous()  # cotracker3_online.py:333-336
+
     def _support(self, pyr, frames_f: torch.Tensor, qcoords: torch.Tensor):
         return [ops.sample_support(pyr[l], frames_f, (qcoords / 2 ** l).contiguous()) for l in range(self.corr_levels)]
 
-    def _check_inputs(self, video, queries, is_train, add_space_attn=True):
-        if is_train:
-            raise NotImplementedError("inference-only implementation (training is out of scope)")
-        # forward-time flag of the reference (cotracker.py:496-502: `add_space_attn and hasattr(self, "space_virtual_blocks")`)
-        self._space_attn = bool(add_space_attn) and getattr(self, "add_space_attn", True)
-        if not video.is_cuda:
-            raise RuntimeError("cotracker_amd runs on an MI355X GPU only: move the model and inputs to 'cuda'. "
-                               "There is no CPU path.")
+    def _check_inputs(self, video, queries, is_train, add_space_attn):
+        """-> (B, T, whether this call runs the space attention).  The last is the forward-time flag of the reference
+        (cotracker.py:496-502: `add_space_attn and hasattr(self, "space_virtual_blocks")`)."""
+        self._check_call(video, is_train)
         B, T, C, H, W = video.shape
         assert H % self.stride == 0 and W % self.stride == 0
         assert queries.shape[0] == B and queries.shape[2] == 3
-        return B, T, H, W
+        return B, T, bool(add_space_attn) and self.add_space_attn
 
 
 class CoTrackerThreeOnline(CoTrackerThreeBase):
     """Sliding-window / streaming tracker (cotracker3_online.py:159-541)."""
 
+    _TRANSIENT = {**CoTrackerThreeBase._TRANSIENT, "_overlap_hint": type(None)}
+    online_ind = _online_attr("ind")
+    online_track_support = _online_attr("track_support")
+    online_coords_predicted = _online_attr("coords_predicted")
+    online_vis_predicted = _online_attr("vis_predicted")
+    online_conf_predicted = _online_attr("conf_predicted")
+    online_f0_tail = _online_attr("f0_tail")
+
     def init_video_online_processing(self):  # cotracker3_online.py:163-169
         self._resolve_deferred_range_check()  # the last chunk of the previous stream (graph streaming defers its check by one call)
-        self.online_ind = 0
+        self._online = [OnlineState(track_support=[None] * self.corr_levels)]  # (B > 1: replicated by the first call)
         self.online_track_feat = [None] * self.corr_levels  # unused by v3 (SURVEY §4.2), kept for API parity
-        self.online_track_support = [None] * self.corr_levels
-        self.online_coords_predicted = None
-        self.online_vis_predicted = None
-        self.online_conf_predicted = None
-        self.online_f0_tail = None        # level-0 features of the frames the NEXT chunk starts with (feature cache)
-        self._online_prev_frames = None   # the previous chunk itself (a reference), to prove the overlap on the host
-        self._overlap_hint = None         # the predictor's verdict for the NEXT call (it resizes chunks into fresh tensors)
-        self._pending_overlap = None
-        self._pending_range = None
-        self._online_batch = None  # B > 1: one state tuple per batch element (the attributes above hold the last one run)
+        self._overlap_hint = None  # the predictor's verdict for the NEXT call (it resizes chunks into fresh tensors)
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200,
                 is_online=False):
-        B, T, H, W = self._check_inputs(video, queries, is_train, add_space_attn)
-        S = self.window_len
-        assert S >= 2
-        if is_online:
-            assert T <= S, "Online mode: video chunk must be <= window size."
-            assert getattr(self, "online_ind", None) is not None, "Call model.init_video_online_processing() first."
-        self._hint_now, self._overlap_hint = getattr(self, "_overlap_hint", None), None
-        # streaming with the window graph (CoTrackerOnlinePredictor): deferred range check, the chunk stream stays asynchronous
-        joint = B > 1 and self.batch_mode == "joint"
-        deferred = bool(is_online and self.hip_graph and (B == 1 or joint) and self.stream_range_check == "deferred")
-        if joint:
-            # ONE window call per window for all B videos; one finiteness check over the stacked outputs, and a hit re-runs the
-            # whole batch on the exact-f32 back end (per-element online states restored first)
-            coords, vis, conf = self._guarded(
-                lambda prec: self._forward_joint(video, queries, iters, fmaps_chunk_size, is_online, prec),
-                self._joint_snapshot(B) if is_online else None, self._joint_restore, deferred)
-            self.last_logits = (vis, conf)
-            return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
-        run = lambda b: self._guarded(  # noqa: E731
-            lambda prec: self._forward_one(video[b], queries[b], iters, fmaps_chunk_size, is_online, prec),
-            self._online_snapshot() if is_online else None, self._online_restore, deferred)
-        if is_online and B > 1:
-            # the reference carries the batch inside its state tensors; here every batch element owns a state tuple
-            # that is swapped in around its (independent) window
-            states = self._online_batch if self._online_batch is not None else [self._online_snapshot()] * B
-            assert len(states) == B, "batch size changed between online calls"
-            outs = []
-            for b in range(B):
-                self._online_restore(states[b])
-                outs.append(run(b))
-                states[b] = self._online_snapshot()
-            self._online_batch = states
-        else:
-            outs = [run(b) for b in range(B)]
-        coords = torch.stack([o[0] for o in outs])
-        vis = torch.stack([o[1] for o in outs])
-        conf = torch.stack([o[2] for o in outs])
-        self.last_logits = (vis, conf)
-        return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
+        B, T, space_attn = self._check_inputs(video, queries, is_train, add_space_attn)
+        assert self.window_len >= 2
+        states = self._online_states(B, T) if is_online else None
+        hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None  # the verdict for THIS call, all batch elements
 
-    def _joint_snapshot(self, B):
-        """The per-element online states of a joint streaming call (a list of _online_snapshot tuples; all elements start from
-        the state init_video_online_processing left)."""
-        states = self._online_batch if self._online_batch is not None else [self._online_snapshot()] * B
-        assert len(states) == B, "batch size changed between online calls"
-        return list(states)
+        def make_gens(group):
+            # joint batch mode: the frames of the whole batch through the encoder as ONE frame batch -- unless every element
+            # encodes through its own feature cache (per-video encoder calls)
+            f0 = self._encode_batch(video, fmaps_chunk_size) if len(group) > 1 and not (is_online and self.online_feature_cache) else None
+            return [self._video_gen(video[b], queries[b], fmaps_chunk_size, states[b] if is_online else None, hint,
+                                    None if f0 is None else f0[b]) for b in group]
+        return self._track(video, iters, make_gens, states, space_attn=space_attn)
 
-    def _joint_restore(self, states):
-        if states is not None:
-            self._online_batch = list(states)
-
-    def _forward_joint(self, video, queries, iters, chunk, is_online, precision=None):
-        """batch_mode == "joint": the B videos advance window by window in lock step (equal T, so equal window indices); every
-        window is one joint call.  Online state stays one tuple per element, swapped in around that element's host code.
-        online_feature_cache: each element then encodes through its own cache (per-video encoder calls); otherwise the B*T
-        frames go through the encoder as one frame batch."""
-        B = video.shape[0]
-        pw = self.packed(video.device, precision)
-        states = self._joint_snapshot(B) if is_online else None
-        per_element_encode = is_online and self.online_feature_cache
-        f0 = None if per_element_encode else self._encode_batch(video, chunk)
-        gens = [self._forward_gen(video[b], queries[b], chunk, is_online, None if f0 is None else f0[b]) for b in range(B)]
-        outs = self._drive(gens, lambda reqs: self._run_windows(reqs, iters, pw, bool(is_online and self.hip_graph)), states)
-        if is_online:
-            self._online_batch = states
-        return tuple(torch.stack([o[k] for o in outs]) for k in range(3))
-
-    def _drive(self, gens, run_windows, states=None):
-        """Advance the per-video generators of _forward_gen in lock step: collect one window request from each, run them with
-        run_windows(requests) -> results, hand every generator its result, until they return (coords, vis, conf).  `states`: the
-        per-element online state tuples, swapped in around every step of an element (and updated in place)."""
-        B = len(gens)
-        reqs, outs = [None] * B, [None] * B
-
-        def step(b, value):
-            if states is not None:
-                self._online_restore(states[b])
-            try:
-                reqs[b] = gens[b].send(value)
-            except StopIteration as stop:
-                reqs[b], outs[b] = None, stop.value
-            if states is not None:
-                states[b] = self._online_snapshot()
-
-        for b in range(B):
-            step(b, None)
-        while any(r is not None for r in reqs):
-            assert all(r is not None for r in reqs), "joint batch: the videos must have the same number of windows"
-            res = run_windows(reqs)
-            for b in range(B):
-                step(b, res[b])
-        return outs
-
-    def _online_snapshot(self):
-        return (self.online_ind, list(self.online_track_support), self.online_coords_predicted, self.online_vis_predicted,
-                self.online_conf_predicted, self.online_f0_tail, self._online_prev_frames)
-
-    def _online_restore(self, snap):
-        if snap is not None:
-            (self.online_ind, sup, self.online_coords_predicted, self.online_vis_predicted,
-             self.online_conf_predicted, self.online_f0_tail, self._online_prev_frames) = snap
-            self.online_track_support = list(sup)
-
-    def _encode_online(self, video, chunk, S, step):
+    def _encode_online(self, video, chunk, S, step, st, hint):
         """Streaming: consecutive chunks overlap by S - step frames (predictor.py:225,288-290 feeds the last 2*step frames
         every step), and the encoder is per-frame, so the overlapping frames' level-0 features are the ones computed one
         call ago.  With ``online_feature_cache`` (opt-in) only the `step` NEW frames go through the CNN (half the encoder
@@ -653,55 +678,49 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         storage, offset advanced by `step` frames, same strides / dtype, tensor version unchanged: `tail_aliases`), which is
         what slicing a resident video gives (``video[:, i:i + S]``, then ``video[:, i + step:i + step + S]``).
         CoTrackerOnlinePredictor applies the same test to the chunk it is handed and passes the verdict down
-        (``_overlap_hint``), because it resizes every chunk into a fresh tensor.  A chunk whose overlap cannot be proven
-        that way is simply encoded in full, exactly what the reference does with it (round 3 compared the frames on the
+        (``_overlap_hint`` -> `hint`), because it resizes every chunk into a fresh tensor.  A chunk whose overlap cannot be
+        proven that way is simply encoded in full, exactly what the reference does with it (round 3 compared the frames on the
         device with torch.equal: a blocking device-to-host wait in every streaming call -- ADVICE r3)."""
         T = video.shape[0]
         ov = S - step
-        tail, prev = self.online_f0_tail, self._online_prev_frames
-        hint = getattr(self, "_hint_now", None)  # the predictor's verdict for this forward call (all batch elements)
-        proven = hint if hint is not None else tail_aliases(prev, video, 0, step)
+        tail = st.f0_tail
+        proven = hint if hint is not None else tail_aliases(st.prev_frames, video, 0, step)
         if self.online_feature_cache and T == S and tail is not None and tail.shape[0] == ov and proven:
             f0 = torch.cat([tail, self._encode(video[ov:].float(), chunk)], dim=0)
         else:
             f0 = self._encode(video.float(), chunk)
         if self.online_feature_cache and T == S:
-            self.online_f0_tail = f0[step:]
-            self._online_prev_frames = video  # a reference, not a copy: keeps the storage alive, so "same address" means "same allocation"
+            st.f0_tail = f0[step:]
+            st.prev_frames = video  # a reference, not a copy: keeps the storage alive, so "same address" means "same allocation"
             try:
                 video._ctk_version = video._version  # the version the cached features were computed from
             except Exception:
                 pass
         else:
-            self.online_f0_tail = self._online_prev_frames = None
+            st.f0_tail = st.prev_frames = None
         return f0
 
-    def _forward_one(self, video, queries, iters, chunk, is_online, precision=None):
-        pw = self.packed(video.device, precision)
-        gen = self._forward_gen(video, queries, chunk, is_online)
-        return self._drive([gen], lambda reqs: self._run_windows(reqs, iters, pw, bool(is_online and self.hip_graph)))[0]
-
-    def _forward_gen(self, video, queries, chunk, is_online, f0=None):
-        """One video's host code as a generator: yields one request (fm, support, coords_init, vis_init, conf_init, mask) per
-        window, receives that window's (coords, vis, conf), returns (coords_pred, vis_pred, conf_pred).  f0: this video's
-        level-0 features when the caller has encoded them already (joint batch mode)."""
+    def _video_gen(self, video, queries, chunk, st, hint=None, f0=None):
+        """One video's host code as a generator (see _track): yields one request per window, receives that window's (coords,
+        vis, conf), returns (coords_pred, vis_pred, conf_pred).  st: this video's OnlineState (streaming: ONE window, at
+        st.ind) or None (sliding over all T frames).  f0: this video's level-0 features when the caller has encoded them
+        already (joint batch mode)."""
+        is_online = st is not None
         T = video.shape[0]
         N = queries.shape[0]
         S = self.window_len
         step = S // 2
         dev = video.device
-        queries = queries.float()
-        qframes = queries[:, 0].long()                      # cotracker3_online.py:333
-        qcoords = (queries[:, 1:3] / self.stride).contiguous()  # :335-336
+        qframes, qcoords = self._split_queries(queries)
 
         # encoder + pyramid.  The reference pads the *video* by repeating its last frame
         # (:321-328); the encoder is per-frame, so repeating the last feature map is identical.
         pad = (S - T) if is_online else (S - T % S) % S
         if f0 is not None:
             if is_online:  # encoded by the caller: this element's feature cache is not fed
-                self.online_f0_tail = self._online_prev_frames = None
+                st.f0_tail = st.prev_frames = None
         else:
-            f0 = self._encode_online(video, chunk, S, step) if is_online else self._encode(video.float(), chunk)
+            f0 = self._encode_online(video, chunk, S, step, st, hint) if is_online else self._encode(video.float(), chunk)
         if pad > 0:
             f0 = torch.cat([f0, f0[-1:].expand(pad, -1, -1, -1)], dim=0).contiguous()
         pyr = ops.build_pyramid(f0, self.corr_levels)
@@ -710,32 +729,29 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         vis_pred = torch.zeros(T, N, device=dev)
         conf_pred = torch.zeros(T, N, device=dev)
         if is_online:
-            if self.online_coords_predicted is not None:  # :349-360
+            if st.coords_predicted is not None:  # :349-360
                 p = min(step, T - step)
-                coords_pred = F.pad(self.online_coords_predicted, (0, 0, 0, 0, 0, p))
-                vis_pred = F.pad(self.online_vis_predicted, (0, 0, 0, p))
-                conf_pred = F.pad(self.online_conf_predicted, (0, 0, 0, p))
-            left = 0 if self.online_ind == 0 else self.online_ind + step
-            right = self.online_ind + S
+                coords_pred = F.pad(st.coords_predicted, (0, 0, 0, 0, 0, p))
+                vis_pred = F.pad(st.vis_predicted, (0, 0, 0, p))
+                conf_pred = F.pad(st.conf_predicted, (0, 0, 0, p))
+            left = 0 if st.ind == 0 else st.ind + step
+            right = st.ind + S
             sample_mask = ((qframes >= left) & (qframes < right)).float()[:, None, None]  # :411-414
-            frames_rel = (qframes - self.online_ind).float().contiguous()
+            frames_rel = (qframes - st.ind).float().contiguous()
         else:
             frames_rel = qframes.float().contiguous()
 
         support = self._support(pyr, frames_rel, qcoords)
-        if is_online:  # :424-440 -- accumulate only the tracks whose query frame is in this chunk
-            for l in range(self.corr_levels):
-                if self.online_track_support[l] is None:
-                    self.online_track_support[l] = torch.zeros_like(support[l])
-                self.online_track_support[l] = self.online_track_support[l] + support[l] * sample_mask
-                support[l] = self.online_track_support[l]
+        if is_online:  # :424-440 -- accumulate only the tracks whose query frame is in this chunk (a NEW list: see OnlineState)
+            st.track_support = support = [(torch.zeros_like(s_) if acc is None else acc) + s_ * sample_mask
+                                          for acc, s_ in zip(st.track_support, support)]
 
         coords_init = qcoords[None].expand(S, N, 2).contiguous()
         vis_init = torch.zeros(S, N, device=dev)
         conf_init = torch.zeros(S, N, device=dev)
 
         num_windows = (T - S + step - 1) // step + 1
-        indices = [self.online_ind] if is_online else range(0, step * num_windows, step)
+        indices = [st.ind] if is_online else range(0, step * num_windows, step)
         for ind in indices:
             if ind > 0:  # carry-over from the previous window, :457-482
                 overlap = S - step
@@ -751,16 +767,14 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
                 conf_init = torch.where(copy_over, fprev, conf_init).contiguous()
             mask = (qframes < ind + S).to(torch.uint8).contiguous()  # attention_mask :484, used as :493-496
             fm = pyr if is_online else [p_[ind:ind + S] for p_ in pyr]
-            coords, vis, conf = yield (fm, support, coords_init, vis_init, conf_init, mask)
+            coords, vis, conf = yield (fm, support, coords_init, vis_init, conf_init, mask, False)
             S_trim = T if is_online else min(T - ind, S)
             coords_pred[ind:ind + S] = (coords * float(self.stride))[:S_trim]
             vis_pred[ind:ind + S] = vis[:S_trim]
             conf_pred[ind:ind + S] = conf[:S_trim]
         if is_online:
-            self.online_ind += step
-            self.online_coords_predicted = coords_pred
-            self.online_vis_predicted = vis_pred
-            self.online_conf_predicted = conf_pred
+            st.ind += step
+            st.coords_predicted, st.vis_predicted, st.conf_predicted = coords_pred, vis_pred, conf_pred
         return coords_pred, vis_pred, conf_pred
 
 
@@ -769,47 +783,27 @@ class CoTrackerThreeOffline(CoTrackerThreeBase):
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200):
-        B, T, H, W = self._check_inputs(video, queries, is_train, add_space_attn)
+        B, T, space_attn = self._check_inputs(video, queries, is_train, add_space_attn)
         assert T >= 1
-        if B > 1 and self.batch_mode == "joint":  # one window call for all B videos, one range check over the stacked outputs
-            coords, vis, conf = self._guarded(lambda prec: self._forward_joint(video, queries, iters, fmaps_chunk_size, prec))
-            self.last_logits = (vis, conf)
-            return coords, torch.sigmoid(vis), torch.sigmoid(conf), None
-        outs = [self._guarded(lambda prec, b=b: self._forward_one(video[b], queries[b], iters, fmaps_chunk_size, prec))
-                for b in range(B)]
-        vis, conf = torch.stack([o[1] for o in outs]), torch.stack([o[2] for o in outs])
-        self.last_logits = (vis, conf)
-        return torch.stack([o[0] for o in outs]), torch.sigmoid(vis), torch.sigmoid(conf), None
 
-    def _forward_one(self, video, queries, iters, chunk, precision=None):
-        pw = self.packed(video.device, precision)
-        win = self._window(self._encode(video.float(), chunk), queries, iters)
-        ops.forward_window(win, pw)
-        coords, vis, conf = win.keep[2:5]
-        return coords * float(self.stride), vis, conf
+        def make_gens(group):  # joint batch mode: the B*T frames through the encoder as one frame batch
+            f0 = self._encode_batch(video, fmaps_chunk_size) if len(group) > 1 else None
+            return [self._video_gen(video[b], queries[b], fmaps_chunk_size, None if f0 is None else f0[b]) for b in group]
+        return self._track(video, iters, make_gens, space_attn=space_attn)
 
-    def _forward_joint(self, video, queries, iters, chunk, precision=None):
-        """batch_mode == "joint": the B*T frames through the encoder as one frame batch, then ONE window call for the B videos."""
-        B = video.shape[0]
-        pw = self.packed(video.device, precision)
-        f0 = self._encode_batch(video, chunk)
-        wins = [self._window(f0[b], queries[b], iters) for b in range(B)]
-        ops.forward_windows(wins, pw, self.max_corr_rows)
-        return (torch.stack([w_.keep[2] for w_ in wins]) * float(self.stride), torch.stack([w_.keep[3] for w_ in wins]),
-                torch.stack([w_.keep[4] for w_ in wins]))
-
-    def _window(self, f0, queries, iters):
-        """The single window over all T frames of one video: f0 = its level-0 features [T,H/4,W/4,128]."""
+    def _video_gen(self, video, queries, chunk, f0=None):
+        """One video's host code (see _track): the single window over all T frames.  f0: its level-0 features [T,H/4,W/4,128]
+        when the caller has encoded them already.  The window carries no point mask and may overwrite the tensors it is given."""
+        if f0 is None:
+            f0 = self._encode(video.float(), chunk)
         T = f0.shape[0]
         N = queries.shape[0]
         dev = f0.device
-        queries = queries.float()
-        qframes = queries[:, 0].long()
-        qcoords = (queries[:, 1:3] / self.stride).contiguous()
+        qframes, qcoords = self._split_queries(queries)
         pyr = ops.build_pyramid(f0, self.corr_levels)
         support = self._support(pyr, qframes.float().contiguous(), qcoords)
         coords = qcoords[None].expand(T, N, 2).contiguous()
         vis = torch.zeros(T, N, device=dev)
         conf = torch.zeros(T, N, device=dev)
-        return ops.Window(pyr, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=None,
-                          max_corr_rows=self.max_corr_rows, space_attn=getattr(self, "_space_attn", True))
+        coords, vis, conf = yield (pyr, support, coords, vis, conf, None, True)
+        return coords * float(self.stride), vis, conf

@@ -29,6 +29,13 @@ def _chk_f32(*ts):
             raise ValueError("expected contiguous float32 CUDA(HIP) tensors")
 
 
+def _query_bytes(name: str, *args) -> int:
+    """A `*_bytes` query of the C-ABI (the size comes back through the trailing size_t*)."""
+    nbytes = C.c_size_t(0)
+    L.check(getattr(L.load(), name)(*args, C.byref(nbytes)), name)
+    return nbytes.value
+
+
 # ------------------------------------------------------------------------------------------
 # primitives
 # ------------------------------------------------------------------------------------------
@@ -37,9 +44,7 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     GEMM back end (ctk_pack_weight).  Returns a uint8 device tensor that must outlive its users."""
     _chk_f32(w)
     N, K = w.shape
-    nbytes = C.c_size_t(0)
-    L.check(L.load().ctk_pack_weight_bytes(N, K, C.byref(nbytes)), "ctk_pack_weight_bytes")
-    blob = torch.empty(nbytes.value, device=w.device, dtype=torch.uint8)
+    blob = torch.empty(_query_bytes("ctk_pack_weight_bytes", N, K), device=w.device, dtype=torch.uint8)
     L.check(L.load().ctk_pack_weight(_ptr(w), K, N, K, _ptr(blob), _stream()), "ctk_pack_weight")
     return blob
 
@@ -313,14 +318,11 @@ def v2_vis_head(track_feat: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> t
 def update_former_ex(x: torch.Tensor, x_split: bool, S: int, N: int, fw: "L.FormerWeights", point_mask: Optional[torch.Tensor]) -> torch.Tensor:
     """General EfficientUpdateFormer.forward (cotracker.py:483-531) with the CoTracker2 attention mask:
     x [N*S, in_ld] (f32 or SH) -> delta [N*S, out_ld] f32."""
-    lib = L.load()
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_update_former_workspace_bytes(S, N, C.byref(nbytes)), "ctk_update_former_workspace_bytes")
-    ws = _workspace(nbytes.value, x.device)
+    ws = _workspace(_query_bytes("ctk_update_former_workspace_bytes", S, N), x.device)
     delta = torch.empty(N * S, fw.out_ld, device=x.device, dtype=torch.float32)
     if point_mask is not None:
         assert point_mask.dtype == torch.uint8 and point_mask.shape == (N,) and point_mask.is_cuda
-    L.check(lib.ctk_update_former_ex(S, N, _ptr(x), int(x_split), C.byref(fw), _ptr(point_mask), _ptr(delta), _ptr(ws), ws.numel(),
+    L.check(L.load().ctk_update_former_ex(S, N, _ptr(x), int(x_split), C.byref(fw), _ptr(point_mask), _ptr(delta), _ptr(ws), ws.numel(),
                                      _stream()), "ctk_update_former_ex")
     return delta
 
@@ -347,59 +349,6 @@ class V2Window:
         self.S, self.N = S, N
         self.keep = (list(pyr), coords, track_feat, vis, track_mask, point_mask)
         self.device = coords.device
-
-
-def forward_window_v2(win: V2Window, weights) -> None:
-    """CoTracker2.forward_window (cotracker.py:86-173) as one C call: `iters` iterations in place on win's coords /
-    track_feat, visibility logits into win.vis_out."""
-    lib = L.load()
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_forward_window_v2_workspace_bytes(C.byref(win.args), C.byref(weights.struct), C.byref(nbytes)),
-            "ctk_forward_window_v2_workspace_bytes")
-    ws = _workspace(nbytes.value, win.device)
-    L.check(lib.ctk_forward_window_v2(C.byref(win.args), C.byref(weights.struct), _ptr(ws), ws.numel(), _stream()),
-            "ctk_forward_window_v2")
-
-
-class V2WindowGraph:
-    """hipGraph of one CoTracker2 window (ctk_v2_window_graph_create): same contract as WindowGraph -- pointers of the
-    window's tensors, the weights and a private workspace are baked in; refresh contents in place, then launch()."""
-
-    def __init__(self, win: V2Window, weights):
-        lib = L.load()
-        nbytes = C.c_size_t(0)
-        L.check(lib.ctk_forward_window_v2_workspace_bytes(C.byref(win.args), C.byref(weights.struct), C.byref(nbytes)),
-                "ctk_forward_window_v2_workspace_bytes")
-        self.win, self.weights = win, weights
-        self.ws = torch.empty(nbytes.value, device=win.device, dtype=torch.uint8)
-        # one direct iteration first so that every kernel's code object is resident (no lazy loads inside a capture)
-        state = (win.keep[1], win.keep[2])
-        saved = [t_.clone() for t_ in state]
-        iters, win.args.iters = win.args.iters, 1
-        L.check(lib.ctk_forward_window_v2(C.byref(win.args), C.byref(weights.struct), _ptr(self.ws), self.ws.numel(), _stream()),
-                "ctk_forward_window_v2")
-        win.args.iters = iters
-        for t_, s_ in zip(state, saved):
-            t_.copy_(s_)
-        torch.cuda.synchronize(win.device)
-        h = C.c_void_p()
-        L.check(lib.ctk_v2_window_graph_create(C.byref(win.args), C.byref(weights.struct), _ptr(self.ws), self.ws.numel(), C.byref(h)),
-                "ctk_v2_window_graph_create")
-        self._h = h
-        n = C.c_int64(0)
-        L.check(lib.ctk_window_graph_nodes(self._h, C.byref(n)), "ctk_window_graph_nodes")
-        self.nodes = n.value
-
-    def launch(self) -> None:
-        L.check(L.load().ctk_window_graph_launch(self._h, _stream()), "ctk_window_graph_launch")
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                L.load().ctk_window_graph_destroy(h)
-            except Exception:
-                pass
 
 
 # ------------------------------------------------------------------------------------------
@@ -462,14 +411,26 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
+def _run_window(name: str, args, wstruct, nbytes: int, device) -> None:
+    """The direct window calls: entry point `name` on the argument and weight structs with the shared workspace of `nbytes`."""
+    ws = _workspace(nbytes, device)
+    L.check(getattr(L.load(), name)(C.byref(args), C.byref(wstruct), _ptr(ws), ws.numel(), _stream()), name)
+
+
 def forward_window(win: Window, weights) -> None:
     """`iters` update iterations in place on win's coords/vis/conf (cotracker3_online.py:171-264)."""
-    lib = L.load()
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_forward_window_workspace_bytes(C.byref(win.args), C.byref(nbytes)), "ctk_forward_window_workspace_bytes")
-    ws = _workspace(nbytes.value, win.device)
-    mw = weights.struct_for(win.S)
-    L.check(lib.ctk_forward_window(C.byref(win.args), C.byref(mw), _ptr(ws), ws.numel(), _stream()), "ctk_forward_window")
+    nbytes = _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args))
+    _run_window("ctk_forward_window", win.args, weights.struct_for(win.S), nbytes, win.device)
+
+
+def forward_window_v2(win: V2Window, weights) -> None:
+    """CoTracker2.forward_window (cotracker.py:86-173) as one C call: `iters` iterations in place on win's coords /
+    track_feat, visibility logits into win.vis_out."""
+    _run_window("ctk_forward_window_v2", win.args, weights.struct, _v2_workspace_bytes(win, weights), win.device)
+
+
+def _v2_workspace_bytes(win: V2Window, weights) -> int:
+    return _query_bytes("ctk_forward_window_v2_workspace_bytes", C.byref(win.args), C.byref(weights.struct))
 
 
 class WindowGraph:
@@ -480,27 +441,32 @@ class WindowGraph:
     caller refreshes the CONTENTS of win's tensors in place (``copy_``) and calls ``launch()``."""
 
     def __init__(self, win: Window, weights):
+        self.win, self.wins = win, [win]
+        self._capture("ctk_forward_window", "ctk_window_graph_create", win.args, weights, weights.struct_for(win.S),
+                      _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args)), win.keep[2:5], [win.args], win.device)
+
+    def _capture(self, direct: str, create: str, args, weights, wstruct, nbytes: int, state, iter_slots, device) -> None:
+        """The capture protocol of every window graph.  direct / create: the C entry points of the direct call and of the
+        capture (same arguments: `args`, the weights' struct); state: the tensors the window updates in place; iter_slots: the
+        argument structs whose `iters` the warm-up call patches to 1."""
         lib = L.load()
-        nbytes = C.c_size_t(0)
-        L.check(lib.ctk_forward_window_workspace_bytes(C.byref(win.args), C.byref(nbytes)), "ctk_forward_window_workspace_bytes")
-        self.win = win
         self.weights = weights                      # keeps every weight tensor (and in_bias_t for this S) alive
-        self.ws = torch.empty(nbytes.value, device=win.device, dtype=torch.uint8)  # private: its address is baked in
-        mw = weights.struct_for(win.S)
-        h = C.c_void_p()
+        self.ws = torch.empty(nbytes, device=device, dtype=torch.uint8)  # private: its address is baked in
+        call = (C.byref(args), C.byref(wstruct), _ptr(self.ws), self.ws.numel())
         # One direct iteration first: every kernel of the window is resident (HIP loads code objects lazily, which
         # is not allowed inside a capture); the state it touched is restored afterwards.
-        state = win.keep[2:5]
         saved = [t_.clone() for t_ in state]
-        iters, win.args.iters = win.args.iters, 1
-        L.check(lib.ctk_forward_window(C.byref(win.args), C.byref(mw), _ptr(self.ws), self.ws.numel(), _stream()),
-                "ctk_forward_window")
-        win.args.iters = iters
+        iters = iter_slots[0].iters
+        for a in iter_slots:
+            a.iters = 1
+        L.check(getattr(lib, direct)(*call, _stream()), direct)
+        for a in iter_slots:
+            a.iters = iters
         for t_, s_ in zip(state, saved):
             t_.copy_(s_)
-        torch.cuda.synchronize(win.device)          # weight packing / input copies issued so far are complete
-        L.check(lib.ctk_window_graph_create(C.byref(win.args), C.byref(mw), _ptr(self.ws), self.ws.numel(), C.byref(h)),
-                "ctk_window_graph_create")
+        torch.cuda.synchronize(device)              # weight packing / input copies issued so far are complete
+        h = C.c_void_p()
+        L.check(getattr(lib, create)(*call, C.byref(h)), create)
         self._h = h
         n = C.c_int64(0)
         L.check(lib.ctk_window_graph_nodes(self._h, C.byref(n)), "ctk_window_graph_nodes")
@@ -516,6 +482,15 @@ class WindowGraph:
                 L.load().ctk_window_graph_destroy(h)
             except Exception:
                 pass
+
+
+class V2WindowGraph(WindowGraph):
+    """hipGraph of one CoTracker2 window (ctk_v2_window_graph_create): the contract of WindowGraph."""
+
+    def __init__(self, win: V2Window, weights):
+        self.win, self.wins = win, [win]
+        self._capture("ctk_forward_window_v2", "ctk_v2_window_graph_create", win.args, weights, weights.struct,
+                      _v2_workspace_bytes(win, weights), win.keep[1:3], [win.args], win.device)
 
 
 class WindowBatch:
@@ -543,65 +518,24 @@ class WindowBatch:
         self.device = wins[0].device
 
     def workspace_bytes(self) -> int:
-        nbytes = C.c_size_t(0)
-        L.check(L.load().ctk_forward_window_batch_workspace_bytes(C.byref(self.struct), C.byref(nbytes)),
-                "ctk_forward_window_batch_workspace_bytes")
-        return nbytes.value
+        return _query_bytes("ctk_forward_window_batch_workspace_bytes", C.byref(self.struct))
 
 
 def forward_windows(wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None) -> None:
     """ONE joint window call for B videos (ctk_forward_window_batch): `iters` update iterations in place on every
     win's coords / vis / conf.  One video: exactly forward_window(wins[0])."""
     batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
-    ws = _workspace(batch.workspace_bytes(), batch.device)
-    mw = weights.struct_for(batch.S)
-    L.check(L.load().ctk_forward_window_batch(C.byref(batch.struct), C.byref(mw), _ptr(ws), ws.numel(), _stream()),
-            "ctk_forward_window_batch")
+    _run_window("ctk_forward_window_batch", batch.struct, weights.struct_for(batch.S), batch.workspace_bytes(), batch.device)
 
 
-class WindowBatchGraph:
-    """hipGraph of one joint window of B videos (ctk_window_batch_graph_create): the contract of WindowGraph -- the
-    pointers of every win's tensors, of the weights and of a private workspace are baked in, the caller refreshes the
-    tensors' contents in place and calls ``launch()``."""
+class WindowBatchGraph(WindowGraph):
+    """hipGraph of one joint window of B videos (ctk_window_batch_graph_create): the contract of WindowGraph for every win."""
 
     def __init__(self, wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None):
-        lib = L.load()
         self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
         self.wins = batch.wins
-        self.weights = weights
-        self.ws = torch.empty(batch.workspace_bytes(), device=batch.device, dtype=torch.uint8)  # private: its address is baked in
-        mw = weights.struct_for(batch.S)
-        # one direct iteration first (every kernel resident before the capture), state restored afterwards -- as WindowGraph
-        state = [t_ for w_ in self.wins for t_ in w_.keep[2:5]]
-        saved = [t_.clone() for t_ in state]
-        iters = batch.arr[0].iters
-        for b in range(batch.B):
-            batch.arr[b].iters = 1
-        L.check(lib.ctk_forward_window_batch(C.byref(batch.struct), C.byref(mw), _ptr(self.ws), self.ws.numel(), _stream()),
-                "ctk_forward_window_batch")
-        for b in range(batch.B):
-            batch.arr[b].iters = iters
-        for t_, s_ in zip(state, saved):
-            t_.copy_(s_)
-        torch.cuda.synchronize(batch.device)
-        h = C.c_void_p()
-        L.check(lib.ctk_window_batch_graph_create(C.byref(batch.struct), C.byref(mw), _ptr(self.ws), self.ws.numel(), C.byref(h)),
-                "ctk_window_batch_graph_create")
-        self._h = h
-        n = C.c_int64(0)
-        L.check(lib.ctk_window_graph_nodes(self._h, C.byref(n)), "ctk_window_graph_nodes")
-        self.nodes = n.value
-
-    def launch(self) -> None:
-        L.check(L.load().ctk_window_graph_launch(self._h, _stream()), "ctk_window_graph_launch")
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                L.load().ctk_window_graph_destroy(h)
-            except Exception:
-                pass
+        self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights, weights.struct_for(batch.S),
+                      batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.keep[2:5]], list(batch.arr), batch.device)
 
 
 def corr_volume(win: Window) -> torch.Tensor:
@@ -614,9 +548,7 @@ def corr_volume_sh(win: Window) -> torch.Tensor:
     """Split-half sampler: SH volumes [4, N*S, 76, 2, 32] float16 (use unsplit on a level to compare)."""
     lib = L.load()
     out = torch.empty(L.LEVELS, win.N * win.S, L.CORR_LD // 32, 2, 32, device=win.device, dtype=torch.float16)
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_corr_volume_sh_workspace_bytes(C.byref(win.args), C.byref(nbytes)), "ctk_corr_volume_sh_workspace_bytes")
-    ws = _workspace(nbytes.value, win.device)
+    ws = _workspace(_query_bytes("ctk_corr_volume_sh_workspace_bytes", C.byref(win.args)), win.device)
     L.check(lib.ctk_corr_volume_sh(C.byref(win.args), _ptr(out), _ptr(ws), ws.numel(), _stream()), "ctk_corr_volume_sh")
     return out
 
@@ -625,9 +557,7 @@ def corr_embed(win: Window, weights, x: Optional[torch.Tensor] = None) -> torch.
     lib = L.load()
     if x is None:
         x = torch.zeros(win.N * win.S, L.X_LD, device=win.device, dtype=torch.float32)
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_corr_embed_workspace_bytes(C.byref(win.args), C.byref(nbytes)), "ctk_corr_embed_workspace_bytes")
-    ws = _workspace(nbytes.value, win.device)
+    ws = _workspace(_query_bytes("ctk_corr_embed_workspace_bytes", C.byref(win.args)), win.device)
     mw = weights.struct_for(win.S)
     L.check(lib.ctk_corr_embed(C.byref(win.args), C.byref(mw), _ptr(x), _ptr(ws), ws.numel(), _stream()), "ctk_corr_embed")
     return x
@@ -648,9 +578,7 @@ def update_former(x: torch.Tensor, S: int, N: int, weights) -> torch.Tensor:
     """x [N*S, 1120] (our column layout) -> delta [N*S,4]."""
     _chk_f32(x)
     lib = L.load()
-    nbytes = C.c_size_t(0)
-    L.check(lib.ctk_update_former_workspace_bytes(S, N, C.byref(nbytes)), "ctk_update_former_workspace_bytes")
-    ws = _workspace(nbytes.value, x.device)
+    ws = _workspace(_query_bytes("ctk_update_former_workspace_bytes", S, N), x.device)
     delta = torch.empty(N * S, 4, device=x.device, dtype=torch.float32)
     mw = weights.struct_for(S)
     L.check(lib.ctk_update_former(S, N, _ptr(x), C.byref(mw), _ptr(delta), _ptr(ws), ws.numel(), _stream()), "ctk_update_former")
