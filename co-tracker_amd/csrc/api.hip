@@ -549,7 +549,7 @@ extern "C" const char* ctk_error_string(int code) {
     case CTK_OK: return "ok";
     case CTK_E_NULL: return "required pointer is NULL";
     case CTK_E_SHAPE: return "unsupported shape";
-    case CTK_E_ALIGN: return "pointer or leading dimension not 16-byte aligned";
+    case CTK_E_ALIGN: return "pointer or leading dimension not aligned";
     case CTK_E_WORKSPACE: return "workspace too small";
     case CTK_E_STATE: return "call not allowed in the current state";
     default: return code > 0 ? hipGetErrorString(static_cast<hipError_t>(code)) : "unknown error";
@@ -797,6 +797,9 @@ int check_v2(const ctk_v2_window_args* a, const ctk_v2_weights* w) {
     if (!a->fmaps[l]) return CTK_E_NULL;
     if (a->H[l] <= 0 || a->W[l] <= 0) return CTK_E_SHAPE;
   }
+  // what ctk_v2_vis_head, the LAST call of the window, would refuse (float2 loads): said here, before the iterations have
+  // updated coords and track_feat in place
+  if ((reinterpret_cast<uintptr_t>(a->track_feat) & 7u) || (reinterpret_cast<uintptr_t>(w->vis_w) & 7u)) return CTK_E_ALIGN;
   return CTK_OK;
 }
 }  // namespace

@@ -51,7 +51,8 @@ __global__ void enc_stem_im2col_kernel(const float* frames /*[F,3,H,W] 0..255*/,
 }
 
 // ---- instance-norm statistics: partial sums per (frame, pixel block, channel) in f64, then the final mean / rstd ---------
-constexpr int ST_ROWS = 512;  // pixels per partial block
+constexpr int ST_ROWS = 512;     // pixels per partial block
+constexpr int ST_MAX_F = 65535;  // frames per call: the frame is blockIdx.y
 __global__ __launch_bounds__(256) void enc_inorm_partial_kernel(const float* x, long HW, int C, int nblk, double* part /*[F][nblk][C][2]*/) {
   const int f = blockIdx.y, b = blockIdx.x, tid = threadIdx.x;
   const int C4 = C / 4, groups = 256 / C4;             // row groups working in parallel on the block's pixels
@@ -61,8 +62,9 @@ __global__ __launch_bounds__(256) void enc_inorm_partial_kernel(const float* x, 
   if (grp < groups) {
     const long p0 = (long)b * ST_ROWS, p1 = min(p0 + ST_ROWS, HW);
     const float* base = x + ((long)f * HW) * C + c4 * 4;
-    // 4 rows in flight per thread (a single dependent load per iteration left the kernel latency-bound at 1.9 TB/s); f32 partial
-    // sums over at most 4 values, f64 beyond
+    // 4 rows in flight per thread (a single dependent load per iteration left the kernel latency-bound at 1.9 TB/s).  Every value
+    // is widened BEFORE it is added: a float32 sum of four values rounds at the scale of 4 |mean|, and var = E[x^2] - mean^2
+    // amplifies that by 2 |mean| (rstd off by 1e-4 .. 1e-2 relative on a channel whose offset is 100 .. 1000 times its spread)
     long p = p0 + grp;
     for (; p + 3 * groups < p1; p += 4 * groups) {
       f32x4 v[4];
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(256) void enc_inorm_partial_kernel(const float* x, 
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(base + (p + (long)u * groups) * C);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        s[e] += (double)((v[0][e] + v[1][e]) + (v[2][e] + v[3][e]));
+        s[e] += ((double)v[0][e] + (double)v[1][e]) + ((double)v[2][e] + (double)v[3][e]);
         ss[e] += (double)v[0][e] * (double)v[0][e] + (double)v[1][e] * (double)v[1][e] + (double)v[2][e] * (double)v[2][e] + (double)v[3][e] * (double)v[3][e];
       }
     }
@@ -219,6 +221,7 @@ __global__ __launch_bounds__(256) void enc_l2norm_kernel(const float* x, long P,
 extern "C" int ctk_enc_stem_im2col(const float* frames, int32_t F, int32_t H, int32_t W, void* out_sh, void* stream) {
   if (!frames || !out_sh) return CTK_E_NULL;
   if (F <= 0 || H < 7 || W < 7) return CTK_E_SHAPE;
+  if (!ctk_aligned16(out_sh)) return CTK_E_ALIGN;  // f16x8 stores
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
   const long total = (long)F * Ho * Wo * 20;
   CtkProfScope ps("enc_stem_im2col", 0.0, 4.0 * (3.0 * F * H * W + 160.0 * F * Ho * Wo), static_cast<hipStream_t>(stream));
@@ -230,14 +233,15 @@ extern "C" int ctk_enc_stem_im2col(const float* frames, int32_t F, int32_t H, in
 
 extern "C" int ctk_enc_inorm_workspace_bytes(int32_t F, int64_t HW, int32_t C, size_t* out_bytes) {
   if (!out_bytes) return CTK_E_NULL;
-  if (F <= 0 || HW <= 0 || C <= 0) return CTK_E_SHAPE;
+  if (F <= 0 || F > ST_MAX_F || HW <= 0 || C <= 0 || (C % 8) || C > 1024) return CTK_E_SHAPE;  // the rules of ctk_enc_inorm_stats
   *out_bytes = (size_t)F * ((HW + ST_ROWS - 1) / ST_ROWS) * C * 2 * sizeof(double);
   return CTK_OK;
 }
 
 extern "C" int ctk_enc_inorm_stats(const float* x, int32_t F, int64_t HW, int32_t C, float eps, float* stats, void* workspace, void* stream) {
   if (!x || !stats || !workspace) return CTK_E_NULL;
-  if (F <= 0 || HW <= 0 || C <= 0 || (C % 8) || C > 1024 || 256 / (C / 4) < 1) return CTK_E_SHAPE;
+  if (F <= 0 || F > ST_MAX_F || HW <= 0 || C <= 0 || (C % 8) || C > 1024 || 256 / (C / 4) < 1) return CTK_E_SHAPE;
+  if (!ctk_aligned16(x) || !ctk_aligned16(workspace)) return CTK_E_ALIGN;  // f32x4 loads; f64 partial sums
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nblk = (int)((HW + ST_ROWS - 1) / ST_ROWS);
   CtkProfScope ps("enc_inorm_stats", 0.0, 4.0 * F * (double)HW * C, s);
@@ -251,8 +255,9 @@ extern "C" int ctk_enc_inorm_stats(const float* x, int32_t F, int64_t HW, int32_
 
 extern "C" int ctk_enc_inorm_apply(const float* x, const float* stats, const float* skip, const float* skip_stats, int32_t F, int64_t HW, int32_t C,
                                    void* out_sh, float* out_f32, void* stream) {
-  if (!x || !stats || (!out_sh && !out_f32)) return CTK_E_NULL;
+  if (!x || !stats || (!out_sh && !out_f32) || (skip_stats && !skip)) return CTK_E_NULL;
   if (F <= 0 || HW <= 0 || C <= 0 || (C % 32)) return CTK_E_SHAPE;
+  if (!ctk_aligned16(x) || !ctk_aligned16(skip) || !ctk_aligned16(out_sh) || !ctk_aligned16(out_f32)) return CTK_E_ALIGN;  // f32x4 / f16x8 accesses
   const long total8 = (long)F * HW * (C / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);
   CtkProfScope ps("enc_inorm_apply", 0.0, 4.0 * F * (double)HW * C * (1.0 + (skip ? 1.0 : 0.0) + (out_sh ? 1.0 : 0.0) + (out_f32 ? 1.0 : 0.0)), s);
@@ -270,10 +275,12 @@ extern "C" int ctk_enc_fuse(const float* const* src, const int32_t* H, const int
   for (int k = 0; k < 4; ++k) {
     if (!src[k]) return CTK_E_NULL;
     if (H[k] <= 0 || W[k] <= 0 || C[k] <= 0 || (C[k] % 8)) return CTK_E_SHAPE;
+    if (!ctk_aligned16(src[k])) return CTK_E_ALIGN;  // f32x4 loads
     p.src[k] = src[k]; p.H[k] = H[k]; p.W[k] = W[k]; p.C[k] = C[k]; p.c0[k] = c0;
     c0 += C[k];
   }
   if (F <= 0 || Ho <= 0 || Wo <= 0 || (c0 % 32)) return CTK_E_SHAPE;
+  if (!ctk_aligned16(out_sh)) return CTK_E_ALIGN;
   p.F = F; p.Ho = Ho; p.Wo = Wo; p.Ctot = c0;
   const long total = (long)F * Ho * Wo * (c0 / 8);
   hipStream_t s = static_cast<hipStream_t>(stream);

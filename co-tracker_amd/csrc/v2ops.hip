@@ -59,8 +59,18 @@ __global__ void v2_assemble_kernel(const float* coords, const float* fcorrs, con
   }
 }
 
+__device__ __forceinline__ double v2_wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // coords[t,n] += delta[n*S+t][0:2]; normed[t*N+n][:] = GroupNorm(1,128)(delta[n*S+t][2:130])  (cotracker.py:157-167)
-// one wavefront per row, 2 channels per lane
+// one wavefront per row, 2 channels per lane.  Two passes in float32.  Deliberate limit (include/ctk.h): the 7-level float32 sum
+// of the mean rounds at the scale of the row's offset, |mean error| <= 2^-21 |mean| (measured ~3e-8 |mean|), so a row of offset
+// 1e3 and spread 1 is ~5e-5 off.  Rows of the update former have offsets of the order of their spread.  An f64 mean was measured:
+// it moves the last bit of most rows, and the 512x512 CoTracker2 parity run (a chaotic map held to 1e-4 logit) then lands at
+// 1.07e-4 instead of 5.8e-5 on the exact-f32 back end -- not taken until that run has headroom.
 __global__ __launch_bounds__(256) void v2_apply_delta_kernel(const float* delta, int out_ld, int S, int N, float* coords,
                                                               const float* gamma, const float* beta, float eps, float* normed) {
   const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // n*S + t
@@ -83,15 +93,17 @@ __global__ __launch_bounds__(256) void v2_apply_delta_kernel(const float* delta,
   *reinterpret_cast<float2*>(normed + tn * V2_C + lane * 2) = o;
 }
 
-// vis[r] = <track_feat[r], w> + b   (vis_predictor, cotracker.py:81-83,172)
+// vis[r] = <track_feat[r], w> + b   (vis_predictor, cotracker.py:81-83,172).  Products and sum in f64: the logit is a small
+// difference of large terms (a float32 sum is off by ~1e-6 sum|tf w|, measured 1.1e-4 on one logit of the 512x512 CoTracker2
+// parity run -- the whole 1e-4 budget); 128 products per row cost nothing here
 __global__ __launch_bounds__(256) void v2_vis_head_kernel(const float* tf, const float* w, const float* b, long R, float* out) {
   const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (row >= R) return;
   const float2 v = *reinterpret_cast<const float2*>(tf + row * V2_C + lane * 2);
   const float2 ww = *reinterpret_cast<const float2*>(w + lane * 2);
-  const float s = ctk_wave_sum(v.x * ww.x + v.y * ww.y);
-  if (lane == 0) out[row] = s + b[0];
+  const double s = v2_wave_sum_f64((double)v.x * (double)ww.x + (double)v.y * (double)ww.y);
+  if (lane == 0) out[row] = (float)(s + (double)b[0]);
 }
 
 // sample_features4d (model_utils.py:258-290) of a channels-last map [H,W,C] at (x, y): bilinear_sampler's 4-D path =
@@ -110,6 +122,8 @@ __global__ void sample4d_kernel(const float* map, int H, int W, int C, const flo
   o = __fmaf_rn(m[((long)ty.i1 * W + tx.i1) * C], __fmul_rn(ty.w1, tx.w1), o);
   out[i] = o;
 }
+
+inline bool v2_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 }  // namespace
 
@@ -131,6 +145,7 @@ extern "C" int ctk_v2_apply_delta(int32_t S, int32_t N, const float* delta, int3
                                   const float* beta, float eps, float* normed, void* stream) {
   if (!delta || !coords || !gamma || !beta || !normed) return CTK_E_NULL;
   if (S <= 0 || N <= 0 || out_ld < 2 + V2_C) return CTK_E_SHAPE;
+  if (!v2_aligned8(normed)) return CTK_E_ALIGN;  // float2 stores (delta is read with scalar loads: any out_ld, any alignment)
   const long rows = (long)S * N;
   hipStream_t s = static_cast<hipStream_t>(stream);
   CtkProfScope ps("v2_apply_delta", 0.0, 4.0 * rows * (out_ld + V2_C), s);
@@ -143,6 +158,7 @@ extern "C" int ctk_v2_apply_delta(int32_t S, int32_t N, const float* delta, int3
 extern "C" int ctk_v2_vis_head(const float* track_feat, int64_t R, const float* w, const float* b, float* out, void* stream) {
   if (!track_feat || !w || !b || !out) return CTK_E_NULL;
   if (R <= 0) return CTK_E_SHAPE;
+  if (!v2_aligned8(track_feat) || !v2_aligned8(w)) return CTK_E_ALIGN;  // float2 loads
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(v2_vis_head_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, track_feat, w, b, (long)R, out);
   CTK_HIP_CHECK_LAUNCH();

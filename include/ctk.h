@@ -80,7 +80,7 @@ enum {
   CTK_OK = 0,
   CTK_E_NULL = -1,      /* required pointer is NULL            */
   CTK_E_SHAPE = -2,     /* size out of range / not supported   */
-  CTK_E_ALIGN = -3,     /* pointer or leading dimension not 16-byte aligned */
+  CTK_E_ALIGN = -3,     /* pointer or leading dimension not aligned (16 bytes unless the entry point says otherwise) */
   CTK_E_WORKSPACE = -4, /* workspace too small                 */
   CTK_E_STATE = -5      /* call not allowed in the current state (e.g. graph capture while the profiler is on) */
 };
@@ -262,7 +262,14 @@ int ctk_update_former_ex(int32_t S, int32_t N, const void* x, int32_t x_split, c
  * ctk_v2_apply_delta: coords[t,n] += delta[n*S+t][0:2]; normed[t*N+n][0:128] = GroupNorm(1,128)(delta[n*S+t][2:130])
  *   (:157-167; the Linear + GELU + residual of track_feat_updater is then one ctk_gemm with resid = C = track_feat).
  * ctk_v2_vis_head: vis_predictor (:172).  ctk_sample_features4d: sample_features4d (model_utils.py:258-290) of a
- *   channels-last map [H,W,C] at (x, y) -> [N,C] (4-D grid_sample semantics; used for pos_emb, :126-130).          */
+ *   channels-last map [H,W,C] at (x, y) -> [N,C] (4-D grid_sample semantics; used for pos_emb, :126-130).
+ * Argument rules (checked before any launch): S, N, R > 0; in_ld >= 456 and in_ld % 32 == 0; out_ld >= 130 (any value: the
+ *   delta rows are read with scalar loads); normed (ctk_v2_apply_delta), track_feat and w (ctk_v2_vis_head) 8-byte aligned,
+ *   CTK_E_ALIGN otherwise (ctk_forward_window_v2 and its workspace / graph entry points check track_feat and vis_w up front).
+ *   ctk_v2_vis_head accumulates its dot product in f64.  ctk_v2_apply_delta is two float32 passes over the row: next to the
+ *   usual 2e-6 max|normed| its result carries the rounding of the float32 row sum, <= 2^-21 |row mean| rstd |gamma| -- a deliberate
+ *   limit, negligible for rows whose offset is of the order of their spread (what the update former produces), 5e-5 of the
+ *   output for an offset of 1e3 times the spread.                                                                           */
 int ctk_v2_assemble(int32_t S, int32_t N, const float* coords, const float* fcorrs, const float* track_feat,
                     const float* track_mask, const float* vis, const float* pos, int32_t in_ld, void* x, int32_t x_split,
                     void* stream);
@@ -358,22 +365,27 @@ int ctk_conv2d_sh(const void* in_sh, int32_t F, int32_t Hin, int32_t Win, int32_
                   const void* zeros, void* stream);
 /* Stem: x = 2*(frame/255) - 1 (cotracker3_online.py:320) and the 7x7 stride-2 pad-3 patches of the 3-channel frames
  * [F,3,H,W] as SH rows of 160 columns ((ky,kx,c) order, 147 used, rest 0): conv1 (blocks.py:150-157) = ctk_conv2d_sh on
- * a [F][Ho][Wo] grid with Cin = 160, 1x1, stride 1.  out_sh: F*Ho*Wo*160*4 bytes, Ho = (H-1)/2+1.                         */
+ * a [F][Ho][Wo] grid with Cin = 160, 1x1, stride 1.  out_sh: F*Ho*Wo*160*4 bytes, 16-byte aligned, Ho = (H-1)/2+1.
+ * F > 0, H >= 7, W >= 7.                                                                                                  */
 int ctk_enc_stem_im2col(const float* frames, int32_t F, int32_t H, int32_t W, void* out_sh, void* stream);
 /* nn.InstanceNorm2d (no affine, eps, biased variance; blocks.py:110-113,147-148) statistics of x f32 [F][HW][C]:
- * stats [F][C][2] = (mean, 1/sqrt(var + eps)), sums in f64 in a fixed order.  workspace: ctk_enc_inorm_workspace_bytes.    */
+ * stats [F][C][2] = (mean, 1/sqrt(var + eps)), sums in f64 in a fixed order.  workspace: ctk_enc_inorm_workspace_bytes
+ * (= F * ceil(HW / 512) * C * 16).  0 < F <= 65535, HW > 0, C % 8 == 0, C <= 1024 (both entry points); x and workspace
+ * 16-byte aligned.                                                                                                         */
 int ctk_enc_inorm_workspace_bytes(int32_t F, int64_t HW, int32_t C, size_t* out_bytes);
 int ctk_enc_inorm_stats(const float* x, int32_t F, int64_t HW, int32_t C, float eps, float* stats, void* workspace, void* stream);
 /* y = relu((x - mean) * rstd)  (blocks.py:130-131, 188-190, 216-217); with skip: out = relu(skip' + y) (blocks.py:138) where
  * skip' = skip, or (skip - mean_s) * rstd_s when skip_stats is given (the 1x1 downsample branch, blocks.py:123-126,133-136).
- * Writes SH (out_sh, the next convolution's input) and / or f32 (out_f32); C % 32 == 0.                                    */
+ * Writes SH (out_sh, the next convolution's input) and / or f32 (out_f32), at least one of them; C % 32 == 0; F, HW > 0;
+ * skip_stats needs skip; x, skip, out_sh and out_f32 16-byte aligned.                                                       */
 int ctk_enc_inorm_apply(const float* x, const float* stats, const float* skip, const float* skip_stats, int32_t F, int64_t HW,
                         int32_t C, void* out_sh, float* out_f32, void* stream);
 /* F.interpolate(., (Ho, Wo), bilinear, align_corners=True) of the four stage outputs (f32 NHWC [F][H_k][W_k][C_k]) and
- * torch.cat over channels (blocks.py:198-215) -> SH [F][Ho][Wo][sum C_k / 32] lines, the input of conv2.                    */
+ * torch.cat over channels (blocks.py:198-215) -> SH [F][Ho][Wo][sum C_k / 32] lines, the input of conv2.  Four sources, none
+ * NULL; H_k, W_k, F, Ho, Wo > 0; C_k % 8 == 0 and sum C_k % 32 == 0; every source and out_sh 16-byte aligned.                */
 int ctk_enc_fuse(const float* const* src, const int32_t* H, const int32_t* W, const int32_t* C, int32_t F, int32_t Ho, int32_t Wo,
                  void* out_sh, void* stream);
-/* fmaps / sqrt(max(sum_c fmaps^2, 1e-12)) on NHWC [P][128] (cotracker3_online.py:384-394).                                  */
+/* fmaps / sqrt(max(sum_c fmaps^2, 1e-12)) on NHWC [P][128] (cotracker3_online.py:384-394).  P > 0; out may be x.                */
 int ctk_enc_l2norm(const float* x, int64_t P, float* out, void* stream);
 
 /* ---- primitives (exported for unit tests and reuse) ------------------------------ */

@@ -1,0 +1,183 @@
+"""Argument validation of the encoder's pixel entry points and the CoTracker2 row entry points (include/ctk.h:
+ctk_enc_stem_im2col, ctk_enc_inorm_workspace_bytes, ctk_enc_inorm_stats, ctk_enc_inorm_apply, ctk_enc_fuse, ctk_enc_l2norm,
+ctk_v2_assemble, ctk_v2_apply_delta, ctk_v2_vis_head), without a GPU: every rule the header documents is refused with its
+CTK_E_* code BEFORE any HIP call.  The pointers below are made-up addresses: every call in this file is invalid in exactly
+one way, so none of them may reach a launch.  The file runs only where no device is visible: there a call that slipped through
+a missing check returns a positive hipError_t, which no assertion here accepts, instead of launching on these addresses."""
+import ctypes as C
+import os
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason="made-up device addresses: only where a stray launch cannot run")
+
+E_NULL, E_SHAPE, E_ALIGN = -1, -2, -3
+P = 0x10000        # a "pointer": non-NULL, 16-byte aligned, never dereferenced
+ODD = P + 8        # 8-byte aligned only
+ODD4 = P + 4       # 4-byte aligned only
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    from cotracker_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        g.build()
+    return _lib.load()
+
+
+def _each_missing(call, good, required):
+    """call(*args) with each required pointer (by position) set to None in turn -> CTK_E_NULL."""
+    for i in required:
+        args = list(good)
+        args[i] = None
+        assert call(*args) == E_NULL, (call.__name__, i)
+
+
+def _with(good, **at):
+    args = list(good)
+    for i, v in at.items():
+        args[int(i[1:])] = v
+    return args
+
+
+def test_abi_version_is_unchanged(lib):
+    assert lib.ctk_abi_version() == 9
+    assert b"aligned" in lib.ctk_error_string(E_ALIGN)
+
+
+def test_stem_im2col_arguments(lib):
+    f = lib.ctk_enc_stem_im2col
+    good = [P, 2, 64, 96, P, None]          # frames, F, H, W, out_sh, stream
+    _each_missing(f, good, (0, 4))
+    for bad in (_with(good, _1=0), _with(good, _1=-1), _with(good, _2=6), _with(good, _3=6), _with(good, _2=0), _with(good, _3=-7)):
+        assert f(*bad) == E_SHAPE, bad
+    assert f(*_with(good, _4=ODD)) == E_ALIGN                   # f16x8 stores
+    assert f(*_with(good, _0=None, _2=6)) == E_NULL             # NULL is reported before the shape
+
+
+def test_inorm_workspace_bytes_arguments(lib):
+    f = lib.ctk_enc_inorm_workspace_bytes
+    n = C.c_size_t(77)
+    assert f(3, 1536, 64, None) == E_NULL
+    for F, HW, Cn in ((0, 1536, 64), (-1, 1536, 64), (65536, 1536, 64), (3, 0, 64), (3, -5, 64), (3, 1536, 0), (3, 1536, 60),
+                      (3, 1536, 1032), (3, 1536, 2048)):
+        assert f(F, HW, Cn, C.byref(n)) == E_SHAPE and n.value == 77, (F, HW, Cn)
+    # the query itself needs no device: F * ceil(HW / 512) * C * 16 bytes (f64 sum and sum of squares per partial block)
+    for F, HW, Cn in ((1, 1, 8), (3, 511, 64), (3, 512, 96), (2, 513, 128), (16, 49152, 256), (65535, 7, 1024)):
+        assert f(F, HW, Cn, C.byref(n)) == 0 and n.value == F * ((HW + 511) // 512) * Cn * 16, (F, HW, Cn, n.value)
+
+
+def test_inorm_stats_arguments(lib):
+    f = lib.ctk_enc_inorm_stats
+    good = [P, 3, 1536, 64, 1e-5, P, P, None]   # x, F, HW, C, eps, stats, workspace, stream
+    _each_missing(f, good, (0, 5, 6))
+    for bad in (_with(good, _1=0), _with(good, _1=65536), _with(good, _2=0), _with(good, _2=-1), _with(good, _3=0), _with(good, _3=-8),
+                _with(good, _3=4), _with(good, _3=68), _with(good, _3=1032), _with(good, _3=4096)):
+        assert f(*bad) == E_SHAPE, bad
+    assert f(*_with(good, _0=ODD)) == E_ALIGN                   # f32x4 loads
+    assert f(*_with(good, _6=ODD)) == E_ALIGN                   # the f64 partial sums
+
+
+def test_inorm_apply_arguments(lib):
+    f = lib.ctk_enc_inorm_apply
+    good = [P, P, P, P, 3, 1536, 64, P, P, None]   # x, stats, skip, skip_stats, F, HW, C, out_sh, out_f32, stream
+    _each_missing(f, good, (0, 1))
+    assert f(*_with(good, _7=None, _8=None)) == E_NULL           # neither output given
+    assert f(*_with(good, _2=None)) == E_NULL                    # skip statistics without a skip
+    for bad in (_with(good, _4=0), _with(good, _5=0), _with(good, _6=0), _with(good, _6=8), _with(good, _6=16), _with(good, _6=48),
+                _with(good, _6=-32)):
+        assert f(*bad) == E_SHAPE, bad
+    for i in (0, 2, 7, 8):                                       # x, skip, out_sh, out_f32: 16-byte vector accesses
+        assert f(*_with(good, **{f"_{i}": ODD})) == E_ALIGN, i
+    assert f(*_with(good, _2=None, _3=None, _8=None, _6=40)) == E_SHAPE   # the optional ones left out: the rest is still checked
+
+
+def test_fuse_arguments(lib):
+    f = lib.ctk_enc_fuse
+
+    def args(src=(P, P, P, P), H=(32, 16, 8, 4), W=(48, 24, 12, 6), Cs=(64, 96, 128, 128), F=2, Ho=16, Wo=24, out=P,
+             null=None):
+        a = [(C.c_void_p * 4)(*src), (C.c_int32 * 4)(*H), (C.c_int32 * 4)(*W), (C.c_int32 * 4)(*Cs), F, Ho, Wo, out, None]
+        if null is not None:
+            a[null] = None
+        return a
+
+    for i in (0, 1, 2, 3, 7):
+        assert f(*args(null=i)) == E_NULL, i
+    for k in range(4):
+        src = [P] * 4
+        src[k] = None
+        assert f(*args(src=src)) == E_NULL, k                    # a NULL source
+        src[k] = ODD
+        assert f(*args(src=src)) == E_ALIGN, k
+        for name, val in (("H", 0), ("W", 0), ("Cs", 0), ("Cs", 4), ("Cs", 100)):
+            v = list(args.__defaults__[("H", "W", "Cs").index(name) + 1])
+            v[k] = val
+            assert f(*args(**{name: v})) == E_SHAPE, (k, name, val)
+    assert f(*args(Cs=(64, 96, 128, 120))) == E_SHAPE            # every C_k % 8 == 0 but the total (408) % 32 != 0
+    assert f(*args(Cs=(8, 8, 8, 16))) == E_SHAPE                 # total 40
+    for kw in ({"F": 0}, {"Ho": 0}, {"Wo": 0}, {"F": -2}):
+        assert f(*args(**kw)) == E_SHAPE, kw
+    assert f(*args(out=ODD)) == E_ALIGN
+
+
+def test_l2norm_arguments(lib):
+    f = lib.ctk_enc_l2norm
+    good = [P, 100, P, None]
+    _each_missing(f, good, (0, 2))
+    assert f(*_with(good, _1=0)) == E_SHAPE and f(*_with(good, _1=-4)) == E_SHAPE
+
+
+def test_v2_assemble_arguments(lib):
+    f = lib.ctk_v2_assemble
+    good = [8, 5, P, P, P, P, P, P, 480, P, 0, None]   # S, N, coords, fcorrs, track_feat, track_mask, vis, pos, in_ld, x, x_split, stream
+    _each_missing(f, good, (2, 3, 4, 5, 6, 7, 9))
+    for bad in (_with(good, _0=0), _with(good, _1=0), _with(good, _0=-8), _with(good, _8=448), _with(good, _8=455), _with(good, _8=456),
+                _with(good, _8=470), _with(good, _8=496 + 8), _with(good, _8=0)):
+        assert f(*bad) == E_SHAPE, bad
+    assert f(*_with(good, _8=456, _10=1)) == E_SHAPE            # 456 % 32 != 0 for the SH output too
+
+
+def test_v2_apply_delta_arguments(lib):
+    f = lib.ctk_v2_apply_delta
+    good = [8, 5, P, 192, P, P, P, 1e-5, P, None]   # S, N, delta, out_ld, coords, gamma, beta, eps, normed, stream
+    _each_missing(f, good, (2, 4, 5, 6, 8))
+    for bad in (_with(good, _0=0), _with(good, _1=0), _with(good, _1=-5), _with(good, _3=129), _with(good, _3=128), _with(good, _3=0)):
+        assert f(*bad) == E_SHAPE, bad
+    assert f(*_with(good, _8=ODD4)) == E_ALIGN                   # float2 stores of the normalised rows: 8 bytes
+
+
+def test_v2_vis_head_arguments(lib):
+    f = lib.ctk_v2_vis_head
+    good = [P, 40, P, P, P, None]   # track_feat, R, w, b, out, stream
+    _each_missing(f, good, (0, 2, 3, 4))
+    assert f(*_with(good, _1=0)) == E_SHAPE and f(*_with(good, _1=-1)) == E_SHAPE
+    assert f(*_with(good, _0=ODD4)) == E_ALIGN and f(*_with(good, _2=ODD4)) == E_ALIGN   # float2 loads: 8 bytes
+
+
+def test_v2_window_refuses_what_its_last_call_would_refuse(lib):
+    """ctk_forward_window_v2 ends with the visibility head; a track_feat or vis_w it would refuse is refused by the window's own
+    validation (shared by the workspace query, the direct call and the graph capture), before an iteration has updated anything."""
+    from cotracker_amd import _lib as L
+    a, w, n = L.V2WindowArgs(), L.V2Weights(), C.c_size_t(0)
+    a.S, a.N, a.iters = 8, 10, 4
+    for l in range(L.LEVELS):
+        a.H[l], a.W[l], a.fmaps[l] = 16 >> l, 24 >> l, P
+    a.coords = a.track_feat = a.vis = a.track_mask = a.vis_out = P
+    w.former.in_dim, w.former.in_ld, w.former.out_dim, w.former.out_ld = 456, 480, 130, 192
+    w.pos_hwc, w.pos_h, w.pos_w = P, 16, 24
+    w.norm_w = w.norm_b = w.upd_w = w.upd_b = w.vis_w = w.vis_b = P
+    query = lib.ctk_forward_window_v2_workspace_bytes
+    a.track_feat = ODD4
+    assert query(C.byref(a), C.byref(w), C.byref(n)) == E_ALIGN
+    assert lib.ctk_forward_window_v2(C.byref(a), C.byref(w), P, 1 << 40, None) == E_ALIGN
+    h = C.c_void_p()
+    assert lib.ctk_v2_window_graph_create(C.byref(a), C.byref(w), P, 1 << 40, C.byref(h)) == E_ALIGN and not h.value
+    a.track_feat, w.vis_w = P, ODD4
+    assert query(C.byref(a), C.byref(w), C.byref(n)) == E_ALIGN
+    assert lib.ctk_forward_window_v2(C.byref(a), C.byref(w), P, 1 << 40, None) == E_ALIGN
+    w.vis_w = ODD        # 8-byte aligned is enough for the float2 loads
+    rc = query(C.byref(a), C.byref(w), C.byref(n))      # a query: no launch
+    assert rc != E_ALIGN
