@@ -22,6 +22,10 @@ VIRT = 64
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH = 0, 1, 2
 ABI_VERSION = 9
 MAX_BATCH = 16  # CTK_MAX_BATCH: videos of one joint window (ctk_forward_window_batch)
+# ctk_window_batch.flags: the B windows are B query groups of ONE video -- the same fmaps pointers in every group, and coords / vis /
+# conf / support[l] / point_mask of group b lying right behind group b - 1 in one allocation each (include/ctk.h).  The library
+# then keeps ONE split-half pyramid copy and launches the correlation sampler once per chunk piece over all groups.
+BATCH_SHARED_FMAPS = 1
 PAD_ZEROS, PAD_BORDER = 0, 1  # ctk_bilinear_sampler padding_mode
 # ctk_set_option keys (include/ctk.h)
 (OPT_GEMM_PP, OPT_GEMM_TAIL_PCT, OPT_CORR_VERSION, OPT_CORR_MAP, OPT_ATTENTION_VALU, OPT_ATTENTION_TIME_PERSISTENT,
@@ -96,8 +100,8 @@ class AttnBatch2(C.Structure):
 
 
 class WindowBatch(C.Structure):
-    """ctk_window_batch: B windows of equal shape for one joint call."""
-    _fields_ = [("B", C.c_int32), ("reserved", C.c_int32), ("videos", C.POINTER(WindowArgs))]
+    """ctk_window_batch: B windows of equal shape for one joint call; flags = 0 or BATCH_SHARED_FMAPS."""
+    _fields_ = [("B", C.c_int32), ("flags", C.c_int32), ("videos", C.POINTER(WindowArgs))]
 
 
 class FormerWeights(C.Structure):
@@ -148,6 +152,8 @@ SYMBOLS = {
     "ctk_forward_window_batch_workspace_bytes": (C.c_int, [_P(WindowBatch), _P(C.c_size_t)]),
     "ctk_forward_window_batch": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, C.c_size_t, _fp]),
     "ctk_window_batch_graph_create": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, C.c_size_t, _P(C.c_void_p)]),
+    "ctk_corr_embed_batch_workspace_bytes": (C.c_int, [_P(WindowBatch), _P(C.c_size_t)]),
+    "ctk_corr_embed_batch": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_window_graph_launch": (C.c_int, [C.c_void_p, _fp]),
     "ctk_window_graph_nodes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "ctk_window_graph_destroy": (C.c_int, [C.c_void_p]),

@@ -9,10 +9,10 @@
 #include <new>
 
 int ctk_launch_corr_volume(const ctk_window_args* a, int n0, int ncount, float* out, long level_stride, int ld,
-                           hipStream_t s);
+                           hipStream_t s, bool groups = false);
 int ctk_launch_pyramid_split(const float* fmap, long pixels, void* out, int version, hipStream_t s);
 int ctk_launch_corr_volume_sh(const ctk_window_args* a, const void* const* fm_sh, int n0, int ncount, void* out,
-                              long level_stride_halves, int version, hipStream_t s);
+                              long level_stride_halves, int version, hipStream_t s, bool groups = false);
 int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream_t s);
 int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, const float* beta, float eps, void* y2, float eps2,
                           int out_split, hipStream_t s);
@@ -363,6 +363,7 @@ struct CorrWs {
   float* vol;  // [4][chunk*S][2432]   (SH format in split mode: same bytes)
   float* h1;   // [4*chunk*S][384]     (SH format in split mode)
   void* fm_sh[CTK_MAX_BATCH][CTK_LEVELS];  // split mode: SH copy of every video's pyramid (scaled by 2^8), [S*H*W][4][2][32] halves
+                                           // (query groups of one video, CTK_BATCH_SHARED_FMAPS: ONE copy, every fm_sh[b] = fm_sh[0])
   size_t bytes;
   int chunk;
   int corr_version;  // CTK_OPT_CORR_VERSION as read ONCE per entry-point call: the layout of fm_sh and the sampler kernel must agree
@@ -376,8 +377,8 @@ int corr_chunk_points(const ctk_window_args* a, int B = 1) {
   return (int)c;
 }
 
-// a = videos[0] of a joint window (the videos agree in every size)
-CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1) {
+// a = videos[0] of a joint window (the videos agree in every size); shared: the B windows are query groups of one video
+CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1, bool shared = false) {
   CorrWs w;
   w.corr_version = ctk_opt(CTK_OPT_CORR_VERSION);
   w.chunk = corr_chunk_points(a, B);
@@ -390,6 +391,10 @@ CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1) {
   off += align256(rows * CTK_LEVELS * CTK_HID * sizeof(float));
   for (int b = 0; b < B; ++b)
     for (int l = 0; l < CTK_LEVELS; ++l) {  // always carved (the size query does not know the weights' mode): ~8 MB per frame
+      if (shared && b > 0) {
+        w.fm_sh[b][l] = w.fm_sh[0][l];
+        continue;
+      }
       w.fm_sh[b][l] = p + off;
       off += align256((size_t)a->S * (a->H[l] > 0 ? a->H[l] : 0) * (a->W[l] > 0 ? a->W[l] : 0) * CTK_C * sizeof(float));
     }
@@ -397,7 +402,8 @@ CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1) {
   return w;
 }
 
-// split mode, once per window: SH copy of the pyramid for the correlation sampler's footprint DMA
+// split mode, once per window: SH copy of the pyramid for the correlation sampler's footprint DMA (B = 1 for query groups of
+// one video: the copy is shared)
 int prepare_pyramid_sh(const ctk_window_args* videos, const CorrWs& ws, hipStream_t s, int B = 1) {
   for (int b = 0; b < B; ++b) {
     const ctk_window_args* a = videos + b;
@@ -416,8 +422,11 @@ int prepare_pyramid_sh(const ctk_window_args* videos, const CorrWs& ws, hipStrea
 // B videos (`videos[0..B)`, equal sizes): the chunk loop walks the STACKED point list g = b*N + n, so corr_mlp is one fc1 and one
 // fc2 launch per chunk over the rows of every video in it; the sampler is launched once per video that owns points of the chunk,
 // into that video's rows of the volume (its grid is already 4 workgroups per point: the single-video kernel, unchanged).
+// shared (CTK_BATCH_SHARED_FMAPS, validated by check_batch): the B windows are query groups of ONE video whose coords / support /
+// point_mask are consecutive slices of one allocation each -- the sampler is then launched ONCE per chunk piece over the
+// stacked points [g0, g0 + pc), in its grouped instantiation (point g reads group g / N's coordinates).
 int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights* w, float* x, bool x_split, const CorrWs& ws,
-                   hipStream_t s) {
+                   hipStream_t s, bool shared = false) {
   const ctk_window_args* a = videos;
   const bool sp = split_mode(w);
   if (x_split && !sp) return CTK_E_SHAPE;
@@ -443,13 +452,18 @@ int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights
       hipStream_t gs = s;
       // stacked points [g0, g0 + pc) -> per video b: its points [m0, m0 + mc), rows (g - g0)*S + t of every level of the volume
       const int g0 = n0 + p0;
-      for (int b = g0 / a->N; b < B && b * a->N < g0 + pc; ++b) {
-        const int lo = g0 > b * a->N ? g0 : b * a->N;
-        const int hi = g0 + pc < (b + 1) * a->N ? g0 + pc : (b + 1) * a->N;
-        const int m0 = lo - b * a->N, mc = hi - lo;
-        float* vb = vol + (size_t)(lo - g0) * a->S * CTK_CORR_LD;  // (an SH row has the bytes of an f32 row)
-        if (sp) CTK_TRY(ctk_launch_corr_volume_sh(videos + b, ws.fm_sh[b], m0, mc, vb, rows * CTK_CORR_LD * 2, ws.corr_version, s));
-        else CTK_TRY(ctk_launch_corr_volume(videos + b, m0, mc, vb, rows * CTK_CORR_LD, CTK_CORR_LD, s));
+      if (shared && B > 1) {  // one grouped launch over the stacked points of every group in the piece
+        if (sp) CTK_TRY(ctk_launch_corr_volume_sh(a, ws.fm_sh[0], g0, pc, vol, rows * CTK_CORR_LD * 2, ws.corr_version, s, true));
+        else CTK_TRY(ctk_launch_corr_volume(a, g0, pc, vol, rows * CTK_CORR_LD, CTK_CORR_LD, s, true));
+      } else {
+        for (int b = g0 / a->N; b < B && b * a->N < g0 + pc; ++b) {
+          const int lo = g0 > b * a->N ? g0 : b * a->N;
+          const int hi = g0 + pc < (b + 1) * a->N ? g0 + pc : (b + 1) * a->N;
+          const int m0 = lo - b * a->N, mc = hi - lo;
+          float* vb = vol + (size_t)(lo - g0) * a->S * CTK_CORR_LD;  // (an SH row has the bytes of an f32 row)
+          if (sp) CTK_TRY(ctk_launch_corr_volume_sh(videos + b, ws.fm_sh[b], m0, mc, vb, rows * CTK_CORR_LD * 2, ws.corr_version, s));
+          else CTK_TRY(ctk_launch_corr_volume(videos + b, m0, mc, vb, rows * CTK_CORR_LD, CTK_CORR_LD, s));
+        }
       }
       if (pipelined && pieces > 1) {
         CTK_TRY(pipe.fork());
@@ -479,6 +493,7 @@ int check_window(const ctk_window_args* a) {
 int check_batch(const ctk_window_batch* bt) {
   if (!bt) return CTK_E_NULL;
   if (bt->B < 1 || bt->B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  if (bt->flags & ~CTK_BATCH_SHARED_FMAPS) return CTK_E_SHAPE;  // unknown flag bits
   if (!bt->videos) return CTK_E_NULL;
   const ctk_window_args* a = bt->videos;
   for (int b = 0; b < bt->B; ++b) CTK_TRY(check_window(a + b));
@@ -491,39 +506,60 @@ int check_batch(const ctk_window_batch* bt) {
     if ((v->point_mask == nullptr) != (a->point_mask == nullptr)) return CTK_E_NULL;
   }
   if ((long)bt->B * (a->N + CTK_VIRT) * a->S > 2000000000L / CTK_MLP * 64) return CTK_E_SHAPE;  // (row counts travel as int)
+  if ((bt->flags & CTK_BATCH_SHARED_FMAPS) && bt->B > 1) {
+    // query groups of one video: the same pyramid, and state / support as consecutive slices of one allocation each -- what
+    // the grouped sampler launch addresses with g = b*N + n (include/ctk.h)
+    const size_t SN = (size_t)a->S * a->N;
+    if (!a->coords || !a->vis || !a->conf) return CTK_E_NULL;
+    for (int l = 0; l < CTK_LEVELS; ++l)
+      if (!a->fmaps[l] || !a->support[l]) return CTK_E_NULL;
+    for (int b = 1; b < bt->B; ++b) {
+      const ctk_window_args* v = a + b;
+      if (!v->coords || !v->vis || !v->conf) return CTK_E_NULL;
+      if (v->coords != a->coords + b * SN * 2 || v->vis != a->vis + b * SN || v->conf != a->conf + b * SN) return CTK_E_SHAPE;
+      for (int l = 0; l < CTK_LEVELS; ++l) {
+        if (!v->support[l]) return CTK_E_NULL;
+        if (v->fmaps[l] != a->fmaps[l]) return CTK_E_SHAPE;
+        if (v->support[l] != a->support[l] + (size_t)b * a->N * CTK_TAPS * CTK_C) return CTK_E_SHAPE;
+      }
+      if (a->point_mask && v->point_mask != a->point_mask + (size_t)b * a->N) return CTK_E_SHAPE;
+    }
+  }
   return CTK_OK;
 }
 
-size_t window_bytes(const ctk_window_args* a, int B) {
+bool shared_fmaps(const ctk_window_batch* bt) { return (bt->flags & CTK_BATCH_SHARED_FMAPS) != 0 && bt->B > 1; }
+
+size_t window_bytes(const ctk_window_args* a, int B, bool shared = false) {
   size_t total = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
   total += carve_uf(a->S, a->N, nullptr, B).bytes;
-  total += carve_corr(a, nullptr, B).bytes;
+  total += carve_corr(a, nullptr, B, shared).bytes;
   return total;
 }
 
-// One window of B videos (validated by the caller): ctk_forward_window is the B == 1 call.
+// One window of B videos (validated by the caller): ctk_forward_window is the B == 1 call.  shared: B query groups of one video.
 int forward_windows(const ctk_window_args* videos, int B, const ctk_model_weights* w, void* workspace, size_t workspace_bytes,
-                    hipStream_t s) {
+                    hipStream_t s, bool shared = false) {
   const ctk_window_args* a = videos;
   for (int b = 0; b < B; ++b)
     if (!videos[b].coords || !videos[b].vis || !videos[b].conf) return CTK_E_NULL;
   if (!workspace) return CTK_E_NULL;
   if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
-  if (window_bytes(a, B) > workspace_bytes) return CTK_E_WORKSPACE;
+  if (window_bytes(a, B, shared) > workspace_bytes) return CTK_E_WORKSPACE;
   char* base = static_cast<char*>(workspace);
   float* x = reinterpret_cast<float*>(base);
   size_t off = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
   const UfWs uws = carve_uf(a->S, a->N, base + off, B);
   off += uws.bytes;
-  const CorrWs cws = carve_corr(a, base + off, B);
+  const CorrWs cws = carve_corr(a, base + off, B, shared);
   const bool sp = split_mode(w);  // split mode: the transformer input x is kept in SH format
   CtkBatchState st{};
   for (int b = 0; b < B; ++b) {
     st.coords[b] = videos[b].coords; st.vis[b] = videos[b].vis; st.conf[b] = videos[b].conf;
   }
-  if (sp && a->iters > 0) CTK_TRY(prepare_pyramid_sh(videos, cws, s, B));
+  if (sp && a->iters > 0) CTK_TRY(prepare_pyramid_sh(videos, cws, s, shared ? 1 : B));
   for (int it = 0; it < a->iters; ++it) {                          // cotracker3_online.py:187
-    CTK_TRY(run_corr_embed(videos, B, w, x, sp, cws, s));          // :190-210
+    CTK_TRY(run_corr_embed(videos, B, w, x, sp, cws, s, shared));  // :190-210
     if (B == 1) CTK_TRY(ctk_assemble_tokens(a, x, sp, s));         // :212-245
     else CTK_TRY(ctk_launch_assemble_batch(st, B, a->S, a->N, a->scale_x, a->scale_y, x, sp, s));
     CTK_TRY(input_projection(a->S, B * a->N, x, sp, w, uws, s));   // :247 + cotracker.py:484
@@ -532,7 +568,7 @@ int forward_windows(const ctk_window_args* videos, int B, const ctk_model_weight
     fr.space_attn = (a->flags & CTK_WINDOW_NO_SPACE_ATTN) == 0;
     fr.B = B;
     // (CoTracker3's point_mask acts through the sampler alone -- it zeroes the support features of not-yet-queried tracks,
-    // cotracker3_online.py:493-496 -- and the sampler is launched per video with that video's mask: fr.point_mask stays null)
+    // cotracker3_online.py:493-496 -- and the sampler reads every point's own mask byte: fr.point_mask stays null)
     CTK_TRY(run_transformer(a->S, a->N, fr, uws, s));              // :250
     if (B == 1) CTK_TRY(ctk_launch_heads(uws.tokens, w->head_w, w->head_b, a->S, a->N, nullptr, a->coords, a->vis, a->conf, s));  // :252-259
     else CTK_TRY(ctk_launch_heads_batch(uws.tokens, w->head_w, w->head_b, st, B, a->S, a->N, s));
@@ -661,7 +697,7 @@ extern "C" int ctk_forward_window(const ctk_window_args* a, const ctk_model_weig
 extern "C" int ctk_forward_window_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes) {
   if (!out_bytes) return CTK_E_NULL;
   CTK_TRY(check_batch(batch));
-  *out_bytes = window_bytes(batch->videos, batch->B);
+  *out_bytes = window_bytes(batch->videos, batch->B, shared_fmaps(batch));
   return CTK_OK;
 }
 
@@ -669,7 +705,27 @@ extern "C" int ctk_forward_window_batch(const ctk_window_batch* batch, const ctk
                                         size_t workspace_bytes, void* stream) {
   CTK_TRY(check_batch(batch));
   CTK_TRY(check_weights(w));
-  return forward_windows(batch->videos, batch->B, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  return forward_windows(batch->videos, batch->B, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream), shared_fmaps(batch));
+}
+
+extern "C" int ctk_corr_embed_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes) {
+  if (!out_bytes) return CTK_E_NULL;
+  CTK_TRY(check_batch(batch));
+  *out_bytes = carve_corr(batch->videos, nullptr, batch->B, shared_fmaps(batch)).bytes;
+  return CTK_OK;
+}
+
+extern "C" int ctk_corr_embed_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* x, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  CTK_TRY(check_batch(batch));
+  if (!w || !x || !workspace) return CTK_E_NULL;
+  if (!ctk_aligned16(workspace) || !ctk_aligned16(x)) return CTK_E_ALIGN;
+  const bool shared = shared_fmaps(batch);
+  const CorrWs ws = carve_corr(batch->videos, workspace, batch->B, shared);
+  if (ws.bytes > workspace_bytes) return CTK_E_WORKSPACE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (split_mode(w)) CTK_TRY(prepare_pyramid_sh(batch->videos, ws, s, shared ? 1 : batch->B));
+  return run_corr_embed(batch->videos, batch->B, w, x, false, ws, s, shared);
 }
 
 // ---- hipGraph of one window (BASELINE.json configs[3]) ------------------------------------------------------
@@ -745,7 +801,7 @@ extern "C" int ctk_window_batch_graph_create(const ctk_window_batch* batch, cons
   if (!workspace) return CTK_E_NULL;
   for (int b = 0; b < batch->B; ++b)
     if (!batch->videos[b].coords || !batch->videos[b].vis || !batch->videos[b].conf) return CTK_E_NULL;
-  if (window_bytes(batch->videos, batch->B) > workspace_bytes) return CTK_E_WORKSPACE;
+  if (window_bytes(batch->videos, batch->B, shared_fmaps(batch)) > workspace_bytes) return CTK_E_WORKSPACE;
   return capture_graph([&](hipStream_t cs) { return ctk_forward_window_batch(batch, w, workspace, workspace_bytes, cs); }, out);
 }
 

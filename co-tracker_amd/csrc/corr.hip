@@ -30,14 +30,18 @@ struct CorrP {
   const float* support[CTK_LEVELS];
   int H[CTK_LEVELS], W[CTK_LEVELS];
   float sx[CTK_LEVELS], sy[CTK_LEVELS];
-  const float* coords;  // [S,N,2]
-  const uint8_t* mask;  // [N] or null
+  const float* coords;  // [S,N,2]  (grouped launch: [B,S,N,2])
+  const uint8_t* mask;  // [N] or null  (grouped: [B*N])
   float* out;           // [L][nchunk*S][ld]
   long out_level_stride;
   int ld;
   int S, N, n0, ncount, tchunks;
 };
 
+// GROUPS: the launch covers the stacked points g = b*N + n of B query groups that share the pyramid (CTK_BATCH_SHARED_FMAPS,
+// include/ctk.h): support [B*N,49,128] and mask [B*N] are indexed by g, the coordinates are [B,S,N,2] -- column
+// g + (g / N) * (S - 1) * N of row t of an [S,N,2] array.  Nothing else differs from the single-video launch.
+template <bool GROUPS>
 __global__ __launch_bounds__(256) void corr_volume_kernel(CorrP p) {
   __shared__ __attribute__((aligned(16))) float sup[64 * SUP_PITCH];
 
@@ -47,6 +51,7 @@ __global__ __launch_bounds__(256) void corr_volume_kernel(CorrP p) {
   const int lvl = bid % CTK_LEVELS;
   const int nl = bid / CTK_LEVELS;  // local point index
   const int n = p.n0 + nl;
+  const int cn = GROUPS ? n + (n / p.N) * (p.S - 1) * p.N : n;  // the point's column in the coordinate rows
   const int t0 = tc * TC;
   const int nt = min(TC, p.S - t0);
   const int rows = nt * CTK_TAPS;
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(256) void corr_volume_kernel(CorrP p) {
     const int rr = r.valid ? ri : rows - 1;
     const int tl = rr / CTK_TAPS, pp = rr - tl * CTK_TAPS;
     const int hx = pp / 7, wy = pp - hx * 7;  // first 7-index = x offset, second = y (cotracker3_online.py:102-104)
-    const float* cptr = p.coords + ((long)(t0 + tl) * p.N + n) * 2;
+    const float* cptr = p.coords + ((long)(t0 + tl) * p.N + cn) * 2;
     const float cx = __fmul_rn(cptr[0], inv), cy = __fmul_rn(cptr[1], inv);
     const CtkTap tx = ctk_tap(__fadd_rn(cx, (float)(hx - 3)), W, sx);
     const CtkTap ty = ctk_tap(__fadd_rn(cy, (float)(wy - 3)), H, sy);
@@ -339,8 +344,9 @@ int fill_corr_params(const ctk_window_args* a, CorrP& p) {
 
 // Internal launcher shared with api.hip: correlation volumes of points [n0, n0+ncount) into
 // out[l][(n-n0)*S + t][ld].
+// groups: a = group 0 of the query groups of one video and [n0, n0+ncount) are stacked points (see corr_volume_kernel).
 int ctk_launch_corr_volume(const ctk_window_args* a, int n0, int ncount, float* out, long level_stride, int ld,
-                           hipStream_t s) {
+                           hipStream_t s, bool groups) {
   CorrP p;
   int rc = fill_corr_params(a, p);
   if (rc) return rc;
@@ -356,7 +362,8 @@ int ctk_launch_corr_volume(const ctk_window_args* a, int n0, int ncount, float* 
   const double units = (double)ncount * a->S * CTK_LEVELS;
   CtkProfScope ps("corr_volume", units * 2.0 * 49 * 49 * 128,
                   units * (64.0 * 128 * 4 + 49.0 * 128 * 4 / a->S + 2.0 + 2401.0 * 4), s);
-  hipLaunchKernelGGL(corr_volume_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+  if (groups) hipLaunchKernelGGL(corr_volume_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(corr_volume_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }
@@ -364,7 +371,7 @@ int ctk_launch_corr_volume(const ctk_window_args* a, int n0, int ncount, float* 
 extern "C" int ctk_corr_volume(const ctk_window_args* a, float* out, void* stream) {
   if (!a) return CTK_E_NULL;
   return ctk_launch_corr_volume(a, 0, a->N, out, (long)a->N * a->S * CTK_CORR_LD, CTK_CORR_LD,
-                                static_cast<hipStream_t>(stream));
+                                static_cast<hipStream_t>(stream), false);
 }
 
 extern "C" int ctk_tap_indices(const ctk_window_args* a, int32_t* out, void* stream) {

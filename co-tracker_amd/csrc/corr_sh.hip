@@ -62,13 +62,23 @@ struct CorrShP {
   const float* support[CTK_LEVELS];
   int H[CTK_LEVELS], W[CTK_LEVELS];
   float sx[CTK_LEVELS], sy[CTK_LEVELS];
-  const float* coords;  // [S,N,2]
-  const uint8_t* mask;  // [N] or null
+  const float* coords;  // [S,N,2]  (grouped launch: [B,S,N,2], the groups' coordinates one behind the other)
+  const uint8_t* mask;  // [N] or null  (grouped: [B*N])
   _Float16* out;        // [L][ncount*S][2*CTK_CORR_LD] halves
   long out_level_stride;
   int S, N, n0, ncount, tchunks;
   int map;  // version 3: workgroup -> (point, level) dealing (CTK_OPT_CORR_MAP), see corr_volume_sh3_kernel
 };
+
+// Query groups over one video (CTK_BATCH_SHARED_FMAPS, include/ctk.h): ONE launch covers the stacked points g = b*N + n of B
+// groups that share the pyramid.  Support patches [B*N,49,128] and the mask [B*N] are indexed by g as they are; only the
+// coordinates carry the group in front of the frame axis ([B,S,N,2]), so point g of frame t sits at column
+// g + (g / N) * (S - 1) * N of row t of an [S,N,2] array.  Everything else -- and so every point's arithmetic -- is the
+// single-video kernel's.
+template <bool GROUPS>
+__device__ __forceinline__ int coord_column(const CorrShP& p, int n) {
+  return GROUPS ? n + (n / p.N) * (p.S - 1) * p.N : n;
+}
 
 struct FrameTab {  // per-frame tap table (LDS), 256 bytes
   int fx0[7], fx1[7], fy0[7], fy1[7];       // tap corner columns / rows relative to the footprint origin
@@ -78,6 +88,7 @@ struct FrameTab {  // per-frame tap table (LDS), 256 bytes
 };
 static_assert(sizeof(FrameTab) == 256, "FrameTab layout");
 
+template <bool GROUPS>
 __global__ __launch_bounds__(256, 2) void corr_volume_sh_kernel(CorrShP p) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS1_BYTES];
   unsigned char* fp = lds;
@@ -114,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void corr_volume_sh_kernel(CorrShP p) {
   const _Float16* fm = p.fm[lvl];
 
   // ---- prologue: coordinates -> LDS; support patch -> split, scaled, swizzled image ------------------------
-  if (tid < 2 * nt) cxy[tid] = p.coords[((long)(t0 + (tid >> 1)) * p.N + n) * 2 + (tid & 1)];
+  if (tid < 2 * nt) cxy[tid] = p.coords[((long)(t0 + (tid >> 1)) * p.N + coord_column<GROUPS>(p, n)) * 2 + (tid & 1)];
   {
     const float* sp = p.support[lvl] + (long)n * CTK_TAPS * CTK_C;
     f32x4 v[7];
@@ -392,10 +403,16 @@ constexpr int LDS3_BYTES = 2 * C_BYTES + 2 * STG_BYTES1 + TAB_BYTES;  // 65920
 static_assert(SUP_BYTES + 15 * 128 <= 2 * C_BYTES, "the support image (prologue only) aliases the C tables");
 static_assert(2 * LDS3_BYTES <= 160 * 1024, "two workgroups per CU");
 
-// DBG (bisection bits; instantiated with DBG != 0 only in dev builds, make dev + CTK_CORR_DBG): 1 = no volume stores, 2 = every lane reads pixel 0 (no footprint traffic), 16 = no MFMAs,
+// MODE & 255 = DBG (bisection bits; instantiated with DBG != 0 only in dev builds, make dev + CTK_CORR_DBG): 1 = no volume stores, 2 = every lane reads pixel 0 (no footprint traffic), 16 = no MFMAs,
 // 32 = no blend, 64 = no store phase at all (no staging reads, no splits)
-template <int DBG>
+// MODE & SH3_GROUPS: the grouped launch over the stacked points of B query groups (coord_column above).  The mode is ONE int so
+// that the production instance keeps its name, corr_volume_sh3_kernel<0>: the ISA checks of __graft_entry__.build() and
+// tests/test_kernel_isa.py look it up by that name, and build() checks corr_volume_sh3_kernel<SH3_GROUPS> beside it.
+constexpr int SH3_GROUPS = 256;
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void corr_volume_sh3_kernel(CorrShP p) {
+  constexpr int DBG = MODE & 255;
+  constexpr bool GROUPS = (MODE & SH3_GROUPS) != 0;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS3_BYTES];
   float* Cb = reinterpret_cast<float*>(lds);                                  // [2][FROWS][CPITCH]
   float* stgb = reinterpret_cast<float*>(lds + 2 * C_BYTES);                  // [2][CTK_CORR_LD]
@@ -462,7 +479,7 @@ __global__ __launch_bounds__(256, 2) void corr_volume_sh3_kernel(CorrShP p) {
   const _Float16* fm = p.fm[lvl];
   const long plane = p.plane[lvl];
   // ---- prologue (as version 1): coordinates -> LDS; support patch -> split, scaled, swizzled image; tap tables ----
-  if (tid < 2 * nt) cxy[tid] = p.coords[((long)(t0 + (tid >> 1)) * p.N + n) * 2 + (tid & 1)];
+  if (tid < 2 * nt) cxy[tid] = p.coords[((long)(t0 + (tid >> 1)) * p.N + coord_column<GROUPS>(p, n)) * 2 + (tid & 1)];
   {
     const float* sp = p.support[lvl] + (long)n * CTK_TAPS * CTK_C;
     f32x4 v[7];
@@ -747,8 +764,10 @@ int ctk_launch_pyramid_split(const float* fmap, long pixels, void* out, int vers
 
 // Correlation volumes of points [n0, n0+ncount) in SH format: out[l][(n-n0)*S + t][2*CTK_CORR_LD halves].
 // fm_sh[l] = ctk_launch_pyramid_split of a->fmaps[l].
+// groups: a = group 0 of the query groups of one video (CTK_BATCH_SHARED_FMAPS; api.hip has checked that the groups' coords /
+// support / point_mask lie one behind the other) and [n0, n0+ncount) are STACKED points g = b*N + n of any of the groups.
 int ctk_launch_corr_volume_sh(const ctk_window_args* a, const void* const* fm_sh, int n0, int ncount, void* out,
-                              long level_stride_halves, int version, hipStream_t s) {
+                              long level_stride_halves, int version, hipStream_t s, bool groups) {
   if (!a || !out) return CTK_E_NULL;
   if (a->S <= 0 || a->N <= 0) return CTK_E_SHAPE;
   CorrShP p;
@@ -787,7 +806,10 @@ int ctk_launch_corr_volume_sh(const ctk_window_args* a, const void* const* fm_sh
   // the order of version 1), 1 / 2 = point pairs, 4 = blocks of 16 points (profiles/r05_sampler_v3_bisect.txt).
   p.map = ctk_opt(CTK_OPT_CORR_MAP);
   const int v = version;  // (the caller read CTK_OPT_CORR_VERSION once, for the pyramid copy and for this launch)
-  if (v == 3) {
+  if (groups) {
+    if (v == 3) hipLaunchKernelGGL(corr_volume_sh3_kernel<SH3_GROUPS>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(corr_volume_sh_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+  } else if (v == 3) {
 #ifdef CTK_DEV
     // dev build only (make dev): CTK_CORR_DBG = bisection bits of version 3 (they change the RESULT: tools/bench_corr.py)
     static const int dbg = [] { const char* e = getenv("CTK_CORR_DBG"); return e ? atoi(e) : 0; }();
@@ -801,7 +823,7 @@ int ctk_launch_corr_volume_sh(const ctk_window_args* a, const void* const* fm_sh
     hipLaunchKernelGGL(corr_volume_sh3_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, p);
 #endif
   } else {
-    hipLaunchKernelGGL(corr_volume_sh_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(corr_volume_sh_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, p);
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

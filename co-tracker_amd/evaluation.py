@@ -26,6 +26,12 @@ def get_uniformly_sampled_pts(size: int, num_frames: int, extent, device="cpu") 
 
 
 class EvaluationPredictor(torch.nn.Module):
+    # single_point mode: evaluated points per model call.  1 (default) = one call per point, as the reference.  G > 1: the query
+    # sets of G points (point + local grid + global grid [+ random points]) go through ONE query-group call of the model
+    # (video [1,...], queries [G,n,3]: the video is encoded once, model.py), the last call takes the remainder.  The sets are
+    # built in the sequential order, so the torch RNG is consumed as before.  Not a reference kwarg: set it after construction.
+    query_group = 1
+
     def __init__(self, cotracker_model, interp_shape: Tuple[int, int] = (384, 512), grid_size: int = 5,
                  local_grid_size: int = 8, single_point: bool = True, sift_size: int = 0,
                  num_uniformly_sampled_pts: int = 0, n_iters: int = 6, local_extent: int = 50) -> None:
@@ -74,13 +80,23 @@ class EvaluationPredictor(torch.nn.Module):
             traj = torch.zeros(B, T, N, 2, device=video.device)
             vis = torch.zeros(B, T, N, device=video.device)
             conf = torch.zeros(B, T, N, device=video.device)
-            for i in range(N):
-                q = queries[:, i:i + 1]
-                q = torch.cat([q] + self._support_queries(video, (float(q[0, 0, 1]), float(q[0, 0, 2]))), dim=1)
-                out = self.model(video=video, queries=q, iters=self.n_iters)
-                traj[:, :, i] = out[0][:, :, 0, :2]
-                vis[:, :, i] = out[1][:, :, 0]
-                conf[:, :, i] = out[2][:, :, 0] if len(out) > 3 else 1.0
+            G = max(1, int(self.query_group))
+            for i0 in range(0, N, G):
+                sets = []
+                for i in range(i0, min(i0 + G, N)):
+                    q = queries[:, i:i + 1]
+                    sets.append(torch.cat([q] + self._support_queries(video, (float(q[0, 0, 1]), float(q[0, 0, 2]))), dim=1))
+                if len(sets) == 1:
+                    out = self.model(video=video, queries=sets[0], iters=self.n_iters)
+                    traj[:, :, i0] = out[0][:, :, 0, :2]
+                    vis[:, :, i0] = out[1][:, :, 0]
+                    conf[:, :, i0] = out[2][:, :, 0] if len(out) > 3 else 1.0
+                else:  # one query-group call: [g,T,n,.] results, the evaluated point is point 0 of its group
+                    g = len(sets)
+                    out = self.model(video=video, queries=torch.cat(sets, dim=0), iters=self.n_iters)
+                    traj[0, :, i0:i0 + g] = out[0][:, :, 0, :2].transpose(0, 1)
+                    vis[0, :, i0:i0 + g] = out[1][:, :, 0].transpose(0, 1)
+                    conf[0, :, i0:i0 + g] = out[2][:, :, 0].transpose(0, 1) if len(out) > 3 else 1.0
             conf = conf if len(out) > 3 else None
         else:  # all queries jointly, plus the global grid / random points
             extra = self._support_queries(video)

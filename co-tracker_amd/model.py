@@ -310,6 +310,10 @@ class TrackerBase(nn.Module):
         # window / iteration chain ONCE for all B videos (ctk_forward_window_batch: one launch per Linear over B times the
         # rows) and the encoder on the B*T frames as one frame batch.  Results are fp32-class equal to "loop", not
         # bit-identical (include/ctk.h).  Not a reference kwarg: set it after construction, like hip_graph and precision.
+        # A query-group call -- video [1,T,3,H,W] with queries [G,N,3], G > 1 -- tracks G independent query sets over the ONE
+        # video: the encoder, the pyramid and the support sampling run once for the call, and the groups' windows run one after
+        # the other ("loop": bit-identical to G separate calls) or as joint windows of up to CTK_MAX_BATCH groups that share the
+        # pyramid ("joint": ctk_window_batch.flags = CTK_BATCH_SHARED_FMAPS).  Returns [G,T,N,.] tensors.  Offline / sliding only.
         self.batch_mode = "loop"
 
     @property
@@ -439,17 +443,22 @@ class TrackerBase(nn.Module):
         assert len(self._online) == B, "batch size changed between online calls"
         return self._online
 
-    def _track(self, video, iters, make_gens, states=None, **window_kw):
+    def _track(self, video, iters, make_gens, states=None, units=None, **window_kw):
         """The one forward path.  make_gens(group) -> one generator per video of `group` (a list of batch indices): one
         video's host code, which yields one window request per window, receives that window's result and returns that video's
         logits (coords, vis[, conf]).  The videos are grouped -- groups of one in "loop" mode, ONE group of B in "joint" mode --
         and each group advances in lock step, all its requests going through one _run_windows call.  The range guard wraps one
         group: "loop" checks every video and re-runs a hit on the exact-f32 back end on its own; "joint" checks the stacked
         outputs once and re-runs the whole batch.  states: the OnlineStates of a streaming call (None: offline / sliding), put
-        back as they were before the re-run.  Returns forward's tuple: (coords, sigmoid of every logit ..., None)."""
-        B = video.shape[0]
+        back as they were before the re-run.  units: the G query groups of a query-group call (one video; see __init__) -- they
+        take the place of the B videos, and "joint" runs them in sub-batches of at most CTK_MAX_BATCH, each under its own
+        range guard.  Returns forward's tuple: (coords, sigmoid of every logit ..., None)."""
+        B = video.shape[0] if units is None else units
         joint = B > 1 and self.batch_mode == "joint"
-        groups = [list(range(B))] if joint else [[b] for b in range(B)]
+        if joint and units is not None:
+            groups = [list(range(g0, min(g0 + L.MAX_BATCH, B))) for g0 in range(0, B, L.MAX_BATCH)]
+        else:
+            groups = [list(range(B))] if joint else [[b] for b in range(B)]
         graphed = bool(states is not None and self.hip_graph)
         # streaming with the window graph (CoTrackerOnlinePredictor): deferred range check, the chunk stream stays asynchronous
         deferred = graphed and len(groups) == 1 and self.stream_range_check == "deferred"
@@ -464,7 +473,10 @@ class TrackerBase(nn.Module):
                 for b, st in zip(group, saved):
                     states[b] = st
             parts.append(self._guarded(run, None if states is None else [replace(states[b]) for b in group], restore, deferred))
-        out = parts[0] if joint else tuple(torch.stack(o) for o in zip(*parts))
+        if joint:
+            out = parts[0] if len(parts) == 1 else tuple(torch.cat(o) for o in zip(*parts))
+        else:
+            out = tuple(torch.stack(o) for o in zip(*parts))
         self.last_logits = out[1:]
         return (out[0], *[torch.sigmoid(o) for o in out[1:]], None)
 
@@ -560,13 +572,18 @@ class CoTrackerThreeBase(TrackerBase):
         g.launch()
         return [w_.keep[2:5] for w_ in g.wins]
 
-    def _run_windows(self, reqs, iters, pw, graphed, space_attn=True):
+    def _run_windows(self, reqs, iters, pw, graphed, space_attn=True, shared=False):
         """One window per request -- (fmaps, support, coords, vis, conf, point_mask or None, owned), one request per video -- all of
         them in ONE call when there are several (joint batch mode).  The window overwrites its coords / vis / conf: a request
-        that is not `owned` hands over state it still needs (the sliding carry-over), so the window gets clones.  Returns every
-        video's (coords, vis, conf)."""
+        that is not `owned` hands over state it still needs (the sliding carry-over), so the window gets clones.  shared: the
+        requests are query groups of one video (the same fmaps): several of them run as one shared-pyramid joint window.
+        Returns every video's (coords, vis, conf)."""
         if graphed:
             return self._graphed_windows(reqs, iters, pw, space_attn)
+        if shared and len(reqs) > 1:
+            wins = self._group_windows(reqs, iters, space_attn)
+            ops.forward_windows(wins, pw, self.max_corr_rows, shared=True)
+            return [w_.keep[2:5] for w_ in wins]
         wins = []
         for fm, support, coords, vis, conf, mask, owned in reqs:
             if not owned:
@@ -578,6 +595,42 @@ class CoTrackerThreeBase(TrackerBase):
         else:
             ops.forward_windows(wins, pw, self.max_corr_rows)
         return [w_.keep[2:5] for w_ in wins]
+
+    def _group_windows(self, reqs, iters, space_attn):
+        """The requests of G query groups over one video as the windows of a shared joint window: the groups' state is stacked
+        into one [G,S,N,.] tensor each (a copy, so nobody's carry-over is overwritten); the support patches are used where they
+        are when they already lie one group behind the other (slices of the one sample_support result of _group_context) and
+        stacked otherwise."""
+        N = reqs[0][2].shape[1]
+
+        def consecutive(parts):
+            step = parts[0].numel() * parts[0].element_size()
+            return all(p_.is_contiguous() and p_.data_ptr() == parts[0].data_ptr() + i * step for i, p_ in enumerate(parts))
+        support = []
+        for l in range(self.corr_levels):
+            parts = [r[1][l] for r in reqs]
+            support.append(torch.cat(parts) if not consecutive(parts) else
+                           parts[0].as_strided((len(parts) * N, *parts[0].shape[1:]), parts[0].stride()))
+        coords, vis, conf = (torch.stack([r[i] for r in reqs]) for i in (2, 3, 4))
+        mask = None if reqs[0][5] is None else torch.stack([r[5] for r in reqs])
+        return ops.group_windows(reqs[0][0], support, coords, vis, conf, self._scale_xy(), point_mask=mask, iters=iters,
+                                 max_corr_rows=self.max_corr_rows, space_attn=space_attn)
+
+    def _group_context(self, video, queries, chunk, pad_to=None):
+        """What the G groups of a query-group call share: the ONE video's level-0 features (padded with the last feature map to a
+        multiple of `pad_to` frames -- the sliding model), the pyramid, and the support patches of all groups from one
+        sample_support per level over the concatenated query list [G*N] (sliced per group by the caller: consecutive slices of
+        one allocation, which is what the shared joint window wants).  The encoder and the support sampler are per frame / per
+        point: every group gets the bits its own call would have computed."""
+        G, N = queries.shape[:2]
+        f0 = self._encode(video.float(), chunk)
+        T = f0.shape[0]
+        if pad_to and T % pad_to:
+            f0 = torch.cat([f0, f0[-1:].expand(pad_to - T % pad_to, -1, -1, -1)], dim=0).contiguous()
+        pyr = ops.build_pyramid(f0, self.corr_levels)
+        qframes, qcoords = self._split_queries(queries.reshape(G * N, 3))
+        support = self._support(pyr, qframes.float().contiguous(), qcoords)
+        return pyr, [[s_[g * N:(g + 1) * N] for s_ in support] for g in range(G)]
 
     # -- shared pieces ------------------------------------------------------------------
     def _scale_xy(self):
@@ -627,13 +680,15 @@ class CoTrackerThreeBase(TrackerBase):
         return [ops.sample_support(pyr[l], frames_f, (qcoords / 2 ** l).contiguous()) for l in range(self.corr_levels)]
 
     def _check_inputs(self, video, queries, is_train, add_space_attn):
-        """-> (B, T, whether this call runs the space attention).  The last is the forward-time flag of the reference
-        (cotracker.py:496-502: `add_space_attn and hasattr(self, "space_virtual_blocks")`)."""
+        """-> (B, T, whether this call runs the space attention, whether it is a query-group call).  The third is the forward-time
+        flag of the reference (cotracker.py:496-502: `add_space_attn and hasattr(self, "space_virtual_blocks")`).  A query-group
+        call is ONE video with G > 1 query sets (queries [G,N,3]): B is then G, the number of result rows."""
         self._check_call(video, is_train)
         B, T, C, H, W = video.shape
         assert H % self.stride == 0 and W % self.stride == 0
-        assert queries.shape[0] == B and queries.shape[2] == 3
-        return B, T, bool(add_space_attn) and self.add_space_attn
+        G = queries.shape[0]
+        assert (G == B or (B == 1 and G > 1)) and queries.shape[2] == 3
+        return G, T, bool(add_space_attn) and self.add_space_attn, G != B
 
 
 class CoTrackerThreeOnline(CoTrackerThreeBase):
@@ -656,18 +711,26 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200,
                 is_online=False):
-        B, T, space_attn = self._check_inputs(video, queries, is_train, add_space_attn)
+        B, T, space_attn, grouped = self._check_inputs(video, queries, is_train, add_space_attn)
         assert self.window_len >= 2
+        if grouped and is_online:
+            raise NotImplementedError("streaming (is_online=True) takes one query set per video: a query-group call (video [1,...], "
+                                      f"queries [{B},...]) is available offline and sliding only")
         states = self._online_states(B, T) if is_online else None
         hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None  # the verdict for THIS call, all batch elements
+        ctx = []  # query-group call: what the groups share, computed once for the call (a range-guard re-run included)
 
         def make_gens(group):
+            if grouped:
+                if not ctx:
+                    ctx.extend(self._group_context(video[0], queries, fmaps_chunk_size, pad_to=self.window_len))
+                return [self._video_gen(video[0], queries[g], fmaps_chunk_size, None, pyr=ctx[0], support=ctx[1][g]) for g in group]
             # joint batch mode: the frames of the whole batch through the encoder as ONE frame batch -- unless every element
             # encodes through its own feature cache (per-video encoder calls)
             f0 = self._encode_batch(video, fmaps_chunk_size) if len(group) > 1 and not (is_online and self.online_feature_cache) else None
             return [self._video_gen(video[b], queries[b], fmaps_chunk_size, states[b] if is_online else None, hint,
                                     None if f0 is None else f0[b]) for b in group]
-        return self._track(video, iters, make_gens, states, space_attn=space_attn)
+        return self._track(video, iters, make_gens, states, units=B if grouped else None, space_attn=space_attn, shared=grouped)
 
     def _encode_online(self, video, chunk, S, step, st, hint):
         """Streaming: consecutive chunks overlap by S - step frames (predictor.py:225,288-290 feeds the last 2*step frames
@@ -700,11 +763,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             st.f0_tail = st.prev_frames = None
         return f0
 
-    def _video_gen(self, video, queries, chunk, st, hint=None, f0=None):
+    def _video_gen(self, video, queries, chunk, st, hint=None, f0=None, pyr=None, support=None):
         """One video's host code as a generator (see _track): yields one request per window, receives that window's (coords,
         vis, conf), returns (coords_pred, vis_pred, conf_pred).  st: this video's OnlineState (streaming: ONE window, at
         st.ind) or None (sliding over all T frames).  f0: this video's level-0 features when the caller has encoded them
-        already (joint batch mode)."""
+        already (joint batch mode).  pyr, support: the (padded) pyramid and this query set's support patches when the caller
+        has them already (one group of a query-group call, sliding only: _group_context)."""
         is_online = st is not None
         T = video.shape[0]
         N = queries.shape[0]
@@ -716,14 +780,15 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         # encoder + pyramid.  The reference pads the *video* by repeating its last frame
         # (:321-328); the encoder is per-frame, so repeating the last feature map is identical.
         pad = (S - T) if is_online else (S - T % S) % S
-        if f0 is not None:
-            if is_online:  # encoded by the caller: this element's feature cache is not fed
-                st.f0_tail = st.prev_frames = None
-        else:
-            f0 = self._encode_online(video, chunk, S, step, st, hint) if is_online else self._encode(video.float(), chunk)
-        if pad > 0:
-            f0 = torch.cat([f0, f0[-1:].expand(pad, -1, -1, -1)], dim=0).contiguous()
-        pyr = ops.build_pyramid(f0, self.corr_levels)
+        if pyr is None:
+            if f0 is not None:
+                if is_online:  # encoded by the caller: this element's feature cache is not fed
+                    st.f0_tail = st.prev_frames = None
+            else:
+                f0 = self._encode_online(video, chunk, S, step, st, hint) if is_online else self._encode(video.float(), chunk)
+            if pad > 0:
+                f0 = torch.cat([f0, f0[-1:].expand(pad, -1, -1, -1)], dim=0).contiguous()
+            pyr = ops.build_pyramid(f0, self.corr_levels)
 
         coords_pred = torch.zeros(T, N, 2, device=dev)
         vis_pred = torch.zeros(T, N, device=dev)
@@ -741,7 +806,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         else:
             frames_rel = qframes.float().contiguous()
 
-        support = self._support(pyr, frames_rel, qcoords)
+        if support is None:
+            support = self._support(pyr, frames_rel, qcoords)
         if is_online:  # :424-440 -- accumulate only the tracks whose query frame is in this chunk (a NEW list: see OnlineState)
             st.track_support = support = [(torch.zeros_like(s_) if acc is None else acc) + s_ * sample_mask
                                           for acc, s_ in zip(st.track_support, support)]
@@ -783,25 +849,34 @@ class CoTrackerThreeOffline(CoTrackerThreeBase):
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200):
-        B, T, space_attn = self._check_inputs(video, queries, is_train, add_space_attn)
+        B, T, space_attn, grouped = self._check_inputs(video, queries, is_train, add_space_attn)
         assert T >= 1
+        ctx = []  # query-group call: what the groups share, computed once for the call (a range-guard re-run included)
 
         def make_gens(group):  # joint batch mode: the B*T frames through the encoder as one frame batch
+            if grouped:
+                if not ctx:
+                    ctx.extend(self._group_context(video[0], queries, fmaps_chunk_size))
+                return [self._video_gen(None, queries[g], fmaps_chunk_size, pyr=ctx[0], support=ctx[1][g]) for g in group]
             f0 = self._encode_batch(video, fmaps_chunk_size) if len(group) > 1 else None
             return [self._video_gen(video[b], queries[b], fmaps_chunk_size, None if f0 is None else f0[b]) for b in group]
-        return self._track(video, iters, make_gens, space_attn=space_attn)
+        return self._track(video, iters, make_gens, units=B if grouped else None, space_attn=space_attn, shared=grouped)
 
-    def _video_gen(self, video, queries, chunk, f0=None):
+    def _video_gen(self, video, queries, chunk, f0=None, pyr=None, support=None):
         """One video's host code (see _track): the single window over all T frames.  f0: its level-0 features [T,H/4,W/4,128]
-        when the caller has encoded them already.  The window carries no point mask and may overwrite the tensors it is given."""
-        if f0 is None:
-            f0 = self._encode(video.float(), chunk)
-        T = f0.shape[0]
-        N = queries.shape[0]
-        dev = f0.device
+        when the caller has encoded them already; pyr, support: the pyramid and this query set's support patches when the caller
+        has them already (one group of a query-group call: _group_context).  The window carries no point mask and may overwrite
+        the tensors it is given."""
         qframes, qcoords = self._split_queries(queries)
-        pyr = ops.build_pyramid(f0, self.corr_levels)
-        support = self._support(pyr, qframes.float().contiguous(), qcoords)
+        if pyr is None:
+            if f0 is None:
+                f0 = self._encode(video.float(), chunk)
+            pyr = ops.build_pyramid(f0, self.corr_levels)
+        T = pyr[0].shape[0]
+        N = queries.shape[0]
+        dev = pyr[0].device
+        if support is None:
+            support = self._support(pyr, qframes.float().contiguous(), qcoords)
         coords = qcoords[None].expand(T, N, 2).contiguous()
         vis = torch.zeros(T, N, device=dev)
         conf = torch.zeros(T, N, device=dev)

@@ -164,10 +164,25 @@ class CoTracker2(TrackerBase):
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, is_online=False):
-        """CoTracker2.forward (cotracker.py:193-384): returns (coords [B,T,N,2] px, vis [B,T,N] post-sigmoid, None)."""
+        """CoTracker2.forward (cotracker.py:193-384): returns (coords [B,T,N,2] px, vis [B,T,N] post-sigmoid, None).
+        A query-group call (video [1,...], queries [G,N,3], G > 1; TrackerBase.__init__) encodes the video once and runs the G
+        query sets one after the other on those features (this model has no joint mode): [G,T,N,.] results, bit-identical to G
+        separate calls.  Sliding only."""
         self._check_call(video, is_train)
         B, T = video.shape[:2]
-        assert self.window_len >= 2
+        G = queries.shape[0]
+        assert self.window_len >= 2 and (G == B or (B == 1 and G > 1))
+        if G != B:
+            if is_online:
+                raise NotImplementedError("streaming (is_online=True) takes one query set per video: a query-group call (video "
+                                          f"[1,...], queries [{G},...]) is available in sliding mode only")
+            f0 = []  # encoded once for the call (a range-guard re-run included)
+
+            def make_gens(group):
+                if not f0:
+                    f0.append(self._encode(video[0]))
+                return [self._video_gen(video[0], queries[g], None, f0[0]) for g in group]
+            return self._track(video, iters, make_gens, units=G)
         states = self._online_states(B, T) if is_online else None
         return self._track(video, iters, lambda group: [self._video_gen(video[b], queries[b], states[b] if is_online else None)
                                                         for b in group], states)
@@ -225,9 +240,10 @@ class CoTracker2(TrackerBase):
             return out
         return self.fnet(2 * (frames.float() / 255.0) - 1.0).float().permute(0, 2, 3, 1).contiguous()
 
-    def _video_gen(self, video, queries, st):
+    def _video_gen(self, video, queries, st, f0=None):
         """One video's host code as a generator (see TrackerBase._track): yields forward_window's arguments per window, receives
-        (coords, vis logits), returns (coords_pred, vis_pred).  st: this video's OnlineState (streaming) or None (sliding)."""
+        (coords, vis logits), returns (coords_pred, vis_pred).  st: this video's OnlineState (streaming) or None (sliding).
+        f0: the video's level-0 features when the caller has encoded them already (a query-group call)."""
         is_online = st is not None
         T, N = video.shape[0], queries.shape[0]
         S, step, dev = self.window_len, self.window_len // 2, video.device
@@ -242,7 +258,8 @@ class CoTracker2(TrackerBase):
             vis_pred = F.pad(st.vis_predicted, (0, 0, 0, p))
         # encoder; padding the video with its last frame (:264-270) == repeating the last feature map (fnet is per-frame)
         pad = (S - T) if is_online else (S - T % S) % S
-        f0 = self._encode(video)  # NHWC, not normalised
+        if f0 is None:
+            f0 = self._encode(video)  # NHWC, not normalised
         if pad > 0:
             f0 = torch.cat([f0, f0[-1:].expand(pad, -1, -1, -1)], dim=0).contiguous()
         pyr = ops.build_pyramid(f0, 4)  # CorrBlock pyramid (blocks.py:300-307) for every frame at once

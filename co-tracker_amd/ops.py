@@ -496,9 +496,13 @@ class V2WindowGraph(WindowGraph):
 class WindowBatch:
     """ctk_window_batch over B Windows of equal shape (S, N, iters, level sizes, scale, flags, mask presence): the
     argument of the joint calls.  ``points_per_chunk`` counts points of the STACKED list of B*N tracks (default: what
-    ``max_corr_rows`` rows of correlation volume hold, as for one window) and is written into wins[0]'s slot of the array."""
+    ``max_corr_rows`` rows of correlation volume hold, as for one window) and is written into wins[0]'s slot of the array.
+    ``shared``: the windows are query groups of ONE video (ctk_window_batch.flags = CTK_BATCH_SHARED_FMAPS) -- the same fmaps
+    in every window, state / support / mask as consecutive slices of one allocation each, which is what ``group_windows``
+    builds; the library checks it and answers anything else with CTK_E_SHAPE."""
 
-    def __init__(self, wins: Sequence[Window], max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None):
+    def __init__(self, wins: Sequence[Window], max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None,
+                 shared: bool = False):
         B = len(wins)
         if not 1 <= B <= L.MAX_BATCH:
             raise ValueError(f"a joint window takes 1..{L.MAX_BATCH} videos, got {B}")
@@ -513,7 +517,7 @@ class WindowBatch:
                 self.arr[b].points_per_chunk = int(ppc)
         elif points_per_chunk is not None:
             self.arr[0].points_per_chunk = int(points_per_chunk)
-        self.struct = L.WindowBatch(B, 0, C.cast(self.arr, C.POINTER(L.WindowArgs)))
+        self.struct = L.WindowBatch(B, L.BATCH_SHARED_FMAPS if shared else 0, C.cast(self.arr, C.POINTER(L.WindowArgs)))
         self.B, self.S, self.N = B, wins[0].S, wins[0].N
         self.device = wins[0].device
 
@@ -521,18 +525,30 @@ class WindowBatch:
         return _query_bytes("ctk_forward_window_batch_workspace_bytes", C.byref(self.struct))
 
 
-def forward_windows(wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None) -> None:
+def group_windows(fmaps: Sequence[torch.Tensor], support: Sequence[torch.Tensor], coords: torch.Tensor, vis: torch.Tensor,
+                  conf: torch.Tensor, scale_xy, point_mask: Optional[torch.Tensor] = None, **window_kw) -> List[Window]:
+    """The G windows of G query groups over ONE video, as ``WindowBatch(..., shared=True)`` takes them: every window points at
+    the same fmaps and at its slice of support[l] [G*N,49,128], coords [G,S,N,2], vis / conf [G,S,N] and point_mask [G,N]."""
+    G, _, N = coords.shape[:3]
+    assert all(s_.shape[0] == G * N for s_ in support) and (point_mask is None or point_mask.shape == (G, N))
+    return [Window(fmaps, [s_[g * N:(g + 1) * N] for s_ in support], coords[g], vis[g], conf[g], scale_xy,
+                   point_mask=None if point_mask is None else point_mask[g], **window_kw) for g in range(G)]
+
+
+def forward_windows(wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None,
+                    shared: bool = False) -> None:
     """ONE joint window call for B videos (ctk_forward_window_batch): `iters` update iterations in place on every
-    win's coords / vis / conf.  One video: exactly forward_window(wins[0])."""
-    batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
+    win's coords / vis / conf.  One video: exactly forward_window(wins[0]).  shared: B query groups of one video (WindowBatch)."""
+    batch = WindowBatch(wins, max_corr_rows, points_per_chunk, shared)
     _run_window("ctk_forward_window_batch", batch.struct, weights.struct_for(batch.S), batch.workspace_bytes(), batch.device)
 
 
 class WindowBatchGraph(WindowGraph):
     """hipGraph of one joint window of B videos (ctk_window_batch_graph_create): the contract of WindowGraph for every win."""
 
-    def __init__(self, wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None):
-        self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk)
+    def __init__(self, wins: Sequence[Window], weights, max_corr_rows: int = 262144, points_per_chunk: Optional[int] = None,
+                 shared: bool = False):
+        self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk, shared)
         self.wins = batch.wins
         self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights, weights.struct_for(batch.S),
                       batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.keep[2:5]], list(batch.arr), batch.device)
@@ -560,6 +576,17 @@ def corr_embed(win: Window, weights, x: Optional[torch.Tensor] = None) -> torch.
     ws = _workspace(_query_bytes("ctk_corr_embed_workspace_bytes", C.byref(win.args)), win.device)
     mw = weights.struct_for(win.S)
     L.check(lib.ctk_corr_embed(C.byref(win.args), C.byref(mw), _ptr(x), _ptr(ws), ws.numel(), _stream()), "ctk_corr_embed")
+    return x
+
+
+def corr_embed_batch(wins: Sequence[Window], weights, points_per_chunk: Optional[int] = None, shared: bool = False) -> torch.Tensor:
+    """corr_embed of a joint window (ctk_corr_embed_batch): x [B*N*S, 1120] f32, row (b*N + n)*S + t, columns [0,1024) written."""
+    batch = WindowBatch(wins, points_per_chunk=points_per_chunk, shared=shared)
+    x = torch.zeros(batch.B * batch.N * batch.S, L.X_LD, device=batch.device, dtype=torch.float32)
+    ws = _workspace(_query_bytes("ctk_corr_embed_batch_workspace_bytes", C.byref(batch.struct)), batch.device)
+    mw = weights.struct_for(batch.S)
+    L.check(L.load().ctk_corr_embed_batch(C.byref(batch.struct), C.byref(mw), _ptr(x), _ptr(ws), ws.numel(), _stream()),
+            "ctk_corr_embed_batch")
     return x
 
 

@@ -58,6 +58,12 @@ class CoTrackerPredictor(torch.nn.Module):
     # True for the default group) the chunks are dealt out over the ranks and all-gathered (sharding.dense_sharded);
     # otherwise they are tracked in sequence on this device, as in the reference.
     dense_group = None
+    # dense mode: chunks per model call.  1 (default) = one call per chunk, as the reference.  G > 1: G chunks go through ONE
+    # query-group call of the model (video [1,...], queries [G,n,3]: resized and encoded once per call, `backward_tracking`
+    # included -- the flipped video is again one video with G groups; model.py), the last call takes the remainder.  Chunk order
+    # and the concatenation along the point axis are unchanged.  One video only, and not together with `dense_group` (both
+    # raise).  Not a reference kwarg: set it after construction.
+    dense_chunks_per_call = 1
 
     def _dense_layout(self, video, grid_size=80):
         H, W = video.shape[-2:]
@@ -74,13 +80,44 @@ class CoTrackerPredictor(torch.nn.Module):
         pts[:, :, 2] = torch.arange(gh, device=video.device).repeat_interleave(gw) * step + offset // step
         return self._compute_sparse_tracks(video=video, queries=pts, backward_tracking=backward_tracking)
 
+    def _dense_chunks(self, video, offsets, grid_query_frame, grid_size=80, backward_tracking=False):
+        """The chunks `offsets` of ONE video as one query-group call; returns them concatenated along the point axis."""
+        H, W = video.shape[-2:]
+        step = W // grid_size
+        gw, gh = W // step, H // step
+        pts = torch.zeros(len(offsets), gw * gh, 3, device=video.device)
+        off = torch.tensor(list(offsets), device=video.device)[:, None]
+        pts[:, :, 0] = grid_query_frame
+        pts[:, :, 1] = torch.arange(gw, device=video.device).repeat(gh)[None] * step + off % step
+        pts[:, :, 2] = torch.arange(gh, device=video.device).repeat_interleave(gw)[None] * step + off // step
+        tracks, vis = self._compute_sparse_tracks(video=video, queries=pts, backward_tracking=backward_tracking)
+        T = tracks.shape[1]
+        return tracks.transpose(0, 1).reshape(1, T, -1, 2), vis.transpose(0, 1).reshape(1, T, -1)
+
     def _compute_dense_tracks(self, video, grid_query_frame, grid_size=80, backward_tracking=False):
+        per_call = max(1, int(self.dense_chunks_per_call))
         if self.dense_group is not None:
+            if per_call > 1:
+                raise NotImplementedError("dense_chunks_per_call > 1 together with dense_group (sharded dense mode) is not implemented: "
+                                          "set one of them")
             from .sharding import dense_sharded
             return dense_sharded(self, video, grid_query_frame, grid_size, backward_tracking,
                                  group=None if self.dense_group is True else self.dense_group)
         tracks = vis = None
-        for offset in range(self._dense_layout(video, grid_size)[0]):
+        n_chunks = self._dense_layout(video, grid_size)[0]
+        if per_call > 1:
+            if video.shape[0] != 1:
+                raise ValueError("dense_chunks_per_call > 1 tracks the chunks of ONE video per model call: video must be [1,T,3,H,W]")
+            for o0 in range(0, n_chunks, per_call):
+                offsets = range(o0, min(o0 + per_call, n_chunks))
+                if len(offsets) == 1:
+                    t_step, v_step = self._dense_chunk(video, offsets[0], grid_query_frame, grid_size, backward_tracking)
+                else:
+                    t_step, v_step = self._dense_chunks(video, offsets, grid_query_frame, grid_size, backward_tracking)
+                tracks = _cat(tracks, t_step, 2)
+                vis = _cat(vis, v_step, 2)
+            return tracks, vis
+        for offset in range(n_chunks):
             t_step, v_step = self._dense_chunk(video, offset, grid_query_frame, grid_size, backward_tracking)
             tracks = _cat(tracks, t_step, 2)
             vis = _cat(vis, v_step, 2)
@@ -126,6 +163,7 @@ class CoTrackerPredictor(torch.nn.Module):
 
         # the query point itself is the prediction at its query frame, and visible (predictor.py:177-185)
         n = tracks.shape[2]
+        B = tracks.shape[0]  # (= queries.shape[0]: the G query groups of a query-group call, dense_chunks_per_call)
         qt = queries[:, :n, 0].long()
         bi = torch.arange(B, device=tracks.device)[:, None].expand(B, n)
         ni = torch.arange(n, device=tracks.device)[None, :].expand(B, n)

@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged): ctk_window_batch.reserved is now `flags` (same offset and size; 0 = as before) with the bit
+ *       CTK_BATCH_SHARED_FMAPS (B query groups over ONE video: one pyramid copy, one grouped sampler launch per chunk piece);
+ *       + ctk_corr_embed_batch and its workspace query (corr_embed of a joint window on its own, for tests).
  *   v9, additive (no existing struct or symbol changed, number unchanged): + ctk_forward_window_batch, its workspace query and
  *       ctk_window_batch_graph_create (joint windows of up to CTK_MAX_BATCH videos); + ctk_attention_ex (two-level batch).
  *   v9 (round 6): + ctk_set_option / ctk_get_option (every back-end choice of the library in one validated, atomic table; the
@@ -194,11 +197,30 @@ int ctk_window_graph_destroy(ctk_window_graph* g);
  * ends).  ctk_window_batch_graph_create captures one such call; the handle is a ctk_window_graph -- launch / nodes / destroy
  * as above -- and bakes in the pointers of every videos[b], of *w and of workspace.
  * A captured graph -- of either kind -- also bakes in the OPTION values (ctk_set_option) read while it was captured:
- * changing an option later does not change what an existing graph runs; re-create the graph.                            */
+ * changing an option later does not change what an existing graph runs; re-create the graph.
+ *
+ * Query groups over ONE video: flags = CTK_BATCH_SHARED_FMAPS.  The B windows are B independent query groups (each with its
+ * own 64 virtual tracks, exactly as B videos) that track over the SAME frames:
+ *   - videos[b].fmaps[l] == videos[0].fmaps[l] for every b and level;
+ *   - the groups' state and support are equally strided slices of ONE allocation each, group b right behind group b - 1:
+ *       videos[b].coords     == videos[0].coords     + b * S*N*2        (floats)
+ *       videos[b].vis / conf == videos[0].vis / conf + b * S*N
+ *       videos[b].support[l] == videos[0].support[l] + b * N*49*128
+ *       videos[b].point_mask == videos[0].point_mask + b * N            (bytes; or NULL in every group)
+ *     i.e. coords [B,S,N,2], vis / conf [B,S,N], support[l] [B*N,49,128], point_mask [B*N];
+ *   anything else is CTK_E_SHAPE (a NULL among those pointers: CTK_E_NULL) before any launch.
+ * The workspace then holds ONE split-half copy of the pyramid instead of B (the size query returns less), converted once per
+ * window, and the correlation sampler -- split-half versions 3 and 1 and the exact-f32 one -- is launched ONCE per chunk piece
+ * over the stacked points g = b*N + n of every group in it (the grouped instantiation of the same kernel body: point g reads
+ * the shared pyramid, support row g and the coordinates of its own group; each point's arithmetic is that of the per-video
+ * launch, so its volume rows are the same bits).  Everything after the sampler is the joint window above, unchanged: the
+ * results are those of the same B windows passed with flags = 0 and aliased fmaps.  B == 1 with the flag is B == 1 without.
+ * Unknown flag bits: CTK_E_SHAPE.                                                                                        */
 #define CTK_MAX_BATCH 16
+#define CTK_BATCH_SHARED_FMAPS 1    /* ctk_window_batch.flags: B query groups of one video (see above) */
 typedef struct ctk_window_batch {
   int32_t B;
-  int32_t reserved;                 /* 0 */
+  int32_t flags;                    /* 0 or CTK_BATCH_SHARED_FMAPS (was `reserved`, 0) */
   const ctk_window_args* videos;    /* [B] */
 } ctk_window_batch;
 int ctk_forward_window_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes);
@@ -206,6 +228,12 @@ int ctk_forward_window_batch(const ctk_window_batch* batch, const ctk_model_weig
                              size_t workspace_bytes, void* stream);
 int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
                                   size_t workspace_bytes, ctk_window_graph** out);
+/* Op A (corr_embed, below) of a joint window on its own: x f32 [B*N*S, CTK_X_LD], row (b*N + n)*S + t, columns [0,1024)
+ * written.  Same validation, chunking and sampler launches as the correlation stage of ctk_forward_window_batch (with or
+ * without CTK_BATCH_SHARED_FMAPS); B == 1 is ctk_corr_embed(&videos[0]).                                                  */
+int ctk_corr_embed_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes);
+int ctk_corr_embed_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* x, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */

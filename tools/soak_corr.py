@@ -6,7 +6,8 @@ version in VERS (interleaved: each leaves its own LDS contents and timing behind
 
 Written in round 5 to corner an intermittent mismatch of version 3 (1 launch in ~30, only in the chunk's second frame, only
 lanes 48..63 of a wave, only the first register of a ds_write2_b32): a v_pk_fma_f32 with op_sel:[0,1,0] right in front of the
-LDS write.  profiles/r05_sampler_v3_pk_hazard.txt has the story.  Env: REPS (3), VERS ("1,3"), QUIET."""
+LDS write.  profiles/r05_sampler_v3_pk_hazard.txt has the story.  Env: REPS (3), VERS ("1,3"), QUIET; WINDOW=c3 (production-shape
+soak of the default sampler) or WINDOW=groups (the grouped launch of a query-group call), LAUNCHES."""
 import collections
 import os
 import sys
@@ -55,6 +56,39 @@ if os.environ.get("WINDOW") == "c3":
     print(f"soak c3 window: S={S} N={N} ({N * 4} workgroups per launch), {n_launch} launches of the default sampler, "
           f"first launch vs exact-f32 sampler max {worst:.3g}; launches that differ bitwise from the first: {len(mism)}")
     sys.exit(1 if mism or worst >= 3e-6 else 0)
+if os.environ.get("WINDOW") == "groups":
+    # The GROUPED launch of a query-group call (ctk_window_batch.flags = CTK_BATCH_SHARED_FMAPS; corr_volume_sh3_kernel<SH3_GROUPS>,
+    # a second instantiation of the default sampler's body): 16 groups of 90 points -- the single-point evaluation shape -- over
+    # one S = 16 window, 5 760 workgroups per launch.  LAUNCHES (500) corr_embed calls with the grouped launch, each compared bit
+    # for bit with the first, and the first with the per-group launches of the same windows (flag 0).  Exit code 1 on a mismatch.
+    from cotracker_amd.model import CoTrackerThreeOffline
+    from cotracker_amd.weights import fill_synthetic_
+    S, H0, W0, G, N = 16, 96, 128, 16, 90
+    n_launch = int(os.environ.get("LAUNCHES", "500"))
+    m = CoTrackerThreeOffline(window_len=S).eval()
+    fill_synthetic_(m, seed=0)
+    pw = m.to(dev).packed(dev)
+    r = np.random.RandomState(11)
+    f0 = torch.from_numpy(r.standard_normal((S, H0, W0, 128)).astype(np.float32)).to(dev)
+    pyr = ops.build_pyramid((f0 / f0.norm(dim=-1, keepdim=True)).contiguous())
+    c = r.uniform(0, 1, size=(G, S, N, 2)) * np.array([W0 - 1, H0 - 1]) + r.uniform(-2, 2, size=(G, S, N, 2))
+    c[:, :, ::13] = np.round(c[:, :, ::13])  # some integer coordinates: 9-wide footprints
+    coords = torch.from_numpy(c.astype(np.float32)).to(dev)
+    qc = coords[:, 0].reshape(G * N, 2).contiguous()
+    sup = [ops.sample_support(pyr[l], torch.zeros(G * N, device=dev), (qc / 2 ** l).contiguous()) for l in range(4)]
+    z = torch.zeros(G, S, N, device=dev)
+    wins = ops.group_windows(pyr, sup, coords, z, z.clone(), (W0, H0), iters=1)
+    first = ops.corr_embed_batch(wins, pw, shared=True).clone()
+    same = torch.equal(first, ops.corr_embed_batch(wins, pw, shared=False))
+    mism = 0
+    for i in range(n_launch):
+        out = ops.corr_embed_batch(wins, pw, shared=True)
+        if not torch.equal(out, first):
+            mism += 1
+            print(f"launch {i}: {int((out != first).sum())} values differ", flush=True)
+    print(f"soak grouped launch: G={G} N={N} S={S} ({G * N * 4} workgroups per launch), {n_launch} launches; grouped == per-group "
+          f"launches: {same}; launches that differ bitwise from the first: {mism}")
+    sys.exit(1 if mism or not same else 0)
 bad = 0
 summary = {}
 launches = 0
