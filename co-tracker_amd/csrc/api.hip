@@ -118,26 +118,36 @@ struct JoinGuard {
   }
 };
 
-// A Linear's weight: torch-layout f32 and/or the ctk_pack_weight blob (preferred when present).
+// A Linear's weight [N][K]: torch-layout f32 and/or the ctk_pack_weight blob (preferred when present).
 struct WRef {
   const float* w;
   const void* p;
 };
 
-// lda / ldc / a_bs / c_bs are given in f32 ELEMENTS of the logical matrix; an SH operand stores two halves
-// per element, so its strides double (a row of K columns = 2K halves).
-int gemm(const float* A, long lda, int M, WRef W, long ldw, int N, int K, float* C, long ldc, const float* bias,
-         int act, const float* resid, long ldr, hipStream_t s, const float* bias_rows = nullptr, int period = 0,
-         int batch = 1, long a_bs = 0, long c_bs = 0, int k_valid = 0, bool a_split = false, bool c_split = false) {
-  ctk_gemm_args g;
-  g.A = A; g.lda = lda; g.M = M; g.W = W.w; g.Wp = W.p; g.ldw = ldw; g.N = N; g.K = K; g.C = C; g.ldc = ldc;
-  g.bias = bias; g.bias_rows = bias_rows; g.bias_period = period; g.resid = resid; g.ldr = ldr; g.act = act;
-  g.batch = batch; g.a_bs = a_bs; g.c_bs = c_bs; g.k_valid = k_valid;
-  g.a_split = a_split; g.c_split = c_split;
-  if (a_split) { g.lda *= 2; g.a_bs *= 2; }
-  if (c_split) { g.ldc *= 2; g.c_bs *= 2; }
-  return ctk_gemm(&g, s);
-}
+// One nn.Linear, y[M][N] = x[M][K] W^T + bias.  The constructor takes what every Linear has and assumes dense rows (x rows K
+// floats apart, y rows N); a call site then names only what distinguishes it.  run() is the one place that finishes
+// ctk_gemm_args: leading dimensions and batch strides are given in f32 ELEMENTS of the logical matrix, and an SH operand
+// stores two halves per element, so its strides double there (a row of K columns = 2K halves).
+struct Linear {
+  ctk_gemm_args g{};
+  Linear(const float* x, long M, WRef W, int N, int K, float* y, const float* bias) {
+    g.A = x; g.lda = K; g.M = (int)M; g.W = W.w; g.Wp = W.p; g.ldw = K; g.N = N; g.K = K; g.C = y; g.ldc = N; g.bias = bias;
+    g.act = CTK_ACT_NONE; g.batch = 1;
+  }
+  Linear& act(int a) { g.act = a; return *this; }
+  Linear& ldy(long ld) { g.ldc = ld; return *this; }                  // y is a column block of a wider matrix
+  Linear& add(const float* resid) { g.resid = resid; return *this; }  // y = ... + resid, resid laid out as y
+  Linear& bias_rows(const float* rows, int period) { g.bias_rows = rows; g.bias_period = period; return *this; }  // + rows[m % period]
+  Linear& k_valid(int k) { g.k_valid = k; return *this; }             // non-padding columns of K (flop accounting only)
+  Linear& batched(int n, long x_bs, long y_bs) { g.batch = n; g.a_bs = x_bs; g.c_bs = y_bs; return *this; }  // n Linears, one W
+  Linear& sh(bool in, bool out) { g.a_split = in; g.c_split = out; return *this; }  // x / y in SH format
+  int run(hipStream_t s) {
+    if (g.resid) g.ldr = g.ldc;
+    if (g.a_split) { g.lda *= 2; g.a_bs *= 2; }
+    if (g.c_split) { g.ldc *= 2; g.c_bs *= 2; }
+    return ctk_gemm(&g, s);
+  }
+};
 
 bool split_mode(const ctk_model_weights* w) { return w->in_p != nullptr; }
 
@@ -202,17 +212,8 @@ int mlp_block(const UfWs& ws, long r0, long R, const ctk_block_weights& b, hipSt
   float* xn = ws.xn + r0 * CTK_HID;
   float* hid = ws.hid + r0 * CTK_MLP;
   CTK_TRY(ctk_layernorm(tok, xn, R, nullptr, nullptr, 1e-6f, sp, s));
-  CTK_TRY(gemm(xn, CTK_HID, (int)R, WRef{b.w1, b.w1_p}, CTK_HID, CTK_MLP, CTK_HID, hid, CTK_MLP, b.b1, CTK_ACT_GELU_TANH, nullptr, 0, s,
-               nullptr, 0, 1, 0, 0, 0, sp, sp));
-  CTK_TRY(gemm(hid, CTK_MLP, (int)R, WRef{b.w2, b.w2_p}, CTK_MLP, CTK_HID, CTK_MLP, tok, CTK_HID, b.b2, CTK_ACT_NONE, tok, CTK_HID, s,
-               nullptr, 0, 1, 0, 0, 0, sp, false));
-  return CTK_OK;
-}
-
-int check_block(const ctk_block_weights& b, bool cross) {
-  if (!b.bq || !b.bkv || !b.bo || !b.b1 || !b.b2) return CTK_E_NULL;
-  if ((!b.wq && !b.wq_p) || (!b.wkv && !b.wkv_p) || (!b.wo && !b.wo_p) || (!b.w1 && !b.w1_p) || (!b.w2 && !b.w2_p)) return CTK_E_NULL;
-  if (cross && (!b.ctx_gamma || !b.ctx_beta)) return CTK_E_NULL;
+  CTK_TRY(Linear(xn, R, {b.w1, b.w1_p}, CTK_MLP, CTK_HID, hid, b.b1).act(CTK_ACT_GELU_TANH).sh(sp, sp).run(s));
+  CTK_TRY(Linear(hid, R, {b.w2, b.w2_p}, CTK_HID, CTK_MLP, tok, b.b2).add(tok).sh(sp, false).run(s));
   return CTK_OK;
 }
 
@@ -254,22 +255,35 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
   const ctk_attn_batch2 vself_b{S, 0, VS, VS, VS, 0, 0};
   const ctk_attn_batch2 p2v_b{S, 0, PS, VS, PS, 0, 0};   // queries / out: point rows, keys: virtual rows
   const long R = P + V;
-  const long QL = 3 * CTK_HID;            // qkv leading dimension
-  float* tok = ws.tokens;
-  float* xn = ws.xn;
-  float* qkv = ws.qkv;
-  float* att = ws.att;
-  CTK_TRY(ctk_launch_virtual_init(w->virtual_tokens, S, tok + P * CTK_HID, B, s));  // cotracker.py:487-488
+  const long QL = 3 * CTK_HID;  // leading dimension of qkv: q | k | v columns
+  // the per-row buffers from one row on: point rows (and "all rows") start at row 0, the virtual rows behind them at row P
+  struct Rows { float *tok, *xn, *att, *q, *k, *v; };
+  auto rows_from = [&](long r) {
+    return Rows{ws.tokens + r * CTK_HID, ws.xn + r * CTK_HID, ws.att + r * CTK_HID, ws.qkv + r * QL, ws.qkv + r * QL + CTK_HID, ws.qkv + r * QL + 2 * CTK_HID};
+  };
+  const Rows pt = rows_from(0), vt = rows_from(P);
+  // The three projections of an attention block.  The four blocks below stay written out: they differ in which rows are
+  // normalised how, where q comes from and on which stream -- more than a shared helper would have parameters for.
+  auto to_q = [&](const ctk_block_weights& b, const float* xn, long rows, const Rows& q, hipStream_t st) {  // q columns of q.q
+    return Linear(xn, rows, {b.wq, b.wq_p}, CTK_HID, CTK_HID, q.q, b.bq).ldy(QL).sh(sp, false).run(st);
+  };
+  auto to_kv = [&](const ctk_block_weights& b, const Rows& kv, long rows) {  // k | v columns of kv.q from kv.xn
+    return Linear(kv.xn, rows, {b.wkv, b.wkv_p}, 2 * CTK_HID, CTK_HID, kv.k, b.bkv).ldy(QL).sh(sp, false).run(s);
+  };
+  auto to_out = [&](const ctk_block_weights& b, const Rows& q, long rows) {  // q.tok += to_out(q.att)
+    return Linear(q.att, rows, {b.wo, b.wo_p}, CTK_HID, CTK_HID, q.tok, b.bo).add(q.tok).sh(sp, false).run(s);
+  };
+  CTK_TRY(ctk_launch_virtual_init(w->virtual_tokens, S, vt.tok, B, s));  // cotracker.py:487-488
 
   for (int i = 0; i < fr.depth; ++i) {
     // ---- time attention over S for every track (incl. virtual)      cotracker.py:494-497
     {
       const ctk_block_weights& b = w->time_blocks[i];
-      CTK_TRY(ctk_layernorm(tok, xn, R, nullptr, nullptr, 1e-6f, sp, s));
-      CTK_TRY(gemm(xn, CTK_HID, (int)R, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(gemm(xn, CTK_HID, (int)R, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv, QL, S, 1, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, S, 1, att, S, 1, B * (N + CTK_VIRT), S, S, 1, nullptr, s, sp));
-      CTK_TRY(gemm(att, CTK_HID, (int)R, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok, CTK_HID, b.bo, CTK_ACT_NONE, tok, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
+      CTK_TRY(ctk_layernorm(pt.tok, pt.xn, R, nullptr, nullptr, 1e-6f, sp, s));
+      CTK_TRY(to_q(b, pt.xn, R, pt, s));
+      CTK_TRY(to_kv(b, pt, R));
+      CTK_TRY(attn(pt.q, QL, S, 1, pt.k, pt.v, QL, S, 1, pt.att, S, 1, B * (N + CTK_VIRT), S, S, 1, nullptr, s, sp));
+      CTK_TRY(to_out(b, pt, R));
       CTK_TRY(mlp_block(ws, 0, R, b, s, sp));
     }
     // The points<-virtual block's query side -- norm1(points) and to_q(points) -- depends only on the point tokens the
@@ -281,55 +295,69 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
     // to_q kernel and the main stream's persistent to_kv kernel each want every CU's whole LDS and serialise)
     const bool side_q = fr.aux != nullptr && (overlap_mode() & 2) != 0;
     JoinGuard side{s, fr.aux};
-    auto side_work = [&]() -> int {
-      const ctk_block_weights& b = w->point2virtual[i];
+    if (side_q) {
       CTK_TRY(side.fork());
-      CTK_TRY(ctk_layernorm(tok, ws.xn2, P, nullptr, nullptr, 1e-6f, sp, fr.aux));                                          // norm1(points)
-      CTK_TRY(gemm(ws.xn2, CTK_HID, (int)P, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv, QL, b.bq, CTK_ACT_NONE, nullptr, 0, fr.aux, nullptr, 0, 1, 0, 0, 0, sp, false));
-      return CTK_OK;
-    };
-    if (side_q) CTK_TRY(side_work());
+      CTK_TRY(ctk_layernorm(pt.tok, ws.xn2, P, nullptr, nullptr, 1e-6f, sp, fr.aux));  // norm1(points)
+      CTK_TRY(to_q(w->point2virtual[i], ws.xn2, P, pt, fr.aux));
+    }
     // ---- virtual <- points cross attention                          cotracker.py:510-512
     {
       const ctk_block_weights& b = w->virtual2point[i];
-      CTK_TRY(ctk_layernorm(tok + P * CTK_HID, xn + P * CTK_HID, V, nullptr, nullptr, 1e-6f, sp, s));   // norm1(virtual)
+      CTK_TRY(ctk_layernorm(vt.tok, vt.xn, V, nullptr, nullptr, 1e-6f, sp, s));   // norm1(virtual)
       // norm_context(points) -- and, from the same read of the point tokens (the virtual-track chain below does not touch them),
       // norm1(points) of this depth's points<-virtual block into xn2 (round 5: one pass, two norms)
-      if (!side_q) CTK_TRY(ctk_launch_layernorm2(tok, xn, P, b.ctx_gamma, b.ctx_beta, 1e-5f, ws.xn2, 1e-6f, sp, s));
-      else CTK_TRY(ctk_layernorm(tok, xn, P, b.ctx_gamma, b.ctx_beta, 1e-5f, sp, s));                   // norm_context(points)
-      CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv + P * QL, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(gemm(xn, CTK_HID, (int)P, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
+      if (!side_q) CTK_TRY(ctk_launch_layernorm2(pt.tok, pt.xn, P, b.ctx_gamma, b.ctx_beta, 1e-5f, ws.xn2, 1e-6f, sp, s));
+      else CTK_TRY(ctk_layernorm(pt.tok, pt.xn, P, b.ctx_gamma, b.ctx_beta, 1e-5f, sp, s));                   // norm_context(points)
+      CTK_TRY(to_q(b, vt.xn, V, vt, s));
+      CTK_TRY(to_kv(b, pt, P));
       // batch = frame t; query i = virtual track (row P + i*S + t); key j = point (row j*S + t)
-      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + CTK_HID, qkv + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, B * S, CTK_VIRT, N,
+      CTK_TRY(attn(vt.q, QL, 1, S, pt.k, pt.v, QL, 1, S, vt.att, 1, S, B * S, CTK_VIRT, N,
                    v2p_splits(N), ws.partial, s, sp, fr.point_mask, nullptr, joint ? &v2p_b : nullptr));  // mask over KEYS (cotracker.py:566-569)
-      CTK_TRY(gemm(att + P * CTK_HID, CTK_HID, (int)V, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok + P * CTK_HID, CTK_HID, b.bo, CTK_ACT_NONE,
-                   tok + P * CTK_HID, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
+      CTK_TRY(to_out(b, vt, V));
       CTK_TRY(mlp_block(ws, P, V, b, s, sp));
     }
     // ---- virtual self attention (AttnBlock over 64 virtual tracks per frame)  cotracker.py:514
     {
       const ctk_block_weights& b = w->virtual_self[i];
-      CTK_TRY(ctk_layernorm(tok + P * CTK_HID, xn + P * CTK_HID, V, nullptr, nullptr, 1e-6f, sp, s));
-      CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv + P * QL, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + P * QL + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv + P * QL, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att + P * CTK_HID, 1, S, B * S,
+      CTK_TRY(ctk_layernorm(vt.tok, vt.xn, V, nullptr, nullptr, 1e-6f, sp, s));
+      CTK_TRY(to_q(b, vt.xn, V, vt, s));
+      CTK_TRY(to_kv(b, vt, V));
+      CTK_TRY(attn(vt.q, QL, 1, S, vt.k, vt.v, QL, 1, S, vt.att, 1, S, B * S,
                    CTK_VIRT, CTK_VIRT, 1, nullptr, s, sp, nullptr, nullptr, joint ? &vself_b : nullptr));
-      CTK_TRY(gemm(att + P * CTK_HID, CTK_HID, (int)V, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok + P * CTK_HID, CTK_HID, b.bo, CTK_ACT_NONE,
-                   tok + P * CTK_HID, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
+      CTK_TRY(to_out(b, vt, V));
       CTK_TRY(mlp_block(ws, P, V, b, s, sp));
     }
     // ---- points <- virtual cross attention                          cotracker.py:515-517
     {
       const ctk_block_weights& b = w->point2virtual[i];
-      CTK_TRY(ctk_layernorm(tok + P * CTK_HID, xn + P * CTK_HID, V, b.ctx_gamma, b.ctx_beta, 1e-5f, sp, s));           // norm_context(virtual)
-      if (!side_q) CTK_TRY(gemm(ws.xn2, CTK_HID, (int)P, WRef{b.wq, b.wq_p}, CTK_HID, CTK_HID, CTK_HID, qkv, QL, b.bq, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));  // xn2 = norm1(points), written beside norm_context(points) above
+      CTK_TRY(ctk_layernorm(vt.tok, vt.xn, V, b.ctx_gamma, b.ctx_beta, 1e-5f, sp, s));           // norm_context(virtual)
+      if (!side_q) CTK_TRY(to_q(b, ws.xn2, P, pt, s));  // xn2 = norm1(points), written beside norm_context(points) above
       else CTK_TRY(side.join());  // join: q(points) is ready
-      CTK_TRY(gemm(xn + P * CTK_HID, CTK_HID, (int)V, WRef{b.wkv, b.wkv_p}, CTK_HID, 2 * CTK_HID, CTK_HID, qkv + P * QL + CTK_HID, QL, b.bkv, CTK_ACT_NONE, nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, sp, false));
-      CTK_TRY(attn(qkv, QL, 1, S, qkv + P * QL + CTK_HID, qkv + P * QL + 2 * CTK_HID, QL, 1, S, att, 1, S, B * S, N, CTK_VIRT, 1, nullptr, s, sp,
+      CTK_TRY(to_kv(b, vt, V));
+      CTK_TRY(attn(pt.q, QL, 1, S, vt.k, vt.v, QL, 1, S, pt.att, 1, S, B * S, N, CTK_VIRT, 1, nullptr, s, sp,
                    nullptr, fr.point_mask, joint ? &p2v_b : nullptr));  // mask over QUERIES (cotracker.py:561-564)
-      CTK_TRY(gemm(att, CTK_HID, (int)P, WRef{b.wo, b.wo_p}, CTK_HID, CTK_HID, CTK_HID, tok, CTK_HID, b.bo, CTK_ACT_NONE, tok, CTK_HID, s, nullptr, 0, 1, 0, 0, 0, sp, false));
+      CTK_TRY(to_out(b, pt, P));
       CTK_TRY(mlp_block(ws, 0, P, b, s, sp));
     }
+  }
+  return CTK_OK;
+}
+
+// Every block of a former: the pointers its launches read; packed blobs all-or-nothing (fr.split: the SH activation pipeline
+// needs every Linear of the transformer split, the f32 pipeline none)
+int check_former(const FormerRef& fr) {
+  auto check_block = [&](const ctk_block_weights& b, bool cross) {
+    if (!b.bq || !b.bkv || !b.bo || !b.b1 || !b.b2) return CTK_E_NULL;
+    if ((!b.wq && !b.wq_p) || (!b.wkv && !b.wkv_p) || (!b.wo && !b.wo_p) || (!b.w1 && !b.w1_p) || (!b.w2 && !b.w2_p)) return CTK_E_NULL;
+    if (cross && (!b.ctx_gamma || !b.ctx_beta)) return CTK_E_NULL;
+    const bool all_p = b.wq_p && b.wkv_p && b.wo_p && b.w1_p && b.w2_p, any_p = b.wq_p || b.wkv_p || b.wo_p || b.w1_p || b.w2_p;
+    return (fr.split ? !all_p : any_p) ? CTK_E_NULL : CTK_OK;
+  };
+  for (int i = 0; i < fr.depth; ++i) {
+    CTK_TRY(check_block(fr.time_blocks[i], false));
+    CTK_TRY(check_block(fr.virtual2point[i], true));
+    CTK_TRY(check_block(fr.virtual_self[i], false));
+    CTK_TRY(check_block(fr.point2virtual[i], true));
   }
   return CTK_OK;
 }
@@ -337,25 +365,15 @@ int run_transformer(int S, int N, const FormerRef& fr, const UfWs& ws, hipStream
 int check_weights(const ctk_model_weights* w) {
   if (!w) return CTK_E_NULL;
   if ((!w->in_w && !w->in_p) || !w->in_bias_t || !w->virtual_tokens || !w->head_w || !w->head_b) return CTK_E_NULL;
-  const bool sp = split_mode(w);  // packed blobs are all-or-nothing: the SH activation pipeline needs every Linear split
-  auto bad = [sp](const ctk_block_weights& b) { return sp != (b.wq_p && b.wkv_p && b.wo_p && b.w1_p && b.w2_p) || (!sp && (b.wq_p || b.wkv_p || b.wo_p || b.w1_p || b.w2_p)); };
-  if (sp != (w->corr_fc1_p && w->corr_fc2_p)) return CTK_E_NULL;
-  for (int i = 0; i < CTK_DEPTH; ++i)
-    if (bad(w->time_blocks[i]) || bad(w->virtual2point[i]) || bad(w->virtual_self[i]) || bad(w->point2virtual[i])) return CTK_E_NULL;
-  for (int i = 0; i < CTK_DEPTH; ++i) {
-    CTK_TRY(check_block(w->time_blocks[i], false));
-    CTK_TRY(check_block(w->virtual2point[i], true));
-    CTK_TRY(check_block(w->virtual_self[i], false));
-    CTK_TRY(check_block(w->point2virtual[i], true));
-  }
-  return CTK_OK;
+  if (split_mode(w) != (w->corr_fc1_p && w->corr_fc2_p)) return CTK_E_NULL;  // (corr_mlp belongs to the same pipeline)
+  return check_former(former_of(w));
 }
 
 // N = point tracks of ALL videos of the call (the per-frame bias is indexed by row % S: rows are track-major in every video)
 int input_projection(int S, int N, const float* x, bool x_split, const ctk_model_weights* w, const UfWs& ws, hipStream_t s) {
   // tokens = input_transform(x + time_emb)   (cotracker3_online.py:247, cotracker.py:484)
-  return gemm(x, CTK_X_LD, N * S, WRef{w->in_w, w->in_p}, CTK_X_LD, CTK_HID, CTK_X_LD, ws.tokens, CTK_HID, nullptr, CTK_ACT_NONE, nullptr, 0,
-              s, w->in_bias_t, S, 1, 0, 0, CTK_X_DIM, x_split, false);
+  return Linear(x, N * S, {w->in_w, w->in_p}, CTK_HID, CTK_X_LD, ws.tokens, nullptr)
+      .bias_rows(w->in_bias_t, S).k_valid(CTK_X_DIM).sh(x_split, false).run(s);
 }
 
 // ---- corr_embed workspace -------------------------------------------------------------------
@@ -470,11 +488,11 @@ int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights
         gs = aux;
       }
       // corr_mlp.fc1 + exact GELU over all 4 levels at once        cotracker3_online.py:205, blocks.py:71-72
-      CTK_TRY(gemm(vol, CTK_CORR_LD, (int)(rows * CTK_LEVELS), WRef{w->corr_fc1_w, w->corr_fc1_p}, CTK_CORR_LD, CTK_HID, CTK_CORR_LD, h1, CTK_HID,
-                   w->corr_fc1_b, CTK_ACT_GELU_ERF, nullptr, 0, gs, nullptr, 0, 1, 0, 0, CTK_CORR_K, sp, sp));
+      CTK_TRY(Linear(vol, rows * CTK_LEVELS, {w->corr_fc1_w, w->corr_fc1_p}, CTK_HID, CTK_CORR_LD, h1, w->corr_fc1_b)
+                  .act(CTK_ACT_GELU_ERF).k_valid(CTK_CORR_K).sh(sp, sp).run(gs));
       // corr_mlp.fc2, one batch per level, written into x[g*S+t][l*256 ...]   (torch.cat :209)
-      CTK_TRY(gemm(h1, CTK_HID, (int)rows, WRef{w->corr_fc2_w, w->corr_fc2_p}, CTK_HID, 256, CTK_HID, x + (long)g0 * a->S * CTK_X_LD + CTK_X_CORR,
-                   CTK_X_LD, w->corr_fc2_b, CTK_ACT_NONE, nullptr, 0, gs, nullptr, 0, CTK_LEVELS, rows * CTK_HID, 256, 0, sp, x_split));
+      CTK_TRY(Linear(h1, rows, {w->corr_fc2_w, w->corr_fc2_p}, 256, CTK_HID, x + (long)g0 * a->S * CTK_X_LD + CTK_X_CORR, w->corr_fc2_b)
+                  .ldy(CTK_X_LD).batched(CTK_LEVELS, rows * CTK_HID, 256).sh(sp, x_split).run(gs));
     }
     if (pipelined && pieces > 1) CTK_TRY(pipe.join());  // join before the next chunk reuses the buffers / x is consumed
   }
@@ -528,6 +546,13 @@ int check_batch(const ctk_window_batch* bt) {
   return CTK_OK;
 }
 
+// the window state every video of a call updates in place
+bool has_state(const ctk_window_args* videos, int B) {
+  for (int b = 0; b < B; ++b)
+    if (!videos[b].coords || !videos[b].vis || !videos[b].conf) return false;
+  return true;
+}
+
 bool shared_fmaps(const ctk_window_batch* bt) { return (bt->flags & CTK_BATCH_SHARED_FMAPS) != 0 && bt->B > 1; }
 
 size_t window_bytes(const ctk_window_args* a, int B, bool shared = false) {
@@ -541,9 +566,7 @@ size_t window_bytes(const ctk_window_args* a, int B, bool shared = false) {
 int forward_windows(const ctk_window_args* videos, int B, const ctk_model_weights* w, void* workspace, size_t workspace_bytes,
                     hipStream_t s, bool shared = false) {
   const ctk_window_args* a = videos;
-  for (int b = 0; b < B; ++b)
-    if (!videos[b].coords || !videos[b].vis || !videos[b].conf) return CTK_E_NULL;
-  if (!workspace) return CTK_E_NULL;
+  if (!has_state(videos, B) || !workspace) return CTK_E_NULL;
   if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
   if (window_bytes(a, B, shared) > workspace_bytes) return CTK_E_WORKSPACE;
   char* base = static_cast<char*>(workspace);
@@ -624,25 +647,18 @@ extern "C" int ctk_update_former_ex(int32_t S, int32_t N, const void* x, int32_t
   if (!w->time_blocks || !w->virtual2point || !w->virtual_self || !w->point2virtual) return CTK_E_NULL;
   const bool sp = w->in_p != nullptr;
   if (x_split && !sp) return CTK_E_SHAPE;
-  for (int i = 0; i < w->depth; ++i) {
-    CTK_TRY(check_block(w->time_blocks[i], false));
-    CTK_TRY(check_block(w->virtual2point[i], true));
-    CTK_TRY(check_block(w->virtual_self[i], false));
-    CTK_TRY(check_block(w->point2virtual[i], true));
-    if (sp != (w->time_blocks[i].wq_p != nullptr)) return CTK_E_NULL;
-  }
+  const FormerRef fr{w->depth, w->time_blocks, w->virtual2point, w->virtual_self, w->point2virtual, w->virtual_tokens, point_mask, sp, nullptr};
+  CTK_TRY(check_former(fr));
   if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
   const UfWs ws = carve_uf(S, N, workspace);
   if (ws.bytes > workspace_bytes) return CTK_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   // tokens = input_transform(x) (+ per-frame bias rows = W e_t + b when in_bias_t is given, else + in_b)
-  CTK_TRY(gemm(static_cast<const float*>(x), w->in_ld, N * S, WRef{w->in_w, w->in_p}, w->in_ld, CTK_HID, w->in_ld, ws.tokens, CTK_HID,
-               w->in_bias_t ? nullptr : w->in_b, CTK_ACT_NONE, nullptr, 0, s, w->in_bias_t, S, 1, 0, 0, w->in_dim, x_split != 0, false));
-  const FormerRef fr{w->depth, w->time_blocks, w->virtual2point, w->virtual_self, w->point2virtual, w->virtual_tokens, point_mask, sp, nullptr};
+  CTK_TRY(Linear(static_cast<const float*>(x), N * S, {w->in_w, w->in_p}, CTK_HID, w->in_ld, ws.tokens, w->in_bias_t ? nullptr : w->in_b)
+              .bias_rows(w->in_bias_t, S).k_valid(w->in_dim).sh(x_split != 0, false).run(s));
   CTK_TRY(run_transformer(S, N, fr, ws, s));
   // heads: delta[n*S+t][0..out_ld) = tokens @ head_w^T + head_b   (flow_head, cotracker.py:526)
-  return gemm(ws.tokens, CTK_HID, N * S, WRef{w->head_w, w->head_p}, CTK_HID, w->out_ld, CTK_HID, delta, w->out_ld, w->head_b, CTK_ACT_NONE,
-              nullptr, 0, s, nullptr, 0, 1, 0, 0, 0, false, false);
+  return Linear(ws.tokens, N * S, {w->head_w, w->head_p}, w->out_ld, CTK_HID, delta, w->head_b).run(s);
 }
 
 extern "C" int ctk_corr_embed_workspace_bytes(const ctk_window_args* a, size_t* out_bytes) {
@@ -773,36 +789,35 @@ int capture_graph(F enqueue, ctk_window_graph** out) {
   *out = g;
   return CTK_OK;
 }
+
+// The three *_graph_create entry points.  valid(): the call's host-only validation -- everything its forward call would refuse
+// is said before the capture machinery is touched; bytes(): its workspace size; enqueue(stream): that forward call.
+template <typename V, typename B, typename F>
+int graph_create(void* workspace, size_t workspace_bytes, ctk_window_graph** out, V valid, B bytes, F enqueue) {
+  if (!out) return CTK_E_NULL;
+  *out = nullptr;
+  if (ctk_profile_is_on()) return CTK_E_STATE;
+  CTK_TRY(valid());
+  if (!workspace) return CTK_E_NULL;
+  if (bytes() > workspace_bytes) return CTK_E_WORKSPACE;
+  return capture_graph(enqueue, out);
+}
 }  // namespace
 
 extern "C" int ctk_window_graph_create(const ctk_window_args* a, const ctk_model_weights* w, void* workspace,
                                        size_t workspace_bytes, ctk_window_graph** out) {
-  if (!out) return CTK_E_NULL;
-  *out = nullptr;
-  if (ctk_profile_is_on()) return CTK_E_STATE;
-  // validate before touching the capture machinery (ctk_forward_window repeats these checks)
-  CTK_TRY(check_window(a));
-  CTK_TRY(check_weights(w));
-  if (!workspace || !a->coords || !a->vis || !a->conf) return CTK_E_NULL;
-  size_t need = 0;
-  CTK_TRY(ctk_forward_window_workspace_bytes(a, &need));
-  if (need > workspace_bytes) return CTK_E_WORKSPACE;
-  return capture_graph([&](hipStream_t cs) { return ctk_forward_window(a, w, workspace, workspace_bytes, cs); }, out);
+  auto valid = [&]() -> int { CTK_TRY(check_window(a)); CTK_TRY(check_weights(w)); return has_state(a, 1) ? CTK_OK : CTK_E_NULL; };
+  auto bytes = [&] { return window_bytes(a, 1); };
+  auto enqueue = [&](hipStream_t cs) { return ctk_forward_window(a, w, workspace, workspace_bytes, cs); };
+  return graph_create(workspace, workspace_bytes, out, valid, bytes, enqueue);
 }
 
 extern "C" int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
                                              size_t workspace_bytes, ctk_window_graph** out) {
-  if (!out) return CTK_E_NULL;
-  *out = nullptr;
-  if (ctk_profile_is_on()) return CTK_E_STATE;
-  // validate before touching the capture machinery (ctk_forward_window_batch repeats these checks)
-  CTK_TRY(check_batch(batch));
-  CTK_TRY(check_weights(w));
-  if (!workspace) return CTK_E_NULL;
-  for (int b = 0; b < batch->B; ++b)
-    if (!batch->videos[b].coords || !batch->videos[b].vis || !batch->videos[b].conf) return CTK_E_NULL;
-  if (window_bytes(batch->videos, batch->B, shared_fmaps(batch)) > workspace_bytes) return CTK_E_WORKSPACE;
-  return capture_graph([&](hipStream_t cs) { return ctk_forward_window_batch(batch, w, workspace, workspace_bytes, cs); }, out);
+  auto valid = [&]() -> int { CTK_TRY(check_batch(batch)); CTK_TRY(check_weights(w)); return has_state(batch->videos, batch->B) ? CTK_OK : CTK_E_NULL; };
+  auto bytes = [&] { return window_bytes(batch->videos, batch->B, shared_fmaps(batch)); };
+  auto enqueue = [&](hipStream_t cs) { return ctk_forward_window_batch(batch, w, workspace, workspace_bytes, cs); };
+  return graph_create(workspace, workspace_bytes, out, valid, bytes, enqueue);
 }
 
 // ---- CoTracker2 window driver (cotracker.py:86-173): one capture-safe call per window --------------------------
@@ -886,21 +901,18 @@ extern "C" int ctk_forward_window_v2(const ctk_v2_window_args* a, const ctk_v2_w
     CTK_TRY(ctk_update_former_ex(S, N, ws.x, x_split, fw, a->point_mask, ws.delta, ws.former, ws.former_bytes, stream));  // :152-155
     CTK_TRY(ctk_v2_apply_delta(S, N, ws.delta, fw->out_ld, a->coords, w->norm_w, w->norm_b, 1e-5f, ws.normed, stream));  // :157-159,167
     // track_feat += GELU(Linear(GroupNorm(delta_feats)))   (track_feat_updater, cotracker.py:162-170), rows t*N+n
-    CTK_TRY(gemm(ws.normed, CTK_C, S * N, WRef{w->upd_w, w->upd_p}, CTK_C, CTK_C, CTK_C, a->track_feat, CTK_C, w->upd_b, CTK_ACT_GELU_ERF,
-                 a->track_feat, CTK_C, static_cast<hipStream_t>(stream)));
+    CTK_TRY(Linear(ws.normed, S * N, {w->upd_w, w->upd_p}, CTK_C, CTK_C, a->track_feat, w->upd_b)
+                .act(CTK_ACT_GELU_ERF).add(a->track_feat).run(static_cast<hipStream_t>(stream)));
   }
   return ctk_v2_vis_head(a->track_feat, (int64_t)S * N, w->vis_w, w->vis_b, a->vis_out, stream);   // :172
 }
 
 extern "C" int ctk_v2_window_graph_create(const ctk_v2_window_args* a, const ctk_v2_weights* w, void* workspace,
                                           size_t workspace_bytes, ctk_window_graph** out) {
-  if (!out) return CTK_E_NULL;
-  *out = nullptr;
-  if (ctk_profile_is_on()) return CTK_E_STATE;
-  CTK_TRY(check_v2(a, w));
-  if (!workspace) return CTK_E_NULL;
-  if (carve_v2(a, w, nullptr).bytes > workspace_bytes) return CTK_E_WORKSPACE;
-  return capture_graph([&](hipStream_t cs) { return ctk_forward_window_v2(a, w, workspace, workspace_bytes, cs); }, out);
+  auto valid = [&]() -> int { return check_v2(a, w); };
+  auto bytes = [&] { return carve_v2(a, w, nullptr).bytes; };
+  auto enqueue = [&](hipStream_t cs) { return ctk_forward_window_v2(a, w, workspace, workspace_bytes, cs); };
+  return graph_create(workspace, workspace_bytes, out, valid, bytes, enqueue);
 }
 
 extern "C" int ctk_window_graph_launch(ctk_window_graph* g, void* stream) {

@@ -21,11 +21,9 @@
 //    40 halves (80 B): the 16 lanes of a ds_read_b128 group hit 16 distinct 16-byte bank groups.
 //    Double-buffered LDS, one barrier per K-tile, next tile's global loads issued before the MFMAs.
 #include "ctk_common.h"
-#include "ctk_options.h"
 #include "ctk_profile.h"
 #include "gemm_params.h"
 #include <cstdio>
-#include <cstdlib>
 
 namespace {
 
@@ -99,13 +97,11 @@ __device__ __forceinline__ void gemm_epilogue(const CtkGemmP& g, f32x16 (&acc)[M
 // For the 12-K-tile Linears of the transformer (K = 384) the epilogue, not the MFMA loop, is the bulk of a wave's
 // instruction stream (SQ counters, profiles/r01_gemm_sh_sq_counters.txt: fc1 issues ~2350 VALU per wave there vs
 // ~530 in its main loop), and an epilogue wave keeps its SIMD's MFMA pipe idle unless the co-resident workgroup is
-// in its main loop.  EPI encodes the flags as constants -- act (bits 0-1), residual (2), SH output (3), per-row
-// bias table (4), bias (5) -- so the runtime branches, the zero residual adds and the per-quad 64-bit addressing
+// in its main loop.  EPI encodes the flags as constants (ctk_epi_code, gemm_params.h: act, residual, SH output, per-row
+// bias table, bias), so the runtime branches, the zero residual adds and the per-quad 64-bit addressing
 // of the generic epilogue disappear: two row base pointers per lane, every column offset an instruction immediate.
+// The kernels below are instantiated for the combinations of the update path (CTK_HOT_EPILOGUES) and for EPI_GENERIC.
 constexpr int EPI_GENERIC = -1;
-constexpr int epi_code(int act, bool res, bool split, bool brows, bool bias) {
-  return act | (res ? 4 : 0) | (split ? 8 : 0) | (brows ? 16 : 0) | (bias ? 32 : 0);
-}
 
 template <int MR, int NR, int EPI>
 __device__ __forceinline__ void gemm_epilogue_c(const CtkGemmP& g, f32x16 (&acc)[MR][NR], const int m_base,
@@ -290,10 +286,9 @@ __global__ __launch_bounds__(256) void gemm_f16x3_kernel(CtkGemmP g) {
 // XOR swizzle of the 16-byte chunk index applied on the SOURCE address (lane (row, pos) fetches chunk
 // pos ^ ((row >> 1) & 7)) and undone in the fragment reads: the 16 lanes of a ds_read_b128 group then
 // cover 16 distinct 16-byte bank groups.  No staging registers, no conversion, no ds_write.
-// NS = LDS stages.  NS = 2: tile kt+2 is requested in the middle of tile kt and must have landed one tile later.
-// NS = 3 (one workgroup per CU): tile kt+3 is requested there and has two tiles of MFMAs to land; the mid-tile
-// barrier is then a raw s_barrier behind a COUNTED s_waitcnt vmcnt (one tile stays in flight across it) --
-// __syncthreads() would drain the DMA queue (cdna_hip_programming.md, "Pipelining across barriers").
+// NS = LDS stages, always 2: tile kt+2 is requested in the middle of tile kt and must have landed one tile later.  (The parameter
+// stays in the list because the kernels' mangled names are keys of tools/pmc_traffic.py and of the tables under profiles/; the
+// three-stage pipeline it once selected is part of profiles/gemm_tile_experiments.patch.)
 template <int WM, int WN, int MR, int NR, int NS, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_sh_kernel(CtkGemmP g) {
   constexpr int NW = WM * WN;
@@ -302,7 +297,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_sh_kernel(CtkGemmP g) {
   constexpr int GPW = GROUPS / NW;        // groups per wave
   static_assert(GROUPS % NW == 0, "DMA groups must divide evenly over the waves");
   constexpr int STAGE = (BM + BN) * 128;  // bytes
-  static_assert(NS == 2 || NS == 3, "2 or 3 LDS stages");
+  static_assert(NS == 2, "2 LDS stages");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[NS * STAGE];
 
   const unsigned nblk = gridDim.x;
@@ -393,22 +388,12 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_sh_kernel(CtkGemmP g) {
   // phase never waits on LDS latency.  The barrier in the middle of the tile releases its stage: all waves have
   // finished reading it (lgkmcnt(0) is part of __syncthreads) and their DMA of tile kt+1 has landed (vmcnt(0));
   // the DMA of tile kt+2 then has a whole tile of MFMAs to land before it is waited for.
-  // Wait until at most `tiles` of my DMA tiles are still in flight (and my LDS reads are done), then barrier.
-  auto sync_tiles = [&](int tiles) {
-    if (NS == 2) {
-      __syncthreads();  // vmcnt(0): my DMA landed; lgkmcnt(0): my reads of the stage about to be overwritten are done
-    } else {
-      if (tiles >= 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(GPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-  };
   Frags fa, fb;
   dma(0, 0);
   if (KT > 1) dma(1, 1);
-  if (NS == 3 && KT > 2) dma(2, 2);
   {
+    // (`later` is 0 or 1 with two stages.  The `>= 2` arm cannot be taken, but hipcc only finds that out late, and without it
+    // it commutes the operands of the epilogue's v_pk_fma_f32: kept so that the kernels' ISA stays what was measured.)
     const int later = min(NS - 1, KT - 1);  // tiles requested after tile 0
     if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GPW) : "memory");
     else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GPW) : "memory");
@@ -431,8 +416,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_sh_kernel(CtkGemmP g) {
     mma_term(fa, 1);
     mma_term(fa, 2);
     __builtin_amdgcn_sched_barrier(0);
-    // tile kt+1 must have landed; with 3 stages tile kt+2 (if any) stays in flight across the barrier
-    sync_tiles((NS == 3 && kt + 2 < KT) ? 1 : 0);
+    __syncthreads();  // vmcnt(0): my DMA of tile kt+1 landed; lgkmcnt(0): my reads of the stage about to be overwritten are done
     if (kt + NS < KT) dma(kt + NS, st);  // stage st is free: every wave has its fragments of tile kt in registers
     load_frags(st_next, 0, fa);
     __builtin_amdgcn_sched_barrier(0);
@@ -459,9 +443,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_sh_kernel(CtkGemmP g) {
 }
 
 // ---- deep-pipeline 64 x 64 kernel for the small-M Linears (the 64 virtual tracks: M = 64 S rows) ------------------
-// gemm_sh_kernel<2,2,1,1,2> spends a whole LDS-DMA latency per K-tile there when its operands are cold (6 MFMAs per wave
+// A two-stage 64 x 64 gemm_sh_kernel spends a whole LDS-DMA latency per K-tile there when its operands are cold (6 MFMAs per wave
 // and K-tile cannot hide an L2 miss behind two stages).  Same tile and fragment layout, but NS stages of 16 KiB: NS - 1
-// K-tiles are always in flight behind a counted vmcnt, one raw barrier per K-tile.
+// K-tiles are always in flight behind a counted vmcnt, one raw barrier per K-tile..
 template <int NS, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(256) void gemm_sh_deep64_kernel(CtkGemmP g) {
   constexpr int BM = 64, BN = 64, STAGE = (BM + BN) * 128, GPW = 4;  // 16 pieces of 8 rows per K-tile, 4 per wave
@@ -589,18 +573,15 @@ __global__ void weight_pack_kernel(const float* W, long ldw, int N, int K, const
 
 }  // namespace
 
+// ---- tile choice -------------------------------------------------------------------------------------------------------
+// SH operands: persistent kernel (gemm_pp.hip) -> 256 x 256 -> 128 x 128 -> 64 x 64.  The other tiles that were built and measured
+// (256 x 128 with 2 and 3 stages, 128 x 384, 64 x 128, one wave per SIMD, an 8-stage 64 x 64 ring) are kept as
+// profiles/gemm_tile_experiments.patch.
 namespace {
-// Dev-build knob (read once; the release library always takes 0): CTK_GEMM_TILE = 0 auto (128x128, 2 blocks/CU) | 2 force 256x128 (8 waves, 1 block/CU,
-// 2 LDS stages) | 3 force 256x128 with 3 LDS stages (counted vmcnt + raw barrier) | 4 use 128x384 for N = 384 | 5 64x128 tile (3 workgroups per CU) | 6 256x256 tile for every N % 256 == 0 launch |
-// 1 128x128 everywhere (no 256x256).
-int gemm_tile_pref() { return (int)CTK_DEV_KNOB("CTK_GEMM_TILE", 0); }
-
-template <typename K>
-int launch_with_lds(K kernel, unsigned blocks, unsigned threads, size_t lds_bytes, const CtkGemmP& g, hipStream_t s) {
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, s, g);
-  (void)lds_bytes;
-  return CTK_OK;
-}
+// 128 x 128 tiles once they fill most of the 512 resident slots (two 4-wave workgroups per CU), 64 x 64 below
+constexpr long BIG_MIN_BLOCKS128 = 384;
+// 256 x 256 tiles: one 8-wave block per CU, want >= 2 rounds
+constexpr long T256_MIN_BLOCKS256 = 512;
 }  // namespace
 
 // 64 x 64 tiles (SH operands): the 64 S-row virtual-track Linears, and the tail rows a persistent launch of gemm_pp.hip
@@ -610,164 +591,63 @@ int ctk_launch_gemm_sh64(CtkGemmP& g, double flops, double bytes, hipStream_t s)
   char pname[32];
   snprintf(pname, sizeof(pname), "gemm_sh_64_k%d_n%d", g.K, g.N);
   CtkProfScope ps(pname, flops, bytes, s);
-  const int deep = (int)CTK_DEV_KNOB("CTK_GEMM_DEEP64", 4);  // dev builds: 0 = 2-stage kernel, 4 / 8 = stages
   const dim3 grid((unsigned)((long)g.mblocks * g.nblocks * g.batch));
-  if (deep >= 8) hipLaunchKernelGGL((gemm_sh_deep64_kernel<8>), grid, dim3(256), 0, s, g);
-  else if (deep >= 4) {
-    const int code = epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
-#define CTK_SH64(E) hipLaunchKernelGGL((gemm_sh_deep64_kernel<4, E>), grid, dim3(256), 0, s, g)
-    switch (code) {
-      case epi_code(CTK_ACT_GELU_ERF, false, true, false, true): CTK_SH64(epi_code(CTK_ACT_GELU_ERF, false, true, false, true)); break;    // corr_mlp.fc1
-      case epi_code(CTK_ACT_NONE, false, true, false, true): CTK_SH64(epi_code(CTK_ACT_NONE, false, true, false, true)); break;            // corr_mlp.fc2 -> x
-      case epi_code(CTK_ACT_NONE, false, false, true, false): CTK_SH64(epi_code(CTK_ACT_NONE, false, false, true, false)); break;          // input_transform
-      case epi_code(CTK_ACT_NONE, false, false, false, true): CTK_SH64(epi_code(CTK_ACT_NONE, false, false, false, true)); break;          // to_q / to_kv
-      case epi_code(CTK_ACT_NONE, true, false, false, true): CTK_SH64(epi_code(CTK_ACT_NONE, true, false, false, true)); break;            // to_out / mlp.fc2 (+ residual)
-      case epi_code(CTK_ACT_GELU_TANH, false, true, false, true): CTK_SH64(epi_code(CTK_ACT_GELU_TANH, false, true, false, true)); break;  // mlp.fc1
-      default: CTK_SH64(EPI_GENERIC);
-    }
-#undef CTK_SH64
+#define CTK_SH64(E) case E: hipLaunchKernelGGL((gemm_sh_deep64_kernel<4, E>), grid, dim3(256), 0, s, g); break;
+  switch (ctk_epi_code(g)) {
+    CTK_HOT_EPILOGUES(CTK_SH64)
+    default: hipLaunchKernelGGL((gemm_sh_deep64_kernel<4, EPI_GENERIC>), grid, dim3(256), 0, s, g);
   }
-  else hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 1, 1, 2>), grid, dim3(256), 0, s, g);
+#undef CTK_SH64
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }
 
 int ctk_launch_gemm_f16x3(CtkGemmP& g, double flops, double bytes, hipStream_t s) {
+  const long blocks128 = (long)((g.M + 127) / 128) * (g.N / 128) * g.batch;
+  const bool big = (g.N % 128) == 0 && blocks128 >= BIG_MIN_BLOCKS128;
+  if (!g.a_split) {  // f32 activations, split while they are staged
+    const int T = big ? 2 : 1;
+    g.mblocks = (g.M + 64 * T - 1) / (64 * T); g.nblocks = g.N / (64 * T);
+    const dim3 grid((unsigned)((long)g.mblocks * g.nblocks * g.batch));
+    CtkProfScope ps(big ? "gemm_f16x3_128x128" : "gemm_f16x3_64x64", flops, bytes, s);
+    if (big) hipLaunchKernelGGL((gemm_f16x3_kernel<2, 2>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((gemm_f16x3_kernel<1, 1>), grid, dim3(256), 0, s, g);
+    CTK_HIP_CHECK_LAUNCH();
+    return CTK_OK;
+  }
+  // round 3: persistent ping-pong kernels for the big N % 256 == 0 / N % 192 == 0 Linears
+  const int rc = ctk_launch_gemm_pp(g, flops, bytes, s);
+  if (rc >= 0) return rc;
+  if (!big) return ctk_launch_gemm_sh64(g, flops, bytes, s);
   // recorder rows are per (tile, K, N): the K = 384 Linears and corr_mlp.fc1 (K = 2432) sit at very different
   // fractions of the MFMA ceiling and must not be averaged under one name
   char pname[32];
-  auto prof_name = [&](const char* tile) {
-    snprintf(pname, sizeof(pname), "gemm_sh_%s_k%d_n%d", tile, g.K, g.N);
-    return pname;
-  };
-
-  if (g.a_split) {  // round 3: persistent ping-pong kernels for the big N % 256 == 0 / N % 192 == 0 Linears
-    const int rc = ctk_launch_gemm_pp(g, flops, bytes, s);
-    if (rc >= 0) return rc;
-  }
-  const long blocks128 = (long)((g.M + 127) / 128) * (g.N / 128) * g.batch;
-  // 128 x 128 tiles once they fill most of the 512 resident slots, 64 x 64 below (CTK_GEMM_BIG_MIN overrides the threshold)
-  const long big_min = CTK_DEV_KNOB("CTK_GEMM_BIG_MIN", 384L);
-  const bool big = (g.N % 128) == 0 && blocks128 >= big_min;
-  if (g.a_split) {
-    const int pref = gemm_tile_pref();
-    // 128x384 tile (8 waves as 2 x 4, each 64 x 96): the block owns full rows of an N = 384 Linear, A is fetched once
-    // instead of three times and a wave issues 1.6 instead of 3.2 non-MFMA instructions per MFMA.  Opt-in only
-    // (CTK_GEMM_TILE=4): for corr_mlp.fc1 it is 6 % faster in tools/bench_gemm.py (2.62 -> 2.47 ms) but slower inside
-    // the update iteration (2.49 ms per launch, +25 ms per C3 step) -- one 8-wave block per CU starts cold behind
-    // the sampler where two 4-wave blocks overlap their prologues.  Round 2 re-measured it with compile-time epilogues
-    // for every N = 384 Linear (profiles/r02_gemm_fullrow_ab.txt): q/out -3...-9 %, fc2 -3...-9 %, C3 step +3.5 % slower.
-    const long rows128 = (g.M + 127) / 128;
-    const int code256 = epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
-    const bool epi256 = code256 == epi_code(CTK_ACT_NONE, false, false, false, true) ||      // to_kv
-                        code256 == epi_code(CTK_ACT_GELU_TANH, false, true, false, true) ||  // mlp.fc1
-                        code256 == epi_code(CTK_ACT_NONE, false, true, false, true);         // corr_mlp.fc2
-    const long blocks256 = (long)((g.M + 255) / 256) * (g.N / 256) * g.batch;  // one 8-wave block per CU: want >= 2 rounds
-    if (big && (g.N % 256) == 0 && blocks256 >= 512 && pref != 1 && (pref == 6 || epi256)) {
-      // 256x256 tile, 8 waves as 2 x 4, wave tile 128 x 64: 48 MFMAs per 24 fragment reads (128x128: 24 per 16).
-      // Default for the N % 256 == 0 Linears that have a compile-time epilogue (to_kv, mlp.fc1, corr_mlp.fc2):
-      // -5..-11 % per launch in tools/bench_gemm.py, -0.6 % per C3 step measured in situ.  CTK_GEMM_TILE=1 disables.
-      g.mblocks = (g.M + 255) / 256; g.nblocks = g.N / 256;
-      CtkProfScope ps(prof_name("256"), flops, bytes, s);
-      const dim3 grid((unsigned)((long)g.mblocks * g.nblocks * g.batch)), blk(512);
-      if (code256 == epi_code(CTK_ACT_NONE, false, false, false, true))
-        hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 4, 2, 2, epi_code(CTK_ACT_NONE, false, false, false, true)>), grid, blk, 0, s, g);
-      else if (code256 == epi_code(CTK_ACT_GELU_TANH, false, true, false, true))
-        hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 4, 2, 2, epi_code(CTK_ACT_GELU_TANH, false, true, false, true)>), grid, blk, 0, s, g);
-      else if (code256 == epi_code(CTK_ACT_NONE, false, true, false, true))
-        hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 4, 2, 2, epi_code(CTK_ACT_NONE, false, true, false, true)>), grid, blk, 0, s, g);
-      else
-        hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 4, 2, 2, EPI_GENERIC>), grid, blk, 0, s, g);
-    } else if (g.N == 384 && g.batch == 1 && pref == 4 && rows128 >= 256) {
-      g.mblocks = (int)rows128; g.nblocks = 1;
-      CtkProfScope ps(prof_name("128x384"), flops, bytes, s);
-      const int code = epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
-      const dim3 grid((unsigned)rows128), blk(512);
-#define CTK_SH384(E) hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 2, 3, 2, E>), grid, blk, 0, s, g)
-      switch (code) {
-        case epi_code(CTK_ACT_GELU_ERF, false, true, false, true): CTK_SH384(epi_code(CTK_ACT_GELU_ERF, false, true, false, true)); break;  // corr_mlp.fc1
-        case epi_code(CTK_ACT_NONE, false, false, true, false): CTK_SH384(epi_code(CTK_ACT_NONE, false, false, true, false)); break;        // input_transform
-        case epi_code(CTK_ACT_NONE, false, false, false, true): CTK_SH384(epi_code(CTK_ACT_NONE, false, false, false, true)); break;        // to_q
-        case epi_code(CTK_ACT_NONE, true, false, false, true): CTK_SH384(epi_code(CTK_ACT_NONE, true, false, false, true)); break;          // to_out / mlp.fc2
-        default: CTK_SH384(EPI_GENERIC);
-      }
-#undef CTK_SH384
-    } else if (g.N == 384 && g.batch == 1 && (pref == 8 || pref == 9) && rows128 >= 256) {
-      // Round-2 experiments, ONE wave per SIMD (4 waves, one workgroup per CU, up to 512 registers per wave):
-      //   8: 128 x 384 tile, waves 1 x 4, wave tile 128 x 96 (36 MFMAs per 14 fragment reads), 2 LDS stages of 64 KB
-      //   9: 256 x 128 tile, waves 2 x 2, wave tile 128 x 64 (24 MFMAs per 12 reads), 3 LDS stages of 48 KB, counted vmcnt
-      const int code = epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
-      const dim3 blk(256);
-      if (pref == 8) {
-        g.mblocks = (int)rows128; g.nblocks = 1;
-        CtkProfScope ps(prof_name("w128x384"), flops, bytes, s);
-        const dim3 grid((unsigned)rows128);
-#define CTK_SHW(E) hipLaunchKernelGGL((gemm_sh_kernel<1, 4, 4, 3, 2, E>), grid, blk, 0, s, g)
-        switch (code) {
-          case epi_code(CTK_ACT_GELU_ERF, false, true, false, true): CTK_SHW(epi_code(CTK_ACT_GELU_ERF, false, true, false, true)); break;
-          case epi_code(CTK_ACT_NONE, false, false, false, true): CTK_SHW(epi_code(CTK_ACT_NONE, false, false, false, true)); break;
-          case epi_code(CTK_ACT_NONE, true, false, false, true): CTK_SHW(epi_code(CTK_ACT_NONE, true, false, false, true)); break;
-          default: CTK_SHW(EPI_GENERIC);
-        }
-#undef CTK_SHW
-      } else {
-        g.mblocks = (g.M + 255) / 256; g.nblocks = g.N / 128;
-        CtkProfScope ps(prof_name("w256x128x3"), flops, bytes, s);
-        const dim3 grid((unsigned)((long)g.mblocks * g.nblocks));
-#define CTK_SHW(E) hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 4, 2, 3, E>), grid, blk, 0, s, g)
-        switch (code) {
-          case epi_code(CTK_ACT_GELU_ERF, false, true, false, true): CTK_SHW(epi_code(CTK_ACT_GELU_ERF, false, true, false, true)); break;
-          case epi_code(CTK_ACT_NONE, false, false, false, true): CTK_SHW(epi_code(CTK_ACT_NONE, false, false, false, true)); break;
-          case epi_code(CTK_ACT_NONE, true, false, false, true): CTK_SHW(epi_code(CTK_ACT_NONE, true, false, false, true)); break;
-          default: CTK_SHW(EPI_GENERIC);
-        }
-#undef CTK_SHW
-      }
-    } else if (big && pref == 3) {
-      g.mblocks = (g.M + 255) / 256; g.nblocks = g.N / 128;
-      CtkProfScope ps("gemm_sh_256x128x3", flops, bytes, s);
-      hipLaunchKernelGGL((gemm_sh_kernel<4, 2, 2, 2, 3>), dim3((unsigned)((long)g.mblocks * g.nblocks * g.batch)), dim3(512), 0, s, g);
-    } else if (big && pref == 2) {
-      g.mblocks = (g.M + 255) / 256; g.nblocks = g.N / 128;
-      CtkProfScope ps("gemm_sh_256x128", flops, bytes, s);
-      hipLaunchKernelGGL((gemm_sh_kernel<4, 2, 2, 2, 2>), dim3((unsigned)((long)g.mblocks * g.nblocks * g.batch)), dim3(512), 0, s, g);
-    } else if (big) {
-      g.mblocks = (g.M + 127) / 128; g.nblocks = g.N / 128;
-      // the six flag combinations of the update path get compile-time epilogues; anything else the generic one
-      const int code = epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
-      // CTK_GEMM_TILE=5: 64x128 tile (wave 32x64, 48 KB of LDS -> three workgroups per CU instead of two)
-      const bool t64 = pref == 5;
-      if (t64) { g.mblocks = (g.M + 63) / 64; }
-      CtkProfScope ps(prof_name(t64 ? "64x128" : "128"), flops, bytes, s);
-      const dim3 grid((unsigned)((long)g.mblocks * g.nblocks * g.batch)), blk(256);
-#define CTK_SH128(E)                                                                     \
-  do {                                                                                   \
-    if (t64) hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 1, 2, 2, E>), grid, blk, 0, s, g); \
-    else hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 2, 2, 2, E>), grid, blk, 0, s, g);     \
-  } while (0)
-      if (CTK_DEV_KNOB("CTK_GEMM_EPI", 1) == 0) CTK_SH128(EPI_GENERIC);  // dev builds: CTK_GEMM_EPI=0 forces the generic epilogue
-      else switch (code) {
-        case epi_code(CTK_ACT_GELU_ERF, false, true, false, true): CTK_SH128(epi_code(CTK_ACT_GELU_ERF, false, true, false, true)); break;    // corr_mlp.fc1
-        case epi_code(CTK_ACT_NONE, false, true, false, true): CTK_SH128(epi_code(CTK_ACT_NONE, false, true, false, true)); break;            // corr_mlp.fc2 -> x
-        case epi_code(CTK_ACT_NONE, false, false, true, false): CTK_SH128(epi_code(CTK_ACT_NONE, false, false, true, false)); break;          // input_transform (+ time bias rows)
-        case epi_code(CTK_ACT_NONE, false, false, false, true): CTK_SH128(epi_code(CTK_ACT_NONE, false, false, false, true)); break;          // to_q / to_kv
-        case epi_code(CTK_ACT_NONE, true, false, false, true): CTK_SH128(epi_code(CTK_ACT_NONE, true, false, false, true)); break;            // to_out / mlp.fc2 (+ residual)
-        case epi_code(CTK_ACT_GELU_TANH, false, true, false, true): CTK_SH128(epi_code(CTK_ACT_GELU_TANH, false, true, false, true)); break;  // mlp.fc1
-        default: CTK_SH128(EPI_GENERIC);
-      }
-#undef CTK_SH128
-    } else {
-      return ctk_launch_gemm_sh64(g, flops, bytes, s);
-    }
-  } else if (big) {
-    g.mblocks = (g.M + 127) / 128; g.nblocks = g.N / 128;
-    CtkProfScope ps("gemm_f16x3_128x128", flops, bytes, s);
-    hipLaunchKernelGGL((gemm_f16x3_kernel<2, 2>), dim3((unsigned)blocks128), dim3(256), 0, s, g);
+  const int code = ctk_epi_code(g);
+  const long blocks256 = (long)((g.M + 255) / 256) * (g.N / 256) * g.batch;
+  if ((g.N % 256) == 0 && blocks256 >= T256_MIN_BLOCKS256 && ctk_epi_is_hot_n256(code)) {
+    // 256x256 tile, 8 waves as 2 x 4, wave tile 128 x 64: 48 MFMAs per 24 fragment reads (128x128: 24 per 16).
+    // For the N % 256 == 0 Linears of the update path (to_kv, mlp.fc1, corr_mlp.fc2):
+    // -5..-11 % per launch in tools/bench_gemm.py, -0.6 % per C3 step measured in situ.
+    g.mblocks = (g.M + 255) / 256; g.nblocks = g.N / 256;
+    snprintf(pname, sizeof(pname), "gemm_sh_256_k%d_n%d", g.K, g.N);
+    CtkProfScope ps(pname, flops, bytes, s);
+    const dim3 grid((unsigned)((long)g.mblocks * g.nblocks * g.batch));
+#define CTK_SH256(E) case E: hipLaunchKernelGGL((gemm_sh_kernel<2, 4, 4, 2, 2, E>), grid, dim3(512), 0, s, g); break;
+    switch (code) { CTK_HOT_EPILOGUES_N256(CTK_SH256) }
+#undef CTK_SH256
   } else {
-    g.mblocks = (g.M + 63) / 64; g.nblocks = g.N / 64;
-    const long blocks = (long)g.mblocks * g.nblocks * g.batch;
-    CtkProfScope ps("gemm_f16x3_64x64", flops, bytes, s);
-    hipLaunchKernelGGL((gemm_f16x3_kernel<1, 1>), dim3((unsigned)blocks), dim3(256), 0, s, g);
+    // 128x128 tile, 4 waves as 2 x 2, two workgroups per CU: the update path's flag combinations get compile-time
+    // epilogues, anything else the generic one
+    g.mblocks = (g.M + 127) / 128; g.nblocks = g.N / 128;
+    snprintf(pname, sizeof(pname), "gemm_sh_128_k%d_n%d", g.K, g.N);
+    CtkProfScope ps(pname, flops, bytes, s);
+    const dim3 grid((unsigned)blocks128);
+#define CTK_SH128(E) case E: hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 2, 2, 2, E>), grid, dim3(256), 0, s, g); break;
+    switch (code) {
+      CTK_HOT_EPILOGUES(CTK_SH128)
+      default: hipLaunchKernelGGL((gemm_sh_kernel<2, 2, 2, 2, 2, EPI_GENERIC>), grid, dim3(256), 0, s, g);
+    }
+#undef CTK_SH128
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

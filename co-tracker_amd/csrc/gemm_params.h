@@ -59,6 +59,33 @@ struct CtkGemmP {
   int mblocks, nblocks;
 };
 
+// ---- compile-time epilogues of the SH-operand kernels (gemm_f16x3.hip, gemm_pp.hip) ------------------------------------
+// EPI encodes a Linear's epilogue flags as template constants: act (bits 0-1), residual (2), SH output (3), per-row bias
+// table (4), bias (5).
+constexpr int ctk_epi_code(int act, bool res, bool split, bool brows, bool bias) {
+  return act | (res ? 4 : 0) | (split ? 8 : 0) | (brows ? 16 : 0) | (bias ? 32 : 0);
+}
+inline int ctk_epi_code(const CtkGemmP& g) {
+  return ctk_epi_code(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
+}
+// THE list of the update path's flag combinations: every SH-operand kernel family is instantiated once per entry, X(code)
+#define CTK_HOT_EPILOGUES(X)                                                                                                  \
+  X(ctk_epi_code(CTK_ACT_GELU_ERF, false, true, false, true))  /* corr_mlp.fc1 */                                             \
+  X(ctk_epi_code(CTK_ACT_NONE, false, true, false, true))      /* corr_mlp.fc2 -> x (SH) */                                   \
+  X(ctk_epi_code(CTK_ACT_NONE, false, false, true, false))     /* input_transform (+ per-frame bias rows) */                  \
+  X(ctk_epi_code(CTK_ACT_NONE, false, false, false, true))     /* to_q / to_kv */                                             \
+  X(ctk_epi_code(CTK_ACT_NONE, true, false, false, true))      /* to_out / mlp.fc2 (+ residual) */                            \
+  X(ctk_epi_code(CTK_ACT_GELU_TANH, false, true, false, true)) /* mlp.fc1 */
+// its N % 256 == 0 Linears: the 256 x 256 tile of gemm_f16x3.hip exists for these three only
+#define CTK_HOT_EPILOGUES_N256(X)                                                                                             \
+  X(ctk_epi_code(CTK_ACT_NONE, false, true, false, true))      /* corr_mlp.fc2 */                                             \
+  X(ctk_epi_code(CTK_ACT_NONE, false, false, false, true))     /* to_kv */                                                    \
+  X(ctk_epi_code(CTK_ACT_GELU_TANH, false, true, false, true)) /* mlp.fc1 */
+#define CTK_EPI_OR_EQ(E) || code == (E)
+constexpr bool ctk_epi_is_hot(int code) { return false CTK_HOT_EPILOGUES(CTK_EPI_OR_EQ); }
+constexpr bool ctk_epi_is_hot_n256(int code) { return false CTK_HOT_EPILOGUES_N256(CTK_EPI_OR_EQ); }
+#undef CTK_EPI_OR_EQ
+
 // gemm_f16x3.hip
 int ctk_launch_gemm_f16x3(CtkGemmP& g, double flops, double bytes, hipStream_t s);
 int ctk_launch_gemm_sh64(CtkGemmP& g, double flops, double bytes, hipStream_t s);  // 64 x 64 tiles (SH operands)

@@ -696,13 +696,6 @@ extern "C" int ctk_debug_pp_trace(unsigned long long* host_out, int n) {
 }
 #endif
 
-// the compile-time epilogues the persistent kernels are instantiated for (the PP_CASE list below)
-static bool pp_epi_supported(int code) {
-  return code == pp_epi(CTK_ACT_GELU_ERF, false, true, false, true) || code == pp_epi(CTK_ACT_NONE, false, true, false, true) ||
-         code == pp_epi(CTK_ACT_NONE, false, false, true, false) || code == pp_epi(CTK_ACT_NONE, false, false, false, true) ||
-         code == pp_epi(CTK_ACT_NONE, true, false, false, true) || code == pp_epi(CTK_ACT_GELU_TANH, false, true, false, true);
-}
-
 // Tail split (CTK_OPT_GEMM_PP bit 5, default ON).  A persistent launch deals whole 256-row tiles in rounds of #CUs: the N = 384
 // Linears of a C3 window are 800 / 808 tiles = 3 full rounds + a round that is 1/8 full, and the launch lasts four tile times
 // (profiles/r03_gemm_lab_streamk.txt: mlp.fc2 350 us for 768 tiles, 414 us for 800).  When the last round would be at most
@@ -726,10 +719,10 @@ int ctk_launch_gemm_pp(CtkGemmP& g, double flops, double bytes, hipStream_t s) {
   const int cus = pp_num_cus();
   if (tiles < cus) return -1;  // less than one tile per CU (virtual-track GEMMs, short streaming windows): the 64x64 / 128x128 kernels fill the chip better (tools/gemm_lab.cpp)
   const int wgs = cus;
-  const int code = pp_epi(g.act, g.resid != nullptr, g.c_split != 0, g.bias_rows != nullptr, g.bias != nullptr);
+  const int code = ctk_epi_code(g);
   if (g.resid && g.K < 8 * 32) return -1;  // the residual rides on a tile's first eight K-tiles (gemm_pp192_kernel)
   if (t256 && g.resid) return -1;  // residual preload of a 128-register accumulator tile spills; no Linear of the path has this shape
-  if (!pp_epi_supported(code)) return -1;
+  if (!ctk_epi_is_hot(code)) return -1;  // the list PP_CASE below is instantiated over
   // ---- tail split: whole rounds here, the row blocks of a nearly empty last round as 64 x 64 tiles
   CtkGemmP tail = g;
   int tail_rows = 0;
@@ -770,14 +763,9 @@ int ctk_launch_gemm_pp(CtkGemmP& g, double flops, double bytes, hipStream_t s) {
     else { PP_DBG_CASE(gemm_pp192_kernel, E) {                                                                  \
       if (g.K > 768) hipLaunchKernelGGL((gemm_pp192_kernel<E, false, 1>), grid, blk, 0, s, g, (int)tiles, 0);  \
       else hipLaunchKernelGGL((gemm_pp192_kernel<E, false, 0>), grid, blk, 0, s, g, (int)tiles, 0); } }        \
-    break
+    break;
   switch (code) {
-    PP_CASE(pp_epi(CTK_ACT_GELU_ERF, false, true, false, true));    // corr_mlp.fc1
-    PP_CASE(pp_epi(CTK_ACT_NONE, false, true, false, true));        // corr_mlp.fc2 -> x (SH)
-    PP_CASE(pp_epi(CTK_ACT_NONE, false, false, true, false));       // input_transform (+ per-frame bias rows)
-    PP_CASE(pp_epi(CTK_ACT_NONE, false, false, false, true));       // to_q / to_kv
-    PP_CASE(pp_epi(CTK_ACT_NONE, true, false, false, true));        // to_out / mlp.fc2 (+ residual)
-    PP_CASE(pp_epi(CTK_ACT_GELU_TANH, false, true, false, true));   // mlp.fc1
+    CTK_HOT_EPILOGUES(PP_CASE)
     default:
       return -1;
   }

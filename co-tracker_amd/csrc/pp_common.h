@@ -61,11 +61,7 @@ __device__ __forceinline__ void pp_dma16(const unsigned char* base /*uniform*/, 
 }
 
 // ---- epilogue ----------------------------------------------------------------------------------
-// EPI bit layout as gemm_f16x3.hip: act (bits 0-1), residual (2), SH output (3), per-row bias table (4), bias (5).
-constexpr int pp_epi(int act, bool res, bool split, bool brows, bool bias) {
-  return act | (res ? 4 : 0) | (split ? 8 : 0) | (brows ? 16 : 0) | (bias ? 32 : 0);
-}
-
+// EPI: the bit layout of ctk_epi_code (gemm_params.h).
 // acc[mi][ni] is the swapped-operand 32x32 accumulator D'[n][m]: lane = output row r32 (+ row_of(mi)), register quad q =
 // output columns col_of(ni) + 8q + 4*half + 0..3.
 // Stores: written straight from that layout a store instruction touches 32 rows x 32 bytes, and a CU retires such an

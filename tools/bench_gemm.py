@@ -68,7 +68,7 @@ def main():
                     res.setdefault((name, mode), []).append(e0.elapsed_time(e1))
     for mode in MODES:
         tot_t = tot_f = 0.0
-        print(f"--- back end {mode}, CTK_GEMM_TILE={os.environ.get('CTK_GEMM_TILE', '0')} (TF/s = algorithmic f32-equivalent flops / time)")
+        print(f"--- back end {mode} (TF/s = algorithmic f32-equivalent flops / time)")
         print(f"{'shape':10s} {'M':>8s} {'K':>6s} {'N':>6s} {'ms(med)':>9s} {'TF/s':>8s} {'x/iter':>6s}")
         for name, M, K, N, act, resid, cnt, kv in SHAPES:
             ts = sorted(res[(name, mode)])

@@ -36,7 +36,7 @@ for rd in range(6):
 med = {}
 for M, K, t in rows:
     med.setdefault((M, K), []).append(t)
-print(f"N={N}  CTK_GEMM_TILE={os.environ.get('CTK_GEMM_TILE', '0')}")
+print(f"N={N}")
 print(f"{'M':>8s} {'K':>6s} {'tiles':>7s} {'us(med)':>9s} {'TF/s':>8s} {'us per tile-round':>18s}")
 A, y = [], []
 for (M, K), ts in sorted(med.items()):
