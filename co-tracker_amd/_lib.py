@@ -104,6 +104,19 @@ class WindowBatch(C.Structure):
     _fields_ = [("B", C.c_int32), ("flags", C.c_int32), ("videos", C.POINTER(WindowArgs))]
 
 
+class StreamArgs(C.Structure):
+    """ctk_stream_args: the device-resident stream state of G query groups over one live video (include/ctk.h)."""
+    _fields_ = [
+        ("G", C.c_int32), ("N", C.c_int32), ("S", C.c_int32), ("step", C.c_int32),
+        ("ind", C.c_int32), ("T_valid", C.c_int32), ("T_cap", C.c_int32), ("stride", C.c_float),
+        ("queries", _fp), ("hist_coords", _fp), ("hist_vis", _fp), ("hist_conf", _fp),
+        ("coords", _fp), ("vis", _fp), ("conf", _fp), ("point_mask", _fp),
+        ("H", C.c_int32 * LEVELS), ("W", C.c_int32 * LEVELS),
+        ("fmaps", _fp * LEVELS), ("support", _fp * LEVELS),
+        ("nonfinite", _fp),
+    ]
+
+
 class FormerWeights(C.Structure):
     """ctk_former_weights: the general update former (CoTracker2)."""
     _fields_ = [
@@ -157,6 +170,9 @@ SYMBOLS = {
     "ctk_window_graph_launch": (C.c_int, [C.c_void_p, _fp]),
     "ctk_window_graph_nodes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "ctk_window_graph_destroy": (C.c_int, [C.c_void_p]),
+    "ctk_stream_begin": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_support": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_commit": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

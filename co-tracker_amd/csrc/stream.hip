@@ -1,0 +1,199 @@
+// Device-resident stream state of G query groups over one live video (include/ctk.h, "stream state step").
+//
+// Three byte-moving kernels, each launched ONCE per streaming call for all G*N points.  They replace the per-stream torch glue of
+// the host model (carry-over + masks, support sampling + masked accumulation, write-back + finiteness reductions) and keep its
+// arithmetic operation for operation -- the acceptance test is bit equality with streams that still run that glue -- so every
+// float step is an explicit IEEE intrinsic and this translation unit is compiled with -ffp-contract=off (Makefile: NOFMA).
+//   begin    cotracker3_online.py:457-484   window state + point mask from the queries and the history
+//   support  cotracker3_online.py:411-440   trilinear support patches of the points whose query frame entered this window, added
+//                                           into the persistent accumulators
+//   commit   cotracker3_online.py:498-510   finished window -> history rows, optional non-finite flag
+// No LDS, no atomics except the one flag OR, no device-side globals.
+#include "ctk_common.h"
+
+namespace {
+
+// torch divides a tensor by a host scalar as a multiplication with the scalar's float reciprocal (queries / stride, / 2^l, history /
+// stride): the kernels take 1 / stride, rounded once on the host, and multiply.
+// float -> integer frame index as torch's .long() does it (truncation toward zero); NaN / out-of-range frames match no window
+__device__ __forceinline__ long qframe_of(float f) { return (long)f; }
+
+// ---- begin: one thread per (g, t, n) of the window state ------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stream_begin_kernel(int G, int N, int S, int step, int ind, long T_cap, float inv_stride,
+                                                           const float* __restrict__ queries, const float* __restrict__ hc,
+                                                           const float* __restrict__ hv, const float* __restrict__ hf,
+                                                           float* __restrict__ coords, float* __restrict__ vis,
+                                                           float* __restrict__ conf, uint8_t* __restrict__ mask) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)G * S * N;
+  if (i >= total) return;
+  const int n = (int)(i % N);
+  const int t = (int)((i / N) % S);
+  const long g = i / ((long)N * S);
+  const float* q = queries + (g * N + n) * 3;
+  const long qf = qframe_of(q[0]);
+  const int overlap = S - step;
+  float2 c;
+  float v = 0.0f, f = 0.0f;
+  if (ind > 0 && qf < (long)ind + overlap) {
+    // carry-over: rows ind .. ind+overlap-1 of the history, the last of them repeated `step` times
+    const long row = (g * T_cap + ind + min(t, overlap - 1)) * N + n;
+    const float2 h = *reinterpret_cast<const float2*>(hc + row * 2);
+    c.x = __fmul_rn(h.x, inv_stride);
+    c.y = __fmul_rn(h.y, inv_stride);
+    v = hv[row];
+    f = hf[row];
+  } else {
+    c.x = __fmul_rn(q[1], inv_stride);
+    c.y = __fmul_rn(q[2], inv_stride);
+  }
+  *reinterpret_cast<float2*>(coords + i * 2) = c;
+  vis[i] = v;
+  conf[i] = f;
+  if (t == 0) mask[g * N + n] = qf < (long)ind + S ? 1 : 0;
+}
+
+// ---- support: one wave per (level, point, tap) row of 128 channels, float2 per lane ----------------------------------------
+struct StreamLevels {
+  const float* fm[CTK_LEVELS];
+  float* acc[CTK_LEVELS];
+  int H[CTK_LEVELS], W[CTK_LEVELS];
+  float sx[CTK_LEVELS], sy[CTK_LEVELS];
+};
+
+__global__ __launch_bounds__(256) void stream_support_kernel(StreamLevels lv, long P /* G*N */, int S, float sz, int left, int right,
+                                                             int ind, float inv_stride, const float* __restrict__ queries) {
+  const long wid = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wid >= P * CTK_TAPS) return;
+  const long n = wid / CTK_TAPS;
+  const float* q = queries + n * 3;
+  const long qf = qframe_of(q[0]);
+  if (qf < left || qf >= right) return;  // not this window's point: its accumulator row is neither read nor written
+  const int l = blockIdx.y;
+  const int pp = (int)(wid - n * CTK_TAPS);
+  const int hx = pp / 7, wy = pp - hx * 7;
+  const int H = lv.H[l], W = lv.W[l];
+  // (queries / stride) / 2^l, then the tap arithmetic of sample_support_kernel (corr.hip)
+  const float linv = 1.0f / (float)(1 << l);
+  const float cx = __fmul_rn(__fmul_rn(q[1], inv_stride), linv), cy = __fmul_rn(__fmul_rn(q[2], inv_stride), linv);
+  const CtkTap tx = ctk_tap(__fadd_rn(cx, (float)(hx - 3)), W, lv.sx[l]);
+  const CtkTap ty = ctk_tap(__fadd_rn(cy, (float)(wy - 3)), H, lv.sy[l]);
+  const CtkTap tz = ctk_tap(__fadd_rn((float)(qf - ind), 0.0f), S, sz);
+  const float* fm = lv.fm[l];
+  float2 o = make_float2(0.f, 0.f);
+  const int zi[2] = {tz.i0, tz.i1};
+  const float zw[2] = {tz.w0, tz.w1};
+  const int yi[2] = {ty.i0, ty.i1};
+  const float yw[2] = {ty.w0, ty.w1};
+  const int xi[2] = {tx.i0, tx.i1};
+  const float xw[2] = {tx.w0, tx.w1};
+#pragma unroll
+  for (int dz = 0; dz < 2; ++dz)
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const float w = __fmul_rn(__fmul_rn(xw[dx], yw[dy]), zw[dz]);
+        const float2 v = *reinterpret_cast<const float2*>(fm + (((long)zi[dz] * H + yi[dy]) * W + xi[dx]) * CTK_C + lane * 2);
+        o.x = __fadd_rn(o.x, __fmul_rn(v.x, w));
+        o.y = __fadd_rn(o.y, __fmul_rn(v.y, w));
+      }
+  float2* dst = reinterpret_cast<float2*>(lv.acc[l] + wid * CTK_C + lane * 2);
+  float2 a = *dst;  // acc + s: the accumulation of the host glue (zeros + s * 1 on the one call that samples this point)
+  a.x = __fadd_rn(a.x, o.x);
+  a.y = __fadd_rn(a.y, o.y);
+  *dst = a;
+}
+
+// ---- commit: one thread per (g, t < T_valid, n) ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stream_commit_kernel(int G, int N, int S, int T_valid, int ind, long T_cap, float stride,
+                                                            const float* __restrict__ coords, const float* __restrict__ vis,
+                                                            const float* __restrict__ conf, float* __restrict__ hc,
+                                                            float* __restrict__ hv, float* __restrict__ hf,
+                                                            int32_t* __restrict__ flag) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long total = (long)G * T_valid * N;
+  bool bad = false;
+  if (i < total) {
+    const int n = (int)(i % N);
+    const int t = (int)((i / N) % T_valid);
+    const long g = i / ((long)N * T_valid);
+    const long src = (g * S + t) * N + n;
+    const long row = (g * T_cap + ind + t) * N + n;
+    const float2 c = *reinterpret_cast<const float2*>(coords + src * 2);
+    float2 o;
+    o.x = __fmul_rn(c.x, stride);
+    o.y = __fmul_rn(c.y, stride);
+    const float v = vis[src], f = conf[src];
+    *reinterpret_cast<float2*>(hc + row * 2) = o;
+    hv[row] = v;
+    hf[row] = f;
+    bad = !(isfinite(o.x) && isfinite(o.y) && isfinite(v) && isfinite(f));
+  }
+  if (flag != nullptr && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+int check_common(const ctk_stream_args* a) {
+  if (!a) return CTK_E_NULL;
+  if (a->G <= 0 || a->N <= 0 || a->S <= 0 || a->step <= 0 || a->step >= a->S || a->ind < 0 || a->ind % a->step != 0)
+    return CTK_E_SHAPE;
+  if ((long)a->T_cap < (long)a->ind + a->S) return CTK_E_SHAPE;
+  if (!(a->stride > 0.0f) || !(a->stride <= 65536.0f)) return CTK_E_SHAPE;
+  if ((long)a->G * a->N > (1L << 26) || (long)a->G * a->N * a->S > (1L << 30)) return CTK_E_SHAPE;
+  return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" int ctk_stream_begin(const ctk_stream_args* a, void* stream) {
+  const int rc = check_common(a);
+  if (rc != CTK_OK) return rc;
+  if (!a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf || !a->coords || !a->vis || !a->conf || !a->point_mask)
+    return CTK_E_NULL;
+  const long total = (long)a->G * a->S * a->N;
+  hipLaunchKernelGGL(stream_begin_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     a->G, a->N, a->S, a->step, a->ind, (long)a->T_cap, 1.0f / a->stride, a->queries, a->hist_coords, a->hist_vis,
+                     a->hist_conf, a->coords, a->vis, a->conf, a->point_mask);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+extern "C" int ctk_stream_support(const ctk_stream_args* a, void* stream) {
+  const int rc = check_common(a);
+  if (rc != CTK_OK) return rc;
+  if (!a->queries) return CTK_E_NULL;
+  StreamLevels lv;
+  for (int l = 0; l < CTK_LEVELS; ++l) {
+    if (!a->fmaps[l] || !a->support[l]) return CTK_E_NULL;
+    if (a->H[l] <= 0 || a->W[l] <= 0) return CTK_E_SHAPE;
+    lv.fm[l] = a->fmaps[l];
+    lv.acc[l] = a->support[l];
+    lv.H[l] = a->H[l];
+    lv.W[l] = a->W[l];
+    lv.sx[l] = ctk_sampler_scale(a->W[l]);
+    lv.sy[l] = ctk_sampler_scale(a->H[l]);
+  }
+  const long P = (long)a->G * a->N;
+  const long waves = P * CTK_TAPS;
+  const int left = a->ind == 0 ? 0 : a->ind + a->step;  // cotracker3_online.py:411-414
+  const int right = a->ind + a->S;
+  hipLaunchKernelGGL(stream_support_kernel, dim3((unsigned)((waves + 3) / 4), CTK_LEVELS), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), lv, P, a->S, ctk_sampler_scale(a->S), left, right, a->ind, 1.0f / a->stride,
+                     a->queries);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+extern "C" int ctk_stream_commit(const ctk_stream_args* a, void* stream) {
+  const int rc = check_common(a);
+  if (rc != CTK_OK) return rc;
+  if (a->T_valid <= 0 || a->T_valid > a->S) return CTK_E_SHAPE;
+  if (!a->hist_coords || !a->hist_vis || !a->hist_conf || !a->coords || !a->vis || !a->conf) return CTK_E_NULL;
+  const long total = (long)a->G * a->T_valid * a->N;
+  hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->T_valid, a->ind, (long)a->T_cap, a->stride, a->coords,
+                     a->vis, a->conf, a->hist_coords, a->hist_vis, a->hist_conf, a->nonfinite);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}

@@ -313,8 +313,22 @@ class TrackerBase(nn.Module):
         # A query-group call -- video [1,T,3,H,W] with queries [G,N,3], G > 1 -- tracks G independent query sets over the ONE
         # video: the encoder, the pyramid and the support sampling run once for the call, and the groups' windows run one after
         # the other ("loop": bit-identical to G separate calls) or as joint windows of up to CTK_MAX_BATCH groups that share the
-        # pyramid ("joint": ctk_window_batch.flags = CTK_BATCH_SHARED_FMAPS).  Returns [G,T,N,.] tensors.  Offline / sliding only.
+        # pyramid ("joint": ctk_window_batch.flags = CTK_BATCH_SHARED_FMAPS).  Returns [G,T,N,.] tensors.  Offline / sliding; streaming: stream_groups below.
         self.batch_mode = "loop"
+        # Streaming query groups (CoTracker3 online model only; opt-in like batch_mode / online_feature_cache): with it on,
+        # forward(video [1,T,3,H,W], queries [G,N,3], is_online=True), G > 1, streams G independent query sets over the ONE live
+        # video -- one encoder run and one pyramid per chunk, the stream state of all groups resident on the device and stepped by
+        # three launches per call (ops.StreamGroups, csrc/stream.hip), the groups' windows one after the other ("loop":
+        # bit-identical to G single-group streams) or as shared-pyramid joint windows ("joint").  Off: that call raises, as before.
+        self.stream_groups = False
+
+    @property
+    def stream_groups(self) -> bool:
+        return getattr(self, "_stream_groups", False)  # (a model pickled before the attribute existed)
+
+    @stream_groups.setter
+    def stream_groups(self, on):
+        self._stream_groups = bool(on)
 
     @property
     def batch_mode(self) -> str:
@@ -418,9 +432,9 @@ class TrackerBase(nn.Module):
     def _resolve_deferred_range_check(self):
         pending, self._pending_range = getattr(self, "_pending_range", None), None
         if pending is not None:
-            flag, ev = pending
+            flag, ev, *nonfinite = pending  # (flag, event): flag = "all finite"; (flag, event, True): flag = "something was not"
             ev.synchronize()
-            if not bool(flag):
+            if bool(flag) == bool(nonfinite):
                 self.range_fallbacks += 1
                 raise FloatingPointError("cotracker_amd: the previous streaming chunk produced non-finite tracks on the "
                                          "split-half (f16x3) back end (an activation left the f16 range |x| < 65504, or the "
@@ -695,6 +709,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     """Sliding-window / streaming tracker (cotracker3_online.py:159-541)."""
 
     _TRANSIENT = {**CoTrackerThreeBase._TRANSIENT, "_overlap_hint": type(None)}
+    _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups)
     online_ind = _online_attr("ind")
     online_track_support = _online_attr("track_support")
     online_coords_predicted = _online_attr("coords_predicted")
@@ -707,12 +722,16 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         self._online = [OnlineState(track_support=[None] * self.corr_levels)]  # (B > 1: replicated by the first call)
         self.online_track_feat = [None] * self.corr_levels  # unused by v3, kept for API parity
         self._overlap_hint = None  # the predictor's verdict for the NEXT call (it resizes chunks into fresh tensors)
+        if self._gstream is not None:  # its buffers (and the graphs captured on them) serve the next stream of the same shape
+            self._gstream.live = False
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200,
                 is_online=False):
         B, T, space_attn, grouped = self._check_inputs(video, queries, is_train, add_space_attn)
         assert self.window_len >= 2
+        if grouped and is_online and self.stream_groups:
+            return self._forward_stream_groups(video, queries, iters, fmaps_chunk_size, space_attn)
         if grouped and is_online:
             raise NotImplementedError("streaming (is_online=True) takes one query set per video: a query-group call (video [1,...], "
                                       f"queries [{B},...]) is available offline and sliding only")
@@ -731,6 +750,98 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             return [self._video_gen(video[b], queries[b], fmaps_chunk_size, states[b] if is_online else None, hint,
                                     None if f0 is None else f0[b]) for b in group]
         return self._track(video, iters, make_gens, states, units=B if grouped else None, space_attn=space_attn, shared=grouped)
+
+    # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
+    def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
+        """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is
+        encoded once (through the stream's ONE feature cache), the pyramid is built once into the resident buffers of
+        ops.StreamGroups, and three launches step the state of all G*N points: support (the points whose query frame entered this
+        window), begin (carry-over and masks), then the groups' windows, then commit (history rows, non-finite flag).  Returns
+        views of the first ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place."""
+        G, N = queries.shape[:2]
+        T = video.shape[1]
+        S = self.window_len
+        step = S // 2
+        st = self._online_states(1, T)[0]
+        hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None
+        self._resolve_deferred_range_check()
+        H, W = video.shape[3] // self.stride, video.shape[4] // self.stride
+        sizes = [(H >> l, W >> l) for l in range(self.corr_levels)]
+        gs = self._gstream
+        if gs is None or not gs.fits(queries, S, step, self.stride, sizes):
+            assert st.ind == 0, "the query groups of a stream are fixed by its first call"
+            self._drop_graphs()  # (they hold pointers into the old stream's buffers)
+            gs = self._gstream = ops.StreamGroups(queries, S, step, self.stride, sizes)
+        elif not gs.live:
+            assert st.ind == 0, "the query groups of a stream are fixed by its first call"
+            gs.restart(queries)
+        assert not gs.closed, "a chunk shorter than the window ends the stream"
+        gs.closed = T < S
+        ind = st.ind
+        f0 = self._encode_online(video[0], chunk, S, step, st, hint)
+        gs.set_pyramid(f0)
+        gs.sample_support(ind)  # independent of the Linear back end: not repeated by a range-guard re-run
+        graphed = bool(self.hip_graph)
+        guard = self.precision == "f16x3" and self.range_guard
+        deferred = graphed and self.stream_range_check == "deferred"
+        # what a window step overwrites and a re-run must find again: the history rows the carry-over reads (commit rewrites them)
+        saved = [h_[:, ind:ind + S - step].clone() for h_ in gs.hist] if guard and not deferred and ind > 0 else None
+
+        def run(precision, flag):
+            pw = self.packed(video.device, precision)
+            gs.begin(ind)
+            self._stream_group_windows(gs, iters, pw, graphed, space_attn)
+            gs.commit(ind, T, flag)
+
+        run(self.precision, guard)
+        if guard and deferred:
+            flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            flag.copy_(gs.nonfinite, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._pending_range = (flag, ev, True)
+        elif guard and bool(gs.nonfinite.item()):
+            self.range_fallbacks += 1
+            warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left the f16 "
+                          "range (|x| < 65504) or the input is non-finite; re-running this streaming call of all query groups on "
+                          "the exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
+            if saved is not None:
+                for h_, s_ in zip(gs.hist, saved):
+                    h_[:, ind:ind + S - step].copy_(s_)
+            gs.nonfinite.zero_()
+            run("f32", False)
+        st.ind = ind + step
+        out = gs.history(ind + T)
+        # reference-visible online_* attributes (API parity): the state of ALL groups, views of the resident buffers
+        st.track_support, (st.coords_predicted, st.vis_predicted, st.conf_predicted) = gs.support, out
+        self.last_logits = out[1:]
+        return (out[0], torch.sigmoid(out[1]), torch.sigmoid(out[2]), None)
+
+    def _stream_group_windows(self, gs, iters, pw, graphed, space_attn):
+        """The windows of one streaming query-group call on the resident buffers of `gs`: one group after the other ("loop") or
+        sub-batches of at most CTK_MAX_BATCH groups as shared-pyramid joint windows ("joint").  graphed: every sub-batch replays
+        its own captured graph -- the cache keeps one graph per sub-batch of THIS stream state (G = 18 in joint mode: 16 + 2) and
+        drops whatever else it held; the option table stays part of the key."""
+        joint = self.batch_mode == "joint"
+        size = L.MAX_BATCH if joint else 1
+        kw = dict(iters=int(iters), max_corr_rows=int(self.max_corr_rows), space_attn=bool(space_attn))
+        base = ("stream_groups", gs.serial, id(pw), int(iters), int(self.max_corr_rows), tuple(self.model_resolution),
+                int(self.stride), bool(space_attn), joint, L.option_values()) if graphed else None
+        if graphed and any(k[:-1] != base for k in self._graphs):
+            self._drop_graphs()
+        for g0 in range(0, gs.G, size):
+            g1 = min(g0 + size, gs.G)
+            wins = gs.windows(g0, g1, self._scale_xy(), **kw)
+            if graphed:
+                g = self._graphs.get(base + (g0,))
+                if g is None:
+                    g = self._graphs[base + (g0,)] = (ops.WindowBatchGraph(wins, pw, self.max_corr_rows, shared=True) if joint else
+                                                      ops.WindowGraph(wins[0], pw))
+                g.launch()
+            elif joint:
+                ops.forward_windows(wins, pw, self.max_corr_rows, shared=True)
+            else:
+                ops.forward_window(wins[0], pw)
 
     def _encode_online(self, video, chunk, S, step, st, hint):
         """Streaming: consecutive chunks overlap by S - step frames (predictor.py:225,288-290 feeds the last 2*step frames

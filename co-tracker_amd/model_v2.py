@@ -158,6 +158,11 @@ class CoTracker2(TrackerBase):
         if mode != "loop":
             raise ValueError(f"batch_mode must be 'loop' or 'joint', got {mode!r}")
 
+    @TrackerBase.stream_groups.setter
+    def stream_groups(self, on):  # streaming takes one query set per video here: the device stream state is the CoTracker3 online model's
+        if on:
+            raise NotImplementedError("CoTracker2 (model_v2.py) streams one query set per video; stream_groups on a v2 model is not implemented")
+
     def init_video_online_processing(self):  # cotracker.py:187-191
         self._resolve_deferred_range_check()  # the last chunk of the previous stream (graph streaming defers its check by one call)
         self._online = [OnlineState()]  # (B > 1: replicated by the first call)

@@ -186,10 +186,12 @@ def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = No
     return out
 
 
-def avg_pool2_nhwc(x: torch.Tensor) -> torch.Tensor:
-    _chk_f32(x)
+def avg_pool2_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk_f32(x, out)
     F_, H, W, Cc = x.shape
-    out = torch.empty(F_, H // 2, W // 2, Cc, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(F_, H // 2, W // 2, Cc, device=x.device, dtype=torch.float32)
+    assert out.shape == (F_, H // 2, W // 2, Cc)
     L.check(L.load().ctk_avg_pool2_nhwc(_ptr(x), F_, H, W, _ptr(out), _stream()), "ctk_avg_pool2_nhwc")
     return out
 
@@ -552,6 +554,134 @@ class WindowBatchGraph(WindowGraph):
         self.wins = batch.wins
         self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights, weights.struct_for(batch.S),
                       batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.keep[2:5]], list(batch.arr), batch.device)
+
+
+# ------------------------------------------------------------------------------------------
+# stream state of G query groups over one live video (include/ctk.h: ctk_stream_begin / _support / _commit)
+# ------------------------------------------------------------------------------------------
+class StreamGroups:
+    """The device-resident state of G query groups streamed over ONE video, in the layouts the shared joint window wants, and
+    the three launches that step it (csrc/stream.hip).  Everything a window call reads or writes lives here and keeps its
+    address for the life of the object -- the pyramid [S,H_l,W_l,128], the window state coords [G,S,N,2] / vis / conf [G,S,N],
+    point_mask [G,N], the support accumulators support[l] [G*N,49,128] -- so captured window graphs bake these pointers in and
+    nothing is stacked or copied per call.  The history [G,T_cap,N,.] is a capacity buffer outside the graphs, grown
+    geometrically.  ``serial`` changes whenever the baked-in buffers are re-allocated (graph cache key)."""
+
+    _serial = 0
+
+    def __init__(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes):
+        G, N = queries.shape[:2]
+        dev = queries.device
+        self.G, self.N, self.S, self.step, self.stride = G, N, S, step, float(stride)
+        self.level_sizes = tuple(level_sizes)
+        self.queries = queries.reshape(G * N, 3).float().contiguous().clone()
+        self.pyr = [torch.empty(S, h, w, 128, device=dev) for h, w in level_sizes]
+        self.coords = torch.empty(G, S, N, 2, device=dev)
+        self.vis = torch.empty(G, S, N, device=dev)
+        self.conf = torch.empty(G, S, N, device=dev)
+        self.mask = torch.empty(G, N, device=dev, dtype=torch.uint8)
+        self.support = [torch.zeros(G * N, 49, 128, device=dev) for _ in level_sizes]
+        self.nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.T_cap = 0
+        self.hist = None
+        self.reserve(4 * S)
+        self.closed = False  # a chunk shorter than the window ends the stream
+        self.live = True     # False: the stream it carried is over, the buffers wait for restart()
+        StreamGroups._serial += 1
+        self.serial = StreamGroups._serial
+        self._wins = {}
+
+    def fits(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes) -> bool:
+        return (tuple(queries.shape[:2]) == (self.G, self.N) and queries.device == self.queries.device and
+                (S, step, float(stride), tuple(level_sizes)) == (self.S, self.step, self.stride, self.level_sizes))
+
+    def restart(self, queries: torch.Tensor) -> None:
+        """A new stream on the same buffers (same shapes: the captured graphs stay valid)."""
+        self.queries.copy_(queries.reshape(self.G * self.N, 3))
+        for s_ in self.support:
+            s_.zero_()
+        for h_ in self.hist:
+            h_.zero_()
+        self.nonfinite.zero_()
+        self.closed, self.live = False, True
+
+    def reserve(self, T: int) -> None:
+        """History capacity of at least T frames: doubled when it runs out (one copy per doubling, not per call); rows past the
+        committed ones are zero."""
+        if T <= self.T_cap:
+            return
+        cap = max(T, 2 * self.T_cap)
+        dev = self.queries.device
+        new = [torch.zeros(self.G, cap, self.N, 2, device=dev), torch.zeros(self.G, cap, self.N, device=dev),
+               torch.zeros(self.G, cap, self.N, device=dev)]
+        if self.hist is not None:
+            for n_, o_ in zip(new, self.hist):
+                n_[:, :self.T_cap].copy_(o_)
+        self.hist, self.T_cap = new, cap
+
+    def history(self, T: int):
+        """Views of the first T history rows: (coords [G,T,N,2] pixels, vis logits [G,T,N], conf logits [G,T,N])."""
+        return tuple(h_[:, :T] for h_ in self.hist)
+
+    def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
+        a = L.StreamArgs()
+        a.G, a.N, a.S, a.step, a.ind, a.T_valid, a.T_cap, a.stride = self.G, self.N, self.S, self.step, ind, T_valid, self.T_cap, self.stride
+        a.queries = _ptr(self.queries)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_) for h_ in self.hist)
+        a.coords, a.vis, a.conf, a.point_mask = _ptr(self.coords), _ptr(self.vis), _ptr(self.conf), _ptr(self.mask)
+        for l, f_ in enumerate(self.pyr):
+            a.H[l], a.W[l], a.fmaps[l], a.support[l] = f_.shape[1], f_.shape[2], _ptr(f_), _ptr(self.support[l])
+        a.nonfinite = _ptr(self.nonfinite) if flag else None
+        return a
+
+    def set_pyramid(self, f0: torch.Tensor) -> None:
+        """Level-0 features [T <= S, H, W, 128] of this call's chunk into the resident pyramid: the last frame repeated up to S
+        frames (cotracker3_online.py:321-328 pads the video; the encoder is per frame), then the pooled levels."""
+        T = f0.shape[0]
+        self.pyr[0][:T].copy_(f0)
+        if T < self.S:
+            self.pyr[0][T:].copy_(f0[-1:].expand(self.S - T, -1, -1, -1))
+        for l in range(1, len(self.pyr)):
+            avg_pool2_nhwc(self.pyr[l - 1], out=self.pyr[l])
+
+    def begin(self, ind: int) -> None:
+        self.reserve(ind + self.S)
+        L.check(L.load().ctk_stream_begin(C.byref(self._args(ind)), _stream()), "ctk_stream_begin")
+
+    def sample_support(self, ind: int) -> None:
+        self.reserve(ind + self.S)
+        L.check(L.load().ctk_stream_support(C.byref(self._args(ind)), _stream()), "ctk_stream_support")
+
+    def commit(self, ind: int, T_valid: int, flag: bool) -> None:
+        L.check(L.load().ctk_stream_commit(C.byref(self._args(ind, T_valid, flag)), _stream()), "ctk_stream_commit")
+
+    def windows(self, g0: int, g1: int, scale_xy, **window_kw) -> List[Window]:
+        """The windows of groups g0 .. g1-1 on the resident buffers (slices of one allocation each: WindowBatch(shared=True)).
+        Cached: a captured graph keeps the very Window objects it was captured on."""
+        key = (g0, g1, tuple(scale_xy), tuple(sorted(window_kw.items())))
+        if key not in self._wins:
+            N = self.N
+            self._wins[key] = group_windows(self.pyr, [s_[g0 * N:g1 * N] for s_ in self.support], self.coords[g0:g1], self.vis[g0:g1],
+                                            self.conf[g0:g1], scale_xy, point_mask=self.mask[g0:g1], use_aux_stream=False, **window_kw)
+        return self._wins[key]
+
+    def __getstate__(self):  # ctypes structs with raw pointers are rebuilt on demand
+        return {**self.__dict__, "_wins": {}}
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = {} if k == "_wins" else copy.deepcopy(v, memo)
+        StreamGroups._serial += 1
+        new.serial = StreamGroups._serial  # other buffers: graphs captured on the original do not apply
+        return new
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        StreamGroups._serial += 1
+        self.serial = StreamGroups._serial
 
 
 def corr_volume(win: Window) -> torch.Tensor:

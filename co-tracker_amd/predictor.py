@@ -220,7 +220,12 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                 queries[:, :, 1:] *= queries.new_tensor([(iw - 1) / (W - 1), (ih - 1) / (H - 1)])
                 if add_support_grid:
                     g = get_points_on_a_grid(self.support_grid_size, self.interp_shape, device=video_chunk.device)
-                    queries = torch.cat([queries, torch.cat([torch.zeros_like(g[:, :, :1]), g], dim=2)], dim=1)
+                    g = torch.cat([torch.zeros_like(g[:, :, :1]), g], dim=2)
+                    queries = torch.cat([queries, g.expand(queries.shape[0], -1, -1)], dim=1)  # (every query group gets the grid)
+                if queries.shape[0] > 1 and B == 1 and not self.v2:
+                    # G query sets over the one live stream (model.stream_groups): later calls return tracks [G,T,N,2] and
+                    # visibility [G,T,N].  (CoTracker2 streams one query set per video: its model call raises, as before.)
+                    self.model.stream_groups = True
             elif grid_size > 0:
                 pts = get_points_on_a_grid(grid_size, self.interp_shape, device=video_chunk.device)
                 self.N = grid_size ** 2

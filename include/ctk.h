@@ -47,6 +47,8 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged): + ctk_stream_begin / ctk_stream_support / ctk_stream_commit on the struct ctk_stream_args: the stream state
+ *       of G query groups over one live video, stepped on the device.
  *   v9, additive (number unchanged): ctk_window_batch.reserved is now `flags` (same offset and size; 0 = as before) with the bit
  *       CTK_BATCH_SHARED_FMAPS (B query groups over ONE video: one pyramid copy, one grouped sampler launch per chunk piece);
  *       + ctk_corr_embed_batch and its workspace query (corr_embed of a joint window on its own, for tests).
@@ -234,6 +236,51 @@ int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model
 int ctk_corr_embed_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes);
 int ctk_corr_embed_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* x, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ---- stream state step: G query groups over ONE live video, state resident on the device ---------------------------------
+ * The streaming glue of the reference (cotracker3_online.py:349-360 history growth, :411-440 support accumulation, :457-484
+ * carry-over and attention mask, :498-510 write-back) as three launches per streaming call for ALL G*N points, on buffers the
+ * caller owns and keeps between calls:
+ *   queries      [G*N,3]       (frame, x, y) in model-resolution pixels, as the reference's `queries`
+ *   history      hist_coords [G,T_cap,N,2] pixels, hist_vis / hist_conf [G,T_cap,N] logits; rows [0, ind + T_valid) are valid
+ *                after a commit; a capacity buffer the caller grows (T_cap >= ind + S is checked by every entry point)
+ *   window state coords [G,S,N,2] feature units, vis / conf [G,S,N], point_mask [G*N]: the layouts ctk_window_batch wants under
+ *                CTK_BATCH_SHARED_FMAPS, so they may be the window's (and a captured graph's) own buffers
+ *   support[l]   [G*N,49,128] persistent accumulators, zero when the stream starts
+ * `ind` is the first frame of the window (a multiple of `step`), the same number for every group; overlap = S - step.
+ *   begin:   point_mask = qframe < ind + S.  A point with ind > 0 and qframe < ind + overlap takes history rows ind .. ind+overlap-1
+ *            (coords / stride), the last of them repeated `step` times; any other point takes its query (x, y) / stride and zero
+ *            logits.  qframe = (integer) queries[.,0], truncated as torch's .long().
+ *   support: per level, ONLY the points with left <= qframe < right (left = 0 at ind == 0, else ind + step; right = ind + S) are
+ *            sampled at frame qframe - ind of fmaps[l] (NHWC [S,H_l,W_l,128], the window's pyramid) at (x, y) / stride / 2^l
+ *            with the arithmetic of ctk_sample_support, and ADDED into support[l]; every other row is neither read nor written.
+ *            The sample ranges of successive calls are disjoint: each point is written once per stream.
+ *   commit:  history rows ind .. ind+T_valid-1 = (coords * stride, vis, conf) of window rows 0 .. T_valid-1 (T_valid < S: a short
+ *            last chunk).  nonfinite (optional): a device word that gets 1 OR-ed in when a committed value is not finite.
+ * Every float step is the IEEE operation of the reference expression (division, multiplication, addition; no contraction), so a
+ * stream stepped by these calls carries the same bits as one stepped by the torch expressions.  Each entry point validates what
+ * it reads (NULL: CTK_E_NULL; G, N, S, step <= 0, step >= S, ind < 0, ind % step != 0, T_cap < ind + S, T_valid outside 1..S,
+ * stride outside (0, 65536], level sizes <= 0: CTK_E_SHAPE) before any launch; no host synchronisation; capture-safe.       */
+typedef struct ctk_stream_args {
+  int32_t G, N;               /* query groups, points per group                                   */
+  int32_t S, step;            /* window length and advance per call (window_len, window_len // 2) */
+  int32_t ind;                /* first frame of this call's window                                */
+  int32_t T_valid;            /* commit: frames of the chunk (1..S)                               */
+  int32_t T_cap;              /* frames the history buffers hold                                  */
+  float stride;               /* model stride: pixels per level-0 feature cell (4)                */
+  const float* queries;
+  float* hist_coords; float* hist_vis; float* hist_conf;
+  float* coords; float* vis; float* conf;
+  uint8_t* point_mask;
+  int32_t H[CTK_LEVELS];      /* support: level sizes of fmaps                                    */
+  int32_t W[CTK_LEVELS];
+  const float* fmaps[CTK_LEVELS];
+  float* support[CTK_LEVELS];
+  int32_t* nonfinite;         /* commit: optional flag word, or NULL                              */
+} ctk_stream_args;
+int ctk_stream_begin(const ctk_stream_args* a, void* stream);
+int ctk_stream_support(const ctk_stream_args* a, void* stream);
+int ctk_stream_commit(const ctk_stream_args* a, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
