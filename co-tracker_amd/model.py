@@ -370,6 +370,41 @@ class TrackerBase(nn.Module):
                 torch.cuda.current_stream().synchronize()
             self._graphs = {}
 
+    def _graph_cache(self, generation, pw):
+        """The one cache of captured window graphs, self._graphs.  A graph bakes in its buffers, the weights `pw` and the option
+        table as read at capture, so those join `generation` -- what the caller's graphs have in common (shapes, iters, model
+        settings) -- in every key.  ONE eviction rule: graphs of any other generation are dropped (their workspaces freed) before
+        a new one is captured.  The host paths have one graph per generation, so one live graph per model; the sub-batches of a
+        streaming query-group call (G = 18 in joint mode: 16 + 2) are the members of one.  Returns get(member, build) -> the
+        member's graph, captured by build() on a miss."""
+        gen = (generation, id(pw), pw.device.index, L.option_values())
+        if any(k[0] != gen for k in self._graphs):
+            self._drop_graphs()
+
+        def get(member, build):
+            if (gen, member) not in self._graphs:
+                self._graphs[gen, member] = build()
+            return self._graphs[gen, member]
+        return get
+
+    def _graphed_windows(self, reqs, iters, pw, ident=(), **window_kw):
+        """Streaming with hip_graph: one window per request (see _run_windows) through ONE captured hipGraph per (shapes, iters,
+        model settings `ident`, number of requests).  It is captured on private clones of the first call's windows (the static
+        buffers), which later calls refresh in place before the replay.  Returns every window's result(): views of the static
+        buffers, overwritten by the next replay (CoTracker3 consumes them at once; CoTracker2 hands out clones, as ever)."""
+        captured = []
+
+        def capture():
+            captured.extend(self._window(r, iters, **window_kw).clone() for r in reqs)
+            return self._window_graph(captured, pw, len(reqs) > 1)
+        shapes = tuple(t_.shape for t_ in ops.window_tensors(reqs[0]))
+        g = self._graph_cache((shapes, len(reqs), int(iters), ident), pw)(None, capture)
+        if not captured:
+            for win, r in zip(g.wins, reqs):
+                win.refresh(r)
+        g.launch()
+        return [w_.result() for w_ in g.wins]
+
     # device-side caches (ctypes structs with raw pointers) are rebuilt on demand: keep them out of pickles / deep copies
     # (the online state is ordinary tensors and is copied, less its feature cache: OnlineState.__getstate__)
     _TRANSIENT = {"_packed": dict, "_graphs": dict, "_hip_encoder": type(None), "_pending_range": type(None)}
@@ -402,39 +437,43 @@ class TrackerBase(nn.Module):
         return new
 
     # -- f16 range guard ----------------------------------------------------------------
-    def _guarded(self, run, snapshot=None, restore=None, deferred=False):
-        """run(precision) -> (coords, vis_logit[, conf_logit]) under the f16 range guard described in __init__.
-        deferred=True (streaming): the finiteness flag of this call is copied to the host asynchronously and examined at
-        the START of the next call, so the stream of chunk calls never waits for the GPU; a hit then raises (the chunk
-        that overflowed has already been returned, and the online state is poisoned: the stream must be re-run with
-        ``precision="f32"``)."""
+    def _guarded(self, run, snapshot, restore, deferred=False, nonfinite=None, what="forward"):
+        """run(precision, check) -> outputs (coords, vis_logit[, conf_logit]) under the f16 range guard described in __init__;
+        check: whether the guard examines this run.  The verdict is read from the outputs (all finite?) or, `nonfinite` given,
+        from that device flag word, which the run raises itself (non-zero: something was not finite).  On a hit the state is put
+        back -- restore(what snapshot() returned before the run) -- and `what` re-runs on the exact-f32 back end.
+        deferred=True (streaming): the flag of this call is copied to the host asynchronously and examined at the START of the
+        next call, so the stream of chunk calls never waits for the GPU; a hit then raises (the chunk that overflowed has
+        already been returned, and the online state is poisoned: the stream must be re-run with ``precision="f32"``)."""
         self._resolve_deferred_range_check()
-        out = run(self.precision)
-        if self.precision == "f16x3" and self.range_guard:
-            finite = torch.stack([torch.isfinite(o).all() for o in out]).all()
-            if deferred:
-                flag = torch.empty((), dtype=torch.bool, pin_memory=True)
-                flag.copy_(finite, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._pending_range = (flag, ev)
-                return out
-            if not bool(finite):
-                self.range_fallbacks += 1
-                warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left "
-                              "the f16 range (|x| < 65504) or the input is non-finite; re-running this forward on the "
-                              "exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
-                if snapshot is not None:  # (offline / sliding: no online state to put back before the exact-f32 re-run)
-                    restore(snapshot)
-                out = run("f32")
+        guard = self.precision == "f16x3" and self.range_guard
+        saved = snapshot() if guard and not deferred else None
+        out = run(self.precision, guard)
+        if not guard:
+            return out
+        # (flag, the value of it that means "fine"): interpreted on the host, whichever way round the device computed it
+        flag, fine = (torch.stack([torch.isfinite(o).all() for o in out]).all(), True) if nonfinite is None else (nonfinite, 0)
+        if deferred:
+            pinned = torch.empty(flag.shape, dtype=flag.dtype, pin_memory=True)
+            pinned.copy_(flag, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._pending_range = (pinned, fine, ev)
+        elif flag.item() != fine:
+            self.range_fallbacks += 1
+            warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left "
+                          f"the f16 range (|x| < 65504) or the input is non-finite; re-running this {what} on the "
+                          "exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
+            restore(saved)
+            out = run("f32", False)
         return out
 
     def _resolve_deferred_range_check(self):
         pending, self._pending_range = getattr(self, "_pending_range", None), None
         if pending is not None:
-            flag, ev, *nonfinite = pending  # (flag, event): flag = "all finite"; (flag, event, True): flag = "something was not"
+            pinned, fine, ev = pending
             ev.synchronize()
-            if bool(flag) == bool(nonfinite):
+            if pinned.item() != fine:
                 self.range_fallbacks += 1
                 raise FloatingPointError("cotracker_amd: the previous streaming chunk produced non-finite tracks on the "
                                          "split-half (f16x3) back end (an activation left the f16 range |x| < 65504, or the "
@@ -467,32 +506,35 @@ class TrackerBase(nn.Module):
         back as they were before the re-run.  units: the G query groups of a query-group call (one video; see __init__) -- they
         take the place of the B videos, and "joint" runs them in sub-batches of at most CTK_MAX_BATCH, each under its own
         range guard.  Returns forward's tuple: (coords, sigmoid of every logit ..., None)."""
-        B = video.shape[0] if units is None else units
-        joint = B > 1 and self.batch_mode == "joint"
-        if joint and units is not None:
-            groups = [list(range(g0, min(g0 + L.MAX_BATCH, B))) for g0 in range(0, B, L.MAX_BATCH)]
-        else:
-            groups = [list(range(B))] if joint else [[b] for b in range(B)]
+        joint, groups = self._index_groups(video.shape[0] if units is None else units, units is not None)
         graphed = bool(states is not None and self.hip_graph)
         # streaming with the window graph (CoTrackerOnlinePredictor): deferred range check, the chunk stream stays asynchronous
         deferred = graphed and len(groups) == 1 and self.stream_range_check == "deferred"
         parts = []
         for group in groups:
-            def run(precision):
+            def run(precision, _check):
                 pw = self.packed(video.device, precision)
                 outs = self._drive(make_gens(group), lambda reqs: self._run_windows(reqs, iters, pw, graphed, **window_kw))
                 return tuple(torch.stack(o) for o in zip(*outs)) if joint else outs[0]
 
-            def restore(saved):
-                for b, st in zip(group, saved):
+            def restore(saved):  # (offline / sliding: no online state to put back before the exact-f32 re-run)
+                for b, st in zip(group, saved or ()):
                     states[b] = st
-            parts.append(self._guarded(run, None if states is None else [replace(states[b]) for b in group], restore, deferred))
+            parts.append(self._guarded(run, lambda: states and [replace(states[b]) for b in group], restore, deferred))
         if joint:
             out = parts[0] if len(parts) == 1 else tuple(torch.cat(o) for o in zip(*parts))
         else:
             out = tuple(torch.stack(o) for o in zip(*parts))
         self.last_logits = out[1:]
         return (out[0], *[torch.sigmoid(o) for o in out[1:]], None)
+
+    def _index_groups(self, n, units=False):
+        """How a call over n videos -- or over the n query groups of one video (units) -- splits into window calls: -> (joint,
+        index groups).  "loop": one index per group; "joint": ONE group of all n videos, or sub-batches of at most CTK_MAX_BATCH
+        query groups."""
+        joint = n > 1 and self.batch_mode == "joint"
+        size = (L.MAX_BATCH if units else n) if joint else 1
+        return joint, [list(range(i, min(i + size, n))) for i in range(0, n, size)]
 
     @staticmethod
     def _drive(gens, run_windows):
@@ -515,6 +557,37 @@ class TrackerBase(nn.Module):
             for b in range(B):
                 step(b, res[b])
         return outs
+
+    # -- what the sliding / streaming host code of both model families shares -------------
+    @staticmethod
+    def _pad_history(T, step, *hist):
+        """Streaming: the prediction histories of the chunks so far, grown by the rows this chunk adds (cotracker3_online.py:349-360,
+        cotracker.py:247-259)."""
+        p = min(step, T - step)
+        return [F.pad(h_, (0, 0) * (h_.dim() - 1) + (0, p)) for h_ in hist]
+
+    def _carry_over(self, qframes, ind, S, step, preds, inits):
+        """The window at frame ind > 0 starts from its predecessor (cotracker3_online.py:457-482, cotracker.py:306-327): for the
+        tracks queried before the end of the overlap, the overlapping rows of the prediction histories `preds` (coordinates first,
+        in pixels), the last one repeated over the `step` new frames, replace `inits`.  Returns the new inits."""
+        overlap = S - step
+        copy_over = (qframes < ind + overlap)[None, :]
+        prevs = [p_[ind:ind + overlap] / self.stride if i == 0 else p_[ind:ind + overlap] for i, p_ in enumerate(preds)]
+        prevs = [torch.cat([p_, p_[-1:].expand(step, *p_.shape[1:])], dim=0) for p_ in prevs]
+        return [torch.where(copy_over[..., None] if x0.dim() == 3 else copy_over, p_, x0).contiguous() for p_, x0 in zip(prevs, inits)]
+
+    def _hip_encode(self, frames, step, normalize):
+        """frames [T,3,H,W] in 0..255 -> NHWC level-0 features [T,H/4,W/4,128] from this device's HipEncoder (built on first use),
+        `step` frames per call, every chunk written straight into its frame range of the preallocated output."""
+        enc = getattr(self, "_hip_encoder", None)
+        if enc is None or enc.device != frames.device:
+            from .encoder_hip import HipEncoder
+            enc = self._hip_encoder = HipEncoder(self.fnet, frames.device, normalize=normalize)
+        T, _, H, W = frames.shape
+        out = torch.empty(T, H // self.stride, W // self.stride, self.latent_dim, device=frames.device, dtype=torch.float32)
+        for t0 in range(0, T, step):
+            enc(frames[t0:t0 + step].float().contiguous(), out=out[t0:t0 + step])
+        return out
 
 
 class CoTrackerThreeBase(TrackerBase):
@@ -554,80 +627,52 @@ class CoTrackerThreeBase(TrackerBase):
         # by storage aliasing; bench.py --workload c4_online --feature-cache)
         self.online_feature_cache = False
 
-    def _graphed_windows(self, reqs, iters, pw, space_attn):
-        """Run one window per request (see _run_windows) through the captured hipGraph of this (shapes, iters, weights, B)
-        combination: static buffers are created (and the graph captured) on first use, then only refreshed in place and
-        replayed.  One request: the single-window graph (ctk_window_graph_create); several: ONE graph of the joint window
-        (ctk_window_batch_graph_create).  Returns the static (coords, vis, conf) of every video (overwritten by the next
-        call).  The option table is part of the key: a graph bakes in the options read at capture."""
-        fm, coords = reqs[0][0], reqs[0][2]
-        B = len(reqs)
-        key = (tuple(tuple(f.shape) for f in fm), coords.shape[1], int(iters), id(pw), coords.device.index,
-               int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), space_attn, B, L.option_values())
-        g = self._graphs.get(key)
-        if g is None:
-            wins = [ops.Window([f.clone() for f in fm_], [s_.clone() for s_ in sup_], c_.clone(), v_.clone(), f_.clone(),
-                               self._scale_xy(), iters=iters, point_mask=m_.clone(), max_corr_rows=self.max_corr_rows,
-                               space_attn=space_attn) for fm_, sup_, c_, v_, f_, m_, _ in reqs]
-            self._drop_graphs()  # one live graph per model: a new shape replaces the old one (frees its workspace)
-            g = ops.WindowGraph(wins[0], pw) if B == 1 else ops.WindowBatchGraph(wins, pw, self.max_corr_rows)
-            self._graphs = {key: g}
-        else:
-            for win, (fm_, sup_, c_, v_, f_, m_, _) in zip(g.wins, reqs):
-                st_fm, st_sup, sc, sv, sf, sm = win.keep
-                for d, s_ in zip(st_fm, fm_):
-                    d.copy_(s_)
-                for d, s_ in zip(st_sup, sup_):
-                    d.copy_(s_)
-                sc.copy_(c_)
-                sv.copy_(v_)
-                sf.copy_(f_)
-                sm.copy_(m_)
-        g.launch()
-        return [w_.keep[2:5] for w_ in g.wins]
+    def _window(self, r, iters, space_attn=True):
+        return ops.Window(r.fmaps, r.support, r.coords, r.vis, r.conf, self._scale_xy(), iters=iters, point_mask=r.mask,
+                          max_corr_rows=self.max_corr_rows, space_attn=space_attn)
+
+    def _window_graph(self, wins, pw, joint, shared=False):
+        """One window: the single-window graph (ctk_window_graph_create); joint: ONE graph of the joint window of all of them
+        (ctk_window_batch_graph_create)."""
+        return ops.WindowBatchGraph(wins, pw, self.max_corr_rows, shared=shared) if joint else ops.WindowGraph(wins[0], pw)
 
     def _run_windows(self, reqs, iters, pw, graphed, space_attn=True, shared=False):
-        """One window per request -- (fmaps, support, coords, vis, conf, point_mask or None, owned), one request per video -- all of
-        them in ONE call when there are several (joint batch mode).  The window overwrites its coords / vis / conf: a request
-        that is not `owned` hands over state it still needs (the sliding carry-over), so the window gets clones.  shared: the
-        requests are query groups of one video (the same fmaps): several of them run as one shared-pyramid joint window.
-        Returns every video's (coords, vis, conf)."""
+        """One window per request (ops.WindowRequest), one request per video -- all of them in ONE call when there are several
+        (joint batch mode).  The window overwrites its coords / vis / conf: a request that is not `owned` hands over state it
+        still needs (the sliding carry-over), so the window gets clones.  shared: the requests are query groups of one video (the
+        same fmaps): several of them run as one shared-pyramid joint window.  Returns every video's (coords, vis, conf)."""
         if graphed:
-            return self._graphed_windows(reqs, iters, pw, space_attn)
+            ident = (int(self.max_corr_rows), tuple(self.model_resolution), int(self.stride), space_attn)
+            return self._graphed_windows(reqs, iters, pw, ident, space_attn=space_attn)
         if shared and len(reqs) > 1:
             wins = self._group_windows(reqs, iters, space_attn)
-            ops.forward_windows(wins, pw, self.max_corr_rows, shared=True)
-            return [w_.keep[2:5] for w_ in wins]
-        wins = []
-        for fm, support, coords, vis, conf, mask, owned in reqs:
-            if not owned:
-                coords, vis, conf = coords.clone(), vis.clone(), conf.clone()
-            wins.append(ops.Window(fm, support, coords, vis, conf, self._scale_xy(), iters=iters, point_mask=mask,
-                                   max_corr_rows=self.max_corr_rows, space_attn=space_attn))
+        else:
+            wins = [self._window(r if r.owned else r._replace(coords=r.coords.clone(), vis=r.vis.clone(), conf=r.conf.clone()),
+                                 iters, space_attn) for r in reqs]
         if len(wins) == 1:
             ops.forward_window(wins[0], pw)
         else:
-            ops.forward_windows(wins, pw, self.max_corr_rows)
-        return [w_.keep[2:5] for w_ in wins]
+            ops.forward_windows(wins, pw, self.max_corr_rows, shared=shared)
+        return [w_.result() for w_ in wins]
 
     def _group_windows(self, reqs, iters, space_attn):
         """The requests of G query groups over one video as the windows of a shared joint window: the groups' state is stacked
         into one [G,S,N,.] tensor each (a copy, so nobody's carry-over is overwritten); the support patches are used where they
         are when they already lie one group behind the other (slices of the one sample_support result of _group_context) and
         stacked otherwise."""
-        N = reqs[0][2].shape[1]
+        N = reqs[0].coords.shape[1]
+        cols = ops.WindowRequest(*zip(*reqs))  # field by field: cols.coords = every group's coords, ...
 
         def consecutive(parts):
             step = parts[0].numel() * parts[0].element_size()
             return all(p_.is_contiguous() and p_.data_ptr() == parts[0].data_ptr() + i * step for i, p_ in enumerate(parts))
         support = []
         for l in range(self.corr_levels):
-            parts = [r[1][l] for r in reqs]
+            parts = [sup[l] for sup in cols.support]
             support.append(torch.cat(parts) if not consecutive(parts) else
                            parts[0].as_strided((len(parts) * N, *parts[0].shape[1:]), parts[0].stride()))
-        coords, vis, conf = (torch.stack([r[i] for r in reqs]) for i in (2, 3, 4))
-        mask = None if reqs[0][5] is None else torch.stack([r[5] for r in reqs])
-        return ops.group_windows(reqs[0][0], support, coords, vis, conf, self._scale_xy(), point_mask=mask, iters=iters,
+        mask = None if cols.mask[0] is None else torch.stack(cols.mask)
+        return ops.group_windows(reqs[0].fmaps, support, torch.stack(cols.coords), torch.stack(cols.vis), torch.stack(cols.conf), self._scale_xy(), point_mask=mask, iters=iters,
                                  max_corr_rows=self.max_corr_rows, space_attn=space_attn)
 
     def _group_context(self, video, queries, chunk, pad_to=None):
@@ -657,17 +702,11 @@ class CoTrackerThreeBase(TrackerBase):
         speed as one 120-frame batch in situ (C3 step 1 521 vs 1 517-1 533 ms; 100 vs 102-130 ms in
         tools/bench_encoder_chunk.py) at a tenth of the activation memory; every chunk is normalised straight into its
         frame range of the output (no torch.cat of the 755 MB feature tensor)."""
-        T, _, H, W = frames.shape
         step = max(1, min(int(chunk), int(self.encoder_chunk)))
-        out = torch.empty(T, H // self.stride, W // self.stride, self.latent_dim, device=frames.device, dtype=torch.float32)
         if self.encoder_backend == "hip" and self.encoder_dtype == torch.float32:
-            enc = getattr(self, "_hip_encoder", None)
-            if enc is None or enc.device != frames.device:
-                from .encoder_hip import HipEncoder
-                enc = self._hip_encoder = HipEncoder(self.fnet, frames.device)
-            for t0 in range(0, T, step):
-                enc(frames[t0:t0 + step].float().contiguous(), out=out[t0:t0 + step])
-            return out
+            return self._hip_encode(frames, step, normalize=True)
+        T, _, H, W = frames.shape
+        out = torch.empty(T, H // self.stride, W // self.stride, self.latent_dim, device=frames.device, dtype=torch.float32)
         for t0 in range(0, T, step):
             x = 2 * (frames[t0:t0 + step] / 255.0) - 1.0  # cotracker3_online.py:320
             if self.encoder_dtype == torch.float32:
@@ -758,9 +797,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         ops.StreamGroups, and three launches step the state of all G*N points: support (the points whose query frame entered this
         window), begin (carry-over and masks), then the groups' windows, then commit (history rows, non-finite flag).  Returns
         views of the first ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place."""
-        G, N = queries.shape[:2]
-        T = video.shape[1]
-        S = self.window_len
+        T, S = video.shape[1], self.window_len
         step = S // 2
         st = self._online_states(1, T)[0]
         hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None
@@ -782,66 +819,40 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         gs.set_pyramid(f0)
         gs.sample_support(ind)  # independent of the Linear back end: not repeated by a range-guard re-run
         graphed = bool(self.hip_graph)
-        guard = self.precision == "f16x3" and self.range_guard
-        deferred = graphed and self.stream_range_check == "deferred"
+        joint, groups = self._index_groups(gs.G, units=True)
+        kw = dict(iters=int(iters), max_corr_rows=int(self.max_corr_rows), space_attn=bool(space_attn))
         # what a window step overwrites and a re-run must find again: the history rows the carry-over reads (commit rewrites them)
-        saved = [h_[:, ind:ind + S - step].clone() for h_ in gs.hist] if guard and not deferred and ind > 0 else None
+        rows = slice(ind, ind + S - step)
 
-        def run(precision, flag):
+        def run(precision, check):
+            """begin, the groups' windows -- one group after the other ("loop") or shared-pyramid joint windows of at most
+            CTK_MAX_BATCH groups ("joint"); graphed: each replays its own graph, a member of this stream state's generation --, commit."""
             pw = self.packed(video.device, precision)
             gs.begin(ind)
-            self._stream_group_windows(gs, iters, pw, graphed, space_attn)
-            gs.commit(ind, T, flag)
+            graphs = graphed and self._graph_cache(("stream_groups", gs.serial, tuple(self.model_resolution), int(self.stride), joint,
+                                                    *kw.values()), pw)
+            for group in groups:
+                wins = gs.windows(group[0], group[-1] + 1, self._scale_xy(), **kw)
+                if graphed:
+                    graphs(group[0], lambda: self._window_graph(wins, pw, joint, shared=True)).launch()
+                elif joint:
+                    ops.forward_windows(wins, pw, self.max_corr_rows, shared=True)
+                else:
+                    ops.forward_window(wins[0], pw)
+            gs.commit(ind, T, check)
 
-        run(self.precision, guard)
-        if guard and deferred:
-            flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            flag.copy_(gs.nonfinite, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._pending_range = (flag, ev, True)
-        elif guard and bool(gs.nonfinite.item()):
-            self.range_fallbacks += 1
-            warnings.warn("cotracker_amd: non-finite tracks from the split-half (f16x3) back end -- an activation left the f16 "
-                          "range (|x| < 65504) or the input is non-finite; re-running this streaming call of all query groups on "
-                          "the exact-f32 MFMA back end", RuntimeWarning, stacklevel=3)
-            if saved is not None:
-                for h_, s_ in zip(gs.hist, saved):
-                    h_[:, ind:ind + S - step].copy_(s_)
+        def restore(saved):
+            for h_, s_ in zip(gs.hist, saved or ()):
+                h_[:, rows].copy_(s_)
             gs.nonfinite.zero_()
-            run("f32", False)
+        self._guarded(run, lambda: ind > 0 and [h_[:, rows].clone() for h_ in gs.hist], restore,
+                      graphed and self.stream_range_check == "deferred", gs.nonfinite, "streaming call of all query groups")
         st.ind = ind + step
         out = gs.history(ind + T)
         # reference-visible online_* attributes (API parity): the state of ALL groups, views of the resident buffers
         st.track_support, (st.coords_predicted, st.vis_predicted, st.conf_predicted) = gs.support, out
         self.last_logits = out[1:]
         return (out[0], torch.sigmoid(out[1]), torch.sigmoid(out[2]), None)
-
-    def _stream_group_windows(self, gs, iters, pw, graphed, space_attn):
-        """The windows of one streaming query-group call on the resident buffers of `gs`: one group after the other ("loop") or
-        sub-batches of at most CTK_MAX_BATCH groups as shared-pyramid joint windows ("joint").  graphed: every sub-batch replays
-        its own captured graph -- the cache keeps one graph per sub-batch of THIS stream state (G = 18 in joint mode: 16 + 2) and
-        drops whatever else it held; the option table stays part of the key."""
-        joint = self.batch_mode == "joint"
-        size = L.MAX_BATCH if joint else 1
-        kw = dict(iters=int(iters), max_corr_rows=int(self.max_corr_rows), space_attn=bool(space_attn))
-        base = ("stream_groups", gs.serial, id(pw), int(iters), int(self.max_corr_rows), tuple(self.model_resolution),
-                int(self.stride), bool(space_attn), joint, L.option_values()) if graphed else None
-        if graphed and any(k[:-1] != base for k in self._graphs):
-            self._drop_graphs()
-        for g0 in range(0, gs.G, size):
-            g1 = min(g0 + size, gs.G)
-            wins = gs.windows(g0, g1, self._scale_xy(), **kw)
-            if graphed:
-                g = self._graphs.get(base + (g0,))
-                if g is None:
-                    g = self._graphs[base + (g0,)] = (ops.WindowBatchGraph(wins, pw, self.max_corr_rows, shared=True) if joint else
-                                                      ops.WindowGraph(wins[0], pw))
-                g.launch()
-            elif joint:
-                ops.forward_windows(wins, pw, self.max_corr_rows, shared=True)
-            else:
-                ops.forward_window(wins[0], pw)
 
     def _encode_online(self, video, chunk, S, step, st, hint):
         """Streaming: consecutive chunks overlap by S - step frames (predictor.py:225,288-290 feeds the last 2*step frames
@@ -905,11 +916,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         vis_pred = torch.zeros(T, N, device=dev)
         conf_pred = torch.zeros(T, N, device=dev)
         if is_online:
-            if st.coords_predicted is not None:  # :349-360
-                p = min(step, T - step)
-                coords_pred = F.pad(st.coords_predicted, (0, 0, 0, 0, 0, p))
-                vis_pred = F.pad(st.vis_predicted, (0, 0, 0, p))
-                conf_pred = F.pad(st.conf_predicted, (0, 0, 0, p))
+            if st.coords_predicted is not None:
+                coords_pred, vis_pred, conf_pred = self._pad_history(T, step, st.coords_predicted, st.vis_predicted, st.conf_predicted)
             left = 0 if st.ind == 0 else st.ind + step
             right = st.ind + S
             sample_mask = ((qframes >= left) & (qframes < right)).float()[:, None, None]  # :411-414
@@ -930,21 +938,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         num_windows = (T - S + step - 1) // step + 1
         indices = [st.ind] if is_online else range(0, step * num_windows, step)
         for ind in indices:
-            if ind > 0:  # carry-over from the previous window, :457-482
-                overlap = S - step
-                copy_over = (qframes < ind + overlap)[None, :]
-                cprev = coords_pred[ind:ind + overlap] / self.stride
-                cprev = torch.cat([cprev, cprev[-1:].expand(step, -1, -1)], dim=0)
-                vprev = vis_pred[ind:ind + overlap]
-                vprev = torch.cat([vprev, vprev[-1:].expand(step, -1)], dim=0)
-                fprev = conf_pred[ind:ind + overlap]
-                fprev = torch.cat([fprev, fprev[-1:].expand(step, -1)], dim=0)
-                coords_init = torch.where(copy_over[..., None], cprev, coords_init).contiguous()
-                vis_init = torch.where(copy_over, vprev, vis_init).contiguous()
-                conf_init = torch.where(copy_over, fprev, conf_init).contiguous()
+            if ind > 0:
+                coords_init, vis_init, conf_init = self._carry_over(qframes, ind, S, step, (coords_pred, vis_pred, conf_pred),
+                                                                    (coords_init, vis_init, conf_init))
             mask = (qframes < ind + S).to(torch.uint8).contiguous()  # attention_mask :484, used as :493-496
             fm = pyr if is_online else [p_[ind:ind + S] for p_ in pyr]
-            coords, vis, conf = yield (fm, support, coords_init, vis_init, conf_init, mask, False)
+            coords, vis, conf = yield ops.WindowRequest(fm, support, coords_init, vis_init, conf_init, mask, False)
             S_trim = T if is_online else min(T - ind, S)
             coords_pred[ind:ind + S] = (coords * float(self.stride))[:S_trim]
             vis_pred[ind:ind + S] = vis[:S_trim]
@@ -991,5 +990,5 @@ class CoTrackerThreeOffline(CoTrackerThreeBase):
         coords = qcoords[None].expand(T, N, 2).contiguous()
         vis = torch.zeros(T, N, device=dev)
         conf = torch.zeros(T, N, device=dev)
-        coords, vis, conf = yield (pyr, support, coords, vis, conf, None, True)
+        coords, vis, conf = yield ops.WindowRequest(pyr, support, coords, vis, conf, None, True)
         return coords * float(self.stride), vis, conf

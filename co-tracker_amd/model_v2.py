@@ -7,7 +7,6 @@ attributes, ``forward`` signature / 3-tuple return, online-state methods and the
 """
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
@@ -198,51 +197,27 @@ class CoTracker2(TrackerBase):
         vis [S,N], track_mask [S,N] float 0/1, point_mask [N] uint8.  Returns (coords [S,N,2] feature units, vis logits [S,N])."""
         return self._run_windows([(pyr, coords, track_feat, vis, track_mask, point_mask)], iters, pw, False)[0]
 
+    def _window(self, req, iters):
+        return ops.V2Window(*req, iters)
+
+    def _window_graph(self, wins, pw, joint):
+        return ops.V2WindowGraph(wins[0], pw)
+
     def _run_windows(self, reqs, iters, pw, graphed):
-        """The window of one request (forward_window's arguments): one direct call, or one hipGraph replay of it in streaming mode."""
+        """The window of one request (forward_window's arguments): one direct call, or -- streaming -- one replay of the hipGraph the
+        whole window (iters x (5 + ~390) launches) was captured into; its results are handed out as clones."""
         (req,) = reqs  # (no joint batch mode: every group is one video)
         if graphed:
-            return [self._graphed_window(*req, iters, pw)]
+            return [tuple(t_.clone() for t_ in res) for res in self._graphed_windows(reqs, iters, pw)]
         pyr, coords, track_feat, vis, track_mask, point_mask = req
-        win = ops.V2Window(pyr, coords.clone(), track_feat.clone(), vis.contiguous(), track_mask, point_mask, iters)
+        win = self._window((pyr, coords.clone(), track_feat.clone(), vis.contiguous(), track_mask, point_mask), iters)
         ops.forward_window_v2(win, pw)
-        return [(win.keep[1], win.vis_out)]
-
-    def _graphed_window(self, pyr, coords, track_feat, vis, track_mask, point_mask, iters, pw):
-        """Streaming: the whole window (iters x (5 + ~390) launches) is captured once per shape and replayed per chunk."""
-        # (the option table is part of the key: a captured graph bakes in the options read at capture, include/ctk.h)
-        key = (tuple(tuple(f.shape) for f in pyr), coords.shape[1], int(iters), id(pw), coords.device.index, L.option_values())
-        g = self._graphs.get(key)
-        if g is None:
-            self._drop_graphs()  # one live graph per model
-            win = ops.V2Window([f.clone() for f in pyr], coords.clone(), track_feat.clone(), vis.clone(), track_mask.clone(),
-                               point_mask.clone(), iters)
-            g = ops.V2WindowGraph(win, pw)
-            self._graphs = {key: g}
-        else:
-            st_pyr, c_, tf_, v_, tm_, pm_ = g.win.keep
-            for d, s_ in zip(st_pyr, pyr):
-                d.copy_(s_)
-            c_.copy_(coords)
-            tf_.copy_(track_feat)
-            v_.copy_(vis)
-            tm_.copy_(track_mask)
-            pm_.copy_(point_mask)
-        g.launch()
-        return g.win.keep[1].clone(), g.win.vis_out.clone()
+        return [win.result()]
 
     def _encode(self, frames):
         """frames [T,3,H,W] in 0..255 -> NHWC level-0 features [T,H/4,W/4,128], NOT normalised (cotracker.py:273-275)."""
         if self.encoder_backend == "hip":
-            enc = self._hip_encoder
-            if enc is None or enc.device != frames.device:
-                from .encoder_hip import HipEncoder
-                enc = self._hip_encoder = HipEncoder(self.fnet, frames.device, normalize=False)
-            T, _, H, W = frames.shape
-            out = torch.empty(T, H // self.stride, W // self.stride, self.latent_dim, device=frames.device, dtype=torch.float32)
-            for t0 in range(0, T, self.encoder_chunk):
-                enc(frames[t0:t0 + self.encoder_chunk].float().contiguous(), out=out[t0:t0 + self.encoder_chunk])
-            return out
+            return self._hip_encode(frames, self.encoder_chunk, normalize=False)
         return self.fnet(2 * (frames.float() / 255.0) - 1.0).float().permute(0, 2, 3, 1).contiguous()
 
     def _video_gen(self, video, queries, st, f0=None):
@@ -257,10 +232,8 @@ class CoTracker2(TrackerBase):
         qcoords = (queries[:, 1:3] / self.stride).contiguous()
         coords_pred = torch.zeros(T, N, 2, device=dev)
         vis_pred = torch.zeros(T, N, device=dev)
-        if is_online and st.coords_predicted is not None:  # :247-259
-            p = min(step, T - step)
-            coords_pred = F.pad(st.coords_predicted, (0, 0, 0, 0, 0, p))
-            vis_pred = F.pad(st.vis_predicted, (0, 0, 0, p))
+        if is_online and st.coords_predicted is not None:
+            coords_pred, vis_pred = self._pad_history(T, step, st.coords_predicted, st.vis_predicted)
         # encoder; padding the video with its last frame (:264-270) == repeating the last feature map (fnet is per-frame)
         pad = (S - T) if is_online else (S - T % S) % S
         if f0 is None:
@@ -284,14 +257,8 @@ class CoTracker2(TrackerBase):
         vis_init = torch.full((S, N), 10.0, device=dev)
         for ind in indices:
             overlap = S - step
-            if ind > 0:  # :306-327
-                copy_over = (qframes < ind + overlap)[None, :]
-                cprev = coords_pred[ind:ind + overlap] / self.stride
-                cprev = torch.cat([cprev, cprev[-1:].expand(step, -1, -1)], dim=0)
-                vprev = vis_pred[ind:ind + overlap]
-                vprev = torch.cat([vprev, vprev[-1:].expand(step, -1)], dim=0)
-                coords_init = torch.where(copy_over[..., None], cprev, coords_init).contiguous()
-                vis_init = torch.where(copy_over, vprev, vis_init).contiguous()
+            if ind > 0:
+                coords_init, vis_init = self._carry_over(qframes, ind, S, step, (coords_pred, vis_pred), (coords_init, vis_init))
             amask = qframes < ind + S                                                        # attention_mask, :331-333
             tmask = qframes[None, :] <= torch.arange(ind, ind + S, device=dev)[:, None]      # track_mask, :338-344
             if ind > 0:

@@ -4,6 +4,7 @@ Every function enqueues HIP kernels from libctk_hip.so on the current torch stre
 computes on the CPU and nothing falls back to PyTorch ops.
 """
 import ctypes as C
+from collections import namedtuple
 from typing import List, Optional, Sequence
 
 import torch
@@ -113,26 +114,31 @@ def layernorm(x: torch.Tensor, gamma=None, beta=None, eps: float = 1e-6, out_spl
     return y
 
 
+def _attn_args(q, k, v, nbatch: int, N1: int, N2: int, q_bs: int, kv_bs: int, inner: int, splits: int, out_split: bool,
+               key_mask, query_mask):
+    """ctk_attn_args of `nbatch` problems q [N1 rows] over k / v [N2 rows]: batch strides q_bs (q, out) / kv_bs (k, v) and inner
+    stride `inner`, in rows.  Returns (args, out, split-K partials): the caller keeps the third alive across its launch."""
+    _chk_f32(q, k, v)
+    out = torch.empty(nbatch * N1, L.HID // 32, 2, 32, device=q.device, dtype=torch.float16) if out_split else torch.empty_like(q)
+    a = L.AttnArgs()
+    a.q, a.q_ld, a.q_bs, a.q_is = _ptr(q), L.HID, q_bs, inner
+    a.k, a.v, a.kv_ld, a.kv_bs, a.kv_is = _ptr(k), _ptr(v), L.HID, kv_bs, inner
+    a.out, a.o_ld, a.o_bs, a.o_is = _ptr(out), (2 * L.HID if out_split else L.HID), q_bs, inner
+    a.o_split = int(out_split)
+    a.nbatch, a.n1, a.n2 = nbatch, N1, N2
+    a.splits = splits
+    part = torch.empty(splits * nbatch * 8 * N1 * 50, device=q.device, dtype=torch.float32) if splits > 1 else None
+    a.partial = _ptr(part)
+    a.key_mask, a.query_mask = _ptr(key_mask), _ptr(query_mask)  # uint8, per key / per query (CoTracker2 attention mask)
+    return a, out, part
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: int = 1, out_split: bool = False,
               key_mask: Optional[torch.Tensor] = None, query_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q [B,N1,384], k/v [B,N2,384] (8 heads x 48, heads contiguous in the last dim) -> [B,N1,384]
-    (or its SH form [B*N1, 12, 2, 32] float16 when out_split)."""
-    _chk_f32(q, k, v)
-    B, N1, _ = q.shape
-    N2 = k.shape[1]
-    out = torch.empty(B * N1, L.HID // 32, 2, 32, device=q.device, dtype=torch.float16) if out_split else torch.empty_like(q)
-    a = L.AttnArgs()
-    a.q, a.q_ld, a.q_bs, a.q_is = _ptr(q), L.HID, N1, 1
-    a.k, a.v, a.kv_ld, a.kv_bs, a.kv_is = _ptr(k), _ptr(v), L.HID, N2, 1
-    a.out, a.o_ld, a.o_bs, a.o_is = _ptr(out), (2 * L.HID if out_split else L.HID), N1, 1
-    a.o_split = int(out_split)
-    a.nbatch, a.n1, a.n2 = B, N1, N2
-    a.splits = splits
-    part = None
-    if splits > 1:
-        part = torch.empty(splits * B * 8 * N1 * 50, device=q.device, dtype=torch.float32)
-    a.partial = _ptr(part)
-    a.key_mask, a.query_mask = _ptr(key_mask), _ptr(query_mask)  # uint8 [N2] / [N1] (CoTracker2 attention mask)
+    (or its SH form [B*N1, 12, 2, 32] float16 when out_split).  key_mask [N2] / query_mask [N1] uint8."""
+    (B, N1, _), N2 = q.shape, k.shape[1]
+    a, out, _part = _attn_args(q, k, v, B, N1, N2, N1, N2, 1, splits, out_split, key_mask, query_mask)
     L.check(L.load().ctk_attention(C.byref(a), _stream()), "ctk_attention")
     return out
 
@@ -143,23 +149,9 @@ def attention_batch2(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: 
     video, then the track, then the inner batch = frame) -> out [Bo, N1, Bi, 384] (or its SH form [Bo*N1*Bi, 12, 2, 32]).
     Batch (bo, bi) attends q[bo, :, bi] over k / v[bo, :, bi]: ONE launch with inner = Bi, row strides bs = 1, is = Bi and the
     outer strides N1*Bi (q, out) and N2*Bi (k, v) -- different for the two sides.  key_mask [Bo, N2] / query_mask [Bo, N1] uint8."""
-    _chk_f32(q, k, v)
-    Bo, N1, Bi, _ = q.shape
-    N2 = k.shape[1]
+    (Bo, N1, Bi, _), N2 = q.shape, k.shape[1]
     assert k.shape == (Bo, N2, Bi, L.HID) and v.shape == k.shape
-    out = torch.empty(Bo * N1 * Bi, L.HID // 32, 2, 32, device=q.device, dtype=torch.float16) if out_split else torch.empty_like(q)
-    a = L.AttnArgs()
-    a.q, a.q_ld, a.q_bs, a.q_is = _ptr(q), L.HID, 1, Bi
-    a.k, a.v, a.kv_ld, a.kv_bs, a.kv_is = _ptr(k), _ptr(v), L.HID, 1, Bi
-    a.out, a.o_ld, a.o_bs, a.o_is = _ptr(out), (2 * L.HID if out_split else L.HID), 1, Bi
-    a.o_split = int(out_split)
-    a.nbatch, a.n1, a.n2 = Bo * Bi, N1, N2
-    a.splits = splits
-    part = None
-    if splits > 1:
-        part = torch.empty(splits * Bo * Bi * 8 * N1 * 50, device=q.device, dtype=torch.float32)
-    a.partial = _ptr(part)
-    a.key_mask, a.query_mask = _ptr(key_mask), _ptr(query_mask)
+    a, out, _part = _attn_args(q, k, v, Bo * Bi, N1, N2, 1, 1, Bi, splits, out_split, key_mask, query_mask)
     b2 = L.AttnBatch2()
     b2.inner, b2.reserved = Bi, 0
     b2.q_os, b2.kv_os, b2.o_os = N1 * Bi, N2 * Bi, N1 * Bi
@@ -241,7 +233,6 @@ def corrblock_sample(pyr_nhwc: Sequence[torch.Tensor], targets: torch.Tensor, co
     L.check(L.load().ctk_corrblock_sample(fm, Hs, Ws, S, N, _ptr(targets), _ptr(coords), _ptr(out), _stream()),
             "ctk_corrblock_sample")
     return out
-
 
 
 # ------------------------------------------------------------------------------------------
@@ -328,7 +319,35 @@ def update_former_ex(x: torch.Tensor, x_split: bool, S: int, N: int, fw: "L.Form
                                      _stream()), "ctk_update_former_ex")
     return delta
 
-class V2Window:
+
+# One CoTracker3 window as a host model asks for it: Window's tensors in the order of Window.keep, and whether the window may
+# overwrite coords / vis / conf (`owned`; if not, the caller still needs them -- the sliding carry-over -- and the window gets clones).
+WindowRequest = namedtuple("WindowRequest", "fmaps support coords vis conf mask owned")
+
+
+def window_tensors(parts) -> List[torch.Tensor]:
+    """The tensors of a window's `keep`, or of a request in that order, as one flat list (per-level lists expanded; no None, no flag)."""
+    return [t_ for p_ in parts for t_ in (p_ if isinstance(p_, list) else [p_]) if torch.is_tensor(t_)]
+
+
+class _WindowTensors:
+    """What Window and V2Window know about the tensors behind their ctypes struct.  keep: the constructor's tensor arguments in
+    its order, held alive; state: those the window call updates in place, which a graph warm-up must save and restore."""
+
+    def inputs(self) -> List[torch.Tensor]:  # every tensor a graph replay must refresh, in the one fixed order of `keep`
+        return window_tensors(self.keep)
+
+    def clone(self):
+        """A window of the same arguments on private copies of all inputs: the static buffers of a captured graph."""
+        return self._like(*[[t_.clone() for t_ in p_] if isinstance(p_, list) else p_ if p_ is None else p_.clone() for p_ in self.keep])
+
+    def refresh(self, src) -> None:
+        """copy_ every input from `src`: a window of the same shape, or a request (its tensors in the order of `keep`)."""
+        for d, s_ in zip(self.inputs(), window_tensors(getattr(src, "keep", src))):
+            d.copy_(s_)
+
+
+class V2Window(_WindowTensors):
     """ctypes ctk_v2_window_args of one CoTracker2 window plus the tensors it points to (coords / track_feat are
     updated in place by forward_window_v2, vis_out receives the visibility logits)."""
 
@@ -350,13 +369,18 @@ class V2Window:
         self.args = a
         self.S, self.N = S, N
         self.keep = (list(pyr), coords, track_feat, vis, track_mask, point_mask)
+        self.state = (coords, track_feat)
+        self._like = lambda *parts: V2Window(*parts, iters)
         self.device = coords.device
+
+    def result(self):  # what the host code consumes after the call: (coords, visibility logits)
+        return self.state[0], self.vis_out
 
 
 # ------------------------------------------------------------------------------------------
 # window-level ops
 # ------------------------------------------------------------------------------------------
-class Window:
+class Window(_WindowTensors):
     """Holds the ctypes ctk_window_args plus the tensors it points to."""
 
     def __init__(self, fmaps: Sequence[torch.Tensor], support: Sequence[torch.Tensor], coords: torch.Tensor,
@@ -385,7 +409,12 @@ class Window:
         self.args = a
         self.S, self.N = S, N
         self.keep = (list(fmaps), list(support), coords, vis, conf, point_mask)
+        self.state = (coords, vis, conf)
+        self._like = lambda fm, sup, c, v, f, m: Window(fm, sup, c, v, f, scale_xy, iters, m, max_corr_rows, use_aux_stream, space_attn)
         self.device = coords.device
+
+    def result(self):  # what the host code consumes after the call: the state, updated in place
+        return self.state
 
 
 _ws_cache = {}
@@ -401,15 +430,12 @@ def aux_stream(device) -> torch.cuda.Stream:
     return _aux_streams[key]
 
 
-
 def _workspace(nbytes: int, device) -> torch.Tensor:
     key = (device.index if device.index is not None else torch.cuda.current_device())
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        _ws_cache.pop(key, None)
-        buf = None
-        buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        _ws_cache[key] = buf
+        buf = _ws_cache[key] = None  # (the old buffer is released before the larger one is allocated)
+        buf = _ws_cache[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
     return buf
 
 
@@ -443,9 +469,9 @@ class WindowGraph:
     caller refreshes the CONTENTS of win's tensors in place (``copy_``) and calls ``launch()``."""
 
     def __init__(self, win: Window, weights):
-        self.win, self.wins = win, [win]
+        self.wins = [win]
         self._capture("ctk_forward_window", "ctk_window_graph_create", win.args, weights, weights.struct_for(win.S),
-                      _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args)), win.keep[2:5], [win.args], win.device)
+                      _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args)), win.state, [win.args], win.device)
 
     def _capture(self, direct: str, create: str, args, weights, wstruct, nbytes: int, state, iter_slots, device) -> None:
         """The capture protocol of every window graph.  direct / create: the C entry points of the direct call and of the
@@ -490,9 +516,9 @@ class V2WindowGraph(WindowGraph):
     """hipGraph of one CoTracker2 window (ctk_v2_window_graph_create): the contract of WindowGraph."""
 
     def __init__(self, win: V2Window, weights):
-        self.win, self.wins = win, [win]
+        self.wins = [win]
         self._capture("ctk_forward_window_v2", "ctk_v2_window_graph_create", win.args, weights, weights.struct,
-                      _v2_workspace_bytes(win, weights), win.keep[1:3], [win.args], win.device)
+                      _v2_workspace_bytes(win, weights), win.state, [win.args], win.device)
 
 
 class WindowBatch:
@@ -553,7 +579,7 @@ class WindowBatchGraph(WindowGraph):
         self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk, shared)
         self.wins = batch.wins
         self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights, weights.struct_for(batch.S),
-                      batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.keep[2:5]], list(batch.arr), batch.device)
+                      batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.state], list(batch.arr), batch.device)
 
 
 # ------------------------------------------------------------------------------------------
