@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X CoTracker3 hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one ``CoTrackerPredictor.forward`` (resize -> CNN encoder -> pyramid -> all windows x 6
@@ -11,7 +11,13 @@ weights in sliding-window mode (``offline=False, window_len=16``: 14 windows of 
 metric = tracked-point-frames/s = N*T / seconds per step, summed over ranks (weak scaling: every
 rank tracks its own 6400-point chunk; results are all-gathered inside the timed region).
 
-Prints ONE JSON line (rank 0) with the contract keys plus
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K timed steps, the --dump-outputs
+files, and ONE JSON line (rank 0) with the contract keys (metric, value, unit, ms_per_step, dtype, config, ...).
+
+--full runs the same warm-up and timed steps and then adds, in the same JSON line, everything else the benchmark measures or checks
+(each takes time of its own after the timed steps; --no-profile / --no-extra-lines / --no-cpu-baseline drop single legs of it):
+  steps_bit_identical -- every timed step's outputs compared bit for bit with the first timed step's
+  all_gather_ms -- N>1: the path's one collective timed alone, with its share of a step (a gate: < 1 %)
   roofline     -- the TIME-DOMINANT CLASS of kernels of the step (all Linear GEMM launches call-weighted, or the correlation
                   sampler): algorithmic flops / HIP-event duration vs the split-half MFMA ceiling (2500/3 TF/s), with
                   frac_at_sustained_clock = issued f16 MFMA rate / the rate ctk_probe_mfma(kind 2) holds in THIS run
@@ -80,9 +86,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c3_sliding", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extra-lines", action="store_true", help="skip the extra timed rows (exact-f32 back end, C2, C4) of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks: bitwise comparison of the "
+                         "timed steps, parity against the reference goldens, the profiled step with per-kernel and roofline figures, "
+                         "the extra timed rows, the CPU baseline and (--gpus > 1) the all-gather timing.  Off by default: a plain run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the profiled step (kernels, roofline, sustained_mfma, gemm_clock)")
+    ap.add_argument("--no-extra-lines", action="store_true", help="--full: skip the extra timed rows (exact-f32 back end, C2, C4)")
     ap.add_argument("--no-graph", action="store_true", help="c4_online: direct launches instead of the captured hipGraph")
     ap.add_argument("--feature-cache", action="store_true", help="c4_online: opt in to model.online_feature_cache (re-use the previous "
                     "chunk's features for the overlapping frames; the reference re-encodes them)")
@@ -716,8 +727,10 @@ def main():
     sync()
     # Every timed step of a non-streaming workload sees the same video and queries, and the library claims bit-reproducible
     # results: keep REFERENCES to every step's outputs (fresh tensors per call: no copy, no host wait inside the timed region)
-    # and compare them bit for bit after the closing synchronisation (`steps_bit_identical` in the line).  One C3 step is
-    # 84 sampler launches x 25 600 workgroups + ~8 600 other launches, so this is a free production-shape soak of every kernel.
+    # and, with --full, compare them bit for bit after the closing synchronisation (`steps_bit_identical` in the line).  One C3
+    # step is 84 sampler launches x 25 600 workgroups + ~8 600 other launches, so this is a production-shape soak of every kernel.
+    # The timed region is the same in a plain and a --full run: the references are kept, and the parity tap (`tapped`) is in place,
+    # in both, so that the two report the same ms_per_step.
     kept = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -727,7 +740,7 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     steps_bit_identical = None
-    if kept:
+    if kept and args.full:
         def same(a, b):
             if a is None or b is None:
                 return a is b
@@ -752,9 +765,9 @@ def main():
     sec_per_step = float(tmax.item()) / args.steps
     assert torch.isfinite(out[0]).all()
     assert pred.model.range_fallbacks == 0 if hasattr(pred.model, "range_fallbacks") else True
-    # the one collective of the path, timed alone (every rank takes part; the profiled extra step below is rank 0 only)
+    # --full: the one collective of the path, timed alone (every rank takes part; the profiled extra step below is rank 0 only)
     all_gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         tr_l, vi_l = local_step()
         n_tot = n_gather if c5 else world * N
         sync()
@@ -773,7 +786,7 @@ def main():
     result = {
         "metric": "tracked-point-frames/sec (N*T/s)", "value": round(value, 1), "unit": "tracked-point-frames/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(sec_per_step * 1e3, 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "full": bool(args.full),
         "dtype": "f32 (Linear layers as split-half f16 MFMA x3, f32 accumulate)" if args.precision == "f16x3" else "f32",
         "data": "synthetic",
         "rccl_ranks": dist.get_world_size() if world > 1 else 1, "dist_backend": args.dist_backend if world > 1 else None,
@@ -793,9 +806,10 @@ def main():
         result["config"]["online_feature_cache"] = bool(pred.model.online_feature_cache)
         result["config"]["graph_nodes"] = next(iter(pred.model._graphs.values())).nodes if pred.model._graphs else 0
 
+    # Everything from here to the printed line is --full.
     # parity of what was just timed: the last timed step's model-level outputs against the reference's CPU run of the
     # same workload (world == 1, c3_sliding / c2_offline have goldens at exactly these sizes), plus C2 end to end
-    if rank == 0:
+    if rank == 0 and args.full:
         parity = {}
         golden_name = {"c3_sliding": "c3_g80", "c2_offline": "c2", "c1_standin": "c1", "c3_offline_g40": "c3_off",
                        "c5_shard": "c5_chunk0"}.get(args.workload)
@@ -813,7 +827,7 @@ def main():
                 parity["c2"] = {"error": f"{type(e).__name__}: {e}"}
         result["parity"] = parity
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         # one extra step with the library's HIP-event recorder on (events on the launch stream)
         if streaming:
             pred.model.hip_graph = False  # events cannot be recorded inside a captured graph: profile the direct launches
@@ -866,7 +880,7 @@ def main():
                 result["gemm_clock"] = gemm_clock_probe(dev)
             except Exception as e:  # a reported diagnosis, never a reason to lose the bench line
                 result["gemm_clock"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and args.workload == "c3_sliding" and args.precision == "f16x3" and not args.no_extra_lines:
+    if rank == 0 and world == 1 and args.full and args.workload == "c3_sliding" and args.precision == "f16x3" and not args.no_extra_lines:
         # driver-timed versions of the numbers that used to exist only as builder-run files in profiles/ (<15 s together)
         extra = {}
         for key, kw in (("c3_sliding_f32", dict(name="c3_sliding", precision="f32", steps=2, warmup=1)),
@@ -879,13 +893,13 @@ def main():
                 extra[key] = {"error": f"{type(e).__name__}: {e}"}
         result["extra_lines"] = extra
         result["value_f32"] = extra["c3_sliding_f32"].get("value")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.workload)
     if rank == 0:
         print(json.dumps(result))
     if world > 1:
         dist.destroy_process_group()
-        if args.dist_backend == "nccl" and not args.single_device and not result["all_gather_ok"]:
+        if args.dist_backend == "nccl" and not args.single_device and result["all_gather_ok"] is False:
             raise SystemExit(f"the all-gather took {all_gather_ms:.2f} ms = {100 * result['all_gather_share_of_step']:.2f} % of a step "
                              "(bar: < 1 %): the path's one collective is no longer noise -- see SURVEY 8e / DESIGN 6")
 

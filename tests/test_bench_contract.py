@@ -1,6 +1,6 @@
 """bench.py contract pieces that need no GPU: workload table vs BASELINE.json, the roofline object, the CPU baseline
 (numpy oracle on a bounded sample), the PMC-traffic attachment rule and the --dump-outputs writer; on the GPU, --steps and
---dump-outputs of a real run."""
+--dump-outputs of a real run, and what a plain run leaves to --full."""
 import json
 import os
 import subprocess
@@ -26,6 +26,15 @@ def test_default_workload_is_the_baseline_config():
     finally:
         sys.argv = old
     assert (a.gpus, a.workload, a.precision) == (1, "c3_sliding", "f16x3") and a.steps >= 1 and a.warmup >= 1
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """A plain run is the headline alone; everything else the benchmark measures or checks is asked for with --full."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    a = bench.parse()
+    assert a.full is True and (a.steps, a.warmup) == (20, 5) and not (a.no_cpu_baseline or a.no_profile or a.no_extra_lines)
 
 
 def test_roofline_objects():
@@ -139,16 +148,19 @@ def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
 @pytest.mark.gpu
 def test_steps_and_dump_outputs_of_a_real_run(tmp_path):
     """Two runs of the same command (each a fresh process): --steps is the number of timed steps, and the dumped outputs of the
-    last timed step are the same arrays, of the shapes a caller of the predictor receives."""
+    last timed step are the same arrays, of the shapes a caller of the predictor receives.  --full: the bitwise comparison of the
+    timed steps is one of the checks a plain run leaves out."""
     lines = []
     for d in ("a", "b"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3", "--warmup", "1",
-                            "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True,
+                           timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
     H, W, T, G, *_ = bench.WORKLOADS["tiny"]
     line = lines[0]
     assert line["steps"] == 3 and line["steps_bit_identical"]["steps_compared"] == 3 and line["steps_bit_identical"]["identical"]
+    assert line["full"] is True and "c2" in line["parity"]
     assert sorted(line["dumped_outputs"]) == ["confidence_logits", "pred_tracks", "pred_visibility", "visibility_logits"]
     for name in line["dumped_outputs"]:
         a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
@@ -156,3 +168,30 @@ def test_steps_and_dump_outputs_of_a_real_run(tmp_path):
     tracks = np.load(tmp_path / "a" / "pred_tracks.npy")
     assert tracks.shape == (1, T, G * G, 2) and np.load(tmp_path / "a" / "pred_visibility.npy").shape == (1, T, G * G)
     assert 0 <= tracks[..., 0].mean() < W and 0 <= tracks[..., 1].mean() < H
+
+
+@pytest.mark.gpu
+def test_a_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the line carries the headline and its configuration and nothing that takes a run or a check of its own; the
+    dumped outputs are those of a --full run of the same arguments."""
+    lines = {}
+    for d, more in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / d)] + more, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1, out
+        lines[d] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    H, W, T, G, *_ = bench.WORKLOADS["tiny"]
+    assert plain["full"] is False and plain["steps"] == 2 and plain["warmup"] == 1 and plain["n_gpus"] == 1
+    assert plain["metric"] == full["metric"] and plain["unit"] == full["unit"] == "tracked-point-frames/s" and plain["dtype"] == full["dtype"]
+    assert plain["higher_is_better"] is True and plain["ms_per_step"] > 0 and plain["config"] == full["config"]
+    assert abs(plain["value"] - G * G * T / (plain["ms_per_step"] * 1e-3)) <= 1e-3 * plain["value"]
+    moved = ("parity", "kernels", "profiled_step_ms", "hip_kernels_ms", "sustained_mfma", "roofline", "roofline_gemm", "roofline_sampler",
+             "gemm_clock", "extra_lines", "value_f32", "cpu_baseline", "traffic_source")
+    assert not [k for k in moved if k in plain] and plain["steps_bit_identical"] is None and plain["all_gather_ms"] is None
+    assert full["full"] is True and full["steps_bit_identical"]["identical"] and "parity" in full and full["kernels"] and "roofline" in full
+    assert sorted(plain["dumped_outputs"]) == sorted(full["dumped_outputs"])
+    for name in plain["dumped_outputs"]:
+        assert np.array_equal(np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))), name

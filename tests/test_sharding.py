@@ -152,7 +152,8 @@ def test_track_sharded_nccl_world2():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c5_shard", "--steps", "1", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-extra-lines", "--no-profile"], capture_output=True, text=True, env=env, timeout=1200)
+                          "--full", "--no-cpu-baseline", "--no-extra-lines", "--no-profile"], capture_output=True, text=True, env=env,
+                         timeout=1200)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["dist_backend"] == "nccl"

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Same-box A/B of two builds of the library on the headline step: tools/ab_step.sh <libA.so> <libB.so> [rounds]
-# (interleaved A B A B ..., `bench.py --steps 8 --warmup 2` each; prints ms per step and the top kernel rows of the last run of each)
+# (interleaved A B A B ..., `bench.py --steps 8 --warmup 2 --full` each; prints ms per step and the top kernel rows of the last run of each)
 A=$1; B=$2; N=${3:-2}
 for i in $(seq $N); do
   for L in $A $B; do
-    CTK_LIB_PATH=$PWD/$L python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-extra-lines 2>/dev/null | tail -1 > /tmp/ab.json
+    CTK_LIB_PATH=$PWD/$L python bench.py --steps 8 --warmup 2 --full --no-cpu-baseline --no-extra-lines 2>/dev/null | tail -1 > /tmp/ab.json
     python - $L <<'PY'
 import json, sys
 d = json.load(open('/tmp/ab.json'))

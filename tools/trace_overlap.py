@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Do two HIP streams really overlap?  Reads a rocprofv3 --kernel-trace CSV of a bench step run with CTK_OVERLAP=8 and reports,
 for every dispatch on the less-used queue (the auxiliary stream), how much of its duration other kernels were running and which.
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile --no-extra-lines
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python bench.py --steps 1 --warmup 1
     python tools/trace_overlap.py /tmp/kt"""
 import collections
 import csv
