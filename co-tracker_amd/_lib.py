@@ -22,6 +22,7 @@ VIRT = 64
 ACT_NONE, ACT_GELU_ERF, ACT_GELU_TANH = 0, 1, 2
 ABI_VERSION = 9
 MAX_BATCH = 16  # CTK_MAX_BATCH: videos of one joint window (ctk_forward_window_batch)
+STREAM_EMPTY_FRAME = float(2 ** 30)  # CTK_STREAM_EMPTY_FRAME: the query frame of an empty slot of a stream (ctk_stream_assign)
 # ctk_window_batch.flags: the B windows are B query groups of ONE video -- the same fmaps pointers in every group, and coords / vis /
 # conf / support[l] / point_mask of group b lying right behind group b - 1 in one allocation each (include/ctk.h).  The library
 # then keeps ONE split-half pyramid copy and launches the correlation sampler once per chunk piece over all groups.
@@ -173,6 +174,7 @@ SYMBOLS = {
     "ctk_stream_begin": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_support": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_commit": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_assign": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, C.c_int32, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

@@ -8,6 +8,8 @@
 //   support  cotracker3_online.py:411-440   trilinear support patches of the points whose query frame entered this window, added
 //                                           into the persistent accumulators
 //   commit   cotracker3_online.py:498-510   finished window -> history rows, optional non-finite flag
+// A fourth kernel, assign, runs BETWEEN two calls and does no float arithmetic at all: it hands slots of the resident query table
+// to new queries (or empties them) and clears what their previous occupants left.
 // No LDS, no atomics except the one flag OR, no device-side globals.
 #include "ctk_common.h"
 
@@ -134,6 +136,37 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(int G, int N, int S,
   if (flag != nullptr && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
+// ---- assign: blockIdx.x = listed slot m; the y blocks stride over the slot's accumulator floats, then over its history rows ----
+struct AssignLevels {
+  float* acc[CTK_LEVELS];
+};
+constexpr int ASSIGN_ACC4 = CTK_TAPS * CTK_C / 4;  // float4 stores per slot and level: the slot's 49 x 128 floats are one run
+
+__global__ __launch_bounds__(256) void stream_assign_kernel(AssignLevels lv, int G, int N, long T_cap, int rows,
+                                                            const int32_t* __restrict__ slots, const float* __restrict__ newq,
+                                                            float* __restrict__ queries, float* __restrict__ hc,
+                                                            float* __restrict__ hv, float* __restrict__ hf) {
+  const long m = blockIdx.x;
+  const long slot = slots[m];
+  if (slot < 0 || slot >= (long)G * N) return;  // defence only: the host checks the list before it is copied over
+  const long tid = (long)blockIdx.y * blockDim.x + threadIdx.x;
+  const long nthreads = (long)gridDim.y * blockDim.x;
+  if (tid < 3) queries[slot * 3 + tid] = newq[m * 3 + tid];
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long i = tid; i < (long)CTK_LEVELS * ASSIGN_ACC4; i += nthreads) {
+    const int l = (int)(i / ASSIGN_ACC4);
+    const long j = i - (long)l * ASSIGN_ACC4;
+    reinterpret_cast<float4*>(lv.acc[l] + slot * (CTK_TAPS * CTK_C))[j] = z4;  // (a slot's run starts on a 25088-byte multiple)
+  }
+  const long g = slot / N, n = slot - g * N;
+  for (long t = tid; t < rows; t += nthreads) {
+    const long row = (g * T_cap + t) * N + n;
+    *reinterpret_cast<float2*>(hc + row * 2) = make_float2(0.f, 0.f);
+    hv[row] = 0.0f;
+    hf[row] = 0.0f;
+  }
+}
+
 int check_common(const ctk_stream_args* a) {
   if (!a) return CTK_E_NULL;
   if (a->G <= 0 || a->N <= 0 || a->S <= 0 || a->step <= 0 || a->step >= a->S || a->ind < 0 || a->ind % a->step != 0)
@@ -194,6 +227,26 @@ extern "C" int ctk_stream_commit(const ctk_stream_args* a, void* stream) {
   hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->T_valid, a->ind, (long)a->T_cap, a->stride, a->coords,
                      a->vis, a->conf, a->hist_coords, a->hist_vis, a->hist_conf, a->nonfinite);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+extern "C" int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
+                                 void* stream) {
+  const int rc = check_common(a);
+  if (rc != CTK_OK) return rc;
+  if (!slots || !new_queries || !a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf) return CTK_E_NULL;
+  AssignLevels lv;
+  for (int l = 0; l < CTK_LEVELS; ++l) {
+    if (!a->support[l]) return CTK_E_NULL;
+    if (!ctk_aligned16(a->support[l])) return CTK_E_SHAPE;  // cleared with 16-byte stores
+    lv.acc[l] = a->support[l];
+  }
+  if (M <= 0 || (long)M > (long)a->G * a->N || rows < 0 || rows > a->T_cap) return CTK_E_SHAPE;
+  // 4 x 1568 float4 stores per slot: 8 blocks of 256 threads take them in about three rounds each, a long history in a few more
+  hipLaunchKernelGGL(stream_assign_kernel, dim3((unsigned)M, 8), dim3(256), 0, static_cast<hipStream_t>(stream), lv, a->G, a->N,
+                     (long)a->T_cap, rows, slots, new_queries, const_cast<float*>(a->queries), a->hist_coords, a->hist_vis,
+                     a->hist_conf);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }

@@ -321,6 +321,22 @@ class TrackerBase(nn.Module):
         # three launches per call (ops.StreamGroups, csrc/stream.hip), the groups' windows one after the other ("loop":
         # bit-identical to G single-group streams) or as shared-pyramid joint windows ("joint").  Off: that call raises, as before.
         self.stream_groups = False
+        # Slots on a running stream (CoTracker3 online model only; opt-in): with it on, EVERY forward(video [1,T,3,H,W], queries
+        # [G,N,3], is_online=True) -- G == 1 included, which otherwise takes the torch glue of _video_gen -- runs on the
+        # device-resident stream state and returns [G,T_so_far,N,.].  A row of the query table whose frame is ops.EMPTY_FRAME (and
+        # whose position is (0, 0)) is an EMPTY SLOT: tracked as the reference tracks a query that has not arrived (a blank token of
+        # the space attention: the number of spare slots is part of the result, as the support grid is).  Between two calls
+        # stream_assign() hands slots to new queries and stream_release() empties them: writes into resident buffers, so no shape,
+        # no address and no captured graph changes.  More than one video with the switch on: NotImplementedError.
+        self.stream_slots = False
+
+    @property
+    def stream_slots(self) -> bool:
+        return getattr(self, "_stream_slots", False)  # (a model pickled before the attribute existed)
+
+    @stream_slots.setter
+    def stream_slots(self, on):
+        self._stream_slots = bool(on)
 
     @property
     def stream_groups(self) -> bool:
@@ -748,7 +764,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     """Sliding-window / streaming tracker (cotracker3_online.py:159-541)."""
 
     _TRANSIENT = {**CoTrackerThreeBase._TRANSIENT, "_overlap_hint": type(None)}
-    _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups)
+    _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups) or of any stream with stream_slots
     online_ind = _online_attr("ind")
     online_track_support = _online_attr("track_support")
     online_coords_predicted = _online_attr("coords_predicted")
@@ -769,7 +785,10 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
                 is_online=False):
         B, T, space_attn, grouped = self._check_inputs(video, queries, is_train, add_space_attn)
         assert self.window_len >= 2
-        if grouped and is_online and self.stream_groups:
+        if is_online and self.stream_slots and video.shape[0] != 1:
+            raise NotImplementedError("stream_slots streams the query sets of ONE video: a batch of videos with the switch on is not "
+                                      "implemented")
+        if is_online and (self.stream_slots or (grouped and self.stream_groups)):
             return self._forward_stream_groups(video, queries, iters, fmaps_chunk_size, space_attn)
         if grouped and is_online:
             raise NotImplementedError("streaming (is_online=True) takes one query set per video: a query-group call (video [1,...], "
@@ -789,6 +808,55 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             return [self._video_gen(video[b], queries[b], fmaps_chunk_size, states[b] if is_online else None, hint,
                                     None if f0 is None else f0[b]) for b in group]
         return self._track(video, iters, make_gens, states, units=B if grouped else None, space_attn=space_attn, shared=grouped)
+
+    # -- slots of a running stream (stream_slots): assign and release between two calls ---------------------------------------
+    def _slot_stream(self):
+        """The stream state that stream_assign / stream_release write, or RuntimeError: the switch is off, no call of a stream
+        has been made yet (its queries go through forward), or a short chunk has closed the stream."""
+        if not self.stream_slots:
+            raise RuntimeError("model.stream_slots is off: this stream has no slots to assign")
+        gs, st = self._gstream, getattr(self, "_online", None)
+        if gs is None or not gs.live or not st or st[0].ind == 0:
+            raise RuntimeError("no stream is running: the queries of the first call go through forward(); slots are assigned between "
+                               "two calls of a stream")
+        if gs.closed:
+            raise RuntimeError("a chunk shorter than the window has ended the stream")
+        return gs, st[0].ind
+
+    def stream_assign(self, slots, queries):
+        """Between two streaming calls: slot slots[m] (flat index g*N + n of the [G,N] query table) tracks queries[m] = (frame, x,
+        y), model-resolution pixels, from now on; an occupied slot gets a new occupant.  The frame must not lie below
+        online_ind + window_len // 2, the first frame that the stream has not handed to the support sampling yet (ValueError: "its
+        features have left the stream"); frames beyond the next window are fine, the slot stays blank until its frame arrives.
+        The slot's support features and all its history rows committed so far are cleared; stream_first_row tells from which row
+        on the returned tracks belong to the new occupant.  Nothing of the next call changes shape or address: no graph is
+        captured again.  The frame column is checked on the host (queries on the device: one small copy, the only wait);
+        every refusal is raised before anything is written.  The `queries` argument of later forward calls is checked for shape
+        and device only: the resident table (stream_queries) is the truth."""
+        gs, ind = self._slot_stream()
+        gs.assign(slots, queries, min_frame=ind + self.window_len // 2)
+
+    def stream_release(self, slots):
+        """Between two streaming calls: empty the listed slots (frame ops.EMPTY_FRAME, position (0, 0), state cleared)."""
+        gs, _ = self._slot_stream()
+        gs.release(slots)
+
+    @property
+    def stream_occupied(self):
+        """[G,N] bool on the host: the slots that hold a query (host bookkeeping; a copy)."""
+        return self._slot_stream()[0].occupied.clone()
+
+    @property
+    def stream_first_row(self):
+        """[G,N] long on the host: the history row from which a slot's rows belong to its present occupant (0 for the queries of
+        the first call, online_ind at the time of an assign); the rows below it carry no information (a copy)."""
+        return self._slot_stream()[0].first_row.clone()
+
+    @property
+    def stream_queries(self):
+        """[G,N,3] on the device: the resident query table as it stands (a copy)."""
+        gs = self._slot_stream()[0]
+        return gs.queries.reshape(gs.G, gs.N, 3).clone()
 
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):

@@ -162,6 +162,11 @@ class CoTracker2(TrackerBase):
         if on:
             raise NotImplementedError("CoTracker2 (model_v2.py) streams one query set per video; stream_groups on a v2 model is not implemented")
 
+    @TrackerBase.stream_slots.setter
+    def stream_slots(self, on):  # slots live in the device stream state, which is the CoTracker3 online model's
+        if on:
+            raise NotImplementedError("CoTracker2 (model_v2.py) takes the queries of a stream at its first call; stream_slots on a v2 model is not implemented")
+
     def init_video_online_processing(self):  # cotracker.py:187-191
         self._resolve_deferred_range_check()  # the last chunk of the previous stream (graph streaming defers its check by one call)
         self._online = [OnlineState()]  # (B > 1: replicated by the first call)

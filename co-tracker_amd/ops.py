@@ -583,15 +583,26 @@ class WindowBatchGraph(WindowGraph):
 
 
 # ------------------------------------------------------------------------------------------
-# stream state of G query groups over one live video (include/ctk.h: ctk_stream_begin / _support / _commit)
+# stream state of G query groups over one live video (include/ctk.h: ctk_stream_begin / _support / _commit / _assign)
 # ------------------------------------------------------------------------------------------
+# the query frame of an empty slot: finite, exact in float32, .long() of it is defined, and no stream reaches it -- so the row is never
+# inside a sample range and never below ind + S (never sampled, point_mask 0: the blank track of a query that has not arrived)
+EMPTY_FRAME = L.STREAM_EMPTY_FRAME
+
+
 class StreamGroups:
     """The device-resident state of G query groups streamed over ONE video, in the layouts the shared joint window wants, and
     the three launches that step it (csrc/stream.hip).  Everything a window call reads or writes lives here and keeps its
     address for the life of the object -- the pyramid [S,H_l,W_l,128], the window state coords [G,S,N,2] / vis / conf [G,S,N],
     point_mask [G,N], the support accumulators support[l] [G*N,49,128] -- so captured window graphs bake these pointers in and
     nothing is stacked or copied per call.  The history [G,T_cap,N,.] is a capacity buffer outside the graphs, grown
-    geometrically.  ``serial`` changes whenever the baked-in buffers are re-allocated (graph cache key)."""
+    geometrically.  ``serial`` changes whenever the baked-in buffers are re-allocated (graph cache key).
+
+    Slots: a row of the query table whose frame is EMPTY_FRAME (and whose position is (0, 0)) is an empty slot, and assign() /
+    release() hand slots to new queries or empty them between two calls -- writes into the resident buffers: no address, no
+    shape and therefore no captured graph changes.  The bookkeeping lives on the host: ``occupied`` [G,N] (bool) and
+    ``first_row`` [G,N] (the history row from which the rows belong to the present occupant); ``committed`` counts the history
+    rows written so far and ``next_ind`` is the first frame of the next call's window (both follow commit())."""
 
     _serial = 0
 
@@ -616,6 +627,20 @@ class StreamGroups:
         StreamGroups._serial += 1
         self.serial = StreamGroups._serial
         self._wins = {}
+        self._new_book()
+
+    def _new_book(self) -> None:
+        self.committed, self.next_ind = 0, 0
+        self._occupied = None  # read from the query table when it is first asked for: the calls of a stream never wait for it
+        self.first_row = torch.zeros(self.G, self.N, dtype=torch.long)
+
+    @property
+    def occupied(self) -> torch.Tensor:
+        """[G,N] bool, on the host: which slots hold a query.  The first look copies the frame column of the resident table to
+        the host (one small device-to-host copy per stream); assign() and release() keep it up to date from then on."""
+        if self._occupied is None:
+            self._occupied = (self.queries[:, 0].cpu() != EMPTY_FRAME).reshape(self.G, self.N)
+        return self._occupied
 
     def fits(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes) -> bool:
         return (tuple(queries.shape[:2]) == (self.G, self.N) and queries.device == self.queries.device and
@@ -630,6 +655,7 @@ class StreamGroups:
             h_.zero_()
         self.nonfinite.zero_()
         self.closed, self.live = False, True
+        self._new_book()
 
     def reserve(self, T: int) -> None:
         """History capacity of at least T frames: doubled when it runs out (one copy per doubling, not per call); rows past the
@@ -680,6 +706,51 @@ class StreamGroups:
 
     def commit(self, ind: int, T_valid: int, flag: bool) -> None:
         L.check(L.load().ctk_stream_commit(C.byref(self._args(ind, T_valid, flag)), _stream()), "ctk_stream_commit")
+        self.committed, self.next_ind = ind + T_valid, ind + self.step
+
+    def assign(self, slots, queries: torch.Tensor, rows: Optional[int] = None, min_frame: Optional[int] = None) -> None:
+        """Between two calls: slot slots[m] (flat index g*N + n) gets the query queries[m] = (frame, x, y) in model-resolution
+        pixels, its support accumulators and its history rows [0, rows) are cleared (rows: default every row committed so far), and
+        the bookkeeping follows (first_row = next_ind).  One launch (ctk_stream_assign); the slot list reaches the device with one
+        non-blocking copy, and so do queries given on the host.  The frame column is checked HERE, on the host -- for queries on
+        the device that is one small device-to-host copy; the positions never leave the device --: a frame that is not finite, or
+        whose integer part lies below `min_frame` (the caller's rule: the first frame no support call has handed out yet), raises
+        ValueError, like a slot out of range, a slot listed twice or a wrong shape; nothing is written then.  Touches neither
+        ``serial`` nor the windows, the pyramid or any buffer address."""
+        idx = torch.as_tensor(slots).detach().cpu().reshape(-1)
+        M = idx.numel()
+        if M == 0 or idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool:
+            raise ValueError("assign: slots must be a non-empty list of integer slot indices g*N + n")
+        idx = idx.long()
+        if int(idx.min()) < 0 or int(idx.max()) >= self.G * self.N:
+            raise ValueError(f"assign: slot index outside [0, {self.G * self.N})")
+        if torch.unique(idx).numel() != M:
+            raise ValueError("assign: a slot is listed twice")
+        if not isinstance(queries, torch.Tensor) or tuple(queries.shape) != (M, 3) or not queries.dtype.is_floating_point:
+            raise ValueError(f"assign: queries must be a float tensor [{M},3] = (frame, x, y), one row per listed slot")
+        rows = self.committed if rows is None else int(rows)
+        if not 0 <= rows <= self.T_cap:
+            raise ValueError(f"assign: rows must lie in [0, {self.T_cap}]")
+        dev = self.queries.device
+        frames = queries[:, 0].detach().float().cpu()
+        if not bool((torch.isfinite(frames) & (frames <= EMPTY_FRAME)).all()):
+            raise ValueError("assign: a query frame is not finite (or lies beyond EMPTY_FRAME)")
+        if min_frame is not None and int(frames.long().min()) < min_frame:
+            raise ValueError(f"assign: query frame {int(frames.long().min())} lies before frame {min_frame}: its features have left "
+                             "the stream")
+        if queries.device == dev:
+            q = queries.detach().float().contiguous()
+        else:
+            q = queries.detach().float().contiguous().pin_memory().to(dev, non_blocking=True)
+        s32 = idx.to(torch.int32).pin_memory().to(dev, non_blocking=True)
+        _ = self.occupied  # (the bookkeeping is read from the table BEFORE this assign changes it)
+        L.check(L.load().ctk_stream_assign(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, rows, _stream()), "ctk_stream_assign")
+        self._occupied.view(-1)[idx] = frames != EMPTY_FRAME
+        self.first_row.view(-1)[idx] = self.next_ind
+
+    def release(self, slots) -> None:
+        """Empty the listed slots: assign of (EMPTY_FRAME, 0, 0).  No frame rule."""
+        self.assign(slots, torch.tensor([[EMPTY_FRAME, 0.0, 0.0]]).expand(torch.as_tensor(slots).numel(), 3))
 
     def windows(self, g0: int, g1: int, scale_xy, **window_kw) -> List[Window]:
         """The windows of groups g0 .. g1-1 on the resident buffers (slices of one allocation each: WindowBatch(shared=True)).

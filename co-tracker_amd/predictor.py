@@ -196,6 +196,66 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         self.model = model
         self.model.eval()
         self.model.hip_graph = True  # streaming: replay the captured window graph per chunk (configs[3])
+        # Not a reference kwarg (set it after construction, before the first step): K empty slots per query set, which
+        # add_queries() fills and remove_queries() empties while the stream runs (model.stream_slots).  The first step builds
+        # [user queries N | K empty | support grid], and later steps return the N + K user-visible points.  An empty slot is
+        # tracked as a blank point and takes part in the space attention: like the support grid, K is part of the result.
+        self.spare_points = 0
+        self._first_row = self._hw = None
+
+    def add_queries(self, queries, group: int = 0):
+        """Between two steps of a running stream (after its first tracked chunk): track queries [M,3] = (frame, x, y) -- frame
+        counted from the start of the stream, not below the first frame the stream has not sampled yet (model.stream_assign);
+        x, y in pixels of the raw video, rescaled like first-step queries -- in the M lowest free slots of query set `group`.
+        Returns their point indices (LongTensor [M]) in the returned tracks.  Fewer than M free slots: RuntimeError, nothing
+        assigned."""
+        ih, iw = self.interp_shape
+        H, W = self._hw
+        q = queries.clone().float()
+        if q.dim() != 2 or q.shape[1] != 3:
+            raise ValueError("add_queries: queries must be [M,3] = (frame, x, y)")
+        q[:, 1:] *= q.new_tensor([(iw - 1) / (W - 1), (ih - 1) / (H - 1)])
+        occ = self.model.stream_occupied
+        free = (~occ[group, :self.N]).nonzero().reshape(-1)
+        if free.numel() < q.shape[0]:
+            raise RuntimeError(f"add_queries: {q.shape[0]} queries for {free.numel()} free slots (spare_points = {self.spare_points})")
+        points = free[:q.shape[0]]
+        self.model.stream_assign(points + group * occ.shape[1], q)
+        self._mark_rows()
+        return points
+
+    def remove_queries(self, points, group: int = 0):
+        """Between two steps of a running stream: stop tracking the listed points (any of the N + K user-visible ones) of query set
+        `group`; their slots are free for add_queries()."""
+        points = torch.as_tensor(points).reshape(-1).long().cpu()
+        if points.numel() and (int(points.min()) < 0 or int(points.max()) >= self.N):
+            raise ValueError(f"remove_queries: point index outside [0, {self.N})")
+        self.model.stream_release(points + group * self.queries.shape[1])
+        self._mark_rows()
+
+    def _mark_rows(self):
+        """The row from which each user-visible point carries information, on the device: visibility is False below it, and
+        everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""
+        occ, first = self.model.stream_occupied, self.model.stream_first_row
+        first[~occ] = torch.iinfo(torch.long).max
+        self._first_row = first[:, :self.N].to(self.queries.device)
+
+    def _with_spare(self, queries):
+        """First step: the query sets followed by spare_points empty slots each (the support grid comes after them)."""
+        K = int(self.spare_points)
+        if K <= 0:
+            return queries
+        if self.v2:
+            raise NotImplementedError("CoTracker2 takes the queries of a stream at its first step: spare_points on a v2 predictor is "
+                                      "not implemented")
+        from .ops import EMPTY_FRAME
+        G, N = queries.shape[:2]
+        self.N = N + K
+        self.model.stream_slots = True
+        first = torch.zeros(G, N + K, dtype=torch.long)
+        first[:, N:] = torch.iinfo(torch.long).max
+        self._first_row = first.to(queries.device)
+        return torch.cat([queries, queries.new_tensor([EMPTY_FRAME, 0.0, 0.0]).expand(G, K, 3)], dim=1)
 
     def finish(self):
         """Not in the reference (its stream has no end marker): examine the f16-range check of the LAST chunk, which graph
@@ -213,11 +273,13 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if is_first_step:  # predictor.py:242-274: reset state, remember the queries, no tracking yet
             self.model.init_video_online_processing()
             self._prev_chunk = None
+            self._first_row, self._hw = None, (H, W)
             if queries is not None:
                 assert queries.shape[2] == 3
                 self.N = queries.shape[1]
                 queries = queries.clone().float()
                 queries[:, :, 1:] *= queries.new_tensor([(iw - 1) / (W - 1), (ih - 1) / (H - 1)])
+                queries = self._with_spare(queries)
                 if add_support_grid:
                     g = get_points_on_a_grid(self.support_grid_size, self.interp_shape, device=video_chunk.device)
                     g = torch.cat([torch.zeros_like(g[:, :, :1]), g], dim=2)
@@ -229,10 +291,11 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             elif grid_size > 0:
                 pts = get_points_on_a_grid(grid_size, self.interp_shape, device=video_chunk.device)
                 self.N = grid_size ** 2
-                queries = torch.cat([torch.full_like(pts[:, :, :1], float(grid_query_frame)), pts], dim=2)
+                queries = self._with_spare(torch.cat([torch.full_like(pts[:, :, :1], float(grid_query_frame)), pts], dim=2))
             self.queries = queries
             return (None, None)
 
+        self._hw = (H, W)
         # streaming feature cache (opt-in, model.online_feature_cache): prove ON THE HOST that this chunk's first T - step frames
         # are the memory of the previous chunk's last T - step frames (a view of the same resident video advanced by `step`
         # frames) and tell the model -- it only ever sees the freshly resized tensor below.  No device work, no wait.
@@ -257,4 +320,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             conf = conf[:, :, :self.N] if conf is not None else None
         if conf is not None:
             vis = vis * conf  # predictor.py:297-298
-        return tracks * tracks.new_tensor([(W - 1) / (iw - 1), (H - 1) / (ih - 1)]), vis > 0.6
+        vis = vis > 0.6
+        if self._first_row is not None:  # spare_points: nothing is visible in an empty slot, nor before a slot's occupant arrived
+            vis = vis & (torch.arange(vis.shape[1], device=vis.device)[None, :, None] >= self._first_row[:, None, :])
+        return tracks * tracks.new_tensor([(W - 1) / (iw - 1), (H - 1) / (ih - 1)]), vis

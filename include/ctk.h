@@ -47,6 +47,8 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_assign: slots of the resident query table of a running
+ *       stream are handed to new queries, or emptied, between two calls (CTK_STREAM_EMPTY_FRAME).
  *   v9, additive (number unchanged): + ctk_stream_begin / ctk_stream_support / ctk_stream_commit on the struct ctk_stream_args: the stream state
  *       of G query groups over one live video, stepped on the device.
  *   v9, additive (number unchanged): ctk_window_batch.reserved is now `flags` (same offset and size; 0 = as before) with the bit
@@ -281,6 +283,27 @@ typedef struct ctk_stream_args {
 int ctk_stream_begin(const ctk_stream_args* a, void* stream);
 int ctk_stream_support(const ctk_stream_args* a, void* stream);
 int ctk_stream_commit(const ctk_stream_args* a, void* stream);
+
+/* ---- slots of a running stream: assign and release between two calls ------------------------------------------------------------
+ * A row of `queries` whose frame is CTK_STREAM_EMPTY_FRAME and whose (x, y) is (0, 0) is an EMPTY SLOT: by the rules above its
+ * frame is never inside a sample range and never below ind + S, so it is never sampled, keeps point_mask == 0 and is tracked as
+ * the reference tracks a point whose query frame has not arrived (a blank token; it costs what a point costs).  The constant is
+ * finite, exact in float32 and converts to a long; no stream reaches it.
+ *   assign:  for each of the M listed slots (flat indices g*N + n into [0, G*N), pairwise different: two writers of one row are
+ *            not defined; a listed index outside the range writes nothing) the query row becomes new_queries[m] = (frame, x, y),
+ *            the slot's 49 x 128 accumulator rows on all four levels become zero, and so do its history rows [0, rows) (coords,
+ *            vis and conf): nothing of a previous occupant can be read back.  (EMPTY_FRAME, 0, 0) releases the slot.  The caller
+ *            assigns BETWEEN two calls and only frames that no support call has handed out yet: trunc(frame) >= ind + step, ind
+ *            the first frame of the NEXT call's window; an earlier frame would never be sampled.  The frame rule is the caller's
+ *            (the frames live on the device); rows = the history rows committed so far.
+ * Reads of `a`: G, N, T_cap, queries (written, although the struct declares it const for the three step calls), hist_*, support[]
+ * (16-byte aligned: cleared with vector stores), and what every entry point validates.  slots [M] and new_queries [M,3] are device
+ * memory.  One launch on `stream`; no float arithmetic, no atomics, no host synchronisation; capture-safe.  NULL a, slots,
+ * new_queries, queries, history or accumulator pointer: CTK_E_NULL; M <= 0, M > G*N, rows < 0, rows > T_cap, a misaligned
+ * accumulator and what the step calls refuse in G, N, S, step, ind, T_cap, stride: CTK_E_SHAPE; all before any launch. */
+#define CTK_STREAM_EMPTY_FRAME 1073741824.0f /* 2^30 */
+int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
+                      void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
