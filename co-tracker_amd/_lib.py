@@ -27,6 +27,8 @@ STREAM_EMPTY_FRAME = float(2 ** 30)  # CTK_STREAM_EMPTY_FRAME: the query frame o
 # conf / support[l] / point_mask of group b lying right behind group b - 1 in one allocation each (include/ctk.h).  The library
 # then keeps ONE split-half pyramid copy and launches the correlation sampler once per chunk piece over all groups.
 BATCH_SHARED_FMAPS = 1
+INGEST_U8, INGEST_F32 = 0, 1  # ctk_ingest_args.dtype
+INGEST_HWC, INGEST_CHW = 0, 1  # ctk_ingest_args.layout
 PAD_ZEROS, PAD_BORDER = 0, 1  # ctk_bilinear_sampler padding_mode
 # ctk_set_option keys (include/ctk.h)
 (OPT_GEMM_PP, OPT_GEMM_TAIL_PCT, OPT_CORR_VERSION, OPT_CORR_MAP, OPT_ATTENTION_VALU, OPT_ATTENTION_TIME_PERSISTENT,
@@ -118,6 +120,16 @@ class StreamArgs(C.Structure):
     ]
 
 
+class IngestArgs(C.Structure):
+    """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
+    _fields_ = [
+        ("src", _fp), ("dtype", C.c_int32), ("layout", C.c_int32),
+        ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("reserved", C.c_int32),
+        ("frame_stride", C.c_int64), ("row_stride", C.c_int64),
+        ("dst", _fp),
+    ]
+
+
 class FormerWeights(C.Structure):
     """ctk_former_weights: the general update former (CoTracker2)."""
     _fields_ = [
@@ -175,6 +187,7 @@ SYMBOLS = {
     "ctk_stream_support": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_commit": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_assign": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, C.c_int32, _fp]),
+    "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

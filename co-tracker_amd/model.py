@@ -764,7 +764,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     """Sliding-window / streaming tracker (cotracker3_online.py:159-541)."""
 
     _TRANSIENT = {**CoTrackerThreeBase._TRANSIENT, "_overlap_hint": type(None)}
-    _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups) or of any stream with stream_slots
+    _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups), of any stream with stream_slots, of a push stream
+    _feed = None     # how the running stream gets its frames: "forward" (chunks) or "push" (stream_push: new frames only); None: no tracked call yet
     online_ind = _online_attr("ind")
     online_track_support = _online_attr("track_support")
     online_coords_predicted = _online_attr("coords_predicted")
@@ -779,6 +780,16 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         self._overlap_hint = None  # the predictor's verdict for the NEXT call (it resizes chunks into fresh tensors)
         if self._gstream is not None:  # its buffers (and the graphs captured on them) serve the next stream of the same shape
             self._gstream.live = False
+        self._feed = None
+
+    def _fed(self, how, mark=True):
+        """One stream is fed one way: overlapping chunks through forward, or new frames only through stream_push.  The chunk path may
+        run on the torch glue, which leaves no resident pyramid to continue from, and a pushed stream has no chunk to be handed."""
+        if self._feed not in (None, how):
+            raise RuntimeError(f"this stream is fed through {'stream_push' if self._feed == 'push' else 'forward'}: call "
+                               "init_video_online_processing() before feeding the model the other way")
+        if mark:
+            self._feed = how
 
     @torch.no_grad()
     def forward(self, video, queries, iters=4, is_train=False, add_space_attn=True, fmaps_chunk_size=200,
@@ -788,6 +799,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         if is_online and self.stream_slots and video.shape[0] != 1:
             raise NotImplementedError("stream_slots streams the query sets of ONE video: a batch of videos with the switch on is not "
                                       "implemented")
+        if is_online:
+            self._fed("forward")
         if is_online and (self.stream_slots or (grouped and self.stream_groups)):
             return self._forward_stream_groups(video, queries, iters, fmaps_chunk_size, space_attn)
         if grouped and is_online:
@@ -813,7 +826,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     def _slot_stream(self):
         """The stream state that stream_assign / stream_release write, or RuntimeError: the switch is off, no call of a stream
         has been made yet (its queries go through forward), or a short chunk has closed the stream."""
-        if not self.stream_slots:
+        if not self.stream_slots and self._feed != "push":  # (a push stream always runs on the device stream state)
             raise RuntimeError("model.stream_slots is off: this stream has no slots to assign")
         gs, st = self._gstream, getattr(self, "_online", None)
         if gs is None or not gs.live or not st or st[0].ind == 0:
@@ -862,16 +875,24 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is
         encoded once (through the stream's ONE feature cache), the pyramid is built once into the resident buffers of
-        ops.StreamGroups, and three launches step the state of all G*N points: support (the points whose query frame entered this
-        window), begin (carry-over and masks), then the groups' windows, then commit (history rows, non-finite flag).  Returns
-        views of the first ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place."""
+        ops.StreamGroups, and _stream_step runs the window on them."""
         T, S = video.shape[1], self.window_len
         step = S // 2
         st = self._online_states(1, T)[0]
         hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None
         self._resolve_deferred_range_check()
-        H, W = video.shape[3] // self.stride, video.shape[4] // self.stride
-        sizes = [(H >> l, W >> l) for l in range(self.corr_levels)]
+        gs = self._stream_state(queries, st, video.shape[3], video.shape[4])
+        gs.closed = T < S
+        f0 = self._encode_online(video[0], chunk, S, step, st, hint)
+        gs.set_pyramid(f0)
+        return self._stream_step(gs, st, video.device, T, iters, space_attn)
+
+    def _stream_state(self, queries, st, H, W):
+        """The resident stream state for this call: the running one, the buffers of the previous stream of the same shape handed to
+        a new stream (no new graph), or a new ops.StreamGroups."""
+        S = self.window_len
+        step = S // 2
+        sizes = [((H // self.stride) >> l, (W // self.stride) >> l) for l in range(self.corr_levels)]
         gs = self._gstream
         if gs is None or not gs.fits(queries, S, step, self.stride, sizes):
             assert st.ind == 0, "the query groups of a stream are fixed by its first call"
@@ -881,10 +902,16 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             assert st.ind == 0, "the query groups of a stream are fixed by its first call"
             gs.restart(queries)
         assert not gs.closed, "a chunk shorter than the window ends the stream"
-        gs.closed = T < S
+        return gs
+
+    def _stream_step(self, gs, st, device, T, iters, space_attn):
+        """What every call on the device stream state does once the resident pyramid holds this window's S frames (T of them real):
+        three launches step the state of all G*N points -- support (the points whose query frame entered this window), begin
+        (carry-over and masks), then the groups' windows, then commit (history rows, non-finite flag).  Returns views of the first
+        ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place."""
+        S = self.window_len
+        step = S // 2
         ind = st.ind
-        f0 = self._encode_online(video[0], chunk, S, step, st, hint)
-        gs.set_pyramid(f0)
         gs.sample_support(ind)  # independent of the Linear back end: not repeated by a range-guard re-run
         graphed = bool(self.hip_graph)
         joint, groups = self._index_groups(gs.G, units=True)
@@ -895,7 +922,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         def run(precision, check):
             """begin, the groups' windows -- one group after the other ("loop") or shared-pyramid joint windows of at most
             CTK_MAX_BATCH groups ("joint"); graphed: each replays its own graph, a member of this stream state's generation --, commit."""
-            pw = self.packed(video.device, precision)
+            pw = self.packed(device, precision)
             gs.begin(ind)
             graphs = graphed and self._graph_cache(("stream_groups", gs.serial, tuple(self.model_resolution), int(self.stride), joint,
                                                     *kw.values()), pw)
@@ -921,6 +948,48 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         st.track_support, (st.coords_predicted, st.vis_predicted, st.conf_predicted) = gs.support, out
         self.last_logits = out[1:]
         return (out[0], torch.sigmoid(out[1]), torch.sigmoid(out[2]), None)
+
+    # -- push stream: new frames only, the overlap stays in the resident pyramid ------------------------------------------------
+    @torch.no_grad()
+    def stream_push(self, frames, queries, iters=4, add_space_attn=True, final=False):
+        """One streaming call that is handed the NEW frames only: frames [n,3,H,W] float32 in 0..255 at model resolution, queries
+        [G,N,3] as forward takes them (G == 1 included).  The first tracked call of a stream brings the whole first window,
+        n == window_len; every later one the n == window_len // 2 frames the window advances by.  final=True admits fewer (at least
+        one): a video shorter than a window, or the short closing chunk, which ends the stream exactly as forward's chunk of
+        T = window_len // 2 + n < window_len frames does.  Returns what forward(chunk, queries, is_online=True) returns for the chunk
+        of the last window_len (or T) frames on the device stream state -- the same bits: the encoder and the pooling are per frame,
+        so the features the resident pyramid keeps from the previous call (ops.StreamGroups.advance_pyramid) are the ones a
+        re-computation would give -- while every frame is encoded and pooled once.  Always on the device stream state, whatever
+        stream_groups / stream_slots say, in both batch_modes, with and without hip_graph; stream_assign / stream_release work on
+        it; online_feature_cache plays no part.  A stream is fed one way: after a tracked forward call this raises RuntimeError until
+        init_video_online_processing(), and forward does after a push."""
+        if not (isinstance(frames, torch.Tensor) and frames.dim() == 4 and frames.shape[1] == 3 and frames.dtype == torch.float32):
+            raise ValueError("stream_push: frames must be a float32 tensor [n,3,H,W] (the new frames, model resolution, 0..255)")
+        self._fed("push", mark=False)
+        self._check_call(frames, False)
+        n, _, H, W = frames.shape
+        assert H % self.stride == 0 and W % self.stride == 0
+        assert queries.dim() == 3 and queries.shape[2] == 3
+        S = self.window_len
+        step = S // 2
+        assert S >= 2 and 2 * step == S, "stream_push: window_len must be even (the kept half and the new half of a window)"
+        st = self._online_states(1, min(n, S))[0]
+        first = st.ind == 0
+        full = S if first else step
+        if not (n == full or (final and 1 <= n < full)):
+            raise ValueError(f"stream_push: this call takes {full} new frames ({'the first window' if first else 'one step'}), or "
+                             f"1..{full - 1} with final=True; got {n}" + ("" if final or n >= full else " without final=True"))
+        T = n if first else S - step + n
+        self._fed("push")
+        self._resolve_deferred_range_check()
+        gs = self._stream_state(queries, st, H, W)
+        gs.closed = T < S
+        f_new = self._encode(frames.contiguous(), S)  # (the CNN is per frame: these are the bits a full chunk's call computes)
+        if first:
+            gs.set_pyramid(f_new)
+        else:
+            gs.advance_pyramid(f_new, T)
+        return self._stream_step(gs, st, frames.device, T, iters, bool(add_space_attn) and self.add_space_attn)
 
     def _encode_online(self, video, chunk, S, step, st, hint):
         """Streaming: consecutive chunks overlap by S - step frames (predictor.py:225,288-290 feeds the last 2*step frames

@@ -167,6 +167,9 @@ class CoTracker2(TrackerBase):
         if on:
             raise NotImplementedError("CoTracker2 (model_v2.py) takes the queries of a stream at its first call; stream_slots on a v2 model is not implemented")
 
+    def stream_push(self, *args, **kwargs):  # the resident pyramid it advances belongs to the CoTracker3 online model's stream state
+        raise NotImplementedError("CoTracker2 (model_v2.py) is fed overlapping chunks through forward(); stream_push on a v2 model is not implemented")
+
     def init_video_online_processing(self):  # cotracker.py:187-191
         self._resolve_deferred_range_check()  # the last chunk of the previous stream (graph streaming defers its check by one call)
         self._online = [OnlineState()]  # (B > 1: replicated by the first call)

@@ -163,6 +163,50 @@ def attention_batch2(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, splits: 
 # ------------------------------------------------------------------------------------------
 # pyramid / samplers
 # ------------------------------------------------------------------------------------------
+def ingest_frames(src: torch.Tensor, out: torch.Tensor, layout: Optional[str] = None) -> torch.Tensor:
+    """Raw frames -> the encoder's input (ctk_ingest_frames): src uint8 or float32, channels-last [F,H,W,3] (layout "hwc") or
+    planar [F,3,H,W] ("chw"), on the device; out float32 [F,3,h,w], contiguous -- e.g. a frame range of a resident buffer.  Value
+    for value F.interpolate(src as float NCHW, (h, w), mode="bilinear", align_corners=True).  layout None: read off the shape
+    (ValueError when both readings fit: H == 3 or W == 3).  The strides are taken from the tensor: a view is read where it lies
+    when its innermost dimensions are dense -- the pixels of a row ("hwc": channel stride 1, pixel stride 3) or the rows of a
+    frame's planes ("chw": element stride 1, channel stride H rows) -- and refused otherwise (ValueError; no silent copy)."""
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32) or not src.is_cuda:
+        raise ValueError("ingest_frames: src must be a uint8 or float32 device tensor [F,H,W,3] or [F,3,H,W]")
+    if layout is None:
+        hwc, chw = src.shape[3] == 3, src.shape[1] == 3
+        if hwc == chw:
+            raise ValueError(f"ingest_frames: cannot tell the layout of a {tuple(src.shape)} source: pass layout='hwc' or 'chw'")
+        layout = "hwc" if hwc else "chw"
+    if layout not in ("hwc", "chw") or src.shape[3 if layout == "hwc" else 1] != 3:
+        raise ValueError(f"ingest_frames: a {tuple(src.shape)} source is not layout {layout!r} with 3 channels")
+    a = L.IngestArgs()
+    if layout == "hwc":
+        a.F, a.H, a.W = src.shape[:3]
+        dense = src.stride(3) == 1 and src.stride(2) == 3
+        a.row_stride, a.layout = src.stride(1), L.INGEST_HWC
+        frame = a.H * a.row_stride
+    else:
+        a.F, a.H, a.W = src.shape[0], src.shape[2], src.shape[3]
+        a.row_stride, a.layout = src.stride(2), L.INGEST_CHW
+        dense = src.stride(3) == 1 and src.stride(1) == a.H * a.row_stride
+        frame = 3 * a.H * a.row_stride
+    if a.H == 1:  # (the stride of a dimension of size 1 is arbitrary)
+        a.row_stride = a.W * (3 if layout == "hwc" else 1)
+        frame = a.row_stride * (1 if layout == "hwc" else 3)
+        dense = src.stride(3) == 1 and (src.stride(2) == 3 if layout == "hwc" else (a.W == 1 or src.stride(1) == a.W))
+    if not dense:
+        raise ValueError(f"ingest_frames: the innermost dimensions of the {layout} source are not dense (strides {src.stride()})")
+    a.frame_stride = src.stride(0) if a.F > 1 else frame
+    if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and
+            tuple(out.shape[:2]) == (a.F, 3) and out.device == src.device):
+        raise ValueError(f"ingest_frames: out must be a contiguous float32 [{a.F},3,h,w] tensor on the source's device")
+    a.h, a.w = out.shape[2:]
+    a.dtype = L.INGEST_U8 if src.dtype == torch.uint8 else L.INGEST_F32
+    a.src, a.dst = _ptr(src), _ptr(out)
+    L.check(L.load().ctk_ingest_frames(C.byref(a), _stream()), "ctk_ingest_frames")
+    return out
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -695,6 +739,26 @@ class StreamGroups:
             self.pyr[0][T:].copy_(f0[-1:].expand(self.S - T, -1, -1, -1))
         for l in range(1, len(self.pyr)):
             avg_pool2_nhwc(self.pyr[l - 1], out=self.pyr[l])
+
+    def advance_pyramid(self, f_new: torch.Tensor, T_valid: int) -> None:
+        """The counterpart of set_pyramid for a stream that keeps its overlap: this call's window is the previous one advanced by
+        `step` frames, so on every level rows [step, S) move to [0, S - step) (the halves do not overlap: step == S // 2), the
+        level-0 features f_new [n <= step, H, W, 128] of the NEW frames land behind them, the last of them repeated up to S rows
+        when the chunk is short (T_valid = S - step + n < S, as set_pyramid pads), and the pooled levels are computed for rows
+        [S - step, S) only.  The pooling is per frame, so every row holds the bits set_pyramid would have put there.  No address
+        changes: captured graphs and ``serial`` are untouched."""
+        S, step = self.S, self.step
+        ov = S - step
+        assert 2 * step == S and ov == step, "advance_pyramid: the window halves must not overlap (step == window_len // 2)"
+        n = f_new.shape[0]
+        assert 1 <= n <= step and T_valid == ov + n, (n, T_valid)
+        for p_ in self.pyr:
+            p_[:ov].copy_(p_[step:])
+        self.pyr[0][ov:ov + n].copy_(f_new)
+        if n < step:
+            self.pyr[0][ov + n:].copy_(f_new[-1:].expand(step - n, -1, -1, -1))
+        for l in range(1, len(self.pyr)):
+            avg_pool2_nhwc(self.pyr[l - 1][ov:], out=self.pyr[l][ov:])
 
     def begin(self, ind: int) -> None:
         self.reserve(ind + self.S)

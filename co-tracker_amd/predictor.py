@@ -202,6 +202,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         # tracked as a blank point and takes part in the space attention: like the support grid, K is part of the result.
         self.spare_points = 0
         self._first_row = self._hw = None
+        self._push_buf = None  # push_frames: the resident [window_len,3,ih,iw] float32 frames the next window still needs
+        self._push_reset()
 
     def add_queries(self, queries, group: int = 0):
         """Between two steps of a running stream (after its first tracked chunk): track queries [M,3] = (frame, x, y) -- frame
@@ -273,6 +275,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if is_first_step:  # predictor.py:242-274: reset state, remember the queries, no tracking yet
             self.model.init_video_online_processing()
             self._prev_chunk = None
+            self._push_reset()
             self._first_row, self._hw = None, (H, W)
             if queries is not None:
                 assert queries.shape[2] == 3
@@ -315,6 +318,11 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             conf = None
         else:
             tracks, vis, conf, _ = self.model(video=v, queries=self.queries, iters=6, is_online=True)
+        return self._user_result(tracks, vis, conf, add_support_grid)
+
+    def _user_result(self, tracks, vis, conf, add_support_grid):
+        """What a step hands back: the user-visible points, visibility thresholded, tracks in pixels of the raw video."""
+        (H, W), (ih, iw) = self._hw, self.interp_shape
         if add_support_grid:
             tracks, vis = tracks[:, :, :self.N], vis[:, :, :self.N]
             conf = conf[:, :, :self.N] if conf is not None else None
@@ -324,3 +332,81 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if self._first_row is not None:  # spare_points: nothing is visible in an empty slot, nor before a slot's occupant arrived
             vis = vis & (torch.arange(vis.shape[1], device=vis.device)[None, :, None] >= self._first_row[:, None, :])
         return tracks * tracks.new_tensor([(W - 1) / (iw - 1), (H - 1) / (ih - 1)]), vis
+
+    # -- live stream: push new frames, every frame resized, encoded and pooled once -------------------------------------------
+    def _push_reset(self):
+        self._push_fill = 0         # frames waiting in the buffer
+        self._push_tracked = False  # the first window of this stream has run
+        self._push_closed = False   # final=True has ended the stream
+
+    def _ingest(self, src, dst, layout):
+        from . import ops
+        ops.ingest_frames(src, dst, layout=layout)
+
+    @torch.no_grad()
+    def push_frames(self, frames, final: bool = False, layout: str = None, add_support_grid=False):
+        """Feed a live stream its NEW frames only, as a camera or a decoder delivers them; not in the reference, whose forward wants
+        a float chunk that holds the previous call's last `step` frames again (online_demo.py:54-62 restacks and converts them on
+        every step).  Call it after the unchanged first step, ``forward(chunk, is_first_step=True, queries=...)``, which only reads
+        the chunk's shape and device: a one-frame dummy [1,1,3,H,W] of the right H, W on the right device does.
+
+        frames: uint8 or float32, channels-last [n,H,W,3] or planar [n,3,H,W], or ONE frame [H,W,3] / [3,H,W]; `layout` ("hwc" /
+        "chw") settles the corner where both readings fit (H == 3 or W == 3).  On the device, or on the host: a host tensor is
+        uploaded as it is -- uint8 stays uint8 -- with one copy.  Any number of frames per call: they are resized on arrival by one
+        launch (ops.ingest_frames: the values of forward's F.interpolate) straight into a resident [window_len,3,ih,iw] float32
+        buffer, allocated once per stream shape; nothing of the raw frames is kept.  Whenever the buffer holds what the next window
+        needs -- window_len frames for the first one, `step` for every later one -- one model.stream_push runs: the k-th tracking
+        step happens as soon as frames < k*step + window_len have arrived, whatever the partition, and returns what the k-th tracked
+        forward call returns for the chunk of those frames, while every frame is encoded and pooled once.  A push that completes
+        several windows runs them all and returns the last result; one that completes none returns (None, None).
+
+        final=True: the stream ends with this push; 1 .. step-1 leftover frames (or fewer than window_len when no window has run:
+        a video shorter than one window) are tracked as the short closing chunk.  After it push_frames raises until the next first
+        step.  add_support_grid: as in forward, pass what the first step was given.  Returns (tracks, visibility) shaped, scaled
+        and thresholded as forward returns them; add_queries / remove_queries work between two pushes.  One stream is fed one way:
+        forward on a pushed stream raises (model.stream_push)."""
+        if self.v2:
+            raise NotImplementedError("CoTracker2 streams are fed overlapping chunks through forward(): push_frames on a v2 predictor "
+                                      "is not implemented")
+        if self._hw is None or getattr(self, "queries", None) is None:
+            raise RuntimeError("push_frames: run the first step first: forward(chunk, is_first_step=True, queries=...)")
+        if self._push_closed:
+            raise RuntimeError("push_frames: final=True has ended this stream; start the next one with a first step")
+        if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() not in (3, 4):
+            raise ValueError("push_frames: frames must be a uint8 or float32 tensor [n,H,W,3], [n,3,H,W], [H,W,3] or [3,H,W]")
+        if frames.dim() == 3:
+            frames = frames[None]
+        H, W = self._hw
+        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
+        if layout is None and hwc and chw:
+            raise ValueError(f"push_frames: {tuple(frames.shape)} frames read both ways: pass layout='hwc' or 'chw'")
+        layout = layout or ("hwc" if hwc else "chw")
+        if layout not in ("hwc", "chw") or not (hwc if layout == "hwc" else chw):
+            raise ValueError(f"push_frames: expected {H} x {W} frames, [n,{H},{W},3] or [n,3,{H},{W}]; got {tuple(frames.shape)}"
+                             + (f" for layout {layout!r}" if layout else ""))
+        dev = self.queries.device
+        if frames.device != dev:
+            frames = frames.to(dev, non_blocking=True)  # the one copy; uint8 stays uint8
+        S, step = self.model.window_len, self.step
+        ih, iw = self.interp_shape
+        buf = self._push_buf
+        if buf is None or tuple(buf.shape) != (S, 3, ih, iw) or buf.device != dev:
+            buf = self._push_buf = torch.empty(S, 3, ih, iw, device=dev, dtype=torch.float32)
+        out, i, n = None, 0, frames.shape[0]
+        while i < n:
+            need = step if self._push_tracked else S
+            k = min(n - i, need - self._push_fill)
+            self._ingest(frames[i:i + k], buf[self._push_fill:self._push_fill + k], layout)
+            i, self._push_fill = i + k, self._push_fill + k
+            if self._push_fill == need:
+                out = self._push_step(buf[:need], False)
+        if final:
+            if self._push_fill > 0:
+                out = self._push_step(buf[:self._push_fill], True)
+            self._push_closed = True
+        return (None, None) if out is None else self._user_result(*out, add_support_grid)
+
+    def _push_step(self, new_frames, final):
+        tracks, vis, conf, _ = self.model.stream_push(new_frames, self.queries, iters=6, final=final)
+        self._push_fill, self._push_tracked = 0, True
+        return tracks, vis, conf

@@ -47,6 +47,8 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_ingest_frames on the new struct ctk_ingest_args: raw frames
+ *       (uint8 / float32, channels-last / planar, strided) resized to the encoder's input in one launch.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_assign: slots of the resident query table of a running
  *       stream are handed to new queries, or emptied, between two calls (CTK_STREAM_EMPTY_FRAME).
  *   v9, additive (number unchanged): + ctk_stream_begin / ctk_stream_support / ctk_stream_commit on the struct ctk_stream_args: the stream state
@@ -304,6 +306,41 @@ int ctk_stream_commit(const ctk_stream_args* a, void* stream);
 #define CTK_STREAM_EMPTY_FRAME 1073741824.0f /* 2^30 */
 int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
                       void* stream);
+
+/* ---- frame ingest: decoder output -> encoder input in one launch -------------------------------------------------------------
+ * Replaces, for a stream that is fed frame by frame, the per-chunk
+ *     video_chunk = F.interpolate(video_chunk.reshape(B * T, C, H, W), tuple(self.interp_shape), mode="bilinear",
+ *                                 align_corners=True)                                    (predictor.py:288-290)
+ * and the float conversion in front of it (online_demo.py:54-62 restacks uint8 [H,W,3] frames and converts the whole window to
+ * float on every step).  Value for value that call on the source read as float32 NCHW: the arithmetic is stated once in
+ * csrc/ingest_math.h, FMAs where torch's GPU kernel has them, and a uint8 source gives the bits of the same values as float32.
+ * No antialiasing, as the reference.
+ *   src      F frames of H x W pixels, 3 channels; dtype CTK_INGEST_U8 or CTK_INGEST_F32
+ *   layout   CTK_INGEST_HWC: element (f, y, x, c) at src[f * frame_stride + y * row_stride + x * 3 + c]
+ *            CTK_INGEST_CHW: element (f, c, y, x) at src[f * frame_stride + (c * H + y) * row_stride + x]
+ *            strides in ELEMENTS: a cropped view or a pitch-aligned decoder surface needs no copy
+ *   dst      float32 planar [F,3,h,w], contiguous, values in the range of the source (0..255 for uint8): what
+ *            ctk_enc_stem_im2col reads; the 2 * (v / 255) - 1 stays there
+ * One launch on `stream`, no host synchronisation, capture-safe.  Validated before the launch: NULL a, src or dst: CTK_E_NULL; an
+ * unknown dtype or layout, F, H, W, h or w <= 0, F > 65535, a side above CTK_INGEST_MAX_SIDE, row_stride smaller than a row
+ * (3 W or W elements), frame_stride smaller than a frame (H or 3 H rows): CTK_E_SHAPE; dst not 16-byte aligned when w % 4 == 0 (the
+ * rows are stored as 16-byte vectors; 4-byte aligned otherwise), a float32 src not 4-byte aligned: CTK_E_ALIGN.             */
+#define CTK_INGEST_U8 0
+#define CTK_INGEST_F32 1
+#define CTK_INGEST_HWC 0
+#define CTK_INGEST_CHW 1
+#define CTK_INGEST_MAX_SIDE 32768
+typedef struct ctk_ingest_args {
+  const void* src;
+  int32_t dtype, layout;
+  int32_t F, H, W;
+  int32_t h, w;
+  int32_t reserved;     /* 0 */
+  int64_t frame_stride; /* elements between two frames of src   */
+  int64_t row_stride;   /* elements between two pixel rows      */
+  float* dst;
+} ctk_ingest_args;
+int ctk_ingest_frames(const ctk_ingest_args* a, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
