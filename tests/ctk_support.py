@@ -1,0 +1,296 @@
+"""What the test modules share: `from ctk_support import ...` (tests/ is on sys.path; this is a plain module -- not a conftest, not a
+plugin).  Helpers that used to be pasted from file to file live here once; where the copies differed, the difference is an argument
+and every module passes what its own copy did.  A fixture is shared by importing it under the name the module uses
+(`from ctk_support import precision_default as precision  # noqa: F401`).  Tolerances and bars stay in the module that asserts them."""
+import copy
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+S, STEP, STRIDE = 8, 4, 4  # window length, step and stride of the small models; their resolution
+HW = (64, 96)
+
+
+# ---- small things ---------------------------------------------------------------------------------------------------------------
+def dev():
+    return torch.device("cuda:0")
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
+
+
+def maxdiff(a, b):
+    """max |a - b| in float64; tensors (any device) and arrays."""
+    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, dtype=np.float64)
+    return float(np.abs(a - b).max())
+
+
+def logit(p):
+    p = p.detach().cpu().double() if torch.is_tensor(p) else torch.from_numpy(np.asarray(p)).double()
+    return torch.log(p / (1 - p))
+
+
+def bits(x):
+    """A tensor of 1- or 4-byte elements as integers (NaN patterns compare like any other)."""
+    return x.view(torch.uint8) if x.dtype == torch.uint8 else x.contiguous().view(torch.int32)
+
+
+def same_bits(a, b):
+    """Bit-for-bit equality (torch.equal would let -0 pass for +0 and fail NaN against NaN)."""
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    iv = {torch.float32: torch.int32, torch.float16: torch.int16, torch.float64: torch.int64}[a.dtype]
+    return torch.equal(a.contiguous().view(iv).cpu(), b.contiguous().view(iv).cpu())
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    from cotracker_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        g.build()
+    return _lib.load()
+
+
+# ---- the two Linear back ends ---------------------------------------------------------------------------------------------------
+PRECISIONS = ["f16x3", "f32"]
+
+
+@pytest.fixture(params=PRECISIONS)
+def precision_param(request):
+    """Hands out the back end's name; the test passes it on."""
+    return request.param
+
+
+def _as_default(request):
+    from cotracker_amd import model
+    old = model.DEFAULT_PRECISION
+    model.DEFAULT_PRECISION = request.param
+    yield request.param
+    model.DEFAULT_PRECISION = old
+
+
+@pytest.fixture(params=PRECISIONS)
+def precision_default(request):
+    """Also makes the back end model.DEFAULT_PRECISION for the test."""
+    yield from _as_default(request)
+
+
+@pytest.fixture(autouse=True, params=PRECISIONS)
+def precision_default_autouse(request):
+    """precision_default for every test of the importing module, asked for or not."""
+    yield from _as_default(request)
+
+
+# ---- models ---------------------------------------------------------------------------------------------------------------------
+SWITCHES = ("batch_mode", "hip_graph", "range_guard", "online_feature_cache", "stream_range_check", "stream_groups", "stream_slots")
+
+
+def small_model(cache, precision, kind="online", seed=1, window_len=8, model_resolution=(64, 96), **switches):
+    """A small synthetic-weight model on the GPU, built once per `cache` -- the calling module's own dict: tests count graph captures
+    and encoder calls and hold on to the stream state, so modules do not share instances.  kind: "online" / "offline" / "v2".
+    `switches` are set on EVERY hand-out, in the order given (a test that flipped one does not leak into the next)."""
+    from cotracker_amd.build_cotracker import build_cotracker
+    from cotracker_amd.model import CoTrackerThreeOffline, CoTrackerThreeOnline
+    from cotracker_amd.weights import fill_synthetic_
+    assert set(switches) <= set(SWITCHES), set(switches) - set(SWITCHES)
+    key = (precision, kind, seed, window_len, model_resolution)
+    if key not in cache:
+        if kind == "v2":
+            m = build_cotracker(None, v2=True, window_len=window_len).eval()
+        else:
+            cls = {"online": CoTrackerThreeOnline, "offline": CoTrackerThreeOffline}[kind]
+            m = cls(stride=STRIDE, corr_radius=3, window_len=window_len, model_resolution=model_resolution).eval()
+        fill_synthetic_(m, seed=seed)
+        m.precision = precision
+        cache[key] = m.to(dev())
+    m = cache[key]
+    for name, value in switches.items():
+        setattr(m, name, value)
+    return m
+
+
+def overflow_model(precision, **switches):
+    """tests/test_gpu_range.py: an MLP whose hidden activations leave the f16 range.  A fresh model per call."""
+    from cotracker_amd.model import CoTrackerThreeOnline
+    from cotracker_amd.weights import fill_synthetic_
+    m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
+    fill_synthetic_(m, seed=1)
+    with torch.no_grad():
+        m.updateformer.time_blocks[0].mlp.fc1.weight.mul_(3e5)
+        m.updateformer.time_blocks[0].mlp.fc2.weight.mul_(1e-5)
+    m.invalidate_packed_weights()
+    m.precision = precision
+    for name, value in switches.items():
+        setattr(m, name, value)
+    return m.to(dev())
+
+
+def copy_without_stream_state(m, stream_slots):
+    """A deep copy of the model that starts without a stream state of its own, with the slot switch as given."""
+    held, m._gstream = m._gstream, None
+    try:
+        ref = copy.deepcopy(m)
+    finally:
+        m._gstream = held
+    ref.stream_slots = stream_slots
+    return ref
+
+
+def count_encodes(m):
+    """-> a list that grows by the frame count of every encoder call of m, until the caller does `del m._encode`."""
+    calls = []
+    orig = m._encode
+
+    def counted(frames, *a, **k):
+        calls.append(int(frames.shape[0]))
+        return orig(frames, *a, **k)
+    m._encode = counted
+    return calls
+
+
+# ---- streams (tests/test_gpu_stream_groups.py, _slots.py, _push.py) -----------------------------------------------------------------
+def stream_inputs(G, N, T, seed=0, frames=None):
+    """One video of T frames and G query sets.  frames: the query frames to draw from, a list or a function of T; by default they
+    lie in the first, a middle and the last chunk.  Every group keeps a point at frame 0."""
+    g = torch.Generator().manual_seed(seed)
+    video = (torch.rand(1, T, 3, *HW, generator=g) * 255).to(dev())
+    q = torch.rand(G, N, 3, generator=g) * torch.tensor([1.0, HW[1] - 1.0, HW[0] - 1.0])
+    if callable(frames):
+        frames = frames(T)
+    frames = frames or [0, 0, 2, 3, T // 2 - 1, T // 2, T // 2 + 1, T - STEP - 1, T - 3, T - 2]
+    q[..., 0] = torch.tensor(frames, dtype=torch.float32)[torch.randint(0, len(frames), (G, N), generator=g)]
+    q[:, 0, 0] = 0.0
+    return video, q.to(dev())
+
+
+def chunks(T):
+    """The chunk starts of a stream over T frames (T = S + k * STEP: full chunks only)."""
+    return list(range(0, T - S + 1, STEP))
+
+
+def run_stream(m, video, q, iters=2, between=None, starts=None, lengths=None):
+    """-> the (coords, vis, conf) clones after every call.  between(k) runs before call k >= 1 (assigns and releases); starts /
+    lengths: the chunks, where they are not the full ones."""
+    m.init_video_online_processing()
+    outs = []
+    for k, t0 in enumerate(starts if starts is not None else chunks(video.shape[1])):
+        if k and between is not None:
+            between(k)
+        n = S if lengths is None else lengths[k]
+        c, v, f, _ = m(video[:, t0:t0 + n], q, iters=iters, is_online=True)
+        outs.append((c.clone(), v.clone(), f.clone()))
+    return outs
+
+
+# ---- frame ingest (tests/test_gpu_stream_push.py, test_ingest_host.py) --------------------------------------------------------------
+def source(dtype, layout, Fn, H, W, seed, pad=(0, 0), device="cpu"):
+    """A random source on `device`; pad = (extra rows, extra columns) of the allocation it is a cropped view of."""
+    g = torch.Generator().manual_seed(seed)
+    full = (Fn, H + pad[0], W + pad[1], 3) if layout == "hwc" else (Fn, 3, H + pad[0], W + pad[1])
+    x = torch.randint(0, 256, full, dtype=torch.uint8, generator=g)
+    if dtype == torch.float32:
+        x = x.float() + torch.rand(full, generator=g)  # not integer-valued: every product rounds
+    x = x.to(device)
+    return x[:, :H, :W] if layout == "hwc" else x[:, :, :H, :W]
+
+
+def nchw(src, layout, contiguous=False):
+    x = (src.permute(0, 3, 1, 2) if layout == "hwc" else src).float()
+    return x.contiguous() if contiguous else x
+
+
+def fp64_resize(x, size):
+    """x [F,3,H,W] (any dtype, any device) -> float64 [F,3,h,w]: tap indices and weights from the float32 coordinate arithmetic of
+    ATen (area_pixel_compute_scale / _source_index, align_corners=True), values and blend in float64 (the rule of
+    oracle/window_fp64.py for tap positions)."""
+    H, W = x.shape[-2:]
+
+    def axis(n_in, n_out):
+        r = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32) if n_out > 1 \
+            else torch.tensor(0.0)
+        s = r.to(x.device) * torch.arange(n_out, dtype=torch.float32, device=x.device)
+        i0 = s.long()
+        i1 = i0 + (i0 < n_in - 1).long()
+        l1 = s - i0.float()
+        l0 = 1.0 - l1
+        return i0, i1, l0.double(), l1.double()
+
+    y0, y1, ly0, ly1 = axis(H, size[0])
+    x0, x1, lx0, lx1 = axis(W, size[1])
+    v = x.double()
+    top = v[:, :, y0][:, :, :, x0] * lx0 + v[:, :, y0][:, :, :, x1] * lx1
+    bot = v[:, :, y1][:, :, :, x0] * lx0 + v[:, :, y1][:, :, :, x1] * lx1
+    return top * ly0[:, None] + bot * ly1[:, None]
+
+
+def ulps(got, want):
+    """|got - want| in units of the float32 ulp of the value."""
+    want = want.double()
+    mag = want.abs().float().clamp_min(2.0 ** -20)
+    ulp = (torch.nextafter(mag, torch.full_like(mag, float("inf"))) - mag).double()
+    return float(((got.double() - want).abs() / ulp).max())
+
+
+def host_library(tmp_path_factory, name):
+    """tests/host/<name>_host.cpp -- a csrc/*_math.h header behind a plain loop -- built with g++ under -ffp-contract=off, the flag
+    the device translation unit is built with -> the loaded library."""
+    so = os.path.join(str(tmp_path_factory.mktemp(name)), f"lib{name}_host.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
+                    os.path.join(ROOT, "tests", "host", f"{name}_host.cpp")], check=True)
+    return C.CDLL(so)
+
+
+# ---- include/ctk.h as the C compiler sees it ----------------------------------------------------------------------------------------
+def abi_structs():
+    """C name -> ctypes mirror, for every struct that crosses the boundary."""
+    from cotracker_amd import _lib as L
+    return {"ctk_block_weights": L.BlockWeights, "ctk_model_weights": L.ModelWeights, "ctk_window_args": L.WindowArgs,
+            "ctk_gemm_args": L.GemmArgs, "ctk_attn_args": L.AttnArgs, "ctk_attn_batch2": L.AttnBatch2,
+            "ctk_window_batch": L.WindowBatch, "ctk_stream_args": L.StreamArgs, "ctk_ingest_args": L.IngestArgs,
+            "ctk_former_weights": L.FormerWeights, "ctk_v2_window_args": L.V2WindowArgs, "ctk_v2_weights": L.V2Weights,
+            "ctk_profile_row": L.ProfileRow}
+
+
+@functools.lru_cache(maxsize=None)
+def header_layout():
+    """ONE C program, generated from the ctypes classes of cotracker_amd._lib (their field names are the C field names), compiled
+    against include/ctk.h and run once per session ->
+      "sizeof"    {C struct name: bytes},
+      "offsetof"  {C struct name: {field: bytes}} for every field of every mirror,
+      "constants" {"CTK_X": value} for every CTK_* #define / enumerator of the header that _lib mirrors as the number X, in the
+                  number type _lib uses, and "as_long" the same values converted with (long)."""
+    from cotracker_amd import _lib as L
+    header = open(os.path.join(ROOT, "include", "ctk.h")).read()
+    defined = re.findall(r"#define (CTK_\w+)", header) + re.findall(r"\b(CTK_\w+) = -?\d", header)  # macros and enumerators
+    names = sorted({n for n in defined if type(getattr(L, n[4:], None)) in (int, float)})
+    lines = []
+    for cname, cls in abi_structs().items():
+        lines.append(f'printf("S {cname} - %zu\\n", sizeof({cname}));')
+        lines += [f'printf("F {cname} {f[0]} %zu\\n", offsetof({cname}, {f[0]}));' for f in cls._fields_]
+    lines += [f'printf("K {n} %ld %.17g\\n", (long)({n}), (double)({n}));' for n in names]
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "layout.c"), os.path.join(d, "layout")
+        with open(src, "w") as f:
+            f.write('#include <stddef.h>\n#include <stdio.h>\n#include "ctk.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0;\n}\n")
+        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+        out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    lay = {"sizeof": {}, "offsetof": {c: {} for c in abi_structs()}, "constants": {}, "as_long": {}}
+    for kind, a, b, *v in (ln.split() for ln in out.splitlines()):
+        if kind == "S":
+            lay["sizeof"][a] = int(v[0])
+        elif kind == "F":
+            lay["offsetof"][a][b] = int(v[0])
+        else:
+            lay["as_long"][a] = int(b)
+            lay["constants"][a] = float(v[0]) if isinstance(getattr(L, a[4:]), float) else int(b)
+    return lay

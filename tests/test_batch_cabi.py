@@ -3,23 +3,13 @@ the new symbols, struct sizes against the C compiler, argument validation before
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import ROOT, header_layout, lib  # noqa: F401
 
 NEW_SYMBOLS = ("ctk_forward_window_batch_workspace_bytes", "ctk_forward_window_batch", "ctk_window_batch_graph_create",
                "ctk_attention_ex")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def _batch(B, S=16, N=100, iters=6):
@@ -44,16 +34,11 @@ def test_new_symbols_are_declared_bound_and_exported(lib):
     assert lib.ctk_abi_version() == 9  # additive: no existing struct or symbol changed
 
 
-def test_batch_struct_sizes_match_header(tmp_path):
+def test_batch_struct_sizes_match_header():
     from cotracker_amd import _lib as L
     pairs = {"ctk_window_batch": L.WindowBatch, "ctk_attn_batch2": L.AttnBatch2, "ctk_attn_args": L.AttnArgs,
              "ctk_window_args": L.WindowArgs}
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include "ctk.h"\nint main(void){' +
-                   "".join(f'printf("{n} %zu\\n", sizeof({n}));' for n in pairs) + "return 0;}\n")
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    out = header_layout()["sizeof"]
     for n, cls in pairs.items():
         assert C.sizeof(cls) == int(out[n]), (n, C.sizeof(cls), out[n])
     assert C.sizeof(L.WindowBatch) == 16 and C.sizeof(L.AttnBatch2) == 48

@@ -8,16 +8,7 @@ import re
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
+from ctk_support import ROOT, abi_structs, header_layout, lib  # noqa: F401
 
 
 def test_every_declared_symbol_is_exported(lib):
@@ -108,21 +99,22 @@ def test_v2_driver_argument_validation_without_gpu(lib):
     assert lib.ctk_v2_window_graph_create(C.byref(a), C.byref(w), None, 0, C.byref(h)) == -1 and not h.value
 
 
-def test_struct_sizes_match_header(tmp_path):
-    """ctypes mirrors vs the C compiler's view of include/ctk.h: sizeof of every struct that crosses the boundary."""
-    import subprocess
+def test_struct_sizes_match_header():
+    """ctypes mirrors vs the C compiler's view of include/ctk.h: sizeof of every struct that crosses the boundary, offsetof of every
+    field of it (a mirror with two pointers swapped keeps its size), the CTK_* constants the binding restates -- and no
+    ctypes.Structure in the binding that the comparison leaves out."""
     from cotracker_amd import _lib as L
-    pairs = {"ctk_block_weights": L.BlockWeights, "ctk_model_weights": L.ModelWeights, "ctk_window_args": L.WindowArgs,
-             "ctk_gemm_args": L.GemmArgs, "ctk_attn_args": L.AttnArgs, "ctk_former_weights": L.FormerWeights,
-             "ctk_v2_window_args": L.V2WindowArgs, "ctk_v2_weights": L.V2Weights, "ctk_profile_row": L.ProfileRow}
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include "ctk.h"\nint main(void){' +
-                   "".join(f'printf("{n} %zu\\n", sizeof({n}));' for n in pairs) + "return 0;}\n")
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    pairs, lay = abi_structs(), header_layout()
+    mirrors = {v for v in vars(L).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert mirrors == set(pairs.values()), mirrors ^ set(pairs.values())
+    assert len(pairs) == len(lay["sizeof"]) == 13
     for n, cls in pairs.items():
-        assert C.sizeof(cls) == int(out[n]), (n, C.sizeof(cls), out[n])
+        assert C.sizeof(cls) == lay["sizeof"][n], (n, C.sizeof(cls), lay["sizeof"][n])
+        assert [f[0] for f in cls._fields_] == list(lay["offsetof"][n])
+        for f in cls._fields_:
+            assert getattr(cls, f[0]).offset == lay["offsetof"][n][f[0]], (n, f[0], getattr(cls, f[0]).offset, lay["offsetof"][n][f[0]])
+    for name, value in lay["constants"].items():
+        assert getattr(L, name[4:]) == value, (name, getattr(L, name[4:]), value)
     assert C.sizeof(L.BlockWeights) == 17 * 8
 
 

@@ -6,63 +6,23 @@ on the contents of the other videos of its batch, the joint call is deterministi
 two-level attention batch equals B single-level calls bit for bit.  Parity with the reference is per element, at the usual
 bars (1e-3 px, 1e-4 logit), against goldens that already exist (the reference is batch-independent).
 """
+import functools
 import os
 import warnings
 
-import numpy as np
 import pytest
 import torch
 
+import ctk_support
+from ctk_support import ROOT, dev, logit, maxdiff, t
+from ctk_support import precision_default as precision  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL_PX, TOL_LOGIT = 1e-3, 1e-4
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def maxdiff(a, b):
-    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
-    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max())
-
-
-def logit(p):
-    p = p.detach().cpu().double() if torch.is_tensor(p) else torch.from_numpy(np.asarray(p)).double()
-    return torch.log(p / (1 - p))
-
-
-@pytest.fixture(params=["f16x3", "f32"])
-def precision(request):
-    from cotracker_amd import model
-    old = model.DEFAULT_PRECISION
-    model.DEFAULT_PRECISION = request.param
-    yield request.param
-    model.DEFAULT_PRECISION = old
-
-
 _models = {}
-
-
-def small_model(precision, kind="online", seed=1, res=(64, 96)):
-    from cotracker_amd.model import CoTrackerThreeOffline, CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    key = (precision, kind, seed, res)
-    if key not in _models:
-        cls = CoTrackerThreeOnline if kind == "online" else CoTrackerThreeOffline
-        m = cls(stride=4, corr_radius=3, window_len=8, model_resolution=res).eval()
-        fill_synthetic_(m, seed=seed)
-        m.precision = precision
-        _models[key] = m.to(dev())
-    m = _models[key]
-    m.batch_mode, m.hip_graph, m.range_guard, m.online_feature_cache = "loop", False, True, False
-    return m
+small_model = functools.partial(ctk_support.small_model, _models, batch_mode="loop", hip_graph=False, range_guard=True,
+                                online_feature_cache=False)
 
 
 def random_window(seed, S, N, HW=(24, 32), iters=2, with_mask=False, space_attn=True):

@@ -11,13 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+from ctk_support import dev, same_bits
+
 pytestmark = pytest.mark.gpu
 
 EPS = float(np.float32(1e-5))  # the kernel receives eps as a float
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def _p(t):
@@ -32,13 +30,6 @@ def _lib():
 def _stream():
     from cotracker_amd import ops
     return ops._stream()
-
-
-def same_bits(a, b):
-    """Bit-for-bit equality (torch.equal would let -0 pass for +0 and fail NaN against NaN)."""
-    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
-    iv = {torch.float32: torch.int32, torch.float16: torch.int16, torch.float64: torch.int64}[a.dtype]
-    return torch.equal(a.contiguous().view(iv).cpu(), b.contiguous().view(iv).cpu())
 
 
 def sh_of(ref_f32_cpu):

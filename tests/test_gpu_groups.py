@@ -7,56 +7,20 @@ the same windows passed unshared (flag 0, aliased fmaps) bit for bit; a group do
 deterministic, directly and through its hipGraph; the model in "loop" mode equals G separate calls bit for bit.  "joint" mode is
 fp32-class equal to the loop, at the bars tests/test_gpu_batch.py uses for joint against loop.
 """
+import functools
+
 import pytest
 import torch
+
+import ctk_support
+from ctk_support import count_encodes, dev, logit, maxdiff
+from ctk_support import precision_default as precision  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 JOINT_PX, JOINT_LOGIT = 2e-4, 2e-5  # joint vs loop (tests/test_gpu_batch.py)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def maxdiff(a, b):
-    return float((a.detach().double() - b.detach().double()).abs().max())
-
-
-def logit(p):
-    p = p.detach().double()
-    return torch.log(p / (1 - p))
-
-
-@pytest.fixture(params=["f16x3", "f32"])
-def precision(request):
-    from cotracker_amd import model
-    old = model.DEFAULT_PRECISION
-    model.DEFAULT_PRECISION = request.param
-    yield request.param
-    model.DEFAULT_PRECISION = old
-
-
 _models = {}
-
-
-def small_model(precision, kind="online", seed=1, res=(64, 96)):
-    from cotracker_amd.build_cotracker import build_cotracker
-    from cotracker_amd.model import CoTrackerThreeOffline, CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    key = (precision, kind, seed, res)
-    if key not in _models:
-        if kind == "v2":
-            m = build_cotracker(None, v2=True, window_len=8).eval()
-        else:
-            cls = CoTrackerThreeOnline if kind == "online" else CoTrackerThreeOffline
-            m = cls(stride=4, corr_radius=3, window_len=8, model_resolution=res).eval()
-        fill_synthetic_(m, seed=seed)
-        m.precision = precision
-        _models[key] = m.to(dev())
-    m = _models[key]
-    m.batch_mode, m.hip_graph, m.range_guard = "loop", False, True
-    return m
+small_model = functools.partial(ctk_support.small_model, _models, batch_mode="loop", hip_graph=False, range_guard=True)
 
 
 def group_tensors(seed, G, S, N, HW=(24, 32), with_mask=True, qseeds=None):
@@ -201,17 +165,6 @@ def video_and_queries(G, N, T, HW=(64, 96), seed=0, mixed_frames=True):
     q = torch.rand(G, N, 3, generator=g) * torch.tensor([1.0, HW[1] - 1.0, HW[0] - 1.0])
     q[..., 0] = torch.randint(0, T - 2, (G, N), generator=g).float() if mixed_frames else 0.0
     return video, q.to(dev())
-
-
-def count_encodes(m):
-    calls = []
-    orig = m._encode
-
-    def counted(*a, **k):
-        calls.append(1)
-        return orig(*a, **k)
-    m._encode = counted
-    return calls
 
 
 @pytest.mark.parametrize("kind,T", [("offline", 10), ("online", 14)])

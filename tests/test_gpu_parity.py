@@ -11,26 +11,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from ctk_support import dev, logit, maxdiff, t  # noqa: E402
+# every test runs on both Linear back ends: split-half MFMA (the default) and exact-f32 MFMA
+from ctk_support import precision_default_autouse as precision  # noqa: E402,F401
 from oracle import cotracker_oracle as O  # noqa: E402  (checker only)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def maxdiff(a, b):
-    a = a.detach().cpu().double().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
-    b = b.detach().cpu().double().numpy() if torch.is_tensor(b) else np.asarray(b, dtype=np.float64)
-    return float(np.abs(a - b).max())
-
-
-def logit(p):
-    p = p.detach().cpu().double() if torch.is_tensor(p) else torch.from_numpy(np.asarray(p)).double()
-    return torch.log(p / (1 - p))
 
 
 def to_nhwc(f):  # [S,C,H,W] numpy -> NHWC device tensor
@@ -47,16 +31,6 @@ def x_to_ours(x_ref):
     x[:, 1024:1026] = xr[:, 0:2]
     x[:, 1026:1110] = xr[:, 1026:1110]
     return x
-
-
-@pytest.fixture(autouse=True, params=["f16x3", "f32"])
-def precision(request):
-    """Every test runs on both Linear back ends: split-half MFMA (the default) and exact-f32 MFMA."""
-    from cotracker_amd import model
-    old = model.DEFAULT_PRECISION
-    model.DEFAULT_PRECISION = request.param
-    yield request.param
-    model.DEFAULT_PRECISION = old
 
 
 _ops_models = {}

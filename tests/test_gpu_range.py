@@ -15,15 +15,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from ctk_support import dev, maxdiff  # noqa: E402
 from oracle import cotracker_oracle as O  # noqa: E402  (checker only)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def maxdiff(a, b):
-    return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
 
 
 @pytest.mark.parametrize("ascale", [2.0 ** -15, 2.0 ** -10, 1.0, 2.0 ** 10, 2.0 ** 13])

@@ -7,85 +7,23 @@ as exact: every kernel against the torch expressions it replaces; the model in "
 call, with and without the window graph; determinism and group independence of "joint" mode.  "joint" against "loop" is fp32-class
 (the bars of tests/test_gpu_groups.py)."""
 import copy
+import functools
 import warnings
 
 import pytest
 import torch
 
+import ctk_support
+from ctk_support import HW, S, STEP, STRIDE, chunks, count_encodes, dev, maxdiff, run_stream, stream_inputs
+from ctk_support import precision_param as precision  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 JOINT_PX, JOINT_LOGIT = 2e-4, 2e-5  # joint vs loop (tests/test_gpu_groups.py)
-S, STEP, STRIDE = 8, 4, 4
-HW = (64, 96)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def maxdiff(a, b):
-    return float((a.detach().double() - b.detach().double()).abs().max())
-
-
-@pytest.fixture(params=["f16x3", "f32"])
-def precision(request):
-    return request.param
-
-
 _models = {}
-
-
-def small_model(precision, seed=1):
-    from cotracker_amd.model import CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    if (precision, seed) not in _models:
-        m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
-        fill_synthetic_(m, seed=seed)
-        m.precision = precision
-        _models[(precision, seed)] = m.to(dev())
-    m = _models[(precision, seed)]
-    m.batch_mode, m.hip_graph, m.range_guard, m.stream_groups = "loop", False, True, True
-    m.online_feature_cache, m.stream_range_check = False, "deferred"
-    return m
-
-
-def stream_inputs(G, N, T, seed=0, frames=None):
-    """One video of T frames and G query sets whose frames lie in the first, a middle and the last chunk (every group keeps
-    points at frame 0)."""
-    g = torch.Generator().manual_seed(seed)
-    video = (torch.rand(1, T, 3, *HW, generator=g) * 255).to(dev())
-    q = torch.rand(G, N, 3, generator=g) * torch.tensor([1.0, HW[1] - 1.0, HW[0] - 1.0])
-    frames = frames or [0, 0, 2, 3, T // 2 - 1, T // 2, T // 2 + 1, T - STEP - 1, T - 3, T - 2]
-    q[..., 0] = torch.tensor(frames, dtype=torch.float32)[torch.randint(0, len(frames), (G, N), generator=g)]
-    q[:, 0, 0] = 0.0
-    return video, q.to(dev())
-
-
-def chunks(T):
-    """The chunk starts of a stream over T frames (T = S + k * STEP: full chunks only)."""
-    return list(range(0, T - S + 1, STEP))
-
-
-def run_stream(m, video, q, iters=2, starts=None, lengths=None):
-    """-> the (coords, vis, conf) clones after every call."""
-    m.init_video_online_processing()
-    outs = []
-    for i, t0 in enumerate(starts if starts is not None else chunks(video.shape[1])):
-        n = S if lengths is None else lengths[i]
-        c, v, f, _ = m(video[:, t0:t0 + n], q, iters=iters, is_online=True)
-        outs.append((c.clone(), v.clone(), f.clone()))
-    return outs
-
-
-def count_encodes(m):
-    calls = []
-    orig = m._encode
-
-    def counted(frames, *a, **k):
-        calls.append(int(frames.shape[0]))
-        return orig(frames, *a, **k)
-    m._encode = counted
-    return calls
+small_model = functools.partial(ctk_support.small_model, _models, batch_mode="loop", hip_graph=False, range_guard=True, stream_groups=True,
+                                online_feature_cache=False, stream_range_check="deferred")
+overflow_model = functools.partial(ctk_support.overflow_model, stream_groups=True)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -321,21 +259,6 @@ def test_short_last_chunk_and_one_chunk_stream(precision, mode):
     m(video[:, :5], q, iters=2, is_online=True)
     with pytest.raises(AssertionError, match="shorter than the window"):
         m(video[:, STEP:STEP + S], q, iters=2, is_online=True)
-
-
-def overflow_model(precision):
-    """tests/test_gpu_range.py: an MLP whose hidden activations leave the f16 range."""
-    from cotracker_amd.model import CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
-    fill_synthetic_(m, seed=1)
-    with torch.no_grad():
-        m.updateformer.time_blocks[0].mlp.fc1.weight.mul_(3e5)
-        m.updateformer.time_blocks[0].mlp.fc2.weight.mul_(1e-5)
-    m.invalidate_packed_weights()
-    m.precision = precision
-    m.stream_groups = True
-    return m.to(dev())
 
 
 @pytest.mark.parametrize("mode", ["loop", "joint"])

@@ -7,25 +7,28 @@ The oracle is this repository's own chunk path: a stream fed overlapping chunks 
 and the pooling are per frame and the kept features are therefore the bits a re-computation gives.  The kernel is compared with a
 float64 restatement computed on the GPU and, bit for bit, with F.interpolate on the GPU.  Shapes and helpers as in
 tests/test_gpu_stream_slots.py."""
-import copy
+import functools
 import warnings
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import ctk_support
+from ctk_support import HW, S, STEP, STRIDE, dev, fp64_resize, maxdiff, ulps
+
 pytestmark = pytest.mark.gpu
 
-S, STEP, STRIDE = 8, 4, 4
-HW = (64, 96)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def maxdiff(a, b):
-    return float((a.detach().double() - b.detach().double()).abs().max())
+source = functools.partial(ctk_support.source, device=dev())
+nchw = functools.partial(ctk_support.nchw, contiguous=True)
+_models = {}
+small_model = functools.partial(ctk_support.small_model, _models, batch_mode="loop", hip_graph=False, range_guard=True, stream_groups=False,
+                                stream_slots=False, online_feature_cache=False, stream_range_check="deferred")
+# the oracle: a copy of the model, fed overlapping chunks through forward on the device stream state
+chunk_model = functools.partial(ctk_support.copy_without_stream_state, stream_slots=True)
+# query frames spread over the stream
+stream_inputs = functools.partial(ctk_support.stream_inputs,
+                                  frames=lambda T: [0, 0, 2, 3, 7, 9, T // 2 - 1, T // 2, T // 2 + 1, T - S, T - 5, T - 2])
 
 
 # ---- the kernel -------------------------------------------------------------------------------------------------------------
@@ -35,55 +38,11 @@ CASES = [  # (H, W, h, w)
 ]
 
 
-def source(dtype, layout, Fn, H, W, seed, pad=(0, 0)):
-    g = torch.Generator().manual_seed(seed)
-    full = (Fn, H + pad[0], W + pad[1], 3) if layout == "hwc" else (Fn, 3, H + pad[0], W + pad[1])
-    x = torch.randint(0, 256, full, dtype=torch.uint8, generator=g)
-    if dtype == torch.float32:
-        x = x.float() + torch.rand(full, generator=g)
-    x = x.to(dev())
-    return x[:, :H, :W] if layout == "hwc" else x[:, :, :H, :W]
-
-
-def nchw(src, layout):
-    return (src.permute(0, 3, 1, 2) if layout == "hwc" else src).float().contiguous()
-
-
 def ingest(src, layout, size, out=None):
     from cotracker_amd import ops
     if out is None:
         out = torch.empty(src.shape[0], 3, *size, device=dev())
     return ops.ingest_frames(src, out, layout=layout)
-
-
-def fp64_resize(x, size):
-    """x [F,3,H,W] float32 on the GPU -> float64 [F,3,h,w]: taps and weights from ATen's float32 coordinate arithmetic
-    (align_corners=True), values and blend in float64 (the rule of oracle/window_fp64.py for tap positions)."""
-    H, W = x.shape[-2:]
-
-    def axis(n_in, n_out):
-        r = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32) if n_out > 1 \
-            else torch.tensor(0.0)
-        s = r.to(dev()) * torch.arange(n_out, dtype=torch.float32, device=dev())
-        i0 = s.long()
-        i1 = i0 + (i0 < n_in - 1).long()
-        l1 = s - i0.float()
-        l0 = 1.0 - l1
-        return i0, i1, l0.double(), l1.double()
-
-    y0, y1, ly0, ly1 = axis(H, size[0])
-    x0, x1, lx0, lx1 = axis(W, size[1])
-    v = x.double()
-    top = v[:, :, y0][:, :, :, x0] * lx0 + v[:, :, y0][:, :, :, x1] * lx1
-    bot = v[:, :, y1][:, :, :, x0] * lx0 + v[:, :, y1][:, :, :, x1] * lx1
-    return top * ly0[:, None] + bot * ly1[:, None]
-
-
-def ulps(got, want):
-    want = want.double()
-    mag = want.abs().float().clamp_min(2.0 ** -20)
-    ulp = (torch.nextafter(mag, torch.full_like(mag, float("inf"))) - mag).double()
-    return float(((got.double() - want).abs() / ulp).max())
 
 
 @pytest.mark.parametrize("H,W,h,w", CASES)
@@ -154,44 +113,6 @@ def test_advance_pyramid_equals_set_pyramid_of_the_full_chunk():
 
 
 # ---- model.stream_push ----------------------------------------------------------------------------------------------------------
-_models = {}
-
-
-def small_model(precision, seed=1):
-    from cotracker_amd.model import CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    if (precision, seed) not in _models:
-        m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
-        fill_synthetic_(m, seed=seed)
-        m.precision = precision
-        _models[(precision, seed)] = m.to(dev())
-    m = _models[(precision, seed)]
-    m.batch_mode, m.hip_graph, m.range_guard, m.stream_groups, m.stream_slots = "loop", False, True, False, False
-    m.online_feature_cache, m.stream_range_check = False, "deferred"
-    return m
-
-
-def chunk_model(m):
-    """The oracle: a copy of the model, fed overlapping chunks through forward on the device stream state."""
-    held, m._gstream = m._gstream, None
-    try:
-        ref = copy.deepcopy(m)
-    finally:
-        m._gstream = held
-    ref.stream_slots = True
-    return ref
-
-
-def stream_inputs(G, N, T, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    video = (torch.rand(1, T, 3, *HW, generator=g) * 255).to(dev())
-    q = torch.rand(G, N, 3, generator=g) * torch.tensor([1.0, HW[1] - 1.0, HW[0] - 1.0])
-    frames = [0, 0, 2, 3, 7, 9, T // 2 - 1, T // 2, T // 2 + 1, T - S, T - 5, T - 2]  # query frames spread over the stream
-    q[..., 0] = torch.tensor(frames, dtype=torch.float32)[torch.randint(0, len(frames), (G, N), generator=g)]
-    q[:, 0, 0] = 0.0
-    return video, q.to(dev())
-
-
 def assert_same(got, want, what):
     for name, x, y in zip(("tracks", "vis", "conf"), got, want):
         assert x.shape == y.shape and torch.equal(x, y), (what, name, maxdiff(x, y))

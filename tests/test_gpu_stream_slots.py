@@ -9,58 +9,26 @@ whose support rows are zeroed by hand when a slot changes its occupant), equals 
 and release.  Both on the history rows >= first_row of every slot, bit for bit in "loop" mode.  The shapes and helpers are those
 of tests/test_gpu_stream_groups.py."""
 import copy
+import functools
 import pickle
 import warnings
 
 import pytest
 import torch
 
+import ctk_support
+from ctk_support import HW, S, STEP, STRIDE, bits, chunks, count_encodes, dev, maxdiff, run_stream, stream_inputs
+from ctk_support import precision_param as precision  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 JOINT_PX, JOINT_LOGIT = 2e-4, 2e-5  # joint vs loop (tests/test_gpu_groups.py)
-S, STEP, STRIDE = 8, 4, 4
-HW = (64, 96)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def maxdiff(a, b):
-    return float((a.detach().double() - b.detach().double()).abs().max())
-
-
-@pytest.fixture(params=["f16x3", "f32"])
-def precision(request):
-    return request.param
-
-
 _models = {}
-
-
-def small_model(precision, seed=1):
-    from cotracker_amd.model import CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    if (precision, seed) not in _models:
-        m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
-        fill_synthetic_(m, seed=seed)
-        m.precision = precision
-        _models[(precision, seed)] = m.to(dev())
-    m = _models[(precision, seed)]
-    m.batch_mode, m.hip_graph, m.range_guard, m.stream_groups, m.stream_slots = "loop", False, True, True, True
-    m.online_feature_cache, m.stream_range_check = False, "deferred"
-    return m
-
-
-def oracle_of(m):
-    """The same model with the slot switch off: G == 1 streams on the torch glue, G > 1 on the grouped path as it was."""
-    held, m._gstream = m._gstream, None  # (the oracle starts without a stream state of its own)
-    try:
-        ref = copy.deepcopy(m)
-    finally:
-        m._gstream = held
-    ref.stream_slots = False
-    return ref
+small_model = functools.partial(ctk_support.small_model, _models, batch_mode="loop", hip_graph=False, range_guard=True, stream_groups=True,
+                                stream_slots=True, online_feature_cache=False, stream_range_check="deferred")
+overflow_model = functools.partial(ctk_support.overflow_model, stream_groups=True, stream_slots=True)
+# the same model with the slot switch off: G == 1 streams on the torch glue, G > 1 on the grouped path as it was
+oracle_of = functools.partial(ctk_support.copy_without_stream_state, stream_slots=False)
 
 
 def empty_row():
@@ -68,35 +36,9 @@ def empty_row():
     return torch.tensor([ops.EMPTY_FRAME, 0.0, 0.0], device=dev())
 
 
-def stream_inputs(G, N, T, seed=0, frames=None):
-    g = torch.Generator().manual_seed(seed)
-    video = (torch.rand(1, T, 3, *HW, generator=g) * 255).to(dev())
-    q = torch.rand(G, N, 3, generator=g) * torch.tensor([1.0, HW[1] - 1.0, HW[0] - 1.0])
-    frames = frames or [0, 0, 2, 3, T // 2 - 1, T // 2, T // 2 + 1, T - STEP - 1, T - 3, T - 2]
-    q[..., 0] = torch.tensor(frames, dtype=torch.float32)[torch.randint(0, len(frames), (G, N), generator=g)]
-    q[:, 0, 0] = 0.0
-    return video, q.to(dev())
-
-
-def chunks(T):
-    return list(range(0, T - S + 1, STEP))
-
-
 def call_of(frame):
     """The index of the call whose support range [left, right) holds `frame`."""
     return 0 if frame < S else (int(frame) - S) // STEP + 1
-
-
-def run_stream(m, video, q, iters=2, between=None, starts=None):
-    """-> the (coords, vis, conf) clones after every call; between(k) runs before call k >= 1 (assigns and releases)."""
-    m.init_video_online_processing()
-    outs = []
-    for k, t0 in enumerate(starts if starts is not None else chunks(video.shape[1])):
-        if k and between is not None:
-            between(k)
-        c, v, f, _ = m(video[:, t0:t0 + S], q, iters=iters, is_online=True)
-        outs.append((c.clone(), v.clone(), f.clone()))
-    return outs
 
 
 def own_rows(first_row, T):
@@ -113,26 +55,11 @@ def assert_own_rows_equal(got, want, first_row, what):
             (what, maxdiff(torch.where(sel, x, torch.zeros_like(x)), torch.where(sel, y, torch.zeros_like(y))))
 
 
-def count_encodes(m):
-    calls = []
-    orig = m._encode
-
-    def counted(frames, *a, **k):
-        calls.append(int(frames.shape[0]))
-        return orig(frames, *a, **k)
-    m._encode = counted
-    return calls
-
-
 # ----------------------------------------------------------------------------------------------------------------------
 # the kernel against the torch index expressions; every other byte of every buffer stays
 # ----------------------------------------------------------------------------------------------------------------------
 def buffers(gs):
     return [gs.queries, *gs.support, *gs.hist, gs.coords, gs.vis, gs.conf, gs.mask, *gs.pyr, gs.nonfinite]
-
-
-def bits(t):
-    return t.view(torch.uint8) if t.dtype == torch.uint8 else t.contiguous().view(torch.int32)
 
 
 @pytest.mark.parametrize("M,rows", [(1, 0), (1, None), (7, 5), (None, None), (None, 0)], ids=["one-0", "one-cap", "seven-5", "all-cap", "all-0"])
@@ -447,21 +374,6 @@ def test_every_refusal_raises_and_leaves_the_stream_alone():
     with pytest.raises(RuntimeError, match="ended the stream"):
         m.stream_assign([N - 2], ok)
     m._resolve_deferred_range_check()
-
-
-def overflow_model(precision):
-    """tests/test_gpu_range.py: an MLP whose hidden activations leave the f16 range."""
-    from cotracker_amd.model import CoTrackerThreeOnline
-    from cotracker_amd.weights import fill_synthetic_
-    m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=S, model_resolution=HW).eval()
-    fill_synthetic_(m, seed=1)
-    with torch.no_grad():
-        m.updateformer.time_blocks[0].mlp.fc1.weight.mul_(3e5)
-        m.updateformer.time_blocks[0].mlp.fc2.weight.mul_(1e-5)
-    m.invalidate_packed_weights()
-    m.precision = precision
-    m.stream_groups = m.stream_slots = True
-    return m.to(dev())
 
 
 @pytest.mark.parametrize("mode", ["loop", "joint"])

@@ -7,17 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+from ctk_support import dev, same_bits
+
 pytestmark = pytest.mark.gpu
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def same_bits(a, b):
-    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
-    iv = {torch.float32: torch.int32, torch.float16: torch.int16}[a.dtype]
-    return torch.equal(a.contiguous().view(iv).cpu(), b.contiguous().view(iv).cpu())
 
 
 # ---- token assembly --------------------------------------------------------------------------------------------------------------

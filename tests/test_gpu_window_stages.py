@@ -32,6 +32,9 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from ctk_support import dev  # noqa: E402
+# stages 3-8 run on both Linear back ends: split-half MFMA (the default) and exact-f32 MFMA
+from ctk_support import precision_param as precision  # noqa: E402,F401
 from oracle import window_fp64 as W  # noqa: E402  (checker only)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,10 +45,6 @@ F64_CHUNK = 800  # points per float64 volume (16 x 800 x 2401 doubles = 246 MB)
 # the bars the project holds at S = 8, N = 12 (tests/test_gpu_parity.py), and the end-to-end bar
 BAR = {"support": 1e-6, "volume": 3e-6, "corr_embed": 1e-5, "posenc": 1e-6, "former": 3e-5, "former_cap": 1e-4, "px": 1e-3,
        "logit": 1e-4}
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------
@@ -284,12 +283,6 @@ def get_case(name):
 @pytest.fixture(scope="module", params=list(SHAPES))
 def case(request):
     return get_case(request.param)
-
-
-@pytest.fixture(params=["f16x3", "f32"])
-def precision(request):
-    """Stages 3-8 run on both Linear back ends: split-half MFMA (the default) and exact-f32 MFMA."""
-    return request.param
 
 
 def former_ex(cs, precision, depth):

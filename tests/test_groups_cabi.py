@@ -4,23 +4,13 @@ before any HIP call, the workspace saving, the host-side switches."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import ROOT, header_layout, lib  # noqa: F401
 
 S, N = 16, 100
 BASE = 1 << 20  # fake device addresses: validation never dereferences them
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def _groups(B, flags=None, mask=False):
@@ -41,7 +31,7 @@ def _groups(B, flags=None, mask=False):
     return arr, L.WindowBatch(B, L.BATCH_SHARED_FMAPS if flags is None else flags, C.cast(arr, C.POINTER(L.WindowArgs)))
 
 
-def test_flag_in_header_binding_and_library(lib, tmp_path):
+def test_flag_in_header_binding_and_library(lib):
     from cotracker_amd import _lib as L
     header = open(os.path.join(ROOT, "include", "ctk.h")).read()
     m = re.search(r"#define CTK_BATCH_SHARED_FMAPS (\d+)\b", header)
@@ -52,14 +42,10 @@ def test_flag_in_header_binding_and_library(lib, tmp_path):
         assert re.search(rf"\bint {name}\(", header) and name in L.SYMBOLS and getattr(lib, name) is not None
     assert lib.ctk_abi_version() == 9 and re.search(r"#define CTK_ABI_VERSION 9\b", header)  # additive
     # the struct keeps its size and the flag sits where `reserved` sat
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ctk.h"\nint main(void){'
-                   'printf("%zu %zu %zu %d\\n", sizeof(ctk_window_batch), offsetof(ctk_window_batch, flags), '
-                   'offsetof(ctk_window_batch, videos), CTK_BATCH_SHARED_FMAPS);return 0;}\n')
-    exe = tmp_path / "sizes"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    assert out == ["16", "4", "8", "1"]
+    lay = header_layout()
+    out = [lay["sizeof"]["ctk_window_batch"], lay["offsetof"]["ctk_window_batch"]["flags"], lay["offsetof"]["ctk_window_batch"]["videos"],
+           lay["constants"]["CTK_BATCH_SHARED_FMAPS"]]
+    assert out == [16, 4, 8, 1]
     assert C.sizeof(L.WindowBatch) == 16 and L.WindowBatch.flags.offset == 4 and L.WindowBatch.videos.offset == 8
 
 

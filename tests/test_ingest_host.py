@@ -11,23 +11,17 @@ for uint8 and float32 sources, both layouts, strided sources, down- and upscalin
 that the last row and column never read past the image.
 """
 import ctypes as C
-import os
-import subprocess
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import fp64_resize, host_library, nchw, source, ulps
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("ingest")), "libingest_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "host", "ingest_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_library(tmp_path_factory, "ingest")
     lib.host_ingest_frames.restype = C.c_int
     lib.host_ingest_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_void_p, C.c_int,
                                        C.c_int, C.c_void_p]
@@ -49,52 +43,6 @@ def host(tmp_path_factory):
         return (out, top.value) if want_top else out
 
     return run
-
-
-def nchw(src, layout):
-    return (src.permute(0, 3, 1, 2) if layout == "hwc" else src).float()
-
-
-def fp64_resize(x, size):
-    """x [F,3,H,W] (any dtype) -> float64 [F,3,h,w]: tap indices and weights from the float32 coordinate arithmetic of ATen
-    (area_pixel_compute_scale / _source_index, align_corners=True), values and blend in float64."""
-    H, W = x.shape[-2:]
-    h, w = size
-
-    def axis(n_in, n_out):
-        r = np.float32(n_in - 1) / np.float32(n_out - 1) if n_out > 1 else np.float32(0)
-        s = (r * np.arange(n_out, dtype=np.float32)).astype(np.float32)
-        i0 = s.astype(np.int64)
-        i1 = i0 + (i0 < n_in - 1)
-        l1 = (s - i0.astype(np.float32)).astype(np.float32)
-        l0 = (np.float32(1) - l1).astype(np.float32)
-        return i0, i1, l0.astype(np.float64), l1.astype(np.float64)
-
-    y0, y1, ly0, ly1 = axis(H, h)
-    x0, x1, lx0, lx1 = axis(W, w)
-    v = x.double().numpy()
-    top = v[:, :, y0][:, :, :, x0] * lx0 + v[:, :, y0][:, :, :, x1] * lx1
-    bot = v[:, :, y1][:, :, :, x0] * lx0 + v[:, :, y1][:, :, :, x1] * lx1
-    return torch.from_numpy(top * ly0[:, None] + bot * ly1[:, None])
-
-
-def ulps(got, want):
-    """|got - want| in units of the float32 ulp of the value."""
-    want = want.double()
-    ulp = torch.from_numpy(np.spacing(np.maximum(np.abs(want.float().numpy()), np.float32(2.0 ** -20)))).double()
-    return float(((got.double() - want).abs() / ulp).max())
-
-
-def source(dtype, layout, Fn, H, W, seed, pad=(0, 0)):
-    """A random source; pad = (extra rows, extra columns) of the allocation it is a cropped view of."""
-    g = torch.Generator().manual_seed(seed)
-    full = (Fn, H + pad[0], W + pad[1], 3) if layout == "hwc" else (Fn, 3, H + pad[0], W + pad[1])
-    x = torch.randint(0, 256, full, dtype=torch.uint8, generator=g)
-    if dtype == torch.float32:
-        x = x.float() + torch.rand(full, generator=g)  # not integer-valued: every product rounds
-    if layout == "hwc":
-        return x[:, :H, :W]
-    return x[:, :, :H, :W] if pad[0] == 0 else None  # (a planar crop in y breaks the plane stride rule: not a case)
 
 
 CASES = [  # (H, W, h, w)

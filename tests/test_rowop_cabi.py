@@ -5,26 +5,18 @@ CTK_E_* code BEFORE any HIP call.  The pointers below are made-up addresses: eve
 one way, so none of them may reach a launch.  The file runs only where no device is visible: there a call that slipped through
 a missing check returns a positive hipError_t, which no assertion here accepts, instead of launching on these addresses."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason="made-up device addresses: only where a stray launch cannot run")
 
+from ctk_support import lib  # noqa: E402,F401
+
 E_NULL, E_SHAPE, E_ALIGN = -1, -2, -3
 P = 0x10000        # a "pointer": non-NULL, 16-byte aligned, never dereferenced
 ODD = P + 8        # 8-byte aligned only
 ODD4 = P + 4       # 4-byte aligned only
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def _each_missing(call, good, required):

@@ -10,15 +10,13 @@ below is itself checked against the reference's: tests/golden/bilinear_sampler.n
 (tests/golden/make_golden_reference.py).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import host_library
 
 
 def ref_bilinear_sampler(input, coords, align_corners=True, padding_mode="border"):
@@ -36,10 +34,7 @@ def ref_bilinear_sampler(input, coords, align_corners=True, padding_mode="border
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    so = os.path.join(str(tmp_path_factory.mktemp("samp")), "libsampler_host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tests", "host", "sampler_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_library(tmp_path_factory, "sampler")
     lib.host_bilinear_sampler.restype = C.c_int
     lib.host_bilinear_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_int,
                                           C.c_void_p]

@@ -4,25 +4,15 @@ compiler gives it, the host switch `stream_groups` behaves like the other opt-in
 implement (per point and window row) are the reference's tensor expressions (cotracker3_online.py:411-414, 457-484, 498-510)."""
 import copy
 import ctypes as C
-import os
 import pickle
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import header_layout, lib  # noqa: F401
+
 E_NULL, E_SHAPE = -1, -2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def good_args():
@@ -44,15 +34,10 @@ def test_binding_has_the_stream_entry_points(lib):
     assert lib.ctk_abi_version() == 9  # additive
 
 
-def test_struct_size_matches_the_header(tmp_path):
+def test_struct_size_matches_the_header():
     from cotracker_amd import _lib as L
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ctk.h"\nint main(void){'
-                   'printf("%zu %zu %zu %zu\\n", sizeof(ctk_stream_args), offsetof(ctk_stream_args, stride), '
-                   'offsetof(ctk_stream_args, H), offsetof(ctk_stream_args, nonfinite));return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    size, o_stride, o_h, o_flag = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    lay = header_layout()
+    size, (o_stride, o_h, o_flag) = lay["sizeof"]["ctk_stream_args"], (lay["offsetof"]["ctk_stream_args"][f] for f in ("stride", "H", "nonfinite"))
     assert C.sizeof(L.StreamArgs) == size == 200
     assert (L.StreamArgs.stride.offset, L.StreamArgs.H.offset, L.StreamArgs.nonfinite.offset) == (o_stride, o_h, o_flag)
 

@@ -13,17 +13,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import ROOT, header_layout, lib  # noqa: F401
+
 E_NULL, E_SHAPE, E_ALIGN = -1, -2, -3
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def good_args(**kw):
@@ -43,7 +35,7 @@ def ingest(lib, a):
     return lib.ctk_ingest_frames(None if a is None else C.byref(a), None)
 
 
-def test_binding_export_and_abi(lib, tmp_path):
+def test_binding_export_and_abi(lib):
     from cotracker_amd import _lib as L
     assert "ctk_ingest_frames" in L.SYMBOLS and hasattr(lib, "ctk_ingest_frames")
     assert lib.ctk_abi_version() == L.ABI_VERSION == 9  # additive
@@ -52,14 +44,9 @@ def test_binding_export_and_abi(lib, tmp_path):
     header = open(os.path.join(ROOT, "include", "ctk.h")).read()
     assert re.search(r"int ctk_ingest_frames\(const ctk_ingest_args\* a, void\* stream\);", header)
     assert "predictor.py:288-290" in header  # the reference lines the entry point replaces
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ctk.h"\nint main(void){'
-                   'printf("%zu %zu %zu %zu %d %d %d %d\\n", sizeof(ctk_ingest_args), offsetof(ctk_ingest_args, frame_stride), '
-                   'offsetof(ctk_ingest_args, row_stride), offsetof(ctk_ingest_args, dst), CTK_INGEST_U8, CTK_INGEST_F32, CTK_INGEST_HWC, '
-                   'CTK_INGEST_CHW);return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    size, o_fs, o_rs, o_dst, u8, f32, hwc, chw = map(int, subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split())
+    lay = header_layout()
+    size, (o_fs, o_rs, o_dst) = lay["sizeof"]["ctk_ingest_args"], (lay["offsetof"]["ctk_ingest_args"][f] for f in ("frame_stride", "row_stride", "dst"))
+    u8, f32, hwc, chw = (lay["constants"][n] for n in ("CTK_INGEST_U8", "CTK_INGEST_F32", "CTK_INGEST_HWC", "CTK_INGEST_CHW"))
     assert size == C.sizeof(L.IngestArgs)
     assert (o_fs, o_rs, o_dst) == (L.IngestArgs.frame_stride.offset, L.IngestArgs.row_stride.offset, L.IngestArgs.dst.offset)
     assert (u8, f32, hwc, chw) == (L.INGEST_U8, L.INGEST_F32, L.INGEST_HWC, L.INGEST_CHW)

@@ -4,7 +4,6 @@ rule of an assign (frame >= ind + step, ind the first frame of the next call's w
 call samples and begins from their query."""
 import copy
 import ctypes as C
-import os
 import pickle
 import subprocess
 
@@ -12,17 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ctk_support import header_layout, lib  # noqa: F401
+
 E_NULL, E_SHAPE = -1, -2
-
-
-@pytest.fixture(scope="module")
-def lib():
-    import __graft_entry__ as g
-    from cotracker_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
 
 
 def good_args():
@@ -41,19 +32,14 @@ def assign(lib, a, slots=4096, newq=4096, M=5, rows=12):
     return lib.ctk_stream_assign(None if a is None else C.byref(a), slots, newq, M, rows, None)
 
 
-def test_binding_export_and_abi(lib, tmp_path):
+def test_binding_export_and_abi(lib):
     from cotracker_amd import _lib as L
     assert "ctk_stream_assign" in L.SYMBOLS and hasattr(lib, "ctk_stream_assign")
     assert lib.ctk_abi_version() == L.ABI_VERSION == 9  # additive
     nm = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert any(ln.split()[-1] == "ctk_stream_assign" and " T " in ln for ln in nm.splitlines())
-    src = tmp_path / "size.c"
-    src.write_text('#include <stdio.h>\n#include "ctk.h"\nint main(void){'
-                   'printf("%zu %.1f %ld\\n", sizeof(ctk_stream_args), (double)CTK_STREAM_EMPTY_FRAME, (long)CTK_STREAM_EMPTY_FRAME);'
-                   'return 0;}\n')
-    exe = tmp_path / "size"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    size, empty, as_long = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+    lay = header_layout()
+    size, empty, as_long = lay["sizeof"]["ctk_stream_args"], lay["constants"]["CTK_STREAM_EMPTY_FRAME"], lay["as_long"]["CTK_STREAM_EMPTY_FRAME"]
     assert int(size) == C.sizeof(L.StreamArgs) == 200  # the struct did not grow
     assert float(empty) == L.STREAM_EMPTY_FRAME == 2.0 ** 30 and int(as_long) == 2 ** 30
 
