@@ -120,6 +120,21 @@ class StreamArgs(C.Structure):
     ]
 
 
+class StreamEmit:
+    """Holder of ctk_stream_emit_args (include/ctk.h, "endless streams").  The mirror is the nested class: the module-level
+    Structure classes are the census of tests/ctk_support.py::abi_structs(), which this additive struct does not join; its layout
+    is checked against the compiler by tests/test_stream_ring_cabi.py."""
+
+    class Args(C.Structure):
+        """ctk_stream_emit_args: history frames [f0, f1) -> contiguous tracks, logits, visibility."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("f1", C.c_int32),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("tracks", _fp), ("vis_logit", _fp), ("conf_logit", _fp), ("visible", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -187,6 +202,11 @@ SYMBOLS = {
     "ctk_stream_support": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_commit": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_assign": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, C.c_int32, _fp]),
+    "ctk_stream_begin_ring": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_support_ring": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_commit_ring": (C.c_int, [_P(StreamArgs), _fp]),
+    "ctk_stream_assign_ring": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, _fp]),
+    "ctk_stream_emit": (C.c_int, [_P(StreamEmit.Args), _fp]),
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),

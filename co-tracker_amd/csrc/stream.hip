@@ -10,6 +10,12 @@
 //   commit   cotracker3_online.py:498-510   finished window -> history rows, optional non-finite flag
 // A fourth kernel, assign, runs BETWEEN two calls and does no float arithmetic at all: it hands slots of the resident query table
 // to new queries (or empties them) and clears what their previous occupants left.
+// Ring forms (ctk_stream_*_ring): the history holds R = T_cap rows and frame f lives in row f % R.  begin and commit are the same
+// kernel bodies under RING = true, with t and g on grid axes so that the row of a frame is wave-uniform arithmetic; the RING = false
+// instantiations are the linear kernels, instruction for instruction.  support touches no history and assign clears every row of
+// a slot, so their ring forms are the linear kernels behind the ring's capacity rule.
+// A fifth kernel, emit, runs AFTER a call: history frames [f0, f1) of the first N_out points of every group -> contiguous,
+// frame-ordered outputs (tracks scaled to the caller's pixels, the logits, thresholded visibility), in one launch.
 // No LDS, no atomics except the one flag OR, no device-side globals.
 #include "ctk_common.h"
 
@@ -21,17 +27,24 @@ namespace {
 __device__ __forceinline__ long qframe_of(float f) { return (long)f; }
 
 // ---- begin: one thread per (g, t, n) of the window state ------------------------------------------------------------------
+// the history row of frame f in a ring of R rows; every use below has wave-uniform operands (block indices, kernel arguments)
+__device__ __forceinline__ long ring_row(int f, long R) { return (long)((unsigned)f % (unsigned)R); }
+
+template <bool RING>
 __global__ __launch_bounds__(256) void stream_begin_kernel(int G, int N, int S, int step, int ind, long T_cap, float inv_stride,
                                                            const float* __restrict__ queries, const float* __restrict__ hc,
                                                            const float* __restrict__ hv, const float* __restrict__ hf,
                                                            float* __restrict__ coords, float* __restrict__ vis,
                                                            float* __restrict__ conf, uint8_t* __restrict__ mask) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  // RING: grid (n blocks, S, G), so t and g -- and with them the history row -- are wave-uniform; a thread past N has nothing to do
+  if (RING && (int)(blockIdx.x * blockDim.x + threadIdx.x) >= N) return;
+  const long i = RING ? ((long)blockIdx.z * S + blockIdx.y) * N + (blockIdx.x * blockDim.x + threadIdx.x)
+                      : (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)G * S * N;
   if (i >= total) return;
-  const int n = (int)(i % N);
-  const int t = (int)((i / N) % S);
-  const long g = i / ((long)N * S);
+  const int n = RING ? (int)(blockIdx.x * blockDim.x + threadIdx.x) : (int)(i % N);
+  const int t = RING ? (int)blockIdx.y : (int)((i / N) % S);
+  const long g = RING ? (long)blockIdx.z : i / ((long)N * S);
   const float* q = queries + (g * N + n) * 3;
   const long qf = qframe_of(q[0]);
   const int overlap = S - step;
@@ -39,7 +52,8 @@ __global__ __launch_bounds__(256) void stream_begin_kernel(int G, int N, int S, 
   float v = 0.0f, f = 0.0f;
   if (ind > 0 && qf < (long)ind + overlap) {
     // carry-over: rows ind .. ind+overlap-1 of the history, the last of them repeated `step` times
-    const long row = (g * T_cap + ind + min(t, overlap - 1)) * N + n;
+    const long row = RING ? (g * T_cap + ring_row(ind + min(t, overlap - 1), T_cap)) * N + n
+                          : (g * T_cap + ind + min(t, overlap - 1)) * N + n;
     const float2 h = *reinterpret_cast<const float2*>(hc + row * 2);
     c.x = __fmul_rn(h.x, inv_stride);
     c.y = __fmul_rn(h.y, inv_stride);
@@ -109,20 +123,26 @@ __global__ __launch_bounds__(256) void stream_support_kernel(StreamLevels lv, lo
 }
 
 // ---- commit: one thread per (g, t < T_valid, n) ------------------------------------------------------------------------------
+template <bool RING>
 __global__ __launch_bounds__(256) void stream_commit_kernel(int G, int N, int S, int T_valid, int ind, long T_cap, float stride,
                                                             const float* __restrict__ coords, const float* __restrict__ vis,
                                                             const float* __restrict__ conf, float* __restrict__ hc,
                                                             float* __restrict__ hv, float* __restrict__ hf,
                                                             int32_t* __restrict__ flag) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long total = (long)G * T_valid * N;
+  long i = 0, total = 1;
+  if constexpr (RING) {  // grid (n blocks, T_valid, G): a thread past N has nothing to do
+    if ((int)(blockIdx.x * blockDim.x + threadIdx.x) >= N) i = 1;
+  } else {
+    i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    total = (long)G * T_valid * N;
+  }
   bool bad = false;
   if (i < total) {
-    const int n = (int)(i % N);
-    const int t = (int)((i / N) % T_valid);
-    const long g = i / ((long)N * T_valid);
+    const int n = RING ? (int)(blockIdx.x * blockDim.x + threadIdx.x) : (int)(i % N);
+    const int t = RING ? (int)blockIdx.y : (int)((i / N) % T_valid);
+    const long g = RING ? (long)blockIdx.z : i / ((long)N * T_valid);
     const long src = (g * S + t) * N + n;
-    const long row = (g * T_cap + ind + t) * N + n;
+    const long row = RING ? (g * T_cap + ring_row(ind + t, T_cap)) * N + n : (g * T_cap + ind + t) * N + n;
     const float2 c = *reinterpret_cast<const float2*>(coords + src * 2);
     float2 o;
     o.x = __fmul_rn(c.x, stride);
@@ -167,33 +187,73 @@ __global__ __launch_bounds__(256) void stream_assign_kernel(AssignLevels lv, int
   }
 }
 
-int check_common(const ctk_stream_args* a) {
+// ---- emit: one thread per (g, frame, n < N_out); grid (n blocks, f1 - f0, G): the frame's row is wave-uniform arithmetic ---------
+// sigmoid as 1 / (1 + expf(-x)), every step a float32 operation
+__device__ __forceinline__ float emit_sigmoid(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
+
+__global__ __launch_bounds__(256) void stream_emit_kernel(int N, int N_out, long R, int f0, int F, float sx, float sy, float thresh,
+                                                          const float* __restrict__ hc, const float* __restrict__ hv,
+                                                          const float* __restrict__ hf, const int32_t* __restrict__ first_row,
+                                                          float* __restrict__ tracks, float* __restrict__ vis_logit,
+                                                          float* __restrict__ conf_logit, uint8_t* __restrict__ visible) {
+  const int n = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (n >= N_out) return;
+  const int t = (int)blockIdx.y;
+  const long g = (long)blockIdx.z;
+  const int f = f0 + t;
+  const long row = (g * R + ring_row(f, R)) * N + n;
+  const long dst = (g * F + t) * N_out + n;
+  const float2 h = *reinterpret_cast<const float2*>(hc + row * 2);
+  float2 o;
+  o.x = __fmul_rn(h.x, sx);
+  o.y = __fmul_rn(h.y, sy);
+  *reinterpret_cast<float2*>(tracks + dst * 2) = o;
+  if (vis_logit == nullptr && conf_logit == nullptr && visible == nullptr) return;
+  const float v = hv[row], c = hf[row];
+  if (vis_logit != nullptr) vis_logit[dst] = v;
+  if (conf_logit != nullptr) conf_logit[dst] = c;
+  if (visible != nullptr) {
+    bool on = __fmul_rn(emit_sigmoid(v), emit_sigmoid(c)) > thresh;  // (a NaN compares false: not visible)
+    if (first_row != nullptr) on = on && f >= first_row[g * N + n];
+    visible[dst] = on ? 1 : 0;
+  }
+}
+
+constexpr int GRID_YZ_MAX = 65535;  // grid axes y and z
+
+int check_common(const ctk_stream_args* a, bool ring) {
   if (!a) return CTK_E_NULL;
   if (a->G <= 0 || a->N <= 0 || a->S <= 0 || a->step <= 0 || a->step >= a->S || a->ind < 0 || a->ind % a->step != 0)
     return CTK_E_SHAPE;
-  if ((long)a->T_cap < (long)a->ind + a->S) return CTK_E_SHAPE;
+  if (ring ? a->T_cap < a->S : (long)a->T_cap < (long)a->ind + a->S) return CTK_E_SHAPE;
   if (!(a->stride > 0.0f) || !(a->stride <= 65536.0f)) return CTK_E_SHAPE;
   if ((long)a->G * a->N > (1L << 26) || (long)a->G * a->N * a->S > (1L << 30)) return CTK_E_SHAPE;
+  // ring forms: g and t ride on grid axes, and ind + S must not overflow the 32-bit frame arithmetic
+  if (ring && (a->G > GRID_YZ_MAX || a->S > GRID_YZ_MAX || (long)a->ind + a->S > (1L << 30))) return CTK_E_SHAPE;
   return CTK_OK;
 }
 
-}  // namespace
-
-extern "C" int ctk_stream_begin(const ctk_stream_args* a, void* stream) {
-  const int rc = check_common(a);
+int stream_begin(const ctk_stream_args* a, void* stream, bool ring) {
+  const int rc = check_common(a, ring);
   if (rc != CTK_OK) return rc;
   if (!a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf || !a->coords || !a->vis || !a->conf || !a->point_mask)
     return CTK_E_NULL;
-  const long total = (long)a->G * a->S * a->N;
-  hipLaunchKernelGGL(stream_begin_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     a->G, a->N, a->S, a->step, a->ind, (long)a->T_cap, 1.0f / a->stride, a->queries, a->hist_coords, a->hist_vis,
-                     a->hist_conf, a->coords, a->vis, a->conf, a->point_mask);
+  if (ring) {
+    hipLaunchKernelGGL(stream_begin_kernel<true>, dim3((unsigned)((a->N + 255) / 256), (unsigned)a->S, (unsigned)a->G), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->step, a->ind, (long)a->T_cap, 1.0f / a->stride,
+                       a->queries, a->hist_coords, a->hist_vis, a->hist_conf, a->coords, a->vis, a->conf, a->point_mask);
+  } else {
+    const long total = (long)a->G * a->S * a->N;
+    hipLaunchKernelGGL(stream_begin_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->step, a->ind, (long)a->T_cap, 1.0f / a->stride,
+                       a->queries, a->hist_coords, a->hist_vis, a->hist_conf, a->coords, a->vis, a->conf, a->point_mask);
+  }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }
 
-extern "C" int ctk_stream_support(const ctk_stream_args* a, void* stream) {
-  const int rc = check_common(a);
+int stream_support(const ctk_stream_args* a, void* stream, bool ring) {
+  const int rc = check_common(a, ring);
   if (rc != CTK_OK) return rc;
   if (!a->queries) return CTK_E_NULL;
   StreamLevels lv;
@@ -218,22 +278,28 @@ extern "C" int ctk_stream_support(const ctk_stream_args* a, void* stream) {
   return CTK_OK;
 }
 
-extern "C" int ctk_stream_commit(const ctk_stream_args* a, void* stream) {
-  const int rc = check_common(a);
+int stream_commit(const ctk_stream_args* a, void* stream, bool ring) {
+  const int rc = check_common(a, ring);
   if (rc != CTK_OK) return rc;
   if (a->T_valid <= 0 || a->T_valid > a->S) return CTK_E_SHAPE;
   if (!a->hist_coords || !a->hist_vis || !a->hist_conf || !a->coords || !a->vis || !a->conf) return CTK_E_NULL;
-  const long total = (long)a->G * a->T_valid * a->N;
-  hipLaunchKernelGGL(stream_commit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->T_valid, a->ind, (long)a->T_cap, a->stride, a->coords,
-                     a->vis, a->conf, a->hist_coords, a->hist_vis, a->hist_conf, a->nonfinite);
+  if (ring) {
+    hipLaunchKernelGGL(stream_commit_kernel<true>, dim3((unsigned)((a->N + 255) / 256), (unsigned)a->T_valid, (unsigned)a->G),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->T_valid, a->ind, (long)a->T_cap,
+                       a->stride, a->coords, a->vis, a->conf, a->hist_coords, a->hist_vis, a->hist_conf, a->nonfinite);
+  } else {
+    const long total = (long)a->G * a->T_valid * a->N;
+    hipLaunchKernelGGL(stream_commit_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a->G, a->N, a->S, a->T_valid, a->ind, (long)a->T_cap, a->stride, a->coords,
+                       a->vis, a->conf, a->hist_coords, a->hist_vis, a->hist_conf, a->nonfinite);
+  }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }
 
-extern "C" int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
-                                 void* stream) {
-  const int rc = check_common(a);
+int stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows, void* stream,
+                  bool ring) {
+  const int rc = check_common(a, ring);
   if (rc != CTK_OK) return rc;
   if (!slots || !new_queries || !a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf) return CTK_E_NULL;
   AssignLevels lv;
@@ -247,6 +313,44 @@ extern "C" int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots,
   hipLaunchKernelGGL(stream_assign_kernel, dim3((unsigned)M, 8), dim3(256), 0, static_cast<hipStream_t>(stream), lv, a->G, a->N,
                      (long)a->T_cap, rows, slots, new_queries, const_cast<float*>(a->queries), a->hist_coords, a->hist_vis,
                      a->hist_conf);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+}  // namespace
+
+extern "C" int ctk_stream_begin(const ctk_stream_args* a, void* stream) { return stream_begin(a, stream, false); }
+extern "C" int ctk_stream_support(const ctk_stream_args* a, void* stream) { return stream_support(a, stream, false); }
+extern "C" int ctk_stream_commit(const ctk_stream_args* a, void* stream) { return stream_commit(a, stream, false); }
+extern "C" int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
+                                 void* stream) {
+  return stream_assign(a, slots, new_queries, M, rows, stream, false);
+}
+
+// ring forms: T_cap is the ring size R, the history row of frame f is f % R, and the capacity rule is R >= S
+extern "C" int ctk_stream_begin_ring(const ctk_stream_args* a, void* stream) { return stream_begin(a, stream, true); }
+extern "C" int ctk_stream_support_ring(const ctk_stream_args* a, void* stream) { return stream_support(a, stream, true); }
+extern "C" int ctk_stream_commit_ring(const ctk_stream_args* a, void* stream) { return stream_commit(a, stream, true); }
+extern "C" int ctk_stream_assign_ring(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M,
+                                      void* stream) {
+  if (!a) return CTK_E_NULL;
+  return stream_assign(a, slots, new_queries, M, a->T_cap, stream, true);  // every row of the ring: whatever frame it holds
+}
+
+extern "C" int ctk_stream_emit(const ctk_stream_emit_args* a, void* stream) {
+  if (!a) return CTK_E_NULL;
+  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->N_out > a->N || a->R <= 0 || a->reserved != 0) return CTK_E_SHAPE;
+  if (a->f0 < 0 || a->f1 <= a->f0 || (long)a->f1 - a->f0 > a->R || a->f1 > (1 << 30)) return CTK_E_SHAPE;
+  if (a->G > GRID_YZ_MAX || a->f1 - a->f0 > GRID_YZ_MAX || (long)a->G * a->N > (1L << 26)) return CTK_E_SHAPE;
+  if (!a->hist_coords || !a->tracks) return CTK_E_NULL;
+  const bool logits = a->vis_logit || a->conf_logit || a->visible;
+  if (logits && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
+  if (a->first_row && !a->visible) return CTK_E_NULL;  // the mask has nothing to act on
+  if (a->visible && !(a->thresh == a->thresh)) return CTK_E_SHAPE;
+  const int F = a->f1 - a->f0;
+  hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((a->N_out + 255) / 256), (unsigned)F, (unsigned)a->G), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a->N, a->N_out, (long)a->R, a->f0, F, a->sx, a->sy, a->thresh, a->hist_coords,
+                     a->hist_vis, a->hist_conf, a->first_row, a->tracks, a->vis_logit, a->conf_logit, a->visible);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }

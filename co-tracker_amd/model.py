@@ -15,7 +15,9 @@ iterative update (correlation sampling, corr MLP, token assembly, EfficientUpdat
 Window scheduling and online state are Python glue, as in the reference.
 Inference only (``is_train`` must be False).
 """
+import contextlib
 import copy
+import operator
 import warnings
 from dataclasses import dataclass, replace
 from typing import List, Optional
@@ -272,6 +274,7 @@ class TrackerBase(nn.Module):
     reference kwargs, the packed-weight and graph caches, pickling, the f16 range guard, and the forward path over B videos."""
 
     PACKED_WEIGHTS = None  # the packed-weights class of the model family
+    stream_window_start = None  # (a model pickled before the attribute existed)
     BATCH_MODES = ("loop", "joint")
 
     def __init__(self):
@@ -329,6 +332,39 @@ class TrackerBase(nn.Module):
         # stream_assign() hands slots to new queries and stream_release() empties them: writes into resident buffers, so no shape,
         # no address and no captured graph changes.  More than one video with the switch on: NotImplementedError.
         self.stream_slots = False
+        # Endless streams (CoTracker3 online model only; opt-in): None (default), or K >= window_len frames of history.  Read at
+        # the FIRST call of a stream.  With it set, every streaming call -- forward(..., is_online=True) chunks and stream_push,
+        # G == 1 included, both batch_modes, with and without hip_graph -- runs on the device stream state with a RING history of
+        # K rows (ops.StreamGroups(ring_rows=K): frame f in row f % K, allocated once) and returns THIS WINDOW's rows only:
+        # (coords [G,T,N,2], sigmoid(vis), sigmoid(conf), None) for frames stream_window_start .. stream_window_start + T - 1,
+        # copied out of the ring by one launch (ctk_stream_emit; the bits the default mode returns for those rows).  Memory and
+        # the cost of a call no longer depend on the age of the stream; nothing is re-allocated or re-captured after the first
+        # window.  The first window_len - window_len // 2 rows of a call supersede what the previous call returned for those
+        # frames; older rows are final.  last_logits are the emitted logits, and the reference-visible online_coords_predicted /
+        # online_vis_predicted / online_conf_predicted are the RING buffers [G,K,N,.] (row f % K holds frame f), not [.,T_so_far,.].
+        # stream_assign / stream_release clear all K rows of a slot.  Frame numbers are float32 in the query table, so a stream
+        # ends before frame 2^24 (about 6 days at 30 fps): the call whose window would reach it raises RuntimeError before any
+        # launch.  More than one video with it set: NotImplementedError.
+        self.stream_history_frames = None
+        self.stream_window_start = None  # the frame number of row 0 of the last return under stream_history_frames
+
+    @property
+    def stream_history_frames(self) -> Optional[int]:
+        return getattr(self, "_stream_history_frames", None)  # (a model pickled before the attribute existed)
+
+    @stream_history_frames.setter
+    def stream_history_frames(self, K):
+        if K is not None:
+            try:
+                K = None if isinstance(K, bool) else operator.index(K)
+            except TypeError:
+                K = None
+            if K is None:
+                raise ValueError("stream_history_frames must be None or an int >= window_len")
+            S = getattr(self, "window_len", None)
+            if K < (S if S is not None else 1):
+                raise ValueError(f"stream_history_frames must be None or an int >= window_len ({S}), got {K}")
+        self._stream_history_frames = K
 
     @property
     def stream_slots(self) -> bool:
@@ -765,6 +801,18 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
 
     _TRANSIENT = {**CoTrackerThreeBase._TRANSIENT, "_overlap_hint": type(None)}
     _gstream = None  # ops.StreamGroups of a streaming query-group call (stream_groups), of any stream with stream_slots, of a push stream
+    _window_return = True  # stream_history_frames: False while the predictor's own call runs (it emits its result itself: quiet_return)
+
+    @contextlib.contextmanager
+    def quiet_return(self):
+        """For the predictor: inside the block a call on a ring stream steps the state and returns (None, None, None, None) -- the
+        caller emits what it hands back with stream_emit.  The switch is put back when the block is left, whatever the call raised;
+        a stream without a ring returns as ever."""
+        self._window_return = False
+        try:
+            yield
+        finally:
+            self._window_return = True
     _feed = None     # how the running stream gets its frames: "forward" (chunks) or "push" (stream_push: new frames only); None: no tracked call yet
     online_ind = _online_attr("ind")
     online_track_support = _online_attr("track_support")
@@ -799,9 +847,13 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         if is_online and self.stream_slots and video.shape[0] != 1:
             raise NotImplementedError("stream_slots streams the query sets of ONE video: a batch of videos with the switch on is not "
                                       "implemented")
+        ring = is_online and self._ring_rows() is not None
+        if ring and video.shape[0] != 1:
+            raise NotImplementedError("stream_history_frames streams the query sets of ONE video: a batch of videos with it set is not "
+                                      "implemented")
         if is_online:
             self._fed("forward")
-        if is_online and (self.stream_slots or (grouped and self.stream_groups)):
+        if is_online and (ring or self.stream_slots or (grouped and self.stream_groups)):
             return self._forward_stream_groups(video, queries, iters, fmaps_chunk_size, space_attn)
         if grouped and is_online:
             raise NotImplementedError("streaming (is_online=True) takes one query set per video: a query-group call (video [1,...], "
@@ -826,7 +878,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
     def _slot_stream(self):
         """The stream state that stream_assign / stream_release write, or RuntimeError: the switch is off, no call of a stream
         has been made yet (its queries go through forward), or a short chunk has closed the stream."""
-        if not self.stream_slots and self._feed != "push":  # (a push stream always runs on the device stream state)
+        # (a push stream and a stream with a ring history always run on the device stream state)
+        if not self.stream_slots and self._feed != "push" and self._ring_rows() is None:
             raise RuntimeError("model.stream_slots is off: this stream has no slots to assign")
         gs, st = self._gstream, getattr(self, "_online", None)
         if gs is None or not gs.live or not st or st[0].ind == 0:
@@ -871,6 +924,32 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         gs = self._slot_stream()[0]
         return gs.queries.reshape(gs.G, gs.N, 3).clone()
 
+    # -- endless streams (stream_history_frames): ring history, this window's rows per call ----------------------------------------
+    FRAME_LIMIT = 2 ** 24  # frame numbers are float32 in the query table: every integer below is exact
+
+    def _ring_rows(self):
+        """The ring size of the stream the next call belongs to: stream_history_frames as it stands when that call is the first of
+        a stream; after that the running stream's own -- None for one that runs without a ring, on the device state or on the torch
+        glue: the attribute is read at the first call, and a change in mid-stream waits for the next stream."""
+        st, gs = getattr(self, "_online", None), self._gstream
+        if st and st[0].ind > 0:
+            return gs.ring_rows if gs is not None and gs.live else None
+        return self.stream_history_frames
+
+    def _check_frame_limit(self, ind):
+        """Before any launch of a call on a ring: its window [ind, ind + window_len) must stay below FRAME_LIMIT."""
+        if ind + self.window_len > self.FRAME_LIMIT:
+            raise RuntimeError(f"the stream has reached frame {ind}: the next window would pass frame 2^24, beyond which float32 query "
+                               "frames are not exact; start a new stream (init_video_online_processing)")
+
+    def stream_emit(self, f0, f1, N_out=None, scale=(1.0, 1.0), logits=True, thresh=None, first_row=None):
+        """Frames [f0, f1) of the running (or just closed) stream's history, in frame order, by one launch: ops.StreamGroups.emit.
+        Serves a ring history and the default one alike."""
+        gs = self._gstream
+        if gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state")
+        return gs.emit(f0, f1, N_out, scale, logits, thresh, first_row)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is
@@ -880,6 +959,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         step = S // 2
         st = self._online_states(1, T)[0]
         hint, self._overlap_hint = getattr(self, "_overlap_hint", None), None
+        if self._ring_rows() is not None:
+            self._check_frame_limit(st.ind)
         self._resolve_deferred_range_check()
         gs = self._stream_state(queries, st, video.shape[3], video.shape[4])
         gs.closed = T < S
@@ -894,10 +975,11 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         step = S // 2
         sizes = [((H // self.stride) >> l, (W // self.stride) >> l) for l in range(self.corr_levels)]
         gs = self._gstream
-        if gs is None or not gs.fits(queries, S, step, self.stride, sizes):
+        ring = self._ring_rows()  # (read at the first call of a stream; the running stream's own afterwards)
+        if gs is None or not gs.fits(queries, S, step, self.stride, sizes, ring):
             assert st.ind == 0, "the query groups of a stream are fixed by its first call"
             self._drop_graphs()  # (they hold pointers into the old stream's buffers)
-            gs = self._gstream = ops.StreamGroups(queries, S, step, self.stride, sizes)
+            gs = self._gstream = ops.StreamGroups(queries, S, step, self.stride, sizes, ring_rows=ring)
         elif not gs.live:
             assert st.ind == 0, "the query groups of a stream are fixed by its first call"
             gs.restart(queries)
@@ -908,7 +990,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         """What every call on the device stream state does once the resident pyramid holds this window's S frames (T of them real):
         three launches step the state of all G*N points -- support (the points whose query frame entered this window), begin
         (carry-over and masks), then the groups' windows, then commit (history rows, non-finite flag).  Returns views of the first
-        ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place."""
+        ind + T history rows, [G,T_so_far,N,.]: the next call refines the overlapping rows in place.  On a ring
+        (stream_history_frames): this window's T rows, copied out by one emit launch."""
         S = self.window_len
         step = S // 2
         ind = st.ind
@@ -917,7 +1000,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         joint, groups = self._index_groups(gs.G, units=True)
         kw = dict(iters=int(iters), max_corr_rows=int(self.max_corr_rows), space_attn=bool(space_attn))
         # what a window step overwrites and a re-run must find again: the history rows the carry-over reads (commit rewrites them)
-        rows = slice(ind, ind + S - step)
+        rows = gs.frame_rows(ind, ind + S - step)  # (one slice; two where a ring wraps)
 
         def run(precision, check):
             """begin, the groups' windows -- one group after the other ("loop") or shared-pyramid joint windows of at most
@@ -938,11 +1021,22 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
 
         def restore(saved):
             for h_, s_ in zip(gs.hist, saved or ()):
-                h_[:, rows].copy_(s_)
+                for r_, p_ in zip(rows, s_):
+                    h_[:, r_].copy_(p_)
             gs.nonfinite.zero_()
-        self._guarded(run, lambda: ind > 0 and [h_[:, rows].clone() for h_ in gs.hist], restore,
+        self._guarded(run, lambda: ind > 0 and [[h_[:, r_].clone() for r_ in rows] for h_ in gs.hist], restore,
                       graphed and self.stream_range_check == "deferred", gs.nonfinite, "streaming call of all query groups")
         st.ind = ind + step
+        if gs.ring_rows is not None:
+            # reference-visible online_* attributes: the RING buffers [G,K,N,.] (frame f in row f % K)
+            st.track_support, (st.coords_predicted, st.vis_predicted, st.conf_predicted) = gs.support, gs.hist
+            self.stream_window_start = ind
+            if not self._window_return:  # the predictor emits what it hands back itself (stream_emit): one launch instead of this one and its own
+                self.last_logits = None
+                return (None, None, None, None)
+            coords, vis, conf = gs.emit(ind, ind + T)
+            self.last_logits = (vis, conf)
+            return (coords, torch.sigmoid(vis), torch.sigmoid(conf), None)
         out = gs.history(ind + T)
         # reference-visible online_* attributes (API parity): the state of ALL groups, views of the resident buffers
         st.track_support, (st.coords_predicted, st.vis_predicted, st.conf_predicted) = gs.support, out
@@ -980,6 +1074,8 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise ValueError(f"stream_push: this call takes {full} new frames ({'the first window' if first else 'one step'}), or "
                              f"1..{full - 1} with final=True; got {n}" + ("" if final or n >= full else " without final=True"))
         T = n if first else S - step + n
+        if self._ring_rows() is not None:
+            self._check_frame_limit(st.ind)
         self._fed("push")
         self._resolve_deferred_range_check()
         gs = self._stream_state(queries, st, H, W)

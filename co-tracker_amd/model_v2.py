@@ -167,6 +167,11 @@ class CoTracker2(TrackerBase):
         if on:
             raise NotImplementedError("CoTracker2 (model_v2.py) takes the queries of a stream at its first call; stream_slots on a v2 model is not implemented")
 
+    @TrackerBase.stream_history_frames.setter
+    def stream_history_frames(self, K):  # the ring history lives in the device stream state, which is the CoTracker3 online model's
+        if K is not None:
+            raise NotImplementedError("CoTracker2 (model_v2.py) returns the tracks of the whole stream; stream_history_frames on a v2 model is not implemented")
+
     def stream_push(self, *args, **kwargs):  # the resident pyramid it advances belongs to the CoTracker3 online model's stream state
         raise NotImplementedError("CoTracker2 (model_v2.py) is fed overlapping chunks through forward(); stream_push on a v2 model is not implemented")
 

@@ -646,11 +646,20 @@ class StreamGroups:
     release() hand slots to new queries or empty them between two calls -- writes into the resident buffers: no address, no
     shape and therefore no captured graph changes.  The bookkeeping lives on the host: ``occupied`` [G,N] (bool) and
     ``first_row`` [G,N] (the history row from which the rows belong to the present occupant); ``committed`` counts the history
-    rows written so far and ``next_ind`` is the first frame of the next call's window (both follow commit())."""
+    rows written so far and ``next_ind`` is the first frame of the next call's window (both follow commit()).
+
+    Ring (``ring_rows`` = R >= S, for streams without an end): the history holds R rows, frame f in row f % R, allocated once --
+    reserve() never grows it, the ring forms of the four entry points step it (ctk_stream_*_ring), and an assign clears all R rows
+    of a slot.  A wrapped range of frames is not a view: history() raises, emit() copies any [f0, f1) of the last R frames out in
+    frame order with one launch (it serves the linear layout too), and frame_rows() names the rows of a range as slices."""
 
     _serial = 0
+    ring_rows = None  # (a state pickled before the attribute existed)
 
-    def __init__(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes):
+    def __init__(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes, ring_rows: Optional[int] = None):
+        if ring_rows is not None and (int(ring_rows) != ring_rows or ring_rows < S):
+            raise ValueError(f"ring_rows must be an integer >= the window length {S}, got {ring_rows!r}")
+        self.ring_rows = None if ring_rows is None else int(ring_rows)
         G, N = queries.shape[:2]
         dev = queries.device
         self.G, self.N, self.S, self.step, self.stride = G, N, S, step, float(stride)
@@ -665,7 +674,7 @@ class StreamGroups:
         self.nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
         self.T_cap = 0
         self.hist = None
-        self.reserve(4 * S)
+        self.reserve(4 * S if self.ring_rows is None else self.ring_rows)
         self.closed = False  # a chunk shorter than the window ends the stream
         self.live = True     # False: the stream it carried is over, the buffers wait for restart()
         StreamGroups._serial += 1
@@ -686,8 +695,8 @@ class StreamGroups:
             self._occupied = (self.queries[:, 0].cpu() != EMPTY_FRAME).reshape(self.G, self.N)
         return self._occupied
 
-    def fits(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes) -> bool:
-        return (tuple(queries.shape[:2]) == (self.G, self.N) and queries.device == self.queries.device and
+    def fits(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes, ring_rows: Optional[int] = None) -> bool:
+        return (tuple(queries.shape[:2]) == (self.G, self.N) and queries.device == self.queries.device and ring_rows == self.ring_rows and
                 (S, step, float(stride), tuple(level_sizes)) == (self.S, self.step, self.stride, self.level_sizes))
 
     def restart(self, queries: torch.Tensor) -> None:
@@ -703,8 +712,8 @@ class StreamGroups:
 
     def reserve(self, T: int) -> None:
         """History capacity of at least T frames: doubled when it runs out (one copy per doubling, not per call); rows past the
-        committed ones are zero."""
-        if T <= self.T_cap:
+        committed ones are zero.  A ring is allocated once, by the constructor, and never grows."""
+        if T <= self.T_cap or (self.ring_rows is not None and self.hist is not None):
             return
         cap = max(T, 2 * self.T_cap)
         dev = self.queries.device
@@ -717,7 +726,52 @@ class StreamGroups:
 
     def history(self, T: int):
         """Views of the first T history rows: (coords [G,T,N,2] pixels, vis logits [G,T,N], conf logits [G,T,N])."""
+        if self.ring_rows is not None:
+            raise RuntimeError("a ring history has no view of a range of frames (it may wrap): use emit()")
         return tuple(h_[:, :T] for h_ in self.hist)
+
+    def frame_rows(self, f0: int, f1: int) -> List[slice]:
+        """The history rows of frames [f0, f1) as slices in frame order: one, or two where a ring wraps (f1 - f0 <= T_cap)."""
+        if self.ring_rows is None:
+            return [slice(f0, f1)]
+        R = self.ring_rows
+        assert 0 <= f1 - f0 <= R
+        r0, r1 = f0 % R, f0 % R + (f1 - f0)
+        return [slice(r0, r1)] if r1 <= R else [slice(r0, R), slice(0, r1 - R)]
+
+    def emit(self, f0: int, f1: int, N_out: Optional[int] = None, scale=(1.0, 1.0), logits: bool = True, thresh: Optional[float] = None,
+             first_row: Optional[torch.Tensor] = None):
+        """History frames [f0, f1) of the first N_out points of every group, copied out in frame order by ONE launch
+        (ctk_stream_emit): tracks [G,f1-f0,N_out,2] = history coords * scale (one float32 multiplication; (1, 1): a copy), then the
+        two logit tensors [G,f1-f0,N_out] if `logits`, then -- `thresh` given -- visibility (bool) = sigmoid(vis) * sigmoid(conf) >
+        thresh, ANDed with frame >= first_row[g, n] (int32 [G,N] on the device, INT32_MAX: an empty slot) when that is given.  The
+        frames must be among the last T_cap committed ones (a ring keeps no more).  Returns the tuple of what was asked for."""
+        N_out = self.N if N_out is None else int(N_out)
+        if not (0 <= f0 < f1 <= self.committed and f1 - f0 <= self.T_cap and f0 >= (0 if self.ring_rows is None else self.committed - self.T_cap)):
+            raise ValueError(f"emit: frames [{f0}, {f1}) are not among the {min(self.committed, self.T_cap)} frames the history holds "
+                             f"(it ends at frame {self.committed})")
+        if not 1 <= N_out <= self.N:
+            raise ValueError(f"emit: N_out must lie in [1, {self.N}]")
+        dev, F_ = self.queries.device, f1 - f0
+        a = L.StreamEmit.Args()
+        a.G, a.N, a.N_out, a.R, a.f0, a.f1 = self.G, self.N, N_out, self.T_cap, f0, f1
+        a.sx, a.sy, a.thresh, a.reserved = float(scale[0]), float(scale[1]), 0.0 if thresh is None else float(thresh), 0
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_) for h_ in self.hist)
+        out = [torch.empty(self.G, F_, N_out, 2, device=dev)]
+        a.tracks = _ptr(out[0])
+        if logits:
+            out += [torch.empty(self.G, F_, N_out, device=dev), torch.empty(self.G, F_, N_out, device=dev)]
+            a.vis_logit, a.conf_logit = _ptr(out[1]), _ptr(out[2])
+        if thresh is not None:
+            out.append(torch.empty(self.G, F_, N_out, device=dev, dtype=torch.bool))  # (one byte per element, written as 0 / 1)
+            a.visible = _ptr(out[-1])
+            if first_row is not None:
+                if first_row.dtype != torch.int32 or tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or \
+                        not first_row.is_contiguous():
+                    raise ValueError(f"emit: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+                a.first_row = _ptr(first_row)
+        L.check(L.load().ctk_stream_emit(C.byref(a), _stream()), "ctk_stream_emit")
+        return tuple(out)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()
@@ -762,19 +816,23 @@ class StreamGroups:
 
     def begin(self, ind: int) -> None:
         self.reserve(ind + self.S)
-        L.check(L.load().ctk_stream_begin(C.byref(self._args(ind)), _stream()), "ctk_stream_begin")
+        name = "ctk_stream_begin" if self.ring_rows is None else "ctk_stream_begin_ring"
+        L.check(getattr(L.load(), name)(C.byref(self._args(ind)), _stream()), name)
 
     def sample_support(self, ind: int) -> None:
         self.reserve(ind + self.S)
-        L.check(L.load().ctk_stream_support(C.byref(self._args(ind)), _stream()), "ctk_stream_support")
+        name = "ctk_stream_support" if self.ring_rows is None else "ctk_stream_support_ring"
+        L.check(getattr(L.load(), name)(C.byref(self._args(ind)), _stream()), name)
 
     def commit(self, ind: int, T_valid: int, flag: bool) -> None:
-        L.check(L.load().ctk_stream_commit(C.byref(self._args(ind, T_valid, flag)), _stream()), "ctk_stream_commit")
+        name = "ctk_stream_commit" if self.ring_rows is None else "ctk_stream_commit_ring"
+        L.check(getattr(L.load(), name)(C.byref(self._args(ind, T_valid, flag)), _stream()), name)
         self.committed, self.next_ind = ind + T_valid, ind + self.step
 
     def assign(self, slots, queries: torch.Tensor, rows: Optional[int] = None, min_frame: Optional[int] = None) -> None:
         """Between two calls: slot slots[m] (flat index g*N + n) gets the query queries[m] = (frame, x, y) in model-resolution
-        pixels, its support accumulators and its history rows [0, rows) are cleared (rows: default every row committed so far), and
+        pixels, its support accumulators and its history rows [0, rows) are cleared (rows: default every row committed so far; a ring:
+        all its rows, always), and
         the bookkeeping follows (first_row = next_ind).  One launch (ctk_stream_assign); the slot list reaches the device with one
         non-blocking copy, and so do queries given on the host.  The frame column is checked HERE, on the host -- for queries on
         the device that is one small device-to-host copy; the positions never leave the device --: a frame that is not finite, or
@@ -792,7 +850,8 @@ class StreamGroups:
             raise ValueError("assign: a slot is listed twice")
         if not isinstance(queries, torch.Tensor) or tuple(queries.shape) != (M, 3) or not queries.dtype.is_floating_point:
             raise ValueError(f"assign: queries must be a float tensor [{M},3] = (frame, x, y), one row per listed slot")
-        rows = self.committed if rows is None else int(rows)
+        ring = getattr(self, "ring_rows", None) is not None
+        rows = (self.T_cap if ring else self.committed) if rows is None else int(rows)
         if not 0 <= rows <= self.T_cap:
             raise ValueError(f"assign: rows must lie in [0, {self.T_cap}]")
         dev = self.queries.device
@@ -808,7 +867,10 @@ class StreamGroups:
             q = queries.detach().float().contiguous().pin_memory().to(dev, non_blocking=True)
         s32 = idx.to(torch.int32).pin_memory().to(dev, non_blocking=True)
         _ = self.occupied  # (the bookkeeping is read from the table BEFORE this assign changes it)
-        L.check(L.load().ctk_stream_assign(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, rows, _stream()), "ctk_stream_assign")
+        if not ring:
+            L.check(L.load().ctk_stream_assign(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, rows, _stream()), "ctk_stream_assign")
+        else:  # every row of the ring, whatever `rows` says: after a wrap a slot's rows hold frames of any age
+            L.check(L.load().ctk_stream_assign_ring(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, _stream()), "ctk_stream_assign_ring")
         self._occupied.view(-1)[idx] = frames != EMPTY_FRAME
         self.first_row.view(-1)[idx] = self.next_ind
 

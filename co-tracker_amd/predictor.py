@@ -9,6 +9,8 @@ query-frame prediction is overwritten with the query itself, dense mode derives 
 the raw video width.  All tensor work stays on the GPU (the reference's per-batch Python fix-up
 loop, predictor.py:177-185, is a single indexed write here).
 """
+import contextlib
+
 import torch
 import torch.nn.functional as F
 
@@ -201,7 +203,16 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         # [user queries N | K empty | support grid], and later steps return the N + K user-visible points.  An empty slot is
         # tracked as a blank point and takes part in the space attention: like the support grid, K is part of the result.
         self.spare_points = 0
+        # Not a reference kwarg (set it after construction, before the first step): None (default: every step returns everything
+        # since frame 0, as the reference), or K >= window_len for a stream without an end (model.stream_history_frames).  With it
+        # set, forward and push_frames return THIS WINDOW's rows -- tracks [.,T,N,2] in raw-video pixels and visibility [.,T,N]
+        # (bool: visibility * confidence > 0.6, nothing visible below a slot's first row) for frames window_start ..
+        # window_start + T - 1, the N (+ spare_points) user points only -- written by ONE launch (ctk_stream_emit) out of a ring
+        # of K history rows: memory and the cost of a step no longer grow with the stream.  The first window_len - step rows
+        # supersede what the previous step returned for those frames; older rows are final.  recent(n) returns the last n <= K frames.
+        self.history_frames = None
         self._first_row = self._hw = None
+        self._first_row32 = None  # (the tensor it was made from, [G,N_model] int32 for ctk_stream_emit)
         self._push_buf = None  # push_frames: the resident [window_len,3,ih,iw] float32 frames the next window still needs
         self._push_reset()
 
@@ -234,6 +245,48 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             raise ValueError(f"remove_queries: point index outside [0, {self.N})")
         self.model.stream_release(points + group * self.queries.shape[1])
         self._mark_rows()
+
+    @property
+    def window_start(self):
+        """history_frames: the frame number of row 0 of the last result (None before the first tracked step)."""
+        gs = getattr(self.model, "_gstream", None)
+        return self.model.stream_window_start if gs is not None and gs.live and gs.ring_rows is not None else None
+
+    def _quiet(self):
+        """model.quiet_return() for the model call of a step: on a ring stream the model steps the state and this predictor emits
+        the result itself.  (A model without the method has no ring: nothing to ask.)"""
+        return getattr(self.model, "quiet_return", contextlib.nullcontext)()
+
+    def _emit_first_row(self):
+        """_first_row ([G,N] long, the user-visible points) as ctk_stream_emit wants it: int32 over all N_model points of the query
+        table, INT32_MAX for an empty slot.  Rebuilt only when add / remove changed it."""
+        if self._first_row is None:
+            return None
+        if self._first_row32 is None or self._first_row32[0] is not self._first_row:
+            big = torch.iinfo(torch.int32).max
+            fr = torch.zeros(self.queries.shape[:2], dtype=torch.int32, device=self._first_row.device)
+            fr[:, :self.N] = self._first_row.clamp(max=big).to(torch.int32)
+            self._first_row32 = (self._first_row, fr)
+        return self._first_row32[1]
+
+    def _emit_result(self, f0, f1):
+        """Frames [f0, f1) as a step hands them back, by one launch: the N user-visible points, tracks in raw-video pixels (the
+        float32 multiplication of _user_result), visibility * confidence thresholded at 0.6 and masked by the slots' first rows."""
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        return self.model.stream_emit(f0, f1, N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), logits=False, thresh=0.6,
+                                      first_row=self._emit_first_row())
+
+    def recent(self, n: int):
+        """history_frames: (tracks [.,n,N,2], visibility [.,n,N]) of the last n frames tracked so far, in frame order, n <=
+        min(frames so far, history_frames); one launch."""
+        gs = getattr(self.model, "_gstream", None)
+        if gs is None or not gs.live or gs.ring_rows is None:  # (the running stream's own ring: history_frames as the first step read it)
+            raise RuntimeError("recent(n) reads the ring history of a running stream: set history_frames before the first step")
+        done, n = gs.committed, int(n)
+        if not 1 <= n <= min(done, gs.ring_rows):
+            raise ValueError(f"recent: n must lie in [1, {min(done, gs.ring_rows)}] (frames so far: {done}, history_frames: "
+                             f"{gs.ring_rows})")
+        return self._emit_result(done - n, done)
 
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
@@ -277,6 +330,12 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             self._prev_chunk = None
             self._push_reset()
             self._first_row, self._hw = None, (H, W)
+            if self.v2:
+                if self.history_frames is not None:
+                    raise NotImplementedError("CoTracker2 returns the tracks of the whole stream: history_frames on a v2 predictor is "
+                                              "not implemented")
+            else:
+                self.model.stream_history_frames = self.history_frames
             if queries is not None:
                 assert queries.shape[2] == 3
                 self.N = queries.shape[1]
@@ -317,7 +376,10 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             tracks, vis, _ = self.model(video=v, queries=self.queries, iters=6, is_online=True)
             conf = None
         else:
-            tracks, vis, conf, _ = self.model(video=v, queries=self.queries, iters=6, is_online=True)
+            with self._quiet():
+                tracks, vis, conf, _ = self.model(video=v, queries=self.queries, iters=6, is_online=True)
+            if tracks is None:  # the stream runs on a ring (the model decides: history_frames as it stood at the first step)
+                return self._emit_result(self.model.stream_window_start, self.model._gstream.committed)
         return self._user_result(tracks, vis, conf, add_support_grid)
 
     def _user_result(self, tracks, vis, conf, add_support_grid):
@@ -404,9 +466,14 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             if self._push_fill > 0:
                 out = self._push_step(buf[:self._push_fill], True)
             self._push_closed = True
-        return (None, None) if out is None else self._user_result(*out, add_support_grid)
+        if out is None:
+            return (None, None)
+        if out[0] is None:  # history_frames: the last window's rows, out of the ring
+            return self._emit_result(self.model.stream_window_start, self.model._gstream.committed)
+        return self._user_result(*out, add_support_grid)
 
     def _push_step(self, new_frames, final):
-        tracks, vis, conf, _ = self.model.stream_push(new_frames, self.queries, iters=6, final=final)
+        with self._quiet():  # (a ring stream: the result is emitted by push_frames, one launch for the user points)
+            tracks, vis, conf, _ = self.model.stream_push(new_frames, self.queries, iters=6, final=final)
         self._push_fill, self._push_tracked = 0, True
         return tracks, vis, conf

@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_begin_ring / _support_ring / _commit_ring / _assign_ring
+ *       (the same struct with T_cap read as a ring of R history rows, frame f in row f % R) and + ctk_stream_emit on the new struct
+ *       ctk_stream_emit_args: history frames [f0, f1) -> contiguous tracks, logits and thresholded visibility in one launch.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_ingest_frames on the new struct ctk_ingest_args: raw frames
  *       (uint8 / float32, channels-last / planar, strided) resized to the encoder's input in one launch.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_assign: slots of the resident query table of a running
@@ -306,6 +309,50 @@ int ctk_stream_commit(const ctk_stream_args* a, void* stream);
 #define CTK_STREAM_EMPTY_FRAME 1073741824.0f /* 2^30 */
 int ctk_stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
                       void* stream);
+
+/* ---- endless streams: ring history and one emit launch ------------------------------------------------------------------------
+ * Ring forms of the four stream entry points.  They take the same struct with T_cap read as the ring size R: the history
+ * buffers hold R rows and frame f lives in row f % R, so a stream of any length keeps its memory.  `ind` stays the absolute frame
+ * number: the query-frame comparisons and the support tap qframe - ind are those of the linear forms, and for R >= ind + S a ring
+ * form addresses the very rows the linear form addresses.  The capacity rule is R >= S (instead of T_cap >= ind + S); everything
+ * else is validated as in the linear forms, plus G <= 65535, S <= 65535 and ind + S <= 2^30 (CTK_E_SHAPE), before any launch.
+ *   begin_ring    carry-over from rows (ind + min(t, overlap - 1)) % R
+ *   support_ring  touches no history: ctk_stream_support behind the ring's capacity rule
+ *   commit_ring   window rows 0 .. T_valid-1 -> history rows (ind + t) % R
+ *   assign_ring   as ctk_stream_assign with ALL R rows of each listed slot cleared (bounded, so there is no `rows` argument): after
+ *                 the ring has wrapped, a slot's rows hold frames of any age
+ * Frame numbers are float32 in the query table: a caller keeps ind + S <= 2^24 (the host model raises there).               */
+int ctk_stream_begin_ring(const ctk_stream_args* a, void* stream);
+int ctk_stream_support_ring(const ctk_stream_args* a, void* stream);
+int ctk_stream_commit_ring(const ctk_stream_args* a, void* stream);
+int ctk_stream_assign_ring(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, void* stream);
+
+/* emit: history frames [f0, f1), f1 - f0 <= R, of the first N_out <= N points of every group -> contiguous, frame-ordered outputs.
+ * The history row of frame f is f % R: a linear history (R = T_cap >= f1) and a ring are read by the same formula.
+ *   tracks     [G, f1-f0, N_out, 2] = hist_coords * (sx, sy), one float32 multiplication per component (sx = sy = 1: a copy)
+ *   vis_logit  [G, f1-f0, N_out] and conf_logit: hist_vis / hist_conf bit for bit; either may be NULL
+ *   visible    [G, f1-f0, N_out] uint8, optional: sigmoid(vis) * sigmoid(conf) > thresh, sigmoid(x) = 1 / (1 + expf(-x)) in float32 (a
+ *              NaN logit: not visible), ANDed with f >= first_row[g, n] when first_row (int32 [G,N], device; INT32_MAX: an empty
+ *              slot) is given
+ * One launch on `stream`, no host synchronisation, capture-safe.  Before the launch: NULL a, hist_coords or tracks, hist_vis /
+ * hist_conf when any of vis_logit / conf_logit / visible is asked for, first_row without visible: CTK_E_NULL; G, N, N_out, R <= 0,
+ * N_out > N, f0 < 0, f1 <= f0, f1 - f0 > R, f1 > 2^30, G or f1 - f0 > 65535, G * N > 2^26, a NaN thresh with visible, reserved != 0:
+ * CTK_E_SHAPE.                                                                                                                 */
+typedef struct ctk_stream_emit_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are written (the first N_out)               */
+  int32_t R;                  /* history rows per group (ring size, or the capacity of a linear one) */
+  int32_t f0, f1;             /* frames [f0, f1)                                                   */
+  float sx, sy;               /* tracks = history coords * (sx, sy)                                */
+  float thresh;               /* visible: sigmoid(vis) * sigmoid(conf) > thresh                    */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords; const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  float* tracks;
+  float* vis_logit; float* conf_logit;   /* optional */
+  uint8_t* visible;           /* optional */
+} ctk_stream_emit_args;
+int ctk_stream_emit(const ctk_stream_emit_args* a, void* stream);
 
 /* ---- frame ingest: decoder output -> encoder input in one launch -------------------------------------------------------------
  * Replaces, for a stream that is fed frame by frame, the per-chunk
