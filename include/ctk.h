@@ -573,7 +573,8 @@ int ctk_enc_l2norm(const float* x, int64_t P, float* out, void* stream);
 /* ---- primitives (exported for unit tests and reuse) ------------------------------ */
 /* C[M,N] = act(A[M,K] @ W[N,K]^T + bias[N] + bias_rows[(m % period),N]) + resid[M,N]
  * N % 64 == 0, K % 32 == 0, lda/ldw % 4 == 0, A and W 16-byte aligned.  batch > 1 repeats with
- * element strides a_bs / c_bs (shared W).  Two back ends for the same nn.Linear contract:
+ * element strides a_bs / c_bs (shared W).  resid advances by c_bs per batch as well (rows by ldr): batch b adds
+ * resid + b * c_bs.  Two back ends for the same nn.Linear contract:
  *   Wp == NULL : exact-f32 MFMA (v_mfma_f32_32x32x2_f32), W = torch layout [N,K] f32
  *   Wp != NULL : split-half MFMA (3 x v_mfma_f32_32x32x16_f16 per product, f32 accumulate, ~2^-21
  *                relative per product); Wp = blob written by ctk_pack_weight, W is ignored.      */

@@ -61,6 +61,41 @@ def lib():
     return _lib.load()
 
 
+# ---- ctk_gemm as the C-ABI sees it (tests/test_gpu_gemm_matrix.py, test_gpu_parity.py, test_cabi_and_host.py) --------------------------
+def gemm_raw(A, lda, M, N, K, out, ldc, W=None, ldw=0, Wp=None, bias=None, bias_rows=None, period=0, resid=None, ldr=0, act=0,
+             batch=1, a_bs=0, c_bs=0, a_split=False, c_split=False):
+    """Fills ctk_gemm_args field by field (ops.gemm fixes lda = K, batch = 1 and the base pointers) and calls ctk_gemm on the
+    current stream -> its return code.  Pointers: tensors (a view passes the address of its first element), integers or None."""
+    from cotracker_amd import _lib as L
+
+    def p(x):
+        return x.data_ptr() if torch.is_tensor(x) else x
+
+    g = L.GemmArgs()
+    g.A, g.lda, g.M = p(A), lda, M
+    g.W, g.ldw, g.N, g.K = p(W), ldw, N, K
+    g.Wp = p(Wp)
+    g.C, g.ldc = p(out), ldc
+    g.bias, g.bias_rows, g.bias_period = p(bias), p(bias_rows), period
+    g.resid, g.ldr = p(resid), ldr
+    g.act, g.batch, g.a_bs, g.c_bs, g.k_valid = act, batch, a_bs, c_bs, 0
+    g.a_split, g.c_split = int(a_split), int(c_split)
+    stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+    return L.load().ctk_gemm(C.byref(g), stream)
+
+
+def recorded(call):
+    """-> (call(), {recorder row name: launches}) of the library launches `call` made.  The recorder is one per process."""
+    from cotracker_amd import ops
+    ops.profile_enable(True)
+    try:
+        out = call()
+        rows = {r["name"]: r["launches"] for r in ops.profile_read()}
+    finally:
+        ops.profile_enable(False)
+    return out, rows
+
+
 # ---- the two Linear back ends ---------------------------------------------------------------------------------------------------
 PRECISIONS = ["f16x3", "f32"]
 

@@ -85,6 +85,38 @@ def test_argument_validation_without_gpu(lib):
     assert lib.ctk_window_graph_destroy(None) == 0
 
 
+def test_gemm_argument_rules_without_gpu(lib):
+    """The ctk_gemm rules of include/ctk.h that had no check: each returns its documented code before anything is launched (the
+    recorder, switched on around the calls, stays empty: a launch would have opened a row)."""
+    from cotracker_amd import _lib as L
+    from ctk_support import gemm_raw
+    E_SHAPE, E_ALIGN = -2, -3
+    ok = dict(A=1024, lda=64, M=8, N=64, K=32, out=4096, ldc=64, W=2048, ldw=32, Wp=8192)
+    rules = {
+        "SH input without Wp": (dict(Wp=None, a_split=True), E_SHAPE),
+        "SH output without Wp": (dict(Wp=None, c_split=True), E_SHAPE),
+        "c_split with a residual": (dict(c_split=True, resid=16384, ldr=64), E_SHAPE),
+        "c_split with ldc % 64": (dict(c_split=True, ldc=68), E_SHAPE),
+        "a_split with lda % 64": (dict(a_split=True, lda=36), E_ALIGN),
+        "batch > 1 with a_bs % 4": (dict(batch=2, a_bs=514, c_bs=512), E_ALIGN),
+        "batch > 1 with c_bs % 4": (dict(batch=2, a_bs=512, c_bs=514), E_ALIGN),
+        "bias rows with period 0": (dict(bias_rows=16384, period=0), E_SHAPE),
+        "bias rows with period < 0": (dict(bias_rows=16384, period=-4), E_SHAPE),
+        "ldr % 4": (dict(resid=16384, ldr=66), E_ALIGN),
+        "misaligned residual": (dict(resid=16388, ldr=64), E_ALIGN),
+        "misaligned bias": (dict(bias=16388), E_ALIGN),
+        "misaligned bias rows": (dict(bias_rows=16392, period=4), E_ALIGN),
+    }
+    assert lib.ctk_profile_enable(1) == 0
+    try:
+        for what, (change, code) in rules.items():
+            assert gemm_raw(**dict(ok, **change)) == code, what
+        rows, n = (L.ProfileRow * 4)(), C.c_int(-1)
+        assert lib.ctk_profile_read(rows, 4, C.byref(n)) == 0 and n.value == 0
+    finally:
+        lib.ctk_profile_enable(0)
+
+
 def test_v2_driver_argument_validation_without_gpu(lib):
     """ctk_forward_window_v2 / ctk_v2_window_graph_create reject bad arguments before touching the device."""
     from cotracker_amd import _lib as L

@@ -11,7 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from ctk_support import dev, logit, maxdiff, t  # noqa: E402
+from ctk_support import dev, gemm_raw, logit, maxdiff, t  # noqa: E402
 # every test runs on both Linear back ends: split-half MFMA (the default) and exact-f32 MFMA
 from ctk_support import precision_default_autouse as precision  # noqa: E402,F401
 from oracle import cotracker_oracle as O  # noqa: E402  (checker only)
@@ -145,6 +145,18 @@ def test_gemm_sh_k_range_and_batch():
     for lvl in range(4):
         out = ops.gemm(ops.split_rows(h[lvl].contiguous()), w, packed=wp, out_split=True)
         assert maxdiff(ops.unsplit(out), h[lvl].double() @ w.double().t()) < 2e-5
+    # one call on a column window of a wider SH matrix: level 2 of [M][4 * 384] (lda = 2 * 1536 halves, 12 lines in)
+    wide = ops.split_rows(h.permute(1, 0, 2).reshape(M, 4 * 384).contiguous())
+    out = torch.empty(M, 8, 2, 32, dtype=torch.float16, device=dev())
+    assert gemm_raw(wide[:, 24:], 2 * 1536, M, 256, 384, out, 512, Wp=wp, a_split=True, c_split=True) == 0
+    assert maxdiff(ops.unsplit(out), h[2].double() @ w.double().t()) < 2e-5
+    # one batched call, a batch per level, into the column blocks of an SH [M][1120] matrix (corr_mlp.fc2 -> x)
+    x = torch.zeros(M, 35, 2, 32, dtype=torch.float16, device=dev())
+    h_sh = ops.split_rows(h.reshape(4 * M, 384))
+    assert gemm_raw(h_sh, 768, M, 256, 384, x, 2240, Wp=wp, batch=4, a_bs=M * 768, c_bs=512, a_split=True, c_split=True) == 0
+    for lvl in range(4):
+        assert maxdiff(ops.unsplit(x)[:, 256 * lvl:256 * lvl + 256], h[lvl].double() @ w.double().t()) < 2e-5
+    assert float(ops.unsplit(x)[:, 1024:].abs().max()) == 0.0
 
 
 @pytest.mark.parametrize("affine", [False, True])
