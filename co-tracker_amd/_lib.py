@@ -206,6 +206,8 @@ SYMBOLS = {
     "ctk_stream_support_ring": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_commit_ring": (C.c_int, [_P(StreamArgs), _fp]),
     "ctk_stream_assign_ring": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, _fp]),
+    "ctk_stream_assign_resident": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, C.c_int32, _fp]),
+    "ctk_stream_assign_resident_ring": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, _fp]),
     "ctk_stream_emit": (C.c_int, [_P(StreamEmit.Args), _fp]),
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),

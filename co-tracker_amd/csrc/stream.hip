@@ -10,6 +10,8 @@
 //   commit   cotracker3_online.py:498-510   finished window -> history rows, optional non-finite flag
 // A fourth kernel, assign, runs BETWEEN two calls and does no float arithmetic at all: it hands slots of the resident query table
 // to new queries (or empties them) and clears what their previous occupants left.
+// Its resident form (ctk_stream_assign_resident) admits query frames of the window just tracked, whose features the resident pyramid
+// still holds: it samples the slot's support patch then and there and lays the carry-over rows the next begin reads.
 // Ring forms (ctk_stream_*_ring): the history holds R = T_cap rows and frame f lives in row f % R.  begin and commit are the same
 // kernel bodies under RING = true, with t and g on grid axes so that the row of a frame is wave-uniform arithmetic; the RING = false
 // instantiations are the linear kernels, instruction for instruction.  support touches no history and assign clears every row of
@@ -77,25 +79,19 @@ struct StreamLevels {
   float sx[CTK_LEVELS], sy[CTK_LEVELS];
 };
 
-__global__ __launch_bounds__(256) void stream_support_kernel(StreamLevels lv, long P /* G*N */, int S, float sz, int left, int right,
-                                                             int ind, float inv_stride, const float* __restrict__ queries) {
-  const long wid = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  if (wid >= P * CTK_TAPS) return;
-  const long n = wid / CTK_TAPS;
-  const float* q = queries + n * 3;
-  const long qf = qframe_of(q[0]);
-  if (qf < left || qf >= right) return;  // not this window's point: its accumulator row is neither read nor written
-  const int l = blockIdx.y;
-  const int pp = (int)(wid - n * CTK_TAPS);
+// One (level, point, tap) row: the trilinear patch of (z, x, y) -- z a frame of the pyramid lv.fm[l], (x, y) the query position in
+// pixels -- for channels 2 * lane, 2 * lane + 1.  The one copy of this arithmetic: support adds it into the accumulator, the resident
+// assign stores it.
+__device__ __forceinline__ float2 support_row(const StreamLevels& lv, int l, int pp, int lane, long z, float qx, float qy, int S,
+                                              float sz, float inv_stride) {
   const int hx = pp / 7, wy = pp - hx * 7;
   const int H = lv.H[l], W = lv.W[l];
   // (queries / stride) / 2^l, then the tap arithmetic of sample_support_kernel (corr.hip)
   const float linv = 1.0f / (float)(1 << l);
-  const float cx = __fmul_rn(__fmul_rn(q[1], inv_stride), linv), cy = __fmul_rn(__fmul_rn(q[2], inv_stride), linv);
+  const float cx = __fmul_rn(__fmul_rn(qx, inv_stride), linv), cy = __fmul_rn(__fmul_rn(qy, inv_stride), linv);
   const CtkTap tx = ctk_tap(__fadd_rn(cx, (float)(hx - 3)), W, lv.sx[l]);
   const CtkTap ty = ctk_tap(__fadd_rn(cy, (float)(wy - 3)), H, lv.sy[l]);
-  const CtkTap tz = ctk_tap(__fadd_rn((float)(qf - ind), 0.0f), S, sz);
+  const CtkTap tz = ctk_tap(__fadd_rn((float)z, 0.0f), S, sz);
   const float* fm = lv.fm[l];
   float2 o = make_float2(0.f, 0.f);
   const int zi[2] = {tz.i0, tz.i1};
@@ -115,6 +111,20 @@ __global__ __launch_bounds__(256) void stream_support_kernel(StreamLevels lv, lo
         o.x = __fadd_rn(o.x, __fmul_rn(v.x, w));
         o.y = __fadd_rn(o.y, __fmul_rn(v.y, w));
       }
+  return o;
+}
+
+__global__ __launch_bounds__(256) void stream_support_kernel(StreamLevels lv, long P /* G*N */, int S, float sz, int left, int right,
+                                                             int ind, float inv_stride, const float* __restrict__ queries) {
+  const long wid = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wid >= P * CTK_TAPS) return;
+  const long n = wid / CTK_TAPS;
+  const float* q = queries + n * 3;
+  const long qf = qframe_of(q[0]);
+  if (qf < left || qf >= right) return;  // not this window's point: its accumulator row is neither read nor written
+  const int l = blockIdx.y;
+  const float2 o = support_row(lv, l, (int)(wid - n * CTK_TAPS), lane, qf - ind, q[1], q[2], S, sz, inv_stride);
   float2* dst = reinterpret_cast<float2*>(lv.acc[l] + wid * CTK_C + lane * 2);
   float2 a = *dst;  // acc + s: the accumulation of the host glue (zeros + s * 1 on the one call that samples this point)
   a.x = __fadd_rn(a.x, o.x);
@@ -182,6 +192,64 @@ __global__ __launch_bounds__(256) void stream_assign_kernel(AssignLevels lv, int
   for (long t = tid; t < rows; t += nthreads) {
     const long row = (g * T_cap + t) * N + n;
     *reinterpret_cast<float2*>(hc + row * 2) = make_float2(0.f, 0.f);
+    hv[row] = 0.0f;
+    hf[row] = 0.0f;
+  }
+}
+
+// ---- resident assign: the assign for query frames the resident pyramid still holds ------------------------------------------
+// grid (M, 2 * CTK_LEVELS): blockIdx.x = listed slot m, blockIdx.y >> 1 = the level whose accumulator rows this block writes (two
+// blocks of four waves per level); all the y blocks together stride over the slot's history rows.  `ind` is the first frame of the
+// NEXT call's window: the pyramid holds frames [ind - step, ind - step + S), row z = frame - (ind - step).
+//   resident  ind - step <= qframe < ind + overlap: the accumulator rows get the trilinear patch (one wave per tap row, as support:
+//             0 + s, what "cleared accumulator plus sample" leaves), and the history rows of frames [ind, ind + overlap) -- the rows the
+//             next begin carries over -- get (x, y) and zero logits, so that begin starts the point from its query as it starts a
+//             fresh one: fmul(x, 1 / stride) at every t
+//   else      the plain assign: accumulators and history rows zero
+// Every accumulator float and every history row has one writer, which stores its final value.
+template <bool RING>
+__global__ __launch_bounds__(256) void stream_assign_resident_kernel(StreamLevels lv, int G, int N, int S, int step, int ind, float sz,
+                                                                     float inv_stride, long T_cap, int rows,
+                                                                     const int32_t* __restrict__ slots, const float* __restrict__ newq,
+                                                                     float* __restrict__ queries, float* __restrict__ hc,
+                                                                     float* __restrict__ hv, float* __restrict__ hf) {
+  const long m = blockIdx.x;
+  const long slot = slots[m];
+  if (slot < 0 || slot >= (long)G * N) return;  // defence only: the host checks the list before it is copied over
+  const long tid = (long)blockIdx.y * blockDim.x + threadIdx.x;
+  const long nthreads = (long)gridDim.y * blockDim.x;
+  const float q0 = newq[m * 3], qx = newq[m * 3 + 1], qy = newq[m * 3 + 2];
+  if (tid < 3) queries[slot * 3 + tid] = newq[m * 3 + tid];
+  const long qf = qframe_of(q0);
+  const int overlap = S - step;
+  const bool resident = qf >= (long)ind - step && qf < (long)ind + overlap;
+  const int l = blockIdx.y >> 1;
+  float* acc = lv.acc[l] + slot * (CTK_TAPS * CTK_C);  // (a slot's run starts on a 25088-byte multiple)
+  if (resident) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((blockIdx.y & 1) * blockDim.x + threadIdx.x) >> 6));
+    const int lane = threadIdx.x & 63;
+    for (int pp = wave; pp < CTK_TAPS; pp += 8) {
+      const float2 o = support_row(lv, l, pp, lane, qf - ((long)ind - step), qx, qy, S, sz, inv_stride);
+      float2 a;
+      a.x = __fadd_rn(0.0f, o.x);
+      a.y = __fadd_rn(0.0f, o.y);
+      *reinterpret_cast<float2*>(acc + pp * CTK_C + lane * 2) = a;
+    }
+  } else {
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = (int)((blockIdx.y & 1) * blockDim.x + threadIdx.x); j < ASSIGN_ACC4; j += 2 * (int)blockDim.x)
+      reinterpret_cast<float4*>(acc)[j] = z4;
+  }
+  const long g = slot / N, n = slot - g * N;
+  // linear: rows [0, rows) and, resident, the carry rows [ind, ind + overlap) wherever they lie; ring: all T_cap rows
+  const long nrows = RING ? T_cap : (resident ? max((long)rows, (long)ind + overlap) : (long)rows);
+  const long first = RING ? (long)ring_row(ind, T_cap) : (long)ind;  // the row of frame ind
+  for (long t = tid; t < nrows; t += nthreads) {
+    if (!RING && t >= rows && t < ind) continue;  // between the cleared rows and the carry rows: not this call's
+    const long d = RING ? (t >= first ? t - first : t - first + T_cap) : t - first;  // frame of row t, minus ind
+    const bool carry = resident && d >= 0 && d < overlap;
+    const long row = (g * T_cap + t) * N + n;
+    *reinterpret_cast<float2*>(hc + row * 2) = carry ? make_float2(qx, qy) : make_float2(0.f, 0.f);
     hv[row] = 0.0f;
     hf[row] = 0.0f;
   }
@@ -317,6 +385,39 @@ int stream_assign(const ctk_stream_args* a, const int32_t* slots, const float* n
   return CTK_OK;
 }
 
+int stream_assign_resident(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
+                           void* stream, bool ring) {
+  const int rc = check_common(a, ring);  // a->ind: the first frame of the NEXT call's window (linear: T_cap >= ind + S holds its rows)
+  if (rc != CTK_OK) return rc;
+  if (!slots || !new_queries || !a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf) return CTK_E_NULL;
+  StreamLevels lv;
+  for (int l = 0; l < CTK_LEVELS; ++l) {
+    if (!a->support[l] || !a->fmaps[l]) return CTK_E_NULL;
+    if (!ctk_aligned16(a->support[l])) return CTK_E_SHAPE;  // cleared with 16-byte stores
+    if (a->H[l] <= 0 || a->W[l] <= 0) return CTK_E_SHAPE;
+    lv.fm[l] = a->fmaps[l];
+    lv.acc[l] = a->support[l];
+    lv.H[l] = a->H[l];
+    lv.W[l] = a->W[l];
+    lv.sx[l] = ctk_sampler_scale(a->W[l]);
+    lv.sy[l] = ctk_sampler_scale(a->H[l]);
+  }
+  if (a->ind < a->step) return CTK_E_SHAPE;  // no window has been tracked yet: the pyramid holds nothing to sample
+  if (M <= 0 || (long)M > (long)a->G * a->N || rows < 0 || rows > a->T_cap) return CTK_E_SHAPE;
+  const dim3 grid((unsigned)M, 2 * CTK_LEVELS);
+  if (ring) {
+    hipLaunchKernelGGL(stream_assign_resident_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), lv, a->G, a->N, a->S,
+                       a->step, a->ind, ctk_sampler_scale(a->S), 1.0f / a->stride, (long)a->T_cap, rows, slots, new_queries,
+                       const_cast<float*>(a->queries), a->hist_coords, a->hist_vis, a->hist_conf);
+  } else {
+    hipLaunchKernelGGL(stream_assign_resident_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), lv, a->G, a->N, a->S,
+                       a->step, a->ind, ctk_sampler_scale(a->S), 1.0f / a->stride, (long)a->T_cap, rows, slots, new_queries,
+                       const_cast<float*>(a->queries), a->hist_coords, a->hist_vis, a->hist_conf);
+  }
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
 }  // namespace
 
 extern "C" int ctk_stream_begin(const ctk_stream_args* a, void* stream) { return stream_begin(a, stream, false); }
@@ -335,6 +436,17 @@ extern "C" int ctk_stream_assign_ring(const ctk_stream_args* a, const int32_t* s
                                       void* stream) {
   if (!a) return CTK_E_NULL;
   return stream_assign(a, slots, new_queries, M, a->T_cap, stream, true);  // every row of the ring: whatever frame it holds
+}
+
+// resident forms of the assign: a->ind is the first frame of the NEXT call's window, a->fmaps / H / W the resident pyramid
+extern "C" int ctk_stream_assign_resident(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M,
+                                          int32_t rows, void* stream) {
+  return stream_assign_resident(a, slots, new_queries, M, rows, stream, false);
+}
+extern "C" int ctk_stream_assign_resident_ring(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M,
+                                               void* stream) {
+  if (!a) return CTK_E_NULL;
+  return stream_assign_resident(a, slots, new_queries, M, a->T_cap, stream, true);
 }
 
 extern "C" int ctk_stream_emit(const ctk_stream_emit_args* a, void* stream) {

@@ -889,7 +889,7 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError("a chunk shorter than the window has ended the stream")
         return gs, st[0].ind
 
-    def stream_assign(self, slots, queries):
+    def stream_assign(self, slots, queries, resident=False):
         """Between two streaming calls: slot slots[m] (flat index g*N + n of the [G,N] query table) tracks queries[m] = (frame, x,
         y), model-resolution pixels, from now on; an occupied slot gets a new occupant.  The frame must not lie below
         online_ind + window_len // 2, the first frame that the stream has not handed to the support sampling yet (ValueError: "its
@@ -898,9 +898,25 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         on the returned tracks belong to the new occupant.  Nothing of the next call changes shape or address: no graph is
         captured again.  The frame column is checked on the host (queries on the device: one small copy, the only wait);
         every refusal is raised before anything is written.  The `queries` argument of later forward calls is checked for shape
-        and device only: the resident table (stream_queries) is the truth."""
+        and device only: the resident table (stream_queries) is the truth.
+
+        resident=True admits the frames of the window just tracked as well, stream_resident_frames = [online_ind - window_len // 2,
+        online_ind + window_len - window_len // 2): the pyramid of that window is still on the device, so the point's support
+        features are sampled from it now (ops.StreamGroups.assign), and the next window starts the point at its query position on
+        every frame, as the first window of any point does.  The finished window is not run again for it: its rows below
+        online_ind stay empty (stream_first_row)."""
         gs, ind = self._slot_stream()
-        gs.assign(slots, queries, min_frame=ind + self.window_len // 2)
+        step = self.window_len // 2
+        if not resident:
+            return gs.assign(slots, queries, min_frame=ind + step)
+        gs.assign(slots, queries, resident=True)  # (its own frame rule: the refusal names the admissible range)
+
+    @property
+    def stream_resident_frames(self):
+        """(first, last + 1) of the frames whose features the running stream still holds between two calls -- the window just
+        tracked: what stream_assign(resident=True) admits besides later frames."""
+        gs, ind = self._slot_stream()
+        return (ind - self.window_len // 2, ind - self.window_len // 2 + self.window_len)
 
     def stream_release(self, slots):
         """Between two streaming calls: empty the listed slots (frame ops.EMPTY_FRAME, position (0, 0), state cleared)."""

@@ -829,7 +829,16 @@ class StreamGroups:
         L.check(getattr(L.load(), name)(C.byref(self._args(ind, T_valid, flag)), _stream()), name)
         self.committed, self.next_ind = ind + T_valid, ind + self.step
 
-    def assign(self, slots, queries: torch.Tensor, rows: Optional[int] = None, min_frame: Optional[int] = None) -> None:
+    @property
+    def resident_frames(self):
+        """(first, last + 1) of the frames the resident pyramid holds between two calls: the window just tracked, [next_ind - step,
+        next_ind - step + S).  None before the first call of a stream."""
+        if self.next_ind < self.step:
+            return None
+        return (self.next_ind - self.step, self.next_ind - self.step + self.S)
+
+    def assign(self, slots, queries: torch.Tensor, rows: Optional[int] = None, min_frame: Optional[int] = None,
+               resident: bool = False) -> None:
         """Between two calls: slot slots[m] (flat index g*N + n) gets the query queries[m] = (frame, x, y) in model-resolution
         pixels, its support accumulators and its history rows [0, rows) are cleared (rows: default every row committed so far; a ring:
         all its rows, always), and
@@ -838,7 +847,21 @@ class StreamGroups:
         the device that is one small device-to-host copy; the positions never leave the device --: a frame that is not finite, or
         whose integer part lies below `min_frame` (the caller's rule: the first frame no support call has handed out yet), raises
         ValueError, like a slot out of range, a slot listed twice or a wrong shape; nothing is written then.  Touches neither
-        ``serial`` nor the windows, the pyramid or any buffer address."""
+        ``serial`` nor the windows, the pyramid or any buffer address.
+
+        resident=True (ctk_stream_assign_resident, still one launch): query frames of the window just tracked are admitted too --
+        trunc(frame) >= next_ind - step, the first frame of the resident pyramid; this rule is checked here whatever the caller's
+        `min_frame` says (which still applies when given).  Such a slot gets its support patch sampled from the resident pyramid
+        (the bits ctk_stream_support would have added) and, instead of zeros, (x, y) with zero logits in the history rows of frames
+        [next_ind, next_ind + S - step), from which the next begin starts it as a fresh point; later frames are assigned as
+        without the keyword.  Needs a tracked window (next_ind >= step) and a stream no short chunk has closed: RuntimeError.
+        The linear history is reserved up to next_ind + S first, as the next begin would do: it may grow (new history addresses;
+        no address a captured graph has baked in changes -- the history lies outside the graphs)."""
+        if resident:
+            if self.closed:
+                raise RuntimeError("assign: a chunk shorter than the window has ended the stream")
+            if self.next_ind < self.step:
+                raise RuntimeError("assign: resident=True needs a tracked window: no call of this stream has been made yet")
         idx = torch.as_tensor(slots).detach().cpu().reshape(-1)
         M = idx.numel()
         if M == 0 or idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool:
@@ -861,13 +884,22 @@ class StreamGroups:
         if min_frame is not None and int(frames.long().min()) < min_frame:
             raise ValueError(f"assign: query frame {int(frames.long().min())} lies before frame {min_frame}: its features have left "
                              "the stream")
+        if resident and int(frames.long().min()) < self.next_ind - self.step:
+            raise ValueError(f"assign: query frame {int(frames.long().min())} lies before frame {self.next_ind - self.step}, the first "
+                             f"the resident pyramid holds (frames [{self.next_ind - self.step}, {self.next_ind - self.step + self.S}) "
+                             "and later ones are admitted)")
         if queries.device == dev:
             q = queries.detach().float().contiguous()
         else:
             q = queries.detach().float().contiguous().pin_memory().to(dev, non_blocking=True)
         s32 = idx.to(torch.int32).pin_memory().to(dev, non_blocking=True)
         _ = self.occupied  # (the bookkeeping is read from the table BEFORE this assign changes it)
-        if not ring:
+        if resident:  # ind = next_ind: the pyramid's first frame is next_ind - step, the carry rows start at next_ind
+            self.reserve(self.next_ind + self.S)  # (what the next begin reserves: the carry rows lie inside the buffer)
+            name = "ctk_stream_assign_resident_ring" if ring else "ctk_stream_assign_resident"
+            L.check(getattr(L.load(), name)(C.byref(self._args(self.next_ind)), _ptr(s32), _ptr(q), M, *(() if ring else (rows,)),
+                                            _stream()), name)
+        elif not ring:
             L.check(L.load().ctk_stream_assign(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, rows, _stream()), "ctk_stream_assign")
         else:  # every row of the ring, whatever `rows` says: after a wrap a slot's rows hold frames of any age
             L.check(L.load().ctk_stream_assign_ring(C.byref(self._args(0)), _ptr(s32), _ptr(q), M, _stream()), "ctk_stream_assign_ring")

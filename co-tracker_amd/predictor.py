@@ -216,12 +216,17 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         self._push_buf = None  # push_frames: the resident [window_len,3,ih,iw] float32 frames the next window still needs
         self._push_reset()
 
-    def add_queries(self, queries, group: int = 0):
+    def add_queries(self, queries, group: int = 0, resident: bool = False):
         """Between two steps of a running stream (after its first tracked chunk): track queries [M,3] = (frame, x, y) -- frame
         counted from the start of the stream, not below the first frame the stream has not sampled yet (model.stream_assign);
         x, y in pixels of the raw video, rescaled like first-step queries -- in the M lowest free slots of query set `group`.
         Returns their point indices (LongTensor [M]) in the returned tracks.  Fewer than M free slots: RuntimeError, nothing
-        assigned."""
+        assigned.
+
+        resident=True: every frame from resident_frames[0] on is accepted -- the frames of the window just tracked, the newest
+        picture the caller has seen among them (a click on it, a detector's output), whose features the stream still holds; frames a
+        push_frames stream has buffered but not run yet lie behind that window and are assigned the plain way in the same call.
+        The point is tracked from the next step on (visibility is False below that step's first frame)."""
         ih, iw = self.interp_shape
         H, W = self._hw
         q = queries.clone().float()
@@ -233,9 +238,18 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if free.numel() < q.shape[0]:
             raise RuntimeError(f"add_queries: {q.shape[0]} queries for {free.numel()} free slots (spare_points = {self.spare_points})")
         points = free[:q.shape[0]]
-        self.model.stream_assign(points + group * occ.shape[1], q)
+        if resident:
+            self.model.stream_assign(points + group * occ.shape[1], q, resident=True)
+        else:
+            self.model.stream_assign(points + group * occ.shape[1], q)
         self._mark_rows()
         return points
+
+    @property
+    def resident_frames(self):
+        """(first, last + 1) of the frames add_queries(resident=True) admits besides later ones: the window the last step tracked
+        (model.stream_resident_frames).  RuntimeError while no stream is running."""
+        return self.model.stream_resident_frames
 
     def remove_queries(self, points, group: int = 0):
         """Between two steps of a running stream: stop tracking the listed points (any of the N + K user-visible ones) of query set

@@ -47,6 +47,8 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_assign_resident / ctk_stream_assign_resident_ring: the
+ *       slot assign for query frames of the window just tracked, sampled from the resident pyramid between two calls.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_begin_ring / _support_ring / _commit_ring / _assign_ring
  *       (the same struct with T_cap read as a ring of R history rows, frame f in row f % R) and + ctk_stream_emit on the new struct
  *       ctk_stream_emit_args: history frames [f0, f1) -> contiguous tracks, logits and thresholded visibility in one launch.
@@ -326,6 +328,28 @@ int ctk_stream_begin_ring(const ctk_stream_args* a, void* stream);
 int ctk_stream_support_ring(const ctk_stream_args* a, void* stream);
 int ctk_stream_commit_ring(const ctk_stream_args* a, void* stream);
 int ctk_stream_assign_ring(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, void* stream);
+
+/* ---- resident assign: a slot for a query on a frame of the window just tracked -----------------------------------------------------
+ * Between two calls the pyramid of the call just made is still on the device.  Here `ind` is the first frame of the NEXT call's window
+ * (ind >= step: a window has been tracked), and fmaps / H / W name that resident pyramid: S frames [ind - step, ind - step + S) =
+ * [ind - step, ind + overlap), frame f in row f - (ind - step).  One launch for all M listed slots; per slot, by qframe =
+ * trunc(new_queries[m][0]):
+ *   ind - step <= qframe < ind + overlap   the query row is written; support[l] of the slot = 0 + the trilinear patch of frame row
+ *            qframe - (ind - step) at (x, y) / stride / 2^l, the arithmetic of ctk_stream_support operation for operation (what it
+ *            would have added to a cleared accumulator had the query been there when the window ran); the history rows [0, rows) --
+ *            a ring: all R -- become zero, EXCEPT the rows of frames [ind, ind + overlap) (a ring: rows f % R), which get coords
+ *            (x, y) and zero logits: the next begin carries them over into x / stride at every t, zero logits and point_mask 1, bit
+ *            for bit the state of a point that begins from its query.  The next support call does not sample it again (its range
+ *            starts at ind + step = ind + overlap, even S).
+ *   qframe >= ind + overlap (CTK_STREAM_EMPTY_FRAME included)   exactly ctk_stream_assign.
+ *   qframe < ind - step   the frame has left the pyramid: the CALLER refuses it (the frames live on the device); treated as the
+ *            plain assign here.
+ * Validation before any launch: everything ctk_stream_assign checks (with this `ind`, so the linear form wants T_cap >= ind + S: the
+ * carry rows are inside the buffer), plus NULL fmaps[l]: CTK_E_NULL; H[l] or W[l] <= 0, ind < step: CTK_E_SHAPE.  The ring form
+ * takes no `rows`.  No LDS, no atomics, no host synchronisation; capture-safe.                                                  */
+int ctk_stream_assign_resident(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, int32_t rows,
+                               void* stream);
+int ctk_stream_assign_resident_ring(const ctk_stream_args* a, const int32_t* slots, const float* new_queries, int32_t M, void* stream);
 
 /* emit: history frames [f0, f1), f1 - f0 <= R, of the first N_out <= N points of every group -> contiguous, frame-ordered outputs.
  * The history row of frame f is f % R: a linear history (R = T_cap >= f1) and a ring are read by the same formula.

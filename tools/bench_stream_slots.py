@@ -13,7 +13,10 @@ The C4 shape on the cotracker3_online model (window 16, 384 x 512 frames, window
 The rows stream the same resident video IN ONE PROCESS, ALTERNATING pass by pass; every chunk call lies between two HIP events;
 ms_* is the median over the calls after the first two windows of every pass.  Then the cost of an assign: a spare64 stream is
 driven to ind ~ 1000 frames, and stream_assign of 1, 16 and 256 slots (queries given on the host, frames far ahead) is timed
-`--assigns` times each: mean HIP-event time (the launch and the two small copies) and mean host time of the call.
+`--assigns` times each: mean HIP-event time (the launch and the two small copies) and mean host time of the call.  The resident
+form, stream_assign(resident=True) with the query on the newest tracked frame (online_ind + window_len // 2 - 1: every slot samples
+its 4 x 49 x 128 support floats from the resident pyramid), is timed in the same stream, ALTERNATING with the plain one size by size;
+ratio_resident_over_plain_K is the quotient of the two HIP-event means.  --assign-only skips the four stream rows.
 
 --trace runs ONE of glue / slots alone for a kernel trace (no counters in that run); --trace-summary takes two such traces of
 K_A < K_B calls: kernels per steady-state call and, minus the kernel nodes of the window graph the row replays, the launches
@@ -89,9 +92,19 @@ def make_rows(m, dev):
     return stream
 
 
-def bench_line(dev, precision, passes, calls, assigns):
+def bench_line(dev, precision, passes, calls, assigns, assign_only=False):
     m, video = setup(dev, precision)
     stream = make_rows(m, dev)
+    line = {"workload": "c4_one_set", "points": 1024, "frames": list(HW), "window_len": S, "iters": ITERS, "precision": precision,
+            "hip_graph": True, "libctk_sha256": lib_sha()}
+    if not assign_only:
+        line.update(rows_line(stream, video, passes, calls))
+    line.update(assign_line(stream, video, assigns))
+    torch.cuda.empty_cache()
+    return line
+
+
+def rows_line(stream, video, passes, calls):
     for row in ROWS:  # warm every row: weights packed, graphs captured
         stream(row, video, 3, NoTimer())
     ms, last = {r: [] for r in ROWS}, {}
@@ -99,11 +112,9 @@ def bench_line(dev, precision, passes, calls, assigns):
         for row in ROWS:
             last[row] = stream(row, video, calls, Timer(ms[row], 2))
     med = {r: statistics.median(v) for r, v in ms.items()}
-    line = {"workload": "c4_one_set", "points": 1024, "frames": list(HW), "window_len": S, "iters": ITERS, "precision": precision,
-            "hip_graph": True, "passes": passes, "calls_per_pass": calls, "timed_calls_per_row": len(ms["glue"]),
+    line = {"passes": passes, "calls_per_pass": calls, "timed_calls_per_row": len(ms["glue"]),
             "protocol": "rows alternate pass by pass in one process; every chunk call between two HIP events; median over the calls "
-                        "after the first two windows of each pass",
-            "libctk_sha256": lib_sha()}
+                        "after the first two windows of each pass"}
     for r in ROWS:
         line["ms_" + r] = round(med[r], 3)
         line["min_max_ms_" + r] = [round(min(ms[r]), 3), round(max(ms[r]), 3)]
@@ -112,35 +123,51 @@ def bench_line(dev, precision, passes, calls, assigns):
     line["slots_equals_glue_bit_for_bit"] = bool(torch.equal(last["slots"], last["glue"]))
     line["range_fallbacks"] = int(sum(x.range_fallbacks for x in stream.models.values()))
 
-    # the cost of an assign at ind ~ 1000 frames: three sizes, alternating, between the calls of one long spare64 stream
+    return line
+
+
+def assign_line(stream, video, assigns):
+    """The cost of an assign at ind ~ 1000 frames: three sizes, plain and resident alternating, between the calls of one long
+    spare64 stream."""
     sizes = (1, 16, 256)
-    gpu_ms, host_ms = {k: [] for k in sizes}, {k: [] for k in sizes}
+    turns = [(k, kind) for k in sizes for kind in ("plain", "resident")]
+    gpu_ms, host_ms = {t_: [] for t_ in turns}, {t_: [] for t_ in turns}
     far = torch.tensor([[1.0e6, 100.0, 100.0]]).expand(256, 3).contiguous()
     warm = 1000 // STEP
 
     def after_call(x, i):
         if i < warm:
             return
-        k = sizes[(i - warm) % len(sizes)]
+        k, kind = turn = turns[(i - warm) % len(turns)]
         slots = torch.arange(1088 - k, 1088)
+        q = far[:k]
+        if kind == "resident":  # the newest frame the stream has tracked
+            q = torch.tensor([[x.online_ind + STEP - 1.0, 100.0, 100.0]]).expand(k, 3).contiguous()
         torch.cuda.synchronize()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         a.record()
-        x.stream_assign(slots, far[:k])
+        if kind == "resident":
+            x.stream_assign(slots, q, resident=True)
+        else:
+            x.stream_assign(slots, q)
         b.record()
-        host_ms[k].append((time.perf_counter() - t0) * 1e3)
+        host_ms[turn].append((time.perf_counter() - t0) * 1e3)
         b.synchronize()
-        gpu_ms[k].append(a.elapsed_time(b))
-    stream("spare64", video, warm + assigns * len(sizes), NoTimer(), after_call)
+        gpu_ms[turn].append(a.elapsed_time(b))
+    stream("spare64", video, warm + assigns * len(turns), NoTimer(), after_call)
     x = stream.models["spare64"]
-    line["assign_at_ind"] = int(x.online_ind)
-    line["assign_history_rows_cleared"] = int(x._gstream.committed)
+    line = {"assign_at_ind": int(x.online_ind), "assign_history_rows_cleared": int(x._gstream.committed),
+            "assign_protocol": "plain and resident alternate size by size between the calls of one stream; HIP events around the call "
+                               "(the launch and the two small copies); the first assign of each kind and size is left out of the mean"}
     for k in sizes:  # (the first assign of a stream reads the frame column of the table once: left out of the mean)
-        line[f"assign_{k}_gpu_ms_mean"] = round(statistics.mean(gpu_ms[k][1:]), 4)
-        line[f"assign_{k}_host_ms_mean"] = round(statistics.mean(host_ms[k][1:]), 4)
-    line["assigns_timed_per_size"] = len(gpu_ms[1]) - 1
-    torch.cuda.empty_cache()
+        for kind, tag in (("plain", "assign"), ("resident", "assign_resident")):
+            line[f"{tag}_{k}_gpu_ms_mean"] = round(statistics.mean(gpu_ms[k, kind][1:]), 4)
+            line[f"{tag}_{k}_gpu_ms_min_max"] = [round(min(gpu_ms[k, kind][1:]), 4), round(max(gpu_ms[k, kind][1:]), 4)]
+            line[f"{tag}_{k}_host_ms_mean"] = round(statistics.mean(host_ms[k, kind][1:]), 4)
+        line[f"ratio_resident_over_plain_{k}"] = round(statistics.mean(gpu_ms[k, "resident"][1:]) / statistics.mean(gpu_ms[k, "plain"][1:]), 4)
+    line["assigns_timed_per_size"] = len(gpu_ms[1, "plain"]) - 1
+    line["range_fallbacks_assign_stream"] = int(x.range_fallbacks)
     return line
 
 
@@ -172,6 +199,7 @@ def main():
     ap.add_argument("--passes", type=int, default=3, help="stream passes per row")
     ap.add_argument("--calls", type=int, nargs="+", default=[6], help="chunk calls per pass (two values with --trace-summary)")
     ap.add_argument("--assigns", type=int, default=12, help="timed assigns per size")
+    ap.add_argument("--assign-only", action="store_true", help="time the assigns (plain and resident) only, not the four stream rows")
     ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f32"])
     ap.add_argument("--trace", default=None, choices=ROWS, help="run this row alone, for rocprofv3 --kernel-trace")
     ap.add_argument("--trace-summary", nargs=2, default=None, metavar=("OUT_A", "OUT_B"))
@@ -186,7 +214,7 @@ def main():
     if args.trace_summary:
         line = trace_summary(dev, args.precision, args.row, args.trace_summary, args.calls)
     else:
-        line = bench_line(dev, args.precision, max(1, args.passes), max(3, args.calls[0]), max(2, args.assigns) + 1)
+        line = bench_line(dev, args.precision, max(1, args.passes), max(3, args.calls[0]), max(2, args.assigns) + 1, args.assign_only)
     text = json.dumps(line)
     print(text, flush=True)
     if args.out:
