@@ -135,6 +135,22 @@ class StreamEmit:
         ]
 
 
+class StreamHealth:
+    """Holder of ctk_stream_health_args (include/ctk.h, "health"), nested like StreamEmit.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_stream_health_cabi.py."""
+
+    class Args(C.Structure):
+        """ctk_stream_health_args: the last `look` frames of every slot -> frames lost, coverage cell, points per cell."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f1", C.c_int32), ("look", C.c_int32),
+            ("ind_next", C.c_int32), ("thresh", C.c_float),
+            ("x_lo", C.c_float), ("x_hi", C.c_float), ("y_lo", C.c_float), ("y_hi", C.c_float),
+            ("gh", C.c_int32), ("gw", C.c_int32), ("inv_cw", C.c_float), ("inv_ch", C.c_float), ("reserved", C.c_int32),
+            ("queries", _fp), ("hist_coords", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("lost", _fp), ("cell", _fp), ("cover", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -209,6 +225,7 @@ SYMBOLS = {
     "ctk_stream_assign_resident": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, C.c_int32, _fp]),
     "ctk_stream_assign_resident_ring": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, _fp]),
     "ctk_stream_emit": (C.c_int, [_P(StreamEmit.Args), _fp]),
+    "ctk_stream_health": (C.c_int, [_P(StreamHealth.Args), _fp]),
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),

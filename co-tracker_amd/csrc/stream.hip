@@ -18,7 +18,9 @@
 // a slot, so their ring forms are the linear kernels behind the ring's capacity rule.
 // A fifth kernel, emit, runs AFTER a call: history frames [f0, f1) of the first N_out points of every group -> contiguous,
 // frame-ordered outputs (tracks scaled to the caller's pixels, the logits, thresholded visibility), in one launch.
-// No LDS, no atomics except the one flag OR, no device-side globals.
+// A sixth, health, judges the slots over the newest frames of the history with emit's visibility expression: frames lost per slot,
+// the slot's cell of a coverage grid, points per cell (integer counts in LDS, stored with plain stores).
+// No LDS and no atomics except the one flag OR and health's LDS counts; no device-side globals.
 #include "ctk_common.h"
 
 namespace {
@@ -259,6 +261,11 @@ __global__ __launch_bounds__(256) void stream_assign_resident_kernel(StreamLevel
 // sigmoid as 1 / (1 + expf(-x)), every step a float32 operation
 __device__ __forceinline__ float emit_sigmoid(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
 
+// the predictor's visibility rule; a NaN compares false: not visible.  The one copy: emit thresholds with it, health judges with it
+__device__ __forceinline__ bool emit_visible(float v, float c, float thresh) {
+  return __fmul_rn(emit_sigmoid(v), emit_sigmoid(c)) > thresh;
+}
+
 __global__ __launch_bounds__(256) void stream_emit_kernel(int N, int N_out, long R, int f0, int F, float sx, float sy, float thresh,
                                                           const float* __restrict__ hc, const float* __restrict__ hv,
                                                           const float* __restrict__ hf, const int32_t* __restrict__ first_row,
@@ -281,10 +288,99 @@ __global__ __launch_bounds__(256) void stream_emit_kernel(int N, int N_out, long
   if (vis_logit != nullptr) vis_logit[dst] = v;
   if (conf_logit != nullptr) conf_logit[dst] = c;
   if (visible != nullptr) {
-    bool on = __fmul_rn(emit_sigmoid(v), emit_sigmoid(c)) > thresh;  // (a NaN compares false: not visible)
+    bool on = emit_visible(v, c, thresh);
     if (first_row != nullptr) on = on && f >= first_row[g * N + n];
     visible[dst] = on ? 1 : 0;
   }
+}
+
+// ---- health: grid (n blocks, G); one thread per slot n < N_out walks the history backwards from frame f1 - 1 -------------------
+constexpr int HEALTH_CELLS_MAX = 4096;
+
+struct HealthParams {
+  int N, N_out;
+  long R;
+  int f1, look, ind_next;
+  float thresh, x_lo, x_hi, y_lo, y_hi;
+  int gh, gw;
+  float inv_cw, inv_ch;
+  const float* queries;
+  const float* hc;
+  const float* hv;
+  const float* hf;
+  const int32_t* first_row;
+};
+
+// inclusive bounds; a NaN coordinate is outside
+__device__ __forceinline__ bool health_inside(const HealthParams& p, float x, float y) {
+  return x >= p.x_lo && x <= p.x_hi && y >= p.y_lo && y <= p.y_hi;
+}
+
+// the cell of a position inside the bounds (x_hi and y_hi are clamped into the last column and row)
+__device__ __forceinline__ int health_cell(const HealthParams& p, float x, float y) {
+  const int cx = min(max((int)floorf(__fmul_rn(__fsub_rn(x, p.x_lo), p.inv_cw)), 0), p.gw - 1);
+  const int cy = min(max((int)floorf(__fmul_rn(__fsub_rn(y, p.y_lo), p.inv_ch)), 0), p.gh - 1);
+  return cy * p.gw + cx;
+}
+
+// Slot (g, n) judged over the last `look` frames -> its cell, and through `lost` the frames lost.  The cell depends on frame f1 - 1
+// (or the query) only: look = 1 yields the same cell as any longer look.
+__device__ __forceinline__ int health_judge(const HealthParams& p, long g, int n, int look, int& lost) {
+  const long s = g * p.N + n;
+  const int fr = p.first_row[s];
+  const float* q = p.queries + s * 3;
+  const float q0 = q[0];
+  lost = -1;
+  if (fr == INT32_MAX || q0 == CTK_STREAM_EMPTY_FRAME) return -1;  // an empty slot
+  lost = 0;
+  const long start = max((long)fr, qframe_of(q0));
+  if (fr >= p.ind_next || start >= (long)p.f1) {  // pending: no row of the history is this occupant's track yet
+    const float x = q[1], y = q[2];
+    return health_inside(p, x, y) ? health_cell(p, x, y) : -1;
+  }
+  const int stop = (int)max((long)(p.f1 - look), start);  // (0 <= f1 - look: checked on the host)
+  for (int f = p.f1 - 1; f >= stop; --f) {
+    const long row = (g * p.R + ring_row(f, p.R)) * p.N + n;
+    const float2 h = *reinterpret_cast<const float2*>(p.hc + row * 2);
+    if (emit_visible(p.hv[row], p.hf[row], p.thresh) && health_inside(p, h.x, h.y))
+      return f == p.f1 - 1 ? health_cell(p, h.x, h.y) : -1;
+    ++lost;
+  }
+  return -1;
+}
+
+// Block b of group g judges slots [256 b, 256 b + 256) and owns the cells [c0, c1) of the group's cover: it counts them in LDS over
+// ALL slots of the group -- its own from the judgement it has just made, the others judged again at look = 1 (one history row each) --
+// and stores the counts with plain stores.  Integer counting: the order of the LDS adds does not show in the result.
+__global__ __launch_bounds__(256) void stream_health_kernel(HealthParams p, int32_t* __restrict__ lost, int32_t* __restrict__ cell,
+                                                            int32_t* __restrict__ cover) {
+  __shared__ int counts[HEALTH_CELLS_MAX];
+  const long g = (long)blockIdx.y;
+  const int tid = (int)threadIdx.x;
+  const int cells = p.gh * p.gw;
+  const int per = (cells + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int c0 = min((int)blockIdx.x * per, cells), c1 = min(c0 + per, cells);
+  for (int c = c0 + tid; c < c1; c += 256) counts[c - c0] = 0;
+  __syncthreads();
+  const int n0 = (int)blockIdx.x * 256;
+  const int n = n0 + tid;
+  if (n < p.N_out) {
+    int l;
+    const int c = health_judge(p, g, n, p.look, l);
+    lost[g * p.N_out + n] = l;
+    cell[g * p.N_out + n] = c;
+    if (c >= c0 && c < c1) atomicAdd(&counts[c - c0], 1);
+  }
+  if (c0 < c1) {
+    for (int m = tid; m < p.N_out; m += 256) {
+      if (m >= n0 && m < n0 + 256) continue;  // (wave-uniform: m - tid is a multiple of 256)
+      int l;
+      const int c = health_judge(p, g, m, 1, l);
+      if (c >= c0 && c < c1) atomicAdd(&counts[c - c0], 1);
+    }
+  }
+  __syncthreads();
+  for (int c = c0 + tid; c < c1; c += 256) cover[g * cells + c] = counts[c - c0];
 }
 
 constexpr int GRID_YZ_MAX = 65535;  // grid axes y and z
@@ -463,6 +559,30 @@ extern "C" int ctk_stream_emit(const ctk_stream_emit_args* a, void* stream) {
   hipLaunchKernelGGL(stream_emit_kernel, dim3((unsigned)((a->N_out + 255) / 256), (unsigned)F, (unsigned)a->G), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a->N, a->N_out, (long)a->R, a->f0, F, a->sx, a->sy, a->thresh, a->hist_coords,
                      a->hist_vis, a->hist_conf, a->first_row, a->tracks, a->vis_logit, a->conf_logit, a->visible);
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}
+
+extern "C" int ctk_stream_health(const ctk_stream_health_args* a, void* stream) {
+  if (!a) return CTK_E_NULL;
+  if (!a->queries || !a->hist_coords || !a->hist_vis || !a->hist_conf || !a->first_row || !a->lost || !a->cell || !a->cover)
+    return CTK_E_NULL;
+  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->N_out > a->N || a->R <= 0 || a->reserved != 0) return CTK_E_SHAPE;
+  if (a->gh <= 0 || a->gw <= 0 || (long)a->gh * a->gw > HEALTH_CELLS_MAX) return CTK_E_SHAPE;
+  if (a->f1 <= 0 || a->f1 > (1 << 30) || a->look < 1 || a->look > a->R || a->look > a->f1 || a->ind_next < 0) return CTK_E_SHAPE;
+  if (a->G > GRID_YZ_MAX || (long)a->G * a->N > (1L << 26)) return CTK_E_SHAPE;
+  if (!(a->thresh == a->thresh)) return CTK_E_SHAPE;
+  if (!std::isfinite(a->x_lo) || !std::isfinite(a->x_hi) || !std::isfinite(a->y_lo) || !std::isfinite(a->y_hi)) return CTK_E_SHAPE;
+  if (a->x_hi <= a->x_lo || a->y_hi <= a->y_lo) return CTK_E_SHAPE;
+  if (!std::isfinite(a->inv_cw) || !std::isfinite(a->inv_ch) || !(a->inv_cw > 0.0f) || !(a->inv_ch > 0.0f)) return CTK_E_SHAPE;
+  HealthParams p;
+  p.N = a->N, p.N_out = a->N_out, p.R = (long)a->R;
+  p.f1 = a->f1, p.look = a->look, p.ind_next = a->ind_next;
+  p.thresh = a->thresh, p.x_lo = a->x_lo, p.x_hi = a->x_hi, p.y_lo = a->y_lo, p.y_hi = a->y_hi;
+  p.gh = a->gh, p.gw = a->gw, p.inv_cw = a->inv_cw, p.inv_ch = a->inv_ch;
+  p.queries = a->queries, p.hc = a->hist_coords, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
+  hipLaunchKernelGGL(stream_health_kernel, dim3((unsigned)((a->N_out + 255) / 256), (unsigned)a->G), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), p, a->lost, a->cell, a->cover);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }

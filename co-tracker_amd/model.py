@@ -966,6 +966,14 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError("no stream is running on the device stream state")
         return gs.emit(f0, f1, N_out, scale, logits, thresh, first_row)
 
+    def stream_health(self, look, grid, thresh, N_out, first_row, bounds):
+        """The slots of the running (or just closed) stream judged over its last `look` frames, by one launch and without a wait:
+        ops.StreamGroups.health -> (lost, cell, cover) on the device.  Serves a ring history and the default one alike."""
+        gs = self._gstream
+        if gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state")
+        return gs.health(look, grid, thresh, N_out, first_row, bounds)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

@@ -773,6 +773,52 @@ class StreamGroups:
         L.check(L.load().ctk_stream_emit(C.byref(a), _stream()), "ctk_stream_emit")
         return tuple(out)
 
+    HEALTH_CELLS_MAX = 4096  # (csrc/stream.hip: the cover of a group is counted in LDS)
+
+    def health(self, look: int, grid, thresh: float, N_out: Optional[int], first_row: torch.Tensor, bounds):
+        """The slots of every group judged over the last `look` committed frames by ONE launch (ctk_stream_health; include/ctk.h
+        has the rules): -> (lost [G,N_out] int32: frames lost, newest first, -1 for an empty slot and 0 for one whose occupant has
+        not been tracked yet; cell [G,N_out] int32: the slot's cell cy * gw + cx of the grid = (gh, gw) laid over bounds = (x_lo,
+        x_hi, y_lo, y_hi), model-resolution pixels, inclusive, or -1; cover [G,gh*gw] int32: slots per cell).  alive is emit's
+        sigmoid(vis) * sigmoid(conf) > thresh inside the bounds.  first_row: int32 [G,N] on the device, INT32_MAX for an empty slot
+        (what emit takes).  f1 = committed, ind_next = next_ind.  The three results are views of ONE allocation, in this order
+        (``lost._base``: one copy brings all of them to the host).  No wait."""
+        N_out = self.N if N_out is None else int(N_out)
+        gh, gw = (int(v) for v in grid)
+        look = int(look)
+        dev = self.queries.device
+        if self.committed <= 0:
+            raise ValueError("health: no frame has been committed yet")
+        if not 1 <= look <= min(self.T_cap, self.committed):
+            raise ValueError(f"health: look must lie in [1, {min(self.T_cap, self.committed)}] (frames so far: {self.committed}, history "
+                             f"rows: {self.T_cap})")
+        if not 1 <= N_out <= self.N:
+            raise ValueError(f"health: N_out must lie in [1, {self.N}]")
+        if gh < 1 or gw < 1 or gh * gw > self.HEALTH_CELLS_MAX:
+            raise ValueError(f"health: the grid must have between 1 and {self.HEALTH_CELLS_MAX} cells, got {gh} x {gw}")
+        if not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or tuple(first_row.shape) != (self.G, self.N) or \
+                first_row.device != dev or not first_row.is_contiguous():
+            raise ValueError(f"health: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+        a = L.StreamHealth.Args()
+        a.G, a.N, a.N_out, a.R, a.f1, a.look, a.ind_next = self.G, self.N, N_out, self.T_cap, self.committed, look, self.next_ind
+        a.thresh, a.reserved, a.gh, a.gw = float(thresh), 0, gh, gw
+        a.x_lo, a.x_hi, a.y_lo, a.y_hi = (float(v) for v in bounds)
+        if not (a.x_hi > a.x_lo and a.y_hi > a.y_lo):
+            raise ValueError(f"health: empty bounds {tuple(bounds)}")
+        # float32 operands, float32 quotient (the struct fields hold the float32 bounds the kernel compares with)
+        a.inv_cw, a.inv_ch = (float(torch.tensor(float(n_), dtype=torch.float32) / (torch.tensor(hi, dtype=torch.float32) -
+                                                                                   torch.tensor(lo, dtype=torch.float32)))
+                              for n_, lo, hi in ((gw, a.x_lo, a.x_hi), (gh, a.y_lo, a.y_hi)))
+        a.queries = _ptr(self.queries)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_) for h_ in self.hist)
+        a.first_row = _ptr(first_row)
+        k = self.G * N_out
+        flat = torch.empty(2 * k + self.G * gh * gw, device=dev, dtype=torch.int32)
+        lost, cell, cover = flat[:k].view(self.G, N_out), flat[k:2 * k].view(self.G, N_out), flat[2 * k:].view(self.G, gh * gw)
+        a.lost, a.cell, a.cover = _ptr(lost), _ptr(cell), _ptr(cover)
+        L.check(L.load().ctk_stream_health(C.byref(a), _stream()), "ctk_stream_health")
+        return lost, cell, cover
+
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()
         a.G, a.N, a.S, a.step, a.ind, a.T_valid, a.T_cap, a.stride = self.G, self.N, self.S, self.step, ind, T_valid, self.T_cap, self.stride

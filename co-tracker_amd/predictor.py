@@ -187,6 +187,31 @@ class CoTrackerPredictor(torch.nn.Module):
         return tracks, vis
 
 
+def choose_replenish(lost, cover, occupied, max_lost, max_new=None):
+    """The policy of CoTrackerOnlinePredictor.replenish as a pure host function (numpy; no torch device): lost [G,N] (frames each
+    user-visible point has been lost for, -1: an empty slot), cover [G,gh,gw] or [G,cells] (points per cell), occupied [G,N] bool ->
+    (released [K,2], added [M,2], cells [M]): the (group, point) rows to release -- every occupied point with lost >= max_lost --,
+    the (group, point) rows to seed and the row-major cell index of each seed.  Per group, independently: the cells with cover == 0
+    in row-major order, one seed each, on the lowest free slots -- those this call releases included -- until free slots, empty
+    cells or `max_new` (per group; None: no limit) run out.  Rows are ordered by group, then point (released) or cell (added)."""
+    import numpy as np
+    lost, occupied = np.asarray(lost), np.asarray(occupied).astype(bool)
+    G, N = lost.shape
+    cover = np.asarray(cover).reshape(G, -1)
+    assert occupied.shape == (G, N), (occupied.shape, lost.shape)
+    drop = occupied & (lost >= max_lost)
+    free = ~occupied | drop
+    released = np.argwhere(drop).reshape(-1, 2)
+    added, cells = [], []
+    for g in range(G):
+        empty = np.flatnonzero(cover[g] == 0)
+        slots = np.flatnonzero(free[g])
+        m = min(len(empty), len(slots), len(empty) if max_new is None else max(int(max_new), 0))
+        added += [(g, int(n)) for n in slots[:m]]
+        cells += [int(c) for c in empty[:m]]
+    return released.astype(np.int64), np.asarray(added, dtype=np.int64).reshape(-1, 2), np.asarray(cells, dtype=np.int64)
+
+
 class CoTrackerOnlinePredictor(torch.nn.Module):
     def __init__(self, checkpoint="./checkpoints/scaled_online.pth", offline=False, v2=False, window_len=16):
         super().__init__()
@@ -250,6 +275,94 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         """(first, last + 1) of the frames add_queries(resident=True) admits besides later ones: the window the last step tracked
         (model.stream_resident_frames).  RuntimeError while no stream is running."""
         return self.model.stream_resident_frames
+
+    def _health(self, look, grid, thresh, border):
+        """One ctk_stream_health launch over the user-visible points -> (lost, cell, cover [G,gh*gw]) on the device and the bounds."""
+        if self.v2:
+            raise NotImplementedError("CoTracker2 keeps no stream state on the device: track_health / replenish on a v2 predictor is "
+                                      "not implemented")
+        gh, gw = (int(v) for v in grid)
+        if gh < 1 or gw < 1 or gh * gw > 4096:
+            raise ValueError(f"the coverage grid must have between 1 and 4096 cells, got {gh} x {gw}")
+        if not float(border) >= 0.0:
+            raise ValueError("border must be >= 0")
+        if getattr(self, "queries", None) is None or self._hw is None:
+            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+        ih, iw = self.interp_shape
+        bounds = (-float(border), iw - 1 + float(border), -float(border), ih - 1 + float(border))
+        look = self.model.window_len if look is None else int(look)
+        first = self._emit_first_row()
+        if first is None:  # no spare_points: every slot holds a query of the first step
+            first = torch.zeros(self.queries.shape[:2], dtype=torch.int32, device=self.queries.device)
+        return self.model.stream_health(look, (gh, gw), thresh, self.N, first, bounds), bounds
+
+    def track_health(self, look=None, grid=(8, 8), thresh=0.6, border=0.0):
+        """Between two steps (or after the last): how the points of the running stream are doing, on the device, by ONE launch and
+        without a wait -- for callers with a policy of their own.  -> (lost [G,N] int32, cover [G,gh,gw] int32).  lost[g, n]: for how
+        many of the newest frames, counted back from the last tracked one over at most `look` (default window_len) frames and not
+        beyond the point's first tracked frame, the point has been lost -- not visible by the rule of the returned visibility
+        (visibility * confidence > thresh) or outside the picture widened by `border` model-resolution pixels; 0 for a point
+        added since the last step or whose query frame lies ahead; -1 for an empty slot.  cover: how many of the N (+ spare_points)
+        user-visible points lie in each cell of a grid = (gh, gw) over that area on the newest frame (points still waiting count
+        at their query position)."""
+        (lost, _, cover), _ = self._health(look, grid, thresh, border)
+        return lost, cover.view(cover.shape[0], int(grid[0]), int(grid[1]))
+
+    def replenish(self, max_lost, grid=(8, 8), look=None, thresh=0.6, border=0.0, max_new=None, group=None):
+        """Between two steps of a running stream with spare_points: stop tracking what is lost and seed new points where nothing
+        covers the picture.  Every user-visible point lost for >= max_lost frames (track_health's count over `look` >= max_lost
+        frames) is released; then, per query set, every cell of the grid that no point covers gets one new query at its centre on
+        the newest tracked frame, resident_frames[1] - 1, in row-major cell order on the lowest free slots (those just released
+        included) until slots, cells or `max_new` (per query set) run out -- choose_replenish is the rule.  group: one query set
+        only (default: all).  One health launch, ONE small device-to-host copy (the call's only wait), then at most one
+        release and one resident assign for all query sets together; no graph is captured again.  Returns (released [K,2],
+        added [M,2]) as (group, point) rows and queries [M,3] = (frame, x, y) of the seeds in raw-video pixels.  A seed is
+        tracked from the next step on; until then it counts as covering its cell, so a second call adds nothing.  RuntimeError,
+        before anything is written: no tracked step yet, no slots (spare_points), or a short chunk has ended the stream."""
+        max_lost = int(max_lost)
+        look = self.model.window_len if look is None else int(look)
+        if max_lost < 1:
+            raise ValueError("replenish: max_lost must be >= 1")
+        if look < max_lost:
+            raise ValueError(f"replenish: look = {look} frames cannot show a point lost for max_lost = {max_lost}")
+        if self.v2:
+            raise NotImplementedError("CoTracker2 keeps no stream state on the device: track_health / replenish on a v2 predictor is "
+                                      "not implemented")
+        gh, gw = (int(v) for v in grid)
+        if gh < 1 or gw < 1 or gh * gw > 4096:
+            raise ValueError(f"the coverage grid must have between 1 and 4096 cells, got {gh} x {gw}")
+        if not float(border) >= 0.0:
+            raise ValueError("border must be >= 0")
+        if getattr(self, "queries", None) is None or self._hw is None:
+            raise RuntimeError("no stream is running: run the first step and a tracked one first")
+        newest = self.resident_frames[1] - 1  # (RuntimeError: no tracked step, no slots, a closed stream)
+        G, Nm = self.queries.shape[:2]
+        if group is not None and not 0 <= int(group) < G:
+            raise ValueError(f"replenish: group outside [0, {G})")
+        (lost, _, cover), (x_lo, x_hi, y_lo, y_hi) = self._health(look, (gh, gw), thresh, border)
+        flat = lost._base.cpu().numpy()  # the one wait: lost | cell | cover are one allocation
+        lost_h, cover_h = flat[:G * self.N].reshape(G, self.N).copy(), flat[2 * G * self.N:].reshape(G, gh * gw).copy()
+        if group is not None:  # the other query sets: nothing lost, nothing uncovered
+            other = [g for g in range(G) if g != int(group)]
+            lost_h[other], cover_h[other] = 0, 1
+        occ = self.model.stream_occupied[:, :self.N].numpy()
+        released, added, cells = choose_replenish(lost_h, cover_h, occ, max_lost, max_new)
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        q = torch.zeros(len(added), 3)
+        if len(added):
+            c = torch.from_numpy(cells)
+            q[:, 0] = float(newest)
+            q[:, 1] = ((x_lo + ((c % gw).double() + 0.5) * ((x_hi - x_lo) / gw)) * ((W - 1) / (iw - 1))).float()
+            q[:, 2] = ((y_lo + (torch.div(c, gw, rounding_mode="floor").double() + 0.5) * ((y_hi - y_lo) / gh)) * ((H - 1) / (ih - 1))).float()
+        if len(released):
+            self.model.stream_release(torch.from_numpy(released[:, 0] * Nm + released[:, 1]))
+        if len(added):
+            qm = q.clone()
+            qm[:, 1:] *= qm.new_tensor([(iw - 1) / (W - 1), (ih - 1) / (H - 1)])  # (add_queries' rescaling, operation for operation)
+            self.model.stream_assign(torch.from_numpy(added[:, 0] * Nm + added[:, 1]), qm, resident=True)
+        if len(released) or len(added):
+            self._mark_rows()
+        return torch.from_numpy(released), torch.from_numpy(added), q
 
     def remove_queries(self, points, group: int = 0):
         """Between two steps of a running stream: stop tracking the listed points (any of the N + K user-visible ones) of query set

@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_health on the new struct ctk_stream_health_args: per
+ *       slot, how many of the newest frames the point has been lost for and which cell of a coverage grid it is in; per cell, how
+ *       many points cover it -- one launch, integers only.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_assign_resident / ctk_stream_assign_resident_ring: the
  *       slot assign for query frames of the window just tracked, sampled from the resident pyramid between two calls.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_begin_ring / _support_ring / _commit_ring / _assign_ring
@@ -377,6 +380,45 @@ typedef struct ctk_stream_emit_args {
   uint8_t* visible;           /* optional */
 } ctk_stream_emit_args;
 int ctk_stream_emit(const ctk_stream_emit_args* a, void* stream);
+
+/* health: which slots track nothing any more, and which parts of the picture no point covers -- judged over the last `look`
+ * committed frames [f1 - look, f1) of the first N_out <= N slots of every group, read by emit's f % R formula (linear or ring).
+ * For slot (g, n), with qframe = trunc(queries[g*N+n][0]) and start = max(first_row[g,n], qframe):
+ *   empty    first_row == INT32_MAX or query frame == CTK_STREAM_EMPTY_FRAME:  lost = -1, cell = -1
+ *   pending  first_row >= ind_next (assigned since the last commit: its rows are not the occupant's tracks, whatever they hold -- a
+ *            resident assign leaves (x, y) and zero logits there) or start >= f1 (its query frame has not been tracked):  lost = 0,
+ *            cell = the cell of its QUERY position, -1 if that lies outside the bounds
+ *   tracked  alive(f) = sigmoid(vis) * sigmoid(conf) > thresh (emit's `visible` expression, bit for bit) and x_lo <= x <= x_hi and
+ *            y_lo <= y <= y_hi on the history coordinates of frame f; a NaN logit or coordinate: not alive.
+ *            lost = the number of consecutive frames f1-1, f1-2, ... >= max(f1 - look, start) that are not alive (0 <= lost <=
+ *            min(look, f1 - start)); cell = the cell of the position at frame f1 - 1 if alive there, else -1
+ *   cell     cy * gw + cx, cx = clamp((int)floorf((x - x_lo) * inv_cw), 0, gw - 1), cy likewise: two float32 operations each
+ *   cover    [G, gh*gw]: cover[g, c] = the number of slots n < N_out of group g with cell == c.  Every element is written (no fill
+ *            beforehand), integer counting: the result does not depend on scheduling.
+ * Slots n >= N_out are neither read nor judged.  One launch on `stream`, no host synchronisation, capture-safe; writes lost, cell and
+ * cover only.  Before the launch: NULL a or any NULL pointer: CTK_E_NULL; G, N, N_out, R, gh, gw <= 0, N_out > N, gh * gw > 4096,
+ * f1 <= 0, f1 > 2^30, look < 1, look > R, look > f1, ind_next < 0, G > 65535, G * N > 2^26, a NaN thresh, bounds that are not finite
+ * or empty (x_hi <= x_lo, y_hi <= y_lo), inv_cw or inv_ch not finite or <= 0, reserved != 0: CTK_E_SHAPE.                      */
+typedef struct ctk_stream_health_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* slots per group that are judged (the first N_out)                 */
+  int32_t R;                  /* history rows per group (ring size, or the capacity of a linear one) */
+  int32_t f1;                 /* exclusive end: the committed frame count                          */
+  int32_t look;               /* frames looked back, 1 <= look <= min(R, f1)                       */
+  int32_t ind_next;           /* first frame of the next call's window                             */
+  float thresh;               /* alive: sigmoid(vis) * sigmoid(conf) > thresh                      */
+  float x_lo, x_hi, y_lo, y_hi; /* inclusive bounds, model-resolution pixels                       */
+  int32_t gh, gw;             /* coverage grid, gh * gw <= 4096 cells                              */
+  float inv_cw, inv_ch;       /* float32(gw) / (x_hi - x_lo), float32(gh) / (y_hi - y_lo)          */
+  int32_t reserved;           /* 0 */
+  const float* queries;       /* [G*N,3] */
+  const float* hist_coords; const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* [G,N]; INT32_MAX: an empty slot */
+  int32_t* lost;              /* out [G,N_out] */
+  int32_t* cell;              /* out [G,N_out] */
+  int32_t* cover;             /* out [G,gh*gw] */
+} ctk_stream_health_args;
+int ctk_stream_health(const ctk_stream_health_args* a, void* stream);
 
 /* ---- frame ingest: decoder output -> encoder input in one launch -------------------------------------------------------------
  * Replaces, for a stream that is fed frame by frame, the per-chunk
