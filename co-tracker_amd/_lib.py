@@ -151,6 +151,21 @@ class StreamHealth:
         ]
 
 
+class Seed:
+    """Holder of ctk_seed_args (include/ctk.h, "seed points"), nested like StreamEmit.Args and for the same reason; its layout is checked
+    against the compiler by tests/test_stream_seed_cabi.py."""
+
+    class Args(C.Structure):
+        """ctk_seed_args: one frame and a grid of cells -> the best-textured pixel of every cell."""
+        _fields_ = [
+            ("frame", _fp), ("h", C.c_int32), ("w", C.c_int32),
+            ("radius", C.c_int32), ("margin", C.c_int32), ("inset", C.c_int32), ("min_score", C.c_int32),
+            ("x_lo", C.c_float), ("x_hi", C.c_float), ("y_lo", C.c_float), ("y_hi", C.c_float),
+            ("gh", C.c_int32), ("gw", C.c_int32), ("inv_cw", C.c_float), ("inv_ch", C.c_float), ("reserved", C.c_int32),
+            ("seeds", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -226,6 +241,7 @@ SYMBOLS = {
     "ctk_stream_assign_resident_ring": (C.c_int, [_P(StreamArgs), _fp, _fp, C.c_int32, _fp]),
     "ctk_stream_emit": (C.c_int, [_P(StreamEmit.Args), _fp]),
     "ctk_stream_health": (C.c_int, [_P(StreamHealth.Args), _fp]),
+    "ctk_seed_points": (C.c_int, [_P(Seed.Args), _fp]),
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),

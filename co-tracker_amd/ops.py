@@ -207,6 +207,49 @@ def ingest_frames(src: torch.Tensor, out: torch.Tensor, layout: Optional[str] = 
     return out
 
 
+SEED_CELLS_MAX = 65536  # (csrc/seed.hip: one workgroup per cell)
+
+
+def cell_scale(n: int, lo: float, hi: float) -> float:
+    """inv_cw / inv_ch of ctk_stream_health_args and ctk_seed_args: float32 operands, float32 quotient, rounded once."""
+    return float(torch.tensor(float(n), dtype=torch.float32) / (torch.tensor(hi, dtype=torch.float32) - torch.tensor(lo, dtype=torch.float32)))
+
+
+def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin: Optional[int] = None, inset: int = 0,
+                min_score: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The best-textured pixel of every cell of grid = (gh, gw) over ONE frame, by ONE launch (ctk_seed_points; include/ctk.h and
+    csrc/seed_math.h have the rules): frame float32 [3,h,w] (nominally 0..255), contiguous, on the device -- a frame of a resized
+    chunk or of the push buffer -> int32 [gh*gw,3] on the device, row cy * gw + cx = (px, py, score) or (-1, -1, -1) for a cell
+    without a candidate or whose best score is below min_score.  bounds = (x_lo, x_hi, y_lo, y_hi), inclusive, model-resolution
+    pixels (default: the picture, (0, w - 1, 0, h - 1)): with the bounds and grid of StreamGroups.health a seed lies in the cell health
+    counts it in.  margin (default radius + 1: the window and its gradients stay inside the image) and inset keep candidates away
+    from the image border and from the edges of their cell.  out: a contiguous int32 [gh*gw,3] device tensor to write instead of a new
+    one.  No wait."""
+    if not (isinstance(frame, torch.Tensor) and frame.is_cuda and frame.dtype == torch.float32 and frame.dim() == 3 and
+            frame.shape[0] == 3 and frame.is_contiguous()):
+        raise ValueError("seed_points: frame must be a contiguous float32 device tensor [3,h,w]")
+    gh, gw = (int(v) for v in grid)
+    if gh < 1 or gw < 1 or gh * gw > SEED_CELLS_MAX:
+        raise ValueError(f"seed_points: the grid must have between 1 and {SEED_CELLS_MAX} cells, got {gh} x {gw}")
+    radius = int(radius)
+    margin = radius + 1 if margin is None else int(margin)
+    if not 1 <= radius <= 7 or margin < 0 or int(inset) < 0 or int(min_score) < 0:
+        raise ValueError("seed_points: radius must lie in 1..7; margin, inset and min_score must be >= 0")
+    a = L.Seed.Args()
+    a.h, a.w = frame.shape[1:]
+    a.radius, a.margin, a.inset, a.min_score, a.reserved, a.gh, a.gw = radius, margin, int(inset), int(min_score), 0, gh, gw
+    a.x_lo, a.x_hi, a.y_lo, a.y_hi = (float(v) for v in (bounds if bounds is not None else (0.0, a.w - 1.0, 0.0, a.h - 1.0)))
+    if not (a.x_hi > a.x_lo and a.y_hi > a.y_lo):
+        raise ValueError(f"seed_points: empty bounds {(a.x_lo, a.x_hi, a.y_lo, a.y_hi)}")
+    a.inv_cw, a.inv_ch = cell_scale(gw, a.x_lo, a.x_hi), cell_scale(gh, a.y_lo, a.y_hi)
+    seeds = torch.empty(gh * gw, 3, device=frame.device, dtype=torch.int32) if out is None else out
+    if not (seeds.dtype == torch.int32 and tuple(seeds.shape) == (gh * gw, 3) and seeds.device == frame.device and seeds.is_contiguous()):
+        raise ValueError(f"seed_points: out must be a contiguous int32 [{gh * gw},3] tensor on the frame's device")
+    a.frame, a.seeds = _ptr(frame), _ptr(seeds)
+    L.check(L.load().ctk_seed_points(C.byref(a), _stream()), "ctk_seed_points")
+    return seeds
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""

@@ -32,6 +32,17 @@ def get_points_on_a_grid(size, extent, center=None, device="cpu"):
     return torch.stack([gx, gy], dim=-1).reshape(1, -1, 2)
 
 
+def corner_grid(frames, size, lattice):
+    """The first-step grid of grid_seeds = "corners": frames [B,3,ih,iw] float32 (model resolution, on the device), lattice
+    [1,size*size,2] = get_points_on_a_grid(size, (ih, iw)) -> [B,size*size,2]: per video, the best-textured pixel (ops.seed_points:
+    radius 3, candidates 4 pixels inside the image, score >= 1) of every cell of a uniform size x size partition of the picture,
+    row-major like the lattice; a cell without a seed keeps the lattice point of its row and column.  One launch per video and a few
+    elementwise ones; no wait."""
+    from . import ops
+    found = torch.stack([ops.seed_points(f.contiguous(), (size, size)) for f in frames])  # [B,size*size,3] int32
+    return torch.where(found[:, :, :1] >= 0, found[:, :, :2].float(), lattice.expand(frames.shape[0], -1, -1))
+
+
 def _cat(a, b, dim):
     return b if a is None else torch.cat([a, b], dim=dim)
 
@@ -45,6 +56,10 @@ class CoTrackerPredictor(torch.nn.Module):
         self.interp_shape = model.model_resolution
         self.model = model
         self.model.eval()
+        # Not a reference kwarg (set it after construction; forward's signature is the reference's): "grid" -- a grid_size = g request
+        # tracks the reference lattice -- or "corners": the best-textured pixel of every cell of a uniform g x g partition of the
+        # picture on frame grid_query_frame (corner_grid); segm_mask filters afterwards, by the same rule.
+        self.grid_seeds = "grid"
 
     @torch.no_grad()
     def forward(self, video, queries: torch.Tensor = None, segm_mask: torch.Tensor = None, grid_size: int = 0,
@@ -142,11 +157,19 @@ class CoTrackerPredictor(torch.nn.Module):
             queries[:, :, 1:] *= queries.new_tensor([(iw - 1) / (W - 1), (ih - 1) / (H - 1)])
         elif grid_size > 0:
             pts = get_points_on_a_grid(grid_size, self.interp_shape, device=video.device)
+            if self.grid_seeds == "corners":
+                if self.v2:
+                    raise NotImplementedError("grid_seeds = 'corners' on a v2 predictor is not implemented")
+                if not 0 <= int(grid_query_frame) < T:
+                    raise ValueError(f"grid_seeds = 'corners': grid_query_frame = {grid_query_frame} is not a frame of a {T}-frame video")
+                pts = corner_grid(video[:, int(grid_query_frame)], grid_size, pts)
+            elif self.grid_seeds != "grid":
+                raise ValueError(f"grid_seeds must be 'grid' or 'corners', got {self.grid_seeds!r}")
             if segm_mask is not None:
                 segm_mask = F.interpolate(segm_mask, tuple(self.interp_shape), mode="nearest")
                 keep = segm_mask[0, 0][pts[0, :, 1].round().long(), pts[0, :, 0].round().long()].bool()
                 pts = pts[:, keep]
-            queries = torch.cat([torch.full_like(pts[:, :, :1], float(grid_query_frame)), pts], dim=2).repeat(B, 1, 1)
+            queries = torch.cat([torch.full_like(pts[:, :, :1], float(grid_query_frame)), pts], dim=2).repeat(B // pts.shape[0], 1, 1)
         if add_support_grid:
             g = get_points_on_a_grid(self.support_grid_size, self.interp_shape, device=video.device)
             g = torch.cat([torch.zeros_like(g[:, :, :1]), g], dim=2).repeat(B, 1, 1)
@@ -239,6 +262,16 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         self._first_row = self._hw = None
         self._first_row32 = None  # (the tensor it was made from, [G,N_model] int32 for ctk_stream_emit)
         self._push_buf = None  # push_frames: the resident [window_len,3,ih,iw] float32 frames the next window still needs
+        # The newest tracked frame at model resolution, [3,ih,iw]: a VIEW (nothing is launched or copied for it) of the last resized
+        # chunk (forward) or of the push buffer (push_frames), for replenish(seeds="corners").  Valid until the next completed step:
+        # a partial push only writes buffer rows below it.
+        self._newest_frame = None
+        # Not a reference kwarg (set it after construction; forward's signature is the reference's): how a first step with
+        # grid_size = g and no queries places its g * g points.  "grid": the reference lattice.  "corners": a uniform g x g partition
+        # of the picture, every cell taking its best-textured pixel (ops.seed_points) on frame grid_query_frame of the resized
+        # chunk -- which must hold that frame: a one-frame dummy chunk cannot serve (ValueError) --; a cell without a seed keeps the
+        # lattice point of its row and column.  Built on the device without a wait, one launch per video of the batch.
+        self.grid_seeds = "grid"
         self._push_reset()
 
     def add_queries(self, queries, group: int = 0, resident: bool = False):
@@ -308,7 +341,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         (lost, _, cover), _ = self._health(look, grid, thresh, border)
         return lost, cover.view(cover.shape[0], int(grid[0]), int(grid[1]))
 
-    def replenish(self, max_lost, grid=(8, 8), look=None, thresh=0.6, border=0.0, max_new=None, group=None):
+    def replenish(self, max_lost, grid=(8, 8), look=None, thresh=0.6, border=0.0, max_new=None, group=None, seeds="centre", min_score=1,
+                  skip_flat=False):
         """Between two steps of a running stream with spare_points: stop tracking what is lost and seed new points where nothing
         covers the picture.  Every user-visible point lost for >= max_lost frames (track_health's count over `look` >= max_lost
         frames) is released; then, per query set, every cell of the grid that no point covers gets one new query at its centre on
@@ -318,7 +352,19 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         release and one resident assign for all query sets together; no graph is captured again.  Returns (released [K,2],
         added [M,2]) as (group, point) rows and queries [M,3] = (frame, x, y) of the seeds in raw-video pixels.  A seed is
         tracked from the next step on; until then it counts as covering its cell, so a second call adds nothing.  RuntimeError,
-        before anything is written: no tracked step yet, no slots (spare_points), or a short chunk has ended the stream."""
+        before anything is written: no tracked step yet, no slots (spare_points), or a short chunk has ended the stream.
+
+        seeds="corners": a chosen cell takes its best-textured pixel instead of its centre -- ONE more launch (ops.seed_points,
+        ctk_seed_points: the corner score of csrc/seed_math.h) right after the health launch, on the newest tracked frame at
+        model resolution, over the health bounds and grid, candidates max(1, min(cell width, cell height) // 4) pixels inside
+        their cell; still one wait, for two small copies issued after both launches.  A chosen cell whose best score is below
+        min_score (a blank wall: the 7 x 7 correlation has no peak there) takes its centre as before, or, with skip_flat=True,
+        gets no point: its slot stays free.  choose_replenish picks cells and slots as before.  A stream that holds no newest
+        frame (no tracked step since the first step): RuntimeError; any other `seeds`: ValueError; both before any launch."""
+        if seeds not in ("centre", "corners"):
+            raise ValueError(f"replenish: seeds must be 'centre' or 'corners', got {seeds!r}")
+        if int(min_score) < 0:
+            raise ValueError("replenish: min_score must be >= 0")
         max_lost = int(max_lost)
         look = self.model.window_len if look is None else int(look)
         if max_lost < 1:
@@ -339,8 +385,22 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         G, Nm = self.queries.shape[:2]
         if group is not None and not 0 <= int(group) < G:
             raise ValueError(f"replenish: group outside [0, {G})")
+        if seeds == "corners" and self._newest_frame is None:
+            raise RuntimeError("replenish(seeds='corners'): the stream holds no newest frame: run a tracked step first")
         (lost, _, cover), (x_lo, x_hi, y_lo, y_hi) = self._health(look, (gh, gw), thresh, border)
-        flat = lost._base.cpu().numpy()  # the one wait: lost | cell | cover are one allocation
+        corner = None
+        if seeds == "corners":
+            from . import ops
+            inset = max(1, int(min((x_hi - x_lo) / gw, (y_hi - y_lo) / gh) // 4))
+            corner = ops.seed_points(self._newest_frame, (gh, gw), bounds=(x_lo, x_hi, y_lo, y_hi), inset=inset, min_score=int(min_score))
+            n_h = lost._base.numel()
+            host = torch.empty(n_h + corner.numel(), dtype=torch.int32, pin_memory=True)
+            host[:n_h].copy_(lost._base, non_blocking=True)
+            host[n_h:].copy_(corner.view(-1), non_blocking=True)
+            torch.cuda.current_stream(lost.device).synchronize()  # the one wait, for both copies
+            flat, corner = host[:n_h].numpy(), host[n_h:].view(gh * gw, 3)
+        else:
+            flat = lost._base.cpu().numpy()  # the one wait: lost | cell | cover are one allocation
         lost_h, cover_h = flat[:G * self.N].reshape(G, self.N).copy(), flat[2 * G * self.N:].reshape(G, gh * gw).copy()
         if group is not None:  # the other query sets: nothing lost, nothing uncovered
             other = [g for g in range(G) if g != int(group)]
@@ -354,6 +414,14 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             q[:, 0] = float(newest)
             q[:, 1] = ((x_lo + ((c % gw).double() + 0.5) * ((x_hi - x_lo) / gw)) * ((W - 1) / (iw - 1))).float()
             q[:, 2] = ((y_lo + (torch.div(c, gw, rounding_mode="floor").double() + 0.5) * ((y_hi - y_lo) / gh)) * ((H - 1) / (ih - 1))).float()
+            if corner is not None:  # a cell with a seed: its integer model-resolution pixel, through the arithmetic of the centres
+                found = corner[c]
+                has = found[:, 0] >= 0
+                q[has, 1] = (found[has, 0].double() * ((W - 1) / (iw - 1))).float()
+                q[has, 2] = (found[has, 1].double() * ((H - 1) / (ih - 1))).float()
+                if skip_flat:  # a flat cell gets no point; its slot stays free
+                    keep = has.numpy()
+                    q, added, cells = q[has], added[keep], cells[keep]
         if len(released):
             self.model.stream_release(torch.from_numpy(released[:, 0] * Nm + released[:, 1]))
         if len(added):
@@ -457,6 +525,9 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             self._prev_chunk = None
             self._push_reset()
             self._first_row, self._hw = None, (H, W)
+            self._newest_frame = None
+            if self.grid_seeds not in ("grid", "corners"):
+                raise ValueError(f"grid_seeds must be 'grid' or 'corners', got {self.grid_seeds!r}")
             if self.v2:
                 if self.history_frames is not None:
                     raise NotImplementedError("CoTracker2 returns the tracks of the whole stream: history_frames on a v2 predictor is "
@@ -479,6 +550,15 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                     self.model.stream_groups = True
             elif grid_size > 0:
                 pts = get_points_on_a_grid(grid_size, self.interp_shape, device=video_chunk.device)
+                if self.grid_seeds == "corners":
+                    if self.v2:
+                        raise NotImplementedError("grid_seeds = 'corners' on a v2 predictor is not implemented")
+                    if not 0 <= int(grid_query_frame) < T:
+                        raise ValueError(f"grid_seeds = 'corners' reads frame grid_query_frame = {grid_query_frame} of the first step's "
+                                         f"chunk, which holds {T} frame(s)")
+                    frames = F.interpolate(video_chunk[:, int(grid_query_frame)].float(), tuple(self.interp_shape), mode="bilinear",
+                                           align_corners=True)
+                    pts = corner_grid(frames, grid_size, pts)
                 self.N = grid_size ** 2
                 queries = self._with_spare(torch.cat([torch.full_like(pts[:, :, :1], float(grid_query_frame)), pts], dim=2))
             self.queries = queries
@@ -499,6 +579,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                 pass
         v = F.interpolate(video_chunk.reshape(B * T, C, H, W).float(), tuple(self.interp_shape), mode="bilinear",
                           align_corners=True).reshape(B, T, 3, ih, iw)
+        self._newest_frame = v[0, T - 1] if B == 1 else None  # (a view of v; the device stream state holds one video)
         if self.v2:  # CoTracker2 returns (tracks, visibility, train_data): no confidence (predictor.py:283-286)
             tracks, vis, _ = self.model(video=v, queries=self.queries, iters=6, is_online=True)
             conf = None
@@ -603,4 +684,5 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         with self._quiet():  # (a ring stream: the result is emitted by push_frames, one launch for the user points)
             tracks, vis, conf, _ = self.model.stream_push(new_frames, self.queries, iters=6, final=final)
         self._push_fill, self._push_tracked = 0, True
+        self._newest_frame = None if final else new_frames[new_frames.shape[0] - 1]  # (a view of the push buffer)
         return tracks, vis, conf

@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_seed_points on the new struct ctk_seed_args: the
+ *       best-textured pixel (integer corner score of the luminance) of every cell of a grid over one model-resolution frame -- where a
+ *       stream should put a new point; one launch, integers only.
  *   v9, additive (number unchanged; struct ctk_stream_args unchanged): + ctk_stream_health on the new struct ctk_stream_health_args: per
  *       slot, how many of the newest frames the point has been lost for and which cell of a coverage grid it is in; per cell, how
  *       many points cover it -- one launch, integers only.
@@ -419,6 +422,41 @@ typedef struct ctk_stream_health_args {
   int32_t* cover;             /* out [G,gh*gw] */
 } ctk_stream_health_args;
 int ctk_stream_health(const ctk_stream_health_args* a, void* stream);
+
+/* ---- seed points: where to put a new point -------------------------------------------------------------------------------------
+ * The best-textured pixel of every cell of a gh x gw grid over ONE planar float32 frame [3,h,w] (nominally 0..255: a frame of
+ * ctk_ingest_frames' output, or of the resized chunk), by a corner score in integer arithmetic stated once in csrc/seed_math.h:
+ *   luminance  q = (int)rintf(min(max(p, 0), 255)) per channel, a NaN gives 0;  L = (77 qR + 150 qG + 29 qB + 128) >> 8
+ *   gradient   gx = L(y, min(x+1, w-1)) - L(y, max(x-1, 0)), gy likewise (central differences, replicated borders)
+ *   tensor     a = sum gx^2, b = sum gx gy, c = sum gy^2 over the (2 radius + 1)^2 window; pixels outside the image contribute nothing
+ *   score      a + c - ceil_sqrt((a - c)^2 + 4 b^2) = floor(2 lambda_min), >= 0
+ *   cell       pixel (px, py) with x_lo <= px <= x_hi and y_lo <= py <= y_hi (as float32) belongs to cell cy * gw + cx, cx =
+ *              clamp((int)floorf((px - x_lo) * inv_cw), 0, gw - 1), cy likewise: the cell ctk_stream_health counts a point at that
+ *              position in when it is given the same bounds, grid and inv_cw / inv_ch.  A cell's pixels are a rectangle
+ *              [X0,X1] x [Y0,Y1] (possibly empty).
+ *   candidates the pixels of the cell with X0 + inset <= px <= X1 - inset, Y0 + inset <= py <= Y1 - inset, margin <= px <= w - 1 - margin
+ *              and margin <= py <= h - 1 - margin (margin >= radius + 1 keeps the window and its gradients inside the image)
+ *   seeds      [gh*gw,3] int32: row c = (px, py, score) of the candidate with the highest score -- ties: the lowest py, then the
+ *              lowest px -- or (-1, -1, -1) when the cell has no candidate or its best score is below min_score.
+ * Every element of seeds is written by a plain store (no fill beforehand, no atomics); the result does not depend on scheduling.
+ * One launch on `stream`, no host synchronisation, capture-safe; writes seeds only.  Before the launch: NULL a, frame or seeds:
+ * CTK_E_NULL; h or w outside 1..CTK_INGEST_MAX_SIDE, radius outside 1..7, margin, inset or min_score < 0, gh or gw <= 0, gh * gw >
+ * 65536, bounds that are not finite or empty (x_hi <= x_lo, y_hi <= y_lo), inv_cw or inv_ch not finite or <= 0, reserved != 0:
+ * CTK_E_SHAPE; frame or seeds not 4-byte aligned: CTK_E_ALIGN.                                                                */
+typedef struct ctk_seed_args {
+  const float* frame;         /* [3,h,w] planar float32, contiguous                                */
+  int32_t h, w;
+  int32_t radius;             /* window radius, 1..7                                               */
+  int32_t margin;             /* candidates keep this distance from the image border, pixels       */
+  int32_t inset;              /* ... and this distance from the edges of their cell, pixels        */
+  int32_t min_score;          /* a cell whose best score is below it reports no seed               */
+  float x_lo, x_hi, y_lo, y_hi; /* inclusive bounds, model-resolution pixels                       */
+  int32_t gh, gw;             /* grid, gh * gw <= 65536 cells                                      */
+  float inv_cw, inv_ch;       /* float32(gw) / (x_hi - x_lo), float32(gh) / (y_hi - y_lo)          */
+  int32_t reserved;           /* 0 */
+  int32_t* seeds;             /* out [gh*gw,3]: (px, py, score) or (-1, -1, -1)                    */
+} ctk_seed_args;
+int ctk_seed_points(const ctk_seed_args* a, void* stream);
 
 /* ---- frame ingest: decoder output -> encoder input in one launch -------------------------------------------------------------
  * Replaces, for a stream that is fed frame by frame, the per-chunk

@@ -10,11 +10,13 @@ The C4 shape on the online predictor (window 16, 384 x 512 frames, iters 6, wind
 spare slots, fed by push_frames (eight model-resolution float frames per call, sixteen for the first window):
   plain      the stream as it is;
   health     the same stream with a track_health() after every call (it only reads: the tracks must not change);
-  replenish  the same stream with a replenish(max_lost) after every call, inside the timed call.
+  replenish  the same stream with a replenish(max_lost) after every call, inside the timed call;
+  corners    the same with replenish(max_lost, seeds="corners"): one ctk_seed_points launch and one small copy more per call.
 The rows run IN ONE PROCESS, ALTERNATING pass by pass; every call lies between two HIP events; ms_* is the median over the calls
 after the first two windows of every pass, with the smallest and largest single call next to it.  Then, between the calls of one
 stream: the stream time (HIP events) of the ONE health launch against a torch restatement of the same lost / cover over the same
-history rows (torch_health below), alternating, and the host time of replenish() -- the launch, its one device-to-host copy (the
+history rows (torch_health below) and the ONE seed launch (ops.seed_points on the newest tracked frame, the health grid and bounds,
+replenish's inset) on the same stream, alternating, and the host time of replenish() -- the launch, its one device-to-host copy (the
 call's only wait), the host policy, the release and the resident assign.
 
 What must hold: the health path is ONE launch (--trace-summary), `health` equals `plain` bit for bit on every point, and `replenish`
@@ -41,7 +43,7 @@ for p_ in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 from bench_stream_groups import HW, NoTimer, S, Timer, grid, kernel_rows, lib_sha  # noqa: E402
 
-ROWS = ("plain", "health", "replenish")
+ROWS = ("plain", "health", "replenish", "corners")
 STEP = S // 2
 RING = S + 5 * STEP  # frames resident, walked round
 POINTS, SPARE = 1024, 64
@@ -123,6 +125,8 @@ def make_rows(p, video, dev):
                     x.track_health(grid=GRID, thresh=THRESH)
                 elif row == "replenish":
                     log.append(x.replenish(MAX_LOST, grid=GRID, thresh=THRESH))
+                elif row == "corners":
+                    log.append(x.replenish(MAX_LOST, grid=GRID, thresh=THRESH, seeds="corners"))
             outs.append((out[0].clone(), out[1].clone()))
             if after_call is not None:
                 after_call(x, i)
@@ -156,8 +160,9 @@ def compare(plain, other, log):
 def health_line(stream, reps):
     """Between the calls of one `plain` stream: the health launch against torch_health, alternating; then replenish() host time on the
     `replenish` stream (its own after-call log: what it released and seeded)."""
-    gpu_ms = {"health": [], "torch": []}
-    agree = []
+    from cotracker_amd import ops
+    gpu_ms = {"health": [], "torch": [], "seed": []}
+    agree, seeded = [], []
 
     def after_call(x, i):
         if i < 2:
@@ -167,28 +172,35 @@ def health_line(stream, reps):
         ih, iw = x.interp_shape
         args = (S, GRID, THRESH, x.N, first32, (0.0, iw - 1.0, 0.0, ih - 1.0))
         for _ in range(reps):
-            for kind in ("health", "torch"):
+            for kind in ("health", "torch", "seed"):
                 torch.cuda.synchronize()
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-                out = gs.health(*args) if kind == "health" else torch_health(gs, *args)
+                if kind == "seed":
+                    out = ops.seed_points(x._newest_frame, GRID, bounds=args[5], inset=max(1, int(min((iw - 1.0) / GRID[1], (ih - 1.0) / GRID[0]) // 4)))
+                else:
+                    out = gs.health(*args) if kind == "health" else torch_health(gs, *args)
                 b.record()
                 b.synchronize()
                 gpu_ms[kind].append(a.elapsed_time(b))
                 if kind == "health":
                     mine = out
+                elif kind == "seed":
+                    seeded.append(int((out[:, 0] >= 0).sum()))
                 else:
                     agree.append((int((mine[0] != out[0]).sum()), int((mine[2] != out[2]).sum())))
     stream("plain", 5, NoTimer(), after_call)
     line = {"health_protocol": "the ctk_stream_health launch and the torch restatement alternate between the calls of one stream, each "
                                "between two HIP events after a device synchronise; the first pair is left out",
             "health_look": S, "health_grid": list(GRID), "health_points": POINTS + SPARE}
-    for kind in ("health", "torch"):
+    for kind in ("health", "torch", "seed"):
         v = gpu_ms[kind][1:]
         line[f"{kind}_gpu_ms_median"] = round(statistics.median(v), 4)
         line[f"{kind}_gpu_ms_min_max"] = [round(min(v), 4), round(max(v), 4)]
     line["ratio_torch_over_health"] = round(statistics.median(gpu_ms["torch"][1:]) / statistics.median(gpu_ms["health"][1:]), 2)
     line["health_evaluations_timed"] = len(gpu_ms["health"]) - 1
+    line["ratio_seed_over_health"] = round(statistics.median(gpu_ms["seed"][1:]) / statistics.median(gpu_ms["health"][1:]), 2)
+    line["seed_cells_with_a_seed_min_max"] = [min(seeded), max(seeded)]
     line["torch_lost_cover_elements_differing_max"] = [max(a[0] for a in agree), max(a[1] for a in agree)]
     return line
 
@@ -227,6 +239,9 @@ def bench_line(dev, precision, passes, calls, reps):
         line["min_max_ms_" + r] = [round(min(ms[r]), 3), round(max(ms[r]), 3)]
     line["ratio_health_over_plain"] = round(med["health"] / med["plain"], 4)
     line["ratio_replenish_over_plain"] = round(med["replenish"] / med["plain"], 4)
+    line["ratio_corners_over_plain"] = round(med["corners"] / med["plain"], 4)
+    line["ratio_corners_over_replenish"] = round(med["corners"] / med["replenish"], 4)
+    line["corners_released_added_per_call"] = [[len(r_), len(a_)] for r_, a_, _ in last["corners"][1]]
     line["replenish_host_ms_median"] = round(statistics.median(host_ms), 4)
     line["replenish_host_ms_min_max"] = [round(min(host_ms), 4), round(max(host_ms), 4)]
     outs, log = last["replenish"]
