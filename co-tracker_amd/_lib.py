@@ -166,6 +166,25 @@ class Seed:
         ]
 
 
+class Draw:
+    """Holder of ctk_draw_args (include/ctk.h, "draw tracks"), nested like StreamEmit.Args and for the same reason; its layout is checked
+    against the compiler by tests/test_draw_cabi.py."""
+
+    TRAIL_MAX, RADIUS_MAX, HALF_WIDTH_MAX, JUMP_MAX = 64, 32, 16, 4095
+
+    class Args(C.Structure):
+        """ctk_draw_args: history rows, colours and uint8 frames -> marks and trails drawn onto the frames."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("trail", C.c_int32), ("radius", C.c_int32), ("half_width", C.c_int32), ("max_jump", C.c_int32),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("layout", C.c_int32),
+            ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_uint8 * 65),
+            ("frame_stride", C.c_int64), ("row_stride", C.c_int64),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp), ("colors", _fp),
+            ("src", _fp), ("dst", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -243,6 +262,8 @@ SYMBOLS = {
     "ctk_stream_health": (C.c_int, [_P(StreamHealth.Args), _fp]),
     "ctk_seed_points": (C.c_int, [_P(Seed.Args), _fp]),
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
+    "ctk_draw_tracks_workspace_bytes": (C.c_int, [_P(Draw.Args), _P(C.c_size_t)]),
+    "ctk_draw_tracks": (C.c_int, [_P(Draw.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

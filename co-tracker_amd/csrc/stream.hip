@@ -261,7 +261,8 @@ __global__ __launch_bounds__(256) void stream_assign_resident_kernel(StreamLevel
 // sigmoid as 1 / (1 + expf(-x)), every step a float32 operation
 __device__ __forceinline__ float emit_sigmoid(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
 
-// the predictor's visibility rule; a NaN compares false: not visible.  The one copy: emit thresholds with it, health judges with it
+// the predictor's visibility rule; a NaN compares false: not visible.  Emit thresholds with it, health judges with it; draw_math.h
+// (ctk_draw_visible) restates it operation for operation for the draw kernels and their host build
 __device__ __forceinline__ bool emit_visible(float v, float c, float thresh) {
   return __fmul_rn(emit_sigmoid(v), emit_sigmoid(c)) > thresh;
 }

@@ -974,6 +974,14 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError("no stream is running on the device stream state")
         return gs.health(look, grid, thresh, N_out, first_row, bounds)
 
+    def stream_draw(self, frames, f0, colors, **kw):
+        """Points of the running (or just closed) stream drawn onto uint8 frames from its own history, by two launches and without a
+        wait: ops.StreamGroups.draw.  Serves a ring history and the default one alike."""
+        gs = self._gstream
+        if gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state")
+        return gs.draw(frames, f0, colors, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

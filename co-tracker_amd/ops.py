@@ -250,6 +250,162 @@ def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin:
     return seeds
 
 
+# ------------------------------------------------------------------------------------------
+# draw tracks (csrc/draw.hip; include/ctk.h, "draw tracks")
+# ------------------------------------------------------------------------------------------
+_draw_ws_cache = {}
+
+
+def _draw_workspace(nbytes: int, device) -> torch.Tensor:
+    """The primitive table of ctk_draw_tracks, cached per device like _workspace -- a cache of its own: captured window graphs bake
+    the address of that one in, and a draw call must never be the reason it moves."""
+    key = (device.index if device.index is not None else torch.cuda.current_device())
+    buf = _draw_ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _draw_ws_cache[key] = None
+        buf = _draw_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
+    return buf
+
+
+def rainbow_colors(y: torch.Tensor) -> torch.Tensor:
+    """Default colours of draw_tracks: y [...,N] (the points' y on their first row) -> uint8 [...,N,3], an integer HSV ramp red ->
+    yellow -> green -> cyan -> blue over min(y) .. max(y) of each row of points (the idea of the reference visualiser's
+    mode="rainbow", without matplotlib): t = floor((y - lo) / (hi - lo) * 1020) in 0..1020, four ramps of 255 steps.  A y that is not
+    finite takes t = 0.  Torch glue: it runs when the point set changes, not per drawn frame."""
+    y = y.float()
+    finite = torch.isfinite(y)
+    big = torch.finfo(torch.float32).max
+    lo = torch.where(finite, y, y.new_tensor(big)).amin(dim=-1, keepdim=True)
+    hi = torch.where(finite, y, y.new_tensor(-big)).amax(dim=-1, keepdim=True)
+    t = ((y - lo) / (hi - lo).clamp_min(1e-6) * 1020.0).nan_to_num(0.0, 0.0, 0.0).clamp(0.0, 1020.0).long()
+    seg, x = t // 255, t % 255
+    zero, full = torch.zeros_like(x), torch.full_like(x, 255)
+    r = torch.where(seg == 0, full, torch.where(seg == 1, 255 - x, zero))
+    g = torch.where(seg == 0, x, torch.where(seg <= 2, full, torch.where(seg == 3, 255 - x, zero)))
+    b = torch.where(seg <= 1, zero, torch.where(seg == 2, x, full))
+    return torch.stack([r, g, b], dim=-1).to(torch.uint8)
+
+
+def default_alpha(trail: int) -> List[int]:
+    """alpha[0] = 255 (marks), alpha[k] = 255 * (L + 1 - k)^2 // (L + 1)^2 for segment k of L = trail: the quadratic fade of the
+    reference visualiser's trails, in integers."""
+    return [255] + [255 * (trail + 1 - k) ** 2 // (trail + 1) ** 2 for k in range(1, trail + 1)]
+
+
+def _draw_surface(frames: torch.Tensor, layout: Optional[str], who: str):
+    """uint8 device frames [F,H,W,3] / [F,3,H,W] -> (layout, F, H, W, row_stride, frame_stride), strides in elements, read off the
+    tensor by the rules of ingest_frames: a view is used where it lies when its innermost dimensions are dense."""
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 4 and frames.dtype == torch.uint8 and frames.is_cuda):
+        raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+    if layout is None:
+        hwc, chw = frames.shape[3] == 3, frames.shape[1] == 3
+        if hwc == chw:
+            raise ValueError(f"{who}: cannot tell the layout of {tuple(frames.shape)} frames: pass layout='hwc' or 'chw'")
+        layout = "hwc" if hwc else "chw"
+    if layout not in ("hwc", "chw") or frames.shape[3 if layout == "hwc" else 1] != 3:
+        raise ValueError(f"{who}: {tuple(frames.shape)} frames are not layout {layout!r} with 3 channels")
+    if layout == "hwc":
+        F_, H, W = frames.shape[:3]
+        row = frames.stride(1)
+        dense, frame = frames.stride(3) == 1 and frames.stride(2) == 3, H * row
+    else:
+        F_, H, W = frames.shape[0], frames.shape[2], frames.shape[3]
+        row = frames.stride(2)
+        dense, frame = frames.stride(3) == 1 and frames.stride(1) == H * row, 3 * H * row
+    if H == 1:  # (the stride of a dimension of size 1 is arbitrary)
+        row = W * (3 if layout == "hwc" else 1)
+        frame = row * (1 if layout == "hwc" else 3)
+        dense = frames.stride(3) == 1 and (frames.stride(2) == 3 if layout == "hwc" else (W == 1 or frames.stride(1) == W))
+    if F_ < 1 or not dense:
+        raise ValueError(f"{who}: the innermost dimensions of the {layout} frames are not dense (strides {frames.stride()})")
+    return layout, F_, H, W, row, (frames.stride(0) if F_ > 1 else frame)
+
+
+def _draw_style(a, trail, radius, half_width, alpha, max_jump, who: str) -> None:
+    trail, radius, half_width, max_jump = int(trail), int(radius), int(half_width), int(max_jump)
+    D = L.Draw
+    if not (0 <= trail <= D.TRAIL_MAX and 1 <= radius <= D.RADIUS_MAX and 0 <= half_width <= D.HALF_WIDTH_MAX and 1 <= max_jump <= D.JUMP_MAX):
+        raise ValueError(f"{who}: trail must lie in 0..{D.TRAIL_MAX}, radius in 1..{D.RADIUS_MAX}, half_width in 0..{D.HALF_WIDTH_MAX}, "
+                         f"max_jump in 1..{D.JUMP_MAX}")
+    alpha = default_alpha(trail) if alpha is None else [int(v) for v in alpha]
+    if len(alpha) < trail + 1 or any(not 0 <= v <= 255 for v in alpha):
+        raise ValueError(f"{who}: alpha must hold trail + 1 = {trail + 1} values in 0..255 (alpha[0]: the marks)")
+    a.trail, a.radius, a.half_width, a.max_jump, a.reserved = trail, radius, half_width, max_jump, 0
+    for k in range(trail + 1):
+        a.alpha[k] = alpha[k]
+
+
+def _draw_launch(a, frames: torch.Tensor, out: Optional[torch.Tensor], layout: Optional[str], who: str) -> torch.Tensor:
+    """Fills the surface fields of ctk_draw_args from `frames` (and `out`), then the two launches of ctk_draw_tracks."""
+    geo = _draw_surface(frames, layout, who)
+    a.layout = L.INGEST_HWC if geo[0] == "hwc" else L.INGEST_CHW
+    _, a.F, a.H, a.W, a.row_stride, a.frame_stride = geo
+    if out is None or out is frames:
+        a.src, a.dst, out = None, _ptr(frames), frames
+    else:
+        if out.device != frames.device or out.shape != frames.shape or _draw_surface(out, geo[0], who) != geo:
+            raise ValueError(f"{who}: out must be uint8 frames of the shape, strides and device of `frames`")
+        a.src, a.dst = _ptr(frames), _ptr(out)
+    ws = _draw_workspace(_query_bytes("ctk_draw_tracks_workspace_bytes", C.byref(a)), frames.device)
+    L.check(L.load().ctk_draw_tracks(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_draw_tracks")
+    return out
+
+
+def draw_tracks(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor, colors: Optional[torch.Tensor] = None, *,
+                trail: int = 0, radius: int = 4, half_width: int = 1, alpha=None, max_jump: int = 256, first_frame: int = 0,
+                scale=(1.0, 1.0), first_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                layout: Optional[str] = None) -> torch.Tensor:
+    """Marks and fading trails of tracked points drawn onto uint8 frames on the device by two launches and without a wait
+    (ctk_draw_tracks; include/ctk.h and csrc/draw_math.h have the rules) -- what the reference does on the host in
+    cotracker/utils/visualizer.py.  Works on any result of any predictor here, offline ones included.
+
+    frames   uint8 [F,H,W,3] or [F,3,H,W] on the device, drawn IN PLACE unless `out` (same shape and strides) is given; the strides
+             are taken from the tensor and the layout is inferred as ingest_frames does it.  Picture j shows frame first_frame + j.
+    tracks   float32 [T,N,2] or [G,T,N,2], pixels = rint(tracks * scale); visible bool / uint8 [T,N] or [G,T,N].
+    colors   uint8 [N,3] or [G,N,3]; default rainbow_colors of the points' y on their first row (first_row, else frame 0).
+    A visible point is a disc of `radius`, an invisible one a ring; segment k = 1..trail joins frames f-k and f-k+1 where both are
+    visible and no more than max_jump pixels apart, `half_width` pixels to each side, blended with alpha[k] (default: the
+    quadratic fade default_alpha(trail); alpha[0]: the marks).  first_row int [N] / [G,N]: nothing of a point is drawn below that
+    frame (INT32_MAX: never).  Returns the drawn frames (`frames` itself, or `out`)."""
+    who = "draw_tracks"
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
+            tracks.shape[-1] == 2):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
+    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
+    G, T, N, _ = tracks.shape
+    dev = tracks.device
+    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
+            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
+        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
+    visible = visible.reshape(G, T, N)
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
+        raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+    F_, first_frame = frames.shape[0], int(first_frame)
+    if first_frame < 0 or first_frame + F_ > T:
+        raise ValueError(f"{who}: pictures of frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    a = L.Draw.Args()
+    _draw_style(a, trail, radius, half_width, alpha, max_jump, who)
+    if first_row is not None:
+        big = torch.iinfo(torch.int32).max  # (an int64 table marks an empty slot with its own maximum: clamped, not wrapped)
+        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
+    if colors is None:
+        at = torch.zeros(G, 1, N, dtype=torch.long, device=dev) if first_row is None else first_row.long().clamp(0, T - 1)[:, None]
+        colors = rainbow_colors(tracks[..., 1].gather(1, at)[:, 0])
+    if not (isinstance(colors, torch.Tensor) and colors.dtype == torch.uint8 and colors.numel() == G * N * 3 and colors.shape[-1] == 3):
+        raise ValueError(f"{who}: colors must be a uint8 tensor [{N},3] or [{G},{N},3]")
+    colors = colors.to(dev).reshape(G, N, 3).contiguous()
+    if F_ + a.trail > T:  # the C-ABI keeps F + trail <= R (rows of a ring must not alias): rows that no picture reads are appended
+        pad = F_ + a.trail - T
+        tracks = torch.cat([tracks, tracks.new_zeros(G, pad, N, 2)], dim=1)
+        visible = torch.cat([visible, visible.new_zeros(G, pad, N)], dim=1)
+    tracks, visible = tracks.contiguous(), visible.contiguous()
+    a.G, a.N, a.N_out, a.R, a.f0 = G, N, N, tracks.shape[1], first_frame
+    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
+    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
+    a.first_row, a.colors = _ptr(first_row), _ptr(colors)
+    return _draw_launch(a, frames, out, layout, who)
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -861,6 +1017,49 @@ class StreamGroups:
         a.lost, a.cell, a.cover = _ptr(lost), _ptr(cell), _ptr(cover)
         L.check(L.load().ctk_stream_health(C.byref(a), _stream()), "ctk_stream_health")
         return lost, cell, cover
+
+    def draw(self, frames: torch.Tensor, f0: int, colors: torch.Tensor, *, N_out: Optional[int] = None, scale=(1.0, 1.0),
+             thresh: float = 0.6, first_row: Optional[torch.Tensor] = None, trail: int = 8, radius: int = 4, half_width: int = 1,
+             alpha=None, max_jump: int = 256, out: Optional[torch.Tensor] = None, layout: Optional[str] = None,
+             group: Optional[int] = None) -> torch.Tensor:
+        """The first N_out points of every group (or of `group` alone) drawn onto uint8 frames straight from the stream's own
+        history and logits -- no emit in between --, by the two launches of ctk_draw_tracks (draw_tracks has the picture): picture j
+        of `frames` shows frame f0 + j, visibility is emit's sigmoid(vis) * sigmoid(conf) > thresh, positions are history coords *
+        scale (emit's multiplication).  colors uint8 [G,N,3] and first_row int32 [G,N] (what emit takes) on the device, over all N
+        slots.  The frames f0 - trail .. f0 + F - 1 (those >= 0) must be among the committed ones the history still holds:
+        ValueError otherwise.  No wait."""
+        who = "draw"
+        N_out = self.N if N_out is None else int(N_out)
+        if not 1 <= N_out <= self.N:
+            raise ValueError(f"{who}: N_out must lie in [1, {self.N}]")
+        if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
+            raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+        a = L.Draw.Args()
+        _draw_style(a, trail, radius, half_width, alpha, max_jump, who)
+        f0, F_, dev = int(f0), frames.shape[0], self.queries.device
+        if f0 < 0 or f0 + F_ > self.committed:
+            raise ValueError(f"{who}: pictures of frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
+        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
+        if max(f0 - a.trail, 0) < oldest:
+            raise ValueError(f"{who}: frames [{f0 - a.trail}, {f0 + F_}) with their trail have left the history: it holds the last "
+                             f"{self.T_cap} of {self.committed} frames")
+        if F_ + a.trail > self.T_cap:  # (ctk_draw_tracks keeps F + trail <= R: the rows of a ring must not alias)
+            raise ValueError(f"{who}: {F_} pictures with a trail of {a.trail} need more than the {self.T_cap} history rows one call may "
+                             f"span: draw fewer frames per call")
+        g0, G = (0, self.G) if group is None else (int(group), 1)
+        if not 0 <= g0 < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        for name, t_, dt, shape in (("colors", colors, torch.uint8, (self.G, self.N, 3)), ("first_row", first_row, torch.int32, (self.G, self.N))):
+            if t_ is None and name == "first_row":
+                continue
+            if not isinstance(t_, torch.Tensor) or t_.dtype != dt or tuple(t_.shape) != shape or t_.device != dev or not t_.is_contiguous():
+                raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        a.G, a.N, a.N_out, a.R, a.f0 = G, self.N, N_out, self.T_cap, f0
+        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
+        a.visible, a.colors = None, _ptr(colors[g0:])
+        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        return _draw_launch(a, frames, out, layout, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -266,6 +266,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         # chunk (forward) or of the push buffer (push_frames), for replenish(seeds="corners").  Valid until the next completed step:
         # a partial push only writes buffer rows below it.
         self._newest_frame = None
+        self._colors = None  # draw(): (queries, _first_row, default colours [G,N_model,3]) as they stood when the colours were made
         # Not a reference kwarg (set it after construction; forward's signature is the reference's): how a first step with
         # grid_size = g and no queries places its g * g points.  "grid": the reference lattice.  "corners": a uniform g x g partition
         # of the picture, every cell taking its best-textured pixel (ops.seed_points) on frame grid_query_frame of the resized
@@ -482,6 +483,63 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             raise ValueError(f"recent: n must lie in [1, {min(done, gs.ring_rows)}] (frames so far: {done}, history_frames: "
                              f"{gs.ring_rows})")
         return self._emit_result(done - n, done)
+
+    def _draw_colors(self, gs):
+        """Default colours of draw(): ops.rainbow_colors over the y of every slot's query -- the point's position on its first row --,
+        uint8 [G,N_model,3] on the device, read from the resident query table of the stream state `gs` that draw() has validated
+        (any stream on the device state: slots or not, running or just closed).  Rebuilt only when the query table changed: a first
+        step replaces self.queries, add / remove / replenish replace self._first_row."""
+        held = getattr(self, "_colors", None)
+        if held is None or held[0] is not self.queries or held[1] is not self._first_row:
+            from . import ops
+            held = self._colors = (self.queries, self._first_row, ops.rainbow_colors(gs.queries.reshape(gs.G, gs.N, 3)[..., 2]))
+        return held[2]
+
+    @torch.no_grad()
+    def draw(self, frames, first_frame=None, trail=8, radius=4, half_width=1, colors=None, out=None, group=None):
+        """Not in the reference, whose cotracker/utils/visualizer.py draws on the host: the N (+ spare_points) user-visible points
+        of the running stream drawn onto `frames` -- raw-video resolution, uint8, [F,H,W,3] or [F,3,H,W] (or one frame), on the
+        device -- in place (or into `out`), by two launches and without a wait (ops.StreamGroups.draw: the stream's own history and
+        logits, no emit in between).  Picture j shows frame first_frame + j; default: the newest F tracked frames.  A point that
+        the returned visibility calls visible (visibility * confidence > 0.6, at or above its slot's first row) is a disc of
+        `radius` pixels, any other tracked one a ring; `trail` segments of `half_width` join the visible positions of the frames
+        before, fading quadratically.  colors: uint8 [N,3] or [G,N,3] for the user-visible points; default a rainbow over the
+        points' query y, rebuilt only when add_queries / remove_queries / replenish changed the query table.  group: one query set
+        only (default: all, drawn in order).  ValueError when first_frame - trail has left the ring (history_frames) or the
+        pictures lie beyond what has been tracked.  Returns the drawn frames."""
+        if self.v2:
+            raise NotImplementedError("CoTracker2 keeps no stream state on the device: draw on a v2 predictor is not implemented")
+        gs = getattr(self.model, "_gstream", None)
+        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+            raise ValueError("draw: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
+        one = frames.dim() == 3
+        if one:
+            frames = frames[None]
+            out = out[None] if out is not None else None
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
+        if not (hwc or chw):
+            raise ValueError(f"draw: expected {H} x {W} frames, [F,{H},{W},3] or [F,3,{H},{W}]; got {tuple(frames.shape)}")
+        done, F_ = gs.committed, frames.shape[0]
+        first_frame = done - F_ if first_frame is None else int(first_frame)
+        if first_frame < 0 or first_frame + F_ > done:
+            raise ValueError(f"draw: pictures of frames [{first_frame}, {first_frame + F_}) lie beyond what has been tracked ({done} frames)")
+        G, Nm = self.queries.shape[:2]
+        dev = self.queries.device
+        if colors is None:
+            colors = self._draw_colors(gs)
+        else:
+            c = torch.as_tensor(colors)
+            if c.dtype != torch.uint8 or c.shape[-1] != 3 or c.numel() not in (self.N * 3, G * self.N * 3):
+                raise ValueError(f"draw: colors must be uint8 [{self.N},3] or [{G},{self.N},3]")
+            colors = torch.zeros(G, Nm, 3, dtype=torch.uint8, device=dev)
+            colors[:, :self.N] = c.to(dev).reshape(-1, self.N, 3)
+        res = self.model.stream_draw(frames, first_frame, colors, N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
+                                     first_row=self._emit_first_row(), trail=trail, radius=radius, half_width=half_width, out=out,
+                                     layout="hwc" if hwc and not chw else ("chw" if chw and not hwc else None), group=group)
+        return res[0] if one else res
 
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and

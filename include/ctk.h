@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_draw_tracks and ctk_draw_tracks_workspace_bytes on the
+ *       new struct ctk_draw_args: marks and fading trails of the tracked points drawn onto uint8 frames on the device, by integer
+ *       rules (csrc/draw_math.h); two launches, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_seed_points on the new struct ctk_seed_args: the
  *       best-textured pixel (integer corner score of the luminance) of every cell of a grid over one model-resolution frame -- where a
  *       stream should put a new point; one launch, integers only.
@@ -492,6 +495,67 @@ typedef struct ctk_ingest_args {
   float* dst;
 } ctk_ingest_args;
 int ctk_ingest_frames(const ctk_ingest_args* a, void* stream);
+
+/* ---- draw tracks: the picture of what is tracked, on the device ------------------------------------------------------------------
+ * Replaces, for a caller whose frames and tracks are on the device, cotracker/utils/visualizer.py (draw_tracks_on_video: video and
+ * tracks to the host, then a PIL loop over frames x points x trail segments).  The reference's rasterisation cannot be pinned bit for
+ * bit; the rules here are integer arithmetic stated once in csrc/draw_math.h, and the result depends on them alone:
+ *   history    hist_coords [G,R,N,2] (and hist_vis / hist_conf [G,R,N]), the row of frame f is f % R as in ctk_stream_emit: a linear
+ *              history, a ring, or a plain result tensor [T,N,2] with R = T.  Picture j of F shows frame f0 + j.
+ *   position   v = x * sx (y * sy), one float32 multiplication; valid iff both components lie in -65536 .. 65536 (a NaN or an infinity
+ *              does not); pixel q = (int)rintf(v), round half to even
+ *   shown      frame f of slot (g, n): f >= 0, f >= first_row[g, n] (optional int32 [G,N]; INT32_MAX: an empty slot, of which nothing is
+ *              drawn) and a valid position
+ *   visible    visible[g, f % R, n] != 0 (uint8 [G,R,N]) when `visible` is given; otherwise sigmoid(vis) * sigmoid(conf) > thresh,
+ *              ctk_stream_emit's expression bit for bit (a NaN logit: not visible)
+ *   mark       of slot (g, n) on picture frame f, iff the frame is shown; d2 = squared pixel distance to q.  Visible: the disc
+ *              d2 <= r*r + r; not visible: the ring (r-1)*(r-1) + (r-1) < d2 <= r*r + r            (r = radius)
+ *   segment    k = 1 .. trail of slot (g, n) on picture frame f joins A = frame f - k to B = frame f - k + 1, iff both frames are
+ *              shown AND visible and |Bx - Ax| <= max_jump and |By - Ay| <= max_jump.  With d = B - A, p = P - A, dd = d.d, t = p.d,
+ *              w2 = hw*hw + hw (hw = half_width): t <= 0: p.p <= w2; t >= dd: |p - d|^2 <= w2; otherwise cross(p, d)^2 <= w2 * dd
+ *   blend      out = (v * (255 - a) + c * a + 127) / 255 per channel, c = colors[g, n], a = alpha[k] (alpha[0]: the marks)
+ *   order      a pixel = the source pixel with, first, every segment that covers it blended in for k = trail down to 1, inside that g
+ *              ascending, inside that n ascending; then the marks, g ascending, n ascending.  Nothing else: no scheduling, no atomics.
+ *   frames     dst (and the optional src: NULL = in place) uint8, F pictures of H x W pixels, layout and strides (in elements)
+ *              exactly as ctk_ingest_args: CTK_INGEST_HWC element (j, y, x, c) at j * frame_stride + y * row_stride + x * 3 + c,
+ *              CTK_INGEST_CHW element (j, c, y, x) at j * frame_stride + (c * H + y) * row_stride + x; src and dst share the strides.
+ *              A pitch-aligned surface or a crop needs no copy: bytes of a row beyond W pixels are neither read nor written.  In place,
+ *              only changed pixels' 4-pixel groups are written; with src every pixel of dst is.
+ * Only the first N_out <= N slots of a group are drawn.  Two launches on `stream` (a table of F * (trail + 1) * G * N_out primitive
+ * records in draw order into `workspace`, then one workgroup per pixel tile), no host synchronisation, capture-safe; writes dst and
+ * the workspace only.  Before any launch: NULL a, hist_coords, colors, dst or workspace, `visible` NULL with hist_vis or hist_conf NULL:
+ * CTK_E_NULL; G, N, N_out, R or F <= 0, N_out > N, F + trail > R, f0 < 0, f0 + F > 2^30, F > 65535, H or W outside
+ * 1..CTK_INGEST_MAX_SIDE, an unknown layout, row_stride smaller than a row (3 W or W), frame_stride smaller than a frame (H or 3 H
+ * rows), G > 65535, G * N > 2^26, a NaN thresh without `visible`, trail outside 0..64, radius outside 1..32, half_width outside 0..16,
+ * max_jump outside 1..4095, reserved != 0, workspace_bytes below what ctk_draw_tracks_workspace_bytes answers: CTK_E_SHAPE; workspace
+ * not 16-byte aligned, hist_coords not 8-byte aligned: CTK_E_ALIGN.  The query checks the same shapes and no pointer of the struct. */
+typedef struct ctk_draw_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are drawn (the first N_out)                 */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* picture j shows frame f0 + j, 0 <= j < F                          */
+  int32_t trail;              /* segments per point and picture, 0..64                             */
+  int32_t radius;             /* marks, 1..32                                                      */
+  int32_t half_width;         /* segments, 0..16                                                   */
+  int32_t max_jump;           /* a segment longer than this along x or y is not drawn, 1..4095     */
+  float sx, sy;               /* pixel = rint(history coords * (sx, sy))                           */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t layout;             /* CTK_INGEST_HWC / CTK_INGEST_CHW                                   */
+  int32_t H, W;
+  int32_t reserved;           /* 0 */
+  uint8_t alpha[65];          /* alpha[0]: marks; alpha[k]: segment k                              */
+  int64_t frame_stride;       /* elements between two pictures                                     */
+  int64_t row_stride;         /* elements between two pixel rows                                   */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const uint8_t* colors;      /* [G,N,3] */
+  const uint8_t* src;         /* optional: NULL = in place                                         */
+  uint8_t* dst;
+} ctk_draw_args;
+int ctk_draw_tracks_workspace_bytes(const ctk_draw_args* a, size_t* out_bytes);
+int ctk_draw_tracks(const ctk_draw_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
