@@ -185,6 +185,25 @@ class Draw:
         ]
 
 
+class Motion:
+    """Holder of ctk_fit_motion_args (include/ctk.h, "fit motion"), nested like StreamEmit.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_motion_cabi.py."""
+
+    TRANSLATION, SIMILARITY = 0, 1
+    POINTS_MAX, HYPOTHESES_MAX = 8192, 4096
+
+    class Args(C.Structure):
+        """ctk_fit_motion_args: history rows -> per frame a 2 x 3 motion matrix, an inlier mark per point and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("lag", C.c_int32), ("model", C.c_int32), ("K", C.c_int32), ("seed", C.c_uint32),
+            ("tol", C.c_float), ("min_base", C.c_float), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("motion", _fp), ("inlier", _fp), ("stats", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -264,6 +283,8 @@ SYMBOLS = {
     "ctk_ingest_frames": (C.c_int, [_P(IngestArgs), _fp]),
     "ctk_draw_tracks_workspace_bytes": (C.c_int, [_P(Draw.Args), _P(C.c_size_t)]),
     "ctk_draw_tracks": (C.c_int, [_P(Draw.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_motion_workspace_bytes": (C.c_int, [_P(Motion.Args), _P(C.c_size_t)]),
+    "ctk_fit_motion": (C.c_int, [_P(Motion.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

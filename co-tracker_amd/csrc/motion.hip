@@ -1,0 +1,241 @@
+// Camera motion per frame on the device (include/ctk.h, "fit motion"): a robust fit of a translation or a similarity to the motion of
+// the tracked points from frame f - lag to frame f, and the points that do not follow it, by the integer rules stated once in
+// motion_math.h.  One launch, no atomics, no fill; every output element is one plain store.
+//
+// One workgroup of 256 threads owns one (group, frame):
+// 1. stage    the two history rows are gathered once, in chunks of 256 slots, one slot per thread.  The threads whose slot is a
+//             correspondence take their place m in an LDS list by a wave ballot and a prefix count (wave totals through LDS), which
+//             keeps the slots' order: the numbering m is part of the rule.  A point is (Px, Py, Qx, Qy) int32, 16 bytes: the list of
+//             N_out <= 8192 slots is dynamic LDS, 128 KiB at most.  A thread remembers which of its slots (one per chunk, 32 at most)
+//             are in the list as one bit each, and the list place of every (chunk, wave) stays in LDS for step 3.
+// 2. score    a lane takes one hypothesis (K beyond 256: further rounds) and walks m = 0 .. M - 1, every lane reading the same LDS
+//             address (a broadcast), counting inliers in a register; the keys are reduced by a wave shuffle and through LDS.
+// 3. refit    every thread rebuilds the winner from its key, and the chunks are walked once more: a slot's list place comes from its
+//             bit, a ballot and the kept (chunk, wave) place -- nothing is gathered twice.  `inlier` is written here, -1 included, and
+//             the eight int64 sums are reduced by wave shuffles and through LDS (integer adds: the order does not matter).  Thread 0
+//             divides and writes the matrix and the stats.
+#include "ctk_common.h"
+#include "ctk_profile.h"
+#include "motion_math.h"
+
+namespace {
+
+constexpr int MOTION_CHUNK = 256;
+constexpr int MOTION_CHUNKS_MAX = CTK_MOTION_POINTS_MAX / MOTION_CHUNK;  // 32: one bit each in a thread's register
+
+struct MotionParams {
+  int G, N, N_out, R, f0, lag, K, T;
+  uint32_t seed;
+  int64_t base2;
+  float sx, sy, thresh;
+  const float* hc;
+  const uint8_t* visible;
+  const float* hv;
+  const float* hf;
+  const int32_t* first_row;
+  float* motion;
+  int8_t* inlier;
+  int32_t* stats;
+};
+
+__device__ __forceinline__ int64_t motion_wave_max(int64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int64_t w = __shfl_xor((long long)v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ int64_t motion_wave_sum(int64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
+  return v;
+}
+
+// the winner (or any hypothesis) rebuilt from its number
+template <int MODEL>
+__device__ __forceinline__ bool motion_make_hyp(const MotionParams& p, const int4* pts, int f, int k, int M, CtkMotionHyp* h) {
+  int i, j;
+  ctk_motion_sample(p.seed, f, k, M, MODEL, &i, &j);
+  const int4 a = pts[i], b = pts[j];
+  return ctk_motion_hyp(MODEL, a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, p.T, p.base2, h);
+}
+
+// grid: x = frame f0 + x, y = group; dynamic LDS: N_out * 16 bytes
+template <int MODEL>
+__global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
+  extern __shared__ int4 pts[];
+  __shared__ int chunk_place[MOTION_CHUNKS_MAX][4];
+  __shared__ int wave_hits[4];
+  __shared__ int64_t wave_key[4];
+  __shared__ int64_t wave_sum[4][CTK_MS_COUNT];
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.f0 + pic, fs = f - p.lag;
+  const long g = (long)blockIdx.y;
+  const long row_q = (g * p.R + f % p.R) * p.N;
+  const long row_p = fs >= 0 ? (g * p.R + fs % p.R) * p.N : 0;
+
+  // 1. stage
+  uint32_t mine = 0;
+  int M = 0;
+  for (int c = 0, c0 = 0; c0 < p.N_out; c0 += MOTION_CHUNK, ++c) {
+    const int n = c0 + tid;
+    bool hit = false;
+    int4 pt = make_int4(0, 0, 0, 0);
+    if (n < p.N_out && fs >= 0) {
+      const int first = p.first_row != nullptr ? p.first_row[g * p.N + n] : 0;
+      if (fs >= first) {  // (f > fs: frame f is at or above the first row too)
+        const float2 hp = *reinterpret_cast<const float2*>(p.hc + (row_p + n) * 2);
+        const float2 hq = *reinterpret_cast<const float2*>(p.hc + (row_q + n) * 2);
+        const bool ok0 = ctk_motion_quant(hp.x, p.sx, &pt.x), ok1 = ctk_motion_quant(hp.y, p.sy, &pt.y);
+        const bool ok2 = ctk_motion_quant(hq.x, p.sx, &pt.z), ok3 = ctk_motion_quant(hq.y, p.sy, &pt.w);
+        if (ok0 && ok1 && ok2 && ok3) {
+          if (p.visible != nullptr) hit = p.visible[row_p + n] != 0 && p.visible[row_q + n] != 0;
+          else hit = ctk_draw_visible(p.hv[row_p + n], p.hf[row_p + n], p.thresh) && ctk_draw_visible(p.hv[row_q + n], p.hf[row_q + n], p.thresh);
+        }
+      }
+    }
+    const unsigned long long mask = __ballot(hit);
+    if (lane == 0) wave_hits[wave] = __popcll(mask);
+    __syncthreads();
+    int before = M, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int h = wave_hits[w];
+      before += w < wave ? h : 0;
+      total += h;
+    }
+    if (lane == 0) chunk_place[c][wave] = before;
+    if (hit) {
+      pts[before + __popcll(mask & below)] = pt;
+      mine |= 1u << c;
+    }
+    M += total;
+    __syncthreads();  // the list is read, and wave_hits written again, only behind it
+  }
+
+  // 2. score
+  int64_t best = -1;
+  if (M >= (MODEL == CTK_MOTION_SIMILARITY ? 2 : 1)) {
+    for (int k = tid; k < p.K; k += MOTION_CHUNK) {
+      CtkMotionHyp h;
+      if (!motion_make_hyp<MODEL>(p, pts, f, k, M, &h)) continue;
+      int count = 0;
+      for (int m = 0; m < M; ++m) {
+        const int4 q = pts[m];
+        count += ctk_motion_inlier(MODEL, h, q.x, q.y, q.z, q.w) ? 1 : 0;
+      }
+      const int64_t key = ctk_motion_key(count, k, p.K);
+      best = key > best ? key : best;
+    }
+  }
+  best = motion_wave_max(best);
+  if (lane == 0) wave_key[wave] = best;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 4; ++w) best = wave_key[w] > best ? wave_key[w] : best;
+
+  // 3. refit
+  const bool have = best >= 0;
+  CtkMotionHyp hb;
+  hb.px = hb.py = hb.qx = hb.qy = 0, hb.D = hb.A = hb.B = hb.TD = 0;
+  if (have) motion_make_hyp<MODEL>(p, pts, f, ctk_motion_key_k(best, p.K), M, &hb);
+  int64_t s[CTK_MS_COUNT];
+#pragma unroll
+  for (int i = 0; i < CTK_MS_COUNT; ++i) s[i] = 0;
+  int8_t* inl = p.inlier + (g * F + pic) * (long)p.N_out;
+  for (int c = 0, c0 = 0; c0 < p.N_out; c0 += MOTION_CHUNK, ++c) {
+    const int n = c0 + tid;
+    const bool hit = (mine >> c) & 1u;
+    const unsigned long long mask = __ballot(hit);
+    if (n < p.N_out) {
+      int8_t v = -1;
+      if (hit) {
+        const int4 q = pts[chunk_place[c][wave] + __popcll(mask & below)];
+        const bool in = have && ctk_motion_inlier(MODEL, hb, q.x, q.y, q.z, q.w);
+        if (in) ctk_motion_accumulate(s, q.x, q.y, q.z, q.w);
+        v = in ? 1 : 0;
+      }
+      inl[n] = v;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < CTK_MS_COUNT; ++i) {
+    const int64_t t = motion_wave_sum(s[i]);
+    if (lane == 0) wave_sum[wave][i] = t;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < CTK_MS_COUNT; ++i) s[i] = wave_sum[0][i] + wave_sum[1][i] + wave_sum[2][i] + wave_sum[3][i];
+    float row[6];
+    if (have) ctk_motion_refit(MODEL, s, row);
+    else ctk_motion_identity(row);
+    float* mo = p.motion + (g * F + pic) * 6;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) mo[i] = row[i];
+    int32_t* st = p.stats + (g * F + pic) * 4;
+    st[0] = M, st[1] = have ? (int)s[CTK_MS_N] : 0, st[2] = have ? ctk_motion_key_k(best, p.K) : -1, st[3] = 0;
+  }
+}
+
+// everything but the pointers
+int motion_check_shape(const ctk_fit_motion_args* a) {
+  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->R <= 0 || a->F <= 0 || a->N_out > a->N || a->N_out > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
+  if (a->lag < 1 || (long)a->F + a->lag > a->R || a->f0 < 0 || (long)a->f0 + a->F > (1L << 30) || a->F > 65535) return CTK_E_SHAPE;
+  if (a->G > 65535 || (long)a->G * a->N > (1L << 26) || a->reserved != 0) return CTK_E_SHAPE;
+  if (a->model != CTK_MOTION_TRANSLATION && a->model != CTK_MOTION_SIMILARITY) return CTK_E_SHAPE;
+  if (a->K < 1 || a->K > CTK_MOTION_HYPOTHESES_MAX) return CTK_E_SHAPE;
+  if (ctk_motion_tol(a->tol) == 0 || ctk_motion_base2(a->min_base) < 0) return CTK_E_SHAPE;
+  if (!(a->sx > 0.0f && a->sx <= 3.402823466e+38f) || !(a->sy > 0.0f && a->sy <= 3.402823466e+38f)) return CTK_E_SHAPE;
+  if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
+  return CTK_OK;
+}
+
+template <int MODEL>
+void motion_launch(const MotionParams& p, int F, hipStream_t s) {
+  const size_t lds = (size_t)p.N_out * sizeof(int4);
+  // (beyond 64 KiB of dynamic LDS a kernel has to say so once; not a stream operation)
+  if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_motion_kernel<MODEL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             CTK_MOTION_POINTS_MAX * (int)sizeof(int4));
+  hipLaunchKernelGGL((fit_motion_kernel<MODEL>), dim3((unsigned)F, (unsigned)p.G), dim3(256), lds, s, p);
+}
+
+}  // namespace
+
+extern "C" int ctk_fit_motion_workspace_bytes(const ctk_fit_motion_args* a, size_t* out_bytes) {
+  if (!a || !out_bytes) return CTK_E_NULL;
+  const int rc = motion_check_shape(a);
+  if (rc != CTK_OK) return rc;
+  *out_bytes = 0;  // the one-launch form keeps everything in LDS
+  return CTK_OK;
+}
+
+extern "C" int ctk_fit_motion(const ctk_fit_motion_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!a) return CTK_E_NULL;
+  if (!a->hist_coords || !a->motion || !a->inlier || !a->stats) return CTK_E_NULL;
+  if (!a->visible && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
+  const int rc = motion_check_shape(a);
+  if (rc != CTK_OK) return rc;
+  size_t need = 0;
+  ctk_fit_motion_workspace_bytes(a, &need);
+  if (workspace_bytes < need || (need > 0 && !workspace)) return CTK_E_SHAPE;
+  if ((reinterpret_cast<uintptr_t>(a->hist_coords) & 7u) != 0) return CTK_E_ALIGN;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+
+  MotionParams p;
+  p.G = a->G, p.N = a->N, p.N_out = a->N_out, p.R = a->R, p.f0 = a->f0, p.lag = a->lag, p.K = a->K;
+  p.T = ctk_motion_tol(a->tol), p.base2 = ctk_motion_base2(a->min_base), p.seed = a->seed;
+  p.sx = a->sx, p.sy = a->sy, p.thresh = a->thresh;
+  p.hc = a->hist_coords, p.visible = a->visible, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
+  p.motion = a->motion, p.inlier = a->inlier, p.stats = a->stats;
+  {
+    CtkProfScope prof("fit_motion", 0.0, (double)a->G * a->F * a->N_out * 33.0, s);
+    if (a->model == CTK_MOTION_SIMILARITY) motion_launch<CTK_MOTION_SIMILARITY>(p, a->F, s);
+    else motion_launch<CTK_MOTION_TRANSLATION>(p, a->F, s);
+  }
+  CTK_HIP_CHECK_LAUNCH();
+  return CTK_OK;
+}

@@ -406,6 +406,97 @@ def draw_tracks(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tenso
     return _draw_launch(a, frames, out, layout, who)
 
 
+# ------------------------------------------------------------------------------------------
+# fit motion (csrc/motion.hip; include/ctk.h, "fit motion")
+# ------------------------------------------------------------------------------------------
+_motion_ws_cache = {}
+MOTION_MODELS = {"translation": L.Motion.TRANSLATION, "similarity": L.Motion.SIMILARITY}
+
+
+def _motion_workspace(nbytes: int, device) -> torch.Tensor:
+    """The workspace of ctk_fit_motion, cached per device like _draw_workspace and for the same reason a cache of its own: captured
+    window graphs bake the address of _workspace in, and a motion call must never be the reason it moves."""
+    key = (device.index if device.index is not None else torch.cuda.current_device())
+    buf = _motion_ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _motion_ws_cache[key] = None
+        buf = _motion_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
+    return buf
+
+
+def _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who: str) -> None:
+    if model not in MOTION_MODELS:
+        raise ValueError(f"{who}: model must be one of {sorted(MOTION_MODELS)}, got {model!r}")
+    lag, hypotheses, seed = int(lag), int(hypotheses), int(seed)
+    if lag < 1 or not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: lag must be >= 1, hypotheses in 1..{L.Motion.HYPOTHESES_MAX}, seed in 0..2^32 - 1")
+    a.lag, a.model, a.K, a.seed, a.tol, a.min_base, a.reserved = lag, MOTION_MODELS[model], hypotheses, seed, float(tol), float(min_base), 0
+
+
+def _motion_launch(a, device, out, who: str):
+    """Allocates (or checks) the three outputs of ctk_fit_motion for the G, F, N_out of `a`, then the launch."""
+    shapes = ((a.G, a.F, 2, 3), (a.G, a.F, a.N_out), (a.G, a.F, 4))
+    dtypes = (torch.float32, torch.int8, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(sh, device=device, dtype=dt) for sh, dt in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
+                                not t_.is_contiguous() for t_, sh, dt in zip(out, shapes, dtypes)):
+            raise ValueError(f"{who}: out must be contiguous (motion float32 {list(shapes[0])}, inlier int8 {list(shapes[1])}, stats int32 "
+                             f"{list(shapes[2])}) on {device}")
+    a.motion, a.inlier, a.stats = (_ptr(t_) for t_ in out)
+    ws = _motion_workspace(_query_bytes("ctk_fit_motion_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_motion(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_motion")
+    return out
+
+
+def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, model: str = "similarity", tol: float = 2.0,
+               hypotheses: int = 128, min_base: float = 16.0, seed: int = 0, scale=(1.0, 1.0), first_frame: int = 0,
+               frames: Optional[int] = None, out=None):
+    """How the camera moved from frame f - lag to frame f, and which points moved differently: a robust fit over the tracked points,
+    per frame, by one launch and without a wait (ctk_fit_motion; include/ctk.h and csrc/motion_math.h have the rules).  Works on any
+    result of any predictor here, offline ones included.
+
+    tracks   float32 [T,N,2] or [G,T,N,2] (N <= 8192), positions = tracks * scale; visible bool / uint8 [T,N] or [G,T,N]: a point
+             counts on a frame pair when it is visible on both.
+    model    "similarity" (rotation, scale, shift) or "translation"; `hypotheses` seeded samples per frame are scored with the bound
+             `tol` (pixels, max norm) and the best one is refitted over its inliers; a similarity's sample pair is at least
+             `min_base` pixels apart.  The same seed gives the same answer for a frame however a range is cut into calls.
+    Rows are the frames first_frame .. first_frame + frames - 1 (default: to the end).  Returns (motion float32 [G,F,2,3]:
+    destination = motion @ (source, 1); inlier int8 [G,F,N]: -1 no correspondence, 0 outlier, 1 inlier; stats int32 [G,F,4] =
+    (correspondences, inliers, best hypothesis or -1, 0)) -- `out` when given.  A frame without an admissible hypothesis (among
+    them every f < lag) has the identity."""
+    who = "fit_motion"
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
+            tracks.shape[-1] == 2):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
+    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
+    G, T, N, _ = tracks.shape
+    dev = tracks.device
+    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
+            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
+        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
+    visible = visible.reshape(G, T, N)
+    if not 1 <= N <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: between 1 and {L.Motion.POINTS_MAX} points per group, got {N}")
+    first_frame = int(first_frame)
+    F_ = T - first_frame if frames is None else int(frames)
+    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
+        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    a = L.Motion.Args()
+    _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
+    if F_ + a.lag > T:  # the C-ABI keeps F + lag <= R (rows of a ring must not alias): rows that no frame reads are appended
+        pad = F_ + a.lag - T
+        tracks = torch.cat([tracks, tracks.new_zeros(G, pad, N, 2)], dim=1)
+        visible = torch.cat([visible, visible.new_zeros(G, pad, N)], dim=1)
+    tracks, visible = tracks.contiguous(), visible.contiguous()
+    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N, tracks.shape[1], first_frame, F_
+    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
+    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
+    return _motion_launch(a, dev, out, who)
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -1060,6 +1151,44 @@ class StreamGroups:
         a.visible, a.colors = None, _ptr(colors[g0:])
         a.first_row = None if first_row is None else _ptr(first_row[g0:])
         return _draw_launch(a, frames, out, layout, who)
+
+    def motion(self, f0: int, F: int, *, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+               first_row: Optional[torch.Tensor] = None, lag: int = 1, model: str = "similarity", tol: float = 2.0, hypotheses: int = 128,
+               min_base: float = 16.0, seed: int = 0, group: Optional[int] = None, out=None):
+        """The camera motion of frames f0 .. f0 + F - 1 (each against the frame `lag` before it) fitted to the first N_out points of
+        every group (or of `group` alone) straight from the stream's own history and logits -- no emit in between --, by the one
+        launch of ctk_fit_motion (fit_motion has the picture): visibility is emit's sigmoid(vis) * sigmoid(conf) > thresh, positions
+        are history coords * scale (emit's multiplication), tol and min_base are in those pixels.  first_row int32 [G,N] (what emit
+        takes) on the device.  The frames f0 - lag .. f0 + F - 1 (those >= 0) must be among the committed ones the history still
+        holds: ValueError otherwise.  -> (motion [G,F,2,3], inlier [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
+        who = "motion"
+        N_out = self.N if N_out is None else int(N_out)
+        if not 1 <= N_out <= min(self.N, L.Motion.POINTS_MAX):
+            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Motion.POINTS_MAX)}]")
+        a = L.Motion.Args()
+        _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
+        f0, F_, dev = int(f0), int(F), self.queries.device
+        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
+            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
+        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
+        if max(f0 - a.lag, 0) < oldest:
+            raise ValueError(f"{who}: frames [{f0 - a.lag}, {f0 + F_}) with their lag have left the history: it holds the last "
+                             f"{self.T_cap} of {self.committed} frames")
+        if F_ + a.lag > self.T_cap:  # (ctk_fit_motion keeps F + lag <= R: the rows of a ring must not alias)
+            raise ValueError(f"{who}: {F_} frames with a lag of {a.lag} need more than the {self.T_cap} history rows one call may "
+                             f"span: fit fewer frames per call")
+        g0, G = (0, self.G) if group is None else (int(group), 1)
+        if not 0 <= g0 < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
+                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
+            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
+        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
+        a.visible = None
+        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        return _motion_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -541,6 +541,35 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                                      layout="hwc" if hwc and not chw else ("chw" if chw and not hwc else None), group=group)
         return res[0] if one else res
 
+    @torch.no_grad()
+    def camera_motion(self, n=None, first_frame=None, lag=1, model="similarity", tol=2.0, hypotheses=128, min_base=16.0, seed=0, group=None):
+        """Not in the reference, whose cotracker/utils/visualizer.py subtracts the mean displacement of points a user mask calls
+        background, on the host: how the camera moved from frame f - lag to frame f of the running stream, fitted robustly to the N
+        (+ spare_points) user-visible points, and which points moved differently -- by one launch and without a wait
+        (ops.StreamGroups.motion: the stream's own history and logits, no emit in between).  The rows are the n frames from
+        first_frame on; default: the newest `step` frames (those tracked so far), ending at the newest; n = 1: the newest frame only.
+        A point counts on a pair of frames when the returned visibility calls it visible on both (visibility * confidence > 0.6, at
+        or above its slot's first row).  model "similarity" or "translation"; tol and min_base are raw-video pixels, as are the
+        matrices: raw-video position on frame f = motion @ (position on frame f - lag, 1).  group: one query set only.  ValueError
+        when first_frame - lag has left the ring (history_frames) or the frames lie beyond what has been tracked.  Returns
+        (motion float32 [G,n,2,3], inlier int8 [G,n,N]: -1 not on both frames, 0 moves differently, 1 moves with the camera; stats
+        int32 [G,n,4] = (points on both frames, inliers, best hypothesis or -1, 0)), on the device; a frame without a fit has the
+        identity."""
+        if self.v2:
+            raise NotImplementedError("CoTracker2 keeps no stream state on the device: camera_motion on a v2 predictor is not implemented")
+        gs = getattr(self.model, "_gstream", None)
+        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+        done = gs.committed
+        n = (min(self.step, done) if first_frame is None else done - int(first_frame)) if n is None else int(n)
+        first_frame = done - n if first_frame is None else int(first_frame)
+        if n < 1 or first_frame < 0 or first_frame + n > done:
+            raise ValueError(f"camera_motion: frames [{first_frame}, {first_frame + n}) lie beyond what has been tracked ({done} frames)")
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        return self.model.stream_motion(first_frame, n, N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
+                                        first_row=self._emit_first_row(), lag=lag, model=model, tol=tol, hypotheses=hypotheses,
+                                        min_base=min_base, seed=seed, group=group)
+
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
         everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""

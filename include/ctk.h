@@ -47,6 +47,9 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_motion and ctk_fit_motion_workspace_bytes on the
+ *       new struct ctk_fit_motion_args: per frame, a robust fit (seeded hypotheses, integer scoring) of a translation or a similarity
+ *       to the motion of the tracked points, and the points that do not follow it (csrc/motion_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_draw_tracks and ctk_draw_tracks_workspace_bytes on the
  *       new struct ctk_draw_args: marks and fading trails of the tracked points drawn onto uint8 frames on the device, by integer
  *       rules (csrc/draw_math.h); two launches, no atomics.
@@ -556,6 +559,72 @@ typedef struct ctk_draw_args {
 } ctk_draw_args;
 int ctk_draw_tracks_workspace_bytes(const ctk_draw_args* a, size_t* out_bytes);
 int ctk_draw_tracks(const ctk_draw_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit motion: how the camera moved between two frames, and which points moved differently ----------------------------------------
+ * For a caller whose tracks are on the device: the motion of frame f - lag to frame f of every group g, f in [f0, f0 + F), fitted
+ * robustly to the tracked points, and the points that do not follow it.  (cotracker/utils/visualizer.py:248-256 compensates camera
+ * motion by the mean displacement of points a user-supplied mask calls background, on the host.)  The rules are integer arithmetic
+ * stated once in csrc/motion_math.h, and the result depends on them alone:
+ *   history    hist_coords [G,R,N,2] (and hist_vis / hist_conf [G,R,N]), the row of frame f is f % R as in ctk_stream_emit: a linear
+ *              history, a ring, or a plain result tensor [T,N,2] with R = T.
+ *   position   v = x * sx (y * sy), one float32 multiplication; valid iff both components are finite and |v| <= 8192;
+ *              P = (int)rintf(v * 16.0f), 1/16 pixel (the product by 16 is exact), |P| <= 2^17
+ *   pair       slot n is a correspondence of frame f iff f - lag >= 0, f - lag >= first_row[g, n] (optional int32 [G,N]; INT32_MAX: an
+ *              empty slot), both positions are valid and both frames are visible: visible[g, f % R, n] != 0 (uint8 [G,R,N]) when
+ *              `visible` is given, otherwise sigmoid(vis) * sigmoid(conf) > thresh, ctk_stream_emit's expression bit for bit.  The M
+ *              correspondences are numbered m = 0 .. M - 1 in ascending n; P_m is the source (frame f - lag), Q_m the destination.
+ *   hypothesis k of K: mix(x) = x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32);
+ *              h0 = mix(seed ^ mix(f * 0x9e3779b9 + 2k)), h1 = mix(seed ^ mix(f * 0x9e3779b9 + 2k + 1)); i = h0 % M; j = h1 % (M - 1),
+ *              j += (j >= i).  f is the absolute frame number: a frame's answer does not depend on how a range is cut into calls.
+ *   similarity (model 1) d = P_j - P_i, e = Q_j - Q_i, D = d.d, A = d.e, B = d x e in int64 (D, |A|, |B| <= 2^37).  Admissible iff
+ *              D >= base2 = ((int64)rintf(min_base * 16))^2 and D >= 1.  With u = P_m - P_i, w = Q_m - Q_i:
+ *              rx = D w.x - (A u.x - B u.y), ry = D w.y - (B u.x + A u.y) (products <= 2^55); m is an inlier iff |rx| <= T D and
+ *              |ry| <= T D, T = (int)rintf(tol * 16) in 1..4096 (T D <= 2^49): a max-norm test of tol pixels, inside int64.
+ *   translation (model 0) only i; m is an inlier iff |w.x - u.x| <= T and |w.y - u.y| <= T; admissible whenever M >= 1.
+ *   best       the maximum of (inlier count, K - 1 - k) over the admissible hypotheses: most inliers, then the lowest k.
+ *   refit      over the inliers of the best, int64 sums n, Spx, Spy, Sqx, Sqy, Spp = sum |P|^2, Sdot = sum P.Q, Scr = sum P x Q;
+ *              den = n Spp - (Spx^2 + Spy^2), na = n Sdot - (Spx Sqx + Spy Sqy), nb = n Scr - (Spx Sqy - Spy Sqx), all below 2^63 for
+ *              n <= 8192; then in double, one IEEE operation per step: a = na / den, b = nb / den,
+ *              tx = (Sqx - (a Spx - b Spy)) / (n * 16), ty = (Sqy - (b Spx + a Spy)) / (n * 16).  Translation: a = 1, b = 0,
+ *              tx = (Sqx - Spx) / (n * 16), ty likewise.
+ *   outputs    motion float32 [G,F,2,3] = (float)[[a, -b, tx], [b, a, ty]]: destination = matrix * (source, 1), in the pixels of
+ *              the scaled positions;  inlier int8 [G,F,N_out]: -1 no correspondence, 0 outlier, 1 inlier of the best hypothesis;
+ *              stats int32 [G,F,4] = (M, inlier count, best k, 0).  With no admissible hypothesis (M < 2 for a similarity, M < 1 for
+ *              a translation, every sampled pair closer than min_base) the matrix is the identity -- not NaN: callers multiply
+ *              these up --, the stats are (M, 0, -1, 0) and the correspondences get 0.  Every element is written by one plain store.
+ * Only the first N_out <= N slots of a group are looked at.  One launch on `stream`, one workgroup per (group, frame) with the
+ * correspondences in N_out * 16 bytes of LDS; no atomics, no host synchronisation, capture-safe; writes the three outputs only.  The
+ * workspace query answers 0 (nothing is kept outside LDS) and `workspace` may then be NULL.  Before any launch: NULL a, hist_coords,
+ * motion, inlier or stats, `visible` NULL with hist_vis or hist_conf NULL: CTK_E_NULL; G, N, N_out, R or F <= 0, N_out > N,
+ * N_out > 8192, lag < 1, F + lag > R, f0 < 0, f0 + F > 2^30, F > 65535, G > 65535, G * N > 2^26, model not 0 or 1, K outside 1..4096,
+ * tol NaN or with T outside 1..4096, min_base NaN, negative or above 8192, sx or sy not finite or <= 0, a NaN thresh without
+ * `visible`, reserved != 0, workspace_bytes below what ctk_fit_motion_workspace_bytes answers: CTK_E_SHAPE; hist_coords not 8-byte
+ * aligned: CTK_E_ALIGN.  Frames with f - lag < 0 are no error: they have no correspondences.  The query checks the same shapes and
+ * no pointer of the struct. */
+typedef struct ctk_fit_motion_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t lag;                /* the motion is that of frame f - lag to frame f, >= 1              */
+  int32_t model;              /* 0 translation, 1 similarity                                       */
+  int32_t K;                  /* hypotheses per frame, 1..4096                                     */
+  uint32_t seed;
+  float tol;                  /* inlier bound, pixels (max norm); T = rint(tol * 16) in 1..4096    */
+  float min_base;             /* a similarity's sample pair is at least this far apart, pixels     */
+  float sx, sy;               /* position = history coords * (sx, sy)                              */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  float* motion;              /* [G,F,2,3] */
+  int8_t* inlier;             /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_fit_motion_args;
+int ctk_fit_motion_workspace_bytes(const ctk_fit_motion_args* a, size_t* out_bytes);
+int ctk_fit_motion(const ctk_fit_motion_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
