@@ -204,6 +204,29 @@ class Motion:
         ]
 
 
+class Warp:
+    """Holder of ctk_warp_args and ctk_smooth_path_args (include/ctk.h, "warp frames"), nested like Motion.Args and for the same reason;
+    their layouts are checked against the compiler by tests/test_warp_cabi.py."""
+
+    BORDER_FILL, BORDER_EDGE = 0, 1
+
+    class Args(C.Structure):
+        """ctk_warp_args: uint8 pictures and one 2 x 3 matrix each -> the resampled pictures."""
+        _fields_ = [
+            ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("layout", C.c_int32), ("border", C.c_int32), ("reserved", C.c_int32),
+            ("fill", C.c_uint8 * 4),
+            ("src_frame_stride", C.c_int64), ("src_row_stride", C.c_int64), ("dst_frame_stride", C.c_int64), ("dst_row_stride", C.c_int64),
+            ("matrices", _fp), ("src", _fp), ("dst", _fp),
+        ]
+
+    class PathArgs(C.Structure):
+        """ctk_smooth_path_args: per-frame camera motions and a persistent state -> the warp matrices that steady the camera."""
+        _fields_ = [
+            ("G", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("reserved", C.c_int32),
+            ("motion", _fp), ("post", _fp), ("state", _fp), ("warp", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -285,6 +308,8 @@ SYMBOLS = {
     "ctk_draw_tracks": (C.c_int, [_P(Draw.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_motion_workspace_bytes": (C.c_int, [_P(Motion.Args), _P(C.c_size_t)]),
     "ctk_fit_motion": (C.c_int, [_P(Motion.Args), _fp, C.c_size_t, _fp]),
+    "ctk_warp_frames": (C.c_int, [_P(Warp.Args), _fp]),
+    "ctk_smooth_path": (C.c_int, [_P(Warp.PathArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

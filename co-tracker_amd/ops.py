@@ -497,6 +497,156 @@ def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, mod
     return _motion_launch(a, dev, out, who)
 
 
+# ------------------------------------------------------------------------------------------
+# warp frames (csrc/warp.hip; include/ctk.h, "warp frames")
+# ------------------------------------------------------------------------------------------
+WARP_BORDERS = {"fill": L.Warp.BORDER_FILL, "edge": L.Warp.BORDER_EDGE}
+
+
+def _warp_args(frames: torch.Tensor, out: Optional[torch.Tensor], border: str, fill, layout: Optional[str], who: str):
+    """Everything of ctk_warp_args but the matrices, from `frames` and `out` (allocated dense when None) -> (args, out)."""
+    lay, F_, H, W, row, frame = _draw_surface(frames, layout, who)
+    if border not in WARP_BORDERS:
+        raise ValueError(f"{who}: border must be one of {sorted(WARP_BORDERS)}, got {border!r}")
+    fill = [int(v) for v in fill]
+    if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
+        raise ValueError(f"{who}: fill must hold three values in 0..255")
+    if out is None:
+        out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+    elif out is frames or not isinstance(out, torch.Tensor) or out.device != frames.device or out.shape != frames.shape:
+        raise ValueError(f"{who}: out must be uint8 frames of the shape and device of `frames`, and not `frames` itself (a warp cannot "
+                         f"run in place)")
+    _, _, _, _, orow, oframe = _draw_surface(out, lay, who)
+    rows, row_bytes = (H, 3 * W) if lay == "hwc" else (3 * H, W)
+    ends = [t_.data_ptr() + (F_ - 1) * fs + (rows - 1) * rs + row_bytes for t_, fs, rs in ((frames, frame, row), (out, oframe, orow))]
+    if frames.data_ptr() < ends[1] and out.data_ptr() < ends[0]:
+        raise ValueError(f"{who}: out overlaps `frames` (a warp cannot run in place)")
+    a = L.Warp.Args()
+    a.F, a.H, a.W, a.layout, a.border, a.reserved = F_, H, W, (L.INGEST_HWC if lay == "hwc" else L.INGEST_CHW), WARP_BORDERS[border], 0
+    for k in range(3):
+        a.fill[k] = fill[k]
+    a.src_frame_stride, a.src_row_stride, a.dst_frame_stride, a.dst_row_stride = frame, row, oframe, orow
+    a.src, a.dst = _ptr(frames), _ptr(out)
+    return a, out
+
+
+def _warp_launch(a, matrices: torch.Tensor, device, who: str) -> None:
+    if not (isinstance(matrices, torch.Tensor) and matrices.dtype == torch.float32 and matrices.device == device and
+            matrices.numel() == a.F * 6 and tuple(matrices.shape[-2:]) == (2, 3) and matrices.is_contiguous()):
+        raise ValueError(f"{who}: matrices must be a contiguous float32 tensor [{a.F},2,3] on {device}")
+    a.matrices = _ptr(matrices)
+    L.check(L.load().ctk_warp_frames(C.byref(a), _stream()), "ctk_warp_frames")
+
+
+def warp_frames(frames: torch.Tensor, matrices: torch.Tensor, *, out: Optional[torch.Tensor] = None, border: str = "fill",
+                fill=(0, 0, 0), layout: Optional[str] = None) -> torch.Tensor:
+    """uint8 pictures resampled under one 2 x 3 matrix each, on the device, by one launch and without a wait (ctk_warp_frames;
+    include/ctk.h and csrc/warp_math.h have the rules) -- what a caller otherwise writes as uint8 -> float, affine_grid,
+    grid_sample, round, -> uint8.
+
+    frames   uint8 [F,H,W,3] or [F,3,H,W] on the device; the strides are taken from the tensor and the layout is inferred as
+             ingest_frames does it (a pitch-aligned surface or a crop needs no copy).
+    matrices float32 [F,2,3] on the device: matrices[j] maps an OUTPUT pixel to a SOURCE position, (sx, sy) = m (x, y, 1), pixel
+             centres at integers.  A matrix that is not finite or out of range (|linear| > 8, |shift| > 32768) copies its picture.
+    border   "fill": a tap outside the picture has the value `fill` (three values 0..255); "edge": the edge pixels go on for ever.
+    out      uint8 frames of the same shape with strides of their own; must not overlap `frames`.  Default: a new dense tensor.
+    Bilinear in 1/256 pixel with Q24 coefficients: the identity copies bit for bit, an integer shift is a shifted copy.  Returns out."""
+    who = "warp_frames"
+    a, out = _warp_args(frames, out, border, fill, layout, who)
+    _warp_launch(a, matrices, frames.device, who)
+    return out
+
+
+def zoom_matrix(H: int, W: int, zoom: float) -> torch.Tensor:
+    """The float32 `post` [2,3] of smooth_path that scales by 1 / zoom about the centre of an H x W picture ((W - 1) / 2, (H - 1) / 2):
+    zoom > 1 shows the middle of the stabilised picture enlarged, which hides the border a correction uncovers.  float32 arithmetic:
+    s = 1 / zoom, t = c - s * c.  On the host."""
+    zoom = float(zoom)
+    if not (zoom > 0.0 and zoom < float("inf")):
+        raise ValueError(f"zoom_matrix: zoom must be positive and finite, got {zoom!r}")
+    s = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(zoom, dtype=torch.float32)
+    cx, cy = torch.tensor((int(W) - 1) / 2, dtype=torch.float32), torch.tensor((int(H) - 1) / 2, dtype=torch.float32)
+    zero = torch.tensor(0.0, dtype=torch.float32)
+    return torch.stack([s, zero, cx - s * cx, zero, s, cy - s * cy]).reshape(2, 3)
+
+
+def _path_state(G: int, device) -> torch.Tensor:
+    """The state of smooth_path before the first frame: the identity per group, float64 [G,6] on the device (no copy from the host)."""
+    state = torch.zeros(G, 6, dtype=torch.float64, device=device)
+    state[:, 0::4] = 1.0
+    return state
+
+
+def smooth_path(motion: torch.Tensor, state: Optional[torch.Tensor] = None, *, alpha: float = 0.1, post: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None):
+    """Per-frame camera motions (fit_motion with lag = 1) -> the matrices that steady the camera, for warp_frames, by one launch and
+    without a wait (ctk_smooth_path; include/ctk.h and csrc/warp_math.h have the rule): a causal, leaky lock-on.  With C_f the
+    cumulative camera pose and S_f = (1 - alpha) S_f-1 + alpha C_f its exponential smoothing, warp[f] = inverse(C_f) S_f.
+
+    motion   float32 [G,F,2,3] or [F,2,3] on the device; a matrix that is not finite counts as the identity.
+    state    float64 [G,6] on the device, updated IN PLACE: what the previous call for the frames just before these returned.  None:
+             the identity (the first frame of `motion` is the one locked onto).
+    alpha    0 locks onto the first frame for ever, 1 corrects nothing; a steady pan of v pixels a frame settles (1 - alpha) v / alpha
+             pixels behind.
+    post     float32 [2,3] (zoom_matrix): composed onto every output, not part of the state.
+    Returns (warp float32 of the shape of `motion` -- `out` when given --, state): a range cut into calls gives the bits of one call."""
+    who = "smooth_path"
+    if not (isinstance(motion, torch.Tensor) and motion.is_cuda and motion.dtype == torch.float32 and motion.dim() in (3, 4) and
+            tuple(motion.shape[-2:]) == (2, 3) and motion.numel() > 0):
+        raise ValueError(f"{who}: motion must be a float32 device tensor [G,F,2,3] or [F,2,3]")
+    dev, shape = motion.device, tuple(motion.shape)
+    G, F_ = (1, shape[0]) if motion.dim() == 3 else shape[:2]
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{who}: alpha must lie in [0, 1], got {alpha!r}")
+    if state is None:
+        state = _path_state(G, dev)
+    elif not (isinstance(state, torch.Tensor) and state.dtype == torch.float64 and state.device == dev and tuple(state.shape) == (G, 6) and
+              state.is_contiguous()):
+        raise ValueError(f"{who}: state must be a contiguous float64 tensor [{G},6] on {dev}")
+    if post is not None:
+        post = torch.as_tensor(post)
+        if post.dtype != torch.float32 or tuple(post.shape) != (2, 3):
+            raise ValueError(f"{who}: post must be a float32 tensor [2,3]")
+        post = post.to(dev).contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == shape and
+              out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor {list(shape)} on {dev}")
+    motion = motion.contiguous()
+    a = L.Warp.PathArgs()
+    a.G, a.F, a.alpha, a.reserved = G, F_, alpha, 0
+    a.motion, a.post, a.state, a.warp = _ptr(motion), _ptr(post), _ptr(state), _ptr(out)
+    L.check(L.load().ctk_smooth_path(C.byref(a), _stream()), "ctk_smooth_path")
+    return out, state
+
+
+def stabilize(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor, *, alpha: float = 0.1, zoom: float = 1.0,
+              border: str = "fill", fill=(0, 0, 0), out: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+              model: str = "similarity", tol: float = 2.0, hypotheses: int = 128, min_base: float = 16.0, seed: int = 0):
+    """Frames steadied by the motion of their tracked points, on the device: fit_motion(lag = 1), smooth_path, warp_frames -- three
+    launches, no wait.  Works on any result of any predictor here, offline ones included.
+
+    frames   uint8 [F,H,W,3] or [F,3,H,W] on the device; tracks float32 [F,N,2] (or [1,F,N,2]) in the pixels of the frames, visible
+             bool / uint8 [F,N]: picture j is frame j of the tracks.
+    alpha, zoom   smooth_path's alpha; zoom > 1 enlarges the middle (zoom_matrix) to hide the border a correction uncovers.
+    border, fill, out   as warp_frames;  model, tol, hypotheses, min_base, seed   as fit_motion.
+    state    smooth_path's state [1,6] of the frames just before these (None: lock onto frame 0), updated in place.
+    Returns (out, warp float32 [F,2,3]: a point at position x of frame j appears at inverse(warp[j]) x, state)."""
+    who = "stabilize"
+    if not (isinstance(tracks, torch.Tensor) and tracks.dim() in (3, 4) and (tracks.dim() == 3 or tracks.shape[0] == 1)):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [F,N,2] or [1,F,N,2]")
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 4 and frames.shape[0] == tracks.shape[-3]):
+        raise ValueError(f"{who}: frames must be uint8 [F,H,W,3] or [F,3,H,W] with one picture per tracked frame")
+    a, out = _warp_args(frames, out, border, fill, None, who)
+    post = None if float(zoom) == 1.0 else zoom_matrix(a.H, a.W, zoom).to(frames.device)
+    motion = fit_motion(tracks, visible, lag=1, model=model, tol=tol, hypotheses=hypotheses, min_base=min_base, seed=seed)[0]
+    warp, state = smooth_path(motion, state, alpha=alpha, post=post)
+    _warp_launch(a, warp, frames.device, who)
+    return out, warp[0], state
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -945,6 +1095,7 @@ class StreamGroups:
 
     _serial = 0
     ring_rows = None  # (a state pickled before the attribute existed)
+    _stab = None
 
     def __init__(self, queries: torch.Tensor, S: int, step: int, stride: float, level_sizes, ring_rows: Optional[int] = None):
         if ring_rows is not None and (int(ring_rows) != ring_rows or ring_rows < S):
@@ -974,6 +1125,7 @@ class StreamGroups:
 
     def _new_book(self) -> None:
         self.committed, self.next_ind = 0, 0
+        self._stab = {}  # stabilize(): {group: (next frame, state tensor [1,6], alpha, ((H, W, zoom), post tensor or None))}
         self._occupied = None  # read from the query table when it is first asked for: the calls of a stream never wait for it
         self.first_row = torch.zeros(self.G, self.N, dtype=torch.long)
 
@@ -1189,6 +1341,47 @@ class StreamGroups:
         a.visible = None
         a.first_row = None if first_row is None else _ptr(first_row[g0:])
         return _motion_launch(a, dev, out, who)
+
+    def stabilize(self, frames: torch.Tensor, f0: int, *, group: int = 0, reset: bool = False, alpha: float = 0.1, zoom: float = 1.0,
+                  border: str = "fill", fill=(0, 0, 0), out: Optional[torch.Tensor] = None, layout: Optional[str] = None,
+                  N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6, first_row: Optional[torch.Tensor] = None,
+                  model: str = "similarity", tol: float = 2.0, hypotheses: int = 128, min_base: float = 16.0, seed: int = 0):
+        """uint8 `frames` (picture j shows frame f0 + j) steadied by the camera motion of `group`, straight from the stream's own
+        history and logits: self.motion(lag = 1), smooth_path, warp_frames -- three launches, no wait (ops.stabilize has the
+        picture).  The path state is kept here, one per group: the first call for a group, or reset=True, locks onto frame f0 (its
+        matrix is the identity, or the zoom alone: the motion from frame f0 - 1 into it is not part of the path); any other call must
+        go on where the last one ended (f0 = its f0 + F) with the same alpha: ValueError otherwise.  restart() drops the states.  Range errors are those of motion().  -> (out, warp float32 [F,2,3]) on the device."""
+        who = "stabilize"
+        if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
+            raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+        f0, F_, group, alpha = int(f0), frames.shape[0], int(group), float(alpha)
+        if not 0 <= group < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"{who}: alpha must lie in [0, 1], got {alpha!r}")
+        if self._stab is None:
+            self._stab = {}
+        held = None if reset else self._stab.get(group)
+        if held is not None and (held[0] != f0 or held[2] != alpha):
+            raise ValueError(f"{who}: group {group} has been steadied up to frame {held[0]} with alpha = {held[2]}; a call for frame {f0} "
+                             f"with alpha = {alpha} does not go on from there: pass reset=True to lock onto frame {f0} afresh")
+        a, out = _warp_args(frames, out, border, fill, layout, who)  # (everything that can be refused is, before the state moves)
+        key = (a.H, a.W, float(zoom))
+        if held is not None and held[3][0] == key:
+            post = held[3][1]
+        else:
+            post = None if key[2] == 1.0 else zoom_matrix(a.H, a.W, zoom).to(frames.device)
+        motion = self.motion(f0, F_, N_out=N_out, scale=scale, thresh=thresh, first_row=first_row, lag=1, model=model, tol=tol,
+                             hypotheses=hypotheses, min_base=min_base, seed=seed, group=group)[0]
+        if held is None:  # frame f0 is the one locked onto: the motion INTO it is not part of the path
+            motion[0, 0] = 0.0
+            motion[0, 0, 0, 0] = 1.0
+            motion[0, 0, 1, 1] = 1.0
+        state = _path_state(1, self.queries.device) if held is None else held[1]
+        warp, state = smooth_path(motion, state, alpha=alpha, post=post)
+        _warp_launch(a, warp, frames.device, who)
+        self._stab[group] = (f0 + F_, state, alpha, (key, post))
+        return out, warp[0]
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -570,6 +570,50 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                                         first_row=self._emit_first_row(), lag=lag, model=model, tol=tol, hypotheses=hypotheses,
                                         min_base=min_base, seed=seed, group=group)
 
+    @torch.no_grad()
+    def stabilize(self, frames, first_frame=None, alpha=0.1, zoom=1.0, border="fill", fill=(0, 0, 0), out=None, group=0, reset=False,
+                  model="similarity", tol=2.0, hypotheses=128, min_base=16.0, seed=0):
+        """Not in the reference: `frames` -- raw-video resolution, uint8, [F,H,W,3] or [F,3,H,W] (or one frame), on the device, as
+        draw() takes them -- steadied by the camera motion of the running stream, by three launches and without a wait
+        (ops.StreamGroups.stabilize: camera_motion's fit with lag 1 on the stream's own history and logits, ops.smooth_path,
+        ops.warp_frames).  Picture j shows frame first_frame + j; default: the newest F tracked frames.  The N (+ spare_points)
+        user-visible points of query set `group` vote, where the returned visibility calls them visible (visibility * confidence >
+        0.6, at or above their slot's first row); model "similarity" or "translation", tol and min_base in raw-video pixels.
+        alpha: 0 locks onto the first steadied frame for ever, 1 corrects nothing, in between a steady pan of v pixels a frame is
+        followed (1 - alpha) v / alpha pixels behind.  zoom > 1 enlarges the middle to hide the border a correction uncovers; border
+        "fill" paints what lies outside the picture with `fill`, "edge" repeats the edge pixels.  The path goes on from call to call:
+        the first call for a group, or reset=True, locks onto first_frame (that picture is copied, or only zoomed: the motion
+        from the frame before into it is not part of the path); any other call must start at the frame the last one ended
+        on, with the same alpha (ValueError otherwise, as when first_frame - 1 has left the ring or the pictures lie beyond what has
+        been tracked).  A new first step drops the path.  Call draw() first when marks are wanted: the marks are then warped with the
+        picture.  A point at raw position x of a frame appears at inverse(warp) x of the steadied one.  The stream's tracks are
+        untouched.  Returns (frames_out: a new tensor, or `out`; warp float32 [n,2,3] on the device)."""
+        if self.v2:
+            raise NotImplementedError("CoTracker2 keeps no stream state on the device: stabilize on a v2 predictor is not implemented")
+        gs = getattr(self.model, "_gstream", None)
+        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+            raise ValueError("stabilize: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
+        one = frames.dim() == 3
+        if one:
+            frames = frames[None]
+            out = out[None] if out is not None else None
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
+        if not (hwc or chw):
+            raise ValueError(f"stabilize: expected {H} x {W} frames, [F,{H},{W},3] or [F,3,{H},{W}]; got {tuple(frames.shape)}")
+        done, F_ = gs.committed, frames.shape[0]
+        first_frame = done - F_ if first_frame is None else int(first_frame)
+        if first_frame < 0 or first_frame + F_ > done:
+            raise ValueError(f"stabilize: pictures of frames [{first_frame}, {first_frame + F_}) lie beyond what has been tracked ({done} frames)")
+        res, warp = self.model.stream_stabilize(frames, first_frame, group=group, reset=reset, alpha=alpha, zoom=zoom, border=border, fill=fill,
+                                                out=out, layout="hwc" if hwc and not chw else ("chw" if chw and not hwc else None),
+                                                N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
+                                                first_row=self._emit_first_row(), model=model, tol=tol, hypotheses=hypotheses,
+                                                min_base=min_base, seed=seed)
+        return (res[0] if one else res), warp
+
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
         everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""

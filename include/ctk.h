@@ -47,6 +47,10 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_warp_frames on the new struct ctk_warp_args and
+ *       ctk_smooth_path on the new struct ctk_smooth_path_args: uint8 pictures resampled under a 2 x 3 matrix each (Q24 fixed point,
+ *       bilinear in 1/256 pixel), and the causal path rule that turns per-frame camera motions into such matrices
+ *       (csrc/warp_math.h); one launch each, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_motion and ctk_fit_motion_workspace_bytes on the
  *       new struct ctk_fit_motion_args: per frame, a robust fit (seeded hypotheses, integer scoring) of a translation or a similarity
  *       to the motion of the tracked points, and the points that do not follow it (csrc/motion_math.h); one launch, no atomics.
@@ -625,6 +629,77 @@ typedef struct ctk_fit_motion_args {
 } ctk_fit_motion_args;
 int ctk_fit_motion_workspace_bytes(const ctk_fit_motion_args* a, size_t* out_bytes);
 int ctk_fit_motion(const ctk_fit_motion_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- warp frames: pictures resampled under a matrix, and the path that steadies a camera ---------------------------------------------
+ * For a caller whose frames and camera motions (ctk_fit_motion) are on the device: what a stabiliser does with them, instead of
+ * accumulating matrices on the host and resampling through F.grid_sample (uint8 -> float32, affine_grid, a float result, back to
+ * uint8).  The rules are integer or one-IEEE-operation-per-step double arithmetic stated once in csrc/warp_math.h, and the results
+ * depend on them alone.
+ *
+ * ctk_warp_frames: picture j of dst = picture j of src resampled under matrices[j].
+ *   matrix     float32 2 x 3, maps an OUTPUT pixel to a SOURCE position: (sx, sy) = m (x, y, 1); pixel centres are at integers.
+ *              Valid iff all six entries are finite, |m00|, |m01|, |m10|, |m11| <= 8 and |m02|, |m12| <= 32768; an invalid matrix
+ *              counts as the identity (the picture is copied), as ctk_fit_motion answers the identity where nothing can be fitted.
+ *   fixed point c_k = (int64)rint((double)m_k * 16777216.0): Q24, the product is exact, round half to even
+ *   coordinate X = c00 x + c01 y + c02 + 32768 and Y likewise, int64 (below 2^45); ix = X >> 24 (a floor), fx = (X >> 16) & 255
+ *   taps       (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1).  border CTK_WARP_FILL: a tap outside [0, W) x [0, H) has the
+ *              value fill[c]; CTK_WARP_EDGE: tap indices are clamped into range.  Nothing outside the picture is ever read.
+ *   blend      out = ((256 - fx)(256 - fy) p00 + fx (256 - fy) p01 + (256 - fx) fy p10 + fx fy p11 + 32768) >> 16 per channel, int32.
+ *              The identity copies the source bit for bit; an integer translation is a shifted copy.
+ *   frames     src and dst uint8, F pictures of H x W pixels, 3 channels, layout and strides (in elements) with ctk_ingest_args'
+ *              meaning: CTK_INGEST_HWC element (j, y, x, c) at j * frame_stride + y * row_stride + x * 3 + c, CTK_INGEST_CHW element
+ *              (j, c, y, x) at j * frame_stride + (c * H + y) * row_stride + x; src and dst have strides of their own.  Bytes of a row
+ *              beyond W pixels are neither read nor written.  src and dst must not overlap: a warp cannot run in place.
+ * One launch on `stream` (a workgroup stages the source box of its 64 x 16 output tile in 16 KiB of LDS, or reads memory directly where
+ * the box does not fit), no atomics, no host synchronisation, capture-safe; writes dst only (whole dwords when dst,
+ * dst_row_stride and dst_frame_stride are multiples of 4 bytes, bytes otherwise).  Before the launch: NULL a, matrices, src or dst:
+ * CTK_E_NULL; F outside 1..65535, H or W outside 1..CTK_INGEST_MAX_SIDE, an unknown layout or border, a row stride smaller than a row
+ * (3 W or W), a frame stride smaller than a frame (H or 3 H rows), a stride above 2^40, overlapping byte ranges of src and dst,
+ * reserved != 0: CTK_E_SHAPE; matrices not 4-byte aligned: CTK_E_ALIGN.
+ *
+ * ctk_smooth_path: a causal, leaky lock-on whose state stays bounded.  W (2 x 3, double) maps a stabilised pixel to a position in the
+ * current frame; state [G,6] holds it row-major per group, the identity before the first frame.  For frame f of group g, in order:
+ *   input      M = motion[g, f] (ctk_fit_motion with lag 1: frame f - 1 to frame f), float32 converted to double; a matrix with a
+ *              non-finite entry counts as the identity: the state persists and must never become NaN
+ *   compose    P[r][0] = M[r][0] W[0][0] + M[r][1] W[1][0];  P[r][1] = M[r][0] W[0][1] + M[r][1] W[1][1];
+ *              P[r][2] = (M[r][0] W[0][2] + M[r][1] W[1][2]) + M[r][2];  one rounded operation per step, no contraction
+ *   blend      W' = k P elementwise, then W'[0][0] += a, W'[1][1] += a, with a = (double)alpha, k = 1.0 - a.  (With C_f the cumulative
+ *              camera pose and S_f = (1 - alpha) S_f-1 + alpha C_f its exponential smoothing, the correction inverse(C_f) S_f obeys
+ *              this recurrence.)  alpha = 0 locks onto the first frame, alpha = 1 corrects nothing.
+ *   output     warp[g, f] = (float)W', or (float)(W' o post) composed by the same three formulas when post (float32 2 x 3, e.g. a
+ *              zoom that hides the border) is given; post does not enter the state.  warp[g, f] is a matrix for ctk_warp_frames.
+ * One launch on `stream`, one thread per group, sequential over the F frames; no host synchronisation, capture-safe; every element of
+ * warp and state is written by one plain store, and a group's state is read and then written by its own thread only.  Before the
+ * launch: NULL a, motion, state or warp: CTK_E_NULL; G or F outside 1..65535, alpha NaN or outside [0, 1], reserved != 0:
+ * CTK_E_SHAPE; state not 8-byte aligned, motion, warp or post not 4-byte aligned: CTK_E_ALIGN.                                  */
+#define CTK_WARP_FILL 0
+#define CTK_WARP_EDGE 1
+typedef struct ctk_warp_args {
+  int32_t F, H, W;            /* pictures, and their size in pixels                                */
+  int32_t layout;             /* CTK_INGEST_HWC / CTK_INGEST_CHW                                   */
+  int32_t border;             /* CTK_WARP_FILL / CTK_WARP_EDGE                                     */
+  int32_t reserved;           /* 0 */
+  uint8_t fill[4];            /* the value of a tap outside the picture, per channel; three used   */
+  int64_t src_frame_stride;   /* elements between two pictures of src                              */
+  int64_t src_row_stride;     /* elements between two pixel rows of src                            */
+  int64_t dst_frame_stride;
+  int64_t dst_row_stride;
+  const float* matrices;      /* [F,2,3], on the device                                            */
+  const uint8_t* src;
+  uint8_t* dst;
+} ctk_warp_args;
+int ctk_warp_frames(const ctk_warp_args* a, void* stream);
+
+typedef struct ctk_smooth_path_args {
+  int32_t G, F;               /* groups, frames per group                                          */
+  float alpha;                /* 0 locks onto the first frame .. 1 corrects nothing                */
+  int32_t reserved;           /* 0 */
+  const float* motion;        /* [G,F,2,3] */
+  const float* post;          /* [2,3], or NULL                                                    */
+  double* state;              /* [G,6], read and then written                                      */
+  float* warp;                /* [G,F,2,3] */
+} ctk_smooth_path_args;
+int ctk_smooth_path(const ctk_smooth_path_args* a, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
