@@ -16,6 +16,9 @@ CORR_LD = 2432
 CORR_K = 2401
 X_LD = 1120
 X_DIM = 1110
+XF_LD = 1632     # CTK_XF_LD: the folded transformer input xf, 4 x 384 hidden columns + the 96 small-feature columns of x
+XF_SMALL = 1536  # CTK_XF_SMALL: its first small-feature column (vis, conf, posenc 84, 10 zeros)
+XF_DIM = 1622
 HID = 384
 MLP = 1536
 VIRT = 64
@@ -287,6 +290,7 @@ SYMBOLS = {
     "ctk_window_batch_graph_create": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, C.c_size_t, _P(C.c_void_p)]),
     "ctk_corr_embed_batch_workspace_bytes": (C.c_int, [_P(WindowBatch), _P(C.c_size_t)]),
     "ctk_corr_embed_batch": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
+    "ctk_window_tokens_batch": (C.c_int, [_P(WindowBatch), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_window_graph_launch": (C.c_int, [C.c_void_p, _fp]),
     "ctk_window_graph_nodes": (C.c_int, [C.c_void_p, _P(C.c_int64)]),
     "ctk_window_graph_destroy": (C.c_int, [C.c_void_p]),

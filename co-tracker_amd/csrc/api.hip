@@ -18,8 +18,9 @@ int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, c
                           int out_split, hipStream_t s);
 int ctk_launch_heads(const float* tokens, const float* hw, const float* hb, int S, int N, float* delta, float* coords,
                      float* vis, float* conf, hipStream_t s);
+int ctk_launch_assemble(const ctk_window_args* a, void* x, int x_split, int ld, int base, hipStream_t s);
 int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, float scale_x, float scale_y, void* x, int x_split,
-                              hipStream_t s);
+                              int ld, int base, hipStream_t s);
 int ctk_launch_heads_batch(const float* tokens, const float* hw, const float* hb, const CtkBatchState& st, int B, int S, int N,
                            hipStream_t s);
 
@@ -150,6 +151,8 @@ struct Linear {
 };
 
 bool split_mode(const ctk_model_weights* w) { return w->in_p != nullptr; }
+// corr_mlp.fc2 folded into the input projection (include/ctk.h, ctk_model_weights): in_w / in_p are [384, CTK_XF_LD]
+bool folded(const ctk_model_weights* w) { return !w->corr_fc2_w && !w->corr_fc2_p; }
 
 // ---- update-former workspace carve -------------------------------------------------------
 // B videos (joint window): R = B*(N+64)*S rows, the B*N*S point rows first, then the B*64*S virtual rows
@@ -362,24 +365,33 @@ int check_former(const FormerRef& fr) {
   return CTK_OK;
 }
 
-int check_weights(const ctk_model_weights* w) {
+// window: the caller is a window entry point, which takes the folded form of the weights too (the stage entry points read
+// in_w as [384, CTK_X_LD] or need fc2, and keep answering CTK_E_NULL to it)
+int check_weights(const ctk_model_weights* w, bool window = false) {
   if (!w) return CTK_E_NULL;
   if ((!w->in_w && !w->in_p) || !w->in_bias_t || !w->virtual_tokens || !w->head_w || !w->head_b) return CTK_E_NULL;
-  if (split_mode(w) != (w->corr_fc1_p && w->corr_fc2_p)) return CTK_E_NULL;  // (corr_mlp belongs to the same pipeline)
+  if (folded(w)) {
+    if (!window || (!w->corr_fc1_w && !w->corr_fc1_p) || !w->corr_fc1_b) return CTK_E_NULL;
+    if (split_mode(w) != (w->corr_fc1_p != nullptr)) return CTK_E_NULL;
+  } else if (split_mode(w) != (w->corr_fc1_p && w->corr_fc2_p)) {
+    return CTK_E_NULL;  // (corr_mlp belongs to the same pipeline)
+  }
   return check_former(former_of(w));
 }
 
 // N = point tracks of ALL videos of the call (the per-frame bias is indexed by row % S: rows are track-major in every video)
-int input_projection(int S, int N, const float* x, bool x_split, const ctk_model_weights* w, const UfWs& ws, hipStream_t s) {
+// fold: x is the folded input xf [N*S, CTK_XF_LD] and in_w / in_p carry corr_mlp.fc2 (include/ctk.h)
+int input_projection(int S, int N, const float* x, bool x_split, const ctk_model_weights* w, const UfWs& ws, hipStream_t s,
+                     bool fold = false) {
   // tokens = input_transform(x + time_emb)   (cotracker3_online.py:247, cotracker.py:484)
-  return Linear(x, N * S, {w->in_w, w->in_p}, CTK_HID, CTK_X_LD, ws.tokens, nullptr)
-      .bias_rows(w->in_bias_t, S).k_valid(CTK_X_DIM).sh(x_split, false).run(s);
+  return Linear(x, N * S, {w->in_w, w->in_p}, CTK_HID, fold ? CTK_XF_LD : CTK_X_LD, ws.tokens, nullptr)
+      .bias_rows(w->in_bias_t, S).k_valid(fold ? CTK_XF_DIM : CTK_X_DIM).sh(x_split, false).run(s);
 }
 
 // ---- corr_embed workspace -------------------------------------------------------------------
 struct CorrWs {
   float* vol;  // [4][chunk*S][2432]   (SH format in split mode: same bytes)
-  float* h1;   // [4*chunk*S][384]     (SH format in split mode)
+  float* h1;   // [4*chunk*S][384]     (SH format in split mode); null on the folded path, where fc1 writes into xf
   void* fm_sh[CTK_MAX_BATCH][CTK_LEVELS];  // split mode: SH copy of every video's pyramid (scaled by 2^8), [S*H*W][4][2][32] halves
                                            // (query groups of one video, CTK_BATCH_SHARED_FMAPS: ONE copy, every fm_sh[b] = fm_sh[0])
   size_t bytes;
@@ -396,7 +408,7 @@ int corr_chunk_points(const ctk_window_args* a, int B = 1) {
 }
 
 // a = videos[0] of a joint window (the videos agree in every size); shared: the B windows are query groups of one video
-CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1, bool shared = false) {
+CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1, bool shared = false, bool fold = false) {
   CorrWs w;
   w.corr_version = ctk_opt(CTK_OPT_CORR_VERSION);
   w.chunk = corr_chunk_points(a, B);
@@ -405,8 +417,8 @@ CorrWs carve_corr(const ctk_window_args* a, void* base, int B = 1, bool shared =
   size_t off = 0;
   w.vol = reinterpret_cast<float*>(p + off);
   off += align256(rows * CTK_LEVELS * CTK_CORR_LD * sizeof(float));
-  w.h1 = reinterpret_cast<float*>(p + off);
-  off += align256(rows * CTK_LEVELS * CTK_HID * sizeof(float));
+  w.h1 = fold ? nullptr : reinterpret_cast<float*>(p + off);
+  if (!fold) off += align256(rows * CTK_LEVELS * CTK_HID * sizeof(float));
   for (int b = 0; b < B; ++b)
     for (int l = 0; l < CTK_LEVELS; ++l) {  // always carved (the size query does not know the weights' mode): ~8 MB per frame
       if (shared && b > 0) {
@@ -443,12 +455,15 @@ int prepare_pyramid_sh(const ctk_window_args* videos, const CorrWs& ws, hipStrea
 // shared (CTK_BATCH_SHARED_FMAPS, validated by check_batch): the B windows are query groups of ONE video whose coords / support /
 // point_mask are consecutive slices of one allocation each -- the sampler is then launched ONCE per chunk piece over the
 // stacked points [g0, g0 + pc), in its grouped instantiation (point g reads group g / N's coordinates).
+// fold (window path with folded weights): x is xf [B*N*S, CTK_XF_LD] and fc1, one batch per level, writes GELU(fc1) of level l
+// into its columns [384 l, 384 l + 384) -- there is no fc2 launch and no hidden buffer (ws.h1 is null).
 int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights* w, float* x, bool x_split, const CorrWs& ws,
-                   hipStream_t s, bool shared = false) {
+                   hipStream_t s, bool shared = false, bool fold = false) {
   const ctk_window_args* a = videos;
   const bool sp = split_mode(w);
   if (x_split && !sp) return CTK_E_SHAPE;
-  if ((!w->corr_fc1_w && !w->corr_fc1_p) || !w->corr_fc1_b || (!w->corr_fc2_w && !w->corr_fc2_p) || !w->corr_fc2_b) return CTK_E_NULL;
+  if ((!w->corr_fc1_w && !w->corr_fc1_p) || !w->corr_fc1_b) return CTK_E_NULL;
+  if (fold != folded(w) || (!fold && !w->corr_fc2_b)) return CTK_E_NULL;
   hipStream_t aux = B == 1 ? static_cast<hipStream_t>(a->aux_stream) : nullptr;  // a joint window ignores aux_stream
   const bool pipelined = sp && aux != nullptr && (overlap_mode() & 1) != 0;
   const int NT = B * a->N;
@@ -466,7 +481,7 @@ int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights
       if (pc <= 0) break;
       const long rows = (long)pc * a->S;
       float* vol = ws.vol + (size_t)p0 * a->S * CTK_LEVELS * CTK_CORR_LD;
-      float* h1 = ws.h1 + (size_t)p0 * a->S * CTK_LEVELS * CTK_HID;
+      float* h1 = fold ? nullptr : ws.h1 + (size_t)p0 * a->S * CTK_LEVELS * CTK_HID;
       hipStream_t gs = s;
       // stacked points [g0, g0 + pc) -> per video b: its points [m0, m0 + mc), rows (g - g0)*S + t of every level of the volume
       const int g0 = n0 + p0;
@@ -487,12 +502,19 @@ int run_corr_embed(const ctk_window_args* videos, int B, const ctk_model_weights
         CTK_TRY(pipe.fork());
         gs = aux;
       }
-      // corr_mlp.fc1 + exact GELU over all 4 levels at once        cotracker3_online.py:205, blocks.py:71-72
-      CTK_TRY(Linear(vol, rows * CTK_LEVELS, {w->corr_fc1_w, w->corr_fc1_p}, CTK_HID, CTK_CORR_LD, h1, w->corr_fc1_b)
-                  .act(CTK_ACT_GELU_ERF).k_valid(CTK_CORR_K).sh(sp, sp).run(gs));
-      // corr_mlp.fc2, one batch per level, written into x[g*S+t][l*256 ...]   (torch.cat :209)
-      CTK_TRY(Linear(h1, rows, {w->corr_fc2_w, w->corr_fc2_p}, 256, CTK_HID, x + (long)g0 * a->S * CTK_X_LD + CTK_X_CORR, w->corr_fc2_b)
-                  .ldy(CTK_X_LD).batched(CTK_LEVELS, rows * CTK_HID, 256).sh(sp, x_split).run(gs));
+      if (fold) {
+        // corr_mlp.fc1 + exact GELU, one batch per level, written into xf[g*S+t][l*384 ...]: fc2 lives in the projection
+        CTK_TRY(Linear(vol, rows, {w->corr_fc1_w, w->corr_fc1_p}, CTK_HID, CTK_CORR_LD, x + (long)g0 * a->S * CTK_XF_LD, w->corr_fc1_b)
+                    .act(CTK_ACT_GELU_ERF).k_valid(CTK_CORR_K).ldy(CTK_XF_LD).batched(CTK_LEVELS, rows * CTK_CORR_LD, CTK_HID)
+                    .sh(sp, x_split).run(gs));
+      } else {
+        // corr_mlp.fc1 + exact GELU over all 4 levels at once        cotracker3_online.py:205, blocks.py:71-72
+        CTK_TRY(Linear(vol, rows * CTK_LEVELS, {w->corr_fc1_w, w->corr_fc1_p}, CTK_HID, CTK_CORR_LD, h1, w->corr_fc1_b)
+                    .act(CTK_ACT_GELU_ERF).k_valid(CTK_CORR_K).sh(sp, sp).run(gs));
+        // corr_mlp.fc2, one batch per level, written into x[g*S+t][l*256 ...]   (torch.cat :209)
+        CTK_TRY(Linear(h1, rows, {w->corr_fc2_w, w->corr_fc2_p}, 256, CTK_HID, x + (long)g0 * a->S * CTK_X_LD + CTK_X_CORR, w->corr_fc2_b)
+                    .ldy(CTK_X_LD).batched(CTK_LEVELS, rows * CTK_HID, 256).sh(sp, x_split).run(gs));
+      }
     }
     if (pipelined && pieces > 1) CTK_TRY(pipe.join());  // join before the next chunk reuses the buffers / x is consumed
   }
@@ -555,37 +577,51 @@ bool has_state(const ctk_window_args* videos, int B) {
 
 bool shared_fmaps(const ctk_window_batch* bt) { return (bt->flags & CTK_BATCH_SHARED_FMAPS) != 0 && bt->B > 1; }
 
+// Workspace of a window: x | update-former buffers | correlation buffers.  With folded weights x is xf (CTK_XF_LD columns) and
+// the correlation buffers have no hidden h1; the size queries do not know the weights, so they answer for the larger of the two
+// (the unfolded one, x + h1, unless points_per_chunk is below a third of the points).
+size_t x_bytes(const ctk_window_args* a, int B, bool fold) {
+  return align256((size_t)B * a->N * a->S * (fold ? CTK_XF_LD : CTK_X_LD) * sizeof(float));
+}
+
 size_t window_bytes(const ctk_window_args* a, int B, bool shared = false) {
-  size_t total = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
-  total += carve_uf(a->S, a->N, nullptr, B).bytes;
-  total += carve_corr(a, nullptr, B, shared).bytes;
-  return total;
+  size_t need[2];
+  for (int fold = 0; fold < 2; ++fold) need[fold] = x_bytes(a, B, fold != 0) + carve_corr(a, nullptr, B, shared, fold != 0).bytes;
+  return carve_uf(a->S, a->N, nullptr, B).bytes + (need[0] > need[1] ? need[0] : need[1]);
 }
 
 // One window of B videos (validated by the caller): ctk_forward_window is the B == 1 call.  shared: B query groups of one video.
+// tokens_out (ctk_window_tokens_batch): the first half of ONE iteration only -- the tokens the update former would start from
 int forward_windows(const ctk_window_args* videos, int B, const ctk_model_weights* w, void* workspace, size_t workspace_bytes,
-                    hipStream_t s, bool shared = false) {
+                    hipStream_t s, bool shared = false, float* tokens_out = nullptr) {
   const ctk_window_args* a = videos;
   if (!has_state(videos, B) || !workspace) return CTK_E_NULL;
   if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
   if (window_bytes(a, B, shared) > workspace_bytes) return CTK_E_WORKSPACE;
   char* base = static_cast<char*>(workspace);
   float* x = reinterpret_cast<float*>(base);
-  size_t off = align256((size_t)B * a->N * a->S * CTK_X_LD * sizeof(float));
+  const bool fold = folded(w);    // x is xf: fc1's hidden features | small features, and the projection carries fc2
+  size_t off = x_bytes(a, B, fold);
   const UfWs uws = carve_uf(a->S, a->N, base + off, B);
   off += uws.bytes;
-  const CorrWs cws = carve_corr(a, base + off, B, shared);
+  const CorrWs cws = carve_corr(a, base + off, B, shared, fold);
   const bool sp = split_mode(w);  // split mode: the transformer input x is kept in SH format
+  const int x_ld = fold ? CTK_XF_LD : CTK_X_LD, x_small = fold ? CTK_XF_SMALL : CTK_X_VIS;
+  const int iters = tokens_out ? 1 : a->iters;
   CtkBatchState st{};
   for (int b = 0; b < B; ++b) {
     st.coords[b] = videos[b].coords; st.vis[b] = videos[b].vis; st.conf[b] = videos[b].conf;
   }
-  if (sp && a->iters > 0) CTK_TRY(prepare_pyramid_sh(videos, cws, s, shared ? 1 : B));
-  for (int it = 0; it < a->iters; ++it) {                          // cotracker3_online.py:187
-    CTK_TRY(run_corr_embed(videos, B, w, x, sp, cws, s, shared));  // :190-210
-    if (B == 1) CTK_TRY(ctk_assemble_tokens(a, x, sp, s));         // :212-245
-    else CTK_TRY(ctk_launch_assemble_batch(st, B, a->S, a->N, a->scale_x, a->scale_y, x, sp, s));
-    CTK_TRY(input_projection(a->S, B * a->N, x, sp, w, uws, s));   // :247 + cotracker.py:484
+  if (sp && iters > 0) CTK_TRY(prepare_pyramid_sh(videos, cws, s, shared ? 1 : B));
+  for (int it = 0; it < iters; ++it) {                             // cotracker3_online.py:187
+    CTK_TRY(run_corr_embed(videos, B, w, x, sp, cws, s, shared, fold));  // :190-210
+    if (B == 1) CTK_TRY(ctk_launch_assemble(a, x, sp, x_ld, x_small, s));  // :212-245
+    else CTK_TRY(ctk_launch_assemble_batch(st, B, a->S, a->N, a->scale_x, a->scale_y, x, sp, x_ld, x_small, s));
+    CTK_TRY(input_projection(a->S, B * a->N, x, sp, w, uws, s, fold));  // :247 + cotracker.py:484
+    if (tokens_out) {
+      const hipError_t e = hipMemcpyAsync(tokens_out, uws.tokens, (size_t)B * a->N * a->S * CTK_HID * sizeof(float), hipMemcpyDeviceToDevice, s);
+      return e == hipSuccess ? CTK_OK : (int)e;
+    }
     FormerRef fr = former_of(w);
     fr.aux = B == 1 ? static_cast<hipStream_t>(a->aux_stream) : nullptr;
     fr.space_attn = (a->flags & CTK_WINDOW_NO_SPACE_ATTN) == 0;
@@ -705,7 +741,7 @@ extern "C" int ctk_forward_window_workspace_bytes(const ctk_window_args* a, size
 extern "C" int ctk_forward_window(const ctk_window_args* a, const ctk_model_weights* w, void* workspace,
                                   size_t workspace_bytes, void* stream) {
   CTK_TRY(check_window(a));
-  CTK_TRY(check_weights(w));
+  CTK_TRY(check_weights(w, true));
   return forward_windows(a, 1, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
@@ -720,8 +756,18 @@ extern "C" int ctk_forward_window_batch_workspace_bytes(const ctk_window_batch* 
 extern "C" int ctk_forward_window_batch(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
                                         size_t workspace_bytes, void* stream) {
   CTK_TRY(check_batch(batch));
-  CTK_TRY(check_weights(w));
+  CTK_TRY(check_weights(w, true));
   return forward_windows(batch->videos, batch->B, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream), shared_fmaps(batch));
+}
+
+extern "C" int ctk_window_tokens_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* tokens, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  CTK_TRY(check_batch(batch));
+  CTK_TRY(check_weights(w, true));
+  if (!tokens) return CTK_E_NULL;
+  if (!ctk_aligned16(tokens)) return CTK_E_ALIGN;
+  return forward_windows(batch->videos, batch->B, w, workspace, workspace_bytes, static_cast<hipStream_t>(stream), shared_fmaps(batch),
+                         tokens);
 }
 
 extern "C" int ctk_corr_embed_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes) {
@@ -806,7 +852,7 @@ int graph_create(void* workspace, size_t workspace_bytes, ctk_window_graph** out
 
 extern "C" int ctk_window_graph_create(const ctk_window_args* a, const ctk_model_weights* w, void* workspace,
                                        size_t workspace_bytes, ctk_window_graph** out) {
-  auto valid = [&]() -> int { CTK_TRY(check_window(a)); CTK_TRY(check_weights(w)); return has_state(a, 1) ? CTK_OK : CTK_E_NULL; };
+  auto valid = [&]() -> int { CTK_TRY(check_window(a)); CTK_TRY(check_weights(w, true)); return has_state(a, 1) ? CTK_OK : CTK_E_NULL; };
   auto bytes = [&] { return window_bytes(a, 1); };
   auto enqueue = [&](hipStream_t cs) { return ctk_forward_window(a, w, workspace, workspace_bytes, cs); };
   return graph_create(workspace, workspace_bytes, out, valid, bytes, enqueue);
@@ -814,7 +860,7 @@ extern "C" int ctk_window_graph_create(const ctk_window_args* a, const ctk_model
 
 extern "C" int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model_weights* w, void* workspace,
                                              size_t workspace_bytes, ctk_window_graph** out) {
-  auto valid = [&]() -> int { CTK_TRY(check_batch(batch)); CTK_TRY(check_weights(w)); return has_state(batch->videos, batch->B) ? CTK_OK : CTK_E_NULL; };
+  auto valid = [&]() -> int { CTK_TRY(check_batch(batch)); CTK_TRY(check_weights(w, true)); return has_state(batch->videos, batch->B) ? CTK_OK : CTK_E_NULL; };
   auto bytes = [&] { return window_bytes(batch->videos, batch->B, shared_fmaps(batch)); };
   auto enqueue = [&](hipStream_t cs) { return ctk_forward_window_batch(batch, w, workspace, workspace_bytes, cs); };
   return graph_create(workspace, workspace_bytes, out, valid, bytes, enqueue);

@@ -72,6 +72,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, float* y
 }
 
 // ---- token assembly: x[n*S+t][1024..1119] = [vis, conf, posenc(rel fwd/bwd coords), 0-pad] ---
+// (the same 96 columns at `base` of rows `ld` columns apart: the folded input xf of api.hip has them at CTK_XF_SMALL of CTK_XF_LD)
 // cotracker3_online.py:212-245 and posenc :19-39.  The time embedding (:247) is folded into the
 // input projection's per-frame bias (ctk_model_weights.in_bias_t).
 // One thread = 8 consecutive columns of a row (12 threads per row): a 16-byte hi piece and a 16-byte lo piece per thread.  Round 2
@@ -105,25 +106,26 @@ constexpr int ASM_G8 = (CTK_X_LD - CTK_X_VIS) / 8;  // 12 column octets of the 9
 
 // columns e0 .. e0+7 of row `row` of x from track n, frame t of one video's state
 __device__ __forceinline__ void assemble_octet(const float* coords, const float* vis, const float* conf, int S, int N, float scale_x,
-                                               float scale_y, float* x, int x_split, long row, int t, int n, int e0) {
+                                               float scale_y, float* x, int x_split, int ld, int base, long row, int t, int n,
+                                               int e0) {
   f32x4 v[2];
 #pragma unroll
   for (int k = 0; k < 8; ++k) v[k >> 2][k & 3] = assemble_value(coords, vis, conf, S, N, scale_x, scale_y, t, n, e0 + k);
-  if (x_split) {  // SH row: 35 tiles x 64 halves
-    _Float16* xh = reinterpret_cast<_Float16*>(x) + row * (2 * CTK_X_LD) + ctk_sh_col(CTK_X_VIS + e0);
+  if (x_split) {  // SH row: ld / 32 tiles x 64 halves
+    _Float16* xh = reinterpret_cast<_Float16*>(x) + row * (2 * ld) + ctk_sh_col(base + e0);
     f16x8 hi, lo;
     ctk_split8(v[0], v[1], hi, lo);
     *reinterpret_cast<f16x8*>(xh) = hi;
     *reinterpret_cast<f16x8*>(xh + 32) = lo;
   } else {
-    float* xp = x + row * CTK_X_LD + CTK_X_VIS + e0;
+    float* xp = x + row * ld + base + e0;
     *reinterpret_cast<f32x4*>(xp) = v[0];
     *reinterpret_cast<f32x4*>(xp + 4) = v[1];
   }
 }
 
 __global__ void assemble_kernel(const float* coords, const float* vis, const float* conf, int S, int N, float scale_x,
-                                float scale_y, float* x, int x_split) {
+                                float scale_y, float* x, int x_split, int ld, int base) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)S * N * ASM_G8;
   if (i >= total) return;
@@ -131,11 +133,12 @@ __global__ void assemble_kernel(const float* coords, const float* vis, const flo
   const long row = i / ASM_G8;  // n*S + t
   const int t = row % S;
   const int n = row / S;
-  assemble_octet(coords, vis, conf, S, N, scale_x, scale_y, x, x_split, row, t, n, e0);
+  assemble_octet(coords, vis, conf, S, N, scale_x, scale_y, x, x_split, ld, base, row, t, n, e0);
 }
 
 // joint window: row = (b*N + n)*S + t of the stacked x, state of video b from the by-value table
-__global__ void assemble_batch_kernel(CtkBatchState st, int B, int S, int N, float scale_x, float scale_y, float* x, int x_split) {
+__global__ void assemble_batch_kernel(CtkBatchState st, int B, int S, int N, float scale_x, float scale_y, float* x, int x_split,
+                                      int ld, int base) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)B * S * N * ASM_G8;
   if (i >= total) return;
@@ -144,7 +147,7 @@ __global__ void assemble_batch_kernel(CtkBatchState st, int B, int S, int N, flo
   const int t = row % S;
   const int bn = row / S;
   const int b = bn / N, n = bn - b * N;
-  assemble_octet(st.coords[b], st.vis[b], st.conf[b], S, N, scale_x, scale_y, x, x_split, row, t, n, e0);
+  assemble_octet(st.coords[b], st.vis[b], st.conf[b], S, N, scale_x, scale_y, x, x_split, ld, base, row, t, n, e0);
 }
 
 // ---- virtual tokens: tokens[(N+v)*S + t] = virual_tracks[v]   (cotracker.py:487-488) --------
@@ -259,16 +262,21 @@ int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, c
   return CTK_OK;
 }
 
-extern "C" int ctk_assemble_tokens(const ctk_window_args* a, void* x, int32_t x_split, void* stream) {
+// the 96 small-feature columns into columns [base, base + 96) of rows `ld` columns apart (both multiples of 32)
+int ctk_launch_assemble(const ctk_window_args* a, void* x, int x_split, int ld, int base, hipStream_t s) {
   if (!a || !a->coords || !a->vis || !a->conf || !x) return CTK_E_NULL;
   if (a->S <= 0 || a->N <= 0 || !(a->scale_x > 0.f) || !(a->scale_y > 0.f)) return CTK_E_SHAPE;
-  const long total = (long)a->S * a->N * ((CTK_X_LD - CTK_X_VIS) / 8);  // threads: 8 columns each
-  CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, static_cast<hipStream_t>(stream));
-  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), a->coords, a->vis, a->conf, a->S, a->N, a->scale_x, a->scale_y,
-                     static_cast<float*>(x), x_split);
+  if ((ld % 32) || (base % 32) || base < 0 || base + 8 * ASM_G8 > ld) return CTK_E_SHAPE;
+  const long total = (long)a->S * a->N * ASM_G8;  // threads: 8 columns each
+  CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, s);
+  hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a->coords, a->vis, a->conf, a->S, a->N,
+                     a->scale_x, a->scale_y, static_cast<float*>(x), x_split, ld, base);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
+}
+
+extern "C" int ctk_assemble_tokens(const ctk_window_args* a, void* x, int32_t x_split, void* stream) {
+  return ctk_launch_assemble(a, x, x_split, CTK_X_LD, CTK_X_VIS, static_cast<hipStream_t>(stream));
 }
 
 int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream_t s) {
@@ -292,13 +300,14 @@ int ctk_launch_heads(const float* tokens, const float* hw, const float* hb, int 
 
 // ---- joint window (ctk_forward_window_batch, B > 1): one launch for all videos -------------------------------------------
 int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, float scale_x, float scale_y, void* x, int x_split,
-                              hipStream_t s) {
+                              int ld, int base, hipStream_t s) {
   if (!x) return CTK_E_NULL;
   if (B <= 0 || B > CTK_MAX_BATCH || S <= 0 || N <= 0 || !(scale_x > 0.f) || !(scale_y > 0.f)) return CTK_E_SHAPE;
+  if ((ld % 32) || (base % 32) || base < 0 || base + 8 * ASM_G8 > ld) return CTK_E_SHAPE;
   const long total = (long)B * S * N * ASM_G8;
   CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, s);
   hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st, B, S, N, scale_x, scale_y,
-                     static_cast<float*>(x), x_split);
+                     static_cast<float*>(x), x_split, ld, base);
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
 }

@@ -112,6 +112,38 @@ def sincos_time_embed(dim: int, window_len: int) -> torch.Tensor:
     return torch.cat([torch.sin(out), torch.cos(out)], dim=1)[None].float()
 
 
+def interpolate_time_embed(te: torch.Tensor, S: int) -> torch.Tensor:
+    """interpolate_time_embed (cotracker3_online.py:145-156): te [1,W,D] -> [S,D]."""
+    if S != te.shape[1]:
+        te = F.interpolate(te.permute(0, 2, 1), size=S, mode="linear").permute(0, 2, 1)
+    return te[0]
+
+
+def fold_input_weights(in_w: torch.Tensor, fc2_w: torch.Tensor, fc2_b: torch.Tensor):
+    """corr_mlp.fc2 folded into input_transform (include/ctk.h, ctk_model_weights "folded form").  Nothing nonlinear lies between
+    the two (cotracker3_online.py:205-247), so with Win_l = the 256 columns of input_transform.weight that read level l's embedding
+        W x + b = sum_l (Win_l W2) h1_l + W_small x_small + (b + sum_l Win_l b2),       h1_l = GELU(fc1(volume_l)).
+    in_w [384,1110] in the reference's column order [vis, conf, corr(4 x 256), posenc(84)], fc2_w [256,384], fc2_b [256] ->
+    (weight [384, XF_LD] in the xf column order: 4 x 384 hidden, vis, conf, posenc, zero padding;  sum_l Win_l b2 [384]), float64."""
+    w, w2, b2 = in_w.double(), fc2_w.double(), fc2_b.double()
+    out = torch.zeros(w.shape[0], L.XF_LD, dtype=torch.float64, device=w.device)
+    extra = torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+    for l in range(L.LEVELS):
+        w_l = w[:, 2 + 256 * l:2 + 256 * (l + 1)]
+        out[:, L.HID * l:L.HID * (l + 1)] = w_l @ w2
+        extra += w_l @ b2
+    out[:, L.XF_SMALL:L.XF_SMALL + 2] = w[:, 0:2]
+    out[:, L.XF_SMALL + 2:L.XF_SMALL + 86] = w[:, 1026:1110]
+    return out, extra
+
+
+def input_bias_rows(te: torch.Tensor, in_w: torch.Tensor, in_b: torch.Tensor, extra: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-frame bias of the input projection, float64 [S,384]: input_transform(x + e_t) = W x + (W e_t + b)
+    (cotracker3_online.py:247 + cotracker.py:484), plus `extra` (fold_input_weights) on the folded path."""
+    rows = te.double() @ in_w.double().t() + in_b.double()
+    return rows if extra is None else rows + extra.double()
+
+
 # ------------------------------------------------------------------------------------------
 # device-side packed weights (the ctk_model_weights struct of include/ctk.h)
 # ------------------------------------------------------------------------------------------
@@ -199,24 +231,30 @@ class PackedWeights:
             st.virtual2point[i] = block(f"{u}space_virtual2point_blocks.{i}.", "cross_attn", True)
             st.point2virtual[i] = block(f"{u}space_point2virtual_blocks.{i}.", "cross_attn", True)
         self.struct = st
+        # The window path's struct: corr_mlp.fc2 folded into the input projection (one big GEMM less per iteration).  The
+        # products are formed once here, in float64, and rounded once; the struct above stays for the stage operators.
+        in_wf, self._bias_fold = fold_input_weights(w_ref, sd["corr_mlp.fc2.weight"], sd["corr_mlp.fc2.bias"])
+        in_wf = in_wf.float()
+        sf = L.ModelWeights.from_buffer_copy(st)
+        sf.corr_fc2_w = sf.corr_fc2_p = sf.corr_fc2_b = None
+        sf.in_w, sf.in_p = hold(in_wf), pack(in_wf)
+        self.struct_folded = sf
         self._bias_t = {}
 
     def time_embed(self, S: int) -> torch.Tensor:
         """interpolate_time_embed (cotracker3_online.py:145-156) -> [S,1110] reference column order."""
-        te = self.time_emb
-        if S != te.shape[1]:
-            te = F.interpolate(te.permute(0, 2, 1), size=S, mode="linear").permute(0, 2, 1)
-        return te[0]
+        return interpolate_time_embed(self.time_emb, S)
 
-    def struct_for(self, S: int) -> L.ModelWeights:
+    def struct_for(self, S: int, folded: bool = False) -> L.ModelWeights:
         """Struct whose in_bias_t folds the S-frame time embedding into the input projection:
-        input_transform(x + e_t) = W x + (W e_t + b)   (cotracker3_online.py:247 + cotracker.py:484)."""
-        if S not in self._bias_t:
-            te = self.time_embed(S).double()
-            bias_t = (te @ self.in_w_ref.double().t() + self.in_b.double()).float().contiguous()
-            self._bias_t[S] = bias_t
-        self.struct.in_bias_t = self._bias_t[S].data_ptr()
-        return self.struct
+        input_transform(x + e_t) = W x + (W e_t + b)   (cotracker3_online.py:247 + cotracker.py:484).
+        folded: the struct of the window calls (fc2 inside the projection; its bias rows carry fc2's bias too)."""
+        if (S, folded) not in self._bias_t:
+            rows = input_bias_rows(self.time_embed(S), self.in_w_ref, self.in_b, self._bias_fold if folded else None)
+            self._bias_t[S, folded] = rows.float().contiguous()
+        st = self.struct_folded if folded else self.struct
+        st.in_bias_t = self._bias_t[S, folded].data_ptr()
+        return st
 
 
 # ------------------------------------------------------------------------------------------

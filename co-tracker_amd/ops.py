@@ -932,7 +932,7 @@ def _run_window(name: str, args, wstruct, nbytes: int, device) -> None:
 def forward_window(win: Window, weights) -> None:
     """`iters` update iterations in place on win's coords/vis/conf (cotracker3_online.py:171-264)."""
     nbytes = _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args))
-    _run_window("ctk_forward_window", win.args, weights.struct_for(win.S), nbytes, win.device)
+    _run_window("ctk_forward_window", win.args, weights.struct_for(win.S, folded=True), nbytes, win.device)
 
 
 def forward_window_v2(win: V2Window, weights) -> None:
@@ -954,7 +954,7 @@ class WindowGraph:
 
     def __init__(self, win: Window, weights):
         self.wins = [win]
-        self._capture("ctk_forward_window", "ctk_window_graph_create", win.args, weights, weights.struct_for(win.S),
+        self._capture("ctk_forward_window", "ctk_window_graph_create", win.args, weights, weights.struct_for(win.S, folded=True),
                       _query_bytes("ctk_forward_window_workspace_bytes", C.byref(win.args)), win.state, [win.args], win.device)
 
     def _capture(self, direct: str, create: str, args, weights, wstruct, nbytes: int, state, iter_slots, device) -> None:
@@ -1052,7 +1052,7 @@ def forward_windows(wins: Sequence[Window], weights, max_corr_rows: int = 262144
     """ONE joint window call for B videos (ctk_forward_window_batch): `iters` update iterations in place on every
     win's coords / vis / conf.  One video: exactly forward_window(wins[0]).  shared: B query groups of one video (WindowBatch)."""
     batch = WindowBatch(wins, max_corr_rows, points_per_chunk, shared)
-    _run_window("ctk_forward_window_batch", batch.struct, weights.struct_for(batch.S), batch.workspace_bytes(), batch.device)
+    _run_window("ctk_forward_window_batch", batch.struct, weights.struct_for(batch.S, folded=True), batch.workspace_bytes(), batch.device)
 
 
 class WindowBatchGraph(WindowGraph):
@@ -1062,7 +1062,8 @@ class WindowBatchGraph(WindowGraph):
                  shared: bool = False):
         self.batch = batch = WindowBatch(wins, max_corr_rows, points_per_chunk, shared)
         self.wins = batch.wins
-        self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights, weights.struct_for(batch.S),
+        self._capture("ctk_forward_window_batch", "ctk_window_batch_graph_create", batch.struct, weights,
+                      weights.struct_for(batch.S, folded=True),
                       batch.workspace_bytes(), [t_ for w_ in batch.wins for t_ in w_.state], list(batch.arr), batch.device)
 
 
@@ -1583,6 +1584,20 @@ def corr_embed_batch(wins: Sequence[Window], weights, points_per_chunk: Optional
     L.check(L.load().ctk_corr_embed_batch(C.byref(batch.struct), C.byref(mw), _ptr(x), _ptr(ws), ws.numel(), _stream()),
             "ctk_corr_embed_batch")
     return x
+
+
+def window_tokens(wins: Sequence[Window], weights, points_per_chunk: Optional[int] = None, shared: bool = False,
+                  folded: bool = True) -> torch.Tensor:
+    """The tokens [B*N*S, 384] one iteration of the joint window call hands to the update former (ctk_window_tokens_batch): the
+    correlation stage, token assembly and input projection as the window runs them -- with fc2 folded into the projection, or
+    (folded=False) by the unfolded launches.  The windows' state is not changed."""
+    batch = WindowBatch(wins, points_per_chunk=points_per_chunk, shared=shared)
+    tokens = torch.empty(batch.B * batch.N * batch.S, L.HID, device=batch.device, dtype=torch.float32)
+    ws = _workspace(batch.workspace_bytes(), batch.device)
+    mw = weights.struct_for(batch.S, folded=folded)
+    L.check(L.load().ctk_window_tokens_batch(C.byref(batch.struct), C.byref(mw), _ptr(tokens), _ptr(ws), ws.numel(), _stream()),
+            "ctk_window_tokens_batch")
+    return tokens
 
 
 def assemble_tokens(win: Window, x: torch.Tensor) -> torch.Tensor:

@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no struct changed): a ctk_model_weights with corr_fc1_* set and BOTH corr_fc2_w and corr_fc2_p
+ *       NULL -- CTK_E_NULL until now -- means "corr_mlp.fc2 is folded into the input projection": in_w / in_p are [384, CTK_XF_LD]
+ *       and in_bias_t carries the folded bias (see the struct).  The window entry points take it; the stage entry points that
+ *       need fc2 or the [384, CTK_X_LD] projection still answer CTK_E_NULL.  + ctk_window_tokens_batch (the tokens one
+ *       iteration of a window hands to the update former, for tests).
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_warp_frames on the new struct ctk_warp_args and
  *       ctk_smooth_path on the new struct ctk_smooth_path_args: uint8 pictures resampled under a 2 x 3 matrix each (Q24 fixed point,
  *       bilinear in 1/256 pixel), and the causal path rule that turns per-frame camera motions into such matrices
@@ -104,6 +109,11 @@ extern "C" {
 #define CTK_X_VIS 1024
 #define CTK_X_CONF 1025
 #define CTK_X_POSENC 1026
+/* folded transformer input xf (corr_mlp.fc2 folded into the input projection, see ctk_model_weights): [N*S, CTK_XF_LD],
+ * columns [384 l, 384 l + 384) = GELU(corr_mlp.fc1) of level l, then the 96 small-feature columns of x (vis, conf, posenc, 0) */
+#define CTK_XF_LD 1632     /* 4 * 384 + 96                                              */
+#define CTK_XF_SMALL 1536  /* first small-feature column (x column CTK_X_VIS)           */
+#define CTK_XF_DIM 1622    /* non-padding columns                                       */
 #define CTK_DEPTH 3        /* time_depth = space_depth = 3     cotracker3_online.py:74-75 */
 
 enum {
@@ -131,7 +141,17 @@ typedef struct ctk_block_weights {
   const void* wq_p; const void* wkv_p; const void* wo_p; const void* w1_p; const void* w2_p;
 } ctk_block_weights;
 
-/* EfficientUpdateFormer (cotracker.py:387-531) + corr_mlp (cotracker3_online.py:84). */
+/* EfficientUpdateFormer (cotracker.py:387-531) + corr_mlp (cotracker3_online.py:84).
+ *
+ * Folded form (window entry points only: ctk_forward_window, ctk_forward_window_batch, their graphs, ctk_window_tokens_batch).
+ * Nothing nonlinear lies between corr_mlp.fc2 and input_transform (cotracker3_online.py:205-247 concatenates and adds the
+ * time embedding), so with Win_l = the 256 input_transform columns of level l
+ *     tokens = sum_l h1_l (Win_l W2)^T + x_small Win_small^T + (in_bias_t + sum_l Win_l b2),     h1_l = GELU(fc1(volume_l)),
+ * and the products are weights like any other.  A struct with corr_fc1_* set and corr_fc2_w == corr_fc2_p == NULL says so:
+ *     in_w / in_p   [384, CTK_XF_LD]: columns [384 l, 384 l + 384) = Win_l W2, columns CTK_XF_SMALL.. = the x columns CTK_X_VIS..
+ *     in_bias_t     [S,384] with sum_l Win_l b2 added;   corr_fc2_b is ignored.
+ * One iteration then runs fc1 straight into the xf rows and ONE projection with K = CTK_XF_LD: fc2's launch and the write and
+ * re-read of its 1024 output columns are gone.  Every other entry point taking this struct answers CTK_E_NULL to it. */
 typedef struct ctk_model_weights {
   const float* corr_fc1_w;   /* [384, CTK_CORR_LD] zero-padded columns */
   const float* corr_fc1_b;   /* [384]  */
@@ -261,6 +281,11 @@ int ctk_window_batch_graph_create(const ctk_window_batch* batch, const ctk_model
 int ctk_corr_embed_batch_workspace_bytes(const ctk_window_batch* batch, size_t* out_bytes);
 int ctk_corr_embed_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* x, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* The first half of ONE iteration of ctk_forward_window_batch on its own (for tests): correlation stage, token assembly and
+ * input projection, by the launches the window call makes for these weights (folded or not), then tokens f32 [B*N*S, 384],
+ * row (b*N + n)*S + t, copied out of the workspace.  The state is not changed.  Workspace: that of the window call.      */
+int ctk_window_tokens_batch(const ctk_window_batch* batch, const ctk_model_weights* w, float* tokens, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* ---- stream state step: G query groups over ONE live video, state resident on the device ---------------------------------
  * The streaming glue of the reference (cotracker3_online.py:349-360 history growth, :411-440 support accumulation, :457-484
