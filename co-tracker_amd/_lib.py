@@ -230,6 +230,33 @@ class Warp:
         ]
 
 
+class Field:
+    """Holder of ctk_track_field_args and ctk_warp_field_args (include/ctk.h, "track field"), nested like Warp.Args and for the same
+    reason; their layouts are checked against the compiler by tests/test_field_cabi.py."""
+
+    POINTS_MAX, CS_MIN, CS_MAX, RADIUS_MAX, NO_LEVEL = 8192, 2, 6, 4, 255
+
+    class Args(C.Structure):
+        """ctk_track_field_args: history rows -> per frame a grid of displacements towards another frame, their levels and the counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("H", C.c_int32), ("W", C.c_int32), ("cs", C.c_int32), ("radius", C.c_int32), ("to", C.c_int32), ("lag", C.c_int32),
+            ("anchor_frame", C.c_int32), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp),
+            ("field", _fp), ("level", _fp), ("stats", _fp),
+        ]
+
+    class WarpArgs(C.Structure):
+        """ctk_warp_field_args: uint8 pictures and one field each -> the pictures resampled through it, and the dense flow."""
+        _fields_ = [
+            ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("layout", C.c_int32), ("border", C.c_int32),
+            ("cs", C.c_int32), ("reserved", C.c_int32), ("fill", C.c_uint8 * 4),
+            ("src_frame_stride", C.c_int64), ("src_row_stride", C.c_int64), ("dst_frame_stride", C.c_int64), ("dst_row_stride", C.c_int64),
+            ("field", _fp), ("src", _fp), ("dst", _fp), ("flow", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -314,6 +341,9 @@ SYMBOLS = {
     "ctk_fit_motion": (C.c_int, [_P(Motion.Args), _fp, C.c_size_t, _fp]),
     "ctk_warp_frames": (C.c_int, [_P(Warp.Args), _fp]),
     "ctk_smooth_path": (C.c_int, [_P(Warp.PathArgs), _fp]),
+    "ctk_track_field_workspace_bytes": (C.c_int, [_P(Field.Args), _P(C.c_size_t)]),
+    "ctk_track_field": (C.c_int, [_P(Field.Args), _fp, C.c_size_t, _fp]),
+    "ctk_warp_field": (C.c_int, [_P(Field.WarpArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

@@ -1036,6 +1036,15 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError("no stream is running on the device stream state")
         return gs.stabilize(frames, f0, **kw)
 
+    def stream_field(self, f0, F, **kw):
+        """The displacement fields of frames [f0, f0 + F) of the running (or just closed) stream towards another frame or an anchor,
+        interpolated from its own history by three launches and without a wait: ops.StreamGroups.field.  Serves a ring history and the
+        default one alike."""
+        gs = self._gstream
+        if gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state")
+        return gs.field(f0, F, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

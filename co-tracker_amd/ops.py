@@ -647,6 +647,274 @@ def stabilize(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor,
     return out, warp[0], state
 
 
+# ------------------------------------------------------------------------------------------
+# track field (csrc/field.hip; include/ctk.h, "track field")
+# ------------------------------------------------------------------------------------------
+_field_ws_cache = {}
+
+
+class FieldAnchor:
+    """One frame's row of a group, kept on the device for track_field's anchor form: coords float32 [G,N,2] (unscaled history
+    positions), visible uint8 [G,N], the frame number they were taken on and the group of a stream they belong to."""
+    __slots__ = ("coords", "visible", "frame", "group")
+
+    def __init__(self, coords: torch.Tensor, visible: torch.Tensor, frame: int, group: int = 0):
+        self.coords, self.visible, self.frame, self.group = coords, visible, int(frame), int(group)
+
+
+def _field_workspace(nbytes: int, device) -> torch.Tensor:
+    """The workspace of ctk_track_field (the sum pyramid), cached per device and grown by shape only, like _motion_workspace and for
+    the same reason a cache of its own."""
+    key = (device.index if device.index is not None else torch.cuda.current_device())
+    buf = _field_ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _field_ws_cache[key] = None
+        buf = _field_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
+    return buf
+
+
+def _field_cs(cell, who: str) -> int:
+    cell = int(cell)
+    cs = cell.bit_length() - 1
+    if cell < 1 or 1 << cs != cell or not L.Field.CS_MIN <= cs <= L.Field.CS_MAX:
+        raise ValueError(f"{who}: cell must be a power of two in {1 << L.Field.CS_MIN}..{1 << L.Field.CS_MAX}, got {cell}")
+    return cs
+
+
+def field_grid(size, cell: int = 16):
+    """(gh, gw): the nodes of track_field's grid over a picture of size = (H, W) with cells of `cell` pixels."""
+    cs = _field_cs(cell, "field_grid")
+    return ((int(size[0]) - 1) >> cs) + 2, ((int(size[1]) - 1) >> cs) + 2
+
+
+def _field_rules(a, size, cell, radius, to, lag, anchor, G: int, N: int, device, who: str) -> None:
+    """The picture, the grid and the "to" form of ctk_track_field_args; G, N: what an anchor must match."""
+    H, W, radius = int(size[0]), int(size[1]), int(radius)
+    if not (1 <= H <= 32768 and 1 <= W <= 32768 and 1 <= radius <= L.Field.RADIUS_MAX):
+        raise ValueError(f"{who}: size = (H, W) must lie in 1..32768 and radius in 1..{L.Field.RADIUS_MAX}")
+    if (to is not None) + (lag is not None) + (anchor is not None) != 1:
+        raise ValueError(f"{who}: exactly one of to (a frame), lag (frame f against f - lag) and anchor (FieldAnchor) says where the field leads")
+    a.H, a.W, a.cs, a.radius, a.reserved = H, W, _field_cs(cell, who), radius, 0
+    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
+    if to is not None:
+        a.to = int(to)
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif lag is not None:
+        a.lag = int(lag)
+        if a.lag == 0:
+            raise ValueError(f"{who}: lag must not be 0 (negative: forward flow)")
+    else:
+        c, v = anchor.coords, anchor.visible
+        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and tuple(c.shape) == (G, N, 2) and c.device == device and
+                c.is_contiguous() and isinstance(v, torch.Tensor) and v.dtype in (torch.uint8, torch.bool) and tuple(v.shape) == (G, N) and
+                v.device == device and v.is_contiguous()) or anchor.frame < 0:
+            raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
+                             f"frame >= 0")
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = anchor.frame, _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+
+
+def _field_launch(a, device, out, who: str):
+    """Allocates (or checks) the three outputs of ctk_track_field for the G, F and grid of `a`, then the three launches."""
+    gh, gw = ((a.H - 1) >> a.cs) + 2, ((a.W - 1) >> a.cs) + 2
+    shapes = ((a.G, a.F, gh, gw, 2), (a.G, a.F, gh, gw), (a.G, a.F, 4))
+    dtypes = (torch.int32, torch.uint8, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(sh, device=device, dtype=dt) for sh, dt in zip(shapes, dtypes))
+    else:
+        out = tuple(out)
+        if len(out) != 3 or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
+                                not t_.is_contiguous() for t_, sh, dt in zip(out, shapes, dtypes)):
+            raise ValueError(f"{who}: out must be contiguous (field int32 {list(shapes[0])}, level uint8 {list(shapes[1])}, stats int32 "
+                             f"{list(shapes[2])}) on {device}")
+    a.field, a.level, a.stats = (_ptr(t_) for t_ in out)
+    ws = _field_workspace(_query_bytes("ctk_track_field_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_track_field(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_track_field")
+    return out
+
+
+def track_field(tracks: torch.Tensor, visible: torch.Tensor, *, size, cell: int = 16, radius: int = 2, to: Optional[int] = None,
+                lag: Optional[int] = None, anchor: Optional[FieldAnchor] = None, scale=(1.0, 1.0), N_out: Optional[int] = None,
+                first_frame: int = 0, frames: Optional[int] = None, first_row: Optional[torch.Tensor] = None, out=None):
+    """A dense displacement field interpolated from the tracked points, per frame, by three launches and without a wait
+    (ctk_track_field; include/ctk.h and csrc/field_math.h have the rules).  Works on any result of any predictor here.  The field of
+    frame f lives on f's picture grid and leads to the matching position of a frame "to": a picture known on frame "to" is warped
+    backwards onto frame f by warp_field.
+
+    tracks   float32 [T,N,2] or [G,T,N,2], positions = tracks * scale; visible bool / uint8 [T,N] or [G,T,N].
+    size     (H, W) of the picture in the pixels of the scaled positions; cell: pixels per grid cell, a power of two 4..64; radius: the
+             reach of a point in cells, 1..4.
+    to / lag / anchor   exactly one: a fixed frame; frame f against f - lag (negative: forward flow); a FieldAnchor.
+    N_out    only the first N_out <= 8192 points are looked at (default: all N).  first_row int [N] / [G,N]: a point counts from that
+             frame on (INT32_MAX: never).
+    Rows are the frames first_frame .. first_frame + frames - 1 (default: to the end).  Returns (field int32 [G,F,gh,gw,2] in 1/256
+    pixel, node (i, j) at pixel (i cell, j cell); level uint8 [G,F,gh,gw]: 0 own support, l filled from pyramid level l, 255 nothing;
+    stats int32 [G,F,4] = (correspondences, nodes at level 0, highest level used, 0)) -- `out` when given."""
+    who = "track_field"
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
+            tracks.shape[-1] == 2):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
+    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
+    G, T, N, _ = tracks.shape
+    dev = tracks.device
+    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
+            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
+        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
+    visible = visible.reshape(G, T, N)
+    N_out = N if N_out is None else int(N_out)
+    if not 1 <= N_out <= min(N, L.Field.POINTS_MAX):
+        raise ValueError(f"{who}: N_out must lie in [1, {min(N, L.Field.POINTS_MAX)}]")
+    first_frame = int(first_frame)
+    F_ = T - first_frame if frames is None else int(frames)
+    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
+        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    a = L.Field.Args()
+    _field_rules(a, size, cell, radius, to, lag, anchor, G, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    # the C-ABI keeps the rows one call reads apart (rows of a ring must not alias): rows that hold no visible point are appended
+    rows = max(T, F_ + abs(a.lag), first_frame + F_ + max(-a.lag, 0))
+    if rows > T:
+        tracks = torch.cat([tracks, tracks.new_zeros(G, rows - T, N, 2)], dim=1)
+        visible = torch.cat([visible, visible.new_zeros(G, rows - T, N)], dim=1)
+    tracks, visible = tracks.contiguous(), visible.contiguous()
+    if first_row is not None:
+        big = torch.iinfo(torch.int32).max
+        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
+    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N_out, rows, first_frame, F_
+    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
+    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
+    a.first_row = _ptr(first_row)
+    return _field_launch(a, dev, out, who)
+
+
+def _field_surface(pics: torch.Tensor, layout: Optional[str], who: str):
+    """uint8 device pictures [F,H,W,3] / [F,3,H,W] (as _draw_surface) or masks [F,H,W] -> (C, layout, F, H, W, row_stride,
+    frame_stride), strides in elements."""
+    if isinstance(pics, torch.Tensor) and pics.dim() == 3 and pics.dtype == torch.uint8 and pics.is_cuda:
+        F_, H, W = pics.shape
+        row = pics.stride(1) if H > 1 else W
+        if F_ < 1 or (W > 1 and pics.stride(2) != 1) or row < W:
+            raise ValueError(f"{who}: the rows of the [F,H,W] pictures are not dense (strides {pics.stride()})")
+        return 1, "hwc", F_, H, W, row, (pics.stride(0) if F_ > 1 else H * row)
+    if not (isinstance(pics, torch.Tensor) and pics.dim() == 4):
+        raise ValueError(f"{who}: pictures must be a uint8 device tensor [F,H,W,3], [F,3,H,W] or [F,H,W]")
+    return (3,) + tuple(_draw_surface(pics, layout, who))
+
+
+def _warp_field_args(src: Optional[torch.Tensor], size, cell, border: str, fill, out, flow, layout: Optional[str], F_: int, who: str,
+                     device=None):
+    """ctk_warp_field_args but the field, from `src` and `out` (allocated dense when None), or from size = (H, W) alone when only the
+    flow is asked for -> (args, out, flow)."""
+    a = L.Field.WarpArgs()
+    a.cs, a.reserved = _field_cs(cell, who), 0
+    if border not in WARP_BORDERS:
+        raise ValueError(f"{who}: border must be one of {sorted(WARP_BORDERS)}, got {border!r}")
+    a.border = WARP_BORDERS[border]
+    if src is None:
+        a.F, a.H, a.W, a.C, a.layout = F_, int(size[0]), int(size[1]), 1, L.INGEST_HWC
+        a.src, a.dst, out = None, None, None
+    else:
+        C_, lay, F_, H, W, row, frame = _field_surface(src, layout, who)
+        device = src.device
+        fill = [int(v) for v in ((fill,) * 3 if isinstance(fill, int) else fill)]
+        if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
+            raise ValueError(f"{who}: fill must hold three values in 0..255 (or one)")
+        if out is None:
+            out = torch.empty(tuple(src.shape), dtype=torch.uint8, device=device)
+        elif out is src or not isinstance(out, torch.Tensor) or out.device != device or out.shape != src.shape:
+            raise ValueError(f"{who}: out must be uint8 pictures of the shape and device of the source, and not the source itself (a warp "
+                             f"cannot run in place)")
+        _, _, _, _, _, orow, oframe = _field_surface(out, lay, who)
+        rows, row_bytes = (H, C_ * W) if lay == "hwc" else (C_ * H, W)
+        ends = [t_.data_ptr() + (F_ - 1) * fs + (rows - 1) * rs + row_bytes for t_, fs, rs in ((src, frame, row), (out, oframe, orow))]
+        if src.data_ptr() < ends[1] and out.data_ptr() < ends[0]:
+            raise ValueError(f"{who}: out overlaps the source (a warp cannot run in place)")
+        a.F, a.H, a.W, a.C, a.layout = F_, H, W, C_, (L.INGEST_HWC if lay == "hwc" else L.INGEST_CHW)
+        for k in range(3):
+            a.fill[k] = fill[k]
+        a.src_frame_stride, a.src_row_stride, a.dst_frame_stride, a.dst_row_stride = frame, row, oframe, orow
+        a.src, a.dst = _ptr(src), _ptr(out)
+    if flow is True:
+        flow = torch.empty(a.F, a.H, a.W, 2, dtype=torch.float32, device=device)
+    elif flow is False or flow is None:
+        flow = None
+    elif not (isinstance(flow, torch.Tensor) and flow.dtype == torch.float32 and tuple(flow.shape) == (a.F, a.H, a.W, 2) and
+              flow.is_cuda and (device is None or flow.device == device) and flow.is_contiguous()):
+        raise ValueError(f"{who}: flow must be True or a contiguous float32 tensor [{a.F},{a.H},{a.W},2] on the device")
+    a.flow = _ptr(flow)
+    return a, out, flow
+
+
+def _warp_field_launch(a, field: torch.Tensor, who: str) -> None:
+    gh, gw = ((a.H - 1) >> a.cs) + 2, ((a.W - 1) >> a.cs) + 2
+    if not (isinstance(field, torch.Tensor) and field.dtype == torch.int32 and field.is_cuda and field.numel() == a.F * gh * gw * 2 and
+            tuple(field.shape[-3:]) == (gh, gw, 2) and field.is_contiguous()):
+        raise ValueError(f"{who}: field must be a contiguous int32 device tensor [{a.F},{gh},{gw},2] (track_field's, for this size and cell)")
+    a.field = _ptr(field)
+    L.check(L.load().ctk_warp_field(C.byref(a), _stream()), "ctk_warp_field")
+
+
+def warp_field(src: torch.Tensor, field: torch.Tensor, *, cell: int, border: str = "fill", fill=(0, 0, 0), out: Optional[torch.Tensor] = None,
+               flow=False, layout: Optional[str] = None):
+    """uint8 pictures or masks resampled through one displacement field each, on the device, by one launch and without a wait
+    (ctk_warp_field; include/ctk.h and csrc/field_math.h have the rules): out(x, y) = src((x, y) + field there), bilinear in 1/256
+    pixel with ctk_warp_frames' borders.  A zero field copies bit for bit, a constant field of whole pixels is a shifted copy.
+
+    src      uint8 [F,H,W,3], [F,3,H,W] or [F,H,W] (masks) on the device; strides and layout as warp_frames reads them.
+    field    int32 [F,gh,gw,2], 1/256 pixel, on track_field's grid for (H, W) and `cell`.
+    flow     True (or a float32 tensor [F,H,W,2] to fill): also the per-pixel displacement in pixels.
+    Returns out, or (out, flow) when a flow is asked for."""
+    who = "warp_field"
+    a, out, flow = _warp_field_args(src, None, cell, border, fill, out, flow, layout, 0, who)
+    _warp_field_launch(a, field, who)
+    return out if flow is None else (out, flow)
+
+
+def propagate(picture: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor, *, src_frame: int, frames=None, cell: int = 16,
+              radius: int = 2, border: str = "fill", fill=(0, 0, 0), scale=(1.0, 1.0), N_out: Optional[int] = None,
+              first_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """A picture (or mask, or paint layer) given on frame src_frame carried onto other frames along the tracked points, on the device:
+    track_field(to = src_frame) and warp_field -- four launches, no wait.  Works on any result of any predictor here.
+
+    picture  uint8 [H,W,3], [3,H,W] or [H,W] on the device, in the pixels of tracks * scale.
+    tracks   float32 [T,N,2] (or [1,T,N,2]); visible bool / uint8 [T,N].
+    frames   (first_frame, n), or None: every tracked frame.
+    Returns the pictures [n, ...] in the layout and dtype of `picture` (`out` when given)."""
+    who = "propagate"
+    if not (isinstance(picture, torch.Tensor) and picture.dtype == torch.uint8 and picture.is_cuda and picture.dim() in (2, 3)):
+        raise ValueError(f"{who}: picture must be a uint8 device tensor [H,W,3], [3,H,W] or [H,W]")
+    if not (isinstance(tracks, torch.Tensor) and tracks.dim() in (3, 4) and (tracks.dim() == 3 or tracks.shape[0] == 1)):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [1,T,N,2]")
+    T = tracks.shape[-3]
+    first_frame, n = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    if n < 1:
+        raise ValueError(f"{who}: frames = (first_frame, n) with n >= 1")
+    src = picture[None].expand(n, *picture.shape)  # (a frame stride of 0: every output picture reads the one source)
+    a, out, _ = _warp_field_args(src, None, cell, border, fill, out, None, None, 0, who)
+    field = track_field(tracks, visible, size=(a.H, a.W), cell=cell, radius=radius, to=int(src_frame), scale=scale, N_out=N_out,
+                        first_frame=first_frame, frames=n, first_row=first_row)[0]
+    _warp_field_launch(a, field[0], who)
+    return out
+
+
+def dense_flow(tracks: torch.Tensor, visible: torch.Tensor, *, size, lag: int = 1, frames=None, cell: int = 16, radius: int = 2,
+               scale=(1.0, 1.0), N_out: Optional[int] = None, first_row: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """A dense flow picture per frame interpolated from the tracked points, on the device: track_field(lag) and warp_field's flow --
+    four launches, no wait.  flow[j, y, x] = the displacement in pixels from pixel (x, y) of frame f to its position on frame f - lag
+    (a negative lag: forward flow).  size = (H, W); frames = (first_frame, n) or None: every frame.  Returns float32 [n,H,W,2]."""
+    who = "dense_flow"
+    if not (isinstance(tracks, torch.Tensor) and tracks.dim() in (3, 4) and (tracks.dim() == 3 or tracks.shape[0] == 1)):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [1,T,N,2]")
+    T = tracks.shape[-3]
+    first_frame, n = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    field = track_field(tracks, visible, size=size, cell=cell, radius=radius, lag=lag, scale=scale, N_out=N_out, first_frame=first_frame,
+                        frames=n, first_row=first_row)[0]
+    a, _, flow = _warp_field_args(None, size, cell, "fill", (0, 0, 0), None, True if out is None else out, None, n, who, device=field.device)
+    _warp_field_launch(a, field[0], who)
+    return flow
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -1383,6 +1651,51 @@ class StreamGroups:
         _warp_launch(a, warp, frames.device, who)
         self._stab[group] = (f0 + F_, state, alpha, (key, post))
         return out, warp[0]
+
+    def field(self, f0: int, F: int, *, size, cell: int = 16, radius: int = 2, to: Optional[int] = None, lag: Optional[int] = None,
+              anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+              first_row: Optional[torch.Tensor] = None, group: Optional[int] = None, out=None):
+        """The displacement fields of frames f0 .. f0 + F - 1 towards a frame "to" (one of `to`, `lag`, `anchor`: track_field has the
+        picture) interpolated from the first N_out points of every group (or of `group` alone) straight from the stream's own history
+        and logits -- no emit in between --, by the three launches of ctk_track_field: visibility is emit's sigmoid(vis) *
+        sigmoid(conf) > thresh, positions are history coords * scale, size = (H, W) is in those pixels.  first_row int32 [G,N] (what
+        emit takes) on the device.  Every frame that is read (those >= 0) must be among the committed ones the history still holds:
+        ValueError otherwise; an anchor needs no frame but its own copy.  -> (field [G,F,gh,gw,2], level [G,F,gh,gw], stats [G,F,4])
+        on the device.  No wait."""
+        who = "field"
+        N_out = self.N if N_out is None else int(N_out)
+        if not 1 <= N_out <= min(self.N, L.Field.POINTS_MAX):
+            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Field.POINTS_MAX)}]")
+        f0, F_, dev = int(f0), int(F), self.queries.device
+        g0, G = (0, self.G) if group is None else (int(group), 1)
+        if not 0 <= g0 < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        a = L.Field.Args()
+        _field_rules(a, size, cell, radius, to, lag, anchor, G, self.N, dev, who)
+        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
+            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
+        lo, hi = f0, f0 + F_ - 1  # the frames that are read
+        if a.to >= 0:
+            lo, hi = min(lo, a.to), max(hi, a.to)
+        elif a.lag != 0:
+            lo, hi = min(lo, max(f0 - a.lag, 0)), max(hi, f0 + F_ - 1 - a.lag)
+        if hi >= self.committed:
+            raise ValueError(f"{who}: frames up to {hi} lie beyond what has been tracked ({self.committed} frames)")
+        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
+        if lo < oldest:
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) have left the history: it holds the last {self.T_cap} of {self.committed} "
+                             f"frames (pin the source frame while it is there)")
+        if max(hi - lo + 1, F_ + abs(a.lag)) > self.T_cap:  # (ctk_track_field keeps the rows one call reads apart)
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) need more than the {self.T_cap} history rows one call may span")
+        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
+                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
+            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
+        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
+        a.visible = None
+        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        return _field_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -614,6 +614,99 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                                                 min_base=min_base, seed=seed)
         return (res[0] if one else res), warp
 
+    def _field_stream(self, who):
+        """The running stream's device state for pin / propagate / dense_flow, and the scale of history positions to raw-video pixels."""
+        if self.v2:
+            raise NotImplementedError(f"CoTracker2 keeps no stream state on the device: {who} on a v2 predictor is not implemented")
+        gs = getattr(self.model, "_gstream", None)
+        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+        (H, W), (ih, iw) = self._hw, self.interp_shape
+        return gs, ((W - 1) / (iw - 1), (H - 1) / (ih - 1))
+
+    def _field_frames(self, gs, n, first_frame, who):
+        done = gs.committed
+        n = (min(self.step, done) if first_frame is None else done - int(first_frame)) if n is None else int(n)
+        first_frame = done - n if first_frame is None else int(first_frame)
+        if n < 1 or first_frame < 0 or first_frame + n > done:
+            raise ValueError(f"{who}: frames [{first_frame}, {first_frame + n}) lie beyond what has been tracked ({done} frames)")
+        return first_frame, n
+
+    @torch.no_grad()
+    def pin(self, frame=None, group=0):
+        """Not in the reference: keeps where the points of query set `group` are on `frame` (default: the newest tracked one) --
+        device copies of that frame's row of the stream's history (positions, and the visibility the returned results would call
+        visible) and the frame number, by one launch and without a wait.  The anchor (ops.FieldAnchor) is what propagate() carries a
+        picture of that frame on with after a ring (history_frames) has dropped the frame itself.  A frame still inside the window
+        being tracked is refined by the next step: pin it once it is final, or pin again.  ValueError when the frame has left the
+        ring or has not been tracked."""
+        from . import ops
+        gs, _ = self._field_stream("pin")
+        frame, group = gs.committed - 1 if frame is None else int(frame), int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"pin: group must lie in [0, {gs.G})")
+        if not 0 <= frame < gs.committed:
+            raise ValueError(f"pin: frame {frame} lies beyond what has been tracked ({gs.committed} frames)")
+        coords, visible = self.model.stream_emit(frame, frame + 1, N_out=None, scale=(1.0, 1.0), logits=False, thresh=0.6,
+                                                 first_row=self._emit_first_row())
+        return ops.FieldAnchor(coords[group:group + 1, 0], visible[group:group + 1, 0].view(torch.uint8), frame, group)
+
+    @torch.no_grad()
+    def propagate(self, picture, anchor_or_frame, first_frame=None, n=None, cell=16, radius=2, border="fill", fill=(0, 0, 0), out=None,
+                  group=0):
+        """Not in the reference, which lays a grid on a segm_mask of the first frame and cannot say where that mask is later: a
+        `picture` -- raw-video resolution, uint8, [H,W,3], [3,H,W] or a mask [H,W], on the device -- that shows frame
+        `anchor_or_frame` (a frame number the history still holds, or an anchor from pin()) carried onto the n frames from
+        first_frame on along the N (+ spare_points) user-visible points of query set `group`, by four launches and without a wait
+        (ops.StreamGroups.field on the stream's own history and logits, then ops.warp_field).  Default: the frames of the window
+        just tracked, as in draw().  A dense displacement field is interpolated from the points visible on both frames (cell: pixels
+        per grid cell, a power of two 4..64; radius: the reach of a point in cells, 1..4; holes are filled from coarser levels) and
+        the picture is resampled backwards through it, bilinear in 1/256 pixel; border "fill" paints what comes from outside the
+        picture with `fill`, "edge" repeats the edge pixels.  The weighting is zeroth order: exact to about a tenth of a pixel
+        inside a covered region, biased near its rim and blocky across large holes.  The stream's tracks are untouched.  Returns the
+        pictures [n, ...] in the layout of `picture` (a new tensor, or `out`)."""
+        from . import ops
+        who = "propagate"
+        gs, scale = self._field_stream(who)
+        H, W = self._hw
+        if not (isinstance(picture, torch.Tensor) and picture.dtype == torch.uint8 and picture.is_cuda and
+                tuple(picture.shape) in ((H, W, 3), (3, H, W), (H, W))):
+            raise ValueError(f"{who}: picture must be a uint8 device tensor [{H},{W},3], [3,{H},{W}] or [{H},{W}]")
+        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        if isinstance(anchor_or_frame, ops.FieldAnchor):
+            if anchor_or_frame.group != int(group):
+                raise ValueError(f"{who}: the anchor was pinned on group {anchor_or_frame.group}, not {group}")
+            where = dict(anchor=anchor_or_frame)
+        else:
+            where = dict(to=int(anchor_or_frame))
+        layout = None if picture.dim() == 2 else ("hwc" if tuple(picture.shape) == (H, W, 3) else "chw")
+        src = picture[None].expand(n, *picture.shape)  # (a frame stride of 0: every output picture reads the one source)
+        a, out, _ = ops._warp_field_args(src, None, cell, border, fill, out, None, layout, 0, who)
+        field = self.model.stream_field(first_frame, n, size=(H, W), cell=cell, radius=radius, N_out=self.N, scale=scale, thresh=0.6,
+                                        first_row=self._emit_first_row(), group=int(group), **where)[0]
+        ops._warp_field_launch(a, field[0], who)
+        return out
+
+    @torch.no_grad()
+    def dense_flow(self, n=None, first_frame=None, lag=1, cell=16, radius=2, group=0, out=None):
+        """Not in the reference (whose dense mode tracks every pixel at the full cost of the model): a dense flow picture of each of
+        the n frames from first_frame on (default: the frames of the window just tracked) interpolated from the N (+ spare_points)
+        user-visible points of query set `group`, by four launches and without a wait (ops.StreamGroups.field with `lag`, then the
+        flow output of ops.warp_field).  flow[j, y, x] = the displacement in raw-video pixels from pixel (x, y) of frame f to the
+        matching position on frame f - lag (a negative lag: forward flow, towards frames already tracked).  cell, radius and the
+        limits are propagate()'s.  Returns float32 [n,H,W,2] on the device (a new tensor, or `out`)."""
+        from . import ops
+        who = "dense_flow"
+        gs, scale = self._field_stream(who)
+        H, W = self._hw
+        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        a, _, flow = ops._warp_field_args(None, (H, W), cell, "fill", (0, 0, 0), None, True if out is None else out, None, n, who,
+                                          device=self.queries.device)
+        field = self.model.stream_field(first_frame, n, size=(H, W), cell=cell, radius=radius, lag=lag, N_out=self.N, scale=scale,
+                                        thresh=0.6, first_row=self._emit_first_row(), group=int(group))[0]
+        ops._warp_field_launch(a, field[0], who)
+        return flow
+
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
         everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""

@@ -52,6 +52,10 @@ extern "C" {
  *       and in_bias_t carries the folded bias (see the struct).  The window entry points take it; the stage entry points that
  *       need fc2 or the [384, CTK_X_LD] projection still answer CTK_E_NULL.  + ctk_window_tokens_batch (the tokens one
  *       iteration of a window hands to the update former, for tests).
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_track_field and ctk_track_field_workspace_bytes on the
+ *       new struct ctk_track_field_args, and ctk_warp_field on the new struct ctk_warp_field_args: a dense displacement field
+ *       interpolated from the tracked points on a grid of nodes (integer tent weights, int64 sums, a sum pyramid that fills the
+ *       holes), and uint8 pictures or masks resampled through such a field (csrc/field_math.h); three launches and one, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_warp_frames on the new struct ctk_warp_args and
  *       ctk_smooth_path on the new struct ctk_smooth_path_args: uint8 pictures resampled under a 2 x 3 matrix each (Q24 fixed point,
  *       bilinear in 1/256 pixel), and the causal path rule that turns per-frame camera motions into such matrices
@@ -725,6 +729,125 @@ typedef struct ctk_smooth_path_args {
   float* warp;                /* [G,F,2,3] */
 } ctk_smooth_path_args;
 int ctk_smooth_path(const ctk_smooth_path_args* a, void* stream);
+
+/* ---- track field: a dense displacement field from the tracked points, and pictures carried along it ---------------------------------
+ * For a caller whose tracks are on the device and whose scene does not move as one plane: what ctk_fit_motion's single matrix cannot
+ * say.  An object mask, a paint stroke or a texture known on one frame is carried onto other frames along the tracked points, or a
+ * dense flow picture is made of them, instead of a scattered-data interpolation on the host or a torch chain of float atomics,
+ * F.interpolate and grid_sample.  The rules are integer arithmetic and one IEEE double division per node component, stated once in
+ * csrc/field_math.h, and the results depend on them alone.
+ *
+ * ctk_track_field: for group g and frame f in [f0, f0 + F) ("at") against a frame "to", the field on the picture grid of frame f whose
+ * value at a position is the displacement that leads to the matching position of frame "to": a picture known on frame "to" is
+ * warped BACKWARDS onto frame f by ctk_warp_field.
+ *   history    hist_coords [G,R,N,2] (and hist_vis / hist_conf [G,R,N]), the row of frame f is f % R, as in ctk_fit_motion.
+ *   position   ctk_fit_motion's: v = x * sx (y * sy), one float32 multiplication; valid iff finite and |v| <= 8192;
+ *              P = (int)rintf(v * 16.0f), 1/16 pixel.  P is on frame f, Q on frame "to", d = Q - P, |d| <= 2^18.
+ *   to         exactly one of three forms: a fixed frame to >= 0 (lag = 0, no anchor);  f - lag with lag != 0 (to = -1, no anchor; a
+ *              negative lag gives forward flow);  an anchor (to = -1, lag = 0): anchor_coords [G,N,2] float32 (scaled by sx, sy like the
+ *              history) and anchor_visible [G,N] uint8, taken by the caller on frame anchor_frame >= 0 -- how a picture is carried on
+ *              after a ring has dropped its source frame.
+ *   pair       slot n is a correspondence iff both frames are >= 0, both are >= first_row[g, n] (optional int32 [G,N]; INT32_MAX: an
+ *              empty slot; in anchor form anchor_frame counts as the "to" frame, so a slot released and reassigned after the anchor
+ *              was taken drops out), both positions are valid and both are visible: by ctk_fit_motion's rule bit for bit on the
+ *              history (visible [G,R,N] uint8, or sigmoid(vis) * sigmoid(conf) > thresh), anchor_visible[g, n] != 0 on an anchor.
+ *              Only the first N_out <= 8192 slots are looked at; M = the number of correspondences.
+ *   grid       cell c = 1 << cs, cs in 2..6; gw = ((W - 1) >> cs) + 2 nodes across and gh = ((H - 1) >> cs) + 2 down; node (i, j) sits
+ *              at pixel (i c, j c), Nx = i * c * 16 in 1/16 pixel.
+ *   weight     a separable tent of `radius` cells (1..4), rad = radius * c * 16: wx = max(0, 1024 - (|Px - Nx| * 1024) / rad), an
+ *              integer floor division of non-negatives, wy likewise, w = wx * wy <= 2^20.
+ *   sums       per node Wn = sum w, Sx = sum w d.x, Sy = sum w d.y in int64 (Wn <= 2^33, |S| <= 2^51): integer sums, so the order of
+ *              accumulation does not matter and nothing needs float atomics.
+ *   pyramid    level l + 1 has ceil(h / 2) x ceil(w / 2) nodes, each the sum of its up-to-four children, up to 1 x 1.
+ *   value      node (i, j) takes the lowest level l at which node (j >> l, i >> l) has Wn >= 1:
+ *              F = (int32)llrint((double)(S * 16) / (double)Wn) per component: 1/256 pixel, one IEEE division, round half to even.
+ *              Where even the 1 x 1 level is empty (M = 0, or every correspondence beyond the reach of every node) F = 0 and the level
+ *              is 255.
+ *   outputs    field int32 [G,F,gh,gw,2] (x, y);  level uint8 [G,F,gh,gw]: 0 own support, l > 0 filled from level l, 255 nothing;
+ *              stats int32 [G,F,4] = (M, nodes at level 0, highest level used -- 255 where nothing --, 0).  Every element is written
+ *              by one plain store.
+ * Three launches on `stream`: a gather (one workgroup per (g, f, 16 x 16 node tile); the correspondences are quantised once per
+ * workgroup and staged through LDS in chunks of 256, culled against the tile's box grown by rad; a thread owns one node and keeps its
+ * three sums in registers), the pyramid (one workgroup per (g, f)) and the values.  No atomics, no host synchronisation, capture-safe;
+ * writes the three outputs and the workspace only.  ctk_track_field_workspace_bytes answers G * F * 24 bytes * the nodes of all levels.
+ * Before any launch: NULL a, hist_coords, field, level or stats, `visible` NULL with hist_vis or hist_conf NULL, one of anchor_coords /
+ * anchor_visible without the other, a NULL workspace: CTK_E_NULL; G, N, N_out, R or F <= 0, N_out > N, N_out > 8192, f0 < 0,
+ * f0 + F > 2^30, F > 65535, G > 65535, G * N > 2^26, H or W outside 1..CTK_INGEST_MAX_SIDE, cs outside 2..6, radius outside 1..4, not
+ * exactly one "to" form (to < -1, to >= 0 with lag != 0 or an anchor, lag != 0 with an anchor, none of the three), to > 2^30,
+ * |lag| > 2^30, anchor_frame outside 0..2^30 with an anchor, rows of a ring that would alias (F + |lag| > R; with a fixed frame the
+ * span of [f0, f0 + F) and `to` > R; F > R with an anchor), sx or sy not finite or <= 0, a NaN thresh without `visible`,
+ * reserved != 0, workspace_bytes below what the query answers: CTK_E_SHAPE; hist_coords, anchor_coords, field or the workspace not
+ * 8-byte aligned, stats not 4-byte aligned: CTK_E_ALIGN.  Frames whose "to" frame is negative are no error: they have no
+ * correspondences.  The query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor is given).
+ *
+ * ctk_warp_field: picture j of dst = picture j of src resampled through field[j]; output pixel (x, y):
+ *   cell       i = x >> cs, ax = x & (c - 1); j, ay likewise; i + 1 <= gw - 1 holds by the grid rule
+ *   position   D = (c - ax)(c - ay) F[j][i] + ax (c - ay) F[j][i+1] + (c - ax) ay F[j+1][i] + ax ay F[j+1][i+1] in int64;
+ *              X = x * 256 + ((D + (c * c >> 1)) >> 2 cs), an arithmetic shift; Y likewise; ix = X >> 8, fx = X & 255
+ *   taps       the four taps, the CTK_WARP_FILL / CTK_WARP_EDGE borders and the blend are exactly ctk_warp_frames'.  Nothing outside
+ *              the picture is read.  A zero field copies the source bit for bit; an integer-pixel constant field is a shifted copy.
+ *   flow       (optional, float32 [F,H,W,2]) = (float)(X - x * 256) / 256.0f and the same for Y: exact for |F| <= 2^24
+ *   pictures   F pictures of H x W, C = 3 or C = 1 channels (a mask); layouts, strides (a row holds C W or W elements, a frame H or
+ *              C H rows), fill and border as in ctk_warp_args; src_frame_stride = 0 is allowed too: every picture is resampled
+ *              from the one source.  src and dst must not overlap.  field int32 [F,gh,gw,2] with the grid
+ *              of ctk_track_field for (H, W, cs).  dst and flow are each optional, at least one must be given; src may be NULL when
+ *              dst is.
+ * One launch on `stream` (a workgroup reads the nodes round its 64 x 16 output tile, whose values bound the tile's source box, stages
+ * that box in 16 KiB of LDS or reads memory directly where it does not fit), no atomics, no host synchronisation, capture-safe; writes
+ * dst and flow only.  Before the launch: NULL a or field, dst and flow both NULL, dst without src: CTK_E_NULL; F outside 1..65535, H
+ * or W outside 1..CTK_INGEST_MAX_SIDE, C not 1 or 3, an unknown layout or border, cs outside 2..6, reserved != 0, and with dst a row
+ * stride smaller than a row, a frame stride smaller than a frame (but src_frame_stride = 0), a stride above 2^40 or overlapping byte ranges of src and dst:
+ * CTK_E_SHAPE; field or flow not 8-byte aligned: CTK_E_ALIGN.
+ *
+ * Known limits.  The weighting is zeroth order (a weighted mean of displacements, no local affine fit per node).  On a 480 x 270 picture
+ * with a jittered 24 x 24 grid of points under a similarity of 1.7 degrees and 2 % (c = 16, radius 2) the field is exact to about
+ * 0.05-0.14 pixel inside a covered region, biased by about 0.6 pixel in the outermost `radius` cells, where the support is one-sided,
+ * and blocky across large holes: 3.2 pixels across a hole of 180 x 140 pixels.                                                    */
+typedef struct ctk_track_field_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t H, W;               /* the picture of a frame, in the pixels of the scaled positions     */
+  int32_t cs;                 /* log2 of the cell, 2..6                                            */
+  int32_t radius;             /* reach of a point, in cells, 1..4                                  */
+  int32_t to;                 /* a fixed "to" frame, or -1                                         */
+  int32_t lag;                /* "to" = f - lag, or 0                                              */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  int32_t* field;             /* [G,F,gh,gw,2] */
+  uint8_t* level;             /* [G,F,gh,gw] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_track_field_args;
+int ctk_track_field_workspace_bytes(const ctk_track_field_args* a, size_t* out_bytes);
+int ctk_track_field(const ctk_track_field_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct ctk_warp_field_args {
+  int32_t F, H, W;            /* pictures, and their size in pixels                                */
+  int32_t C;                  /* channels: 3, or 1 (a mask)                                        */
+  int32_t layout;             /* CTK_INGEST_HWC / CTK_INGEST_CHW (the same thing for C = 1)        */
+  int32_t border;             /* CTK_WARP_FILL / CTK_WARP_EDGE                                     */
+  int32_t cs;                 /* log2 of the field's cell, 2..6                                    */
+  int32_t reserved;           /* 0 */
+  uint8_t fill[4];            /* the value of a tap outside the picture, per channel               */
+  int64_t src_frame_stride;   /* elements between two pictures of src; 0: one source for all       */
+  int64_t src_row_stride;     /* elements between two pixel rows of src                            */
+  int64_t dst_frame_stride;
+  int64_t dst_row_stride;
+  const int32_t* field;       /* [F,gh,gw,2], on the device                                        */
+  const uint8_t* src;
+  uint8_t* dst;               /* or NULL */
+  float* flow;                /* [F,H,W,2], or NULL */
+} ctk_warp_field_args;
+int ctk_warp_field(const ctk_warp_field_args* a, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
