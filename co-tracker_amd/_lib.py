@@ -257,6 +257,27 @@ class Field:
         ]
 
 
+class Objects:
+    """Holder of ctk_fit_objects_args (include/ctk.h, "fit objects"), nested like Motion.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_objects_cabi.py."""
+
+    OBJECTS_MAX, NONE = 16, 127
+
+    class Args(C.Structure):
+        """ctk_fit_objects_args: history rows (and labels, or none) -> per frame up to L motion matrices, a label per point, and each
+        fit's counts and box."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("L", C.c_int32), ("min_points", C.c_int32),
+            ("model", C.c_int32), ("K", C.c_int32), ("seed", C.c_uint32),
+            ("tol", C.c_float), ("min_base", C.c_float), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp), ("labels", _fp),
+            ("motion", _fp), ("label", _fp), ("stats", _fp), ("box", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -344,6 +365,8 @@ SYMBOLS = {
     "ctk_track_field_workspace_bytes": (C.c_int, [_P(Field.Args), _P(C.c_size_t)]),
     "ctk_track_field": (C.c_int, [_P(Field.Args), _fp, C.c_size_t, _fp]),
     "ctk_warp_field": (C.c_int, [_P(Field.WarpArgs), _fp]),
+    "ctk_fit_objects_workspace_bytes": (C.c_int, [_P(Objects.Args), _P(C.c_size_t)]),
+    "ctk_fit_objects": (C.c_int, [_P(Objects.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

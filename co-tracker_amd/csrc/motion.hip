@@ -16,7 +16,7 @@
 //             divides and writes the matrix and the stats.
 #include "ctk_common.h"
 #include "ctk_profile.h"
-#include "motion_math.h"
+#include "motion_device.h"  // the wave reductions, motion_hyp_at; motion_math.h
 
 namespace {
 
@@ -38,28 +38,10 @@ struct MotionParams {
   int32_t* stats;
 };
 
-__device__ __forceinline__ int64_t motion_wave_max(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int64_t w = __shfl_xor((long long)v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int64_t motion_wave_sum(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor((long long)v, o, 64);
-  return v;
-}
-
 // the winner (or any hypothesis) rebuilt from its number
 template <int MODEL>
 __device__ __forceinline__ bool motion_make_hyp(const MotionParams& p, const int4* pts, int f, int k, int M, CtkMotionHyp* h) {
-  int i, j;
-  ctk_motion_sample(p.seed, f, k, M, MODEL, &i, &j);
-  const int4 a = pts[i], b = pts[j];
-  return ctk_motion_hyp(MODEL, a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, p.T, p.base2, h);
+  return motion_hyp_at<MODEL>(p.seed, p.T, p.base2, pts, f, k, M, h);
 }
 
 // grid: x = frame f0 + x, y = group; dynamic LDS: N_out * 16 bytes

@@ -1045,6 +1045,15 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError("no stream is running on the device stream state")
         return gs.field(f0, F, **kw)
 
+    def stream_objects(self, f0, F, **kw):
+        """Up to `objects` motion fits per frame [f0, f0 + F) of the running (or just closed) stream over sub-lists of its points --
+        labelled regions, or what the earlier fits left -- against f - lag, a fixed frame or an anchor, from its own history by one
+        launch and without a wait: ops.StreamGroups.objects.  Serves a ring history and the default one alike."""
+        gs = self._gstream
+        if gs is None or not gs.live or gs.committed == 0:
+            raise RuntimeError("no stream is running on the device stream state")
+        return gs.objects(f0, F, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

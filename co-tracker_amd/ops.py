@@ -915,6 +915,124 @@ def dense_flow(tracks: torch.Tensor, visible: torch.Tensor, *, size, lag: int = 
     return flow
 
 
+# ------------------------------------------------------------------------------------------
+# fit objects (csrc/objects.hip; include/ctk.h, "fit objects")
+# ------------------------------------------------------------------------------------------
+OBJECT_NONE = L.Objects.NONE
+
+
+class ObjectSet:
+    """Which points of a query set belong to which object, and the frame that was decided on: labels int8 [N] on the device (-1: no
+    object's), the anchor (FieldAnchor) pinned on that frame, and the number of objects.  What split_objects() and label_objects()
+    of the online predictor return and follow() takes."""
+    __slots__ = ("labels", "anchor", "objects")
+
+    def __init__(self, labels: torch.Tensor, anchor: FieldAnchor, objects: int):
+        self.labels, self.anchor, self.objects = labels, anchor, int(objects)
+
+
+def _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device,
+                   who: str) -> None:
+    """The rounds, the fit and the source form of ctk_fit_objects_args; G, N: what labels and an anchor must match.  `to` or `anchor`
+    replaces the lag; both at once are refused."""
+    objects, min_points = int(objects), int(min_points)
+    if not 1 <= objects <= L.Objects.OBJECTS_MAX or not 1 <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: objects must lie in 1..{L.Objects.OBJECTS_MAX} and min_points in 1..{L.Motion.POINTS_MAX}")
+    if to is not None and anchor is not None:
+        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
+    _motion_rules(a, 1 if (to is not None or anchor is not None) else lag, model, tol, hypotheses, min_base, seed, who)
+    a.L, a.min_points = objects, min_points
+    a.to, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, None, None
+    if to is not None:
+        a.to, a.lag = int(to), 0
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif anchor is not None:
+        c, v = anchor.coords, anchor.visible
+        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and tuple(c.shape) == (G, N, 2) and c.device == device and
+                c.is_contiguous() and isinstance(v, torch.Tensor) and v.dtype in (torch.uint8, torch.bool) and tuple(v.shape) == (G, N) and
+                v.device == device and v.is_contiguous()) or anchor.frame < 0:
+            raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
+                             f"frame >= 0")
+        a.lag, a.anchor_frame = 0, anchor.frame
+        a.anchor_coords, a.anchor_visible = _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+    a.labels = None
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int8 and labels.device == device and labels.numel() == G * N and
+                labels.shape[-1] == N and labels.is_contiguous()):
+            raise ValueError(f"{who}: labels must be a contiguous int8 tensor [{N}] or [{G},{N}] on {device}")
+        a.labels = _ptr(labels)
+
+
+def _objects_launch(a, device, who: str):
+    """Allocates the four outputs of ctk_fit_objects for the G, F, L and N_out of `a`, then the launch."""
+    out = (torch.empty((a.G, a.F, a.L, 2, 3), device=device, dtype=torch.float32), torch.empty((a.G, a.F, a.N_out), device=device, dtype=torch.int8),
+           torch.empty((a.G, a.F, a.L, 4), device=device, dtype=torch.int32), torch.empty((a.G, a.F, a.L, 4), device=device, dtype=torch.int32))
+    a.motion, a.label, a.stats, a.box = (_ptr(t_) for t_ in out)
+    ws = _motion_workspace(_query_bytes("ctk_fit_objects_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_objects(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_objects")
+    return out
+
+
+def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional[torch.Tensor] = None, objects: int = 4, lag: int = 1,
+                to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, model: str = "similarity", tol: float = 2.0,
+                hypotheses: int = 128, min_base: float = 16.0, min_points: int = 8, seed: int = 0, scale=(1, 1), frames=None,
+                first_row: Optional[torch.Tensor] = None):
+    """Which points move together, and how each such group has moved: up to `objects` robust fits per frame over sub-lists of the
+    tracked points, by one launch and without a wait (ctk_fit_objects; include/ctk.h and csrc/objects_math.h have the rules).  Works on
+    any result of any predictor here, offline ones included.
+
+    tracks   float32 [T,N,2] or [G,T,N,2] (N <= 8192), positions = tracks * scale; visible bool / uint8 [T,N] or [G,T,N].
+    source   the matrix of frame f maps a source frame onto f: f - lag (the default), a fixed frame `to`, or a FieldAnchor (positions
+             kept from a frame the tracks no longer hold); `to` or `anchor` replaces the lag.  A point counts when it is visible on
+             both frames (and at or above first_row: int [N] / [G,N], INT32_MAX: never).
+    labels   int8 [N] / [G,N], labels mode: round r fits the points labelled r (anything outside 0..objects-1, -1 by convention:
+             no round's), the rounds are independent.  None, split mode: round 0 fits all points, round r + 1 what round r's
+             inliers left; a round with fewer than min_points inliers ends the rounds.  Split mode's round order is by size -- most
+             inliers first -- per pair of frames and NOT stable from pair to pair: split once, then follow by labels.
+    Each round is fit_motion's fit (model, tol, hypotheses, min_base) seeded with seed ^ mix(r).  Rows are the frames of
+    frames = (first_frame, n); None: every tracked frame.  Returns (motion float32 [G,F,objects,2,3]: position on frame f = motion @
+    (position on the source frame, 1), the identity where nothing was fitted; label int8 [G,F,N]: -1 not on both frames, r = inlier of
+    round r, 127 (OBJECT_NONE) = no round took it; stats int32 [G,F,objects,4] = (points of the round, inliers, best hypothesis or -1,
+    0); box int32 [G,F,objects,4] = (min x, min y, max x, max y) of the round's inliers on frame f in 1/16 pixel, (0, 0, -1, -1) where
+    nothing was fitted)."""
+    who = "fit_objects"
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
+            tracks.shape[-1] == 2):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
+    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
+    G, T, N, _ = tracks.shape
+    dev = tracks.device
+    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
+            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
+        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
+    visible = visible.reshape(G, T, N)
+    if not 1 <= N <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: between 1 and {L.Motion.POINTS_MAX} points per group, got {N}")
+    first_frame, F_ = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
+    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
+        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    a = L.Objects.Args()
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1 and G > 1:
+        labels = labels.expand(G, -1).contiguous()
+    _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    rows = max(T, F_ + a.lag)  # the C-ABI keeps F + lag <= R (rows of a ring must not alias): rows that no frame reads are appended
+    if rows > T:
+        tracks = torch.cat([tracks, tracks.new_zeros(G, rows - T, N, 2)], dim=1)
+        visible = torch.cat([visible, visible.new_zeros(G, rows - T, N)], dim=1)
+    tracks, visible = tracks.contiguous(), visible.contiguous()
+    if first_row is not None:
+        big = torch.iinfo(torch.int32).max
+        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
+    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N, rows, first_frame, F_
+    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
+    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
+    a.first_row = _ptr(first_row)
+    return _objects_launch(a, dev, who)
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -1696,6 +1814,53 @@ class StreamGroups:
         a.visible = None
         a.first_row = None if first_row is None else _ptr(first_row[g0:])
         return _field_launch(a, dev, out, who)
+
+    def objects(self, f0: int, F: int, *, labels: Optional[torch.Tensor] = None, objects: int = 4, lag: int = 1, to: Optional[int] = None,
+                anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+                first_row: Optional[torch.Tensor] = None, model: str = "similarity", tol: float = 2.0, hypotheses: int = 128,
+                min_base: float = 16.0, min_points: int = 8, seed: int = 0, group: Optional[int] = None):
+        """Up to `objects` fits per frame f0 .. f0 + F - 1 over the first N_out points of every group (or of `group` alone), each frame
+        against a source frame (f - lag, a fixed `to`, or an `anchor`: fit_objects has the picture), straight from the stream's own
+        history and logits -- no emit in between --, by the one launch of ctk_fit_objects: visibility is emit's sigmoid(vis) *
+        sigmoid(conf) > thresh, positions are history coords * scale, tol and min_base are in those pixels.  labels int8 [G,N] (of
+        the groups asked for) on the device: labels mode; None: split mode.  first_row int32 [G,N] (what emit takes) on the device.
+        Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError otherwise; an anchor
+        needs no frame but its own copy.  -> (motion [G,F,objects,2,3], label [G,F,N_out], stats [G,F,objects,4], box
+        [G,F,objects,4]) on the device.  No wait."""
+        who = "objects"
+        N_out = self.N if N_out is None else int(N_out)
+        if not 1 <= N_out <= min(self.N, L.Motion.POINTS_MAX):
+            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Motion.POINTS_MAX)}]")
+        f0, F_, dev = int(f0), int(F), self.queries.device
+        g0, G = (0, self.G) if group is None else (int(group), 1)
+        if not 0 <= g0 < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        a = L.Objects.Args()
+        _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
+        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
+            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
+        lo, hi = f0, f0 + F_ - 1  # the frames that are read
+        if a.to >= 0:
+            lo, hi = min(lo, a.to), max(hi, a.to)
+        elif a.lag != 0:
+            lo = min(lo, max(f0 - a.lag, 0))
+        if hi >= self.committed:
+            raise ValueError(f"{who}: frames up to {hi} lie beyond what has been tracked ({self.committed} frames)")
+        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
+        if lo < oldest:
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) have left the history: it holds the last {self.T_cap} of {self.committed} "
+                             f"frames (pin the source frame while it is there)")
+        if max(hi - lo + 1, F_ + a.lag) > self.T_cap:  # (ctk_fit_objects keeps the rows one call reads apart)
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) need more than the {self.T_cap} history rows one call may span")
+        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
+                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
+            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
+        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
+        a.visible = None
+        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        return _objects_launch(a, dev, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -707,6 +707,80 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         ops._warp_field_launch(a, field[0], who)
         return flow
 
+    @torch.no_grad()
+    def split_objects(self, frame=None, lag=8, objects=4, group=0, model="similarity", tol=2.0, hypotheses=128, min_base=16.0, min_points=8,
+                      seed=0):
+        """Not in the reference: which of the N (+ spare_points) user-visible points of query set `group` move together between
+        frame - lag and `frame` (default: the newest tracked one) -- one launch of ctk_fit_objects in split mode
+        (ops.StreamGroups.objects on the stream's own history and logits) and one pin(frame), without a wait.  Round 0 fits all points
+        visible on both frames, round r + 1 what round r's inliers left; a round with fewer than min_points inliers ends the rounds.
+        The round order is by size: most inliers first -- usually the background --, decided per pair of frames and NOT stable from
+        pair to pair; that is why one splits once and follows by labels.  model, tol, hypotheses, min_base (raw-video pixels) and
+        seed are camera_motion()'s.  ValueError when frame - lag is negative or has left the ring (history_frames) or the frame has
+        not been tracked.  Returns an ops.ObjectSet: labels int8 [N_model] on the device (r = the point moved with round r; -1 = no
+        round took it, it was not seen on both frames, or it is no user-visible point), the anchor pinned on `frame`, and `objects`."""
+        from . import ops
+        who = "split_objects"
+        gs, scale = self._field_stream(who)
+        frame, lag, group = gs.committed - 1 if frame is None else int(frame), int(lag), int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        if not 0 <= frame < gs.committed or lag < 1 or frame - lag < 0:
+            raise ValueError(f"{who}: frames {frame - lag} and {frame} must both have been tracked ({gs.committed} frames), lag >= 1")
+        label = self.model.stream_objects(frame, 1, objects=objects, lag=lag, N_out=self.N, scale=scale, thresh=0.6,
+                                          first_row=self._emit_first_row(), model=model, tol=tol, hypotheses=hypotheses, min_base=min_base,
+                                          min_points=min_points, seed=seed, group=group)[1]
+        labels = torch.full((gs.N,), -1, dtype=torch.int8, device=label.device)
+        labels[:self.N] = torch.where(label[0, 0] == ops.OBJECT_NONE, torch.full_like(label[0, 0], -1), label[0, 0])
+        return ops.ObjectSet(labels, self.pin(frame, group), int(objects))
+
+    @torch.no_grad()
+    def label_objects(self, boxes, frame=None, group=0):
+        """Not in the reference: the objects a user boxed on `frame` (default: the newest tracked one).  boxes [L,4] = (x0, y0, x1, y1)
+        in raw-video pixels, L <= 16: a user-visible point of query set `group` that is visible on `frame` and lies inside box r
+        (borders included) gets label r; where boxes overlap the lowest r wins; every other point gets -1.  Elementwise torch on the
+        device and one pin(frame), without a wait.  Returns an ops.ObjectSet (see split_objects) for follow()."""
+        from . import ops
+        who = "label_objects"
+        gs, scale = self._field_stream(who)
+        boxes = torch.as_tensor(boxes, dtype=torch.float32)
+        if boxes.dim() != 2 or boxes.shape[1] != 4 or not 1 <= boxes.shape[0] <= ops.L.Objects.OBJECTS_MAX:
+            raise ValueError(f"{who}: boxes must be [L,4] = (x0, y0, x1, y1) with L in 1..{ops.L.Objects.OBJECTS_MAX}")
+        anchor = self.pin(frame, group)
+        boxes = boxes.to(anchor.coords.device)
+        x, y = anchor.coords[0, :, 0] * scale[0], anchor.coords[0, :, 1] * scale[1]
+        inside = ((x[None] >= boxes[:, 0:1]) & (x[None] <= boxes[:, 2:3]) & (y[None] >= boxes[:, 1:2]) & (y[None] <= boxes[:, 3:4]) &
+                  (anchor.visible[0] != 0)[None])
+        inside[:, self.N:] = False
+        lowest = inside.to(torch.int8).argmax(dim=0).to(torch.int8)  # (the first True)
+        labels = torch.where(inside.any(dim=0), lowest, torch.full_like(lowest, -1))
+        return ops.ObjectSet(labels, anchor, boxes.shape[0])
+
+    @torch.no_grad()
+    def follow(self, objects, n=None, first_frame=None, model="similarity", tol=2.0, hypotheses=128, min_base=16.0, min_points=8, seed=0):
+        """Not in the reference: where the objects of an ops.ObjectSet (split_objects / label_objects) are on the n frames from
+        first_frame on (default: the frames of the window just tracked, as in camera_motion()) -- one launch of ctk_fit_objects in
+        labels mode against the set's anchor (ops.StreamGroups.objects on the stream's own history and logits), without a wait.  The
+        anchor outlives the ring (history_frames): nothing is chained and nothing drifts.  Object r is fitted to the points labelled
+        r that are visible on the frame and on the anchor (a slot released and reassigned after the anchor was taken drops out); the
+        objects are independent, and one with fewer than min_points inliers has no fit on that frame.  model, tol, hypotheses,
+        min_base (raw-video pixels) and seed are camera_motion()'s.  Returns, on the device: motion float32 [n,L,2,3]: raw-video
+        position on frame f = motion @ (position on the anchor's frame, 1), the identity where there is no fit; label int8
+        [n,N]: -1 not on both frames, r = moves with object r, 127 = labelled for no object or does not move with its own; stats int32
+        [n,L,4] = (points of the object on both frames, inliers, best hypothesis or -1, 0); box float32 [n,L,4] = (min x, min y, max
+        x, max y) of the object's inliers on frame f in raw-video pixels, max < min where there is no fit."""
+        from . import ops
+        who = "follow"
+        gs, scale = self._field_stream(who)
+        if not isinstance(objects, ops.ObjectSet):
+            raise ValueError(f"{who}: objects must be an ops.ObjectSet (split_objects, label_objects)")
+        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        motion, label, stats, box = self.model.stream_objects(first_frame, n, labels=objects.labels[None], objects=objects.objects,
+                                                              anchor=objects.anchor, N_out=self.N, scale=scale, thresh=0.6,
+                                                              first_row=self._emit_first_row(), model=model, tol=tol, hypotheses=hypotheses,
+                                                              min_base=min_base, min_points=min_points, seed=seed, group=objects.anchor.group)
+        return motion[0], label[0], stats[0], box[0].to(torch.float32) / 16.0
+
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
         everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""

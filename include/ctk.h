@@ -47,6 +47,10 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_objects and ctk_fit_objects_workspace_bytes on the
+ *       new struct ctk_fit_objects_args: per frame, up to 16 robust fits (ctk_fit_motion's rules) over sub-lists of one list of
+ *       correspondences -- the regions a caller labelled, or what the earlier fits left --, against a fixed frame, f - lag or an
+ *       anchor (ctk_track_field's three forms), with a label per point and a box per fit (csrc/objects_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no struct changed): a ctk_model_weights with corr_fc1_* set and BOTH corr_fc2_w and corr_fc2_p
  *       NULL -- CTK_E_NULL until now -- means "corr_mlp.fc2 is folded into the input projection": in_w / in_p are [384, CTK_XF_LD]
  *       and in_bias_t carries the folded bias (see the struct).  The window entry points take it; the stage entry points that
@@ -848,6 +852,86 @@ typedef struct ctk_warp_field_args {
   float* flow;                /* [F,H,W,2], or NULL */
 } ctk_warp_field_args;
 int ctk_warp_field(const ctk_warp_field_args* a, void* stream);
+
+/* ---- fit objects: which points move together, and where such a group is on other frames --------------------------------------------
+ * For a caller whose tracks are on the device: ctk_fit_motion says how the camera moved and which points moved differently; this says
+ * which of those points move together (split mode) and how a group of points a caller chose -- a car, a person, a boxed region --
+ * has moved since the frame it was chosen on (labels mode).  Up to L robust fits per group g and frame f in [f0, f0 + F), each over a
+ * sub-list of ONE list of correspondences.  The rules are stated once in csrc/objects_math.h; everything not named here is
+ * ctk_fit_motion's bit for bit: positions, mix, the sample, the hypothesis, inlier, key, refit.
+ *   pair       P is the source, Q the destination, which is frame f: the matrix maps the source frame onto frame f.  The source takes
+ *              exactly one of ctk_track_field's three forms: a fixed frame to >= 0 (lag = 0, no anchor);  f - lag with lag >= 1
+ *              (to = -1, no anchor), as in ctk_fit_motion;  an anchor (to = -1, lag = 0): anchor_coords [G,N,2] float32 (scaled by sx,
+ *              sy like the history) and anchor_visible [G,N] uint8, taken by the caller on frame anchor_frame >= 0 -- how a region
+ *              is followed after a ring has dropped the frame it was chosen on.  Slot n is a correspondence by ctk_track_field's
+ *              pair rule: both frames are >= 0 and >= first_row[g, n] (anchor_frame counts as the source frame, so a slot released
+ *              and reassigned after the anchor was taken drops out), both positions are valid and both are visible (visible [G,R,N]
+ *              uint8, or sigmoid(vis) * sigmoid(conf) > thresh; anchor_visible[g, n] != 0 on an anchor).  The M correspondences are
+ *              numbered in ascending n.
+ *   rounds     r = 0 .. L - 1, L in 1..16.  Round r takes list_r, a sub-list of the correspondences in ascending n with M_r entries.
+ *              Labels mode (`labels` int8 [G,N] given): list_r holds the correspondences whose label is r; a label outside 0..L-1
+ *              (-1 by convention) belongs to no round.  Split mode (`labels` NULL): list_0 holds all correspondences, list_{r+1} is
+ *              list_r without the inliers of round r's best hypothesis.  Round r samples with seed_r = seed ^ mix(r) (mix(0) = 0:
+ *              round 0 uses `seed` itself) and is otherwise ctk_fit_motion's hypothesis, scoring, best and refit over list_r, with f
+ *              the absolute frame number.
+ *   acceptance a round whose best has fewer than min_points (1..8192) inliers fits nothing, and so does a round with no admissible
+ *              hypothesis: the identity, stats (M_r, 0, -1, 0), box (0, 0, -1, -1), none of its points taken.  In split mode such a
+ *              round ends the rounds: every later round reports the same M_r and nothing else.  In labels mode the rounds are
+ *              independent.  Split mode's round order is by inlier count per frame (each round takes the largest group that is
+ *              left), so the same object may be round 1 on one frame and round 2 on the next: split once, follow by labels.
+ *   outputs    motion float32 [G,F,L,2,3]: the refit rows;  label int8 [G,F,N_out]: -1 no correspondence, r = inlier of round r's
+ *              accepted best, 127 (CTK_OBJECT_NONE of csrc/objects_math.h) = a correspondence no round took;  stats int32 [G,F,L,4] = (M_r, inliers, best k,
+ *              0);  box int32 [G,F,L,4] = (min Qx, min Qy, max Qx, max Qy) over the round's inliers, 1/16 pixel.  Every element is
+ *              written by one plain store.
+ * In split mode with the lag form and min_points = 1, round 0's matrix and stats and (label == 0) equal ctk_fit_motion's motion, stats
+ * and (inlier == 1) bit for bit.
+ * Only the first N_out <= N slots of a group are looked at.  One launch on `stream`, one workgroup of 256 threads per (group, frame)
+ * with the correspondences and their slots in N_out * 18 bytes of LDS (split mode gathers the rows once and removes a round's inliers
+ * by a stable in-place compaction; labels mode gathers them twice -- a counting and a placing pass -- and runs the rounds over disjoint
+ * segments); no atomics, no host synchronisation, capture-safe; writes the four outputs only.  The cost is about the sum of the
+ * scored lists times K: one ctk_fit_motion in labels mode, at most L of them in split mode.  The workspace query answers 0 and
+ * `workspace` may then be NULL.  Before any launch: NULL a, hist_coords, motion, label, stats or box, `visible` NULL with hist_vis or
+ * hist_conf NULL, one of anchor_coords / anchor_visible without the other: CTK_E_NULL; the shapes ctk_fit_motion refuses (G, N, N_out,
+ * R or F <= 0, N_out > N, N_out > 8192, f0 < 0, f0 + F > 2^30, F > 65535, G > 65535, G * N > 2^26, model not 0 or 1, K outside 1..4096,
+ * tol NaN or with T outside 1..4096, min_base NaN, negative or above 8192, sx or sy not finite or <= 0, a NaN thresh without
+ * `visible`, reserved != 0), the forms ctk_track_field refuses (not exactly one source form, to < -1, to > 2^30, lag > 2^30,
+ * anchor_frame outside 0..2^30 with an anchor, rows of a ring that would alias: F + lag > R; with a fixed frame the span of
+ * [f0, f0 + F) and `to` > R; F > R with an anchor), a negative lag, L outside 1..16, min_points outside 1..8192, workspace_bytes
+ * below what the query answers: CTK_E_SHAPE; hist_coords or anchor_coords not 8-byte aligned, motion, stats or box not 4-byte aligned:
+ * CTK_E_ALIGN.  `labels` needs no alignment.  Frames whose source frame is negative are no error: they have no correspondences.  The
+ * query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor is given).                      */
+typedef struct ctk_fit_objects_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t L;                  /* rounds (objects), 1..16                                           */
+  int32_t min_points;         /* a fit needs this many inliers, 1..8192                            */
+  int32_t model;              /* 0 translation, 1 similarity                                       */
+  int32_t K;                  /* hypotheses per round, 1..4096                                     */
+  uint32_t seed;
+  float tol;                  /* inlier bound, pixels (max norm); T = rint(tol * 16) in 1..4096    */
+  float min_base;             /* a similarity's sample pair is at least this far apart, pixels     */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const int8_t* labels;       /* [G,N]: labels mode; NULL: split mode                              */
+  float* motion;              /* [G,F,L,2,3] */
+  int8_t* label;              /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,L,4] */
+  int32_t* box;               /* [G,F,L,4] */
+} ctk_fit_objects_args;
+int ctk_fit_objects_workspace_bytes(const ctk_fit_objects_args* a, size_t* out_bytes);
+int ctk_fit_objects(const ctk_fit_objects_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
