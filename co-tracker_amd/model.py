@@ -996,63 +996,50 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
             raise RuntimeError(f"the stream has reached frame {ind}: the next window would pass frame 2^24, beyond which float32 query "
                                "frames are not exact; start a new stream (init_video_online_processing)")
 
-    def stream_emit(self, f0, f1, N_out=None, scale=(1.0, 1.0), logits=True, thresh=None, first_row=None):
-        """Frames [f0, f1) of the running (or just closed) stream's history, in frame order, by one launch: ops.StreamGroups.emit.
-        Serves a ring history and the default one alike."""
+    def _running_stream(self):
+        """The device stream state of the running (or just closed) stream, for the readers of its history below; RuntimeError when there
+        is none, or nothing has been committed to it yet."""
         gs = self._gstream
         if gs is None or not gs.live or gs.committed == 0:
             raise RuntimeError("no stream is running on the device stream state")
-        return gs.emit(f0, f1, N_out, scale, logits, thresh, first_row)
+        return gs
+
+    def stream_emit(self, f0, f1, N_out=None, scale=(1.0, 1.0), logits=True, thresh=None, first_row=None):
+        """Frames [f0, f1) of the running (or just closed) stream's history, in frame order, by one launch: ops.StreamGroups.emit.
+        Serves a ring history and the default one alike."""
+        return self._running_stream().emit(f0, f1, N_out, scale, logits, thresh, first_row)
 
     def stream_health(self, look, grid, thresh, N_out, first_row, bounds):
         """The slots of the running (or just closed) stream judged over its last `look` frames, by one launch and without a wait:
         ops.StreamGroups.health -> (lost, cell, cover) on the device.  Serves a ring history and the default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.health(look, grid, thresh, N_out, first_row, bounds)
+        return self._running_stream().health(look, grid, thresh, N_out, first_row, bounds)
 
     def stream_draw(self, frames, f0, colors, **kw):
         """Points of the running (or just closed) stream drawn onto uint8 frames from its own history, by two launches and without a
         wait: ops.StreamGroups.draw.  Serves a ring history and the default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.draw(frames, f0, colors, **kw)
+        return self._running_stream().draw(frames, f0, colors, **kw)
 
     def stream_motion(self, f0, F, **kw):
         """The camera motion of frames [f0, f0 + F) of the running (or just closed) stream fitted to its own history, by one launch and
         without a wait: ops.StreamGroups.motion.  Serves a ring history and the default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.motion(f0, F, **kw)
+        return self._running_stream().motion(f0, F, **kw)
 
     def stream_stabilize(self, frames, f0, **kw):
         """uint8 frames [f0, f0 + F) of the running (or just closed) stream steadied by the camera motion fitted to its own history, by
         three launches and without a wait: ops.StreamGroups.stabilize.  Serves a ring history and the default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.stabilize(frames, f0, **kw)
+        return self._running_stream().stabilize(frames, f0, **kw)
 
     def stream_field(self, f0, F, **kw):
         """The displacement fields of frames [f0, f0 + F) of the running (or just closed) stream towards another frame or an anchor,
         interpolated from its own history by three launches and without a wait: ops.StreamGroups.field.  Serves a ring history and the
         default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.field(f0, F, **kw)
+        return self._running_stream().field(f0, F, **kw)
 
     def stream_objects(self, f0, F, **kw):
         """Up to `objects` motion fits per frame [f0, f0 + F) of the running (or just closed) stream over sub-lists of its points --
         labelled regions, or what the earlier fits left -- against f - lag, a fixed frame or an anchor, from its own history by one
         launch and without a wait: ops.StreamGroups.objects.  Serves a ring history and the default one alike."""
-        gs = self._gstream
-        if gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state")
-        return gs.objects(f0, F, **kw)
+        return self._running_stream().objects(f0, F, **kw)
 
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):

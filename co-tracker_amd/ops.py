@@ -22,6 +22,11 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def _ptr_at(t: torch.Tensor, g0: int) -> int:
+    """The address of t[g0:], without making the view."""
+    return t.data_ptr() + g0 * t.stride(0) * t.element_size()
+
+
 def _chk_f32(*ts):
     for t in ts:
         if t is None:
@@ -251,22 +256,101 @@ def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin:
 
 
 # ------------------------------------------------------------------------------------------
-# draw tracks (csrc/draw.hip; include/ctk.h, "draw tracks")
+# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field and fit_objects differ
+# in the history rows they need (`rows`) and in their own struct fields; StreamGroups has the other source, a stream's history.
 # ------------------------------------------------------------------------------------------
-_draw_ws_cache = {}
+_scratch_cache = {}
 
 
-def _draw_workspace(nbytes: int, device) -> torch.Tensor:
-    """The primitive table of ctk_draw_tracks, cached per device like _workspace -- a cache of its own: captured window graphs bake
-    the address of that one in, and a draw call must never be the reason it moves."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    buf = _draw_ws_cache.get(key)
+def _scratch(kind: str, nbytes: int, device) -> torch.Tensor:
+    """The workspace of one kind of reader ("draw", "motion" -- fit_objects shares it --, "field"), cached per kind and device like
+    _workspace -- but never in that cache: captured window graphs bake the address of that one in, and a reader must never be the
+    reason it moves.  Nor does one kind ever move the buffer of another."""
+    key = (kind, device.index if device.index is not None else torch.cuda.current_device())
+    buf = _scratch_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = _draw_ws_cache[key] = None
-        buf = _draw_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
+        buf = _scratch_cache[key] = None  # (the old buffer goes before the larger one comes)
+        buf = _scratch_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
     return buf
 
 
+def _track_tensors(tracks, visible, who: str, points_max: Optional[int] = None):
+    """tracks [T,N,2] / [G,T,N,2], visible [T,N] / [G,T,N] checked -> (tracks [G,T,N,2], visible [G,T,N], G, T, N, device)."""
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
+            tracks.shape[-1] == 2):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
+    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
+    G, T, N, _ = tracks.shape
+    dev = tracks.device
+    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
+            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
+        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
+    if points_max is not None and not 1 <= N <= points_max:
+        raise ValueError(f"{who}: between 1 and {points_max} points per group, got {N}")
+    return tracks, visible.reshape(G, T, N), G, T, N, dev
+
+
+def _frames_of(first_frame, frames, T: int, who: str):
+    """(first_frame, frames) -> (f0, F), frames None: to the end; the rows must lie in [0, T)."""
+    f0 = int(first_frame)
+    F_ = T - f0 if frames is None else int(frames)
+    if f0 < 0 or F_ < 1 or f0 + F_ > T:
+        raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) of {T} tracked frames")
+    return f0, F_
+
+
+def _first_row_i32(first_row, G: int, N: int, dev):
+    """first_row int [N] / [G,N] (or None) as the C-ABI wants it: contiguous int32 [G,N] on the device."""
+    if first_row is None:
+        return None
+    big = torch.iinfo(torch.int32).max  # (an int64 table marks an empty slot with its own maximum: clamped, not wrapped)
+    return torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
+
+
+def _bind_tensors(a, tracks, visible, first_row, *, rows: int, f0: int, scale, F: Optional[int] = None, N_out: Optional[int] = None):
+    """The source fields of a reader's args from result tensors (_track_tensors, _first_row_i32).  The C-ABI keeps the rows one call
+    reads apart (rows of a ring must not alias), so `rows` > T appends rows that hold no visible point.  `a` keeps the tensors it now
+    points into (padded or made contiguous here, they have no other owner) alive until its launch is issued."""
+    G, T, N, _ = tracks.shape
+    if rows > T:
+        tracks = torch.cat([tracks, tracks.new_zeros(G, rows - T, N, 2)], dim=1)
+        visible = torch.cat([visible, visible.new_zeros(G, rows - T, N)], dim=1)
+    tracks, visible = tracks.contiguous(), visible.contiguous()
+    visible = visible.view(torch.uint8) if visible.dtype == torch.bool else visible
+    a.G, a.N, a.N_out, a.R, a.f0 = G, N, (N if N_out is None else N_out), tracks.shape[1], f0
+    if F is not None:
+        a.F = F
+    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
+    a.hist_coords, a.visible, a.first_row = _ptr(tracks), _ptr(visible), _ptr(first_row)
+    a._held = (tracks, visible, first_row)
+
+
+def _out_tuple(out, specs, device, who: str):
+    """The outputs of a reader, specs = [(name, dtype, shape)]: allocated, or `out` checked against them."""
+    if out is None:
+        return tuple(torch.empty(sh, device=device, dtype=dt) for _, dt, sh in specs)
+    out = tuple(out)
+    if len(out) != len(specs) or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
+                                     not t_.is_contiguous() for t_, (_, dt, sh) in zip(out, specs)):
+        want = ", ".join(f"{name} {str(dt)[6:]} {list(sh)}" for name, dt, sh in specs)
+        raise ValueError(f"{who}: out must be contiguous ({want}) on {device}")
+    return out
+
+
+def _anchor_ptrs(anchor, G: int, N: int, device, who: str):
+    """A FieldAnchor checked against the G groups and N points it must match -> (frame, coords pointer, visible pointer)."""
+    c, v = anchor.coords, anchor.visible
+    if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and tuple(c.shape) == (G, N, 2) and c.device == device and
+            c.is_contiguous() and isinstance(v, torch.Tensor) and v.dtype in (torch.uint8, torch.bool) and tuple(v.shape) == (G, N) and
+            v.device == device and v.is_contiguous()) or anchor.frame < 0:
+        raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
+                         f"frame >= 0")
+    return anchor.frame, _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+
+
+# ------------------------------------------------------------------------------------------
+# draw tracks (csrc/draw.hip; include/ctk.h, "draw tracks")
+# ------------------------------------------------------------------------------------------
 def rainbow_colors(y: torch.Tensor) -> torch.Tensor:
     """Default colours of draw_tracks: y [...,N] (the points' y on their first row) -> uint8 [...,N,3], an integer HSV ramp red ->
     yellow -> green -> cyan -> blue over min(y) .. max(y) of each row of points (the idea of the reference visualiser's
@@ -346,7 +430,7 @@ def _draw_launch(a, frames: torch.Tensor, out: Optional[torch.Tensor], layout: O
         if out.device != frames.device or out.shape != frames.shape or _draw_surface(out, geo[0], who) != geo:
             raise ValueError(f"{who}: out must be uint8 frames of the shape, strides and device of `frames`")
         a.src, a.dst = _ptr(frames), _ptr(out)
-    ws = _draw_workspace(_query_bytes("ctk_draw_tracks_workspace_bytes", C.byref(a)), frames.device)
+    ws = _scratch("draw", _query_bytes("ctk_draw_tracks_workspace_bytes", C.byref(a)), frames.device)
     L.check(L.load().ctk_draw_tracks(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_draw_tracks")
     return out
 
@@ -368,16 +452,7 @@ def draw_tracks(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tenso
     quadratic fade default_alpha(trail); alpha[0]: the marks).  first_row int [N] / [G,N]: nothing of a point is drawn below that
     frame (INT32_MAX: never).  Returns the drawn frames (`frames` itself, or `out`)."""
     who = "draw_tracks"
-    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
-            tracks.shape[-1] == 2):
-        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
-    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
-    G, T, N, _ = tracks.shape
-    dev = tracks.device
-    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
-            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
-        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
-    visible = visible.reshape(G, T, N)
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who)
     if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
         raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
     F_, first_frame = frames.shape[0], int(first_frame)
@@ -385,43 +460,22 @@ def draw_tracks(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tenso
         raise ValueError(f"{who}: pictures of frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
     a = L.Draw.Args()
     _draw_style(a, trail, radius, half_width, alpha, max_jump, who)
-    if first_row is not None:
-        big = torch.iinfo(torch.int32).max  # (an int64 table marks an empty slot with its own maximum: clamped, not wrapped)
-        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
+    first_row = _first_row_i32(first_row, G, N, dev)
     if colors is None:
         at = torch.zeros(G, 1, N, dtype=torch.long, device=dev) if first_row is None else first_row.long().clamp(0, T - 1)[:, None]
         colors = rainbow_colors(tracks[..., 1].gather(1, at)[:, 0])
     if not (isinstance(colors, torch.Tensor) and colors.dtype == torch.uint8 and colors.numel() == G * N * 3 and colors.shape[-1] == 3):
         raise ValueError(f"{who}: colors must be a uint8 tensor [{N},3] or [{G},{N},3]")
     colors = colors.to(dev).reshape(G, N, 3).contiguous()
-    if F_ + a.trail > T:  # the C-ABI keeps F + trail <= R (rows of a ring must not alias): rows that no picture reads are appended
-        pad = F_ + a.trail - T
-        tracks = torch.cat([tracks, tracks.new_zeros(G, pad, N, 2)], dim=1)
-        visible = torch.cat([visible, visible.new_zeros(G, pad, N)], dim=1)
-    tracks, visible = tracks.contiguous(), visible.contiguous()
-    a.G, a.N, a.N_out, a.R, a.f0 = G, N, N, tracks.shape[1], first_frame
-    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
-    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
-    a.first_row, a.colors = _ptr(first_row), _ptr(colors)
+    _bind_tensors(a, tracks, visible, first_row, rows=F_ + a.trail, f0=first_frame, scale=scale)
+    a.colors = _ptr(colors)
     return _draw_launch(a, frames, out, layout, who)
 
 
 # ------------------------------------------------------------------------------------------
 # fit motion (csrc/motion.hip; include/ctk.h, "fit motion")
 # ------------------------------------------------------------------------------------------
-_motion_ws_cache = {}
 MOTION_MODELS = {"translation": L.Motion.TRANSLATION, "similarity": L.Motion.SIMILARITY}
-
-
-def _motion_workspace(nbytes: int, device) -> torch.Tensor:
-    """The workspace of ctk_fit_motion, cached per device like _draw_workspace and for the same reason a cache of its own: captured
-    window graphs bake the address of _workspace in, and a motion call must never be the reason it moves."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    buf = _motion_ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _motion_ws_cache[key] = None
-        buf = _motion_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
-    return buf
 
 
 def _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who: str) -> None:
@@ -435,18 +489,10 @@ def _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who: str) -> N
 
 def _motion_launch(a, device, out, who: str):
     """Allocates (or checks) the three outputs of ctk_fit_motion for the G, F, N_out of `a`, then the launch."""
-    shapes = ((a.G, a.F, 2, 3), (a.G, a.F, a.N_out), (a.G, a.F, 4))
-    dtypes = (torch.float32, torch.int8, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(sh, device=device, dtype=dt) for sh, dt in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 3 or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
-                                not t_.is_contiguous() for t_, sh, dt in zip(out, shapes, dtypes)):
-            raise ValueError(f"{who}: out must be contiguous (motion float32 {list(shapes[0])}, inlier int8 {list(shapes[1])}, stats int32 "
-                             f"{list(shapes[2])}) on {device}")
+    out = _out_tuple(out, [("motion", torch.float32, (a.G, a.F, 2, 3)), ("inlier", torch.int8, (a.G, a.F, a.N_out)),
+                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
     a.motion, a.inlier, a.stats = (_ptr(t_) for t_ in out)
-    ws = _motion_workspace(_query_bytes("ctk_fit_motion_workspace_bytes", C.byref(a)), device)
+    ws = _scratch("motion", _query_bytes("ctk_fit_motion_workspace_bytes", C.byref(a)), device)
     L.check(L.load().ctk_fit_motion(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_motion")
     return out
 
@@ -468,32 +514,11 @@ def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, mod
     (correspondences, inliers, best hypothesis or -1, 0)) -- `out` when given.  A frame without an admissible hypothesis (among
     them every f < lag) has the identity."""
     who = "fit_motion"
-    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
-            tracks.shape[-1] == 2):
-        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
-    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
-    G, T, N, _ = tracks.shape
-    dev = tracks.device
-    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
-            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
-        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
-    visible = visible.reshape(G, T, N)
-    if not 1 <= N <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: between 1 and {L.Motion.POINTS_MAX} points per group, got {N}")
-    first_frame = int(first_frame)
-    F_ = T - first_frame if frames is None else int(frames)
-    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
-        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    f0, F_ = _frames_of(first_frame, frames, T, who)
     a = L.Motion.Args()
     _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
-    if F_ + a.lag > T:  # the C-ABI keeps F + lag <= R (rows of a ring must not alias): rows that no frame reads are appended
-        pad = F_ + a.lag - T
-        tracks = torch.cat([tracks, tracks.new_zeros(G, pad, N, 2)], dim=1)
-        visible = torch.cat([visible, visible.new_zeros(G, pad, N)], dim=1)
-    tracks, visible = tracks.contiguous(), visible.contiguous()
-    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N, tracks.shape[1], first_frame, F_
-    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
-    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
+    _bind_tensors(a, tracks, visible, None, rows=F_ + a.lag, f0=f0, F=F_, scale=scale)
     return _motion_launch(a, dev, out, who)
 
 
@@ -650,9 +675,6 @@ def stabilize(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor,
 # ------------------------------------------------------------------------------------------
 # track field (csrc/field.hip; include/ctk.h, "track field")
 # ------------------------------------------------------------------------------------------
-_field_ws_cache = {}
-
-
 class FieldAnchor:
     """One frame's row of a group, kept on the device for track_field's anchor form: coords float32 [G,N,2] (unscaled history
     positions), visible uint8 [G,N], the frame number they were taken on and the group of a stream they belong to."""
@@ -660,17 +682,6 @@ class FieldAnchor:
 
     def __init__(self, coords: torch.Tensor, visible: torch.Tensor, frame: int, group: int = 0):
         self.coords, self.visible, self.frame, self.group = coords, visible, int(frame), int(group)
-
-
-def _field_workspace(nbytes: int, device) -> torch.Tensor:
-    """The workspace of ctk_track_field (the sum pyramid), cached per device and grown by shape only, like _motion_workspace and for
-    the same reason a cache of its own."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
-    buf = _field_ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _field_ws_cache[key] = None
-        buf = _field_ws_cache[key] = torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
-    return buf
 
 
 def _field_cs(cell, who: str) -> int:
@@ -705,30 +716,16 @@ def _field_rules(a, size, cell, radius, to, lag, anchor, G: int, N: int, device,
         if a.lag == 0:
             raise ValueError(f"{who}: lag must not be 0 (negative: forward flow)")
     else:
-        c, v = anchor.coords, anchor.visible
-        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and tuple(c.shape) == (G, N, 2) and c.device == device and
-                c.is_contiguous() and isinstance(v, torch.Tensor) and v.dtype in (torch.uint8, torch.bool) and tuple(v.shape) == (G, N) and
-                v.device == device and v.is_contiguous()) or anchor.frame < 0:
-            raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
-                             f"frame >= 0")
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = anchor.frame, _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
 
 
 def _field_launch(a, device, out, who: str):
     """Allocates (or checks) the three outputs of ctk_track_field for the G, F and grid of `a`, then the three launches."""
     gh, gw = ((a.H - 1) >> a.cs) + 2, ((a.W - 1) >> a.cs) + 2
-    shapes = ((a.G, a.F, gh, gw, 2), (a.G, a.F, gh, gw), (a.G, a.F, 4))
-    dtypes = (torch.int32, torch.uint8, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(sh, device=device, dtype=dt) for sh, dt in zip(shapes, dtypes))
-    else:
-        out = tuple(out)
-        if len(out) != 3 or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
-                                not t_.is_contiguous() for t_, sh, dt in zip(out, shapes, dtypes)):
-            raise ValueError(f"{who}: out must be contiguous (field int32 {list(shapes[0])}, level uint8 {list(shapes[1])}, stats int32 "
-                             f"{list(shapes[2])}) on {device}")
+    out = _out_tuple(out, [("field", torch.int32, (a.G, a.F, gh, gw, 2)), ("level", torch.uint8, (a.G, a.F, gh, gw)),
+                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
     a.field, a.level, a.stats = (_ptr(t_) for t_ in out)
-    ws = _field_workspace(_query_bytes("ctk_track_field_workspace_bytes", C.byref(a)), device)
+    ws = _scratch("field", _query_bytes("ctk_track_field_workspace_bytes", C.byref(a)), device)
     L.check(L.load().ctk_track_field(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_track_field")
     return out
 
@@ -751,40 +748,17 @@ def track_field(tracks: torch.Tensor, visible: torch.Tensor, *, size, cell: int 
     pixel, node (i, j) at pixel (i cell, j cell); level uint8 [G,F,gh,gw]: 0 own support, l filled from pyramid level l, 255 nothing;
     stats int32 [G,F,4] = (correspondences, nodes at level 0, highest level used, 0)) -- `out` when given."""
     who = "track_field"
-    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
-            tracks.shape[-1] == 2):
-        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
-    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
-    G, T, N, _ = tracks.shape
-    dev = tracks.device
-    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
-            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
-        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
-    visible = visible.reshape(G, T, N)
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who)
     N_out = N if N_out is None else int(N_out)
     if not 1 <= N_out <= min(N, L.Field.POINTS_MAX):
         raise ValueError(f"{who}: N_out must lie in [1, {min(N, L.Field.POINTS_MAX)}]")
-    first_frame = int(first_frame)
-    F_ = T - first_frame if frames is None else int(frames)
-    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
-        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    f0, F_ = _frames_of(first_frame, frames, T, who)
     a = L.Field.Args()
     _field_rules(a, size, cell, radius, to, lag, anchor, G, N, dev, who)
     if a.to >= T:
         raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    # the C-ABI keeps the rows one call reads apart (rows of a ring must not alias): rows that hold no visible point are appended
-    rows = max(T, F_ + abs(a.lag), first_frame + F_ + max(-a.lag, 0))
-    if rows > T:
-        tracks = torch.cat([tracks, tracks.new_zeros(G, rows - T, N, 2)], dim=1)
-        visible = torch.cat([visible, visible.new_zeros(G, rows - T, N)], dim=1)
-    tracks, visible = tracks.contiguous(), visible.contiguous()
-    if first_row is not None:
-        big = torch.iinfo(torch.int32).max
-        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
-    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N_out, rows, first_frame, F_
-    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
-    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
-    a.first_row = _ptr(first_row)
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + abs(a.lag), f0 + F_ + max(-a.lag, 0)),
+                  f0=f0, F=F_, N_out=N_out, scale=scale)
     return _field_launch(a, dev, out, who)
 
 
@@ -948,14 +922,8 @@ def _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, 
         if a.to < 0:
             raise ValueError(f"{who}: to must be a frame >= 0")
     elif anchor is not None:
-        c, v = anchor.coords, anchor.visible
-        if not (isinstance(c, torch.Tensor) and c.dtype == torch.float32 and tuple(c.shape) == (G, N, 2) and c.device == device and
-                c.is_contiguous() and isinstance(v, torch.Tensor) and v.dtype in (torch.uint8, torch.bool) and tuple(v.shape) == (G, N) and
-                v.device == device and v.is_contiguous()) or anchor.frame < 0:
-            raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
-                             f"frame >= 0")
-        a.lag, a.anchor_frame = 0, anchor.frame
-        a.anchor_coords, a.anchor_visible = _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+        a.lag = 0
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
     a.labels = None
     if labels is not None:
         if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int8 and labels.device == device and labels.numel() == G * N and
@@ -966,10 +934,10 @@ def _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, 
 
 def _objects_launch(a, device, who: str):
     """Allocates the four outputs of ctk_fit_objects for the G, F, L and N_out of `a`, then the launch."""
-    out = (torch.empty((a.G, a.F, a.L, 2, 3), device=device, dtype=torch.float32), torch.empty((a.G, a.F, a.N_out), device=device, dtype=torch.int8),
-           torch.empty((a.G, a.F, a.L, 4), device=device, dtype=torch.int32), torch.empty((a.G, a.F, a.L, 4), device=device, dtype=torch.int32))
+    out = _out_tuple(None, [("motion", torch.float32, (a.G, a.F, a.L, 2, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
+                            ("stats", torch.int32, (a.G, a.F, a.L, 4)), ("box", torch.int32, (a.G, a.F, a.L, 4))], device, who)
     a.motion, a.label, a.stats, a.box = (_ptr(t_) for t_ in out)
-    ws = _motion_workspace(_query_bytes("ctk_fit_objects_workspace_bytes", C.byref(a)), device)
+    ws = _scratch("motion", _query_bytes("ctk_fit_objects_workspace_bytes", C.byref(a)), device)
     L.check(L.load().ctk_fit_objects(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_objects")
     return out
 
@@ -997,39 +965,15 @@ def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional
     0); box int32 [G,F,objects,4] = (min x, min y, max x, max y) of the round's inliers on frame f in 1/16 pixel, (0, 0, -1, -1) where
     nothing was fitted)."""
     who = "fit_objects"
-    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() in (3, 4) and
-            tracks.shape[-1] == 2):
-        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [G,T,N,2]")
-    tracks = (tracks[None] if tracks.dim() == 3 else tracks)
-    G, T, N, _ = tracks.shape
-    dev = tracks.device
-    if not (isinstance(visible, torch.Tensor) and visible.dtype in (torch.bool, torch.uint8) and visible.device == dev and
-            visible.numel() == G * T * N and tuple(visible.shape[-2:]) == (T, N)):
-        raise ValueError(f"{who}: visible must be a bool or uint8 tensor [{T},{N}] or [{G},{T},{N}] on {dev}")
-    visible = visible.reshape(G, T, N)
-    if not 1 <= N <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: between 1 and {L.Motion.POINTS_MAX} points per group, got {N}")
-    first_frame, F_ = (0, T) if frames is None else (int(frames[0]), int(frames[1]))
-    if first_frame < 0 or F_ < 1 or first_frame + F_ > T:
-        raise ValueError(f"{who}: frames [{first_frame}, {first_frame + F_}) of {T} tracked frames")
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    f0, F_ = _frames_of(0, None, T, who) if frames is None else _frames_of(frames[0], int(frames[1]), T, who)
     a = L.Objects.Args()
     if isinstance(labels, torch.Tensor) and labels.dim() == 1 and G > 1:
         labels = labels.expand(G, -1).contiguous()
     _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
     if a.to >= T:
         raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    rows = max(T, F_ + a.lag)  # the C-ABI keeps F + lag <= R (rows of a ring must not alias): rows that no frame reads are appended
-    if rows > T:
-        tracks = torch.cat([tracks, tracks.new_zeros(G, rows - T, N, 2)], dim=1)
-        visible = torch.cat([visible, visible.new_zeros(G, rows - T, N)], dim=1)
-    tracks, visible = tracks.contiguous(), visible.contiguous()
-    if first_row is not None:
-        big = torch.iinfo(torch.int32).max
-        first_row = torch.as_tensor(first_row, device=dev).clamp(min=-big, max=big).to(torch.int32).expand(G, N).contiguous()
-    a.G, a.N, a.N_out, a.R, a.f0, a.F = G, N, N, rows, first_frame, F_
-    a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), 0.0
-    a.hist_coords, a.visible = _ptr(tracks), _ptr(visible.view(torch.uint8) if visible.dtype == torch.bool else visible)
-    a.first_row = _ptr(first_row)
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + a.lag), f0=f0, F=F_, scale=scale)
     return _objects_launch(a, dev, who)
 
 
@@ -1461,6 +1405,28 @@ class WindowBatchGraph(WindowGraph):
 EMPTY_FRAME = L.STREAM_EMPTY_FRAME
 
 
+def history_span(committed: int, T_cap: int, ring: bool, f0: int, F: int, back: int = 0, fwd: int = 0, to: int = -1):
+    """The one range rule of the readers of a stream's history (StreamGroups.draw, motion, field, objects): may a call for frames
+    [f0, f0 + F) be served by a history of T_cap rows, `committed` frames in, a ring or not?  Besides its own frames the call reads
+    the `back` frames before each (a trail, a positive lag; those >= 0), the frame `fwd` after each (a negative lag), and the fixed
+    frame `to` (>= 0); an anchor reads nothing more.  -> None, or what is wrong with the frames [lo, hi] that are read:
+    ("beyond", lo, hi): not all committed yet; ("left", lo, hi): a ring has overwritten some; ("span", lo, hi): more rows than one
+    call may span -- the C-ABI keeps F + back + fwd <= T_cap and the rows that are read apart, for the rows of a ring must not alias."""
+    if f0 < 0 or F < 1 or f0 + F > committed:
+        return "beyond", f0, f0 + F - 1
+    lo, hi = max(f0 - back, 0), f0 + F - 1 + fwd
+    if to >= 0:
+        lo, hi = min(lo, to), max(hi, to)
+    if hi >= committed:
+        return "beyond", lo, hi
+    oldest = max(committed - T_cap, 0) if ring else 0
+    if lo < oldest:
+        return "left", lo, hi
+    if max(hi - lo + 1, F + back + fwd) > T_cap:
+        return "span", lo, hi
+    return None
+
+
 class StreamGroups:
     """The device-resident state of G query groups streamed over ONE video, in the layouts the shared joint window wants, and
     the three launches that step it (csrc/stream.hip).  Everything a window call reads or writes lives here and keeps its
@@ -1568,6 +1534,51 @@ class StreamGroups:
         r0, r1 = f0 % R, f0 % R + (f1 - f0)
         return [slice(r0, r1)] if r1 <= R else [slice(r0, R), slice(0, r1 - R)]
 
+    # -- readers of the history: emit, health, draw, motion, field, objects.  What they share is stated here, once: whom a call reads
+    # (_reader), which frames it may read (_held: history_span) and the source fields of its args (_bind_history).  A reader itself
+    # holds its own options, the back / fwd / to of its span, its own struct fields and its launch. ---------------------------------
+    def _reader(self, who: str, N_out, group, first_row, points_max: Optional[int] = None, need_row: bool = False):
+        """Whom a reader reads -> (N_out, g0, G): the first N_out points (default: all N; at most points_max) of the G groups from g0
+        on (`group` alone, or None: all), and first_row checked as what emit takes: int32 [self.G, self.N] on the device, or None."""
+        N_out = self.N if N_out is None else int(N_out)
+        top = self.N if points_max is None else min(self.N, points_max)
+        if not 1 <= N_out <= top:
+            raise ValueError(f"{who}: N_out must lie in [1, {top}]")
+        g0, G = (0, self.G) if group is None else (int(group), 1)
+        if not 0 <= g0 < self.G:
+            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        dev = self.queries.device
+        if (first_row is not None or need_row) and not (isinstance(first_row, torch.Tensor) and first_row.dtype == torch.int32 and
+                                                        tuple(first_row.shape) == (self.G, self.N) and first_row.device == dev and
+                                                        first_row.is_contiguous()):
+            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
+        return N_out, g0, G
+
+    def _held(self, who: str, f0: int, F: int, *, back: int = 0, fwd: int = 0, to: int = -1, hint: str = "") -> None:
+        """ValueError unless the history still holds every frame a call for [f0, f0 + F) reads (back, fwd, to: history_span's); hint:
+        what to do about a call that spans too many rows."""
+        bad = history_span(self.committed, self.T_cap, self.ring_rows is not None, f0, F, back, fwd, to)
+        if bad is None:
+            return
+        kind, lo, hi = bad
+        if kind == "beyond":
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) lie beyond what has been tracked ({self.committed} frames)")
+        if kind == "left":
+            pin = " (pin the source frame while it is there)" if to >= 0 else ""
+            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) have left the history: it holds the last {self.T_cap} of {self.committed} "
+                             f"frames{pin}")
+        raise ValueError(f"{who}: frames [{lo}, {hi + 1}) need more than the {self.T_cap} history rows one call may span{hint}")
+
+    def _bind_history(self, a, g0: int, G: int, N_out: int, f0: int, F: Optional[int], scale, thresh: float, first_row) -> None:
+        """The source fields of a reader's args: the history and logits of the groups from g0 on (F None: the args have no F)."""
+        a.G, a.N, a.N_out, a.R, a.f0 = G, self.N, N_out, self.T_cap, f0
+        if F is not None:
+            a.F = F
+        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
+        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr_at(h_, g0) for h_ in self.hist)
+        a.visible = None
+        a.first_row = None if first_row is None else _ptr_at(first_row, g0)
+
     def emit(self, f0: int, f1: int, N_out: Optional[int] = None, scale=(1.0, 1.0), logits: bool = True, thresh: Optional[float] = None,
              first_row: Optional[torch.Tensor] = None):
         """History frames [f0, f1) of the first N_out points of every group, copied out in frame order by ONE launch
@@ -1575,12 +1586,12 @@ class StreamGroups:
         two logit tensors [G,f1-f0,N_out] if `logits`, then -- `thresh` given -- visibility (bool) = sigmoid(vis) * sigmoid(conf) >
         thresh, ANDed with frame >= first_row[g, n] (int32 [G,N] on the device, INT32_MAX: an empty slot) when that is given.  The
         frames must be among the last T_cap committed ones (a ring keeps no more).  Returns the tuple of what was asked for."""
-        N_out = self.N if N_out is None else int(N_out)
-        if not (0 <= f0 < f1 <= self.committed and f1 - f0 <= self.T_cap and f0 >= (0 if self.ring_rows is None else self.committed - self.T_cap)):
+        if history_span(self.committed, self.T_cap, self.ring_rows is not None, f0, f1 - f0) is not None:
             raise ValueError(f"emit: frames [{f0}, {f1}) are not among the {min(self.committed, self.T_cap)} frames the history holds "
                              f"(it ends at frame {self.committed})")
-        if not 1 <= N_out <= self.N:
-            raise ValueError(f"emit: N_out must lie in [1, {self.N}]")
+        if thresh is None:
+            first_row = None  # (it gates the visibility only)
+        N_out, _, _ = self._reader("emit", N_out, None, first_row)
         dev, F_ = self.queries.device, f1 - f0
         a = L.StreamEmit.Args()
         a.G, a.N, a.N_out, a.R, a.f0, a.f1 = self.G, self.N, N_out, self.T_cap, f0, f1
@@ -1593,12 +1604,7 @@ class StreamGroups:
             a.vis_logit, a.conf_logit = _ptr(out[1]), _ptr(out[2])
         if thresh is not None:
             out.append(torch.empty(self.G, F_, N_out, device=dev, dtype=torch.bool))  # (one byte per element, written as 0 / 1)
-            a.visible = _ptr(out[-1])
-            if first_row is not None:
-                if first_row.dtype != torch.int32 or tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or \
-                        not first_row.is_contiguous():
-                    raise ValueError(f"emit: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
-                a.first_row = _ptr(first_row)
+            a.visible, a.first_row = _ptr(out[-1]), _ptr(first_row)
         L.check(L.load().ctk_stream_emit(C.byref(a), _stream()), "ctk_stream_emit")
         return tuple(out)
 
@@ -1612,7 +1618,6 @@ class StreamGroups:
         sigmoid(vis) * sigmoid(conf) > thresh inside the bounds.  first_row: int32 [G,N] on the device, INT32_MAX for an empty slot
         (what emit takes).  f1 = committed, ind_next = next_ind.  The three results are views of ONE allocation, in this order
         (``lost._base``: one copy brings all of them to the host).  No wait."""
-        N_out = self.N if N_out is None else int(N_out)
         gh, gw = (int(v) for v in grid)
         look = int(look)
         dev = self.queries.device
@@ -1621,13 +1626,9 @@ class StreamGroups:
         if not 1 <= look <= min(self.T_cap, self.committed):
             raise ValueError(f"health: look must lie in [1, {min(self.T_cap, self.committed)}] (frames so far: {self.committed}, history "
                              f"rows: {self.T_cap})")
-        if not 1 <= N_out <= self.N:
-            raise ValueError(f"health: N_out must lie in [1, {self.N}]")
+        N_out, _, _ = self._reader("health", N_out, None, first_row, need_row=True)
         if gh < 1 or gw < 1 or gh * gw > self.HEALTH_CELLS_MAX:
             raise ValueError(f"health: the grid must have between 1 and {self.HEALTH_CELLS_MAX} cells, got {gh} x {gw}")
-        if not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or tuple(first_row.shape) != (self.G, self.N) or \
-                first_row.device != dev or not first_row.is_contiguous():
-            raise ValueError(f"health: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
         a = L.StreamHealth.Args()
         a.G, a.N, a.N_out, a.R, a.f1, a.look, a.ind_next = self.G, self.N, N_out, self.T_cap, self.committed, look, self.next_ind
         a.thresh, a.reserved, a.gh, a.gw = float(thresh), 0, gh, gw
@@ -1659,36 +1660,19 @@ class StreamGroups:
         slots.  The frames f0 - trail .. f0 + F - 1 (those >= 0) must be among the committed ones the history still holds:
         ValueError otherwise.  No wait."""
         who = "draw"
-        N_out = self.N if N_out is None else int(N_out)
-        if not 1 <= N_out <= self.N:
-            raise ValueError(f"{who}: N_out must lie in [1, {self.N}]")
+        N_out, g0, G = self._reader(who, N_out, group, first_row)
         if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
             raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+        dev = self.queries.device
+        if not (isinstance(colors, torch.Tensor) and colors.dtype == torch.uint8 and tuple(colors.shape) == (self.G, self.N, 3) and
+                colors.device == dev and colors.is_contiguous()):
+            raise ValueError(f"{who}: colors must be a contiguous uint8 tensor [{self.G},{self.N},3] on {dev}")
         a = L.Draw.Args()
         _draw_style(a, trail, radius, half_width, alpha, max_jump, who)
-        f0, F_, dev = int(f0), frames.shape[0], self.queries.device
-        if f0 < 0 or f0 + F_ > self.committed:
-            raise ValueError(f"{who}: pictures of frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
-        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
-        if max(f0 - a.trail, 0) < oldest:
-            raise ValueError(f"{who}: frames [{f0 - a.trail}, {f0 + F_}) with their trail have left the history: it holds the last "
-                             f"{self.T_cap} of {self.committed} frames")
-        if F_ + a.trail > self.T_cap:  # (ctk_draw_tracks keeps F + trail <= R: the rows of a ring must not alias)
-            raise ValueError(f"{who}: {F_} pictures with a trail of {a.trail} need more than the {self.T_cap} history rows one call may "
-                             f"span: draw fewer frames per call")
-        g0, G = (0, self.G) if group is None else (int(group), 1)
-        if not 0 <= g0 < self.G:
-            raise ValueError(f"{who}: group must lie in [0, {self.G})")
-        for name, t_, dt, shape in (("colors", colors, torch.uint8, (self.G, self.N, 3)), ("first_row", first_row, torch.int32, (self.G, self.N))):
-            if t_ is None and name == "first_row":
-                continue
-            if not isinstance(t_, torch.Tensor) or t_.dtype != dt or tuple(t_.shape) != shape or t_.device != dev or not t_.is_contiguous():
-                raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor {list(shape)} on {dev}")
-        a.G, a.N, a.N_out, a.R, a.f0 = G, self.N, N_out, self.T_cap, f0
-        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
-        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
-        a.visible, a.colors = None, _ptr(colors[g0:])
-        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        f0 = int(f0)
+        self._held(who, f0, frames.shape[0], back=a.trail, hint=": draw fewer frames per call")
+        self._bind_history(a, g0, G, N_out, f0, None, scale, thresh, first_row)  # (_draw_launch has the F of the surface)
+        a.colors = _ptr_at(colors, g0)
         return _draw_launch(a, frames, out, layout, who)
 
     def motion(self, f0: int, F: int, *, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
@@ -1701,33 +1685,13 @@ class StreamGroups:
         takes) on the device.  The frames f0 - lag .. f0 + F - 1 (those >= 0) must be among the committed ones the history still
         holds: ValueError otherwise.  -> (motion [G,F,2,3], inlier [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
         who = "motion"
-        N_out = self.N if N_out is None else int(N_out)
-        if not 1 <= N_out <= min(self.N, L.Motion.POINTS_MAX):
-            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Motion.POINTS_MAX)}]")
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
         a = L.Motion.Args()
         _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
-        f0, F_, dev = int(f0), int(F), self.queries.device
-        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
-            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
-        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
-        if max(f0 - a.lag, 0) < oldest:
-            raise ValueError(f"{who}: frames [{f0 - a.lag}, {f0 + F_}) with their lag have left the history: it holds the last "
-                             f"{self.T_cap} of {self.committed} frames")
-        if F_ + a.lag > self.T_cap:  # (ctk_fit_motion keeps F + lag <= R: the rows of a ring must not alias)
-            raise ValueError(f"{who}: {F_} frames with a lag of {a.lag} need more than the {self.T_cap} history rows one call may "
-                             f"span: fit fewer frames per call")
-        g0, G = (0, self.G) if group is None else (int(group), 1)
-        if not 0 <= g0 < self.G:
-            raise ValueError(f"{who}: group must lie in [0, {self.G})")
-        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
-                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
-            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
-        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
-        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
-        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
-        a.visible = None
-        a.first_row = None if first_row is None else _ptr(first_row[g0:])
-        return _motion_launch(a, dev, out, who)
+        f0, F_ = int(f0), int(F)
+        self._held(who, f0, F_, back=a.lag, hint=": fit fewer frames per call")
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _motion_launch(a, self.queries.device, out, who)
 
     def stabilize(self, frames: torch.Tensor, f0: int, *, group: int = 0, reset: bool = False, alpha: float = 0.1, zoom: float = 1.0,
                   border: str = "fill", fill=(0, 0, 0), out: Optional[torch.Tensor] = None, layout: Optional[str] = None,
@@ -1781,38 +1745,13 @@ class StreamGroups:
         ValueError otherwise; an anchor needs no frame but its own copy.  -> (field [G,F,gh,gw,2], level [G,F,gh,gw], stats [G,F,4])
         on the device.  No wait."""
         who = "field"
-        N_out = self.N if N_out is None else int(N_out)
-        if not 1 <= N_out <= min(self.N, L.Field.POINTS_MAX):
-            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Field.POINTS_MAX)}]")
-        f0, F_, dev = int(f0), int(F), self.queries.device
-        g0, G = (0, self.G) if group is None else (int(group), 1)
-        if not 0 <= g0 < self.G:
-            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Field.POINTS_MAX)
+        dev = self.queries.device
         a = L.Field.Args()
         _field_rules(a, size, cell, radius, to, lag, anchor, G, self.N, dev, who)
-        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
-            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
-        lo, hi = f0, f0 + F_ - 1  # the frames that are read
-        if a.to >= 0:
-            lo, hi = min(lo, a.to), max(hi, a.to)
-        elif a.lag != 0:
-            lo, hi = min(lo, max(f0 - a.lag, 0)), max(hi, f0 + F_ - 1 - a.lag)
-        if hi >= self.committed:
-            raise ValueError(f"{who}: frames up to {hi} lie beyond what has been tracked ({self.committed} frames)")
-        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
-        if lo < oldest:
-            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) have left the history: it holds the last {self.T_cap} of {self.committed} "
-                             f"frames (pin the source frame while it is there)")
-        if max(hi - lo + 1, F_ + abs(a.lag)) > self.T_cap:  # (ctk_track_field keeps the rows one call reads apart)
-            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) need more than the {self.T_cap} history rows one call may span")
-        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
-                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
-            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
-        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
-        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
-        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
-        a.visible = None
-        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        f0, F_ = int(f0), int(F)
+        self._held(who, f0, F_, back=max(a.lag, 0), fwd=max(-a.lag, 0), to=a.to)  # (a negative lag reads the frame ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _field_launch(a, dev, out, who)
 
     def objects(self, f0: int, F: int, *, labels: Optional[torch.Tensor] = None, objects: int = 4, lag: int = 1, to: Optional[int] = None,
@@ -1828,38 +1767,13 @@ class StreamGroups:
         needs no frame but its own copy.  -> (motion [G,F,objects,2,3], label [G,F,N_out], stats [G,F,objects,4], box
         [G,F,objects,4]) on the device.  No wait."""
         who = "objects"
-        N_out = self.N if N_out is None else int(N_out)
-        if not 1 <= N_out <= min(self.N, L.Motion.POINTS_MAX):
-            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, L.Motion.POINTS_MAX)}]")
-        f0, F_, dev = int(f0), int(F), self.queries.device
-        g0, G = (0, self.G) if group is None else (int(group), 1)
-        if not 0 <= g0 < self.G:
-            raise ValueError(f"{who}: group must lie in [0, {self.G})")
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
+        dev = self.queries.device
         a = L.Objects.Args()
         _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
-        if f0 < 0 or F_ < 1 or f0 + F_ > self.committed:
-            raise ValueError(f"{who}: frames [{f0}, {f0 + F_}) lie beyond what has been tracked ({self.committed} frames)")
-        lo, hi = f0, f0 + F_ - 1  # the frames that are read
-        if a.to >= 0:
-            lo, hi = min(lo, a.to), max(hi, a.to)
-        elif a.lag != 0:
-            lo = min(lo, max(f0 - a.lag, 0))
-        if hi >= self.committed:
-            raise ValueError(f"{who}: frames up to {hi} lie beyond what has been tracked ({self.committed} frames)")
-        oldest = 0 if self.ring_rows is None else max(self.committed - self.T_cap, 0)
-        if lo < oldest:
-            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) have left the history: it holds the last {self.T_cap} of {self.committed} "
-                             f"frames (pin the source frame while it is there)")
-        if max(hi - lo + 1, F_ + a.lag) > self.T_cap:  # (ctk_fit_objects keeps the rows one call reads apart)
-            raise ValueError(f"{who}: frames [{lo}, {hi + 1}) need more than the {self.T_cap} history rows one call may span")
-        if first_row is not None and (not isinstance(first_row, torch.Tensor) or first_row.dtype != torch.int32 or
-                                      tuple(first_row.shape) != (self.G, self.N) or first_row.device != dev or not first_row.is_contiguous()):
-            raise ValueError(f"{who}: first_row must be a contiguous int32 tensor [{self.G},{self.N}] on {dev}")
-        a.G, a.N, a.N_out, a.R, a.f0, a.F = G, self.N, N_out, self.T_cap, f0, F_
-        a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
-        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr(h_[g0:]) for h_ in self.hist)
-        a.visible = None
-        a.first_row = None if first_row is None else _ptr(first_row[g0:])
+        f0, F_ = int(f0), int(F)
+        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_objects_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _objects_launch(a, dev, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":

@@ -16,6 +16,8 @@ import torch.nn.functional as F
 
 from .build_cotracker import build_cotracker
 
+_NO_STREAM = "no stream is running on the device stream state: run the first step and a tracked one first"
+
 
 def get_points_on_a_grid(size, extent, center=None, device="cpu"):
     """size x size points covering an (H, W) extent with margin W/64, row-major, as (x, y)
@@ -321,7 +323,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if not float(border) >= 0.0:
             raise ValueError("border must be >= 0")
         if getattr(self, "queries", None) is None or self._hw is None:
-            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+            raise RuntimeError(_NO_STREAM)
         ih, iw = self.interp_shape
         bounds = (-float(border), iw - 1 + float(border), -float(border), ih - 1 + float(border))
         look = self.model.window_len if look is None else int(look)
@@ -507,25 +509,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         points' query y, rebuilt only when add_queries / remove_queries / replenish changed the query table.  group: one query set
         only (default: all, drawn in order).  ValueError when first_frame - trail has left the ring (history_frames) or the
         pictures lie beyond what has been tracked.  Returns the drawn frames."""
-        if self.v2:
-            raise NotImplementedError("CoTracker2 keeps no stream state on the device: draw on a v2 predictor is not implemented")
-        gs = getattr(self.model, "_gstream", None)
-        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
-            raise ValueError("draw: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
-        one = frames.dim() == 3
-        if one:
-            frames = frames[None]
-            out = out[None] if out is not None else None
-        (H, W), (ih, iw) = self._hw, self.interp_shape
-        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
-        if not (hwc or chw):
-            raise ValueError(f"draw: expected {H} x {W} frames, [F,{H},{W},3] or [F,3,{H},{W}]; got {tuple(frames.shape)}")
-        done, F_ = gs.committed, frames.shape[0]
-        first_frame = done - F_ if first_frame is None else int(first_frame)
-        if first_frame < 0 or first_frame + F_ > done:
-            raise ValueError(f"draw: pictures of frames [{first_frame}, {first_frame + F_}) lie beyond what has been tracked ({done} frames)")
+        gs, scale = self._running("draw")
+        frames, out, one, layout, first_frame = self._raw_frames(frames, out, first_frame, gs, "draw")
         G, Nm = self.queries.shape[:2]
         dev = self.queries.device
         if colors is None:
@@ -536,9 +521,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                 raise ValueError(f"draw: colors must be uint8 [{self.N},3] or [{G},{self.N},3]")
             colors = torch.zeros(G, Nm, 3, dtype=torch.uint8, device=dev)
             colors[:, :self.N] = c.to(dev).reshape(-1, self.N, 3)
-        res = self.model.stream_draw(frames, first_frame, colors, N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
-                                     first_row=self._emit_first_row(), trail=trail, radius=radius, half_width=half_width, out=out,
-                                     layout="hwc" if hwc and not chw else ("chw" if chw and not hwc else None), group=group)
+        res = self.model.stream_draw(frames, first_frame, colors, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(),
+                                     trail=trail, radius=radius, half_width=half_width, out=out, layout=layout, group=group)
         return res[0] if one else res
 
     @torch.no_grad()
@@ -555,20 +539,10 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         (motion float32 [G,n,2,3], inlier int8 [G,n,N]: -1 not on both frames, 0 moves differently, 1 moves with the camera; stats
         int32 [G,n,4] = (points on both frames, inliers, best hypothesis or -1, 0)), on the device; a frame without a fit has the
         identity."""
-        if self.v2:
-            raise NotImplementedError("CoTracker2 keeps no stream state on the device: camera_motion on a v2 predictor is not implemented")
-        gs = getattr(self.model, "_gstream", None)
-        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
-        done = gs.committed
-        n = (min(self.step, done) if first_frame is None else done - int(first_frame)) if n is None else int(n)
-        first_frame = done - n if first_frame is None else int(first_frame)
-        if n < 1 or first_frame < 0 or first_frame + n > done:
-            raise ValueError(f"camera_motion: frames [{first_frame}, {first_frame + n}) lie beyond what has been tracked ({done} frames)")
-        (H, W), (ih, iw) = self._hw, self.interp_shape
-        return self.model.stream_motion(first_frame, n, N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
-                                        first_row=self._emit_first_row(), lag=lag, model=model, tol=tol, hypotheses=hypotheses,
-                                        min_base=min_base, seed=seed, group=group)
+        gs, scale = self._running("camera_motion")
+        first_frame, n = self._newest_frames(gs, n, first_frame, "camera_motion")
+        return self.model.stream_motion(first_frame, n, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(), lag=lag,
+                                        model=model, tol=tol, hypotheses=hypotheses, min_base=min_base, seed=seed, group=group)
 
     @torch.no_grad()
     def stabilize(self, frames, first_frame=None, alpha=0.1, zoom=1.0, border="fill", fill=(0, 0, 0), out=None, group=0, reset=False,
@@ -588,43 +562,46 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         been tracked).  A new first step drops the path.  Call draw() first when marks are wanted: the marks are then warped with the
         picture.  A point at raw position x of a frame appears at inverse(warp) x of the steadied one.  The stream's tracks are
         untouched.  Returns (frames_out: a new tensor, or `out`; warp float32 [n,2,3] on the device)."""
-        if self.v2:
-            raise NotImplementedError("CoTracker2 keeps no stream state on the device: stabilize on a v2 predictor is not implemented")
-        gs = getattr(self.model, "_gstream", None)
-        if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
-            raise ValueError("stabilize: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
-        one = frames.dim() == 3
-        if one:
-            frames = frames[None]
-            out = out[None] if out is not None else None
-        (H, W), (ih, iw) = self._hw, self.interp_shape
-        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
-        if not (hwc or chw):
-            raise ValueError(f"stabilize: expected {H} x {W} frames, [F,{H},{W},3] or [F,3,{H},{W}]; got {tuple(frames.shape)}")
-        done, F_ = gs.committed, frames.shape[0]
-        first_frame = done - F_ if first_frame is None else int(first_frame)
-        if first_frame < 0 or first_frame + F_ > done:
-            raise ValueError(f"stabilize: pictures of frames [{first_frame}, {first_frame + F_}) lie beyond what has been tracked ({done} frames)")
+        gs, scale = self._running("stabilize")
+        frames, out, one, layout, first_frame = self._raw_frames(frames, out, first_frame, gs, "stabilize")
         res, warp = self.model.stream_stabilize(frames, first_frame, group=group, reset=reset, alpha=alpha, zoom=zoom, border=border, fill=fill,
-                                                out=out, layout="hwc" if hwc and not chw else ("chw" if chw and not hwc else None),
-                                                N_out=self.N, scale=((W - 1) / (iw - 1), (H - 1) / (ih - 1)), thresh=0.6,
+                                                out=out, layout=layout, N_out=self.N, scale=scale, thresh=0.6,
                                                 first_row=self._emit_first_row(), model=model, tol=tol, hypotheses=hypotheses,
                                                 min_base=min_base, seed=seed)
         return (res[0] if one else res), warp
 
-    def _field_stream(self, who):
-        """The running stream's device state for pin / propagate / dense_flow, and the scale of history positions to raw-video pixels."""
+    def _running(self, who):
+        """The running stream's device state for the readers of its history (draw .. follow), and the scale of history positions to
+        raw-video pixels."""
         if self.v2:
             raise NotImplementedError(f"CoTracker2 keeps no stream state on the device: {who} on a v2 predictor is not implemented")
         gs = getattr(self.model, "_gstream", None)
         if getattr(self, "queries", None) is None or self._hw is None or gs is None or not gs.live or gs.committed == 0:
-            raise RuntimeError("no stream is running on the device stream state: run the first step and a tracked one first")
+            raise RuntimeError(_NO_STREAM)
         (H, W), (ih, iw) = self._hw, self.interp_shape
         return gs, ((W - 1) / (iw - 1), (H - 1) / (ih - 1))
 
-    def _field_frames(self, gs, n, first_frame, who):
+    def _raw_frames(self, frames, out, first_frame, gs, who):
+        """Raw-video pictures as draw() and stabilize() take them -> (frames [F,...], out, whether one frame was given, the layout by
+        the stream's H x W, first_frame: default the newest F tracked frames)."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+            raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
+        one = frames.dim() == 3
+        if one:
+            frames = frames[None]
+            out = out[None] if out is not None else None
+        H, W = self._hw
+        hwc, chw = tuple(frames.shape[1:]) == (H, W, 3), tuple(frames.shape[1:]) == (3, H, W)
+        if not (hwc or chw):
+            raise ValueError(f"{who}: expected {H} x {W} frames, [F,{H},{W},3] or [F,3,{H},{W}]; got {tuple(frames.shape)}")
+        done, F_ = gs.committed, frames.shape[0]
+        first_frame = done - F_ if first_frame is None else int(first_frame)
+        if first_frame < 0 or first_frame + F_ > done:
+            raise ValueError(f"{who}: pictures of frames [{first_frame}, {first_frame + F_}) lie beyond what has been tracked ({done} frames)")
+        return frames, out, one, ("hwc" if hwc and not chw else ("chw" if chw and not hwc else None)), first_frame
+
+    def _newest_frames(self, gs, n, first_frame, who):
+        """(n, first_frame) of a reader -> (first_frame, n); default: the newest `step` frames, ending at the newest."""
         done = gs.committed
         n = (min(self.step, done) if first_frame is None else done - int(first_frame)) if n is None else int(n)
         first_frame = done - n if first_frame is None else int(first_frame)
@@ -641,7 +618,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         being tracked is refined by the next step: pin it once it is final, or pin again.  ValueError when the frame has left the
         ring or has not been tracked."""
         from . import ops
-        gs, _ = self._field_stream("pin")
+        gs, _ = self._running("pin")
         frame, group = gs.committed - 1 if frame is None else int(frame), int(group)
         if not 0 <= group < gs.G:
             raise ValueError(f"pin: group must lie in [0, {gs.G})")
@@ -667,12 +644,12 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         pictures [n, ...] in the layout of `picture` (a new tensor, or `out`)."""
         from . import ops
         who = "propagate"
-        gs, scale = self._field_stream(who)
+        gs, scale = self._running(who)
         H, W = self._hw
         if not (isinstance(picture, torch.Tensor) and picture.dtype == torch.uint8 and picture.is_cuda and
                 tuple(picture.shape) in ((H, W, 3), (3, H, W), (H, W))):
             raise ValueError(f"{who}: picture must be a uint8 device tensor [{H},{W},3], [3,{H},{W}] or [{H},{W}]")
-        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
         if isinstance(anchor_or_frame, ops.FieldAnchor):
             if anchor_or_frame.group != int(group):
                 raise ValueError(f"{who}: the anchor was pinned on group {anchor_or_frame.group}, not {group}")
@@ -697,9 +674,9 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         limits are propagate()'s.  Returns float32 [n,H,W,2] on the device (a new tensor, or `out`)."""
         from . import ops
         who = "dense_flow"
-        gs, scale = self._field_stream(who)
+        gs, scale = self._running(who)
         H, W = self._hw
-        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
         a, _, flow = ops._warp_field_args(None, (H, W), cell, "fill", (0, 0, 0), None, True if out is None else out, None, n, who,
                                           device=self.queries.device)
         field = self.model.stream_field(first_frame, n, size=(H, W), cell=cell, radius=radius, lag=lag, N_out=self.N, scale=scale,
@@ -721,7 +698,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         round took it, it was not seen on both frames, or it is no user-visible point), the anchor pinned on `frame`, and `objects`."""
         from . import ops
         who = "split_objects"
-        gs, scale = self._field_stream(who)
+        gs, scale = self._running(who)
         frame, lag, group = gs.committed - 1 if frame is None else int(frame), int(lag), int(group)
         if not 0 <= group < gs.G:
             raise ValueError(f"{who}: group must lie in [0, {gs.G})")
@@ -742,7 +719,7 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         device and one pin(frame), without a wait.  Returns an ops.ObjectSet (see split_objects) for follow()."""
         from . import ops
         who = "label_objects"
-        gs, scale = self._field_stream(who)
+        gs, scale = self._running(who)
         boxes = torch.as_tensor(boxes, dtype=torch.float32)
         if boxes.dim() != 2 or boxes.shape[1] != 4 or not 1 <= boxes.shape[0] <= ops.L.Objects.OBJECTS_MAX:
             raise ValueError(f"{who}: boxes must be [L,4] = (x0, y0, x1, y1) with L in 1..{ops.L.Objects.OBJECTS_MAX}")
@@ -771,10 +748,10 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         x, max y) of the object's inliers on frame f in raw-video pixels, max < min where there is no fit."""
         from . import ops
         who = "follow"
-        gs, scale = self._field_stream(who)
+        gs, scale = self._running(who)
         if not isinstance(objects, ops.ObjectSet):
             raise ValueError(f"{who}: objects must be an ops.ObjectSet (split_objects, label_objects)")
-        first_frame, n = self._field_frames(gs, n, first_frame, who)
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
         motion, label, stats, box = self.model.stream_objects(first_frame, n, labels=objects.labels[None], objects=objects.objects,
                                                               anchor=objects.anchor, N_out=self.N, scale=scale, thresh=0.6,
                                                               first_row=self._emit_first_row(), model=model, tol=tol, hypotheses=hypotheses,

@@ -119,7 +119,7 @@ def launch_line(stream, reps, dev):
             kept["anchor"] = x.pin(frame=0)
         if i < 2:
             return
-        gs, scale = x._field_stream("bench")
+        gs, scale = x._running("bench")
         done = gs.committed
         kw = dict(size=RAW, cell=CELL, radius=RADIUS, anchor=kept["anchor"], N_out=x.N, scale=scale, thresh=0.6, first_row=x._emit_first_row(), group=0)
         field, _, stats = x.model.stream_field(done - STEP, STEP, **kw)
