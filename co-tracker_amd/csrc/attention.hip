@@ -657,6 +657,7 @@ __global__ __launch_bounds__(256, 2) void attention_self_kernel(AttnP p) {
   const int qb = r32 / spb, qi = qtile * spb + r32 % spb;
   const bool qvalid = (b0 + qb < p.nbatch) && (qi < p.n1);
   const int qbc = min(b0 + qb, p.nbatch - 1), qic = min(qi, p.n1 - 1);
+  const bool qmasked = p.qmask && !p.qmask[qic];  // CoTracker2 masks: every logit of a masked query is -FLT_MAX
   f16x8 qh[3], ql[3];
   {
     const float* qp = p.q + ((long)qbc * p.q_bs + (long)qic * p.q_is) * p.q_ld + head * HD + half * 8;
@@ -708,9 +709,13 @@ __global__ __launch_bounds__(256, 2) void attention_self_kernel(AttnP p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int slot = 8 * (e >> 2) + 4 * half + (e & 3);
-      const bool ok = (slot / spb == qb) && (b0 + slot / spb < p.nbatch) && (kt * spb + slot % spb < p.n2);
-      if (ok && ((p.kmask && !p.kmask[min(kt * spb + slot % spb, p.n2 - 1)]) || (p.qmask && !p.qmask[qic]))) sacc[e] = NEG_MAX;
-      sacc[e] = ok ? sacc[e] : -INFINITY;
+      const int ki = kt * spb + slot % spb;
+      const bool ok = (slot / spb == qb) && (b0 + slot / spb < p.nbatch) && (ki < p.n2);
+      // (selects, and the query's flag read once in front of the loop: as a conditional store into sacc[e] behind the two
+      // short-circuit mask loads, the compiled attention_self_kernel<2> had lost the query-mask store -- a masked query kept its
+      // logits; tests/test_gpu_attention_matrix.py, query masks on the square kernels)
+      const bool masked = qmasked || (p.kmask && !p.kmask[min(ki, p.n2 - 1)]);
+      sacc[e] = ok ? (masked ? NEG_MAX : sacc[e]) : -INFINITY;
       tmax = fmaxf(tmax, sacc[e]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));

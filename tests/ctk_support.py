@@ -84,6 +84,35 @@ def gemm_raw(A, lda, M, N, K, out, ldc, W=None, ldw=0, Wp=None, bias=None, bias_
     return L.load().ctk_gemm(C.byref(g), stream)
 
 
+# ---- ctk_attention_ex as the C-ABI sees it (tests/test_gpu_attention_matrix.py) ----------------------------------------------------------
+def attention_raw(q, q_ld, q_bs, q_is, k, v, kv_ld, kv_bs, kv_is, out, o_ld, o_bs, o_is, nbatch, n1, n2, splits=1, partial=None,
+                  o_split=False, key_mask=None, query_mask=None, batch2=None):
+    """Fills ctk_attn_args field by field (ops.attention fixes the leading dimensions at 384, o_bs = q_bs and the base pointers)
+    and calls ctk_attention_ex on the current stream -> its return code.  batch2: None (b2 == NULL, the single-level call) or a
+    dict with the fields of ctk_attn_batch2 (inner, q_os, kv_os, o_os, key_mask_os, query_mask_os).  Pointers: tensors (a view
+    passes the address of its first element), integers or None."""
+    from cotracker_amd import _lib as L
+
+    def p(x):
+        return x.data_ptr() if torch.is_tensor(x) else x
+
+    a = L.AttnArgs()
+    a.q, a.q_ld, a.q_bs, a.q_is = p(q), q_ld, q_bs, q_is
+    a.k, a.v, a.kv_ld, a.kv_bs, a.kv_is = p(k), p(v), kv_ld, kv_bs, kv_is
+    a.out, a.o_ld, a.o_bs, a.o_is = p(out), o_ld, o_bs, o_is
+    a.nbatch, a.n1, a.n2 = nbatch, n1, n2
+    a.splits, a.partial, a.o_split = splits, p(partial), int(o_split)
+    a.key_mask, a.query_mask = p(key_mask), p(query_mask)
+    b2 = None
+    if batch2 is not None:
+        b2 = L.AttnBatch2()
+        b2.inner, b2.reserved = batch2["inner"], 0
+        b2.q_os, b2.kv_os, b2.o_os = batch2["q_os"], batch2["kv_os"], batch2["o_os"]
+        b2.key_mask_os, b2.query_mask_os = batch2.get("key_mask_os", 0), batch2.get("query_mask_os", 0)
+    stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+    return L.load().ctk_attention_ex(C.byref(a), None if b2 is None else C.byref(b2), stream)
+
+
 def recorded(call):
     """-> (call(), {recorder row name: launches}) of the library launches `call` made.  The recorder is one per process."""
     from cotracker_amd import ops
