@@ -278,6 +278,37 @@ class Objects:
         ]
 
 
+class Planes:
+    """Holder of ctk_fit_planes_args and ctk_warp_planes_args (include/ctk.h, "fit planes / warp planes"), nested like Objects.Args and
+    for the same reason; their layouts are checked against the compiler by tests/test_planes_cabi.py.  The constants mirror
+    csrc/plane_math.h."""
+
+    PLANES_MAX, NONE, BORDER_KEEP = 16, 127, 2
+
+    class Args(C.Structure):
+        """ctk_fit_planes_args: history rows (and labels, or none) -> per frame up to L homographies, a label per point, and each
+        fit's counts and box."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("L", C.c_int32), ("min_points", C.c_int32),
+            ("inverse", C.c_int32), ("K", C.c_int32), ("seed", C.c_uint32),
+            ("tol", C.c_float), ("min_base", C.c_float), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp), ("labels", _fp),
+            ("homography", _fp), ("label", _fp), ("stats", _fp), ("box", _fp),
+        ]
+
+    class WarpArgs(C.Structure):
+        """ctk_warp_planes_args: uint8 pictures and one 3 x 3 matrix each -> the resampled pictures, of a size of their own."""
+        _fields_ = [
+            ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("C", C.c_int32),
+            ("layout", C.c_int32), ("border", C.c_int32), ("reserved", C.c_int32), ("fill", C.c_uint8 * 4),
+            ("src_frame_stride", C.c_int64), ("src_row_stride", C.c_int64), ("dst_frame_stride", C.c_int64), ("dst_row_stride", C.c_int64),
+            ("matrices", _fp), ("src", _fp), ("dst", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -367,6 +398,9 @@ SYMBOLS = {
     "ctk_warp_field": (C.c_int, [_P(Field.WarpArgs), _fp]),
     "ctk_fit_objects_workspace_bytes": (C.c_int, [_P(Objects.Args), _P(C.c_size_t)]),
     "ctk_fit_objects": (C.c_int, [_P(Objects.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_planes_workspace_bytes": (C.c_int, [_P(Planes.Args), _P(C.c_size_t)]),
+    "ctk_fit_planes": (C.c_int, [_P(Planes.Args), _fp, C.c_size_t, _fp]),
+    "ctk_warp_planes": (C.c_int, [_P(Planes.WarpArgs), _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

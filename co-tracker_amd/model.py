@@ -1041,6 +1041,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         launch and without a wait: ops.StreamGroups.objects.  Serves a ring history and the default one alike."""
         return self._running_stream().objects(f0, F, **kw)
 
+    def stream_planes(self, f0, F, **kw):
+        """Up to `planes` homography fits per frame [f0, f0 + F) of the running (or just closed) stream over the labelled regions of its
+        points -- or over all of them -- against f - lag, a fixed frame or an anchor, from its own history by one launch and without a
+        wait: ops.StreamGroups.planes.  Serves a ring history and the default one alike."""
+        return self._running_stream().planes(f0, F, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

@@ -256,14 +256,14 @@ def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin:
 
 
 # ------------------------------------------------------------------------------------------
-# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field and fit_objects differ
+# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field, fit_objects and fit_planes differ
 # in the history rows they need (`rows`) and in their own struct fields; StreamGroups has the other source, a stream's history.
 # ------------------------------------------------------------------------------------------
 _scratch_cache = {}
 
 
 def _scratch(kind: str, nbytes: int, device) -> torch.Tensor:
-    """The workspace of one kind of reader ("draw", "motion" -- fit_objects shares it --, "field"), cached per kind and device like
+    """The workspace of one kind of reader ("draw", "motion" -- fit_objects and fit_planes share it --, "field"), cached per kind and device like
     _workspace -- but never in that cache: captured window graphs bake the address of that one in, and a reader must never be the
     reason it moves.  Nor does one kind ever move the buffer of another."""
     key = (kind, device.index if device.index is not None else torch.cuda.current_device())
@@ -977,6 +977,273 @@ def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional
     return _objects_launch(a, dev, who)
 
 
+# ------------------------------------------------------------------------------------------
+# fit planes / warp planes (csrc/planes.hip, csrc/warp_planes.hip; include/ctk.h, "fit planes / warp planes")
+# ------------------------------------------------------------------------------------------
+PLANE_BORDERS = {"fill": L.Warp.BORDER_FILL, "edge": L.Warp.BORDER_EDGE, "keep": L.Planes.BORDER_KEEP}
+
+
+def _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device,
+                  who: str) -> None:
+    """The rounds, the fit and the source form of ctk_fit_planes_args; G, N: what labels and an anchor must match.  `to` or `anchor`
+    replaces the lag; both at once are refused."""
+    planes, min_points, hypotheses, seed = int(planes), int(min_points), int(hypotheses), int(seed)
+    if not 1 <= planes <= L.Planes.PLANES_MAX or not 1 <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: planes must lie in 1..{L.Planes.PLANES_MAX} and min_points in 1..{L.Motion.POINTS_MAX}")
+    if labels is None and planes != 1:
+        raise ValueError(f"{who}: without labels there is one list of all points: planes must be 1, got {planes}")
+    if to is not None and anchor is not None:
+        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
+    if not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Motion.HYPOTHESES_MAX} and seed in 0..2^32 - 1")
+    a.L, a.min_points, a.inverse, a.K, a.seed = planes, min_points, 1 if inverse else 0, hypotheses, seed
+    a.tol, a.min_base, a.reserved = float(tol), float(min_base), 0
+    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
+    if to is not None:
+        a.to = int(to)
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif anchor is not None:
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
+    else:
+        a.lag = int(lag)
+        if a.lag < 1:
+            raise ValueError(f"{who}: lag must be >= 1")
+    a.labels = None
+    if labels is not None:
+        if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int8 and labels.device == device and labels.numel() == G * N and
+                labels.shape[-1] == N and labels.is_contiguous()):
+            raise ValueError(f"{who}: labels must be a contiguous int8 tensor [{N}] or [{G},{N}] on {device}")
+        a.labels = _ptr(labels)
+
+
+def _planes_launch(a, device, who: str):
+    """Allocates the four outputs of ctk_fit_planes for the G, F, L and N_out of `a`, then the launch."""
+    out = _out_tuple(None, [("homography", torch.float32, (a.G, a.F, a.L, 3, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
+                            ("stats", torch.int32, (a.G, a.F, a.L, 4)), ("box", torch.int32, (a.G, a.F, a.L, 4))], device, who)
+    a.homography, a.label, a.stats, a.box = (_ptr(t_) for t_ in out)
+    ws = _scratch("motion", _query_bytes("ctk_fit_planes_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_planes(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_planes")
+    return out
+
+
+def fit_planes(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional[torch.Tensor] = None, planes: int = 1, lag: int = 1,
+               to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, inverse: bool = False, tol: float = 2.0,
+               hypotheses: int = 128, min_base: float = 16.0, min_points: int = 8, seed: int = 0, scale=(1, 1), frames=None,
+               first_row: Optional[torch.Tensor] = None):
+    """How planar surfaces seen under perspective -- a screen, a wall, a sign, a pitch -- have moved: up to `planes` robust homography
+    fits per frame over labelled sub-lists of the tracked points, by one launch and without a wait (ctk_fit_planes; include/ctk.h and
+    csrc/plane_math.h have the rules).  Works on any result of any predictor here, offline ones included.
+
+    tracks   float32 [T,N,2] or [G,T,N,2] (N <= 8192), positions = tracks * scale; visible bool / uint8 [T,N] or [G,T,N].
+    source   the matrix of frame f maps a source frame onto f: f - lag (the default), a fixed frame `to`, or a FieldAnchor; `to` or
+             `anchor` replaces the lag.  inverse=True: the matrix maps frame f onto the source frame instead (what a backward warp
+             needs; fitted that way round, nothing is inverted).
+    labels   int8 [N] / [G,N]: plane r is fitted to the points labelled r (anything outside 0..planes-1: no plane's), the planes are
+             independent.  None: planes must be 1 and every point belongs to it.
+    Each fit scores `hypotheses` seeded four-point samples with the bound `tol` (pixels, max norm; a sample needs triangles of twice
+    the area min_base^2) and refits the best over its inliers; one with fewer than min_points inliers is no fit.  Rows are the frames
+    of frames = (first_frame, n); None: every tracked frame.  Returns (homography float32 [G,F,planes,3,3]: (X, Y, Z) = H @ (x, y, 1),
+    position = (X / Z, Y / Z), the identity where nothing was fitted; label int8 [G,F,N]: -1 not on both frames, r = inlier of plane r,
+    127 = no plane took it; stats int32 [G,F,planes,4] = (points of the plane, inliers, best hypothesis or -1, 1 if the refit fell back
+    to the best sample's own matrix); box int32 [G,F,planes,4] = (min x, min y, max x, max y) of the inliers on frame f in 1/16 pixel,
+    (0, 0, -1, -1) where nothing was fitted)."""
+    who = "fit_planes"
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    f0, F_ = _frames_of(0, None, T, who) if frames is None else _frames_of(frames[0], int(frames[1]), T, who)
+    a = L.Planes.Args()
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1 and G > 1:
+        labels = labels.expand(G, -1).contiguous()
+    _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + a.lag), f0=f0, F=F_, scale=scale)
+    return _planes_launch(a, dev, who)
+
+
+def warp_planes(src: torch.Tensor, matrices: torch.Tensor, *, size=None, out: Optional[torch.Tensor] = None, border: str = "fill",
+                fill=(0, 0, 0), layout: Optional[str] = None) -> torch.Tensor:
+    """uint8 pictures resampled under one 3 x 3 matrix each, on the device, by one launch and without a wait (ctk_warp_planes;
+    include/ctk.h and csrc/plane_math.h have the rules) -- what a caller otherwise writes as a projective grid, grid_sample and a
+    torch.where composite.
+
+    src      uint8 [F,Hs,Ws,3], [F,3,Hs,Ws] or [F,Hs,Ws] (masks) on the device, strides and layout as warp_field reads them; one picture
+             ([1, ...], or expanded with a frame stride of 0) serves every matrix.
+    matrices float32 [F,3,3] on the device: matrices[j] maps an OUTPUT pixel to a SOURCE position, (X, Y, Z) = m (x, y, 1), position =
+             (X / Z, Y / Z), pixel centres at integers.  A pixel with Z <= 0, with a position beyond 2^20, or under a matrix that is not
+             finite is outside.
+    size     (H, W) of the output pictures (default: the source's); out: uint8 pictures [F,H,W,...] of the source's layout with
+             strides of their own, which must not overlap the source.
+    border   "fill": a tap outside the source has the value `fill`; "edge": the edge pixels go on for ever; an outside pixel takes
+             `fill` under both.  "keep": a pixel that is outside or has a tap outside the source is NOT written -- the picture is
+             drawn into `out` (required then), which may be the frames of a video themselves.
+    Bilinear in 1/256 pixel: the identity on equal sizes copies bit for bit, an integer shift is a shifted copy.  Returns out."""
+    who = "warp_planes"
+    if border not in PLANE_BORDERS:
+        raise ValueError(f"{who}: border must be one of {sorted(PLANE_BORDERS)}, got {border!r}")
+    if not (isinstance(matrices, torch.Tensor) and matrices.is_cuda and matrices.dtype == torch.float32 and matrices.dim() == 3 and
+            tuple(matrices.shape[1:]) == (3, 3) and matrices.shape[0] >= 1 and matrices.is_contiguous()):
+        raise ValueError(f"{who}: matrices must be a contiguous float32 device tensor [F,3,3]")
+    F_ = matrices.shape[0]
+    if isinstance(src, torch.Tensor) and src.dim() in (3, 4) and src.shape[0] == 1 and F_ > 1:
+        src = src.expand(F_, *src.shape[1:])
+    C_, lay, Fs, Hs, Ws, row, frame = _field_surface(src, layout, who)
+    if Fs != F_ or src.device != matrices.device:
+        raise ValueError(f"{who}: {Fs} pictures on {src.device} for {F_} matrices on {matrices.device}")
+    fill = [int(v) for v in ((fill,) * 3 if isinstance(fill, int) else fill)]
+    if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
+        raise ValueError(f"{who}: fill must hold three values in 0..255 (or one)")
+    H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
+    want = (F_, H, W) if src.dim() == 3 else ((F_, H, W, 3) if lay == "hwc" else (F_, 3, H, W))
+    if out is None:
+        if border == "keep":
+            raise ValueError(f"{who}: border 'keep' draws into `out`: pass the pictures to draw into")
+        if H < 1 or W < 1:
+            raise ValueError(f"{who}: size = (H, W) must be positive")
+        out = torch.empty(want, dtype=torch.uint8, device=src.device)
+    elif not isinstance(out, torch.Tensor) or out.device != src.device or (size is not None and tuple(out.shape) != want) or out.dim() != src.dim():
+        raise ValueError(f"{who}: out must be uint8 pictures {list(want)} on {src.device}")
+    Co, olay, Fo, H, W, orow, oframe = _field_surface(out, lay if src.dim() == 4 else None, who)
+    if (Co, olay, Fo) != (C_, lay, F_):
+        raise ValueError(f"{who}: out must hold {F_} pictures in the layout of the source")
+    a = L.Planes.WarpArgs()
+    a.F, a.H, a.W, a.Hs, a.Ws, a.C, a.layout = F_, H, W, Hs, Ws, C_, (L.INGEST_HWC if lay == "hwc" else L.INGEST_CHW)
+    a.border, a.reserved = PLANE_BORDERS[border], 0
+    for k in range(3):
+        a.fill[k] = fill[k]
+    a.src_frame_stride, a.src_row_stride, a.dst_frame_stride, a.dst_row_stride = frame, row, oframe, orow
+    a.matrices, a.src, a.dst = _ptr(matrices), _ptr(src), _ptr(out)
+    L.check(L.load().ctk_warp_planes(C.byref(a), _stream()), "ctk_warp_planes")  # (overlapping src and out: refused there)
+    return out
+
+
+def quad_matrix(corners, size) -> torch.Tensor:
+    """The float64 3 x 3 matrix [h22 = 1] that maps the pixels of an h x w picture (size = (h, w)) onto a quad: the picture's corner
+    pixels (0, 0), (w - 1, 0), (w - 1, h - 1), (0, h - 1) land on corners [4,2] = ((x, y), ...) in that order.  On the host, from host
+    values only (a list, an array or a host tensor): nothing waits for the device."""
+    who = "quad_matrix"
+    if isinstance(corners, torch.Tensor) and corners.is_cuda:
+        raise ValueError(f"{who}: corners must be host values [4,2] (a device tensor would have to be waited for)")
+    c = torch.as_tensor(corners, dtype=torch.float64).reshape(-1)
+    h, w = int(size[0]), int(size[1])
+    if c.numel() != 8 or not bool(torch.isfinite(c).all()) or h < 2 or w < 2:
+        raise ValueError(f"{who}: corners must hold four finite points [4,2] and size = (h, w) at least (2, 2)")
+    c = c.reshape(4, 2)
+    src = torch.tensor([[0.0, 0.0], [w - 1.0, 0.0], [w - 1.0, h - 1.0], [0.0, h - 1.0]], dtype=torch.float64)
+    A, b = torch.zeros(8, 8, dtype=torch.float64), torch.zeros(8, dtype=torch.float64)
+    for k in range(4):
+        (x, y), (X, Y) = src[k].tolist(), c[k].tolist()
+        A[2 * k] = torch.tensor([x, y, 1.0, 0.0, 0.0, 0.0, -x * X, -y * X], dtype=torch.float64)
+        A[2 * k + 1] = torch.tensor([0.0, 0.0, 0.0, x, y, 1.0, -x * Y, -y * Y], dtype=torch.float64)
+        b[2 * k], b[2 * k + 1] = X, Y
+    pts = c.tolist()
+    flat = any((pts[j][0] - pts[i][0]) * (pts[k][1] - pts[i][1]) - (pts[j][1] - pts[i][1]) * (pts[k][0] - pts[i][0]) == 0.0
+               for i, j, k in ((1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2)))
+    try:
+        sol = None if flat else torch.linalg.solve(A, b)
+    except RuntimeError:
+        sol = None
+    if sol is None or not bool(torch.isfinite(sol).all()):
+        raise ValueError(f"{who}: the corners do not span a quad (three of them lie on a line)")
+    return torch.cat([sol, torch.ones(1, dtype=torch.float64)]).reshape(3, 3)
+
+
+_quad_cache = {}
+_QUAD_CACHE_MAX = 64
+
+
+def quad_constant(corners, size, device, *, inverse: bool) -> torch.Tensor:
+    """quad_matrix(corners, size) -- inverse=True: its inverse -- as a float64 [3,3] constant on `device`, for plane_matrices.  Kept per
+    (corners, size, inverse, device), like the `post` matrix StreamGroups.stabilize keeps: a picture that stays pinned to the same quad
+    costs the 8 x 8 host solve, the inverse and the upload once, not per call.  A new quad goes up through pinned memory with a
+    non-blocking copy: the host never waits for what is queued on the stream.  The last 64 quads are kept."""
+    if isinstance(corners, torch.Tensor) and corners.is_cuda:
+        raise ValueError("quad_constant: corners must be host values [4,2] (a device tensor would have to be waited for)")
+    flat = torch.as_tensor(corners, dtype=torch.float64).reshape(-1).tolist()
+    device = torch.device(device)
+    key = (tuple(flat), int(size[0]), int(size[1]), bool(inverse), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    q = _quad_cache.get(key)
+    if q is None:
+        host = quad_matrix(corners, size)
+        host = torch.linalg.inv(host) if inverse else host
+        q = host.contiguous().pin_memory().to(device, non_blocking=True)
+        while len(_quad_cache) >= _QUAD_CACHE_MAX:
+            _quad_cache.pop(next(iter(_quad_cache)))
+        _quad_cache[key] = q
+    return q
+
+
+def plane_matrices(homography: torch.Tensor, stats: torch.Tensor, quad: torch.Tensor, *, inverse: bool) -> torch.Tensor:
+    """The matrices warp_planes wants from one plane's fits: homography float32 [F,3,3] and stats int32 [F,4] of fit_planes, and the
+    quad of the picture on the source frame: `quad` is quad_constant(..., inverse=inverse) on the device -- the cached constant, used as
+    it is --, or the host float64 quad_matrix, which is inverted here when `inverse` and goes up through pinned memory with a
+    non-blocking copy.  inverse=True (the fits were made with inverse=True): a frame's pixel -> the picture's pixel, inverse(quad) @ H,
+    and the zero matrix -- every pixel outside -- on a frame without a fit.  inverse=False: an upright picture's pixel -> the frame's
+    pixel, H @ quad.  One small float64 matmul and a where on the device; the host waits for nothing."""
+    if not (isinstance(quad, torch.Tensor) and quad.dtype == torch.float64 and tuple(quad.shape) == (3, 3)):
+        raise ValueError("plane_matrices: quad must be a float64 [3,3] tensor (quad_constant, or quad_matrix)")
+    if quad.is_cuda:
+        q = quad
+    else:
+        q = (torch.linalg.inv(quad) if inverse else quad).contiguous().pin_memory().to(homography.device, non_blocking=True)
+    h = homography.to(torch.float64)
+    m = torch.matmul(q, h) if inverse else torch.matmul(h, q)
+    if inverse:
+        m = torch.where((stats[:, 1] > 0)[:, None, None], m, torch.zeros_like(m))
+    return m.to(torch.float32).contiguous()
+
+
+def _plane_of(tracks, who: str):
+    if not (isinstance(tracks, torch.Tensor) and tracks.dim() in (3, 4) and (tracks.dim() == 3 or tracks.shape[0] == 1)):
+        raise ValueError(f"{who}: tracks must be a float32 device tensor [T,N,2] or [1,T,N,2]")
+
+
+def overlay(frames: torch.Tensor, picture: torch.Tensor, corners, tracks: torch.Tensor, visible: torch.Tensor, *, src_frame: int,
+            first_frame: int = 0, labels: Optional[torch.Tensor] = None, planes: int = 1, index: int = 0, layout: Optional[str] = None,
+            **fit) -> torch.Tensor:
+    """A picture pinned onto a planar surface so that it stays put, drawn IN PLACE onto uint8 frames on the device: fit_planes(to =
+    src_frame, inverse=True), plane_matrices with the cached quad_constant, warp_planes(border="keep") -- two launches plus elementwise
+    torch, no wait.  Works on any
+    result of any predictor here.
+
+    frames   uint8 [F,H,W,3] or [F,3,H,W] on the device: picture j shows frame first_frame + j of the tracks.
+    picture  uint8 [h,w,3] (or [3,h,w] for planar frames) on the device; its corner pixels sit at corners [4,2] (host values, the
+             order of quad_matrix) on frame src_frame, in the pixels of tracks * scale.
+    labels, planes, index   the plane that carries the picture: the points labelled `index` (None: all points); **fit: fit_planes'
+             scale, tol, hypotheses, min_base, min_points, seed, first_row.
+    A frame without a fit gets nothing.  No alpha blending and no anti-aliased edge.  Returns frames."""
+    who = "overlay"
+    _plane_of(tracks, who)
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 4 and isinstance(picture, torch.Tensor) and picture.dim() == 3):
+        raise ValueError(f"{who}: frames must be uint8 [F,H,W,3] or [F,3,H,W] and picture [h,w,3] or [3,h,w] on the device")
+    lay = _draw_surface(frames, layout, who)[0]
+    size = tuple(picture.shape[:2]) if lay == "hwc" else tuple(picture.shape[1:])
+    quad = quad_constant(corners, size, frames.device, inverse=True)
+    hom, _, stats, _ = fit_planes(tracks, visible, labels=labels, planes=planes, to=int(src_frame), inverse=True,
+                                  frames=(int(first_frame), frames.shape[0]), **fit)
+    m = plane_matrices(hom[0, :, int(index)], stats[0, :, int(index)], quad, inverse=True)
+    return warp_planes(picture[None], m, out=frames, border="keep", layout=lay)
+
+
+def rectify(frames: torch.Tensor, corners, tracks: torch.Tensor, visible: torch.Tensor, *, src_frame: int, size, first_frame: int = 0,
+            labels: Optional[torch.Tensor] = None, planes: int = 1, index: int = 0, border: str = "fill", fill=(0, 0, 0),
+            out: Optional[torch.Tensor] = None, layout: Optional[str] = None, **fit) -> torch.Tensor:
+    """A planar surface shown upright: the quad whose corners sit at corners [4,2] on frame src_frame, resampled from every frame into
+    an h x w picture (size = (h, w)) through the forward matrices -- fit_planes(to = src_frame), plane_matrices, warp_planes: two
+    launches plus elementwise torch, no wait.  The arguments are overlay()'s; border, fill and out are warp_planes'.  A frame without a
+    fit shows the quad where it was on frame src_frame.  Returns the pictures [F,h,w,3] (or [F,3,h,w])."""
+    who = "rectify"
+    _plane_of(tracks, who)
+    if not (isinstance(frames, torch.Tensor) and frames.dim() == 4):
+        raise ValueError(f"{who}: frames must be a uint8 device tensor [F,H,W,3] or [F,3,H,W]")
+    lay = _draw_surface(frames, layout, who)[0]
+    quad = quad_constant(corners, size, frames.device, inverse=False)
+    hom, _, stats, _ = fit_planes(tracks, visible, labels=labels, planes=planes, to=int(src_frame), inverse=False,
+                                  frames=(int(first_frame), frames.shape[0]), **fit)
+    m = plane_matrices(hom[0, :, int(index)], stats[0, :, int(index)], quad, inverse=False)
+    return warp_planes(frames, m, size=size, out=out, border=border, fill=fill, layout=lay)
+
+
 def normalize_to_nhwc(fmaps_nchw: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[F,128,H,W] -> channel-L2-normalised NHWC [F,H,W,128] (cotracker3_online.py:384-394); `out` = a contiguous
     [F,H,W,128] destination (e.g. a frame range of a preallocated feature tensor)."""
@@ -1406,7 +1673,7 @@ EMPTY_FRAME = L.STREAM_EMPTY_FRAME
 
 
 def history_span(committed: int, T_cap: int, ring: bool, f0: int, F: int, back: int = 0, fwd: int = 0, to: int = -1):
-    """The one range rule of the readers of a stream's history (StreamGroups.draw, motion, field, objects): may a call for frames
+    """The one range rule of the readers of a stream's history (StreamGroups.draw, motion, field, objects, planes): may a call for frames
     [f0, f0 + F) be served by a history of T_cap rows, `committed` frames in, a ring or not?  Besides its own frames the call reads
     the `back` frames before each (a trail, a positive lag; those >= 0), the frame `fwd` after each (a negative lag), and the fixed
     frame `to` (>= 0); an anchor reads nothing more.  -> None, or what is wrong with the frames [lo, hi] that are read:
@@ -1534,7 +1801,7 @@ class StreamGroups:
         r0, r1 = f0 % R, f0 % R + (f1 - f0)
         return [slice(r0, r1)] if r1 <= R else [slice(r0, R), slice(0, r1 - R)]
 
-    # -- readers of the history: emit, health, draw, motion, field, objects.  What they share is stated here, once: whom a call reads
+    # -- readers of the history: emit, health, draw, motion, field, objects, planes.  What they share is stated here, once: whom a call reads
     # (_reader), which frames it may read (_held: history_span) and the source fields of its args (_bind_history).  A reader itself
     # holds its own options, the back / fwd / to of its span, its own struct fields and its launch. ---------------------------------
     def _reader(self, who: str, N_out, group, first_row, points_max: Optional[int] = None, need_row: bool = False):
@@ -1775,6 +2042,28 @@ class StreamGroups:
         self._held(who, f0, F_, back=a.lag, to=a.to)  # (_objects_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
         self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _objects_launch(a, dev, who)
+
+    def planes(self, f0: int, F: int, *, labels: Optional[torch.Tensor] = None, planes: int = 1, lag: int = 1, to: Optional[int] = None,
+               anchor: Optional[FieldAnchor] = None, inverse: bool = False, N_out: Optional[int] = None, scale=(1.0, 1.0),
+               thresh: float = 0.6, first_row: Optional[torch.Tensor] = None, tol: float = 2.0, hypotheses: int = 128,
+               min_base: float = 16.0, min_points: int = 8, seed: int = 0, group: Optional[int] = None):
+        """Up to `planes` homography fits per frame f0 .. f0 + F - 1 over the first N_out points of every group (or of `group` alone),
+        each frame against a source frame (f - lag, a fixed `to`, or an `anchor`: fit_planes has the picture), straight from the
+        stream's own history and logits -- no emit in between --, by the one launch of ctk_fit_planes: visibility is emit's sigmoid(vis)
+        * sigmoid(conf) > thresh, positions are history coords * scale, tol and min_base are in those pixels.  labels int8 [G,N] (of the
+        groups asked for) on the device, or None: one plane of all points.  first_row int32 [G,N] (what emit takes) on the device.
+        Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError otherwise; an anchor
+        needs no frame but its own copy.  -> (homography [G,F,planes,3,3], label [G,F,N_out], stats [G,F,planes,4], box
+        [G,F,planes,4]) on the device.  No wait."""
+        who = "planes"
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
+        dev = self.queries.device
+        a = L.Planes.Args()
+        _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
+        f0, F_ = int(f0), int(F)
+        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_planes_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _planes_launch(a, dev, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

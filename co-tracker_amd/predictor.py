@@ -758,6 +758,91 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                                                               min_base=min_base, min_points=min_points, seed=seed, group=objects.anchor.group)
         return motion[0], label[0], stats[0], box[0].to(torch.float32) / 16.0
 
+    @torch.no_grad()
+    def follow_planes(self, objects, n=None, first_frame=None, inverse=False, tol=2.0, hypotheses=128, min_base=16.0, min_points=8, seed=0):
+        """Not in the reference: where the objects of an ops.ObjectSet (split_objects / label_objects) are on the n frames from
+        first_frame on (default: the frames of the window just tracked) when each is a planar surface seen under perspective -- a
+        screen, a wall, a sign, a pitch -- which follow()'s similarity slides and shears on: one launch of ctk_fit_planes against the
+        set's anchor (ops.StreamGroups.planes on the stream's own history and logits), without a wait.  Object r is fitted to the points
+        labelled r that are visible on the frame and on the anchor; the objects are independent, and one with fewer than min_points
+        inliers (or fewer than four points) has no fit on that frame.  inverse=True: the matrices map frame f onto the anchor's frame
+        (what a backward warp needs; fitted that way round, nothing is inverted).  tol, hypotheses, min_base (raw-video pixels) and seed
+        are ops.fit_planes'.  Returns, on the device: homography float32 [n,L,3,3] in raw-video pixels: (X, Y, Z) = H @ (x, y, 1) of
+        a position on the anchor's frame, position on frame f = (X / Z, Y / Z), the identity where there is no fit; label int8 [n,N]:
+        -1 not on both frames, r = moves with object r, 127 = labelled for no object or does not move with its own; stats int32 [n,L,4]
+        = (points of the object on both frames, inliers, best hypothesis or -1, 1 if the refit fell back); box float32 [n,L,4] = (min
+        x, min y, max x, max y) of the object's inliers on frame f in raw-video pixels, max < min where there is no fit."""
+        from . import ops
+        who = "follow_planes"
+        gs, scale = self._running(who)
+        if not isinstance(objects, ops.ObjectSet):
+            raise ValueError(f"{who}: objects must be an ops.ObjectSet (split_objects, label_objects)")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        hom, label, stats, box = self.model.stream_planes(first_frame, n, labels=objects.labels[None], planes=objects.objects,
+                                                          anchor=objects.anchor, inverse=inverse, N_out=self.N, scale=scale, thresh=0.6,
+                                                          first_row=self._emit_first_row(), tol=tol, hypotheses=hypotheses,
+                                                          min_base=min_base, min_points=min_points, seed=seed, group=objects.anchor.group)
+        return hom[0], label[0], stats[0], box[0].to(torch.float32) / 16.0
+
+    def _plane_index(self, objects, index, who):
+        from . import ops
+        if not isinstance(objects, ops.ObjectSet):
+            raise ValueError(f"{who}: objects must be an ops.ObjectSet (split_objects, label_objects)")
+        index = int(index)
+        if not 0 <= index < objects.objects:
+            raise ValueError(f"{who}: index must lie in [0, {objects.objects})")
+        return index
+
+    @torch.no_grad()
+    def overlay(self, frames, picture, corners, objects, index=0, first_frame=None):
+        """Not in the reference: a `picture` -- uint8, [h,w,3] or a mask-like [h,w], on the device -- pinned onto the planar object
+        `index` of an ops.ObjectSet so that it stays put, drawn IN PLACE onto raw-resolution uint8 frames ([F,H,W,3], [F,3,H,W] or one
+        frame; picture j shows frame first_frame + j, default: the newest F tracked frames).  The picture's corner pixels (0, 0),
+        (w - 1, 0), (w - 1, h - 1), (0, h - 1) sit at corners [4,2] (host values, raw pixels) on the anchor's frame.  Steps:
+        follow_planes(inverse=True); one small device matmul with the constant inverse(ops.quad_matrix), which ops.quad_constant keeps on
+        the device per quad (the host solve and the non-blocking upload happen on the first call for a quad only); a zero matrix where a frame
+        has no fit, so that it gets nothing; ops.warp_planes(border="keep") -- two launches plus elementwise torch, no wait.  A [h,w]
+        picture is drawn into all three channels.  No alpha blending, no anti-aliased edge.  The stream's tracks are untouched.
+        Returns the frames."""
+        from . import ops
+        who = "overlay"
+        gs, _ = self._running(who)
+        index = self._plane_index(objects, index, who)
+        frames, _, one, layout, first_frame = self._raw_frames(frames, None, first_frame, gs, who)
+        if not (isinstance(picture, torch.Tensor) and picture.dtype == torch.uint8 and picture.is_cuda and
+                (picture.dim() == 2 or (picture.dim() == 3 and picture.shape[2] == 3))):
+            raise ValueError(f"{who}: picture must be a uint8 device tensor [h,w,3] or [h,w]")
+        layout = layout or "hwc"
+        size = tuple(picture.shape[:2])
+        quad = ops.quad_constant(corners, size, frames.device, inverse=True)  # (cached: the host solve and the upload happen once per quad)
+        pic = picture[..., None].expand(*size, 3) if picture.dim() == 2 else picture
+        pic = (pic if layout == "hwc" else pic.permute(2, 0, 1)).contiguous()
+        hom, _, stats, _ = self.follow_planes(objects, frames.shape[0], first_frame, inverse=True)
+        m = ops.plane_matrices(hom[:, index], stats[:, index], quad, inverse=True)
+        ops.warp_planes(pic[None], m, out=frames, border="keep", layout=layout)
+        return frames[0] if one else frames
+
+    @torch.no_grad()
+    def rectify(self, frames, corners, objects, index=0, size=(256, 256), first_frame=None, border="fill", fill=(0, 0, 0), out=None):
+        """Not in the reference: the planar object `index` of an ops.ObjectSet shown upright -- the quad whose corners sit at corners
+        [4,2] (host values, raw pixels) on the anchor's frame, resampled from each of the raw-resolution uint8 `frames` (as in overlay())
+        into an h x w picture, size = (h, w), through the forward matrices: follow_planes(); one small device matmul with
+        ops.quad_matrix; ops.warp_planes -- two launches plus elementwise torch, no wait.  border, fill and out are ops.warp_planes'
+        ("fill" or "edge").  A frame without a fit shows the quad where it was on the anchor's frame.  Returns [n,h,w,3] (or [n,3,h,w]
+        for planar frames; [h,w,3] for one frame, as overlay() returns one frame for one; a new tensor, or `out`)."""
+        from . import ops
+        who = "rectify"
+        gs, _ = self._running(who)
+        index = self._plane_index(objects, index, who)
+        frames, out, one, layout, first_frame = self._raw_frames(frames, out, first_frame, gs, who)
+        if border not in ops.WARP_BORDERS:
+            raise ValueError(f"{who}: border must be one of {sorted(ops.WARP_BORDERS)}, got {border!r}")
+        quad = ops.quad_constant(corners, size, frames.device, inverse=False)  # (cached, as in overlay())
+        hom, _, stats, _ = self.follow_planes(objects, frames.shape[0], first_frame)
+        m = ops.plane_matrices(hom[:, index], stats[:, index], quad, inverse=False)
+        res = ops.warp_planes(frames, m, size=size, out=out, border=border, fill=fill, layout=layout or "hwc")
+        return res[0] if one else res
+
     def _mark_rows(self):
         """The row from which each user-visible point carries information, on the device: visibility is False below it, and
         everywhere in an empty slot.  Refreshed from the model's host bookkeeping by add / remove only."""

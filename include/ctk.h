@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_planes and ctk_fit_planes_workspace_bytes on the
+ *       new struct ctk_fit_planes_args: per frame, up to 16 robust homography fits (four-point hypotheses, integer admissibility, an
+ *       order-independent fixed-point refit) over the regions a caller labelled, in the frame of ctk_fit_objects' labels mode; and
+ *       + ctk_warp_planes on the new struct ctk_warp_planes_args: uint8 pictures resampled under a 3 x 3 matrix each, with the new
+ *       border CTK_WARP_KEEP that draws a picture into frames in place (csrc/plane_math.h); one launch each, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_objects and ctk_fit_objects_workspace_bytes on the
  *       new struct ctk_fit_objects_args: per frame, up to 16 robust fits (ctk_fit_motion's rules) over sub-lists of one list of
  *       correspondences -- the regions a caller labelled, or what the earlier fits left --, against a fixed frame, f - lag or an
@@ -932,6 +937,125 @@ typedef struct ctk_fit_objects_args {
 } ctk_fit_objects_args;
 int ctk_fit_objects_workspace_bytes(const ctk_fit_objects_args* a, size_t* out_bytes);
 int ctk_fit_objects(const ctk_fit_objects_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit planes / warp planes: planar surfaces under perspective, and pictures resampled under 3 x 3 matrices ---------------------
+ * For a caller whose tracks are on the device and whose object is a planar surface seen under perspective -- a screen, a wall, a sign,
+ * a pitch --, which a similarity (ctk_fit_objects) slides and shears on: ctk_fit_planes fits up to L homographies per group g and frame
+ * f in [f0, f0 + F), and ctk_warp_planes resamples pictures under such matrices: a picture pinned onto the surface, or the surface
+ * shown upright.  The rules are stated once in csrc/plane_math.h.
+ *
+ * ctk_fit_planes.  The frame of the call is ctk_fit_objects' labels mode; everything not named here is ctk_fit_objects' and
+ * ctk_fit_motion's bit for bit: positions (1/16 pixel), the pair rule with its three source forms, first_row, `visible` or the logits
+ * with thresh, N_out <= 8192, mix, the seed of a round, the key ("most inliers, then the lowest k"), min_points, the labels.
+ *   lists      `labels` int8 [G,N] given: list_r holds the correspondences labelled r, L in 1..16 (CTK_PLANES_MAX, csrc/plane_math.h);
+ *              `labels` NULL: L must be 1 and list_0 holds every correspondence.  There is no split mode.  The rounds are independent.
+ *   inverse    0 / 1.  With 1 the roles of P (source) and Q (frame f) are swapped after staging: the matrix maps frame f onto the
+ *              source frame, which is what a backward warp needs.  No matrix is inverted anywhere.
+ *   sample     hypothesis k of a list with M_r >= 4 entries: h_t = mix(seed_r ^ mix(f * 0x9e3779b9 + 4k + t)), t = 0..3;
+ *              i_t = h_t % (M_r - t), then bumped past the earlier indices taken in ascending order: four distinct indices; f is the
+ *              absolute frame number.
+ *   admissible integers only.  p_t = P_{i_t} - P_{i_0}, q_t likewise; d_abc = (p_b - p_a) x (p_c - p_a) over abc = 123, 023, 013, 012
+ *              (|d| <= 2^37), e_abc of the q likewise.  Admissible iff every |d| and every |e| is at least base2 (ctk_fit_motion's,
+ *              from min_base) and at least 1, and every d has the sign of its e: no three sample points are near a line,
+ *              and the quad keeps its orientation.
+ *   matrix     in double, one rounded operation per step, no contraction, no pivoting: the projective basis B_P = [l1 p1 | l2 p2 |
+ *              l3 p3] on homogeneous (x, y, 1) with (l1, l2, l3) = (d_023, -d_013, d_012), every entry (double)l * (double)coordinate;
+ *              B_Q from the e and q likewise; H' = B_Q adj(B_P), each cofactor a b - c d, each product entry (a b + c d) + e f; all
+ *              nine entries divided by H'[2][2].  An entry that is then not finite makes the hypothesis inadmissible.
+ *   inlier     u = P_m - P_{i_0}, w = Q_m - Q_{i_0} (exact in double): X = (h00 ux + h01 uy) + h02, Y and Z likewise; inlier iff Z > 0
+ *              and |X - wx Z| <= T Z and |Y - wy Z| <= T Z, T = ctk_fit_motion's T (from tol).
+ *   refit      over the inliers of the best, independent of the order of accumulation, no float atomics: an integer max of |u|, |w|
+ *              gives e, its bit length (>= 1); coordinates are scaled by 2^-e into (-1, 1); the 23 sums of the normal equations of
+ *              x h00 + y h01 + h02 - xX h20 - yX h21 = X and its twin for Y (h22 = 1) are each a sum of llrint(term * 2^44) in int64
+ *              (below 2^59); the 8 x 8 system is solved by the square-root-free Cholesky N = L D L^T in a stated loop order (a
+ *              division is one IEEE operation on every machine; that is why it is not the square-root form), and the normalisation
+ *              and the centring are undone by stated products whose factors are powers of two and P_{i_0} / 16, all exact.  The output
+ *              is (float) of that 3 x 3 matrix in pixels; it is not re-normalised: it is the matrix whose centred form has h22 = 1.
+ *              A pivot <= 0 or not finite, or a solution that is not finite, falls back to the best hypothesis' own four-point
+ *              matrix, moved to pixels the same way (stats[3] = 1).
+ *   outputs    homography float32 [G,F,L,3,3]: (X, Y, Z) = H (x, y, 1) in pixels, the identity where nothing is fitted;  label int8
+ *              [G,F,N_out]: -1 / r / 127 as ctk_fit_objects;  stats int32 [G,F,L,4] = (M_r, inliers, best k or -1, 1 if the refit
+ *              fell back else 0);  box int32 [G,F,L,4] = (min x, min y, max x, max y) of the round's inliers ON FRAME f (with either
+ *              value of inverse), 1/16 pixel, (0, 0, -1, -1) where nothing is fitted.  Every element is written by one plain store.
+ * One launch on `stream`, one workgroup of 256 threads per (group, frame) with the correspondences and their slots in N_out * 18 bytes
+ * of LDS; no atomics, no host synchronisation, capture-safe; writes the four outputs only.  The workspace query answers 0 and
+ * `workspace` may be NULL.  Before any launch: NULL a, hist_coords, homography, label, stats or box, `visible` NULL with hist_vis or
+ * hist_conf NULL, one of anchor_coords / anchor_visible without the other: CTK_E_NULL; every shape ctk_fit_objects refuses but `model`
+ * (this struct has none), `inverse` outside 0..1, `labels` NULL with L != 1: CTK_E_SHAPE; hist_coords or anchor_coords not 8-byte
+ * aligned, homography, stats or box not 4-byte aligned: CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the
+ * struct (it only looks whether an anchor and labels are given).
+ *
+ * ctk_warp_planes.  Picture j of dst (H x W) is picture j of src (Hs x Ws, which may differ) under matrices[j], float32 3 x 3, which
+ * maps an OUTPUT pixel to a SOURCE position; pixel centres are at integers.  src_frame_stride = 0: one source for all pictures.
+ *   coordinate per pixel in double, one rounded operation per step: Xh = (m00 x + m01 y) + m02, Yh and Zh likewise.  The pixel is
+ *              OUTSIDE iff the matrix has a non-finite entry, or !(Zh > 0), or r = 1.0 / Zh, sx = Xh r, sy = Yh r has
+ *              !(|sx| <= 1048576 && |sy| <= 1048576).  Otherwise X = llrint(sx * 256.0), ix = X >> 8, fx = X & 255; the taps and the
+ *              blend are ctk_warp_frames' exactly.  The identity on equal sizes copies bit for bit.
+ *   borders    CTK_WARP_FILL and CTK_WARP_EDGE as before; an outside pixel takes `fill` under both.  CTK_WARP_KEEP = 2 (csrc/
+ *              plane_math.h): a pixel that is outside, or that has a tap outside the source, is NOT WRITTEN -- how a picture is drawn
+ *              into frames in place: dst may be the frames themselves; src, the picture, never overlaps them.  Bytes the rule does
+ *              not write keep their value, pitch padding included.
+ *   pictures   C = 3 or 1, layouts and strides as in struct ctk_warp_field_args: a row holds C W or W elements, a frame H or C H rows.
+ * One launch on `stream` (warp.hip's shape: a 64 x 16 tile per workgroup, the tile's source box staged in 16 KiB of LDS where the four
+ * tile corners bound it and it fits, memory read directly otherwise; under CTK_WARP_KEEP a tile whose box misses the source ends
+ * early, no other tile is culled), no atomics, no host synchronisation, capture-safe; writes dst only..  Before the launch: NULL a,
+ * matrices, src or dst: CTK_E_NULL; F outside 1..65535, H, W, Hs or Ws outside 1..CTK_INGEST_MAX_SIDE, C not 1 or 3, an unknown layout
+ * or border, reserved != 0, a row stride smaller than a row, a frame stride smaller than a frame (but src_frame_stride = 0), a stride
+ * above 2^40 or overlapping byte ranges of src and dst: CTK_E_SHAPE; matrices not 4-byte aligned: CTK_E_ALIGN.
+ *
+ * Known limits.  No split mode for planes, no affine model, no homography path in ctk_smooth_path; no alpha blending and no
+ * anti-aliased edges where a picture is drawn, bilinear taps only (no bicubic); the refit is one algebraic least-squares step (no
+ * Sampson or iterated refit); no lens distortion.                                                                                   */
+typedef struct ctk_fit_planes_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t L;                  /* rounds (planes), 1..16; 1 without labels                          */
+  int32_t min_points;         /* a fit needs this many inliers, 1..8192                            */
+  int32_t inverse;            /* 0: source -> frame f; 1: frame f -> source                        */
+  int32_t K;                  /* hypotheses per round, 1..4096                                     */
+  uint32_t seed;
+  float tol;                  /* inlier bound, pixels (max norm); T = rint(tol * 16) in 1..4096    */
+  float min_base;             /* twice a sample triangle's area is at least min_base^2, pixels     */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const int8_t* labels;       /* [G,N], or NULL: one list of every correspondence (L = 1)          */
+  float* homography;          /* [G,F,L,3,3] */
+  int8_t* label;              /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,L,4] */
+  int32_t* box;               /* [G,F,L,4] */
+} ctk_fit_planes_args;
+int ctk_fit_planes_workspace_bytes(const ctk_fit_planes_args* a, size_t* out_bytes);
+int ctk_fit_planes(const ctk_fit_planes_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+typedef struct ctk_warp_planes_args {
+  int32_t F, H, W;            /* pictures, and the size of a picture of dst in pixels              */
+  int32_t Hs, Ws;             /* the size of a picture of src                                      */
+  int32_t C;                  /* channels: 3, or 1 (a mask)                                        */
+  int32_t layout;             /* CTK_INGEST_HWC / CTK_INGEST_CHW (the same thing for C = 1)        */
+  int32_t border;             /* CTK_WARP_FILL / CTK_WARP_EDGE / CTK_WARP_KEEP                     */
+  int32_t reserved;           /* 0 */
+  uint8_t fill[4];            /* the value of a tap or a pixel outside, per channel                */
+  int64_t src_frame_stride;   /* elements between two pictures of src; 0: one source for all       */
+  int64_t src_row_stride;     /* elements between two pixel rows of src                            */
+  int64_t dst_frame_stride;
+  int64_t dst_row_stride;
+  const float* matrices;      /* [F,3,3], on the device                                            */
+  const uint8_t* src;
+  uint8_t* dst;
+} ctk_warp_planes_args;
+int ctk_warp_planes(const ctk_warp_planes_args* a, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
