@@ -309,6 +309,27 @@ class Planes:
         ]
 
 
+class Epipolar:
+    """Holder of ctk_fit_epipolar_args (include/ctk.h, "fit epipolar"), nested like Planes.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_epipolar_cabi.py.  The constants mirror csrc/epipolar_math.h."""
+
+    SAMPLE, MIN_POINTS = 8, 8
+
+    class Args(C.Structure):
+        """ctk_fit_epipolar_args: history rows (and a mask, or none) -> per frame one fundamental matrix, a label and a squared Sampson
+        distance per point, and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("min_points", C.c_int32), ("K", C.c_int32),
+            ("seed", C.c_uint32),
+            ("tol", C.c_float), ("min_base", C.c_float), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp), ("mask", _fp),
+            ("fundamental", _fp), ("label", _fp), ("error", _fp), ("stats", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -401,6 +422,8 @@ SYMBOLS = {
     "ctk_fit_planes_workspace_bytes": (C.c_int, [_P(Planes.Args), _P(C.c_size_t)]),
     "ctk_fit_planes": (C.c_int, [_P(Planes.Args), _fp, C.c_size_t, _fp]),
     "ctk_warp_planes": (C.c_int, [_P(Planes.WarpArgs), _fp]),
+    "ctk_fit_epipolar_workspace_bytes": (C.c_int, [_P(Epipolar.Args), _P(C.c_size_t)]),
+    "ctk_fit_epipolar": (C.c_int, [_P(Epipolar.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

@@ -1047,6 +1047,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         wait: ops.StreamGroups.planes.  Serves a ring history and the default one alike."""
         return self._running_stream().planes(f0, F, **kw)
 
+    def stream_epipolar(self, f0, F, **kw):
+        """One fundamental matrix per frame [f0, f0 + F) of the running (or just closed) stream, fitted to the correspondences with a
+        source frame, and the points that violate it -- straight from the history and logits on the device, by one launch and without
+        a wait: ops.StreamGroups.epipolar.  Serves a ring history and the default one alike."""
+        return self._running_stream().epipolar(f0, F, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

@@ -256,14 +256,14 @@ def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin:
 
 
 # ------------------------------------------------------------------------------------------
-# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field, fit_objects and fit_planes differ
+# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field, fit_objects, fit_planes and fit_epipolar differ
 # in the history rows they need (`rows`) and in their own struct fields; StreamGroups has the other source, a stream's history.
 # ------------------------------------------------------------------------------------------
 _scratch_cache = {}
 
 
 def _scratch(kind: str, nbytes: int, device) -> torch.Tensor:
-    """The workspace of one kind of reader ("draw", "motion" -- fit_objects and fit_planes share it --, "field"), cached per kind and device like
+    """The workspace of one kind of reader ("draw", "motion" -- fit_objects, fit_planes and fit_epipolar share it --, "field"), cached per kind and device like
     _workspace -- but never in that cache: captured window graphs bake the address of that one in, and a reader must never be the
     reason it moves.  Nor does one kind ever move the buffer of another."""
     key = (kind, device.index if device.index is not None else torch.cuda.current_device())
@@ -1317,6 +1317,84 @@ def corrblock_sample(pyr_nhwc: Sequence[torch.Tensor], targets: torch.Tensor, co
 
 
 # ------------------------------------------------------------------------------------------
+# fit epipolar (csrc/epipolar.hip; include/ctk.h, "fit epipolar")
+# ------------------------------------------------------------------------------------------
+def _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device, who: str) -> None:
+    """The fit and the source form of ctk_fit_epipolar_args; G, N: what a mask and an anchor must match.  `to` or `anchor` replaces
+    the lag; both at once are refused."""
+    min_points, hypotheses, seed = int(min_points), int(hypotheses), int(seed)
+    if not L.Epipolar.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: min_points must lie in {L.Epipolar.MIN_POINTS}..{L.Motion.POINTS_MAX}")
+    if to is not None and anchor is not None:
+        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
+    if not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Motion.HYPOTHESES_MAX} and seed in 0..2^32 - 1")
+    a.min_points, a.K, a.seed = min_points, hypotheses, seed
+    a.tol, a.min_base, a.reserved = float(tol), float(min_base), 0
+    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
+    if to is not None:
+        a.to = int(to)
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif anchor is not None:
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
+    else:
+        a.lag = int(lag)
+        if a.lag < 1:
+            raise ValueError(f"{who}: lag must be >= 1")
+    a.mask = None
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.dtype in (torch.int8, torch.uint8, torch.bool) and mask.device == device and
+                mask.numel() == G * N and mask.shape[-1] == N and mask.is_contiguous()):
+            raise ValueError(f"{who}: mask must be a contiguous int8, uint8 or bool tensor [{N}] or [{G},{N}] on {device}")
+        a.mask = _ptr(mask)
+
+
+def _epipolar_launch(a, device, out, who: str):
+    """Allocates (or checks) the four outputs of ctk_fit_epipolar for the G, F and N_out of `a`, then the launch."""
+    out = _out_tuple(out, [("fundamental", torch.float32, (a.G, a.F, 3, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
+                           ("error", torch.float32, (a.G, a.F, a.N_out)), ("stats", torch.int32, (a.G, a.F, 4))], device, who)
+    a.fundamental, a.label, a.error, a.stats = (_ptr(t_) for t_ in out)
+    ws = _scratch("motion", _query_bytes("ctk_fit_epipolar_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_epipolar(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_epipolar")
+    return out
+
+
+def fit_epipolar(tracks: torch.Tensor, visible: torch.Tensor, *, mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None,
+                 anchor: Optional[FieldAnchor] = None, tol: float = 1.0, hypotheses: int = 512, min_base: float = 16.0, min_points: int = 16,
+                 seed: int = 0, first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """Which points are consistent with ONE camera moving through a scene with depth, and which move by themselves: per frame a robust
+    fundamental matrix fitted to the correspondences between a source frame and the frame, by one launch and without a wait
+    (ctk_fit_epipolar; include/ctk.h and csrc/epipolar_math.h have the rules).  Where fit_motion and fit_planes call the nearer half
+    of a static scene outliers under a translating camera, a static point obeys (X, Y, 1) F (x, y, 1)^T = 0 at any depth.  Works on any
+    result of any predictor here, offline ones included.
+
+    tracks   float32 [T,N,2] or [G,T,N,2] (N <= 8192), positions = tracks * scale; visible bool / uint8 [T,N] or [G,T,N].
+    source   (x, y) is on a source frame and (X, Y) on frame f: f - lag (the default), a fixed frame `to`, or a FieldAnchor; `to` or
+             `anchor` replaces the lag.  A point counts when it is visible on both frames (and at or above first_row: int [N] / [G,N]).
+    mask     int8 / uint8 / bool [N] / [G,N]: nonzero = the point may be sampled and refitted on (say, what is known to be background);
+             None: every point may.  Every point, masked or not, is classified and gets an error.
+    The fit scores `hypotheses` seeded eight-point samples with the Sampson bound `tol` (pixels; every sample point lies at least
+    min_base pixels from the first), refits the best over its inliers and once more over the inliers of that; a best sample with fewer
+    than min_points (>= 8) inliers is no fit.  Rows are all T frames.  Returns (fundamental float32 [G,T,3,3] in pixels, all zero where
+    nothing was fitted; label int8 [G,T,N]: -1 not on both frames, 0 violates the matrix (or nothing was fitted), 1 consistent with it;
+    error float32 [G,T,N]: the squared Sampson distance in pixels^2, -1 without a correspondence or a fit; stats int32 [G,T,4] = (points
+    that may be fitted on, inliers among them, best hypothesis or -1, bit 0 / 1: the first / second refit fell back)); `out`: such a
+    tuple to write into.  F is not unique without parallax (a plane, a camera that only turns or stands): the labels then still mean
+    "consistent with some camera motion"; a point that moves along its own epipolar line is not seen."""
+    who = "fit_epipolar"
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    a = L.Epipolar.Args()
+    if isinstance(mask, torch.Tensor) and mask.dim() == 1 and G > 1:
+        mask = mask.expand(G, -1).contiguous()
+    _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
+    return _epipolar_launch(a, dev, out, who)
+
+
+# ------------------------------------------------------------------------------------------
 # CoTracker2 iteration (cotracker.py:86-173): row kernels + the general update former
 # ------------------------------------------------------------------------------------------
 def sample_features4d(map_hwc: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:
@@ -1673,7 +1751,7 @@ EMPTY_FRAME = L.STREAM_EMPTY_FRAME
 
 
 def history_span(committed: int, T_cap: int, ring: bool, f0: int, F: int, back: int = 0, fwd: int = 0, to: int = -1):
-    """The one range rule of the readers of a stream's history (StreamGroups.draw, motion, field, objects, planes): may a call for frames
+    """The one range rule of the readers of a stream's history (StreamGroups.draw, motion, field, objects, planes, epipolar): may a call for frames
     [f0, f0 + F) be served by a history of T_cap rows, `committed` frames in, a ring or not?  Besides its own frames the call reads
     the `back` frames before each (a trail, a positive lag; those >= 0), the frame `fwd` after each (a negative lag), and the fixed
     frame `to` (>= 0); an anchor reads nothing more.  -> None, or what is wrong with the frames [lo, hi] that are read:
@@ -1801,7 +1879,7 @@ class StreamGroups:
         r0, r1 = f0 % R, f0 % R + (f1 - f0)
         return [slice(r0, r1)] if r1 <= R else [slice(r0, R), slice(0, r1 - R)]
 
-    # -- readers of the history: emit, health, draw, motion, field, objects, planes.  What they share is stated here, once: whom a call reads
+    # -- readers of the history: emit, health, draw, motion, field, objects, planes, epipolar.  What they share is stated here, once: whom a call reads
     # (_reader), which frames it may read (_held: history_span) and the source fields of its args (_bind_history).  A reader itself
     # holds its own options, the back / fwd / to of its span, its own struct fields and its launch. ---------------------------------
     def _reader(self, who: str, N_out, group, first_row, points_max: Optional[int] = None, need_row: bool = False):
@@ -2064,6 +2142,28 @@ class StreamGroups:
         self._held(who, f0, F_, back=a.lag, to=a.to)  # (_planes_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
         self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _planes_launch(a, dev, who)
+
+    def epipolar(self, f0: int, F: int, *, mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None,
+                 anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+                 first_row: Optional[torch.Tensor] = None, tol: float = 1.0, hypotheses: int = 512, min_base: float = 16.0,
+                 min_points: int = 16, seed: int = 0, group: Optional[int] = None, out=None):
+        """One fundamental matrix per frame f0 .. f0 + F - 1 over the first N_out points of every group (or of `group` alone), each
+        frame against a source frame (f - lag, a fixed `to`, or an `anchor`: fit_epipolar has the picture), straight from the stream's
+        own history and logits -- no emit in between --, by the one launch of ctk_fit_epipolar: visibility is emit's sigmoid(vis) *
+        sigmoid(conf) > thresh, positions are history coords * scale, tol and min_base are in those pixels.  mask int8 / uint8 / bool
+        [G,N] (of the groups asked for) on the device, or None: every point may be fitted on.  first_row int32 [G,N] (what emit takes) on
+        the device.  Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError
+        otherwise; an anchor needs no frame but its own copy.  -> (fundamental [G,F,3,3], label [G,F,N_out], error [G,F,N_out], stats
+        [G,F,4]) on the device.  No wait."""
+        who = "epipolar"
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
+        dev = self.queries.device
+        a = L.Epipolar.Args()
+        _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
+        f0, F_ = int(f0), int(F)
+        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_epipolar_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _epipolar_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -784,6 +784,62 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
                                                           min_base=min_base, min_points=min_points, seed=seed, group=objects.anchor.group)
         return hom[0], label[0], stats[0], box[0].to(torch.float32) / 16.0
 
+    @torch.no_grad()
+    def epipolar(self, n=None, first_frame=None, lag=8, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None, group=0):
+        """Not in the reference: which of the N (+ spare_points) user-visible points of query set `group` are consistent with ONE
+        camera moving through a scene with depth between frame f - lag and frame f, on the n frames from first_frame on (default: the
+        frames of the window just tracked, as in camera_motion()) -- one launch of ctk_fit_epipolar (ops.StreamGroups.epipolar on the
+        stream's own history and logits), without a wait.  camera_motion()'s similarity and follow_planes()' homography call the
+        nearer half of a static scene outliers once the camera translates; a fundamental matrix holds for a static point at any
+        depth, so what violates it moves by itself.  Each frame scores `hypotheses` seeded eight-point samples with the Sampson bound
+        `tol` (raw-video pixels; every sample point at least min_base pixels from the first), refits the best over its inliers and
+        once more over the inliers of that; a best sample with fewer than min_points (>= 8) inliers is no fit.  mask: int8 / uint8 /
+        bool [N_model] on the device, nonzero = the point may be sampled and refitted on; every point is classified either way.
+        ValueError when first_frame - lag is negative or has left the ring (history_frames) or the frames lie beyond what has been
+        tracked.  Returns, on the device: fundamental float32 [n,3,3] in raw-video pixels: (X, Y, 1) F (x, y, 1)^T = 0 for a static
+        point at (x, y) on frame f - lag and (X, Y) on frame f, all zero where there is no fit; label int8 [n,N]: -1 not on both frames,
+        0 violates the matrix (or there is no fit), 1 consistent with it; error float32 [n,N]: the squared Sampson distance in
+        pixels^2, -1 without a correspondence or a fit; stats int32 [n,4] = (points that may be fitted on, inliers among them, best
+        hypothesis or -1, bit 0 / 1: the first / second refit fell back).  Without parallax -- a planar scene, a camera that only
+        turns or stands -- the matrix is not unique and the labels mean "consistent with some camera motion": compare with
+        follow_planes().  A point that moves along its own epipolar line is not seen."""
+        who = "epipolar"
+        gs, scale = self._running(who)
+        group = int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        fund, label, error, stats = self.model.stream_epipolar(first_frame, n, mask=None if mask is None else mask[None], lag=lag,
+                                                               N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(),
+                                                               tol=tol, hypotheses=hypotheses, min_base=min_base, min_points=min_points,
+                                                               seed=seed, group=group)
+        return fund[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
+    def split_scene(self, frame=None, lag=8, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None):
+        """Not in the reference: the N (+ spare_points) user-visible points of query set `group` split into the static scene and what
+        moves by itself between frame - lag and `frame` (default: the newest tracked one), under a camera that may translate through
+        a scene with depth -- where split_objects() cuts the static scene into depth layers and calls them objects.  One launch of
+        ctk_fit_epipolar (epipolar() has the rules and the limits; tol, hypotheses, min_base, min_points, seed and mask are its),
+        elementwise torch and one pin(frame), without a wait.  ValueError when frame - lag is negative or has left the ring
+        (history_frames) or the frame has not been tracked.  Returns an ops.ObjectSet with objects = 2: labels int8 [N_model] on the
+        device (0 = the static scene, 1 = moves independently, -1 = not seen on both frames, or no user-visible point; all
+        correspondences are 1 where no matrix was fitted) and the anchor pinned on `frame`; follow() and follow_planes() take it
+        unchanged."""
+        from . import ops
+        who = "split_scene"
+        gs, scale = self._running(who)
+        frame, lag, group = gs.committed - 1 if frame is None else int(frame), int(lag), int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        if not 0 <= frame < gs.committed or lag < 1 or frame - lag < 0:
+            raise ValueError(f"{who}: frames {frame - lag} and {frame} must both have been tracked ({gs.committed} frames), lag >= 1")
+        label = self.epipolar(1, frame, lag=lag, tol=tol, hypotheses=hypotheses, min_base=min_base, min_points=min_points, seed=seed,
+                              mask=mask, group=group)[1][0]
+        labels = torch.full((gs.N,), -1, dtype=torch.int8, device=label.device)
+        labels[:self.N] = torch.where(label < 0, label, 1 - label)
+        return ops.ObjectSet(labels, self.pin(frame, group), 2)
+
     def _plane_index(self, objects, index, who):
         from . import ops
         if not isinstance(objects, ops.ObjectSet):

@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_epipolar and ctk_fit_epipolar_workspace_bytes on the
+ *       new struct ctk_fit_epipolar_args: per frame, one robust fundamental matrix (eight-point hypotheses by a pivoted elimination, a
+ *       division-free Sampson test, two order-independent fixed-point refits) fitted to the correspondences of two frames, with a
+ *       label and a squared Sampson distance per point: what moves by itself against what only shows parallax
+ *       (csrc/epipolar_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_planes and ctk_fit_planes_workspace_bytes on the
  *       new struct ctk_fit_planes_args: per frame, up to 16 robust homography fits (four-point hypotheses, integer admissibility, an
  *       order-independent fixed-point refit) over the regions a caller labelled, in the frame of ctk_fit_objects' labels mode; and
@@ -1056,6 +1061,96 @@ typedef struct ctk_warp_planes_args {
   uint8_t* dst;
 } ctk_warp_planes_args;
 int ctk_warp_planes(const ctk_warp_planes_args* a, void* stream);
+
+/* ---- fit epipolar: one fundamental matrix per frame, and the points that do not obey it -------------------------------------------------
+ * For a caller whose tracks are on the device and whose camera TRANSLATES through a scene with depth: near and far points then move
+ * differently in the picture, a similarity (ctk_fit_motion, ctk_fit_objects) or a homography (ctk_fit_planes) calls the nearer half of
+ * the static scene outliers, and nothing tells a point that moves by itself from one that only shows parallax.  ctk_fit_epipolar fits
+ * ONE fundamental matrix F per group g and frame f in [f0, f0 + F) robustly to the correspondences between a source frame and frame f:
+ * every static point satisfies (Q, 1)^T F (P, 1) = 0 at any depth (P on the source frame, Q on frame f), a point that moves on its own
+ * generally does not.  The rules are stated once in csrc/epipolar_math.h.
+ *
+ * The frame of the call is ctk_fit_planes' without labels; everything not named here is ctk_fit_motion's and ctk_fit_planes' bit for
+ * bit: positions (1/16 pixel), the pair rule with its three source forms, first_row, `visible` or the logits with thresh, N_out <=
+ * 8192, mix, T from tol, the key ("most inliers, then the lowest k"), ctk_plane_solve.  There are no lists and no rounds by label.
+ *   fit list   `mask` int8 [G,N] given: a correspondence whose byte is nonzero may be sampled and refitted on; NULL: every
+ *              correspondence may.  M = how many.  Every correspondence, masked or not, is classified and gets an error.
+ *   sample     hypothesis k over M >= 8: h_t = mix(seed ^ mix(f * 0x9e3779b9 + 8k + t)), t = 0..7; i_t = h_t % (M - t), then bumped past
+ *              the earlier indices taken in ascending order: eight distinct indices; f is the absolute frame number.
+ *   admissible integers only.  Both frames are centred on the anchor pair (P_{i_0}, Q_{i_0}); each of the other seven offsets must have a
+ *              squared length >= max(base2', 1) on both frames, base2' = b * b with b = rint(min_base * 16): every sample point lies at
+ *              least min_base pixels from the anchor (ctk_fit_motion's base2; a squared length in 1/16 pixel).
+ *   matrix     in double, one rounded operation per step, no contraction, no square root.  The anchor pair is a correspondence at both
+ *              origins, so F[2][2] = 0 exactly.  e = the bit length of the largest |component| of the seven offset pairs (>= 1);
+ *              offsets are scaled by 2^-e into (-1, 1), exactly.  A sample point gives the row (X x, X y, X, Y x, Y y, Y, x, y) for the
+ *              entries (F00 .. F21); the null vector of the 7 x 8 system comes from Gaussian elimination with complete pivoting (the
+ *              largest |entry| of the remaining block; ties: the lowest row, then the lowest column), back substitution with the free
+ *              unknown 1 in one stated loop order, the permutation undone.  A pivot that is 0 or not finite, or a result that is
+ *              not finite, makes the hypothesis inadmissible.  The entries are divided by the one of largest magnitude, j* (the
+ *              lowest index on ties), which so becomes exactly 1.
+ *   inlier     the Sampson test without a division or a root, on the scaled offsets u, w: a = F (u, 1), b = F^T (w, 1), r = (w, 1) . a,
+ *              g = ((a0 a0 + a1 a1) + b0 b0) + b1 b1, Ts = T 2^-e: inlier iff g > 0 and r r <= (Ts Ts) g.
+ *   refit      over the inliers among the fit list, independent of the order of accumulation, no float atomics: e' = the bit length of
+ *              the inliers' integer reach; a = (X x, X y, X, Y x, Y y, Y, x, y, 1) in the scale e'; the 45 distinct sums of a a^T are
+ *              each a sum of llrint(term * 2^44) in int64 (below 2^58); row and column j* are deleted and the 8 x 8 system N h =
+ *              -column j* is solved by ctk_fit_planes' square-root-free L D L^T; F_{j*} = 1.  If it fails the hypothesis' own matrix
+ *              stays, moved to the scale e' by exact powers of two (stats[3] bit 0).
+ *   second     every entry of the fit list is classified again under the refitted matrix, and the refit is run once more over those
+ *   round      inliers with j* = its entry of largest magnitude; if that fails the first refit's matrix stays (stats[3] bit 1).  This
+ *              round is what keeps a noisy minimal sample from dropping static points.
+ *   outputs    fundamental float32 [G,F,3,3] in pixels: (X, Y, 1) F (x, y, 1)^T = 0 for a static point at (x, y) on the source frame
+ *              and (X, Y) on frame f: S_Q^T F S_P by stated products with powers of two and the anchor / 16, all exact but the two
+ *              sums per entry of the last column and row; (float) of that, not renormalised.  label int8 [G,F,N_out]: -1 not on
+ *              both frames, 0 violates the matrix, 1 consistent with it (the same test under the final matrix, for masked and unmasked
+ *              correspondences alike).  error float32 [G,F,N_out]: the squared Sampson distance in pixels^2, (float)(((r r) / g)
+ *              2^(2e'-8)), one division and one exact scaling; +inf (and label 0) where !(g > 0); -1 where there is no
+ *              correspondence.  stats int32 [G,F,4] = (M, inliers among the fit list under the final matrix, best k or -1, the
+ *              fall-back bits).  Every element is written by one plain store.
+ *   no fit     M < 8, no admissible hypothesis, or fewer than min_points inliers of the best hypothesis: fundamental is all zero,
+ *              every correspondence has label 0 and error -1, stats = (M, 0, -1, 0).
+ * One launch on `stream`, one workgroup of 256 threads per (group, frame) with the correspondences and their slots in N_out * 18 bytes
+ * of LDS (a lane per hypothesis walks the list by LDS broadcast; K above 256 takes further passes; thread 0 solves); no atomics, no
+ * host synchronisation, capture-safe; writes the four outputs only.  The workspace query answers 0 and `workspace` may be NULL.  Before
+ * any launch: NULL a, hist_coords, fundamental, label, error or stats, `visible` NULL with hist_vis or hist_conf NULL, one of
+ * anchor_coords / anchor_visible without the other: CTK_E_NULL; every shape ctk_fit_planes refuses but L and inverse (this struct has
+ * neither), min_points outside 8..8192: CTK_E_SHAPE; hist_coords or anchor_coords not 8-byte aligned, fundamental, error or stats not
+ * 4-byte aligned: CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor
+ * is given).
+ *
+ * Known limits.  F is not unique without parallax -- a planar scene, a camera that only rotates, a static camera: the labels then
+ * still mean "consistent with SOME camera motion", and a caller tells by comparing with ctk_fit_planes' inliers.  A point that moves
+ * along its own epipolar line is not seen by any F.  No rank-2 enforcement; one algebraic refit per round (no iterated or Sampson-
+ * weighted refit); no lens distortion; no essential matrix and no pose decomposition.                                                  */
+typedef struct ctk_fit_epipolar_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t min_points;         /* a fit needs this many inliers of its best hypothesis, 8..8192     */
+  int32_t K;                  /* hypotheses, 1..4096                                               */
+  uint32_t seed;
+  float tol;                  /* Sampson bound, pixels; T = rint(tol * 16) in 1..4096              */
+  float min_base;             /* a sample point lies at least this far from the anchor, pixels     */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const int8_t* mask;         /* [G,N], or NULL: every correspondence may be fitted on             */
+  float* fundamental;         /* [G,F,3,3] */
+  int8_t* label;              /* [G,F,N_out] */
+  float* error;               /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_fit_epipolar_args;
+int ctk_fit_epipolar_workspace_bytes(const ctk_fit_epipolar_args* a, size_t* out_bytes);
+int ctk_fit_epipolar(const ctk_fit_epipolar_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
