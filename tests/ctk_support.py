@@ -113,6 +113,61 @@ def attention_raw(q, q_ld, q_bs, q_is, k, v, kv_ld, kv_bs, kv_is, out, o_ld, o_b
     return L.load().ctk_attention_ex(C.byref(a), None if b2 is None else C.byref(b2), stream)
 
 
+# ---- the correlation samplers as the C-ABI sees them (tests/test_gpu_corr_matrix.py) ---------------------------------------------------------
+CORR_K, CORR_LD = 2401, 2432  # 49 x 49 volume columns and the row length (K padding of corr_mlp.fc1), in 4-byte units
+
+
+def nan_framed(x, pad=8192):
+    """A copy of x (f32) in the middle of a NaN-filled allocation on the GPU, `pad` elements on either side (a multiple of 4: the
+    view keeps the 16-byte alignment of the allocation) -> the contiguous view.  A read that leaves the operand reads NaN."""
+    assert pad % 4 == 0 and x.dtype == torch.float32
+    flat = torch.full((x.numel() + 2 * pad,), float("nan"), device=dev())
+    view = flat[pad:pad + x.numel()].view(x.shape)
+    view.copy_(x)
+    return view
+
+
+def corr_volume_raw(win, sh, canary, guard=4):
+    """ctk_corr_volume (sh=False) or ctk_corr_volume_sh of a whole window into caller-owned memory (ops.corr_volume* allocate their
+    own): [guard rows | 4 levels x N*S rows | guard rows] x CORR_LD 4-byte units, pre-filled with `canary`.  The entry points fix
+    the level stride at N*S rows, so guard rows lie in front of level 0 and behind level 3 only.
+    -> (the volume f32 [4][N*S][CORR_LD] or SH f16 [4][N*S][76][2][32], whether every guard row kept its bits)."""
+    from cotracker_amd import _lib as L
+    from cotracker_amd import ops
+    rows = L.LEVELS * win.N * win.S
+    buf = torch.full((rows + 2 * guard, CORR_LD), canary, dtype=torch.int32, device=win.device)
+    body = buf[guard:guard + rows]
+    stream = torch.cuda.current_stream().cuda_stream
+    if sh:
+        ws = ops._workspace(ops._query_bytes("ctk_corr_volume_sh_workspace_bytes", C.byref(win.args)), win.device)
+        L.check(L.load().ctk_corr_volume_sh(C.byref(win.args), body.data_ptr(), ws.data_ptr(), ws.numel(), stream), "ctk_corr_volume_sh")
+        vol = body.view(torch.float16).view(L.LEVELS, win.N * win.S, CORR_LD // 32, 2, 32)
+    else:
+        L.check(L.load().ctk_corr_volume(C.byref(win.args), body.data_ptr(), stream), "ctk_corr_volume")
+        vol = body.view(torch.float32).view(L.LEVELS, win.N * win.S, CORR_LD)
+    intact = bool((buf[:guard] == canary).all()) and bool((buf[guard + rows:] == canary).all())
+    return vol, intact
+
+
+def sampler_taps(coords, sizes):
+    """The tap tables of a window on the host, from the numpy restatement of the reference's float32 coordinate arithmetic
+    (oracle/cotracker_oracle.py: sampler_indices_weights): coords [S,N,2] float32 in level-0 units, sizes [(H, W)] per level ->
+    per level a dict of [S,N,7] arrays for either axis a in "xy": a+"0" the floor index, a+"1" its clamped upper neighbour,
+    "w"+a+"0" / "w"+a+"1" their float32 weights."""
+    from oracle import cotracker_oracle as O
+    f32 = np.float32
+    out = []
+    d = np.arange(-3, 4).astype(f32)
+    for l, (H, W) in enumerate(sizes):
+        cl = (np.asarray(coords, f32) * f32(1.0 / 2 ** l)).astype(f32)  # coords / 2**l: exact
+        tab = {}
+        for k, (a, size) in enumerate((("x", W), ("y", H))):
+            i0, w0, w1 = O.sampler_indices_weights((cl[..., k:k + 1] + d).astype(f32), size)
+            tab[a + "0"], tab[a + "1"], tab["w" + a + "0"], tab["w" + a + "1"] = i0, np.minimum(i0 + 1, size - 1), w0, w1
+        out.append(tab)
+    return out
+
+
 def recorded(call):
     """-> (call(), {recorder row name: launches}) of the library launches `call` made.  The recorder is one per process."""
     from cotracker_amd import ops
