@@ -226,12 +226,14 @@ __device__ __forceinline__ int oimg_pos(const bool odd_head, const int d0) {
 }
 
 // RowPtr: int row (0..31) -> _Float16* start of that query's SH output row, or nullptr when the slot is padding
-template <class RowPtr>
+// IMG_PITCH: bytes between the image's rows -- OIMG_PITCH, or any pitch of 52 dwords modulo 64 (the same banks) when the image
+// lies inside a larger one (attention_time_rows_kernel)
+template <int IMG_PITCH = OIMG_PITCH, class RowPtr>
 __device__ __forceinline__ void attn_store_sh_head(const f32x16 (&oacc)[2], const float inv, unsigned char* img /* this wave's */,
                                                    const int lane, const int head, RowPtr row_ptr) {
   const int r32 = lane & 31, half = lane >> 5;
   const bool odd = head & 1;
-  unsigned char* wr = img + r32 * OIMG_PITCH;
+  unsigned char* wr = img + r32 * IMG_PITCH;
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -252,7 +254,7 @@ __device__ __forceinline__ void attn_store_sh_head(const f32x16 (&oacc)[2], cons
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     const int idx = k * 64 + lane, row = idx / 12, c = idx - row * 12;
-    const f16x8 v = *reinterpret_cast<const f16x8*>(img + row * OIMG_PITCH + c * 16);
+    const f16x8 v = *reinterpret_cast<const f16x8*>(img + row * IMG_PITCH + c * 16);
     _Float16* base = row_ptr(row);
     const int off = c < 8 ? line_full * 128 + c * 16 : line_part * 128 + part_off + (c < 10 ? (c - 8) * 16 : 64 + (c - 10) * 16);
     if (base) *reinterpret_cast<f16x8*>(reinterpret_cast<unsigned char*>(base) + off) = v;
@@ -947,6 +949,174 @@ __global__ __launch_bounds__(256, 2) void attention_time16_kernel(AttnP p, long 
   }
 }
 
+// ---- time attention, S == 16, q | k | v one row-contiguous block (run_transformer's qkv): one WORKGROUP per track pair ------
+// attention_time16_kernel fetches, per wave, the 192-byte head slices of 32 token rows: one and a half cache lines each, every
+// second line shared with the neighbouring head's wave (usually in another workgroup), ~11 lines per load instruction.  But the 32
+// rows of a track pair are ONE block of 32 x 1152 floats = 147 456 contiguous bytes when k == q + 384, v == q + 768, the leading
+// dimension is 1152, the frames of a track are consecutive rows and the tracks follow one another.  Here a 512-thread workgroup
+// (one wave per head) owns the pair and reads that block as 18 loads of 16 bytes per lane, consecutive lanes consecutive 16
+// bytes: every wave instruction covers 1 KiB = 8 whole lines, and every line is requested once, by one CU.  The workgroups (at
+// most one per CU) walk over the pairs, and the raw block of the NEXT pair is in flight (72 registers per lane, as in
+// attention_time16_kernel) while the current one is multiplied.
+// The block goes through LDS in the row order it arrives in: [32 token slots][TR_PITCH floats]; TR_PITCH = 1152 + 52 is VT_PITCH
+// modulo 64, so the fragment reads of a wave (its head's q and k rows, its V^T columns) meet the banks exactly as they meet those
+// of attention_time16_kernel's wave-private image, and a group of 8 lanes of a 16-byte write never crosses a row (288 chunks per
+// row).  3 x 48 KiB + padding = 154 112 bytes: one workgroup per CU.  The SH output image of a wave (attn_store_sh_head, 192
+// bytes per row) lies on the wave's OWN q slice -- 192 bytes per row, read by nobody else and consumed before the MFMAs -- so it
+// needs no barrier of its own.  TWO workgroup barriers per pair: block written -> fragments read, and fragments read / image
+// drained -> next block written.
+// From the fragments on the arithmetic is attention_time16_kernel's, instruction for instruction: same bits out.
+constexpr int TR_LD = 3 * CTK_HID;                   // 1152 floats per token row
+constexpr int TR_PITCH = TR_LD + VT_PITCH;           // 1204
+constexpr int TR_CHUNKS = TR_LD / 4;                 // 288 sixteen-byte chunks per row
+constexpr int TR_LOADS = 32 * TR_CHUNKS / 512;       // 18 per lane; loads 0..8 are the first track of the pair, 9..17 the second
+static_assert(TR_PITCH % 64 == VT_PITCH && (TR_PITCH * 4) % 16 == 0 && 32 * TR_CHUNKS == 512 * TR_LOADS && TR_CHUNKS % 8 == 0, "pair block layout");
+static_assert(16 * TR_CHUNKS == 512 * (TR_LOADS / 2), "a track is a whole number of workgroup loads");
+static_assert(32 * TR_PITCH * 4 <= 160 * 1024, "one pair per CU");
+constexpr int TR_MIN_ROUNDS = 8;                     // pairs per CU from which ctk_attention_ex picks this kernel on its own
+
+__global__ __launch_bounds__(512, 1) void attention_time_rows_kernel(AttnP p, int npairs) {
+  __shared__ __attribute__((aligned(16))) float blk[32 * TR_PITCH];
+  const int tid = threadIdx.x, head = tid >> 6, lane = tid & 63, r32 = lane & 31, half = lane >> 5;
+  const int vd0 = r32, vd1 = min(32 + r32, HD - 1);
+  const int rb = r32 >> 4, ri = r32 & 15;
+  int pair = blockIdx.x;
+  if (pair >= npairs) return;  // (workgroup-uniform; the host launches no such workgroup)
+  unsigned char* oimg = reinterpret_cast<unsigned char*>(blk + head * HD);  // rows TR_PITCH * 4 bytes apart
+  const float* qrow = blk + r32 * TR_PITCH + head * HD + half * 8;
+  const float* vcol = blk + 2 * CTK_HID + head * HD;
+
+  f32x4 raw[TR_LOADS];
+  // pair pr -> registers.  The second track of a half-empty last pair does not exist: its loads fetch the first track again, as
+  // attention_time16_kernel's clamped rows do (finite operands for masked slots whose probabilities are exactly 0).
+  // Non-temporal: every byte is read once (tools/attention_rows_probe.cpp: the whole-block stream runs at 6.3 TB/s with the hint
+  // and at 5.3 - 5.5 without; the head-slice pattern gains nothing from it).
+  auto load = [&](const int pr) {
+    const float* src = p.q + (long)pr * (32 * TR_LD) + tid * 4;
+    const int second = (2 * pr + 1 < p.nbatch) ? (TR_LOADS / 2) * 512 * 4 : 0;  // floats from load i to load i + 9
+#pragma unroll
+    for (int i = 0; i < TR_LOADS / 2; ++i) {
+      raw[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + i * 512 * 4));
+      raw[i + TR_LOADS / 2] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src + i * 512 * 4 + second));
+    }
+  };
+
+  load(pair);
+  while (true) {
+    const int b0 = 2 * pair;
+    {  // registers -> block image, in arrival order: chunk c = 512 i + tid is chunk c % 288 of token slot c / 288
+#pragma unroll
+      for (int i = 0; i < TR_LOADS / 2; ++i) {
+        const int c = 512 * i + tid, row = c / TR_CHUNKS, cc = c - row * TR_CHUNKS;
+        float* dst = blk + row * TR_PITCH + cc * 4;
+        *reinterpret_cast<f32x4*>(dst) = raw[i];
+        *reinterpret_cast<f32x4*>(dst + 16 * TR_PITCH) = raw[i + TR_LOADS / 2];
+      }
+    }
+    const int next = pair + (int)gridDim.x;
+    const bool more = next < npairs;  // workgroup-uniform
+    if (more) load(next);  // in flight behind the arithmetic below
+    __syncthreads();  // barrier 1 of 2: the block is written
+
+    f16x8 qh[3], ql[3], kh[3], kl[3], vh[2][2], vl[2][2];
+    {
+      f32x4 f[6];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        f[2 * j] = *reinterpret_cast<const f32x4*>(qrow + 16 * j);
+        f[2 * j + 1] = *reinterpret_cast<const f32x4*>(qrow + 16 * j + 4);
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) ctk_split8(f[2 * j] * p.scale2, f[2 * j + 1] * p.scale2, qh[j], ql[j]);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        f[2 * j] = *reinterpret_cast<const f32x4*>(qrow + CTK_HID + 16 * j);
+        f[2 * j + 1] = *reinterpret_cast<const f32x4*>(qrow + CTK_HID + 16 * j + 4);
+      }
+#pragma unroll
+      for (int j = 0; j < 3; ++j) ctk_split8(f[2 * j], f[2 * j + 1], kh[j], kl[j]);
+    }
+    {  // V^T fragments: element (k-step s, e) of lane (dim, half) = V[slot 16 s + 8 (e >> 2) + 4 half + (e & 3)][dim]
+      float v0[16], v1[16];
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int slot = 16 * s + 8 * (e >> 2) + 4 * half + (e & 3);
+          v0[8 * s + e] = vcol[slot * TR_PITCH + vd0];
+          v1[8 * s + e] = vcol[slot * TR_PITCH + vd1];
+        }
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        ctk_split8(f32x4{v0[8 * s], v0[8 * s + 1], v0[8 * s + 2], v0[8 * s + 3]}, f32x4{v0[8 * s + 4], v0[8 * s + 5], v0[8 * s + 6], v0[8 * s + 7]},
+                   vh[0][s], vl[0][s]);
+        ctk_split8(f32x4{v1[8 * s], v1[8 * s + 1], v1[8 * s + 2], v1[8 * s + 3]}, f32x4{v1[8 * s + 4], v1[8 * s + 5], v1[8 * s + 6], v1[8 * s + 7]},
+                   vh[1][s], vl[1][s]);
+      }
+    }
+
+    const bool qvalid = b0 + rb < p.nbatch;
+    f32x16 sacc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sacc[e] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sacc = ctk_mma3(kh[j], kl[j], qh[j], ql[j], sacc);
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int slot = 8 * (e >> 2) + 4 * half + (e & 3);
+      const bool ok = ((slot >> 4) == rb) && (b0 + (slot >> 4) < p.nbatch);
+      sacc[e] = ok ? sacc[e] : -INFINITY;
+      tmax = fmaxf(tmax, sacc[e]);
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mnew = (tmax == -INFINITY) ? 0.0f : tmax;  // padding slot: all probabilities 0, never stored
+    float l = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float pv = __builtin_amdgcn_exp2f(sacc[e] - mnew);
+      l += pv;
+      sacc[e] = pv * PSCALE;
+    }
+    f32x16 oacc[2];
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) oacc[dt][e] = 0.0f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      f16x8 ph, pl;
+      ctk_split8(f32x4{sacc[8 * s], sacc[8 * s + 1], sacc[8 * s + 2], sacc[8 * s + 3]},
+                 f32x4{sacc[8 * s + 4], sacc[8 * s + 5], sacc[8 * s + 6], sacc[8 * s + 7]}, ph, pl);
+      oacc[0] = ctk_mma3(vh[0][s], vl[0][s], ph, pl, oacc[0]);
+      oacc[1] = ctk_mma3(vh[1][s], vl[1][s], ph, pl, oacc[1]);
+    }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / (l * PSCALE);
+    if (p.o_split) {
+      attn_store_sh_head<TR_PITCH * 4>(oacc, inv, oimg, lane, head, [&](int row) -> _Float16* {
+        const int ob = b0 + (row >> 4), oi = row & 15;
+        return ob < p.nbatch ? reinterpret_cast<_Float16*>(p.out) + ((long)ob * p.o_bs + (long)oi * p.o_is) * p.o_ld : nullptr;
+      });
+    } else if (qvalid) {
+      const long orow = ((long)(b0 + rb) * p.o_bs + (long)ri * p.o_is) * p.o_ld;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int d = dt * 32 + q * 8 + half * 4;
+          if (d < HD) {
+            const f32x4 t = {oacc[dt][4 * q] * inv, oacc[dt][4 * q + 1] * inv, oacc[dt][4 * q + 2] * inv, oacc[dt][4 * q + 3] * inv};
+            *reinterpret_cast<f32x4*>(p.out + orow + head * HD + d) = t;
+          }
+        }
+    }
+    if (!more) break;
+    pair = next;
+    __syncthreads();  // barrier 2 of 2: every wave has read its fragments and drained its output image
+  }
+}
+
 __global__ void attention_merge_kernel(AttnP p) {
   // one thread per (batch, head, query, dim)
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -981,6 +1151,15 @@ __global__ void attention_merge_kernel(AttnP p) {
 
 // CTK_OPT_ATTENTION_VALU (include/ctk.h): 0 = MFMA kernels for the 64-key, 64-query and square shapes | 1: the VALU kernel everywhere.
 int attn_backend() { return ctk_opt(CTK_OPT_ATTENTION_VALU); }
+
+int attn_num_cus() {
+  static const int n = [] {
+    int dev = 0, cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    return cu;
+  }();
+  return n;
+}
 
 }  // namespace
 
@@ -1055,8 +1234,22 @@ extern "C" int ctk_attention_ex(const ctk_attn_args* a, const ctk_attn_batch2* b
     p.qtiles = p.bpw == 2 ? 1 : (a->n1 + 31) / 32;
     const long njobs = (long)((a->nbatch + p.bpw - 1) / p.bpw) * p.qtiles;
     CtkProfScope ps(a->q_is == 1 ? "attention_time" : "attention_vself", flops, bytes, s);
-    const bool persistent = ctk_opt(CTK_OPT_ATTENTION_TIME_PERSISTENT) != 0;  // 0 = the non-persistent kernel (bit-identical)
-    if (p.bpw == 2 && !p.kmask && !p.qmask && persistent) {
+    // CTK_OPT_ATTENTION_TIME_PERSISTENT: 0 = the non-persistent kernel | 1 = persistent: one workgroup per track pair where q | k | v
+    // are one row-contiguous block and there are at least TR_MIN_ROUNDS pairs per CU, else one wave per (pair, head) | 2 = one wave
+    // per (pair, head) everywhere | 3 = as 1 without the pair count (tests).  All bit-identical.
+    // The count: one workgroup per CU walks in whole rounds and its operands must come from HBM for whole blocks to pay -- alone on
+    // an MI355X the two kernels tie at 1750 pairs (6.8 rounds, 258 MB of operands); above, the block kernel wins (2250 pairs: -10 %,
+    // 3232: -16..19 %), below the wave kernel does (1250 pairs: +4 %, 600: +8 %; profiles/attention_time_rows_ab.json).
+    const int tmode = ctk_opt(CTK_OPT_ATTENTION_TIME_PERSISTENT);
+    const bool persistent = tmode != 0;
+    const int cus = attn_num_cus();
+    const bool pair_block = a->n1 == 16 && a->k == a->q + CTK_HID && a->v == a->q + 2 * CTK_HID && a->q_ld == TR_LD && a->kv_ld == TR_LD &&
+                            a->q_is == 1 && a->kv_is == 1 && a->q_bs == a->n1 && a->kv_bs == a->n1;
+    const bool rows_kernel = pair_block && (tmode == 3 || (tmode == 1 && njobs >= (long)TR_MIN_ROUNDS * cus));
+    if (p.bpw == 2 && !p.kmask && !p.qmask && rows_kernel) {
+      // persistent workgroups, at most one per CU, each walks over ~npairs / CUs track pairs
+      hipLaunchKernelGGL(attention_time_rows_kernel, dim3((unsigned)(njobs < cus ? njobs : cus)), dim3(512), 0, s, p, (int)njobs);
+    } else if (p.bpw == 2 && !p.kmask && !p.qmask && persistent) {
       // persistent waves: 2 workgroups per CU, each wave walks over ~njobs*8/2048 (batch pair, head) jobs
       const long total = njobs * CTK_HEADS;
       const unsigned blocks = (unsigned)((total + 3) / 4 < 512 ? (total + 3) / 4 : 512);

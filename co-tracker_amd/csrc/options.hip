@@ -23,7 +23,7 @@ constexpr OptSpec kSpec[CTK_OPT_COUNT] = {
     /* CTK_OPT_CORR_VERSION              */ {"CTK_CORR", 3, 1, 3, 0},
     /* CTK_OPT_CORR_MAP                  */ {"CTK_CORR_MAP", 3, 0, 4, 0},
     /* CTK_OPT_ATTENTION_VALU            */ {"CTK_ATTN", 0, 0, 1, 0},
-    /* CTK_OPT_ATTENTION_TIME_PERSISTENT */ {"CTK_ATTN_TIME", 1, 0, 1, 0},
+    /* CTK_OPT_ATTENTION_TIME_PERSISTENT */ {"CTK_ATTN_TIME", 1, 0, 3, 0},
     /* CTK_OPT_OVERLAP                   */ {"CTK_OVERLAP", 0, 0, 3, 3},
 };
 

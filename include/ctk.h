@@ -1460,7 +1460,12 @@ int ctk_profile_enable(int on);
  *   CTK_OPT_CORR_MAP                   CTK_CORR_MAP       3        workgroup -> (point, level) dealing of version 3: 3 = level-major (neighbouring
  *                                                                  points of a grid query run together), 0 = point-major, 1 / 2 / 4 = pairs / blocks
  *   CTK_OPT_ATTENTION_VALU             CTK_ATTN           0        1 = every attention shape on the VALU kernel (the fallback of the MFMA kernels)
- *   CTK_OPT_ATTENTION_TIME_PERSISTENT  CTK_ATTN_TIME      1        0 = the non-persistent time-attention kernel (bit-identical)
+ *   CTK_OPT_ATTENTION_TIME_PERSISTENT  CTK_ATTN_TIME      1        time attention over <= 16 frames without masks: 1 = persistent; where q | k | v of
+ *                                                                  16-frame tracks are one row-contiguous block of leading dimension 1152 (the
+ *                                                                  update transformer's layout) and there are at least 8 track pairs per CU, one
+ *                                                                  workgroup per track pair reads whole blocks, else one wave per (pair, head);
+ *                                                                  2 = one wave per (pair, head) everywhere; 3 = as 1 at any number of pairs;
+ *                                                                  0 = the non-persistent kernel (all four bit-identical)
  *   CTK_OPT_OVERLAP                    CTK_OVERLAP        0        use of ctk_window_args.aux_stream: bit 0 = sampler of one point piece beside
  *                                                                  corr_mlp of the previous one, bit 1 = the points<-virtual query projection
  *                                                                  beside the virtual-track chain (bit-identical; measured <= 0.2 % either way) */

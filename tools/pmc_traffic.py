@@ -54,6 +54,7 @@ NAME_MAP = [
     (r"corr_volume_sh_kernel", "corr_volume_sh"),
     (r"corr_volume_kernel", "corr_volume"),
     (r"attention_merge_kernel", "attention_merge"),
+    (r"attention_time_rows_kernel", "attention_time"),  # (the default where q | k | v are one row-contiguous block)
     (r"attention_time16_kernel", "attention_time"),
     (r"attention_self_kernel", "attention_time"),
     (r"attention_kv64_kernel", "attention_p2v"),   # also the (small) virtual self attention launches
