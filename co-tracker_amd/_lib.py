@@ -330,6 +330,27 @@ class Epipolar:
         ]
 
 
+class Pose:
+    """Holder of ctk_fit_pose_args (include/ctk.h, "fit pose"), nested like Epipolar.Args and for the same reason; its layout is checked
+    against the compiler by tests/test_pose_cabi.py.  The constants mirror csrc/pose_math.h."""
+
+    MIN_POINTS, SUMS, ROUNDS = 8, 28, 2
+
+    class Args(C.Structure):
+        """ctk_fit_pose_args: history rows, four intrinsics and what ctk_fit_epipolar wrote (fundamental, label) -> per frame a pose
+        (R | t), two depths per point, and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("min_points", C.c_int32),
+            ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp), ("mask", _fp),
+            ("fundamental", _fp), ("label", _fp), ("pose", _fp), ("depth", _fp), ("stats", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -424,6 +445,8 @@ SYMBOLS = {
     "ctk_warp_planes": (C.c_int, [_P(Planes.WarpArgs), _fp]),
     "ctk_fit_epipolar_workspace_bytes": (C.c_int, [_P(Epipolar.Args), _P(C.c_size_t)]),
     "ctk_fit_epipolar": (C.c_int, [_P(Epipolar.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_pose_workspace_bytes": (C.c_int, [_P(Pose.Args), _P(C.c_size_t)]),
+    "ctk_fit_pose": (C.c_int, [_P(Pose.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

@@ -1053,6 +1053,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         a wait: ops.StreamGroups.epipolar.  Serves a ring history and the default one alike."""
         return self._running_stream().epipolar(f0, F, **kw)
 
+    def stream_pose(self, f0, F, intrinsics, fundamental, label, **kw):
+        """One camera pose per frame [f0, f0 + F) of the running (or just closed) stream and two depths per point, from what
+        stream_epipolar returned for the same frames and the camera's intrinsics -- straight from the history and logits on the device,
+        by one launch and without a wait: ops.StreamGroups.pose.  Serves a ring history and the default one alike."""
+        return self._running_stream().pose(f0, F, intrinsics, fundamental, label, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

@@ -4,6 +4,7 @@ Every function enqueues HIP kernels from libctk_hip.so on the current torch stre
 computes on the CPU and nothing falls back to PyTorch ops.
 """
 import ctypes as C
+import math
 from collections import namedtuple
 from typing import List, Optional, Sequence
 
@@ -1395,6 +1396,92 @@ def fit_epipolar(tracks: torch.Tensor, visible: torch.Tensor, *, mask: Optional[
 
 
 # ------------------------------------------------------------------------------------------
+# fit pose (csrc/pose.hip; include/ctk.h, "fit pose")
+# ------------------------------------------------------------------------------------------
+def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G: int, F: int, N: int, N_out: int, device,
+                who: str) -> None:
+    """The camera, the inputs that ctk_fit_epipolar wrote and the source form of ctk_fit_pose_args; G, F, N, N_out: what they must
+    match.  `to` or `anchor` replaces the lag; both at once are refused.  Nothing here waits on the device."""
+    min_points = int(min_points)
+    if not L.Pose.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: min_points must lie in {L.Pose.MIN_POINTS}..{L.Motion.POINTS_MAX}")
+    if to is not None and anchor is not None:
+        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
+    if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
+        raise ValueError(f"{who}: intrinsics must be four Python floats (fx, fy, cx, cy) in raw-video pixels")
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
+    a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
+    a.min_points, a.reserved = min_points, 0
+    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
+    if to is not None:
+        a.to = int(to)
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif anchor is not None:
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
+    else:
+        a.lag = int(lag)
+        if a.lag < 1:
+            raise ValueError(f"{who}: lag must be >= 1")
+    if not (isinstance(fundamental, torch.Tensor) and fundamental.dtype == torch.float32 and fundamental.device == device and
+            tuple(fundamental.shape) == (G, F, 3, 3) and fundamental.is_contiguous()):
+        raise ValueError(f"{who}: fundamental must be a contiguous float32 tensor [{G},{F},3,3] on {device} (fit_epipolar's)")
+    if not (isinstance(label, torch.Tensor) and label.dtype == torch.int8 and label.device == device and
+            tuple(label.shape) == (G, F, N_out) and label.is_contiguous()):
+        raise ValueError(f"{who}: label must be a contiguous int8 tensor [{G},{F},{N_out}] on {device} (fit_epipolar's)")
+    a.fundamental, a.label = _ptr(fundamental), _ptr(label)
+    a.mask = None
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.dtype in (torch.int8, torch.uint8, torch.bool) and mask.device == device and
+                mask.numel() == G * N and mask.shape[-1] == N and mask.is_contiguous()):
+            raise ValueError(f"{who}: mask must be a contiguous int8, uint8 or bool tensor [{N}] or [{G},{N}] on {device}")
+        a.mask = _ptr(mask)
+
+
+def _pose_launch(a, device, out, who: str):
+    """Allocates (or checks) the three outputs of ctk_fit_pose for the G, F and N_out of `a`, then the launch."""
+    out = _out_tuple(out, [("pose", torch.float32, (a.G, a.F, 3, 4)), ("depth", torch.float32, (a.G, a.F, a.N_out, 2)),
+                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
+    a.pose, a.depth, a.stats = (_ptr(t_) for t_ in out)
+    ws = _scratch("motion", _query_bytes("ctk_fit_pose_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_pose(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_pose")
+    return out
+
+
+def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamental: torch.Tensor, label: torch.Tensor, *,
+             mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None,
+             min_points: int = 8, first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """How the camera turned, in which direction it moved, and how deep every tracked point is: per frame the fundamental matrix and
+    the labels of fit_epipolar become a pose and two depths per point, by one launch and without a wait (ctk_fit_pose; include/ctk.h
+    and csrc/pose_math.h have the rules).  Works on any result of any predictor here, offline ones included.
+
+    tracks, visible, lag / to / anchor, first_row, scale   what fit_epipolar was called with: they decide what a correspondence is.
+    intrinsics   (fx, fy, cx, cy), four Python floats: one pinhole camera in the pixels of tracks * scale, the same on both frames.
+    fundamental, label   float32 [G,T,3,3] and int8 [G,T,N] as fit_epipolar returned them; they are only read.
+    mask     int8 / uint8 / bool [N] / [G,N]: nonzero = the point may be fitted on if its label is 1; None: every point labelled 1.
+    The pose maps source-camera coordinates to the frame's, X_f = R X_s + t with |t| = 1: a closed-form decomposition of E = K^T F K,
+    the candidate that puts most of the fit list in front of both cameras, two Gauss-Newton rounds on the Sampson error.  Rows are all T
+    frames.  Returns (pose float32 [G,T,3,4] = (R | t), (I | 0) where there is no fit; depth float32 [G,T,N,2] = (depth on the source
+    frame, depth on the frame) in units of the baseline, NaN without a correspondence or a fit -- a point that moves by itself gets a
+    depth that means nothing, and `label` says so; stats int32 [G,T,4] = (points fitted on, those of them in front of both cameras,
+    the chosen candidate or -1, bit 0 / 1: the first / second round fell back, bit 2: an entry was left out of a round)); `out`: such a
+    tuple to write into.  A fit needs min_points (>= 8) points labelled 1.  The scale is unknown and changes from frame to frame; no
+    parallax (a camera that only turns or stands, a plane) means no pose: look at stats[..., 1] / stats[..., 0]."""
+    who = "fit_pose"
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    a = L.Pose.Args()
+    if isinstance(mask, torch.Tensor) and mask.dim() == 1 and G > 1:
+        mask = mask.expand(G, -1).contiguous()
+    _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G, T, N, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
+    return _pose_launch(a, dev, out, who)
+
+
+# ------------------------------------------------------------------------------------------
 # CoTracker2 iteration (cotracker.py:86-173): row kernels + the general update former
 # ------------------------------------------------------------------------------------------
 def sample_features4d(map_hwc: torch.Tensor, coords: torch.Tensor) -> torch.Tensor:
@@ -2164,6 +2251,27 @@ class StreamGroups:
         self._held(who, f0, F_, back=a.lag, to=a.to)  # (_epipolar_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
         self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _epipolar_launch(a, dev, out, who)
+
+    def pose(self, f0: int, F: int, intrinsics, fundamental: torch.Tensor, label: torch.Tensor, *, mask: Optional[torch.Tensor] = None,
+             lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None,
+             scale=(1.0, 1.0), thresh: float = 0.6, first_row: Optional[torch.Tensor] = None, min_points: int = 8,
+             group: Optional[int] = None, out=None):
+        """One camera pose per frame f0 .. f0 + F - 1 and two depths per point over the first N_out points of every group (or of `group`
+        alone), from what epipolar() returned for the same frames, source form, N_out, scale, thresh, first_row and group
+        (fundamental [G,F,3,3], label [G,F,N_out]; only read) and the intrinsics (fx, fy, cx, cy: four Python floats, in the pixels of
+        history coords * scale), straight from the stream's own history and logits by the one launch of ctk_fit_pose: fit_pose has the
+        picture.  mask int8 / uint8 / bool [G,N] (of the groups asked for) on the device, or None.  Every frame that is read (those
+        >= 0) must be among the committed ones the history still holds: ValueError otherwise.  -> (pose [G,F,3,4], depth
+        [G,F,N_out,2], stats [G,F,4]) on the device.  No wait."""
+        who = "pose"
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
+        dev = self.queries.device
+        a = L.Pose.Args()
+        f0, F_ = int(f0), int(F)
+        _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G, F_, self.N, N_out, dev, who)
+        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_pose_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _pose_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

@@ -816,6 +816,36 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         return fund[0], label[0], error[0], stats[0]
 
     @torch.no_grad()
+    def pose(self, intrinsics, n=None, first_frame=None, lag=8, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None,
+             group=0):
+        """Not in the reference: how the camera turned and in which direction it moved between frame f - lag and frame f, and how
+        deep each of the N (+ spare_points) user-visible points of query set `group` is, on the n frames from first_frame on (default:
+        the frames of the window just tracked, as in epipolar()) -- the launch of ctk_fit_epipolar and then the launch of ctk_fit_pose
+        on its matrix and labels (ops.StreamGroups.epipolar and .pose on the stream's own history and logits): two launches, no wait.
+        intrinsics: (fx, fy, cx, cy), four Python floats, one pinhole camera in raw-video pixels.  tol, hypotheses, min_base, seed and
+        mask are epipolar()'s; min_points holds for both: the matrix needs that many inliers, the pose that many points labelled 1.
+        The range errors are epipolar()'s.  Returns, on the device: pose float32 [n,3,4] = (R | t) with X_f = R X_(f - lag) + t in
+        camera coordinates and |t| = 1, (I | 0) where there is no fit; depth float32 [n,N,2] = (depth on frame f - lag, depth on frame
+        f) in units of that frame's baseline, NaN without a correspondence or a fit; label int8 [n,N], epipolar()'s: a point labelled
+        0 moves by itself and its depth means nothing; stats int32 [n,4] = (points fitted on, those of them in front of both cameras,
+        the chosen candidate or -1, bit 0 / 1: the first / second refinement round fell back, bit 2: an entry was left out of one).
+        The scale is unknown and changes from frame to frame; one pinhole camera without distortion; without parallax -- a camera that
+        only turns or stands, a planar scene -- there is no pose: look at stats[:, 1] / stats[:, 0] and compare with follow_planes().
+        No bundle adjustment over more than two frames."""
+        who = "pose"
+        gs, scale = self._running(who)
+        group = int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        mask = None if mask is None else mask[None]
+        source = dict(lag=lag, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(), group=group)
+        fund, label, _, _ = self.model.stream_epipolar(first_frame, n, mask=mask, tol=tol, hypotheses=hypotheses, min_base=min_base,
+                                                       min_points=min_points, seed=seed, **source)
+        pose, depth, stats = self.model.stream_pose(first_frame, n, intrinsics, fund, label, mask=mask, min_points=min_points, **source)
+        return pose[0], depth[0], label[0], stats[0]
+
+    @torch.no_grad()
     def split_scene(self, frame=None, lag=8, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None):
         """Not in the reference: the N (+ spare_points) user-visible points of query set `group` split into the static scene and what
         moves by itself between frame - lag and `frame` (default: the newest tracked one), under a camera that may translate through

@@ -47,6 +47,10 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_pose and ctk_fit_pose_workspace_bytes on the new
+ *       struct ctk_fit_pose_args: per frame, the fundamental matrix and the labels of ctk_fit_epipolar and four intrinsics become a
+ *       rotation, a unit translation (closed-form decomposition, a cheirality vote, two order-independent fixed-point Gauss-Newton
+ *       rounds on the Sampson error) and two depths per correspondence (csrc/pose_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_epipolar and ctk_fit_epipolar_workspace_bytes on the
  *       new struct ctk_fit_epipolar_args: per frame, one robust fundamental matrix (eight-point hypotheses by a pivoted elimination, a
  *       division-free Sampson test, two order-independent fixed-point refits) fitted to the correspondences of two frames, with a
@@ -1151,6 +1155,92 @@ typedef struct ctk_fit_epipolar_args {
 } ctk_fit_epipolar_args;
 int ctk_fit_epipolar_workspace_bytes(const ctk_fit_epipolar_args* a, size_t* out_bytes);
 int ctk_fit_epipolar(const ctk_fit_epipolar_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit pose: how the camera turned, where it went, and how deep every point is ---------------------------------------------------------
+ * For a caller who knows the camera's intrinsics: ctk_fit_epipolar leaves a fundamental matrix F and a label per point in picture
+ * coordinates; ctk_fit_pose turns them, per group g and frame f in [f0, f0 + F), into the 3-D product: the rotation R and the unit
+ * translation t that map source-camera coordinates to frame-f coordinates, X_f = R X_s + t, and the depth of every correspondence on
+ * both frames.  fx, fy, cx, cy describe ONE pinhole camera in raw-video pixels (the pixels of coords * (sx, sy)), the same on both
+ * frames.  The rules are stated once in csrc/pose_math.h.
+ *
+ * The frame of the call is ctk_fit_epipolar's; everything not named here is its own bit for bit: positions (1/16 pixel), the pair rule
+ * with its three source forms, first_row, `visible` or the logits with thresh, N_out <= 8192, the convention (Q, 1)^T F (P, 1) = 0 with
+ * P on the source frame and Q on frame f, ctk_plane_solve.  The gather decides what a correspondence is -- call it with the source
+ * form, first_row, visibility and scale the fundamental matrices were fitted with --; `label` only decides the fit list.
+ *   fit list   the M correspondences whose byte of `label` int8 [G,F,N_out] is 1 and, with `mask` int8 [G,N] given, whose mask byte is
+ *              nonzero.  Every correspondence, on the fit list or not, gets its depths.
+ *   rays       x = ((Px / 16 - cx) / fx, (Py / 16 - cy) / fy, 1) on the source frame, y likewise on frame f, in double: one division
+ *              per component.
+ *   E          from `fundamental` float32 [G,F,3,3]: E = K^T F K expanded into stated products and sums, then divided by its entry of
+ *              largest magnitude (the lowest index on ties).  F counts as no fit when it is all zero (ctk_fit_epipolar's no-fit
+ *              row) or has an entry that is not finite.
+ *   decompose  closed form, no SVD (Horn 1990): h = tr(E E^T) / 2, TT = h I - E E^T = t t^T up to scale; from its largest diagonal
+ *              entry i (> 0 and finite) t0 = TT[i] * rsqrt(TT[i][i]); with the cofactor matrix C of E and W = [t0]x E:
+ *              Ra = (C - W) / (t0 . t0), Rb = (C + W) / (t0 . t0); tn = t0 * rsqrt(t0 . t0).  Four candidates k = 0..3: (Ra, tn),
+ *              (Ra, -tn), (Rb, tn), (Rb, -tn).  rsqrt is eight Newton steps of products and differences on a mantissa scaled by an
+ *              exact even power of two: no library root is taken anywhere.  Every R is orthogonalised by four steps of
+ *              R = 0.5 R (3 I - R^T R); a candidate whose determinant is then not > 0, or with an entry that is not finite as
+ *              float32, is skipped.
+ *   depths     of a correspondence under (R, t), a = R x: den = (a.a)(y.y) - (a.y)^2, z_s = ((a.y)(y.t) - (a.t)(y.y)) / den,
+ *              z_f = ((a.a)(y.t) - (a.y)(a.t)) / den: the least-squares solution of z_s a + t = z_f y; +inf both where !(den > 0).
+ *   cheirality each candidate counts the fit-list entries with z_s > 0 and z_f > 0; the largest count wins, the lowest k on ties.
+ *   refine     two Gauss-Newton rounds on the Sampson error over the fit list, independent of the order of accumulation, no float
+ *              atomics: per entry the residual r = y . (E x), ctk_fit_epipolar's four-term gradient sum g under E = [t]x R, and the
+ *              derivatives Jw = (R x) x (y x t), Jt = (R x) x y; v = (Jw, Jt, r).  An entry takes part iff g > 0 and every
+ *              v_i v_i <= 16 g, which bounds every term by 16: the 28 sums of llrint(((v_i v_j) / g) 2^44) in int64 stay below 2^61.
+ *              With n t t^T on the translation block as the gauge (n entries take part) and an identity block that pads the system
+ *              to 8 x 8, ctk_fit_planes' square-root-free L D L^T gives (dw, dt); R = polar((I + [dw]x) R),
+ *              t = (t + dt) * rsqrt(|t + dt|^2).  A round whose solve or update fails keeps its pose (stats[3] bit 0 / 1); an entry
+ *              that was left out sets stats[3] bit 2.
+ *   outputs    pose float32 [G,F,3,4] = (R | t), the (float) of the doubles.  depth float32 [G,F,N_out,2] = (z_s, z_f) in units of
+ *              the baseline, for EVERY correspondence: a point that moves by itself gets a depth that means nothing, and `label`
+ *              says so; negative depths are written as they come; a NaN is the quiet NaN 0x7FC00000.  stats int32 [G,F,4] = (M,
+ *              entries of the fit list with both depths > 0 under the final pose, the chosen k or -1, the bits).  Every element is
+ *              written by one plain store.
+ *   no fit     F is no fit, M < min_points, the decomposition fails, or no candidate is left: pose = (I | 0), every correspondence's
+ *              depth is the quiet NaN 0x7FC00000, stats = (M, 0, -1, 0).  A slot without a correspondence has NaN depths in either
+ *              case.
+ * One launch on `stream`, one workgroup of 256 threads per (group, frame) with the correspondences and their slots in N_out * 18 bytes
+ * of LDS (thread 0 decomposes and solves; the votes and the sums are reduced by wave shuffles and through LDS); no atomics, no host
+ * synchronisation, capture-safe; `fundamental` and `label` are only read, the three outputs are all that is written.  The workspace
+ * query answers 0 and `workspace` may be NULL.  Before any launch: NULL a, hist_coords, fundamental, label, pose, depth or stats,
+ * `visible` NULL with hist_vis or hist_conf NULL, one of anchor_coords / anchor_visible without the other: CTK_E_NULL; every shape
+ * ctk_fit_epipolar refuses for the fields both structs have, min_points outside 8..8192, fx or fy not finite or not > 0, cx or cy not
+ * finite: CTK_E_SHAPE; hist_coords or anchor_coords not 8-byte aligned, fundamental, pose, depth or stats not 4-byte aligned:
+ * CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor is given).
+ *
+ * Known limits.  The scale is unknown: |t| = 1, depths are in baselines, and the unit changes from frame to frame.  One pinhole
+ * camera, no lens distortion.  No parallax means no pose -- a camera that only turns, a planar scene, a static camera: the caller
+ * tells by stats[1] / stats[0] and by comparing with ctk_fit_planes' inliers.  Two frames at a time: no bundle adjustment over more,
+ * no chaining of poses.                                                                                                                */
+typedef struct ctk_fit_pose_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the inputs and outputs is frame f0 + j, 0 <= j < F       */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t min_points;         /* a pose needs this many entries on its fit list, 8..8192           */
+  float fx, fy, cx, cy;       /* the pinhole camera, raw-video pixels                              */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const int8_t* mask;         /* [G,N], or NULL: every correspondence labelled 1 is fitted on      */
+  const float* fundamental;   /* [G,F,3,3], as ctk_fit_epipolar wrote it; read only                */
+  const int8_t* label;        /* [G,F,N_out], as ctk_fit_epipolar wrote it; read only              */
+  float* pose;                /* [G,F,3,4] */
+  float* depth;               /* [G,F,N_out,2] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_fit_pose_args;
+int ctk_fit_pose_workspace_bytes(const ctk_fit_pose_args* a, size_t* out_bytes);
+int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
