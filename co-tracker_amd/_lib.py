@@ -351,6 +351,27 @@ class Pose:
         ]
 
 
+class Resection:
+    """Holder of ctk_fit_resection_args (include/ctk.h, "fit resection"), nested like Pose.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_resection_cabi.py.  The constants mirror csrc/resection_math.h."""
+
+    LIST_MAX, MIN_POINTS, HYPOTHESES_MAX, ROUNDS = 4096, 6, 1024, 3
+
+    class Args(C.Structure):
+        """ctk_fit_resection_args: history rows, four intrinsics, a 3-D structure and a seed pose per frame -> per frame a pose (R | t)
+        in the structure's unit, a label and a reprojection error per point, and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("min_points", C.c_int32),
+            ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+            ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("tol", C.c_float),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp),
+            ("structure", _fp), ("valid", _fp), ("seed_pose", _fp), ("pose", _fp), ("label", _fp), ("error", _fp), ("stats", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -447,6 +468,8 @@ SYMBOLS = {
     "ctk_fit_epipolar": (C.c_int, [_P(Epipolar.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_pose_workspace_bytes": (C.c_int, [_P(Pose.Args), _P(C.c_size_t)]),
     "ctk_fit_pose": (C.c_int, [_P(Pose.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_resection_workspace_bytes": (C.c_int, [_P(Resection.Args), _P(C.c_size_t)]),
+    "ctk_fit_resection": (C.c_int, [_P(Resection.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

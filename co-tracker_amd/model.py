@@ -1059,6 +1059,12 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         by one launch and without a wait: ops.StreamGroups.pose.  Serves a ring history and the default one alike."""
         return self._running_stream().pose(f0, F, intrinsics, fundamental, label, **kw)
 
+    def stream_resection(self, f0, F, intrinsics, structure, valid, seed_pose, **kw):
+        """One camera pose per frame [f0, f0 + F) of the running (or just closed) stream against a 3-D structure, in that structure's
+        unit and coordinates, started from what stream_pose returned for the same frames -- straight from the history and logits on
+        the device, by one launch and without a wait: ops.StreamGroups.resection.  Serves a ring history and the default one alike."""
+        return self._running_stream().resection(f0, F, intrinsics, structure, valid, seed_pose, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

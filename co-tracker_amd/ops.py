@@ -1398,13 +1398,9 @@ def fit_epipolar(tracks: torch.Tensor, visible: torch.Tensor, *, mask: Optional[
 # ------------------------------------------------------------------------------------------
 # fit pose (csrc/pose.hip; include/ctk.h, "fit pose")
 # ------------------------------------------------------------------------------------------
-def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G: int, F: int, N: int, N_out: int, device,
-                who: str) -> None:
-    """The camera, the inputs that ctk_fit_epipolar wrote and the source form of ctk_fit_pose_args; G, F, N, N_out: what they must
-    match.  `to` or `anchor` replaces the lag; both at once are refused.  Nothing here waits on the device."""
-    min_points = int(min_points)
-    if not L.Pose.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: min_points must lie in {L.Pose.MIN_POINTS}..{L.Motion.POINTS_MAX}")
+def _camera_and_source(a, intrinsics, lag, to, anchor, G: int, N: int, device, who: str) -> None:
+    """The four intrinsics and the source form (lag / to / anchor) of ctk_fit_pose_args and ctk_fit_resection_args.  `to` or `anchor`
+    replaces the lag; both at once are refused.  Nothing here waits on the device."""
     if to is not None and anchor is not None:
         raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
     if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
@@ -1413,7 +1409,6 @@ def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_po
     if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
         raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
     a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
-    a.min_points, a.reserved = min_points, 0
     a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
     if to is not None:
         a.to = int(to)
@@ -1425,6 +1420,17 @@ def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_po
         a.lag = int(lag)
         if a.lag < 1:
             raise ValueError(f"{who}: lag must be >= 1")
+
+
+def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G: int, F: int, N: int, N_out: int, device,
+                who: str) -> None:
+    """The camera, the inputs that ctk_fit_epipolar wrote and the source form of ctk_fit_pose_args; G, F, N, N_out: what they must
+    match.  `to` or `anchor` replaces the lag; both at once are refused.  Nothing here waits on the device."""
+    min_points = int(min_points)
+    if not L.Pose.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: min_points must lie in {L.Pose.MIN_POINTS}..{L.Motion.POINTS_MAX}")
+    _camera_and_source(a, intrinsics, lag, to, anchor, G, N, device, who)
+    a.min_points, a.reserved = min_points, 0
     if not (isinstance(fundamental, torch.Tensor) and fundamental.dtype == torch.float32 and fundamental.device == device and
             tuple(fundamental.shape) == (G, F, 3, 3) and fundamental.is_contiguous()):
         raise ValueError(f"{who}: fundamental must be a contiguous float32 tensor [{G},{F},3,3] on {device} (fit_epipolar's)")
@@ -1479,6 +1485,109 @@ def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamenta
         raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
     _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
     return _pose_launch(a, dev, out, who)
+
+
+# ------------------------------------------------------------------------------------------
+# fit resection (csrc/resection.hip; include/ctk.h, "fit resection")
+# ------------------------------------------------------------------------------------------
+class Structure:
+    """The static points of a query set in 3-D, and the frame whose camera they are stated in: points float32 [N,3] on the device in
+    that camera's coordinates and in the baseline of the pair they were reconstructed from as the unit, valid int8 [N] (nonzero: the
+    point is in the structure), the anchor (FieldAnchor) pinned on that frame, and the intrinsics (fx, fy, cx, cy) they were made
+    with.  What reconstruct() of the online predictor returns and localize() takes."""
+    __slots__ = ("points", "valid", "anchor", "intrinsics")
+
+    def __init__(self, points: torch.Tensor, valid: torch.Tensor, anchor: FieldAnchor, intrinsics):
+        self.points, self.valid, self.anchor, self.intrinsics = points, valid, anchor, tuple(float(v) for v in intrinsics)
+
+
+def structure_from_pose(tracks_row: torch.Tensor, intrinsics, depth: torch.Tensor, label: torch.Tensor, *, max_depth: float = 64.0,
+                        scale=(1, 1)):
+    """The 3-D points that one pair of frames gives, from what fit_pose and fit_epipolar returned for it (elementwise torch, no wait):
+    tracks_row float32 [...,N,2] = the positions on the LATER frame of the pair, depth float32 [...,N,2] and label int8 [...,N] of that
+    frame's row.  X = z * ray with the depth z on the later frame and ray = ((x * sx - cx) / fx, (y * sy - cy) / fy, 1): camera
+    coordinates of the later frame, in baselines of the pair.  A point is valid when it is labelled 1, both its depths are finite and
+    > 0, and z <= max_depth baselines (a parameter, not a measured optimum: far points carry no parallax, their depth is mostly noise).
+    -> (points float32 [...,N,3], zero where not valid; valid int8 [...,N])."""
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    zs, zf = depth[..., 0], depth[..., 1]
+    rx, ry = (tracks_row[..., 0] * float(scale[0]) - cx) / fx, (tracks_row[..., 1] * float(scale[1]) - cy) / fy
+    ok = (label == 1) & torch.isfinite(zs) & torch.isfinite(zf) & (zs > 0) & (zf > 0) & (zf <= float(max_depth))
+    pts = torch.stack([rx * zf, ry * zf, zf], dim=-1)
+    return torch.where(ok[..., None], pts, torch.zeros_like(pts)), ok.to(torch.int8)
+
+
+def _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G: int, F: int, N: int,
+                     device, who: str) -> None:
+    """The camera, the structure, the seed poses, the fit and the source form of ctk_fit_resection_args; G, F, N: what they must
+    match.  Nothing here waits on the device."""
+    min_points, hypotheses, tol = int(min_points), int(hypotheses), float(tol)
+    if not L.Resection.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: min_points must lie in {L.Resection.MIN_POINTS}..{L.Motion.POINTS_MAX}")
+    if not 1 <= hypotheses <= L.Resection.HYPOTHESES_MAX:
+        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Resection.HYPOTHESES_MAX}")
+    if not (math.isfinite(tol) and 0.0 < tol <= 3.0e38):
+        raise ValueError(f"{who}: tol must be finite and > 0 (raw-video pixels)")
+    _camera_and_source(a, intrinsics, lag, to, anchor, G, N, device, who)
+    a.min_points, a.hypotheses, a.seed, a.tol = min_points, hypotheses, int(seed) & 0xffffffff, tol
+    if not (isinstance(structure, torch.Tensor) and structure.dtype == torch.float32 and structure.device == device and
+            tuple(structure.shape) == (G, N, 3) and structure.is_contiguous()):
+        raise ValueError(f"{who}: structure must be a contiguous float32 tensor [{G},{N},3] on {device}")
+    if not (isinstance(valid, torch.Tensor) and valid.dtype in (torch.int8, torch.uint8, torch.bool) and valid.device == device and
+            tuple(valid.shape) == (G, N) and valid.is_contiguous()):
+        raise ValueError(f"{who}: valid must be a contiguous int8, uint8 or bool tensor [{G},{N}] on {device}")
+    if not (isinstance(seed_pose, torch.Tensor) and seed_pose.dtype == torch.float32 and seed_pose.device == device and
+            tuple(seed_pose.shape) == (G, F, 3, 4) and seed_pose.is_contiguous()):
+        raise ValueError(f"{who}: seed_pose must be a contiguous float32 tensor [{G},{F},3,4] on {device} (fit_pose's)")
+    a.structure, a.valid, a.seed_pose = _ptr(structure), _ptr(valid), _ptr(seed_pose)
+
+
+def _resection_launch(a, device, out, who: str):
+    """Allocates (or checks) the four outputs of ctk_fit_resection for the G, F and N_out of `a`, then the launch."""
+    out = _out_tuple(out, [("pose", torch.float32, (a.G, a.F, 3, 4)), ("label", torch.int8, (a.G, a.F, a.N_out)),
+                           ("error", torch.float32, (a.G, a.F, a.N_out)), ("stats", torch.int32, (a.G, a.F, 4))], device, who)
+    a.pose, a.label, a.error, a.stats = (_ptr(t_) for t_ in out)
+    ws = _scratch("motion", _query_bytes("ctk_fit_resection_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_resection(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_resection")
+    return out
+
+
+def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, structure: torch.Tensor, valid: torch.Tensor,
+                  seed_pose: torch.Tensor, *, lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None,
+                  tol: float = 2.0, hypotheses: int = 256, min_points: int = 16, seed: int = 0,
+                  first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """Where the camera is on every frame, in ONE unit and ONE coordinate system: per frame the camera's pose against 3-D points that
+    are known in the source camera's coordinates (a structure: structure_from_pose on one pair of frames), by one launch and without
+    a wait (ctk_fit_resection; include/ctk.h and csrc/resection_math.h have the rules).  Works on any result of any predictor here,
+    offline ones included.
+
+    tracks, visible, lag / to / anchor, first_row, scale   as in fit_pose: they decide what a correspondence is; the source frame
+             (usually a fixed `to` or an anchor) is the frame whose camera the structure is stated in.
+    intrinsics   (fx, fy, cx, cy), four Python floats: one pinhole camera in the pixels of tracks * scale.
+    structure, valid   float32 [G,N,3] / [N,3] and int8 / uint8 / bool [G,N] / [N]: the points and which of them count; only read.
+    seed_pose    float32 [G,T,3,4] / [T,3,4]: a pose per frame to start from, fit_pose's for the same source (its |t| = 1 is rescaled
+             against the structure) or the poses of an earlier call; a row that is not finite counts as (I | 0); only read.
+    Every candidate keeps the seed's rotation (or the identity) and differs in one scale of its translation; the one with most points
+    within tol pixels of their reprojection wins and is refined by three Gauss-Newton rounds on the reprojection error.  Rows are all
+    T frames.  Returns (pose float32 [G,T,3,4] = (R | t) with X_f = R X_source + t in the structure's unit, (I | 0) where there is
+    no fit; label int8 [G,T,N]: -1 no correspondence or not in the structure, 0 outside tol, behind the camera or no fit, 1 within
+    tol; error float32 [G,T,N]: the squared reprojection error in px^2, -1 where the label is -1 or there is no fit; stats int32
+    [G,T,4] = (points fitted on, points labelled 1, the winning candidate or -1, bits 0 / 1 / 4: round 1 / 2 / 3 fell back, bit 2: an
+    entry was left out of a round, bit 3: more than 4096 points, the first 4096 were fitted on, bit 5: the frame is the source frame
+    itself, the pose is exactly (I | 0))); `out`: such a tuple to write into.  A fit needs min_points (>= 6) points within tol.  The
+    unit is the structure's; the seed's rotation must be close (no minimal solver); one pinhole camera without distortion; the
+    structure is not refined (no bundle adjustment)."""
+    who = "fit_resection"
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
+    a = L.Resection.Args()
+    structure = structure[None] if isinstance(structure, torch.Tensor) and structure.dim() == 2 else structure
+    valid = valid[None] if isinstance(valid, torch.Tensor) and valid.dim() == 1 else valid
+    seed_pose = seed_pose[None] if isinstance(seed_pose, torch.Tensor) and seed_pose.dim() == 3 else seed_pose
+    _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G, T, N, dev, who)
+    if a.to >= T:
+        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
+    return _resection_launch(a, dev, out, who)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2272,6 +2381,28 @@ class StreamGroups:
         self._held(who, f0, F_, back=a.lag, to=a.to)  # (_pose_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
         self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _pose_launch(a, dev, out, who)
+
+    def resection(self, f0: int, F: int, intrinsics, structure: torch.Tensor, valid: torch.Tensor, seed_pose: torch.Tensor, *,
+                  lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None,
+                  scale=(1.0, 1.0), thresh: float = 0.6, first_row: Optional[torch.Tensor] = None, tol: float = 2.0, hypotheses: int = 256,
+                  min_points: int = 16, seed: int = 0, group: Optional[int] = None, out=None):
+        """One camera pose per frame f0 .. f0 + F - 1 against a 3-D structure (structure float32 [G,N,3] in the source camera's
+        coordinates, valid int8 / uint8 / bool [G,N], of the groups asked for; only read), started from seed_pose float32 [G,F,3,4]
+        (pose()'s for the same frames and source form; only read), over the first N_out points of every group (or of `group` alone),
+        straight from the stream's own history and logits by the one launch of ctk_fit_resection: fit_resection has the picture.
+        intrinsics: (fx, fy, cx, cy), four Python floats, in the pixels of history coords * scale.  Every frame that is read (those
+        >= 0) must be among the committed ones the history still holds: ValueError otherwise.  -> (pose [G,F,3,4], label
+        [G,F,N_out], error [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
+        who = "resection"
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
+        dev = self.queries.device
+        a = L.Resection.Args()
+        f0, F_ = int(f0), int(F)
+        _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G, F_, self.N, dev,
+                         who)
+        self._held(who, f0, F_, back=a.lag, to=a.to)  # (the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _resection_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

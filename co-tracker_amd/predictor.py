@@ -846,6 +846,78 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         return pose[0], depth[0], label[0], stats[0]
 
     @torch.no_grad()
+    def reconstruct(self, intrinsics, frame=None, lag=8, max_depth=64.0, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16,
+                    seed=0, mask=None):
+        """Not in the reference: the static points of query set `group` in 3-D, reconstructed ONCE from the pair (frame - lag, frame)
+        (default: the newest tracked frame) -- pose() for that one pair (two launches), ops.structure_from_pose (elementwise torch: the
+        depth on `frame` times the point's ray) and one pin(frame), without a wait.  intrinsics: (fx, fy, cx, cy), four Python floats,
+        one pinhole camera in raw-video pixels; tol, hypotheses, min_base, min_points, seed and mask are pose()'s; max_depth (in
+        baselines of the pair) drops far points, which carry no parallax: a parameter, not a measured optimum.  ValueError when
+        frame - lag is negative or has left the ring (history_frames) or the frame has not been tracked, as split_scene().  Returns an
+        ops.Structure: points float32 [N_model,3] on the device in the camera coordinates of `frame`, valid int8 [N_model] (labelled
+        static, both depths finite and > 0, no deeper than max_depth), the anchor pinned on `frame`, the intrinsics; localize() takes
+        it.  The unit is the baseline of this pair, for as long as the structure is used.  A structure lives as long as enough of its
+        points stay tracked: points that replenish() adds later are not in it, and triangulating new points from two localised frames
+        is the next step and is not built.  One pinhole camera, no lens distortion; the structure is never refined (no bundle
+        adjustment); without parallax on the pair (a camera that only turns or stands, a plane) there is no structure: valid is all
+        zero."""
+        from . import ops
+        who = "reconstruct"
+        gs, scale = self._running(who)
+        frame, lag, group = gs.committed - 1 if frame is None else int(frame), int(lag), int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        if not 0 <= frame < gs.committed or lag < 1 or frame - lag < 0:
+            raise ValueError(f"{who}: frames {frame - lag} and {frame} must both have been tracked ({gs.committed} frames), lag >= 1")
+        _, depth, label, _ = self.pose(intrinsics, 1, frame, lag=lag, tol=tol, hypotheses=hypotheses, min_base=min_base,
+                                       min_points=min_points, seed=seed, mask=mask, group=group)
+        anchor = self.pin(frame, group)
+        pts, ok = ops.structure_from_pose(anchor.coords[0, :self.N], intrinsics, depth[0], label[0], max_depth=max_depth, scale=scale)
+        points = torch.zeros((gs.N, 3), dtype=torch.float32, device=pts.device)
+        valid = torch.zeros((gs.N,), dtype=torch.int8, device=pts.device)
+        points[:self.N], valid[:self.N] = pts, ok
+        return ops.Structure(points, valid, anchor, intrinsics)
+
+    @torch.no_grad()
+    def localize(self, structure, n=None, first_frame=None, tol=2.0, hypotheses=256, min_points=16, seed=0, epipolar_tol=1.0,
+                 epipolar_hypotheses=512, min_base=16.0):
+        """Not in the reference: where the camera is on the n frames from first_frame on (default: the frames of the window just
+        tracked, as in pose()) in the ONE unit and the ONE coordinate system of an ops.Structure (reconstruct()) -- every pose of every
+        later call can be compared with every other, which pose() alone cannot give (its |t| = 1 on every frame).  THREE launches and
+        no wait, each against the structure's anchor, which outlives the ring (history_frames), so nothing is chained and nothing
+        drifts: ctk_fit_epipolar with structure.valid as the mask (epipolar_tol, epipolar_hypotheses, min_base and seed are
+        epipolar()'s), ctk_fit_pose on its matrix and labels, and ctk_fit_resection with that pose as the seed: its translation is
+        rescaled against the structure by `hypotheses` sampled points, the candidate with most points within `tol` pixels of their
+        reprojection wins and is refined by three Gauss-Newton rounds on the reprojection error.  min_points holds for all three (the
+        first two need at least 8).  Returns, on the device: pose float32 [n,3,4] = (R | t) with X_f = R X_anchor + t in camera
+        coordinates, (I | 0) where there is no fit -- and exactly (I | 0) on the structure's own frame; label int8 [n,N]: -1 not on
+        both frames or not in the structure, 0 outside tol (a point of the structure that has begun to move), behind the camera or no
+        fit, 1 within tol; error float32 [n,N]: the squared reprojection error in px^2, -1 where the label is -1 or there is no fit;
+        stats int32 [n,4] = (points fitted on, points labelled 1, the winning candidate or -1, bits 0 / 1 / 4: a refinement round fell
+        back, bit 2: an entry was left out, bit 3: more than 4096 points, bit 5: the frame is the structure's own).  The camera's
+        position in the structure's coordinates is -R^T t.  The limits are reconstruct()'s: the unit is the baseline of its pair; the
+        structure lives as long as enough of its points stay tracked (stats[:, 1] tells), points added later by replenish() are not in
+        it, and triangulating new points from two localised frames is the next step and is not built; the seed comes from the
+        two-view pose, so a frame without parallax against the anchor that is not the anchor itself (a camera that only turned)
+        relies on the fixed candidates (R0, 0) and (I, 0) -- there is no minimal P3P solver; one pinhole camera, no lens distortion;
+        no bundle adjustment.  ValueError for frames not yet tracked; NotImplementedError on a v2 predictor."""
+        from . import ops
+        who = "localize"
+        gs, scale = self._running(who)
+        if not isinstance(structure, ops.Structure):
+            raise ValueError(f"{who}: structure must be an ops.Structure (reconstruct)")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        mask, anchor, cam = structure.valid[None], structure.anchor, structure.intrinsics
+        source = dict(anchor=anchor, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(), group=anchor.group)
+        two_view = max(int(min_points), 8)
+        fund, label, _, _ = self.model.stream_epipolar(first_frame, n, mask=mask, tol=epipolar_tol, hypotheses=epipolar_hypotheses,
+                                                       min_base=min_base, min_points=two_view, seed=seed, **source)
+        seeds, _, _ = self.model.stream_pose(first_frame, n, cam, fund, label, mask=mask, min_points=two_view, **source)
+        pose, label, error, stats = self.model.stream_resection(first_frame, n, cam, structure.points[None], mask, seeds, tol=tol,
+                                                                hypotheses=hypotheses, min_points=min_points, seed=seed, **source)
+        return pose[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
     def split_scene(self, frame=None, lag=8, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None):
         """Not in the reference: the N (+ spare_points) user-visible points of query set `group` split into the static scene and what
         moves by itself between frame - lag and `frame` (default: the newest tracked one), under a camera that may translate through

@@ -47,6 +47,10 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_resection and ctk_fit_resection_workspace_bytes on the
+ *       new struct ctk_fit_resection_args: per frame, the camera's pose against a fixed 3-D structure in that structure's unit and
+ *       coordinates (one-scalar candidates on a seed pose scored by integer counts of reprojection inliers, three order-independent
+ *       fixed-point Gauss-Newton rounds on the reprojection error; csrc/resection_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_pose and ctk_fit_pose_workspace_bytes on the new
  *       struct ctk_fit_pose_args: per frame, the fundamental matrix and the labels of ctk_fit_epipolar and four intrinsics become a
  *       rotation, a unit translation (closed-form decomposition, a cheirality vote, two order-independent fixed-point Gauss-Newton
@@ -1241,6 +1245,89 @@ typedef struct ctk_fit_pose_args {
 } ctk_fit_pose_args;
 int ctk_fit_pose_workspace_bytes(const ctk_fit_pose_args* a, size_t* out_bytes);
 int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit resection: the camera's pose against a fixed 3-D structure, every frame in ONE unit ----------------------------------------------
+ * ctk_fit_pose gives every frame a pose in a unit of its own (|t| = 1).  ctk_fit_resection fits the camera of group g and frame f in
+ * [f0, f0 + F) against points whose 3-D positions are KNOWN -- `structure`, in the coordinates of the source camera and in one unit,
+ * for instance the depths ctk_fit_pose gave for one pinned pair of frames, times their rays -- so that every pose of every call is in
+ * that one unit and coordinate system: X_f = R X_source + t.  The rules are stated once in csrc/resection_math.h.
+ *
+ * The frame of the call is ctk_fit_pose's; everything not named here is its own bit for bit: positions (1/16 pixel), the pair rule
+ * with its three source forms, first_row, `visible` or the logits with thresh, N_out <= 8192, the four intrinsics, rays,
+ * ctk_plane_solve, the polar steps.  The gather decides what a correspondence is; only the position Q on frame f is then used.
+ *   fit list   the correspondences whose byte of `valid` int8 [G,N] is nonzero and whose three floats of `structure` float32 [G,N,3]
+ *              are finite, in ascending n.  The first 4096 take part (M of them; an LDS limit), more set stats[3] bit 3.
+ *   project    X' = R X + t; behind the camera (!(Z' > 0)) the error is +inf; else p = (fx X'/Z' + cx, fy Y'/Z' + cy) (one division,
+ *              iz = 1 / Z', per projection) and the error
+ *              e = (px - Qx/16)^2 + (py - Qy/16)^2 in px^2 (a NaN counts as +inf); within tol iff e <= tol^2: no root is taken.
+ *   seed       `seed_pose` float32 [G,F,3,4] = (R0 | t0), only read.  A seed with an entry that is not finite, or whose R0 has no
+ *              determinant > 0 after the four polar steps (an all-zero seed), counts as (I | 0).
+ *   candidates every candidate shares R0 or I and differs in one scalar, so a = R0 X is formed once per entry and a candidate is
+ *              X' = a + s t0.  k < hypotheses (1..1024): the seeded generator of ctk_fit_motion picks an entry of the fit list, and
+ *              s is the least-squares scale of lambda y = a + s t0 for its ray y, a 2 x 2 closed form; an s that is not finite or
+ *              not > 0 is skipped.  Then the fixed candidates k = hypotheses: (R0, t0), k + 1: (R0, 0), k + 2: (I, 0).
+ *   score      an integer count of fit-list entries within tol; the largest wins, the lowest k on ties; fewer than min_points
+ *              (6..8192): no fit.
+ *   still      every structure point with a correspondence (beyond the list cap too; at least one) sits where it sat on the source
+ *              frame, Q = P in 1/16 pixel: as far as the tracks tell the frame IS the source frame.  Then only (I, 0) is scored and no
+ *              round is run: with min_points entries within tol the pose is exactly (I | 0) and stats[2] = hypotheses + 2; stats[3]
+ *              bit 5 is set either way.  (A refit there could only follow the float32 rounding of the structure.)
+ *   refit      three Gauss-Newton rounds on the reprojection error over the entries within tol under the round's pose, independent of
+ *              the order of accumulation, no float atomics: per entry and residual component v = (J (6), r); with
+ *              c2 = 256 (fx^2 + fy^2) an entry takes part iff every v_i^2 <= 16 c2 (else stats[3] bit 2), which bounds every term by
+ *              16: the 28 sums of llrint(((v_i v_j) (1 / c2)) 2^44) in int64 over at most 4096 entries x 2 stay below 2^61.  An identity
+ *              block pads the 6 x 6 system to the 8 x 8 of ctk_fit_planes' square-root-free L D L^T; R = polar((I + [dw]x) R),
+ *              t = t + dt; no gauge, the structure fixes the scale.  A round with fewer than 6 entries, or whose solve or update
+ *              fails, keeps its pose (stats[3] bits 0 / 1 / 4 for rounds 1 / 2 / 3).
+ *   outputs    pose float32 [G,F,3,4] = (R | t).  label int8 [G,F,N_out]: -1 no correspondence or the point is not in the structure,
+ *              0 outside tol, behind the camera, or there is no fit, 1 within tol; entries beyond the list cap are classified too.
+ *              error float32 [G,F,N_out]: e, -1 where the label is -1 or there is no fit.  stats int32 [G,F,4] = (M, slots labelled
+ *              1 under the final pose, the winning k or -1, the bits: 0 / 1 / 4 a round fell back, 2 an entry was left out, 3 the list
+ *              cap dropped entries, 5 the frame is still).  Every element is written by one plain store.
+ *   no fit     pose = (I | 0), stats = (M, 0, -1, bits).
+ * One launch on `stream`, one workgroup of 256 threads per (group, frame) with the fit list in min(N_out, 4096) * 34 bytes of LDS
+ * (thread 0 orthogonalises and solves; counts by ballots, sums by wave shuffles and through LDS); no atomics, no host
+ * synchronisation, capture-safe; `structure`, `valid` and `seed_pose` are only read.  The workspace query answers 0 and `workspace`
+ * may be NULL.  Before any launch: NULL a, hist_coords, structure, valid, seed_pose, pose, label, error or stats, `visible` NULL
+ * with hist_vis or hist_conf NULL, one of anchor_coords / anchor_visible without the other: CTK_E_NULL; every shape ctk_fit_pose
+ * refuses for the fields both structs have (min_points from 6 on), hypotheses outside 1..1024, tol not finite or not > 0:
+ * CTK_E_SHAPE; hist_coords or anchor_coords not 8-byte aligned, structure, seed_pose, pose, error or stats not 4-byte aligned:
+ * CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor is given).
+ *
+ * Known limits.  The unit is the structure's (the baseline of the pair it was reconstructed from).  A structure lives as long as
+ * enough of its points stay tracked; nothing adds points to it.  The candidates come from the seed: a seed whose rotation is far off
+ * finds no fit (no minimal P3P solver).  One pinhole camera, no lens distortion.  No bundle adjustment: the structure is not refined. */
+typedef struct ctk_fit_resection_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the inputs and outputs is frame f0 + j, 0 <= j < F       */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t min_points;         /* a fit needs this many entries within tol, 6..8192                 */
+  int32_t hypotheses;         /* sampled candidates, 1..1024                                       */
+  uint32_t seed;              /* of the generator                                                  */
+  float fx, fy, cx, cy;       /* the pinhole camera, raw-video pixels                              */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  float tol;                  /* reprojection tolerance in raw-video pixels, finite and > 0        */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const float* structure;     /* [G,N,3], source-camera coordinates; read only                     */
+  const int8_t* valid;        /* [G,N], nonzero: the point is in the structure; read only          */
+  const float* seed_pose;     /* [G,F,3,4]; read only                                              */
+  float* pose;                /* [G,F,3,4] */
+  int8_t* label;              /* [G,F,N_out] */
+  float* error;               /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_fit_resection_args;
+int ctk_fit_resection_workspace_bytes(const ctk_fit_resection_args* a, size_t* out_bytes);
+int ctk_fit_resection(const ctk_fit_resection_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
