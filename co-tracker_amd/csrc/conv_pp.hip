@@ -95,7 +95,8 @@ __global__ __launch_bounds__(512) void conv_pp128_kernel(CtkConvP p, int tiles_t
     const bool ph1 = (p.n_valid - n0 > 64) || conv_force_ph1;  // workgroup-uniform: does the second 64-column phase carry stored columns?
 
     // ---- per-lane decode of my A rows: first block pieces 3w+e (e < 3), second block pieces 24 + 3w + e while 3w + e < 8
-    int pix[6], iyx[6];  // pixel index of (f, 0, 0) in the input; packed (iy0 + 0x4000) << 16 | (ix0 + 0x4000)
+    int pix[6], iyx[6];  // pixel index of (f, 0, 0) in the input; packed (iy0 + 0x4000) << 16 | (ix0 + 0x4000): ctk_conv2d_sh
+                         // admits only shapes with -0x4000 <= iy0 <= 0x3fff and -0x4000 <= ix0 <= 0xbfff
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       const int piece = k < 3 ? 3 * wave + k : 24 + 3 * wave + (k - 3);
@@ -487,13 +488,21 @@ extern "C" int ctk_conv2d_sh(const void* in_sh, int32_t F, int32_t Hin, int32_t 
                              const void* zeros, void* stream) {
   if (!in_sh || !wp || !bias || !out || !zeros) return CTK_E_NULL;
   if (F <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || (Cin % 32) || n_out <= 0 || n_pad < n_out || (n_pad % 128) || (n_out % 32) ||
-      n_pad > 1024 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || Hin > 16000 || Win > 16000)
-    return CTK_E_SHAPE;
+      n_pad > 1024 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || pad > 0x4000 || Hin > 16000 || Win > 16000)
+    return CTK_E_SHAPE;  // (pad <= 0x4000: the smallest row origin, -pad, in the packing below; and Hin + 2 pad stays an int)
   if (!ctk_aligned16(in_sh) || !ctk_aligned16(wp) || !ctk_aligned16(bias) || !ctk_aligned16(out) || !ctk_aligned16(zeros)) return CTK_E_ALIGN;
   const int Hout = (Hin + 2 * pad - KH) / stride + 1, Wout = (Win + 2 * pad - KW) / stride + 1;
   if (Hout <= 0 || Wout <= 0) return CTK_E_SHAPE;
   const long M = (long)F * Hout * Wout;
   if (M > 0x7fffffffL || (long)F * Hin * Win > 0x7fffffffL) return CTK_E_SHAPE;
+  // conv_pp128_kernel keeps a row's origin (oy*stride - pad, ox*stride - pad) as (iy0 + 0x4000) << 16 | (ix0 + 0x4000) in one int
+  // and reads it back with an arithmetic >> 16 and & 0xffff: the high half holds 0 .. 0x7fff, the low half 0 .. 0xffff.  The
+  // smallest origin is -pad (>= -0x4000, checked above), the largest (Hout-1)*stride - pad: at most 0x3fff for rows, 0xbfff for
+  // columns.  (With Win <= 16000 and pad <= 0x4000 the column origin stays below 16000 + 0x4000 < 0xc000: the second test never
+  // fires on its own; it is the packing's rule all the same.)  Tap coordinates are origin + ky in a full int afterwards.
+  // K = KH*KW*Cin is an int, and a row of the packed weights is K*4 bytes in an unsigned.
+  if ((long)(Hout - 1) * stride - pad > 0x3fff || (long)(Wout - 1) * stride - pad > 0xbfff) return CTK_E_SHAPE;
+  if ((long)KH * KW * Cin >= (1L << 30)) return CTK_E_SHAPE;
   CtkConvP p;
   CtkGemmP& g = p.g;
   g = CtkGemmP{};

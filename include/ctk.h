@@ -1481,7 +1481,12 @@ int ctk_avg_pool2_nhwc(const float* in, int32_t F, int32_t H, int32_t W, float* 
  *   in_sh  [F][Hin][Win][Cin/32] lines; Cin % 32 == 0
  *   wp     ctk_pack_weight blob of the matrix W'[n_pad][KH*KW*Cin], W'[n][(ky*KW+kx)*Cin + c] = weight[n][c][ky][kx], rows
  *          n >= n_out zero, n_pad % 128 == 0; bias: n_pad floats (zeros beyond n_out)
- *   out    f32 [F*Hout*Wout][n_out], Hout = (Hin + 2 pad - KH)/stride + 1; zeros: >= 128 zero bytes on the device          */
+ *   out    f32 [F*Hout*Wout][n_out], Hout = (Hin + 2 pad - KH)/stride + 1; zeros: >= 128 zero bytes on the device
+ *   Limits (CTK_E_SHAPE otherwise): n_out % 32 == 0, n_out <= n_pad <= 1024; F, KH, KW, stride > 0; 0 < Hin, Win <= 16000;
+ *   Hout, Wout > 0; F*Hout*Wout and F*Hin*Win <= 2^31 - 1; KH*KW*Cin < 2^30; and the range of a row's first tap, which the
+ *   kernel keeps in 15 + 16 bits biased by 16384:  0 <= pad <= 16384,  (Hout-1)*stride - pad <= 16383,
+ *   (Wout-1)*stride - pad <= 49151 (implied by the limits on Win and pad).  E.g. Hin = 16000, 3x3, stride 1 takes pad <= 386.
+ *   All five pointers non-NULL (CTK_E_NULL) and 16-byte aligned (CTK_E_ALIGN).                                              */
 int ctk_conv2d_sh(const void* in_sh, int32_t F, int32_t Hin, int32_t Win, int32_t Cin, const void* wp, const float* bias,
                   int32_t n_out, int32_t n_pad, int32_t KH, int32_t KW, int32_t stride, int32_t pad, float* out,
                   const void* zeros, void* stream);

@@ -84,6 +84,19 @@ def gemm_raw(A, lda, M, N, K, out, ldc, W=None, ldw=0, Wp=None, bias=None, bias_
     return L.load().ctk_gemm(C.byref(g), stream)
 
 
+# ---- ctk_conv2d_sh as the C-ABI sees it (tests/test_gpu_conv_matrix.py, test_cabi_and_host.py) -------------------------------------------
+def conv_raw(in_sh, F, H, W, Cin, wp, bias, n_out, n_pad, KH, KW, stride, pad, out, zeros):
+    """ctk_conv2d_sh on the current stream with every argument the caller's (HipEncoder._conv allocates the output itself and takes
+    the rest from a _Conv) -> its return code.  Pointers: tensors (a view passes the address of its first element), integers or None."""
+    from cotracker_amd import _lib as L
+
+    def p(x):
+        return x.data_ptr() if torch.is_tensor(x) else x
+
+    stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+    return L.load().ctk_conv2d_sh(p(in_sh), F, H, W, Cin, p(wp), p(bias), n_out, n_pad, KH, KW, stride, pad, p(out), p(zeros), stream)
+
+
 # ---- ctk_attention_ex as the C-ABI sees it (tests/test_gpu_attention_matrix.py) ----------------------------------------------------------
 def attention_raw(q, q_ld, q_bs, q_is, k, v, kv_ld, kv_bs, kv_is, out, o_ld, o_bs, o_is, nbatch, n1, n2, splits=1, partial=None,
                   o_split=False, key_mask=None, query_mask=None, batch2=None):

@@ -117,6 +117,54 @@ def test_gemm_argument_rules_without_gpu(lib):
         lib.ctk_profile_enable(0)
 
 
+def test_conv2d_sh_argument_rules_without_gpu(lib):
+    """Every rule of ctk_conv2d_sh in include/ctk.h returns its documented code before anything is launched (every check precedes
+    the first HIP call; the recorder, switched on around the calls, stays empty).  The last block is the range of a row's first
+    tap: conv_pp128_kernel packs (oy*stride - pad + 16384) into the high 15 bits and (ox*stride - pad + 16384) into the low 16
+    bits of one int, so pad <= 16384 and (Hout-1)*stride - pad <= 16383; the entry point used to take such shapes and the kernel
+    gathered other rows.  These rows only ever ran against a library that rejects them."""
+    from cotracker_amd import _lib as L
+    from ctk_support import conv_raw
+    E_NULL, E_SHAPE, E_ALIGN = -1, -2, -3
+    ok = dict(in_sh=4096, F=2, H=16, W=32, Cin=64, wp=8192, bias=12288, n_out=96, n_pad=128, KH=3, KW=3, stride=1, pad=1, out=16384,
+              zeros=20480)
+    ptrs = ("in_sh", "wp", "bias", "out", "zeros")
+    rules = {f"{p} NULL": (dict({p: None}), E_NULL) for p in ptrs}
+    rules.update({f"{p} = 0": (dict({p: 0}), E_NULL) for p in ptrs})
+    rules.update({f"{p} misaligned": (dict({p: ok[p] + 8}), E_ALIGN) for p in ptrs})
+    rules.update({
+        "Cin % 32": (dict(Cin=48), E_SHAPE), "Cin = 0": (dict(Cin=0), E_SHAPE),
+        "n_out % 32": (dict(n_out=80), E_SHAPE), "n_out = 0": (dict(n_out=0), E_SHAPE),
+        "n_pad % 128": (dict(n_pad=192), E_SHAPE), "n_pad < n_out": (dict(n_out=160), E_SHAPE),
+        "n_pad > 1024": (dict(n_out=1056, n_pad=1152), E_SHAPE),
+        "pad < 0": (dict(pad=-1), E_SHAPE),
+        "Hin > 16000": (dict(H=16001), E_SHAPE), "Win > 16000": (dict(W=16001), E_SHAPE),
+        "kernel taller than the padded input": (dict(KH=19), E_SHAPE),   # Hout = (16 + 2 - 19)/1 + 1 = 0
+        "kernel wider than the padded input": (dict(KW=35), E_SHAPE),
+        "M > 2^31 - 1": (dict(F=30000, H=100, W=100, KH=1, KW=1, pad=100), E_SHAPE),  # F*Hin*Win = 3e8, M = 30000 * 300 * 300
+        "F*Hin*Win > 2^31 - 1": (dict(F=9, H=16000, W=16000, KH=1, KW=1, stride=16000, pad=0), E_SHAPE),    # M = 9
+        "KH*KW*Cin >= 2^30": (dict(H=16000, W=16000, KH=8192, KW=8192, Cin=64), E_SHAPE),
+        # the packing's range
+        "pad > 16384": (dict(H=8, W=8, stride=40000, pad=16385), E_SHAPE),                 # Hout = Wout = 1: only the origin -pad is out
+        "pad far beyond": (dict(H=8, W=8, stride=1 << 30, pad=1 << 30), E_SHAPE),            # (Hin + 2 pad would leave the int range)
+        "last row origin = 16384": (dict(F=1, H=16000, W=32, pad=387), E_SHAPE),           # Hout = 16772: 16771 - 387
+        "the issue's example": (dict(F=1, H=16000, W=32, pad=400), E_SHAPE),               # Hin + pad - KH = 16397 > 0x3fff
+        "last row origin, stride 2": (dict(F=1, H=16000, W=32, stride=2, pad=8000), E_SHAPE),  # Hout = 15999: 31996 - 8000 = 23996
+        "last row origin, 1 x 1": (dict(F=1, H=16000, W=32, KH=1, KW=1, pad=385), E_SHAPE),    # Hout = 16770: 16769 - 385 = 16384
+    })
+    for p in ("F", "H", "W", "KH", "KW", "stride"):
+        rules[f"{p} = 0"] = (dict({p: 0}), E_SHAPE)
+        rules[f"{p} < 0"] = (dict({p: -3}), E_SHAPE)
+    assert lib.ctk_profile_enable(1) == 0
+    try:
+        for what, (change, code) in rules.items():
+            assert conv_raw(**dict(ok, **change)) == code, what
+        rows, n = (L.ProfileRow * 4)(), C.c_int(-1)
+        assert lib.ctk_profile_read(rows, 4, C.byref(n)) == 0 and n.value == 0
+    finally:
+        lib.ctk_profile_enable(0)
+
+
 def test_v2_driver_argument_validation_without_gpu(lib):
     """ctk_forward_window_v2 / ctk_v2_window_graph_create reject bad arguments before touching the device."""
     from cotracker_amd import _lib as L
