@@ -372,6 +372,28 @@ class Resection:
         ]
 
 
+class Structure3D:
+    """Holder of ctk_fit_structure_args (include/ctk.h, "fit structure"), nested like Resection.Args and for the same reason; its layout
+    is checked against the compiler by tests/test_structure_cabi.py.  The constants mirror csrc/structure_math.h."""
+
+    VIEWS_MAX, POINTS_MAX, MIN_VIEWS, ROUNDS = 256, 8192, 2, 3
+    BIT_ROUND1, BIT_ROUND2, BIT_ROUND3, BIT_NO_START, BIT_NO_PARALLAX, BIT_INTO, BIT_MINORITY = 1, 2, 4, 8, 16, 32, 64
+
+    class Args(C.Structure):
+        """ctk_fit_structure_args: history rows, four intrinsics, a pose per view, optionally the old structure and its origin -> per
+        slot a 3-D point, a label, a mean reprojection error and the counts; per group the new origin."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("into", C.c_int32), ("source_frame", C.c_int32), ("min_views", C.c_int32), ("refine", C.c_int32),
+            ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("tol", C.c_float), ("min_sin2", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("pose", _fp), ("pose_stats", _fp), ("structure_in", _fp), ("valid_in", _fp), ("origin_in", _fp),
+            ("points", _fp), ("label", _fp), ("error", _fp), ("stats", _fp), ("origin_out", _fp),
+        ]
+
+
 class IngestArgs(C.Structure):
     """ctk_ingest_args: raw frames -> the encoder's planar float32 input (include/ctk.h, "frame ingest")."""
     _fields_ = [
@@ -470,6 +492,8 @@ SYMBOLS = {
     "ctk_fit_pose": (C.c_int, [_P(Pose.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_resection_workspace_bytes": (C.c_int, [_P(Resection.Args), _P(C.c_size_t)]),
     "ctk_fit_resection": (C.c_int, [_P(Resection.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_structure_workspace_bytes": (C.c_int, [_P(Structure3D.Args), _P(C.c_size_t)]),
+    "ctk_fit_structure": (C.c_int, [_P(Structure3D.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_embed": (C.c_int, [_P(WindowArgs), _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_corr_volume": (C.c_int, [_P(WindowArgs), _fp, _fp]),

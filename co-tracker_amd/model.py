@@ -1065,6 +1065,13 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         the device, by one launch and without a wait: ops.StreamGroups.resection.  Serves a ring history and the default one alike."""
         return self._running_stream().resection(f0, F, intrinsics, structure, valid, seed_pose, **kw)
 
+    def stream_structure(self, f0, F, intrinsics, pose, **kw):
+        """One 3-D point per slot from the frames [f0, f0 + F) of the running (or just closed) stream under the poses stream_resection
+        returned for them, the old structure carried along and everything restated in the camera of one of the frames -- straight
+        from the history and logits on the device, by one launch and without a wait: ops.StreamGroups.structure.  Serves a ring
+        history and the default one alike."""
+        return self._running_stream().structure(f0, F, intrinsics, pose, **kw)
+
     # -- streaming query groups (stream_groups): the state of all groups on the device ---------------------------------------
     def _forward_stream_groups(self, video, queries, iters, chunk, space_attn):
         """One streaming call for G query groups over the one live video (see TrackerBase.__init__, stream_groups).  The chunk is

@@ -5,6 +5,7 @@ computes on the CPU and nothing falls back to PyTorch ops.
 """
 import ctypes as C
 import math
+import struct
 from collections import namedtuple
 from typing import List, Optional, Sequence
 
@@ -1490,15 +1491,32 @@ def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamenta
 # ------------------------------------------------------------------------------------------
 # fit resection (csrc/resection.hip; include/ctk.h, "fit resection")
 # ------------------------------------------------------------------------------------------
-class Structure:
+class _StructureOrigin:
+    """The fifth field of Structure, in a slot of its own so that Structure.__slots__ stays the four names its callers unpack."""
+    __slots__ = ("origin",)
+
+
+class Structure(_StructureOrigin):
     """The static points of a query set in 3-D, and the frame whose camera they are stated in: points float32 [N,3] on the device in
     that camera's coordinates and in the baseline of the pair they were reconstructed from as the unit, valid int8 [N] (nonzero: the
     point is in the structure), the anchor (FieldAnchor) pinned on that frame, and the intrinsics (fx, fy, cx, cy) they were made
-    with.  What reconstruct() of the online predictor returns and localize() takes."""
+    with.  What reconstruct() of the online predictor returns and localize() takes.  origin: float32 [3,4] on the device, the pose of
+    this structure's camera against the camera of the first structure it was extended from (extend() of the online predictor), or
+    None: the identity; compose_pose(pose, origin) states a pose against this structure in that first camera's coordinates."""
     __slots__ = ("points", "valid", "anchor", "intrinsics")
 
-    def __init__(self, points: torch.Tensor, valid: torch.Tensor, anchor: FieldAnchor, intrinsics):
+    def __init__(self, points: torch.Tensor, valid: torch.Tensor, anchor: FieldAnchor, intrinsics, origin: Optional[torch.Tensor] = None):
         self.points, self.valid, self.anchor, self.intrinsics = points, valid, anchor, tuple(float(v) for v in intrinsics)
+        self.origin = origin
+
+
+def compose_pose(pose: torch.Tensor, origin: Optional[torch.Tensor]) -> torch.Tensor:
+    """A pose [...,3,4] = (R | t) against a structure whose camera stands at origin [...,3,4] = (R_o | t_o) against a first camera ->
+    the pose against that first camera, (R R_o | R t_o + t) (elementwise torch, no wait).  origin None: the pose itself."""
+    if origin is None:
+        return pose
+    R, t = pose[..., :3], pose[..., 3:]
+    return torch.cat([R @ origin[..., :3], R @ origin[..., 3:] + t], dim=-1)
 
 
 def structure_from_pose(tracks_row: torch.Tensor, intrinsics, depth: torch.Tensor, label: torch.Tensor, *, max_depth: float = 64.0,
@@ -1588,6 +1606,120 @@ def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, struc
         raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
     _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
     return _resection_launch(a, dev, out, who)
+
+
+# ------------------------------------------------------------------------------------------
+# fit structure (csrc/structure.hip; include/ctk.h, "fit structure")
+# ------------------------------------------------------------------------------------------
+def min_sin2_of(min_parallax: float) -> float:
+    """min_parallax in degrees -> the squared sine the kernel compares with (the float32 of sin^2), in (0, 1]."""
+    deg = float(min_parallax)
+    if not (math.isfinite(deg) and 0.0 < deg <= 90.0):
+        raise ValueError("min_parallax must lie in (0, 90] degrees")
+    s2 = struct.unpack("f", struct.pack("f", math.sin(math.radians(deg)) ** 2))[0]
+    if not 0.0 < s2 <= 1.0:
+        raise ValueError("min_parallax is too small: its squared sine is no positive float32")
+    return s2
+
+
+def _structure_rules(a, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax, refine,
+                     G: int, F: int, N: int, device, who: str) -> None:
+    """The camera, the views, the old structure and the fit of ctk_fit_structure_args; G, F, N: what they must match.  Nothing here
+    waits on the device."""
+    min_views, tol, into = int(min_views), float(tol), -1 if into is None else int(into)
+    if not 1 <= F <= L.Structure3D.VIEWS_MAX:
+        raise ValueError(f"{who}: between 1 and {L.Structure3D.VIEWS_MAX} frames are views, got {F}")
+    if not L.Structure3D.MIN_VIEWS <= min_views <= L.Structure3D.VIEWS_MAX:
+        raise ValueError(f"{who}: min_views must lie in {L.Structure3D.MIN_VIEWS}..{L.Structure3D.VIEWS_MAX}")
+    if not (math.isfinite(tol) and 0.0 < tol <= 3.0e38):
+        raise ValueError(f"{who}: tol must be finite and > 0 (raw-video pixels)")
+    if not -1 <= into < F:
+        raise ValueError(f"{who}: into must be one of the {F} views, or None")
+    if int(source_frame) < 0:
+        raise ValueError(f"{who}: source_frame must be a frame >= 0")
+    try:
+        a.min_sin2 = min_sin2_of(min_parallax)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+    if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
+        raise ValueError(f"{who}: intrinsics must be four Python floats (fx, fy, cx, cy) in raw-video pixels")
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
+    a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
+    a.into, a.source_frame, a.min_views, a.refine, a.tol, a.reserved = into, int(source_frame), min_views, 1 if refine else 0, tol, 0
+
+    def f32(x, shape, name, what=""):
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.device == device and tuple(x.shape) == shape and
+                x.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor {list(shape)} on {device}{what}")
+        return _ptr(x)
+    a.pose = f32(pose, (G, F, 3, 4), "pose", " (fit_resection's)")
+    a.pose_stats = None
+    if pose_stats is not None:
+        if not (isinstance(pose_stats, torch.Tensor) and pose_stats.dtype == torch.int32 and pose_stats.device == device and
+                tuple(pose_stats.shape) == (G, F, 4) and pose_stats.is_contiguous()):
+            raise ValueError(f"{who}: pose_stats must be a contiguous int32 tensor [{G},{F},4] on {device} (fit_resection's)")
+        a.pose_stats = _ptr(pose_stats)
+    if (structure is None) != (valid is None):
+        raise ValueError(f"{who}: structure and valid come both or neither")
+    a.structure_in = a.valid_in = None
+    if structure is not None:
+        a.structure_in = f32(structure, (G, N, 3), "structure")
+        if not (isinstance(valid, torch.Tensor) and valid.dtype in (torch.int8, torch.uint8, torch.bool) and valid.device == device and
+                tuple(valid.shape) == (G, N) and valid.is_contiguous()):
+            raise ValueError(f"{who}: valid must be a contiguous int8, uint8 or bool tensor [{G},{N}] on {device}")
+        a.valid_in = _ptr(valid)
+    a.origin_in = None if origin is None else f32(origin, (G, 3, 4), "origin")
+
+
+def _structure_launch(a, device, out, who: str):
+    """Allocates (or checks) the five outputs of ctk_fit_structure for the G and N_out of `a`, then the launch."""
+    out = _out_tuple(out, [("points", torch.float32, (a.G, a.N_out, 3)), ("label", torch.int8, (a.G, a.N_out)),
+                           ("error", torch.float32, (a.G, a.N_out)), ("stats", torch.int32, (a.G, a.N_out, 4)),
+                           ("origin", torch.float32, (a.G, 3, 4))], device, who)
+    a.points, a.label, a.error, a.stats, a.origin_out = (_ptr(t_) for t_ in out)
+    ws = _scratch("motion", _query_bytes("ctk_fit_structure_workspace_bytes", C.byref(a)), device)
+    L.check(L.load().ctk_fit_structure(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_structure")
+    return out
+
+
+def fit_structure(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
+                  structure: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, source_frame: int = 0,
+                  origin: Optional[torch.Tensor] = None, into: Optional[int] = None, tol: float = 2.0, min_views: int = 3,
+                  min_parallax: float = 1.0, refine: bool = False, first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """Points added to a 3-D structure: every point tracked on several LOCALISED frames becomes a 3-D point in the structure's unit, by
+    one launch and without a wait (ctk_fit_structure; include/ctk.h and csrc/structure_math.h have the rules).  Works on any result of
+    any predictor here, offline ones included.
+
+    tracks, visible, first_row, scale   as in fit_resection; all T <= 256 frames are views.
+    intrinsics   (fx, fy, cx, cy), four Python floats: one pinhole camera in the pixels of tracks * scale.
+    pose, pose_stats   float32 [G,T,3,4] / [T,3,4] and int32 [G,T,4] / [T,4] as fit_resection returned them for these frames; a frame
+             whose pose is not finite, is no rotation, or (with pose_stats) had no fit is no view.  Only read.
+    structure, valid, source_frame   the old structure (float32 [G,N,3] / [N,3], int8 / uint8 / bool [G,N] / [N]) and the frame it is
+             stated in, or neither: its points are carried along (label 2) unless first_row says the slot was reassigned after
+             source_frame; refine: they are triangulated too, and a new point that is accepted wins.
+    origin   float32 [G,3,4] / [3,4]: the old structure's own origin (None: the identity).
+    into     a view k (a row of tracks): every point that is written is stated in the camera of that frame, and the returned origin is
+             (R_k R_o | R_k t_o + t_k); None: points stay in the coordinates the poses map from, the origin is copied.
+    Per point: a linear midpoint start over its observations, three Gauss-Newton rounds on the reprojection error with gates of 4, 2
+    and 1 x tol pixels, then accepted when at least min_views (2..256) views and at least half of its observations lie within tol
+    and the first of them shows a parallax of at least min_parallax degrees against another.  Returns (points float32 [G,N,3], zero where label < 1; label int8 [G,N]: -1 fewer
+    than two observations and not carried, 0 rejected, 1 accepted, 2 carried; error float32 [G,N]: the mean squared reprojection error
+    over the counted views in px^2, -1 where the label is not 1; stats int32 [G,N,4] = (observations, counted views, the first
+    counted view or -1, bits 0 / 1 / 2: round 1 / 2 / 3 fell back, bit 3: no start, bit 4: no parallax, bit 5: the `into` view is no
+    view: no structure at all, bit 6: fewer than half of the observations are counted); origin float32 [G,3,4]); `out`: such a tuple to write into.  No bundle adjustment; the parallax test
+    looks at the first counted view against the others only; one pinhole camera without distortion."""
+    who = "fit_structure"
+    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Structure3D.POINTS_MAX)
+    a = L.Structure3D.Args()
+
+    def axis(x, dims):
+        return x[None] if isinstance(x, torch.Tensor) and x.dim() == dims else x
+    _structure_rules(a, intrinsics, axis(pose, 3), axis(pose_stats, 2), axis(structure, 2), axis(valid, 1), source_frame, axis(origin, 2), into,
+                     tol, min_views, min_parallax, refine, G, T, N, dev, who)
+    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T, f0=0, F=T, scale=scale)
+    return _structure_launch(a, dev, out, who)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2403,6 +2535,30 @@ class StreamGroups:
         self._held(who, f0, F_, back=a.lag, to=a.to)  # (the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
         self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
         return _resection_launch(a, dev, out, who)
+
+    def structure(self, f0: int, F: int, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
+                  structure: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, source_frame: int = 0,
+                  origin: Optional[torch.Tensor] = None, into: Optional[int] = None, N_out: Optional[int] = None, scale=(1.0, 1.0),
+                  thresh: float = 0.6, first_row: Optional[torch.Tensor] = None, tol: float = 2.0, min_views: int = 3,
+                  min_parallax: float = 1.0, refine: bool = False, group: Optional[int] = None, out=None):
+        """One 3-D point per slot from the frames f0 .. f0 + F - 1 (F <= 256 views) under pose float32 [G,F,3,4] and pose_stats int32
+        [G,F,4] (resection()'s for the same frames; only read), over the first N_out points of every group (or of `group` alone),
+        straight from the stream's own history and logits by the one launch of ctk_fit_structure: fit_structure has the picture.
+        structure float32 [G,N,3], valid int8 / uint8 / bool [G,N] and origin float32 [G,3,4] (of the groups asked for; only read) are
+        the old structure, stated in frame source_frame; into: a view 0 .. F - 1 or None.  intrinsics: (fx, fy, cx, cy), four Python
+        floats, in the pixels of history coords * scale.  Every frame that is read must be among the committed ones the history still
+        holds: ValueError otherwise.  -> (points [G,N_out,3], label [G,N_out], error [G,N_out], stats [G,N_out,4], origin [G,3,4]) on
+        the device.  No wait."""
+        who = "structure"
+        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Structure3D.POINTS_MAX)
+        dev = self.queries.device
+        a = L.Structure3D.Args()
+        f0, F_ = int(f0), int(F)
+        _structure_rules(a, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax, refine,
+                         G, F_, self.N, dev, who)
+        self._held(who, f0, F_)
+        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
+        return _structure_launch(a, dev, out, who)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()

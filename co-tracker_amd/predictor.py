@@ -857,9 +857,9 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         ops.Structure: points float32 [N_model,3] on the device in the camera coordinates of `frame`, valid int8 [N_model] (labelled
         static, both depths finite and > 0, no deeper than max_depth), the anchor pinned on `frame`, the intrinsics; localize() takes
         it.  The unit is the baseline of this pair, for as long as the structure is used.  A structure lives as long as enough of its
-        points stay tracked: points that replenish() adds later are not in it, and triangulating new points from two localised frames
-        is the next step and is not built.  One pinhole camera, no lens distortion; the structure is never refined (no bundle
-        adjustment); without parallax on the pair (a camera that only turns or stands, a plane) there is no structure: valid is all
+        points stay tracked: points that replenish() adds later are not in it until extend() puts them there (triangulating new points
+        from localised frames and restating the structure on a newer frame; refining what it holds is not built).  One pinhole camera,
+        no lens distortion; the structure is never refined (no bundle adjustment); without parallax on the pair (a camera that only turns or stands, a plane) there is no structure: valid is all
         zero."""
         from . import ops
         who = "reconstruct"
@@ -897,7 +897,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         back, bit 2: an entry was left out, bit 3: more than 4096 points, bit 5: the frame is the structure's own).  The camera's
         position in the structure's coordinates is -R^T t.  The limits are reconstruct()'s: the unit is the baseline of its pair; the
         structure lives as long as enough of its points stay tracked (stats[:, 1] tells), points added later by replenish() are not in
-        it, and triangulating new points from two localised frames is the next step and is not built; the seed comes from the
+        it until extend() puts them there (triangulating new points from localised frames; when stats[:, 1] falls, extend in time --
+        refining the structure is not built); the seed comes from the
         two-view pose, so a frame without parallax against the anchor that is not the anchor itself (a camera that only turned)
         relies on the fixed candidates (R0, 0) and (I, 0) -- there is no minimal P3P solver; one pinhole camera, no lens distortion;
         no bundle adjustment.  ValueError for frames not yet tracked; NotImplementedError on a v2 predictor."""
@@ -916,6 +917,63 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         pose, label, error, stats = self.model.stream_resection(first_frame, n, cam, structure.points[None], mask, seeds, tol=tol,
                                                                 hypotheses=hypotheses, min_points=min_points, seed=seed, **source)
         return pose[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
+    def extend(self, structure, frame=None, n=None, first_frame=None, tol=2.0, min_views=3, min_parallax=1.0, refine=False, poses=None,
+               **localize_kw):
+        """Not in the reference: points added to an ops.Structure, and the structure restated on a newer frame -- the keyframe step
+        that lets a trajectory go on after the points it started with have left the picture.  Every user-visible point of the
+        structure's query set that is tracked on at least min_views of the n frames from first_frame on (default: the frames of the
+        window just tracked; at most 256) becomes a 3-D point in the structure's unit, the old points are carried along, and all of
+        them are stated in the camera of `frame` (default: the newest tracked frame; it must lie inside the n frames), on which the
+        new anchor is pinned: slots that replenish() filled after the old anchor was taken have real positions on the new one, so
+        localize() can fit on them.  FIVE launches and no wait; nothing is re-captured or re-allocated: localize() over the n frames
+        (three; tol is its tolerance too, localize_kw are its other options; skipped when poses = (pose, stats) of such a call is
+        given), one launch of ctk_fit_structure (include/ctk.h, "fit structure": a linear midpoint start, three Gauss-Newton rounds on
+        the reprojection error gated at 4, 2 and 1 x tol pixels, at least min_views views and at least half of the point's
+        observations within tol, a parallax of at least min_parallax degrees;
+        refine: the old points are triangulated too and an accepted new point wins), and pin(frame).  Returns a new ops.Structure:
+        points float32 [N_model,3] in the camera coordinates of `frame`, valid int8 [N_model] (1: carried or newly accepted), the
+        anchor pinned on `frame`, the intrinsics, and origin float32 [3,4]: the pose of `frame` against the camera of the first
+        structure of the chain, so that world_pose(structure, pose) of every later localize() is in one unit and one world.  When
+        `frame` could not be localised there is no structure: valid is all zero, as after a reconstruct() without parallax, and the
+        caller keeps the old one.  Limits: a point stays in the structure's fits only while it is visible on the keyframe; poses chain
+        once per keyframe, not per frame, and each link carries the error of one localize(); no bundle adjustment -- neither the poses
+        nor the carried points are refined; the parallax rule looks at the first counted view against the others only; a frame still
+        inside the window being tracked is refined by the next step (pin()'s limit); one pinhole camera, no lens distortion.
+        ValueError for frames not yet tracked or a `frame` outside the n frames; NotImplementedError on a v2 predictor."""
+        from . import ops
+        who = "extend"
+        gs, scale = self._running(who)
+        if not isinstance(structure, ops.Structure):
+            raise ValueError(f"{who}: structure must be an ops.Structure (reconstruct)")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        frame = gs.committed - 1 if frame is None else int(frame)
+        if not first_frame <= frame < first_frame + n:
+            raise ValueError(f"{who}: frame {frame} must lie inside the frames [{first_frame}, {first_frame + n}) that are triangulated over")
+        if poses is None:
+            pose, _, _, stats = self.localize(structure, n, first_frame, tol=tol, **localize_kw)
+        else:
+            pose, stats = poses
+        anchor, cam = structure.anchor, structure.intrinsics
+        pts, label, _, _, origin = self.model.stream_structure(
+            first_frame, n, cam, pose[None], pose_stats=stats[None], structure=structure.points[None], valid=structure.valid[None],
+            source_frame=anchor.frame, origin=None if structure.origin is None else structure.origin[None], into=frame - first_frame,
+            N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(), tol=tol, min_views=min_views,
+            min_parallax=min_parallax, refine=refine, group=anchor.group)
+        pinned = self.pin(frame, anchor.group)
+        points = torch.zeros((gs.N, 3), dtype=torch.float32, device=pts.device)
+        valid = torch.zeros((gs.N,), dtype=torch.int8, device=pts.device)
+        points[:self.N], valid[:self.N] = pts[0], (label[0] >= 1).to(torch.int8)
+        return ops.Structure(points, valid, pinned, cam, origin[0])
+
+    def world_pose(self, structure, pose):
+        """A pose [...,3,4] that localize() gave against `structure` -> the same pose against the camera of the first structure of its
+        chain of extend() calls: ops.compose_pose(pose, structure.origin) (elementwise torch, no wait)."""
+        from . import ops
+        if not isinstance(structure, ops.Structure):
+            raise ValueError("world_pose: structure must be an ops.Structure (reconstruct, extend)")
+        return ops.compose_pose(pose, structure.origin)
 
     @torch.no_grad()
     def split_scene(self, frame=None, lag=8, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16, seed=0, mask=None):

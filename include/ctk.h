@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_structure and ctk_fit_structure_workspace_bytes on the
+ *       new struct ctk_fit_structure_args: per slot, the tracked positions on up to 256 localised frames become a 3-D point in the
+ *       structure's unit (a linear midpoint start, three gated Gauss-Newton rounds on the reprojection error, a parallax test; plain
+ *       double sums, one thread per slot in ascending view order; csrc/structure_math.h); the old structure is carried along and
+ *       everything is restated in the camera of one of the frames, with the pose chain kept in `origin`; one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_resection and ctk_fit_resection_workspace_bytes on the
  *       new struct ctk_fit_resection_args: per frame, the camera's pose against a fixed 3-D structure in that structure's unit and
  *       coordinates (one-scalar candidates on a seed pose scored by integer counts of reprojection inliers, three order-independent
@@ -1295,7 +1300,7 @@ int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_b
  * CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the struct (it only looks whether an anchor is given).
  *
  * Known limits.  The unit is the structure's (the baseline of the pair it was reconstructed from).  A structure lives as long as
- * enough of its points stay tracked; nothing adds points to it.  The candidates come from the seed: a seed whose rotation is far off
+ * enough of its points stay tracked; ctk_fit_structure (below) adds points to it.  The candidates come from the seed: a seed whose rotation is far off
  * finds no fit (no minimal P3P solver).  One pinhole camera, no lens distortion.  No bundle adjustment: the structure is not refined. */
 typedef struct ctk_fit_resection_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
@@ -1328,6 +1333,88 @@ typedef struct ctk_fit_resection_args {
 } ctk_fit_resection_args;
 int ctk_fit_resection_workspace_bytes(const ctk_fit_resection_args* a, size_t* out_bytes);
 int ctk_fit_resection(const ctk_fit_resection_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit structure: points added to a 3-D structure, and the structure restated on a newer frame ---------------------------------------
+ * ctk_fit_resection places cameras against a structure that only shrinks.  ctk_fit_structure turns "tracked on several localised
+ * frames" into "a 3-D point in the structure's unit": per group g and slot n < N_out, the positions on the frames f0 + j, 0 <= j < F
+ * (the VIEWS), under the poses ctk_fit_resection gave for them, are triangulated.  The rules are stated once in csrc/structure_math.h.
+ *   views      pose float32 [G,F,3,4] (X_f = R X_source + t), optionally pose_stats int32 [G,F,4] (ctk_fit_resection's).  View j counts
+ *              iff its twelve floats are finite, R passes the four polar steps and ctk_fit_pose's validity check, and pose_stats is
+ *              NULL or pose_stats[g,j,2] >= 0.  A view that fails is dropped (it does not become the identity).  c = -R^T t.
+ *   observation  slot n on view j: the view counts, f0 + j >= first_row[g,n] (when given), both coordinates quantise (1/16 pixel),
+ *              the slot is visible there (`visible` or the logits with thresh).  One frame: no source frame, no pair rule.  m = their
+ *              number; y = the ray of the position, d = R^T y.
+ *   start      the linear midpoint solution: A = sum (I - d d^T / (d.d)), b = sum (I - d d^T / (d.d)) c, X = adj(A) b / det(A) by the
+ *              symmetric 3 x 3 cofactor form with one division.  No start (stats[3] bit 3) when m < 2, det is not > 0 or not finite,
+ *              or X is not finite.
+ *   rounds     three Gauss-Newton rounds on the reprojection error; round r uses the observations with e <= (g_r tol)^2, g = 4, 2, 1,
+ *              so that one bad view of a track drops out.  A round with fewer than min_views observations, a failed solve or an X
+ *              that stops being finite keeps its X (stats[3] bits 0 / 1 / 2 for rounds 1 / 2 / 3).
+ *   accept     the counted views are those within tol under the final X (behind a camera the error is +inf).  With a the first of
+ *              them and w_j = X - c_j: parallax holds iff |w_a x w_j|^2 >= |w_a|^2 |w_j|^2 min_sin2 for some counted j (one
+ *              comparison, no root, no division; stats[3] bit 4 where it does not).  Accepted iff counted >= min_views (2..256),
+ *              at least half of the slot's observations are counted (2 counted >= m; stats[3] bit 6 where not: a point that moves by
+ *              itself finds min_views neighbouring views that agree), parallax holds and the written point is finite.
+ *   into       -1, or a view k in [0, F): every written point is R_k X + t_k, so the new structure is stated in the camera of frame
+ *              f0 + k.  Where view k does not count there is no structure: every point zero, label 0 for every slot with an
+ *              observation or in the old structure and -1 for every other, stats[3] bit 5 in every slot.
+ *   carry      structure_in float32 [G,N,3] and valid_in int8 [G,N], both or neither: a slot is carried when its byte is nonzero, its
+ *              floats are finite, first_row[g,n] <= source_frame (when first_row is given: a released and reassigned slot is not
+ *              carried) and its point through the into pose is finite: label 2.  refine = 0: carried slots are not triangulated
+ *              (stats (0, 0, -1, 0)).  refine = 1: they are; accepted, the new point wins (label 1), rejected, the old one stays (2).
+ *   origin     origin_in float32 [G,3,4] or NULL (the identity); origin_out float32 [G,3,4] or NULL = (R_k R_o | R_k t_o + t_k): the
+ *              pose of the new structure's camera against the first one's, so that compose(pose, origin) of every later pose is in
+ *              one world.  A copy of origin_in where into < 0 or view k does not count.
+ *   outputs    points float32 [G,N_out,3], zero where label < 1; label int8 [G,N_out]: -1 fewer than 2 observations and not carried,
+ *              0 triangulated and rejected, 1 triangulated and accepted, 2 carried; error float32 [G,N_out]: the mean squared
+ *              reprojection error over the counted views in px^2 (one division), -1 where the label is not 1; stats int32 [G,N_out,4]
+ *              = (m, counted views, the first counted view or -1, bits).  Every element is written by one plain store.
+ * One launch on `stream`: one thread per slot, workgroups of 64 threads (one wave), grid (ceil(N_out / 64), G); the views are
+ * validated once per workgroup into 30.25 KiB of LDS; every thread walks the views in ascending order five times (the start, three
+ * rounds, the classification), reading the positions again each time; plain double sums, deterministic because one thread owns a
+ * slot.  No atomics, no host synchronisation, capture-safe; every input is only read.  The workspace query answers 0 and `workspace`
+ * may be NULL.  Before any launch: NULL a, hist_coords, pose, points, label, error or stats, `visible` NULL with hist_vis or hist_conf
+ * NULL, one of structure_in / valid_in without the other: CTK_E_NULL; G, N, N_out (<= 8192, <= N), R < 1, f0 < 0, F outside 1..256 or
+ * > R, into outside -1..F-1, source_frame < 0, min_views outside 2..256, refine outside 0..1, tol not finite or not > 0, min_sin2 not
+ * in (0, 1], the camera and the scale as ctk_fit_resection: CTK_E_SHAPE; hist_coords not 8-byte aligned, a float or int32 tensor not
+ * 4-byte aligned: CTK_E_ALIGN.  The query checks the same shapes.
+ *
+ * Known limits.  A point stays in a structure's fits only while it is visible on the frame the structure is stated in.  Poses
+ * chain once per restatement, not per frame.  No bundle adjustment: neither the poses nor the carried points are refined.  The
+ * parallax test looks at the first counted view against the others only.  The start is not robust: the gates drop one wrong view of a
+ * few tol, a grossly wrong one (tens of tol) rejects the slot.  One pinhole camera, no lens distortion. */
+typedef struct ctk_fit_structure_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* view j is frame f0 + j, 0 <= j < F <= 256                         */
+  int32_t into;               /* the view whose camera the outputs are stated in, or -1            */
+  int32_t source_frame;       /* the frame structure_in is stated in (against first_row)           */
+  int32_t min_views;          /* an accepted point needs this many views within tol, 2..256        */
+  int32_t refine;             /* 1: carried slots are triangulated too                             */
+  float fx, fy, cx, cy;       /* the pinhole camera, raw-video pixels                              */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  float tol;                  /* reprojection tolerance in raw-video pixels, finite and > 0        */
+  float min_sin2;             /* the squared sine of the smallest parallax angle, in (0, 1]        */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* pose;          /* [G,F,3,4]; read only                                              */
+  const int32_t* pose_stats;  /* [G,F,4], or NULL; read only                                       */
+  const float* structure_in;  /* [G,N,3], or NULL; read only                                       */
+  const int8_t* valid_in;     /* [G,N], with structure_in; read only                               */
+  const float* origin_in;     /* [G,3,4], or NULL: the identity; read only                         */
+  float* points;              /* [G,N_out,3] */
+  int8_t* label;              /* [G,N_out] */
+  float* error;               /* [G,N_out] */
+  int32_t* stats;             /* [G,N_out,4] */
+  float* origin_out;          /* [G,3,4], or NULL */
+} ctk_fit_structure_args;
+int ctk_fit_structure_workspace_bytes(const ctk_fit_structure_args* a, size_t* out_bytes);
+int ctk_fit_structure(const ctk_fit_structure_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Op A: corr_embed  (cotracker3_online.py:190-210; get_correlation_feat :130-143,
  *      einsum :202-204, corr_mlp :205) -> x[:, 0:1024]                                */
