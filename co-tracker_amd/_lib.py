@@ -500,6 +500,9 @@ SYMBOLS = {
     "ctk_corr_volume_sh_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),
     "ctk_corr_volume_sh": (C.c_int, [_P(WindowArgs), _fp, _fp, C.c_size_t, _fp]),
     "ctk_assemble_tokens": (C.c_int, [_P(WindowArgs), _fp, C.c_int32, _fp]),
+    "ctk_assemble_tokens_batch": (C.c_int, [_P(WindowBatch), _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+    "ctk_virtual_init": (C.c_int, [_fp, C.c_int32, C.c_int32, _fp, _fp]),
+    "ctk_heads_update": (C.c_int, [_P(WindowBatch), _fp, _fp, _fp, _fp, _fp]),
     "ctk_update_former_workspace_bytes": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_size_t)]),
     "ctk_update_former": (C.c_int, [C.c_int32, C.c_int32, _fp, _P(ModelWeights), _fp, _fp, C.c_size_t, _fp]),
     "ctk_update_former_ex": (C.c_int, [C.c_int32, C.c_int32, _fp, C.c_int32, _P(FormerWeights), _fp, _fp, _fp, C.c_size_t, _fp]),
@@ -530,6 +533,7 @@ SYMBOLS = {
     "ctk_pack_weight_bytes": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_size_t)]),
     "ctk_pack_weight": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, _fp, _fp]),
     "ctk_layernorm": (C.c_int, [_fp, _fp, C.c_int64, _fp, _fp, C.c_float, C.c_int32, _fp]),
+    "ctk_layernorm_dual": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp, _fp, C.c_float, C.c_float, C.c_int32, _fp]),
     "ctk_split_rows": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, _fp]),
     "ctk_attention": (C.c_int, [_P(AttnArgs), _fp]),
     "ctk_attention_ex": (C.c_int, [_P(AttnArgs), _P(AttnBatch2), _fp]),

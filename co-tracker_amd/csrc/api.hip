@@ -362,6 +362,12 @@ int check_former(const FormerRef& fr) {
     CTK_TRY(check_block(fr.virtual_self[i], false));
     CTK_TRY(check_block(fr.point2virtual[i], true));
   }
+  // what the row kernels read with 16-byte loads (rowops.hip): the virtual tokens and norm_context's gamma / beta.  (The Linears'
+  // weights and biases are checked by ctk_gemm.)  Here, so that a window refuses them before an iteration has updated anything.
+  if (!ctk_aligned16(fr.virtual_tokens)) return CTK_E_ALIGN;
+  for (int i = 0; i < fr.depth; ++i)
+    for (const ctk_block_weights* b : {&fr.virtual2point[i], &fr.point2virtual[i]})
+      if (!ctk_aligned16(b->ctx_gamma) || !ctk_aligned16(b->ctx_beta)) return CTK_E_ALIGN;
   return CTK_OK;
 }
 
@@ -376,7 +382,8 @@ int check_weights(const ctk_model_weights* w, bool window = false) {
   } else if (split_mode(w) != (w->corr_fc1_p && w->corr_fc2_p)) {
     return CTK_E_NULL;  // (corr_mlp belongs to the same pipeline)
   }
-  return check_former(former_of(w));
+  CTK_TRY(check_former(former_of(w)));
+  return ctk_aligned16(w->head_w) ? CTK_OK : CTK_E_ALIGN;  // heads_kernel holds the 4 x 384 weights as f32x4
 }
 
 // N = point tracks of ALL videos of the call (the per-frame bias is indexed by row % S: rows are track-major in every video)
@@ -663,7 +670,7 @@ extern "C" int ctk_update_former(int32_t S, int32_t N, const float* x, const ctk
   if (!x || !delta || !workspace) return CTK_E_NULL;
   if (S <= 0 || N <= 0) return CTK_E_SHAPE;
   CTK_TRY(check_weights(w));
-  if (!ctk_aligned16(workspace)) return CTK_E_ALIGN;
+  if (!ctk_aligned16(workspace) || !ctk_aligned16(delta)) return CTK_E_ALIGN;  // (delta: one 16-byte store per row)
   const UfWs ws = carve_uf(S, N, workspace);
   if (ws.bytes > workspace_bytes) return CTK_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -237,11 +237,13 @@ __global__ __launch_bounds__(256) void heads_kernel(const float* tokens, const f
 
 }  // namespace
 
+// Every kernel above moves f32x4 / f16x8: the launchers refuse a pointer that is not 16-byte aligned before any HIP call.
 extern "C" int ctk_layernorm(const float* x, void* y, int64_t R, const float* gamma, const float* beta, float eps,
                              int32_t out_split, void* stream) {
   if (!x || !y) return CTK_E_NULL;
-  if (R <= 0) return CTK_E_SHAPE;
   if ((gamma == nullptr) != (beta == nullptr)) return CTK_E_NULL;
+  if (R <= 0) return CTK_E_SHAPE;
+  if (!ctk_aligned16(x) || !ctk_aligned16(y) || !ctk_aligned16(gamma) || !ctk_aligned16(beta)) return CTK_E_ALIGN;
   CtkProfScope ps("layernorm", 8.0 * R * CTK_HID, 8.0 * R * CTK_HID, static_cast<hipStream_t>(stream));
   hipLaunchKernelGGL(layernorm_kernel<false>, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
                      static_cast<float*>(y), (long)R, gamma, beta, eps, out_split, static_cast<float*>(nullptr), 0.0f);
@@ -253,8 +255,9 @@ extern "C" int ctk_layernorm(const float* x, void* y, int64_t R, const float* ga
 int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, const float* beta, float eps, void* y2, float eps2,
                           int out_split, hipStream_t s) {
   if (!x || !y || !y2) return CTK_E_NULL;
-  if (R <= 0) return CTK_E_SHAPE;
   if ((gamma == nullptr) != (beta == nullptr)) return CTK_E_NULL;
+  if (R <= 0) return CTK_E_SHAPE;
+  if (!ctk_aligned16(x) || !ctk_aligned16(y) || !ctk_aligned16(y2) || !ctk_aligned16(gamma) || !ctk_aligned16(beta)) return CTK_E_ALIGN;
   CtkProfScope ps("layernorm", 12.0 * R * CTK_HID, 12.0 * R * CTK_HID, s);
   hipLaunchKernelGGL(layernorm_kernel<true>, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, s, x, static_cast<float*>(y), R, gamma, beta, eps,
                      out_split, static_cast<float*>(y2), eps2);
@@ -262,11 +265,17 @@ int ctk_launch_layernorm2(const float* x, void* y, long R, const float* gamma, c
   return CTK_OK;
 }
 
+extern "C" int ctk_layernorm_dual(const float* x, void* y, void* y2, int64_t R, const float* gamma, const float* beta, float eps,
+                                  float eps2, int32_t out_split, void* stream) {
+  return ctk_launch_layernorm2(x, y, (long)R, gamma, beta, eps, y2, eps2, out_split, static_cast<hipStream_t>(stream));
+}
+
 // the 96 small-feature columns into columns [base, base + 96) of rows `ld` columns apart (both multiples of 32)
 int ctk_launch_assemble(const ctk_window_args* a, void* x, int x_split, int ld, int base, hipStream_t s) {
   if (!a || !a->coords || !a->vis || !a->conf || !x) return CTK_E_NULL;
   if (a->S <= 0 || a->N <= 0 || !(a->scale_x > 0.f) || !(a->scale_y > 0.f)) return CTK_E_SHAPE;
   if ((ld % 32) || (base % 32) || base < 0 || base + 8 * ASM_G8 > ld) return CTK_E_SHAPE;
+  if (!ctk_aligned16(x)) return CTK_E_ALIGN;
   const long total = (long)a->S * a->N * ASM_G8;  // threads: 8 columns each
   CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, s);
   hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a->coords, a->vis, a->conf, a->S, a->N,
@@ -280,6 +289,9 @@ extern "C" int ctk_assemble_tokens(const ctk_window_args* a, void* x, int32_t x_
 }
 
 int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream_t s) {
+  if (!vt || !dst) return CTK_E_NULL;
+  if (S <= 0 || B <= 0 || B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  if (!ctk_aligned16(vt) || !ctk_aligned16(dst)) return CTK_E_ALIGN;
   const long total = (long)B * CTK_VIRT * S * (CTK_HID / 4);
   CtkProfScope ps("virtual_init", 0.0, 16.0 * total, s);
   hipLaunchKernelGGL(virtual_init_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, vt, S, dst, B * CTK_VIRT);
@@ -287,8 +299,17 @@ int ctk_launch_virtual_init(const float* vt, int S, float* dst, int B, hipStream
   return CTK_OK;
 }
 
+extern "C" int ctk_virtual_init(const float* virtual_tokens, int32_t S, int32_t B, float* dst, void* stream) {
+  return ctk_launch_virtual_init(virtual_tokens, S, dst, B, static_cast<hipStream_t>(stream));
+}
+
+// delta and / or the state (all three or none); hb is read with 4-byte loads
 int ctk_launch_heads(const float* tokens, const float* hw, const float* hb, int S, int N, float* delta, float* coords,
                      float* vis, float* conf, hipStream_t s) {
+  if (!tokens || !hw || !hb) return CTK_E_NULL;
+  if ((coords || vis || conf) ? (!coords || !vis || !conf) : !delta) return CTK_E_NULL;
+  if (S <= 0 || N <= 0) return CTK_E_SHAPE;
+  if (!ctk_aligned16(tokens) || !ctk_aligned16(hw) || !ctk_aligned16(delta)) return CTK_E_ALIGN;
   const long rows = (long)S * N;
   CtkProfScope ps("heads_update", 8.0 * rows * CTK_HID, 4.0 * rows * CTK_HID, s);
   const long want = (rows + 7) / 8;  // one row per half-wave at most; 2048 workgroups walk over the rest
@@ -304,6 +325,9 @@ int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, floa
   if (!x) return CTK_E_NULL;
   if (B <= 0 || B > CTK_MAX_BATCH || S <= 0 || N <= 0 || !(scale_x > 0.f) || !(scale_y > 0.f)) return CTK_E_SHAPE;
   if ((ld % 32) || (base % 32) || base < 0 || base + 8 * ASM_G8 > ld) return CTK_E_SHAPE;
+  for (int b = 0; b < B; ++b)
+    if (!st.coords[b] || !st.vis[b] || !st.conf[b]) return CTK_E_NULL;
+  if (!ctk_aligned16(x)) return CTK_E_ALIGN;
   const long total = (long)B * S * N * ASM_G8;
   CtkProfScope ps("assemble_tokens", 0.0, 32.0 * total, s);
   hipLaunchKernelGGL(assemble_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, st, B, S, N, scale_x, scale_y,
@@ -314,7 +338,11 @@ int ctk_launch_assemble_batch(const CtkBatchState& st, int B, int S, int N, floa
 
 int ctk_launch_heads_batch(const float* tokens, const float* hw, const float* hb, const CtkBatchState& st, int B, int S, int N,
                            hipStream_t s) {
-  if (B <= 0 || B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  if (!tokens || !hw || !hb) return CTK_E_NULL;
+  if (B <= 0 || B > CTK_MAX_BATCH || S <= 0 || N <= 0) return CTK_E_SHAPE;
+  for (int b = 0; b < B; ++b)
+    if (!st.coords[b] || !st.vis[b] || !st.conf[b]) return CTK_E_NULL;
+  if (!ctk_aligned16(tokens) || !ctk_aligned16(hw)) return CTK_E_ALIGN;
   const long rows = (long)B * S * N;
   CtkProfScope ps("heads_update", 8.0 * rows * CTK_HID, 4.0 * rows * CTK_HID, s);
   const long want = (rows + 7) / 8;
@@ -322,4 +350,51 @@ int ctk_launch_heads_batch(const float* tokens, const float* hw, const float* hb
                      static_cast<float*>(nullptr), HeadsBatch{st, B});
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;
+}
+
+// ---- the launchers above on their own (include/ctk.h: "for tests") ----------------------------------------------------------
+// A ctk_window_batch is read for the state only: coords / vis / conf, S, N and the scales of each video (equal S, N and scales).
+namespace {
+int check_state_batch(const ctk_window_batch* bt, bool need_scale) {
+  if (!bt || !bt->videos) return CTK_E_NULL;
+  if (bt->B < 1 || bt->B > CTK_MAX_BATCH) return CTK_E_SHAPE;
+  const ctk_window_args* a = bt->videos;
+  for (int b = 0; b < bt->B; ++b) {
+    const ctk_window_args* v = a + b;
+    if (v->S <= 0 || v->N <= 0 || v->S != a->S || v->N != a->N) return CTK_E_SHAPE;
+    if (need_scale && (!(v->scale_x > 0.f) || !(v->scale_y > 0.f) || v->scale_x != a->scale_x || v->scale_y != a->scale_y)) return CTK_E_SHAPE;
+  }
+  if ((long)bt->B * a->S * a->N > 2000000000L / CTK_MLP * 64) return CTK_E_SHAPE;  // (row counts travel as int, as in the window call)
+  return CTK_OK;
+}
+CtkBatchState state_of(const ctk_window_batch* bt) {
+  CtkBatchState st{};
+  for (int b = 0; b < bt->B; ++b) {
+    st.coords[b] = bt->videos[b].coords; st.vis[b] = bt->videos[b].vis; st.conf[b] = bt->videos[b].conf;
+  }
+  return st;
+}
+}  // namespace
+
+extern "C" int ctk_assemble_tokens_batch(const ctk_window_batch* batch, void* x, int32_t x_split, int32_t ld, int32_t base,
+                                         void* stream) {
+  if (!x) return CTK_E_NULL;
+  const int rc = check_state_batch(batch, true);
+  if (rc) return rc;
+  const ctk_window_args* a = batch->videos;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (batch->B == 1) return ctk_launch_assemble(a, x, x_split, ld, base, s);
+  return ctk_launch_assemble_batch(state_of(batch), batch->B, a->S, a->N, a->scale_x, a->scale_y, x, x_split, ld, base, s);
+}
+
+extern "C" int ctk_heads_update(const ctk_window_batch* batch, const float* tokens, const float* head_w, const float* head_b,
+                                float* delta, void* stream) {
+  if (!tokens || !head_w || !head_b) return CTK_E_NULL;
+  const int rc = check_state_batch(batch, false);
+  if (rc) return rc;
+  const ctk_window_args* a = batch->videos;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (batch->B == 1) return ctk_launch_heads(tokens, head_w, head_b, a->S, a->N, delta, a->coords, a->vis, a->conf, s);
+  if (delta) return CTK_E_SHAPE;  // the joint kernel updates the state only
+  return ctk_launch_heads_batch(tokens, head_w, head_b, state_of(batch), batch->B, a->S, a->N, s);
 }

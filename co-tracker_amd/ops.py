@@ -121,6 +121,65 @@ def layernorm(x: torch.Tensor, gamma=None, beta=None, eps: float = 1e-6, out_spl
     return y
 
 
+def layernorm_dual(x: torch.Tensor, gamma=None, beta=None, eps: float = 1e-5, eps2: float = 1e-6, out_split: bool = False):
+    """(LayerNorm(x; gamma, beta, eps), LayerNorm(x; eps2)) from one read of x (ctk_layernorm_dual: the window's launch for the
+    point tokens of a depth)."""
+    _chk_f32(x, gamma, beta)
+    assert x.shape[-1] == L.HID
+    R = x.numel() // L.HID
+    y, y2 = (torch.empty(R, L.HID // 32, 2, 32, device=x.device, dtype=torch.float16) if out_split else torch.empty_like(x)
+             for _ in range(2))
+    L.check(L.load().ctk_layernorm_dual(_ptr(x), _ptr(y), _ptr(y2), R, _ptr(gamma), _ptr(beta), float(eps), float(eps2),
+                                        int(out_split), _stream()), "ctk_layernorm_dual")
+    return y, y2
+
+
+def virtual_init(virtual_tokens: torch.Tensor, S: int, B: int = 1) -> torch.Tensor:
+    """The virtual-token rows a window starts from (ctk_virtual_init): [B*64*S, 384], row (b*64 + v)*S + t = virtual_tokens[v]."""
+    _chk_f32(virtual_tokens)
+    assert virtual_tokens.shape == (L.VIRT, L.HID)
+    dst = torch.empty(B * L.VIRT * S, L.HID, device=virtual_tokens.device, dtype=torch.float32)
+    L.check(L.load().ctk_virtual_init(_ptr(virtual_tokens), S, B, _ptr(dst), _stream()), "ctk_virtual_init")
+    return dst
+
+
+def state_batch(states, S: int, N: int, scale_xy=(1.0, 1.0)):
+    """ctk_window_batch of B videos' state alone, for ctk_assemble_tokens_batch / ctk_heads_update: states = [(coords [S,N,2], vis
+    [S,N], conf [S,N])] per video, as tensors, addresses or None.  -> (the struct, what it points to: keep it alive)."""
+    arr = (L.WindowArgs * len(states))()
+    for a, (c, v, f) in zip(arr, states):
+        a.S, a.N = S, N
+        a.coords, a.vis, a.conf = (_ptr(p) if torch.is_tensor(p) else p for p in (c, v, f))
+        a.scale_x, a.scale_y = float(scale_xy[0]), float(scale_xy[1])
+    return L.WindowBatch(len(states), 0, C.cast(arr, C.POINTER(L.WindowArgs))), (arr, states)
+
+
+def assemble_tokens_batch(states, scale_xy, x: torch.Tensor, folded: bool = False) -> torch.Tensor:
+    """The 96 small-feature columns of B videos (ctk_assemble_tokens_batch) into x: f32 [B*N*S, ld] or SH [B*N*S, ld/32, 2, 32], ld
+    and the first column those of the plain (CTK_X_LD, CTK_X_VIS) or the folded (CTK_XF_LD, CTK_XF_SMALL) input."""
+    S, N = states[0][1].shape
+    ld, base = (L.XF_LD, L.XF_SMALL) if folded else (L.X_LD, L.X_VIS)
+    assert x.is_cuda and x.is_contiguous() and x.numel() == len(states) * N * S * ld * (2 if x.dtype == torch.float16 else 1)
+    batch, keep = state_batch(states, S, N, scale_xy)
+    L.check(L.load().ctk_assemble_tokens_batch(C.byref(batch), _ptr(x), int(x.dtype == torch.float16), ld, base, _stream()),
+            "ctk_assemble_tokens_batch")
+    return x
+
+
+def heads_update(tokens: torch.Tensor, head_w: torch.Tensor, head_b: torch.Tensor, S: int, N: int, states=None,
+                 want_delta: bool = False) -> Optional[torch.Tensor]:
+    """delta = tokens @ head_w^T + head_b per row (ctk_heads_update), added in place to the (coords, vis, conf) of `states` (one
+    triple per video; None: delta only) and / or returned [N*S, 4] (want_delta: one video only)."""
+    _chk_f32(tokens, head_w, head_b)
+    states = states or [(None, None, None)]
+    assert tokens.shape == (len(states) * N * S, L.HID) and head_w.shape == (4, L.HID) and head_b.shape == (4,)
+    delta = torch.empty(N * S, 4, device=tokens.device, dtype=torch.float32) if want_delta or states[0][0] is None else None
+    batch, keep = state_batch(states, S, N)
+    L.check(L.load().ctk_heads_update(C.byref(batch), _ptr(tokens), _ptr(head_w), _ptr(head_b), _ptr(delta), _stream()),
+            "ctk_heads_update")
+    return delta
+
+
 def _attn_args(q, k, v, nbatch: int, N1: int, N2: int, q_bs: int, kv_bs: int, inner: int, splits: int, out_split: bool,
                key_mask, query_mask):
     """ctk_attn_args of `nbatch` problems q [N1 rows] over k / v [N2 rows]: batch strides q_bs (q, out) / kv_bs (k, v) and inner

@@ -192,6 +192,10 @@ typedef struct ctk_model_weights {
   const float* in_bias_t;    /* [S,384] = input_transform.bias + W @ time_emb_S[t]  (time embedding
                                  folded into the projection: W(x+e_t)+b = Wx + (W e_t + b),
                                  cotracker3_online.py:247 + cotracker.py:484) */
+  /* virtual_tokens, head_w and every ctx_gamma / ctx_beta are read 16 bytes at a time by the row kernels: the window
+   * entry points, their graphs and ctk_update_former (and ctk_update_former_ex for its ctk_former_weights) answer CTK_E_ALIGN
+   * to one that is not 16-byte aligned, with the rest of their validation -- before any launch.  ctk_update_former asks the
+   * same of delta.                                                                                                       */
   const float* virtual_tokens; /* virual_tracks [64,384]        cotracker.py:416 */
   const float* head_w;       /* [4,384] = cat(flow_head.weight, vis_conf_head.weight)  cotracker.py:526-529 */
   const float* head_b;       /* [4] */
@@ -1430,9 +1434,37 @@ int ctk_corr_volume(const ctk_window_args* a, float* out, void* stream);
 int ctk_corr_volume_sh_workspace_bytes(const ctk_window_args* a, size_t* out_bytes);
 int ctk_corr_volume_sh(const ctk_window_args* a, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- Op C: assemble_tokens (cotracker3_online.py:212-245, posenc :19-39) -> x[:,1024:1120] */
+/* ---- Op C: assemble_tokens (cotracker3_online.py:212-245, posenc :19-39) -> x[:,1024:1120]
+ * Row n*S + t, columns CTK_X_VIS + [vis, conf, 4 relative coordinates (c[t] - c[t+1], c[t] - c[t-1]) / scale, sin and cos
+ * (sin of the argument + f32(pi/2)) of these times 2^0 .. 2^9, ten zeros]; a missing neighbour frame gives 0.  Every step of
+ * the argument is the reference's own float32 operation; the sine is within 2.5e-7 of the exact sine of that float32
+ * argument, at any magnitude (checked up to arguments of 1e7: tracks far outside the frame).  Only these 96 columns are
+ * written.  x: 16-byte aligned (CTK_E_ALIGN).                                                                        */
 int ctk_assemble_tokens(const ctk_window_args* a, void* x /* f32 [N*S,CTK_X_LD], or SH when x_split */,
                         int32_t x_split, void* stream);
+
+/* ---- the row kernels of a window on their own (for tests): each entry point validates and makes ONE launch, the launch
+ * ctk_forward_window / ctk_forward_window_batch / ctk_update_former make at that place.  A ctk_window_batch is read for
+ * the STATE only: coords [S,N,2] / vis / conf [S,N], S, N (and, where said, scale_x / scale_y) of videos[0 .. B), which must
+ * agree in S, N and the scales; 1 <= B <= CTK_MAX_BATCH; fmaps, support, iters and flags are not looked at.  Validation comes
+ * before any HIP call, in this order: a missing pointer CTK_E_NULL, a bad size CTK_E_SHAPE, a pointer the kernel moves 16 bytes
+ * at a time that is not 16-byte aligned CTK_E_ALIGN (named per entry point; the state is read and written 4 bytes at a time).
+ *
+ * Token assembly (Op C) into columns [base, base + 96) of rows `ld` columns apart: ld % 32 == 0, base % 32 == 0,
+ * 0 <= base <= ld - 96 -- (CTK_X_LD, CTK_X_VIS) is ctk_assemble_tokens, (CTK_XF_LD, CTK_XF_SMALL) the folded input.  x f32
+ * [B*N*S, ld], or SH [B*N*S][ld/32][2][32] halves when x_split; row (b*N + n)*S + t.  B == 1 is the single-video kernel,
+ * B > 1 the joint one (per-video state pointers by value).  Reads the scales.  Aligned: x.                              */
+int ctk_assemble_tokens_batch(const ctk_window_batch* batch, void* x, int32_t x_split, int32_t ld, int32_t base, void* stream);
+/* dst[(b*64 + v)*S + t][0..384) = virtual_tokens[v][0..384)  (cotracker.py:487-488), b < B <= CTK_MAX_BATCH.
+ * Aligned: virtual_tokens, dst.                                                                                          */
+int ctk_virtual_init(const float* virtual_tokens /*[64,384]*/, int32_t S, int32_t B, float* dst /*[B*64*S,384]*/, void* stream);
+/* d = tokens[row] @ head_w^T + head_b for every row (b*N + n)*S + t of tokens [B*N*S, 384] (head_w [4,384]: flow x, flow y,
+ * vis, conf; head_b [4]), then   delta[row] = d   when delta is given, and   coords[t][n] += d[0..1], vis[t][n] += d[2],
+ * conf[t][n] += d[3]   on video b's state when it is given (cotracker3_online.py:252-259).  B == 1: delta [N*S,4] and / or
+ * the state -- coords, vis and conf all three or all NULL; neither is CTK_E_NULL.  B > 1 (the joint kernel): the state of
+ * every video, delta must be NULL (CTK_E_SHAPE).  Aligned: tokens, head_w, delta.                                     */
+int ctk_heads_update(const ctk_window_batch* batch, const float* tokens, const float* head_w, const float* head_b,
+                     float* delta, void* stream);
 
 /* ---- Op B: EfficientUpdateFormer.forward (cotracker.py:483-531): x -> delta [N*S,4] */
 int ctk_update_former_workspace_bytes(int32_t S, int32_t N, size_t* out_bytes);
@@ -1656,9 +1688,16 @@ int ctk_pack_weight_bytes(int32_t N, int32_t K, size_t* out_bytes);
 int ctk_pack_weight(const float* W, int64_t ldw, int32_t N, int32_t K, void* packed, void* stream);
 
 /* LayerNorm over 384 channels, rows [0,R): y = (x-mean)/sqrt(var+eps) [*gamma+beta].
- * y is f32 [R,384], or SH [R][12][2][32] halves when out_split != 0.                     */
+ * y is f32 [R,384], or SH [R][12][2][32] halves when out_split != 0: the split of the f32
+ * result, bit for bit.  gamma and beta: both or neither.  A row's result depends on that row
+ * alone.  x, y, gamma, beta: 16-byte aligned (CTK_E_ALIGN), checked after NULL and R <= 0.   */
 int ctk_layernorm(const float* x, void* y, int64_t R, const float* gamma, const float* beta,
                   float eps, int32_t out_split, void* stream);
+/* Two normalisations from one read of x (for tests: the window's launch for the point tokens
+ * of a depth): y as ctk_layernorm with (gamma, beta, eps), y2 as ctk_layernorm with (NULL, NULL,
+ * eps2) -- the same bits as those two calls.  Same rules; y2 is required and aligned like y. */
+int ctk_layernorm_dual(const float* x, void* y, void* y2, int64_t R, const float* gamma, const float* beta,
+                       float eps, float eps2, int32_t out_split, void* stream);
 
 /* softmax(q k^T * 48^-0.5) v  (Attention.forward, blocks.py:379-398), 8 heads x 48.
  * row(b,i) = b*bs + i*is (rows of a matrix with leading dimension ld floats).           */

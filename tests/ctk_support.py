@@ -130,14 +130,69 @@ def attention_raw(q, q_ld, q_bs, q_is, k, v, kv_ld, kv_bs, kv_is, out, o_ld, o_b
 CORR_K, CORR_LD = 2401, 2432  # 49 x 49 volume columns and the row length (K padding of corr_mlp.fc1), in 4-byte units
 
 
-def nan_framed(x, pad=8192):
+NAN_PATTERN = 0x7FC17FC1  # NaN as one f32 and as two f16
+
+
+def nan_framed(x, pad=8192, pattern=None, whole=False):
     """A copy of x (f32) in the middle of a NaN-filled allocation on the GPU, `pad` elements on either side (a multiple of 4: the
-    view keeps the 16-byte alignment of the allocation) -> the contiguous view.  A read that leaves the operand reads NaN."""
+    view keeps the 16-byte alignment of the allocation) -> the contiguous view.  A read that leaves the operand reads NaN.
+    pattern: the bits of the NaN (NAN_PATTERN reads as NaN in either number format; default: torch's).  whole=True -> (view, the
+    whole allocation), for `frame_intact` after a launch that writes the view."""
     assert pad % 4 == 0 and x.dtype == torch.float32
-    flat = torch.full((x.numel() + 2 * pad,), float("nan"), device=dev())
+    if pattern is None:
+        flat = torch.full((x.numel() + 2 * pad,), float("nan"), device=dev())
+    else:
+        flat = torch.full((x.numel() + 2 * pad,), pattern, dtype=torch.int32, device=dev()).view(torch.float32)
     view = flat[pad:pad + x.numel()].view(x.shape)
     view.copy_(x)
-    return view
+    return (view, flat) if whole else view
+
+
+def frame_intact(flat, view, pattern=NAN_PATTERN):
+    """Whether the `pattern` words around `view` inside its allocation `flat` (nan_framed(..., pattern, whole=True)) kept their bits."""
+    pad = (flat.numel() - view.numel()) // 2
+    w = flat.view(torch.int32)
+    return bool((w[:pad] == pattern).all()) and bool((w[pad + view.numel():] == pattern).all())
+
+
+# ---- the row kernels as the C-ABI sees them (tests/test_gpu_rowop_matrix.py): every pointer the caller's ------------------------------------
+def _addr(x):
+    return x.data_ptr() if torch.is_tensor(x) else x
+
+
+def _current_stream():
+    return torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+
+
+def layernorm_raw(x, y, R, gamma, beta, eps, out_split, y2=None, eps2=0.0):
+    """ctk_layernorm, or with y2 ctk_layernorm_dual, on the current stream -> its return code (ops.layernorm allocates y itself).
+    Pointers here and below: tensors (a view passes the address of its first element), integers or None."""
+    from cotracker_amd import _lib as L
+    if y2 is None:
+        return L.load().ctk_layernorm(_addr(x), _addr(y), R, _addr(gamma), _addr(beta), eps, int(out_split), _current_stream())
+    return L.load().ctk_layernorm_dual(_addr(x), _addr(y), _addr(y2), R, _addr(gamma), _addr(beta), eps, eps2, int(out_split),
+                                       _current_stream())
+
+
+def virtual_init_raw(virtual_tokens, S, B, dst):
+    from cotracker_amd import _lib as L
+    return L.load().ctk_virtual_init(_addr(virtual_tokens), S, B, _addr(dst), _current_stream())
+
+
+def assemble_raw(states, S, N, scale_xy, x, x_split, ld, base):
+    """ctk_assemble_tokens_batch over states = [(coords, vis, conf)] per video -> its return code."""
+    from cotracker_amd import _lib as L
+    from cotracker_amd import ops
+    batch, keep = ops.state_batch(states, S, N, scale_xy)
+    return L.load().ctk_assemble_tokens_batch(C.byref(batch), _addr(x), int(x_split), ld, base, _current_stream())
+
+
+def heads_raw(states, S, N, tokens, head_w, head_b, delta):
+    """ctk_heads_update over states = [(coords, vis, conf)] per video ((None, None, None): delta only) -> its return code."""
+    from cotracker_amd import _lib as L
+    from cotracker_amd import ops
+    batch, keep = ops.state_batch(states, S, N)
+    return L.load().ctk_heads_update(C.byref(batch), _addr(tokens), _addr(head_w), _addr(head_b), _addr(delta), _current_stream())
 
 
 def corr_volume_raw(win, sh, canary, guard=4):

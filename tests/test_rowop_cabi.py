@@ -1,6 +1,8 @@
 """Argument validation of the encoder's pixel entry points and the CoTracker2 row entry points (include/ctk.h:
 ctk_enc_stem_im2col, ctk_enc_inorm_workspace_bytes, ctk_enc_inorm_stats, ctk_enc_inorm_apply, ctk_enc_fuse, ctk_enc_l2norm,
-ctk_v2_assemble, ctk_v2_apply_delta, ctk_v2_vis_head), without a GPU: every rule the header documents is refused with its
+ctk_v2_assemble, ctk_v2_apply_delta, ctk_v2_vis_head) and of the CoTracker3 row entry points (ctk_layernorm, ctk_layernorm_dual,
+ctk_assemble_tokens, ctk_assemble_tokens_batch, ctk_virtual_init, ctk_heads_update, and what of the weights reaches their kernels
+through ctk_forward_window / ctk_update_former), without a GPU: every rule the header documents is refused with its
 CTK_E_* code BEFORE any HIP call.  The pointers below are made-up addresses: every call in this file is invalid in exactly
 one way, so none of them may reach a launch.  The file runs only where no device is visible: there a call that slipped through
 a missing check returns a positive hipError_t, which no assertion here accepts, instead of launching on these addresses."""
@@ -173,3 +175,187 @@ def test_v2_window_refuses_what_its_last_call_would_refuse(lib):
     w.vis_w = ODD        # 8-byte aligned is enough for the float2 loads
     rc = query(C.byref(a), C.byref(w), C.byref(n))      # a query: no launch
     assert rc != E_ALIGN
+
+
+# ---- the CoTracker3 row entry points (csrc/rowops.hip) ----------------------------------------------------------------------------------
+def _state_batch(B=1, **at):
+    """ctk_window_batch of made-up state pointers, S = 8 and N = 5; at: field=value on video B - 1 (the last one) alone."""
+    from cotracker_amd import _lib as L
+    arr = (L.WindowArgs * max(B, 1))()
+    for a in arr:
+        a.S, a.N, a.coords, a.vis, a.conf, a.scale_x, a.scale_y = 8, 5, P, P, P, 1.0, 1.0
+    for k, v in at.items():
+        setattr(arr[max(B, 1) - 1], k, v)
+    return L.WindowBatch(B, 0, C.cast(arr, C.POINTER(L.WindowArgs))), arr
+
+
+def test_new_row_symbols_are_declared_bound_and_exported(lib):
+    import os
+    from cotracker_amd import _lib as L
+    from ctk_support import ROOT
+    header = open(os.path.join(ROOT, "include", "ctk.h")).read()
+    for name in ("ctk_layernorm_dual", "ctk_virtual_init", "ctk_assemble_tokens_batch", "ctk_heads_update"):
+        assert f"int {name}(" in header and name in L.SYMBOLS and hasattr(lib, name), name
+    assert lib.ctk_abi_version() == L.ABI_VERSION == 9
+
+
+def test_layernorm_and_assemble_tokens_alignment(lib):
+    f = lib.ctk_layernorm
+    good = [P, P, 40, P, P, 1e-5, 0, None]      # x, y, R, gamma, beta, eps, out_split, stream
+    _each_missing(f, good, (0, 1, 3, 4))        # (gamma without beta, beta without gamma)
+    assert f(*_with(good, _2=0)) == E_SHAPE and f(*_with(good, _2=-3)) == E_SHAPE
+    for i in (0, 1, 3, 4):                      # f32x4 loads, f32x4 / f16x8 stores
+        for odd in (ODD, ODD4):
+            for split in (0, 1):
+                assert f(*_with(good, **{f"_{i}": odd, "_6": split})) == E_ALIGN, (i, odd, split)
+    assert f(*_with(good, _0=ODD, _3=None, _4=None)) == E_ALIGN      # without the affine part too
+    assert f(*_with(good, _0=None, _2=0)) == E_NULL and f(*_with(good, _0=ODD, _2=0)) == E_SHAPE   # NULL, then shape, then alignment
+    from cotracker_amd import _lib as L
+    a = L.WindowArgs()
+    a.S, a.N, a.coords, a.vis, a.conf, a.scale_x, a.scale_y = 8, 5, P, P, P, 1.0, 1.0
+    g = lib.ctk_assemble_tokens
+    assert g(None, P, 0, None) == E_NULL and g(C.byref(a), None, 0, None) == E_NULL
+    for split in (0, 1):
+        assert g(C.byref(a), ODD, split, None) == E_ALIGN and g(C.byref(a), ODD4, split, None) == E_ALIGN
+    a.N = 0
+    assert g(C.byref(a), ODD, 0, None) == E_SHAPE
+
+
+def test_layernorm_dual_arguments(lib):
+    f = lib.ctk_layernorm_dual
+    good = [P, P, P, 40, P, P, 1e-5, 1e-6, 0, None]   # x, y, y2, R, gamma, beta, eps, eps2, out_split, stream
+    _each_missing(f, good, (0, 1, 2, 4, 5))
+    assert f(*_with(good, _3=0)) == E_SHAPE and f(*_with(good, _3=-1)) == E_SHAPE
+    for i in (0, 1, 2, 4, 5):
+        for split in (0, 1):
+            assert f(*_with(good, **{f"_{i}": ODD, "_8": split})) == E_ALIGN, (i, split)
+    assert f(*_with(good, _2=ODD4, _4=None, _5=None)) == E_ALIGN
+    assert f(*_with(good, _2=None, _3=0)) == E_NULL and f(*_with(good, _2=ODD, _3=0)) == E_SHAPE
+
+
+def test_virtual_init_arguments(lib):
+    f = lib.ctk_virtual_init
+    good = [P, 8, 2, P, None]                   # virtual_tokens, S, B, dst, stream
+    _each_missing(f, good, (0, 3))
+    for bad in (_with(good, _1=0), _with(good, _1=-8), _with(good, _2=0), _with(good, _2=-1), _with(good, _2=17)):
+        assert f(*bad) == E_SHAPE, bad
+    for i in (0, 3):
+        assert f(*_with(good, **{f"_{i}": ODD})) == E_ALIGN and f(*_with(good, **{f"_{i}": ODD4})) == E_ALIGN, i
+    assert f(*_with(good, _0=None, _2=17)) == E_NULL and f(*_with(good, _0=ODD, _2=17)) == E_SHAPE
+
+
+def test_assemble_tokens_batch_arguments(lib):
+    f = lib.ctk_assemble_tokens_batch
+
+    def call(batch, x=P, split=0, ld=1120, base=1024):
+        return f(C.byref(batch[0]) if batch is not None else None, x, split, ld, base, None)
+
+    for B in (1, 2, 16):
+        assert call(_state_batch(B), x=None) == E_NULL
+        for field in ("coords", "vis", "conf"):
+            assert call(_state_batch(B, **{field: None})) == E_NULL, (B, field)
+        for kw in ({"S": 0}, {"N": 0}, {"S": -8}, {"scale_x": 0.0}, {"scale_y": -1.0}, {"scale_x": float("nan")}):
+            assert call(_state_batch(B, **kw)) == E_SHAPE, (B, kw)
+        for ld, base in ((1120, 1056), (1120, 1000), (1100, 992), (1120, -32), (96, 32), (1632, 1568), (0, 0)):
+            assert call(_state_batch(B), ld=ld, base=base) == E_SHAPE, (B, ld, base)
+        for ld, base in ((1120, 1024), (1632, 1536), (96, 0)):       # the two layouts of the window and the smallest one
+            for split in (0, 1):
+                assert call(_state_batch(B), x=ODD, split=split, ld=ld, base=base) == E_ALIGN, (B, ld, base, split)
+                assert call(_state_batch(B), x=ODD4, split=split, ld=ld, base=base) == E_ALIGN
+    assert call(None) == E_NULL
+    from cotracker_amd import _lib as L
+    assert f(C.byref(L.WindowBatch(2, 0, None)), P, 0, 1120, 1024, None) == E_NULL
+    assert call(_state_batch(0)) == E_SHAPE and call(_state_batch(17)) == E_SHAPE and call(_state_batch(-1)) == E_SHAPE
+    for kw in ({"S": 7}, {"N": 6}, {"scale_x": 2.0}, {"scale_y": 0.5}):      # the videos of a joint call agree
+        assert call(_state_batch(3, **kw)) == E_SHAPE, kw
+    assert call(_state_batch(2, coords=None), x=ODD) == E_NULL and call(_state_batch(2, S=0), x=ODD) == E_SHAPE
+
+
+def test_heads_update_arguments(lib):
+    f = lib.ctk_heads_update
+
+    def call(batch, tokens=P, hw=P, hb=P, delta=None):
+        return f(C.byref(batch[0]) if batch is not None else None, tokens, hw, hb, delta, None)
+
+    for B in (1, 2, 16):
+        for kw in ({"tokens": None}, {"hw": None}, {"hb": None}):
+            assert call(_state_batch(B), **kw) == E_NULL, (B, kw)
+        for field in ("coords", "vis", "conf"):
+            assert call(_state_batch(B, **{field: None})) == E_NULL, (B, field)      # the state: all three
+        for kw in ({"S": 0}, {"N": 0}, {"N": -5}):
+            assert call(_state_batch(B, **kw)) == E_SHAPE, (B, kw)
+        for kw in ({"tokens": ODD}, {"hw": ODD}, {"tokens": ODD4}, {"hw": ODD4}):    # f32x4 loads
+            assert call(_state_batch(B), **kw) == E_ALIGN, (B, kw)
+    assert call(None) == E_NULL
+    assert call(_state_batch(0)) == E_SHAPE and call(_state_batch(17)) == E_SHAPE
+    assert call(_state_batch(2, S=7)) == E_SHAPE and call(_state_batch(2, N=4)) == E_SHAPE
+    # B == 1: delta and / or the state; delta is one 16-byte store per row
+    none = dict(coords=None, vis=None, conf=None)
+    assert call(_state_batch(1, **none)) == E_NULL                                   # neither
+    assert call(_state_batch(1, **none), delta=ODD) == E_ALIGN and call(_state_batch(1), delta=ODD4) == E_ALIGN
+    assert call(_state_batch(1, coords=None, vis=None), delta=P) == E_NULL           # a part of the state
+    assert call(_state_batch(1, **none), delta=P, hw=ODD) == E_ALIGN
+    # B > 1: the joint kernel has no delta
+    assert call(_state_batch(2), delta=P) == E_SHAPE and call(_state_batch(16), delta=P) == E_SHAPE
+    assert call(_state_batch(2), tokens=None, delta=P) == E_NULL                     # NULL first
+
+
+def _model_weights():
+    """A ctk_model_weights (f32 back end, unfolded) of made-up pointers that passes every NULL rule."""
+    from cotracker_amd import _lib as L
+    w = L.ModelWeights()
+    for n in ("corr_fc1_w", "corr_fc1_b", "corr_fc2_w", "corr_fc2_b", "in_w", "in_bias_t", "virtual_tokens", "head_w", "head_b"):
+        setattr(w, n, P)
+    for blocks in (w.time_blocks, w.virtual2point, w.virtual_self, w.point2virtual):
+        for b in blocks:
+            for n in ("wq", "bq", "wkv", "bkv", "wo", "bo", "w1", "b1", "w2", "b2", "ctx_gamma", "ctx_beta"):
+                setattr(b, n, P)
+    return w
+
+
+def test_windows_refuse_what_their_row_kernels_would_misread(lib):
+    """head_w, virtual_tokens and norm_context's gamma / beta reach heads_kernel, virtual_init_kernel and layernorm_kernel through
+    the window and update-former calls: refused with the weights' validation, before the workspace is looked at or anything runs."""
+    from cotracker_amd import _lib as L
+    a = L.WindowArgs()
+    a.S, a.N, a.iters, a.coords, a.vis, a.conf, a.scale_x, a.scale_y = 8, 5, 1, P, P, P, 1.0, 1.0
+    batch = L.WindowBatch(1, 0, C.pointer(a))
+    h = C.c_void_p()
+
+    def every_entry(w):
+        return (lib.ctk_update_former(8, 5, P, C.byref(w), P, P, 1 << 40, None),
+                lib.ctk_forward_window(C.byref(a), C.byref(w), P, 1 << 40, None),
+                lib.ctk_forward_window_batch(C.byref(batch), C.byref(w), P, 1 << 40, None),
+                lib.ctk_window_tokens_batch(C.byref(batch), C.byref(w), P, P, 1 << 40, None),
+                lib.ctk_window_graph_create(C.byref(a), C.byref(w), P, 1 << 40, C.byref(h)))
+
+    for odd in (ODD, ODD4):
+        for name in ("head_w", "virtual_tokens"):
+            w = _model_weights()
+            setattr(w, name, odd)
+            assert every_entry(w) == (E_ALIGN,) * 5 and not h.value, name
+        for blocks in ("virtual2point", "point2virtual"):
+            for i in (0, L.DEPTH - 1):
+                for name in ("ctx_gamma", "ctx_beta"):
+                    w = _model_weights()
+                    setattr(getattr(w, blocks)[i], name, odd)
+                    assert every_entry(w) == (E_ALIGN,) * 5 and not h.value, (blocks, i, name)
+    w = _model_weights()
+    assert lib.ctk_update_former(8, 5, P, C.byref(w), ODD, P, 1 << 40, None) == E_ALIGN      # delta: one 16-byte store per row
+    w.head_w = None
+    assert lib.ctk_update_former(8, 5, P, C.byref(w), ODD, P, 1 << 40, None) == E_NULL
+    fw = L.FormerWeights()                                                                  # CoTracker2's former: the same kernels
+    fw.depth, fw.in_dim, fw.in_ld, fw.out_dim, fw.out_ld = 1, 456, 480, 130, 192
+    blocks = [L.BlockWeights() for _ in range(4)]
+    for b in blocks:
+        for n in ("wq", "bq", "wkv", "bkv", "wo", "bo", "w1", "b1", "w2", "b2", "ctx_gamma", "ctx_beta"):
+            setattr(b, n, P)
+    fw.in_w = fw.in_b = fw.virtual_tokens = fw.head_w = fw.head_b = P
+    fw.time_blocks, fw.virtual2point, fw.virtual_self, fw.point2virtual = (C.pointer(b) for b in blocks)
+    ex = lambda: lib.ctk_update_former_ex(8, 5, P, 0, C.byref(fw), None, P, P, 1 << 40, None)  # noqa: E731
+    fw.virtual_tokens = ODD
+    assert ex() == E_ALIGN
+    fw.virtual_tokens, blocks[1].ctx_gamma = P, ODD4
+    assert ex() == E_ALIGN
+    blocks[1].ctx_gamma, blocks[3].ctx_beta = P, ODD
+    assert ex() == E_ALIGN
