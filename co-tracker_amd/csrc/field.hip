@@ -25,6 +25,7 @@
 #include "ctk_common.h"
 #include "ctk_profile.h"
 #include "field_math.h"
+#include "fit_device.h"  // fit_scale_ok
 
 namespace {
 
@@ -182,8 +183,6 @@ __global__ __launch_bounds__(256) void field_resolve_kernel(FieldParams p) {
   p.level[o] = (uint8_t)l;
 }
 
-bool field_scale_ok(float s) { return s > 0.0f && s <= 3.402823466e+38f; }
-
 // everything but the pointers
 int field_check_shape(const ctk_track_field_args* a) {
   const long big = 1L << 30;
@@ -202,7 +201,7 @@ int field_check_shape(const ctk_track_field_args* a) {
     const long lo = a->to < a->f0 ? a->to : a->f0, hi = a->to > (long)a->f0 + a->F - 1 ? a->to : (long)a->f0 + a->F - 1;
     if (hi - lo + 1 > a->R) return CTK_E_SHAPE;
   }
-  if (!field_scale_ok(a->sx) || !field_scale_ok(a->sy)) return CTK_E_SHAPE;
+  if (!fit_scale_ok(a->sx) || !fit_scale_ok(a->sy)) return CTK_E_SHAPE;
   if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
   return CTK_OK;
 }

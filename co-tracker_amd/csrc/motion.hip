@@ -14,9 +14,12 @@
 //             bit, a ballot and the kept (chunk, wave) place -- nothing is gathered twice.  `inlier` is written here, -1 included, and
 //             the eight int64 sums are reduced by wave shuffles and through LDS (integer adds: the order does not matter).  Thread 0
 //             divides and writes the matrix and the stats.
+// Shared with the other fit kernels, from fit_device.h: the source and the slot gather (CtkFitSource, fit_gather; here always the
+// `lag` form: to = -1, no anchor) and the reductions.  The single-pass staging with its `mine` bits and chunk_place stays here: it
+// uses the shared gather only.
 #include "ctk_common.h"
 #include "ctk_profile.h"
-#include "motion_device.h"  // the wave reductions, motion_hyp_at; motion_math.h
+#include "fit_device.h"  // and through it motion_device.h: the wave reductions, motion_hyp_at; motion_math.h
 
 namespace {
 
@@ -24,15 +27,10 @@ constexpr int MOTION_CHUNK = 256;
 constexpr int MOTION_CHUNKS_MAX = CTK_MOTION_POINTS_MAX / MOTION_CHUNK;  // 32: one bit each in a thread's register
 
 struct MotionParams {
-  int G, N, N_out, R, f0, lag, K, T;
+  CtkFitSource src;
+  int K, T;
   uint32_t seed;
   int64_t base2;
-  float sx, sy, thresh;
-  const float* hc;
-  const uint8_t* visible;
-  const float* hv;
-  const float* hf;
-  const int32_t* first_row;
   float* motion;
   int8_t* inlier;
   int32_t* stats;
@@ -54,31 +52,18 @@ __global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
   __shared__ int64_t wave_sum[4][CTK_MS_COUNT];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
-  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.f0 + pic, fs = f - p.lag;
+  const CtkFitSource& src = p.src;
+  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = src.f0 + pic;
   const long g = (long)blockIdx.y;
-  const long row_q = (g * p.R + f % p.R) * p.N;
-  const long row_p = fs >= 0 ? (g * p.R + fs % p.R) * p.N : 0;
+  const FitFrame fr = fit_frame(src, g, f);
 
   // 1. stage
   uint32_t mine = 0;
   int M = 0;
-  for (int c = 0, c0 = 0; c0 < p.N_out; c0 += MOTION_CHUNK, ++c) {
+  for (int c = 0, c0 = 0; c0 < src.N_out; c0 += MOTION_CHUNK, ++c) {
     const int n = c0 + tid;
-    bool hit = false;
     int4 pt = make_int4(0, 0, 0, 0);
-    if (n < p.N_out && fs >= 0) {
-      const int first = p.first_row != nullptr ? p.first_row[g * p.N + n] : 0;
-      if (fs >= first) {  // (f > fs: frame f is at or above the first row too)
-        const float2 hp = *reinterpret_cast<const float2*>(p.hc + (row_p + n) * 2);
-        const float2 hq = *reinterpret_cast<const float2*>(p.hc + (row_q + n) * 2);
-        const bool ok0 = ctk_motion_quant(hp.x, p.sx, &pt.x), ok1 = ctk_motion_quant(hp.y, p.sy, &pt.y);
-        const bool ok2 = ctk_motion_quant(hq.x, p.sx, &pt.z), ok3 = ctk_motion_quant(hq.y, p.sy, &pt.w);
-        if (ok0 && ok1 && ok2 && ok3) {
-          if (p.visible != nullptr) hit = p.visible[row_p + n] != 0 && p.visible[row_q + n] != 0;
-          else hit = ctk_draw_visible(p.hv[row_p + n], p.hf[row_p + n], p.thresh) && ctk_draw_visible(p.hv[row_q + n], p.hf[row_q + n], p.thresh);
-        }
-      }
-    }
+    const bool hit = fit_gather(src, fr, n, &pt);
     const unsigned long long mask = __ballot(hit);
     if (lane == 0) wave_hits[wave] = __popcll(mask);
     __syncthreads();
@@ -113,11 +98,7 @@ __global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
       best = key > best ? key : best;
     }
   }
-  best = motion_wave_max(best);
-  if (lane == 0) wave_key[wave] = best;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 4; ++w) best = wave_key[w] > best ? wave_key[w] : best;
+  best = fit_block_best(best, wave_key);
 
   // 3. refit
   const bool have = best >= 0;
@@ -127,12 +108,12 @@ __global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
   int64_t s[CTK_MS_COUNT];
 #pragma unroll
   for (int i = 0; i < CTK_MS_COUNT; ++i) s[i] = 0;
-  int8_t* inl = p.inlier + (g * F + pic) * (long)p.N_out;
-  for (int c = 0, c0 = 0; c0 < p.N_out; c0 += MOTION_CHUNK, ++c) {
+  int8_t* inl = p.inlier + (g * F + pic) * (long)src.N_out;
+  for (int c = 0, c0 = 0; c0 < src.N_out; c0 += MOTION_CHUNK, ++c) {
     const int n = c0 + tid;
     const bool hit = (mine >> c) & 1u;
     const unsigned long long mask = __ballot(hit);
-    if (n < p.N_out) {
+    if (n < src.N_out) {
       int8_t v = -1;
       if (hit) {
         const int4 q = pts[chunk_place[c][wave] + __popcll(mask & below)];
@@ -143,11 +124,7 @@ __global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
       inl[n] = v;
     }
   }
-#pragma unroll
-  for (int i = 0; i < CTK_MS_COUNT; ++i) {
-    const int64_t t = motion_wave_sum(s[i]);
-    if (lane == 0) wave_sum[wave][i] = t;
-  }
+  fit_block_sums<CTK_MS_COUNT>(s, wave_sum);
   __syncthreads();
   if (tid == 0) {
 #pragma unroll
@@ -163,26 +140,23 @@ __global__ __launch_bounds__(256) void fit_motion_kernel(MotionParams p) {
   }
 }
 
-// everything but the pointers
+// the source of a call: f - lag alone, no fixed frame and no anchor
+CtkFitSource motion_source_of(const ctk_fit_motion_args* a) {
+  CtkFitSource s;
+  s.G = a->G, s.N = a->N, s.N_out = a->N_out, s.R = a->R, s.f0 = a->f0, s.to = -1, s.lag = a->lag, s.anchor_frame = 0;
+  s.sx = a->sx, s.sy = a->sy, s.thresh = a->thresh;
+  s.hc = a->hist_coords, s.visible = a->visible, s.hv = a->hist_vis, s.hf = a->hist_conf, s.first_row = a->first_row;
+  s.ac = nullptr, s.av = nullptr;
+  return s;
+}
+
+// everything but the pointers  (the source rule leaves lag >= 1 as the one form)
 int motion_check_shape(const ctk_fit_motion_args* a) {
-  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->R <= 0 || a->F <= 0 || a->N_out > a->N || a->N_out > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
-  if (a->lag < 1 || (long)a->F + a->lag > a->R || a->f0 < 0 || (long)a->f0 + a->F > (1L << 30) || a->F > 65535) return CTK_E_SHAPE;
-  if (a->G > 65535 || (long)a->G * a->N > (1L << 26) || a->reserved != 0) return CTK_E_SHAPE;
+  if (!fit_check_source(motion_source_of(a), a->F) || a->reserved != 0) return CTK_E_SHAPE;
   if (a->model != CTK_MOTION_TRANSLATION && a->model != CTK_MOTION_SIMILARITY) return CTK_E_SHAPE;
   if (a->K < 1 || a->K > CTK_MOTION_HYPOTHESES_MAX) return CTK_E_SHAPE;
   if (ctk_motion_tol(a->tol) == 0 || ctk_motion_base2(a->min_base) < 0) return CTK_E_SHAPE;
-  if (!(a->sx > 0.0f && a->sx <= 3.402823466e+38f) || !(a->sy > 0.0f && a->sy <= 3.402823466e+38f)) return CTK_E_SHAPE;
-  if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
   return CTK_OK;
-}
-
-template <int MODEL>
-void motion_launch(const MotionParams& p, int F, hipStream_t s) {
-  const size_t lds = (size_t)p.N_out * sizeof(int4);
-  // (beyond 64 KiB of dynamic LDS a kernel has to say so once; not a stream operation)
-  if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_motion_kernel<MODEL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             CTK_MOTION_POINTS_MAX * (int)sizeof(int4));
-  hipLaunchKernelGGL((fit_motion_kernel<MODEL>), dim3((unsigned)F, (unsigned)p.G), dim3(256), lds, s, p);
 }
 
 }  // namespace
@@ -197,26 +171,24 @@ extern "C" int ctk_fit_motion_workspace_bytes(const ctk_fit_motion_args* a, size
 
 extern "C" int ctk_fit_motion(const ctk_fit_motion_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   if (!a) return CTK_E_NULL;
-  if (!a->hist_coords || !a->motion || !a->inlier || !a->stats) return CTK_E_NULL;
-  if (!a->visible && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
+  MotionParams p;
+  p.src = motion_source_of(a);
+  if (fit_null_source(p.src) || !a->motion || !a->inlier || !a->stats) return CTK_E_NULL;
   const int rc = motion_check_shape(a);
   if (rc != CTK_OK) return rc;
   size_t need = 0;
   ctk_fit_motion_workspace_bytes(a, &need);
   if (workspace_bytes < need || (need > 0 && !workspace)) return CTK_E_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(a->hist_coords) & 7u) != 0) return CTK_E_ALIGN;
+  if (!fit_align_source(p.src)) return CTK_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
-  MotionParams p;
-  p.G = a->G, p.N = a->N, p.N_out = a->N_out, p.R = a->R, p.f0 = a->f0, p.lag = a->lag, p.K = a->K;
+  p.K = a->K;
   p.T = ctk_motion_tol(a->tol), p.base2 = ctk_motion_base2(a->min_base), p.seed = a->seed;
-  p.sx = a->sx, p.sy = a->sy, p.thresh = a->thresh;
-  p.hc = a->hist_coords, p.visible = a->visible, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
   p.motion = a->motion, p.inlier = a->inlier, p.stats = a->stats;
   {
     CtkProfScope prof("fit_motion", 0.0, (double)a->G * a->F * a->N_out * 33.0, s);
-    if (a->model == CTK_MOTION_SIMILARITY) motion_launch<CTK_MOTION_SIMILARITY>(p, a->F, s);
-    else motion_launch<CTK_MOTION_TRANSLATION>(p, a->F, s);
+    fit_launch(a->model == CTK_MOTION_SIMILARITY ? fit_motion_kernel<CTK_MOTION_SIMILARITY> : fit_motion_kernel<CTK_MOTION_TRANSLATION>,
+               a->F, a->G, (size_t)a->N_out * sizeof(int4), CTK_MOTION_POINTS_MAX * (int)sizeof(int4), s, p);
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

@@ -1,5 +1,6 @@
-// Device helpers shared by the robust-fit kernels (motion.hip, objects.hip): the wave reductions of a key and of a sum, and a
-// hypothesis rebuilt from its number over a list of (Px, Py, Qx, Qy) points in LDS.  The rules themselves are motion_math.h's.
+// Device helpers shared by the robust-fit kernels: the wave reductions of a key and of a sum, and a hypothesis rebuilt from its number
+// over a list of (Px, Py, Qx, Qy) points in LDS (motion.hip, objects.hip).  The rules themselves are motion_math.h's.  The kernels
+// include fit_device.h, which includes this header and holds what else they share.
 #pragma once
 #include <hip/hip_runtime.h>
 

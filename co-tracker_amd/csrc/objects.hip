@@ -23,9 +23,12 @@
 //                CTK_OBJECT_NONE.
 // Every slot is written once: at the stage (no correspondence, no round), by the round that visits it (labels mode), by the round that
 // takes it or at the end (split mode).
+// Shared with the other fit kernels, from fit_device.h: the source and the slot gather (CtkFitSource, fit_gather), the labels mode's
+// two-pass staging (fit_stage, a segment per label) and the reductions.  The single-pass staging of split mode stays here: it uses the
+// shared gather only.
 #include "ctk_common.h"
 #include "ctk_profile.h"
-#include "motion_device.h"
+#include "fit_device.h"
 #include "objects_math.h"
 
 namespace {
@@ -34,17 +37,10 @@ constexpr int OBJ_CHUNK = 256;
 constexpr int OBJ_ENTRY_BYTES = (int)sizeof(int4) + (int)sizeof(uint16_t);  // a point and its slot
 
 struct ObjectsParams {
-  int G, N, N_out, R, f0, to, lag, anchor_frame, L, min_points, K, T;
+  CtkFitSource src;
+  int L, min_points, K, T;
   uint32_t seed;
   int64_t base2;
-  float sx, sy, thresh;
-  const float* hc;
-  const uint8_t* visible;
-  const float* hv;
-  const float* hf;
-  const int32_t* first_row;
-  const float* ac;
-  const uint8_t* av;
   const int8_t* labels;
   float* motion;
   int8_t* label;
@@ -52,73 +48,32 @@ struct ObjectsParams {
   int32_t* box;
 };
 
-// slot n of group g: frame f (row_q of the history) against the source frame fs (row_p of the history, or of the anchor)
-// -> a correspondence; *pt = (Px, Py, Qx, Qy)
-__device__ __forceinline__ bool objects_gather(const ObjectsParams& p, long g, int f, int fs, long row_p, long row_q, int n, int4* pt) {
-  if (n >= p.N_out || fs < 0) return false;
-  const int first = p.first_row != nullptr ? p.first_row[g * p.N + n] : 0;
-  if (f < first || fs < first) return false;
-  const bool anchored = p.ac != nullptr;
-  const float2 hp = *reinterpret_cast<const float2*>((anchored ? p.ac : p.hc) + (row_p + n) * 2);
-  const float2 hq = *reinterpret_cast<const float2*>(p.hc + (row_q + n) * 2);
-  const bool ok0 = ctk_motion_quant(hp.x, p.sx, &pt->x), ok1 = ctk_motion_quant(hp.y, p.sy, &pt->y);
-  const bool ok2 = ctk_motion_quant(hq.x, p.sx, &pt->z), ok3 = ctk_motion_quant(hq.y, p.sy, &pt->w);
-  if (!(ok0 && ok1 && ok2 && ok3)) return false;
-  const bool vq = p.visible != nullptr ? p.visible[row_q + n] != 0 : ctk_draw_visible(p.hv[row_q + n], p.hf[row_q + n], p.thresh);
-  bool vp;
-  if (anchored) vp = p.av[row_p + n] != 0;
-  else if (p.visible != nullptr) vp = p.visible[row_p + n] != 0;
-  else vp = ctk_draw_visible(p.hv[row_p + n], p.hf[row_p + n], p.thresh);
-  return vp && vq;
-}
-
-__device__ __forceinline__ int objects_wave_min(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int w = __shfl_xor(v, o, 64);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ int objects_wave_max(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int w = __shfl_xor(v, o, 64);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
 // grid: x = frame f0 + x, y = group; dynamic LDS: N_out * 18 bytes
 template <int MODEL>
 __global__ __launch_bounds__(256) void fit_objects_kernel(ObjectsParams p) {
   extern __shared__ int4 pts[];
-  uint16_t* slot = reinterpret_cast<uint16_t*>(pts + p.N_out);
+  uint16_t* slot = reinterpret_cast<uint16_t*>(pts + p.src.N_out);
   __shared__ int wave_hits[4];
-  __shared__ int wave_lab[4][CTK_OBJECTS_MAX];
-  __shared__ int run[2][CTK_OBJECTS_MAX];
-  __shared__ int seg[CTK_OBJECTS_MAX + 1];
+  __shared__ FitStageLds<CTK_OBJECTS_MAX> stage;
   __shared__ int64_t wave_key[4];
   __shared__ int64_t wave_sum[4][CTK_MS_COUNT];
   __shared__ int wave_box[4][4];
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
-  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.f0 + pic;
+  const CtkFitSource& src = p.src;
+  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = src.f0 + pic;
   const long g = (long)blockIdx.y;
-  const bool anchored = p.ac != nullptr, by_labels = p.labels != nullptr;
-  const int fs = ctk_objects_source(f, p.to, p.lag, anchored, p.anchor_frame);
-  const long row_q = (g * p.R + f % p.R) * p.N;
-  const long row_p = anchored ? g * p.N : (fs >= 0 ? (g * p.R + fs % p.R) * p.N : 0);
-  int8_t* lab_out = p.label + (g * F + pic) * (long)p.N_out;
+  const bool by_labels = p.labels != nullptr;
+  const FitFrame fr = fit_frame(src, g, f);
+  int8_t* lab_out = p.label + (g * F + pic) * (long)src.N_out;
 
   // 1. stage
   int M = 0;
   if (!by_labels) {
-    for (int c0 = 0; c0 < p.N_out; c0 += OBJ_CHUNK) {
+    for (int c0 = 0; c0 < src.N_out; c0 += OBJ_CHUNK) {
       const int n = c0 + tid;
       int4 pt = make_int4(0, 0, 0, 0);
-      const bool hit = objects_gather(p, g, f, fs, row_p, row_q, n, &pt);
+      const bool hit = fit_gather(src, fr, n, &pt);
       const unsigned long long mask = __ballot(hit);
       if (lane == 0) wave_hits[wave] = __popcll(mask);
       __syncthreads();
@@ -133,67 +88,24 @@ __global__ __launch_bounds__(256) void fit_objects_kernel(ObjectsParams p) {
         const int place = before + __popcll(mask & below);
         pts[place] = pt;
         slot[place] = (uint16_t)n;
-      } else if (n < p.N_out) {
+      } else if (n < src.N_out) {
         lab_out[n] = -1;
       }
       M += total;
       __syncthreads();  // the list is read, and wave_hits written again, only behind it
     }
   } else {
-    const int8_t* labels = p.labels + g * p.N;
-    int cnt[CTK_OBJECTS_MAX];  // of this wave, per label
-#pragma unroll
-    for (int q = 0; q < CTK_OBJECTS_MAX; ++q) cnt[q] = 0;
-    for (int c0 = 0; c0 < p.N_out; c0 += OBJ_CHUNK) {
-      const int n = c0 + tid;
-      int4 pt;
-      const int r = objects_gather(p, g, f, fs, row_p, row_q, n, &pt) ? ctk_objects_round(labels[n], p.L) : -1;
-#pragma unroll
-      for (int q = 0; q < CTK_OBJECTS_MAX; ++q) cnt[q] += __popcll(__ballot(r == q));
-    }
-#pragma unroll
-    for (int q = 0; q < CTK_OBJECTS_MAX; ++q)
-      if (lane == q) wave_lab[wave][q] = cnt[q];
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int q = 0; q < CTK_OBJECTS_MAX; ++q) {
-        seg[q] = s, run[0][q] = s;
-        s += wave_lab[0][q] + wave_lab[1][q] + wave_lab[2][q] + wave_lab[3][q];
-      }
-      seg[CTK_OBJECTS_MAX] = s;
-    }
-    __syncthreads();
-    for (int c = 0, c0 = 0; c0 < p.N_out; c0 += OBJ_CHUNK, ++c) {
-      const int n = c0 + tid, cur = c & 1;
-      int4 pt = make_int4(0, 0, 0, 0);
-      const bool hit = objects_gather(p, g, f, fs, row_p, row_q, n, &pt);
-      const int r = hit ? ctk_objects_round(labels[n], p.L) : -1;
-      int rank = 0;
-#pragma unroll
-      for (int q = 0; q < CTK_OBJECTS_MAX; ++q) {
-        const unsigned long long mask = __ballot(r == q);
-        if (lane == q) wave_lab[wave][q] = __popcll(mask);
-        if (r == q) rank = __popcll(mask & below);
-      }
-      __syncthreads();
-      if (r >= 0) {
-        int place = run[cur][r] + rank;
-        for (int w = 0; w < wave; ++w) place += wave_lab[w][r];
-        pts[place] = pt;
-        slot[place] = (uint16_t)n;
-      } else if (n < p.N_out) {
-        lab_out[n] = hit ? (int8_t)CTK_OBJECT_NONE : (int8_t)-1;
-      }
-      if (tid < CTK_OBJECTS_MAX) run[cur ^ 1][tid] = run[cur][tid] + wave_lab[0][tid] + wave_lab[1][tid] + wave_lab[2][tid] + wave_lab[3][tid];
-      __syncthreads();  // the running ends of the next chunk are complete, and wave_lab is written again only behind it
-    }
+    const int8_t* labels = p.labels + g * src.N;
+    fit_stage(
+        stage, src.N_out, pts, slot, [&](int n, int4* pt) { return fit_gather(src, fr, n, pt); },
+        [&](int n) { return ctk_objects_round(labels[n], p.L); },
+        [&](int n, bool hit) { lab_out[n] = hit ? (int8_t)CTK_OBJECT_NONE : (int8_t)-1; });
   }
 
   // 2. the rounds
   int lo = 0, Mr = M, r = 0;
   for (; r < p.L; ++r) {
-    if (by_labels) lo = seg[r], Mr = seg[r + 1] - seg[r];
+    if (by_labels) lo = stage.seg[r], Mr = stage.seg[r + 1] - stage.seg[r];
     const int4* list = pts + lo;
     const uint32_t seed_r = ctk_objects_seed(p.seed, r);
     int64_t best = -1;
@@ -210,11 +122,7 @@ __global__ __launch_bounds__(256) void fit_objects_kernel(ObjectsParams p) {
         best = key > best ? key : best;
       }
     }
-    best = motion_wave_max(best);
-    if (lane == 0) wave_key[wave] = best;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 4; ++w) best = wave_key[w] > best ? wave_key[w] : best;
+    best = fit_block_best(best, wave_key);
 
     const bool have = ctk_objects_accept(best, p.min_points);
     CtkMotionHyp hb;
@@ -268,13 +176,9 @@ __global__ __launch_bounds__(256) void fit_objects_kernel(ObjectsParams p) {
         __syncthreads();
       }
     }
-#pragma unroll
-    for (int i = 0; i < CTK_MS_COUNT; ++i) {
-      const int64_t t = motion_wave_sum(s[i]);
-      if (lane == 0) wave_sum[wave][i] = t;
-    }
+    fit_block_sums<CTK_MS_COUNT>(s, wave_sum);
     {
-      const int b0 = objects_wave_min(bx[0]), b1 = objects_wave_min(bx[1]), b2 = objects_wave_max(bx[2]), b3 = objects_wave_max(bx[3]);
+      const int b0 = fit_wave_min(bx[0]), b1 = fit_wave_min(bx[1]), b2 = fit_wave_max(bx[2]), b3 = fit_wave_max(bx[3]);
       if (lane == 0) wave_box[wave][0] = b0, wave_box[wave][1] = b1, wave_box[wave][2] = b2, wave_box[wave][3] = b3;
     }
     __syncthreads();
@@ -325,40 +229,14 @@ __global__ __launch_bounds__(256) void fit_objects_kernel(ObjectsParams p) {
   }
 }
 
-bool objects_scale_ok(float s) { return s > 0.0f && s <= 3.402823466e+38f; }
-
 // everything but the pointers (whether an anchor is given is looked at, as in ctk_track_field)
 int objects_check_shape(const ctk_fit_objects_args* a) {
-  const long big = 1L << 30;
-  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->R <= 0 || a->F <= 0 || a->N_out > a->N || a->N_out > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
-  if (a->f0 < 0 || (long)a->f0 + a->F > big || a->F > 65535 || a->G > 65535 || (long)a->G * a->N > (1L << 26) || a->reserved != 0) return CTK_E_SHAPE;
+  if (!fit_check_source(fit_source_of(a), a->F) || a->reserved != 0) return CTK_E_SHAPE;
   if (a->L < 1 || a->L > CTK_OBJECTS_MAX || a->min_points < 1 || a->min_points > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
   if (a->model != CTK_MOTION_TRANSLATION && a->model != CTK_MOTION_SIMILARITY) return CTK_E_SHAPE;
   if (a->K < 1 || a->K > CTK_MOTION_HYPOTHESES_MAX) return CTK_E_SHAPE;
   if (ctk_motion_tol(a->tol) == 0 || ctk_motion_base2(a->min_base) < 0) return CTK_E_SHAPE;
-  const bool anchored = a->anchor_coords != nullptr || a->anchor_visible != nullptr;
-  if (a->to < -1 || a->to > big || a->lag > big || a->lag < 0) return CTK_E_SHAPE;
-  if ((a->to >= 0 ? 1 : 0) + (a->lag != 0 ? 1 : 0) + (anchored ? 1 : 0) != 1) return CTK_E_SHAPE;
-  if (anchored) {
-    if (a->anchor_frame < 0 || a->anchor_frame > big || a->F > a->R) return CTK_E_SHAPE;
-  } else if (a->lag != 0) {
-    if ((long)a->F + a->lag > a->R) return CTK_E_SHAPE;
-  } else {
-    const long lo = a->to < a->f0 ? a->to : a->f0, hi = a->to > (long)a->f0 + a->F - 1 ? a->to : (long)a->f0 + a->F - 1;
-    if (hi - lo + 1 > a->R) return CTK_E_SHAPE;
-  }
-  if (!objects_scale_ok(a->sx) || !objects_scale_ok(a->sy)) return CTK_E_SHAPE;
-  if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
   return CTK_OK;
-}
-
-template <int MODEL>
-void objects_launch(const ObjectsParams& p, int F, hipStream_t s) {
-  const size_t lds = (size_t)p.N_out * OBJ_ENTRY_BYTES;
-  // (beyond 64 KiB of dynamic LDS a kernel has to say so once; not a stream operation)
-  if (lds > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_objects_kernel<MODEL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             CTK_MOTION_POINTS_MAX * OBJ_ENTRY_BYTES);
-  hipLaunchKernelGGL((fit_objects_kernel<MODEL>), dim3((unsigned)F, (unsigned)p.G), dim3(256), lds, s, p);
 }
 
 }  // namespace
@@ -373,30 +251,26 @@ extern "C" int ctk_fit_objects_workspace_bytes(const ctk_fit_objects_args* a, si
 
 extern "C" int ctk_fit_objects(const ctk_fit_objects_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   if (!a) return CTK_E_NULL;
-  if (!a->hist_coords || !a->motion || !a->label || !a->stats || !a->box) return CTK_E_NULL;
-  if (!a->visible && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
-  if ((a->anchor_coords != nullptr) != (a->anchor_visible != nullptr)) return CTK_E_NULL;
+  ObjectsParams p;
+  p.src = fit_source_of(a);
+  if (fit_null_source(p.src) || !a->motion || !a->label || !a->stats || !a->box) return CTK_E_NULL;
   const int rc = objects_check_shape(a);
   if (rc != CTK_OK) return rc;
   size_t need = 0;
   ctk_fit_objects_workspace_bytes(a, &need);
   if (workspace_bytes < need || (need > 0 && !workspace)) return CTK_E_SHAPE;
-  if (((reinterpret_cast<uintptr_t>(a->hist_coords) | reinterpret_cast<uintptr_t>(a->anchor_coords)) & 7u) != 0) return CTK_E_ALIGN;
+  if (!fit_align_source(p.src)) return CTK_E_ALIGN;
   if (((reinterpret_cast<uintptr_t>(a->motion) | reinterpret_cast<uintptr_t>(a->stats) | reinterpret_cast<uintptr_t>(a->box)) & 3u) != 0) return CTK_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
-  ObjectsParams p;
-  p.G = a->G, p.N = a->N, p.N_out = a->N_out, p.R = a->R, p.f0 = a->f0, p.to = a->to, p.lag = a->lag, p.anchor_frame = a->anchor_frame;
   p.L = a->L, p.min_points = a->min_points, p.K = a->K;
   p.T = ctk_motion_tol(a->tol), p.base2 = ctk_motion_base2(a->min_base), p.seed = a->seed;
-  p.sx = a->sx, p.sy = a->sy, p.thresh = a->thresh;
-  p.hc = a->hist_coords, p.visible = a->visible, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
-  p.ac = a->anchor_coords, p.av = a->anchor_visible, p.labels = a->labels;
+  p.labels = a->labels;
   p.motion = a->motion, p.label = a->label, p.stats = a->stats, p.box = a->box;
   {
     CtkProfScope prof("fit_objects", 0.0, (double)a->G * a->F * (a->N_out * (a->labels ? 67.0 : 33.0) + a->L * 56.0), s);
-    if (a->model == CTK_MOTION_SIMILARITY) objects_launch<CTK_MOTION_SIMILARITY>(p, a->F, s);
-    else objects_launch<CTK_MOTION_TRANSLATION>(p, a->F, s);
+    fit_launch(a->model == CTK_MOTION_SIMILARITY ? fit_objects_kernel<CTK_MOTION_SIMILARITY> : fit_objects_kernel<CTK_MOTION_TRANSLATION>,
+               a->F, a->G, (size_t)a->N_out * OBJ_ENTRY_BYTES, CTK_MOTION_POINTS_MAX * OBJ_ENTRY_BYTES, s, p);
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

@@ -221,6 +221,9 @@ CTK_MM_HD void ctk_plane_system(const int64_t* s, double* N, double* b) {
   b[6] = -S[CTK_PS_XR], b[7] = -S[CTK_PS_YR];
 }
 
+// the doubles a caller keeps for one system and its solution: N, b, L, D, v, z, h
+#define CTK_PLANE_SOLVE_DOUBLES (64 + 8 + 64 + 8 + 8 + 8 + 8)
+
 // N h = b by N = L D L^T; L (8 x 8, the strict lower triangle is used), D, v, z: work space of 64 + 8 + 8 + 8 doubles -> solved
 CTK_MM_HD bool ctk_plane_solve(const double* N, const double* b, double* L, double* D, double* v, double* z, double* h) {
   for (int j = 0; j < 8; ++j) {

@@ -1,9 +1,9 @@
 // Camera pose and point depths on the device (include/ctk.h, "fit pose"): per (group, frame) the fundamental matrix and the labels that
 // ctk_fit_epipolar wrote become a rotation, a unit translation and two depths per correspondence, by the rules of pose_math.h (and,
 // through it, epipolar_math.h, plane_math.h, objects_math.h and motion_math.h).  The frame of the call is ctk_fit_epipolar's
-// (epipolar.hip): the same workgroup layout, the same slot gather, the same two-pass staging -- its loops are copied here, as
-// epipolar.hip copied planes.hip's; only what is done with the list differs.  One launch, no atomics, no workspace; every output
-// element is one plain store; `fundamental` and `label` are only read.
+// (epipolar.hip): the same workgroup layout, and from fit_device.h the same source and slot gather (CtkFitSource, fit_gather), the
+// same two-pass staging (fit_stage, two segments); only what is done with the list differs.  One launch, no atomics, no workspace;
+// every output element is one plain store; `fundamental` and `label` are only read.
 //
 // One workgroup of 256 threads owns one (group, frame).  Dynamic LDS: the list of (Px, Py, Qx, Qy) int32 points, 16 bytes each, and
 // next to it a uint16 side list that leads an entry back to its slot n: N_out * 18 bytes, 144 KiB at most.
@@ -18,7 +18,7 @@
 // outputs   all A entries are walked once more under the final pose: the depths, and the count of the fit list's entries in front.
 #include "ctk_common.h"
 #include "ctk_profile.h"
-#include "motion_device.h"
+#include "fit_device.h"
 #include "pose_math.h"
 
 namespace {
@@ -28,16 +28,9 @@ constexpr int PO_ENTRY_BYTES = (int)sizeof(int4) + (int)sizeof(uint16_t);  // a 
 constexpr int PO_SLOTS = CTK_POSE_SUMS + 2;                                // the sums, the count, and one to keep rows 16-byte multiples
 
 struct PoseParams {
-  int G, N, N_out, R, f0, to, lag, anchor_frame, min_points;
-  float sx, sy, thresh;
+  CtkFitSource src;
+  int min_points;
   CtkPoseCam cam;
-  const float* hc;
-  const uint8_t* visible;
-  const float* hv;
-  const float* hf;
-  const int32_t* first_row;
-  const float* ac;
-  const uint8_t* av;
   const int8_t* mask;
   const float* fundamental;
   const int8_t* label;
@@ -46,39 +39,10 @@ struct PoseParams {
   int32_t* stats;
 };
 
-// slot n of group g: frame f (row_q of the history) against the source frame fs (row_p of the history, or of the anchor)
-// -> a correspondence; *pt = (Px, Py, Qx, Qy)
-__device__ __forceinline__ bool pose_gather(const PoseParams& p, long g, int f, int fs, long row_p, long row_q, int n, int4* pt) {
-  if (n >= p.N_out || fs < 0) return false;
-  const int first = p.first_row != nullptr ? p.first_row[g * p.N + n] : 0;
-  if (f < first || fs < first) return false;
-  const bool anchored = p.ac != nullptr;
-  const float2 hp = *reinterpret_cast<const float2*>((anchored ? p.ac : p.hc) + (row_p + n) * 2);
-  const float2 hq = *reinterpret_cast<const float2*>(p.hc + (row_q + n) * 2);
-  int4 v;
-  const bool ok0 = ctk_motion_quant(hp.x, p.sx, &v.x), ok1 = ctk_motion_quant(hp.y, p.sy, &v.y);
-  const bool ok2 = ctk_motion_quant(hq.x, p.sx, &v.z), ok3 = ctk_motion_quant(hq.y, p.sy, &v.w);
-  if (!(ok0 && ok1 && ok2 && ok3)) return false;
-  *pt = v;
-  const bool vq = p.visible != nullptr ? p.visible[row_q + n] != 0 : ctk_draw_visible(p.hv[row_q + n], p.hf[row_q + n], p.thresh);
-  bool vp;
-  if (anchored) vp = p.av[row_p + n] != 0;
-  else if (p.visible != nullptr) vp = p.visible[row_p + n] != 0;
-  else vp = ctk_draw_visible(p.hv[row_p + n], p.hf[row_p + n], p.thresh);
-  return vp && vq;
-}
-
-// -1: no correspondence; 0: on the fit list; 1: a correspondence off it  (n < N_out wherever lab and mask are read)
-__device__ __forceinline__ int pose_segment(const PoseParams& p, long g, int f, int fs, long row_p, long row_q, int n, const int8_t* lab,
-                                            const int8_t* mask, int4* pt) {
-  if (!pose_gather(p, g, f, fs, row_p, row_q, n, pt)) return -1;
-  return lab[n] == 1 && (mask == nullptr || mask[n] != 0) ? 0 : 1;
-}
-
 // grid: x = frame f0 + x, y = group; dynamic LDS: N_out * 18 bytes
 __global__ __launch_bounds__(256) void fit_pose_kernel(PoseParams p) {
   extern __shared__ __attribute__((aligned(16))) int4 pts[];
-  uint16_t* slot = reinterpret_cast<uint16_t*>(pts + p.N_out);
+  uint16_t* slot = reinterpret_cast<uint16_t*>(pts + p.src.N_out);
   // (the static part is a multiple of 16 bytes, so that the dynamic list behind it keeps its 16-byte alignment)
   __shared__ __attribute__((aligned(16))) double solve[CTK_POSE_SOLVE_DOUBLES];
   __shared__ __attribute__((aligned(16))) int64_t wave_sum[4][PO_SLOTS];
@@ -86,64 +50,27 @@ __global__ __launch_bounds__(256) void fit_pose_kernel(PoseParams p) {
   __shared__ __attribute__((aligned(16))) CtkPose cand[4];  // 96 bytes each
   __shared__ __attribute__((aligned(16))) CtkPose fit;
   __shared__ __attribute__((aligned(16))) int wave_vote[4][4];
-  __shared__ __attribute__((aligned(16))) int wave_lab[4][2];
-  __shared__ __attribute__((aligned(16))) int run[2][2];
-  __shared__ __attribute__((aligned(16))) int seg[4];
+  __shared__ FitStageLds<2> stage;
   __shared__ __attribute__((aligned(16))) int cand_ok[4];
   __shared__ __attribute__((aligned(16))) int wave_count[4];
   __shared__ __attribute__((aligned(16))) int state[4];  // [0]: the decomposition stands; [1]: the chosen k; [2]: the bits
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.f0 + pic;
+  const CtkFitSource& src = p.src;
+  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = src.f0 + pic;
   const long g = (long)blockIdx.y;
-  const bool anchored = p.ac != nullptr;
-  const int fs = ctk_objects_source(f, p.to, p.lag, anchored, p.anchor_frame);
-  const long row_q = (g * p.R + f % p.R) * p.N;
-  const long row_p = anchored ? g * p.N : (fs >= 0 ? (g * p.R + fs % p.R) * p.N : 0);
+  const FitFrame fr = fit_frame(src, g, f);
   const long o = g * F + pic;
-  const int8_t* lab = p.label + o * (long)p.N_out;
-  float* dep_out = p.depth + o * (long)p.N_out * 2;
-  const int8_t* mask = p.mask != nullptr ? p.mask + g * p.N : nullptr;
+  const int8_t* lab = p.label + o * (long)src.N_out;
+  float* dep_out = p.depth + o * (long)src.N_out * 2;
+  const int8_t* mask = p.mask != nullptr ? p.mask + g * src.N : nullptr;
   const CtkPoseCam cam = p.cam;
 
-  // 1. stage: segment 0 = the fit list, segment 1 = every other correspondence
-  {
-    int cnt0 = 0, cnt1 = 0;  // of this wave
-    for (int c0 = 0; c0 < p.N_out; c0 += PO_CHUNK) {
-      int4 pt;
-      const int r = pose_segment(p, g, f, fs, row_p, row_q, c0 + tid, lab, mask, &pt);
-      cnt0 += __popcll(__ballot(r == 0)), cnt1 += __popcll(__ballot(r == 1));
-    }
-    if (lane == 0) wave_lab[wave][0] = cnt0, wave_lab[wave][1] = cnt1;
-    __syncthreads();
-    if (tid == 0) {
-      const int M = wave_lab[0][0] + wave_lab[1][0] + wave_lab[2][0] + wave_lab[3][0];
-      const int B = wave_lab[0][1] + wave_lab[1][1] + wave_lab[2][1] + wave_lab[3][1];
-      seg[0] = 0, seg[1] = M, seg[2] = M + B, seg[3] = 0;
-      run[0][0] = 0, run[0][1] = M;
-    }
-    __syncthreads();
-    for (int c = 0, c0 = 0; c0 < p.N_out; c0 += PO_CHUNK, ++c) {
-      const int n = c0 + tid, cur = c & 1;
-      int4 pt = make_int4(0, 0, 0, 0);
-      const int r = pose_segment(p, g, f, fs, row_p, row_q, n, lab, mask, &pt);
-      const unsigned long long m0 = __ballot(r == 0), m1 = __ballot(r == 1);
-      if (lane == 0) wave_lab[wave][0] = __popcll(m0), wave_lab[wave][1] = __popcll(m1);
-      const int rank = r == 0 ? __popcll(m0 & below) : __popcll(m1 & below);
-      __syncthreads();
-      if (r >= 0) {
-        int place = run[cur][r] + rank;
-        for (int w = 0; w < wave; ++w) place += wave_lab[w][r];
-        pts[place] = pt;  // (place < N_out: the segments partition the correspondences, of which there are at most N_out)
-        slot[place] = (uint16_t)n;
-      } else if (n < p.N_out) {
-        dep_out[n * 2L] = ctk_pose_nan(), dep_out[n * 2L + 1] = ctk_pose_nan();
-      }
-      if (tid < 2) run[cur ^ 1][tid] = run[cur][tid] + wave_lab[0][tid] + wave_lab[1][tid] + wave_lab[2][tid] + wave_lab[3][tid];
-      __syncthreads();  // the running ends of the next chunk are complete, and wave_lab is written again only behind it
-    }
-  }
-  const int M = seg[1], A = seg[2];
+  // 1. stage: segment 0 = the fit list (label 1, and mask nonzero or no mask), segment 1 = every other correspondence
+  fit_stage(
+      stage, src.N_out, pts, slot, [&](int n, int4* pt) { return fit_gather(src, fr, n, pt); },
+      [&](int n) { return lab[n] == 1 && (mask == nullptr || mask[n] != 0) ? 0 : 1; },
+      [&](int n, bool) { dep_out[n * 2L] = ctk_pose_nan(), dep_out[n * 2L + 1] = ctk_pose_nan(); });
+  const int M = stage.seg[1], A = stage.seg[2];
 
   // 2. E and the four candidates
   if (tid == 0) {
@@ -224,6 +151,7 @@ __global__ __launch_bounds__(256) void fit_pose_kernel(PoseParams p) {
         ++took;
       }
     }
+    // (fit_block_sums' loop, written out: called as a function the same loop compiles to 216 VGPRs here, against 160 -- one wave a SIMD less)
 #pragma unroll
     for (int i = 0; i < CTK_POSE_SUMS; ++i) {
       const int64_t t = motion_wave_sum(s[i]);
@@ -272,29 +200,11 @@ __global__ __launch_bounds__(256) void fit_pose_kernel(PoseParams p) {
   }
 }
 
-bool pose_scale_ok(float s) { return s > 0.0f && s <= 3.402823466e+38f; }
-bool pose_finite(float s) { return fabsf(s) <= 3.402823466e+38f; }
-
 // everything but the pointers (whether an anchor is given is looked at)
 int pose_check_shape(const ctk_fit_pose_args* a) {
-  const long big = 1L << 30;
-  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->R <= 0 || a->F <= 0 || a->N_out > a->N || a->N_out > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
-  if (a->f0 < 0 || (long)a->f0 + a->F > big || a->F > 65535 || a->G > 65535 || (long)a->G * a->N > (1L << 26) || a->reserved != 0) return CTK_E_SHAPE;
+  if (!fit_check_source(fit_source_of(a), a->F) || a->reserved != 0) return CTK_E_SHAPE;
   if (a->min_points < CTK_POSE_MIN_POINTS || a->min_points > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
-  if (!pose_scale_ok(a->fx) || !pose_scale_ok(a->fy) || !pose_finite(a->cx) || !pose_finite(a->cy)) return CTK_E_SHAPE;
-  const bool anchored = a->anchor_coords != nullptr || a->anchor_visible != nullptr;
-  if (a->to < -1 || a->to > big || a->lag > big || a->lag < 0) return CTK_E_SHAPE;
-  if ((a->to >= 0 ? 1 : 0) + (a->lag != 0 ? 1 : 0) + (anchored ? 1 : 0) != 1) return CTK_E_SHAPE;
-  if (anchored) {
-    if (a->anchor_frame < 0 || a->anchor_frame > big || a->F > a->R) return CTK_E_SHAPE;
-  } else if (a->lag != 0) {
-    if ((long)a->F + a->lag > a->R) return CTK_E_SHAPE;
-  } else {
-    const long lo = a->to < a->f0 ? a->to : a->f0, hi = a->to > (long)a->f0 + a->F - 1 ? a->to : (long)a->f0 + a->F - 1;
-    if (hi - lo + 1 > a->R) return CTK_E_SHAPE;
-  }
-  if (!pose_scale_ok(a->sx) || !pose_scale_ok(a->sy)) return CTK_E_SHAPE;
-  if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
+  if (!fit_check_camera(a)) return CTK_E_SHAPE;
   return CTK_OK;
 }
 
@@ -310,35 +220,25 @@ extern "C" int ctk_fit_pose_workspace_bytes(const ctk_fit_pose_args* a, size_t* 
 
 extern "C" int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   if (!a) return CTK_E_NULL;
-  if (!a->hist_coords || !a->fundamental || !a->label || !a->pose || !a->depth || !a->stats) return CTK_E_NULL;
-  if (!a->visible && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
-  if ((a->anchor_coords != nullptr) != (a->anchor_visible != nullptr)) return CTK_E_NULL;
+  PoseParams p;
+  p.src = fit_source_of(a);
+  if (fit_null_source(p.src) || !a->fundamental || !a->label || !a->pose || !a->depth || !a->stats) return CTK_E_NULL;
   const int rc = pose_check_shape(a);
   if (rc != CTK_OK) return rc;
   (void)workspace, (void)workspace_bytes;  // the query answers 0: nothing is too small
-  if (((reinterpret_cast<uintptr_t>(a->hist_coords) | reinterpret_cast<uintptr_t>(a->anchor_coords)) & 7u) != 0) return CTK_E_ALIGN;
+  if (!fit_align_source(p.src)) return CTK_E_ALIGN;
   if (((reinterpret_cast<uintptr_t>(a->fundamental) | reinterpret_cast<uintptr_t>(a->pose) | reinterpret_cast<uintptr_t>(a->depth) |
         reinterpret_cast<uintptr_t>(a->stats)) & 3u) != 0)
     return CTK_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
-  PoseParams p;
-  p.G = a->G, p.N = a->N, p.N_out = a->N_out, p.R = a->R, p.f0 = a->f0, p.to = a->to, p.lag = a->lag, p.anchor_frame = a->anchor_frame;
   p.min_points = a->min_points;
-  p.sx = a->sx, p.sy = a->sy, p.thresh = a->thresh;
   p.cam.fx = (double)a->fx, p.cam.fy = (double)a->fy, p.cam.cx = (double)a->cx, p.cam.cy = (double)a->cy;
-  p.hc = a->hist_coords, p.visible = a->visible, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
-  p.ac = a->anchor_coords, p.av = a->anchor_visible, p.mask = a->mask;
-  p.fundamental = a->fundamental, p.label = a->label;
+  p.mask = a->mask, p.fundamental = a->fundamental, p.label = a->label;
   p.pose = a->pose, p.depth = a->depth, p.stats = a->stats;
   {
     CtkProfScope prof("fit_pose", 0.0, (double)a->G * a->F * (a->N_out * 46.0 + 100.0), s);
-    const size_t lds = (size_t)p.N_out * PO_ENTRY_BYTES;
-    // (Beyond 64 KiB of LDS a kernel has to say so once; not a stream operation.  As epipolar.hip, from 48 KiB of dynamic LDS on:
-    // this kernel holds less than 4 KiB of static LDS beside it, 148 KiB of the CU's 160 KiB at most.)
-    if (lds > 49152) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_pose_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               CTK_MOTION_POINTS_MAX * PO_ENTRY_BYTES);
-    hipLaunchKernelGGL(fit_pose_kernel, dim3((unsigned)a->F, (unsigned)p.G), dim3(256), lds, s, p);
+    fit_launch(fit_pose_kernel, a->F, a->G, (size_t)a->N_out * PO_ENTRY_BYTES, CTK_MOTION_POINTS_MAX * PO_ENTRY_BYTES, s, p);
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

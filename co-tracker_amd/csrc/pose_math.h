@@ -69,7 +69,7 @@
 #define CTK_POSE_ROUNDS 2
 #define CTK_POSE_NAN_BITS 0x7FC00000u
 #define CTK_POSE_FLT_MAX 3.4028234663852886e38  // the largest float32, as a double
-#define CTK_POSE_SOLVE_DOUBLES (64 + 8 + 64 + 8 + 8 + 8 + 8)  // N, b, L, D, v, z, h
+#define CTK_POSE_SOLVE_DOUBLES CTK_PLANE_SOLVE_DOUBLES  // the same ctk_plane_solve layout
 
 struct CtkPoseCam {
   double fx, fy, cx, cy;

@@ -1,9 +1,9 @@
 // Camera resection on the device (include/ctk.h, "fit resection"): per (group, frame) the tracked positions of the points of a 3-D
 // structure become the camera's pose in the structure's unit and coordinates, by the rules of resection_math.h (and, through it,
 // pose_math.h, epipolar_math.h, plane_math.h, objects_math.h and motion_math.h).  The frame of the call is ctk_fit_pose's (pose.hip):
-// the same workgroup layout, the same slot gather, the same two-pass staging -- its loops are copied here, as pose.hip copied
-// epipolar.hip's; only what is done with the list differs.  One launch, no atomics, no workspace; every output element is one plain
-// store; `structure`, `valid` and `seed_pose` are only read.
+// the same workgroup layout, and from fit_device.h the same source and slot gather (CtkFitSource, fit_gather) and the same sums.  The
+// staging stays here, with its capped list, its own entry layout and its `same` count: it uses the shared gather only.  One launch, no
+// atomics, no workspace; every output element is one plain store; `structure`, `valid` and `seed_pose` are only read.
 //
 // One workgroup of 256 threads owns one (group, frame).  Dynamic LDS: the fit list, at most CTK_RESECTION_LIST_MAX entries of
 // a = R0 X (three doubles, one array per component), Q (two int32) and the slot n (uint16): 34 bytes each, 136 KiB at most.
@@ -19,7 +19,7 @@
 // outputs   ALL N_out slots are gathered once more from global memory and labelled under the final pose.
 #include "ctk_common.h"
 #include "ctk_profile.h"
-#include "motion_device.h"
+#include "fit_device.h"
 #include "resection_math.h"
 
 namespace {
@@ -29,17 +29,11 @@ constexpr int RS_ENTRY_BYTES = 3 * (int)sizeof(double) + (int)sizeof(int2) + (in
 constexpr int RS_SLOTS = CTK_POSE_SUMS + 2;  // the sums, the count, and one to keep rows 16-byte multiples
 
 struct ResectionParams {
-  int G, N, N_out, R, f0, to, lag, anchor_frame, min_points, K, cap;
+  CtkFitSource src;
+  int min_points, K, cap;
   uint32_t seed;
-  float sx, sy, thresh, tol;
+  float tol;
   CtkPoseCam cam;
-  const float* hc;
-  const uint8_t* visible;
-  const float* hv;
-  const float* hf;
-  const int32_t* first_row;
-  const float* ac;
-  const uint8_t* av;
   const float* structure;
   const int8_t* valid;
   const float* seed_pose;
@@ -49,38 +43,17 @@ struct ResectionParams {
   int32_t* stats;
 };
 
-// slot n of group g: frame f (row_q of the history) against the source frame fs (row_p of the history, or of the anchor)
-// -> a correspondence; *q = (Qx, Qy), *same: P = Q  (pose.hip's gather: the source position decides with the frame's)
-__device__ __forceinline__ bool resection_gather(const ResectionParams& p, long g, int f, int fs, long row_p, long row_q, int n, int2* q,
-                                                 bool* same) {
-  if (n >= p.N_out || fs < 0) return false;
-  const int first = p.first_row != nullptr ? p.first_row[g * p.N + n] : 0;
-  if (f < first || fs < first) return false;
-  const bool anchored = p.ac != nullptr;
-  const float2 hp = *reinterpret_cast<const float2*>((anchored ? p.ac : p.hc) + (row_p + n) * 2);
-  const float2 hq = *reinterpret_cast<const float2*>(p.hc + (row_q + n) * 2);
+// -1: no correspondence, or the point is not in the structure; 0: a structure point with a correspondence  (*q = (Qx, Qy); *same:
+// P = Q -- the source position decides with the frame's; X: the point's doubles)
+__device__ __forceinline__ int resection_segment(const ResectionParams& p, const FitFrame& fr, int n, int2* q, double* X, bool* same) {
+  *same = false;
   int4 v;
-  const bool ok0 = ctk_motion_quant(hp.x, p.sx, &v.x), ok1 = ctk_motion_quant(hp.y, p.sy, &v.y);
-  const bool ok2 = ctk_motion_quant(hq.x, p.sx, &v.z), ok3 = ctk_motion_quant(hq.y, p.sy, &v.w);
-  if (!(ok0 && ok1 && ok2 && ok3)) return false;
+  if (!fit_gather(p.src, fr, n, &v)) return -1;
   *q = make_int2(v.z, v.w);
   *same = v.x == v.z && v.y == v.w;
-  const bool vq = p.visible != nullptr ? p.visible[row_q + n] != 0 : ctk_draw_visible(p.hv[row_q + n], p.hf[row_q + n], p.thresh);
-  bool vp;
-  if (anchored) vp = p.av[row_p + n] != 0;
-  else if (p.visible != nullptr) vp = p.visible[row_p + n] != 0;
-  else vp = ctk_draw_visible(p.hv[row_p + n], p.hf[row_p + n], p.thresh);
-  return vp && vq;
-}
-
-// -1: no correspondence, or the point is not in the structure; 0: a structure point with a correspondence  (X: its doubles)
-__device__ __forceinline__ int resection_segment(const ResectionParams& p, long g, int f, int fs, long row_p, long row_q, int n, int2* q,
-                                                 double* X, bool* same) {
-  *same = false;
-  if (!resection_gather(p, g, f, fs, row_p, row_q, n, q, same)) return -1;
-  const float* s = p.structure + (g * p.N + n) * 3;
+  const float* s = p.structure + (fr.g * p.src.N + n) * 3;
   const float s3[3] = {s[0], s[1], s[2]};
-  return ctk_resection_point(s3, p.valid[g * p.N + n], X) ? 0 : -1;
+  return ctk_resection_point(s3, p.valid[fr.g * p.src.N + n], X) ? 0 : -1;
 }
 
 // grid: x = frame f0 + x, y = group; dynamic LDS: cap * 34 bytes, cap = min(N_out, CTK_RESECTION_LIST_MAX)
@@ -104,16 +77,14 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
   __shared__ __attribute__((aligned(16))) int state[4];  // [0]: every entry of the fit list; [1]: the winning k; [2]: the bits; [3]: still
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned long long below = (1ull << lane) - 1ull;
-  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.f0 + pic;
+  const int N_out = p.src.N_out;
+  const int F = (int)gridDim.x, pic = (int)blockIdx.x, f = p.src.f0 + pic;
   const long g = (long)blockIdx.y;
-  const bool anchored = p.ac != nullptr;
-  const int fs = ctk_objects_source(f, p.to, p.lag, anchored, p.anchor_frame);
-  const long row_q = (g * p.R + f % p.R) * p.N;
-  const long row_p = anchored ? g * p.N : (fs >= 0 ? (g * p.R + fs % p.R) * p.N : 0);
+  const FitFrame fr = fit_frame(p.src, g, f);
   const long o = g * F + pic;
-  int8_t* lab_out = p.label + o * (long)p.N_out;
-  float* err_out = p.error + o * (long)p.N_out;
-  const float* str = p.structure + g * p.N * 3;
+  int8_t* lab_out = p.label + o * (long)N_out;
+  float* err_out = p.error + o * (long)N_out;
+  const float* str = p.structure + g * p.src.N * 3;
   const CtkPoseCam cam = p.cam;
   const double tol2 = ctk_resection_tol2(p.tol);
   const int K = p.K;
@@ -133,11 +104,11 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
   // 2. stage the fit list
   {
     int cnt = 0, cnt_same = 0;  // of this wave
-    for (int c0 = 0; c0 < p.N_out; c0 += RS_CHUNK) {
+    for (int c0 = 0; c0 < N_out; c0 += RS_CHUNK) {
       int2 q;
       double X[3];
       bool same;
-      const int r = resection_segment(p, g, f, fs, row_p, row_q, c0 + tid, &q, X, &same);
+      const int r = resection_segment(p, fr, c0 + tid, &q, X, &same);
       cnt += __popcll(__ballot(r == 0)), cnt_same += __popcll(__ballot(r == 0 && same));
     }
     if (lane == 0) wave_lab[wave] = cnt, wave_count[wave] = cnt_same;
@@ -150,12 +121,12 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
     }
     __syncthreads();
     const CtkPose s0 = seed0;
-    for (int c = 0, c0 = 0; c0 < p.N_out; c0 += RS_CHUNK, ++c) {
+    for (int c = 0, c0 = 0; c0 < N_out; c0 += RS_CHUNK, ++c) {
       const int n = c0 + tid, cur = c & 1;
       int2 q = make_int2(0, 0);
       double X[3] = {0.0, 0.0, 0.0};
       bool same;
-      const int r = resection_segment(p, g, f, fs, row_p, row_q, n, &q, X, &same);
+      const int r = resection_segment(p, fr, n, &q, X, &same);
       const unsigned long long m0 = __ballot(r == 0);
       if (lane == 0) wave_lab[wave] = __popcll(m0);
       const int rank = __popcll(m0 & below);
@@ -268,11 +239,7 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
           }
         }
       }
-#pragma unroll
-      for (int i = 0; i < CTK_POSE_SUMS; ++i) {
-        const int64_t t = motion_wave_sum(s[i]);
-        if (lane == 0) wave_sum[wave][i] = t;
-      }
+      fit_block_sums<CTK_POSE_SUMS>(s, wave_sum);
       {
         const int64_t t = motion_wave_sum((int64_t)took), u = motion_wave_sum((int64_t)left);
         if (lane == 0) wave_sum[wave][CTK_POSE_SUMS] = t, wave_sum[wave][CTK_POSE_SUMS + 1] = u;
@@ -295,13 +262,13 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
   if (chosen >= 0) fin = fit;
   else ctk_resection_eye(&fin);
   int count = 0;
-  for (int c0 = 0; c0 < p.N_out; c0 += RS_CHUNK) {
+  for (int c0 = 0; c0 < N_out; c0 += RS_CHUNK) {
     const int n = c0 + tid;
     int2 q = make_int2(0, 0);
     double X[3] = {0.0, 0.0, 0.0};
     bool same;
-    const int r = resection_segment(p, g, f, fs, row_p, row_q, n, &q, X, &same);
-    if (n < p.N_out) {
+    const int r = resection_segment(p, fr, n, &q, X, &same);
+    if (n < N_out) {
       int8_t lab = -1;
       float err = -1.0f;
       if (r == 0) {
@@ -333,31 +300,12 @@ __global__ __launch_bounds__(256) void fit_resection_kernel(ResectionParams p) {
   }
 }
 
-bool resection_scale_ok(float s) { return s > 0.0f && s <= 3.402823466e+38f; }
-bool resection_finite(float s) { return fabsf(s) <= 3.402823466e+38f; }
-
 // everything but the pointers (whether an anchor is given is looked at)
 int resection_check_shape(const ctk_fit_resection_args* a) {
-  const long big = 1L << 30;
-  if (a->G <= 0 || a->N <= 0 || a->N_out <= 0 || a->R <= 0 || a->F <= 0 || a->N_out > a->N || a->N_out > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
-  if (a->f0 < 0 || (long)a->f0 + a->F > big || a->F > 65535 || a->G > 65535 || (long)a->G * a->N > (1L << 26)) return CTK_E_SHAPE;
+  if (!fit_check_source(fit_source_of(a), a->F)) return CTK_E_SHAPE;
   if (a->min_points < CTK_RESECTION_MIN_POINTS || a->min_points > CTK_MOTION_POINTS_MAX) return CTK_E_SHAPE;
   if (a->hypotheses < 1 || a->hypotheses > CTK_RESECTION_HYPOTHESES_MAX) return CTK_E_SHAPE;
-  if (!resection_scale_ok(a->tol)) return CTK_E_SHAPE;
-  if (!resection_scale_ok(a->fx) || !resection_scale_ok(a->fy) || !resection_finite(a->cx) || !resection_finite(a->cy)) return CTK_E_SHAPE;
-  const bool anchored = a->anchor_coords != nullptr || a->anchor_visible != nullptr;
-  if (a->to < -1 || a->to > big || a->lag > big || a->lag < 0) return CTK_E_SHAPE;
-  if ((a->to >= 0 ? 1 : 0) + (a->lag != 0 ? 1 : 0) + (anchored ? 1 : 0) != 1) return CTK_E_SHAPE;
-  if (anchored) {
-    if (a->anchor_frame < 0 || a->anchor_frame > big || a->F > a->R) return CTK_E_SHAPE;
-  } else if (a->lag != 0) {
-    if ((long)a->F + a->lag > a->R) return CTK_E_SHAPE;
-  } else {
-    const long lo = a->to < a->f0 ? a->to : a->f0, hi = a->to > (long)a->f0 + a->F - 1 ? a->to : (long)a->f0 + a->F - 1;
-    if (hi - lo + 1 > a->R) return CTK_E_SHAPE;
-  }
-  if (!resection_scale_ok(a->sx) || !resection_scale_ok(a->sy)) return CTK_E_SHAPE;
-  if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
+  if (!fit_scale_ok(a->tol) || !fit_check_camera(a)) return CTK_E_SHAPE;
   return CTK_OK;
 }
 
@@ -373,36 +321,27 @@ extern "C" int ctk_fit_resection_workspace_bytes(const ctk_fit_resection_args* a
 
 extern "C" int ctk_fit_resection(const ctk_fit_resection_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   if (!a) return CTK_E_NULL;
-  if (!a->hist_coords || !a->structure || !a->valid || !a->seed_pose || !a->pose || !a->label || !a->error || !a->stats) return CTK_E_NULL;
-  if (!a->visible && (!a->hist_vis || !a->hist_conf)) return CTK_E_NULL;
-  if ((a->anchor_coords != nullptr) != (a->anchor_visible != nullptr)) return CTK_E_NULL;
+  ResectionParams p;
+  p.src = fit_source_of(a);
+  if (fit_null_source(p.src) || !a->structure || !a->valid || !a->seed_pose || !a->pose || !a->label || !a->error || !a->stats) return CTK_E_NULL;
   const int rc = resection_check_shape(a);
   if (rc != CTK_OK) return rc;
   (void)workspace, (void)workspace_bytes;  // the query answers 0: nothing is too small
-  if (((reinterpret_cast<uintptr_t>(a->hist_coords) | reinterpret_cast<uintptr_t>(a->anchor_coords)) & 7u) != 0) return CTK_E_ALIGN;
+  if (!fit_align_source(p.src)) return CTK_E_ALIGN;
   if (((reinterpret_cast<uintptr_t>(a->structure) | reinterpret_cast<uintptr_t>(a->seed_pose) | reinterpret_cast<uintptr_t>(a->pose) |
         reinterpret_cast<uintptr_t>(a->error) | reinterpret_cast<uintptr_t>(a->stats)) & 3u) != 0)
     return CTK_E_ALIGN;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
-  ResectionParams p;
-  p.G = a->G, p.N = a->N, p.N_out = a->N_out, p.R = a->R, p.f0 = a->f0, p.to = a->to, p.lag = a->lag, p.anchor_frame = a->anchor_frame;
   p.min_points = a->min_points, p.K = a->hypotheses, p.seed = a->seed;
   p.cap = a->N_out < CTK_RESECTION_LIST_MAX ? a->N_out : CTK_RESECTION_LIST_MAX;
-  p.sx = a->sx, p.sy = a->sy, p.thresh = a->thresh, p.tol = a->tol;
+  p.tol = a->tol;
   p.cam.fx = (double)a->fx, p.cam.fy = (double)a->fy, p.cam.cx = (double)a->cx, p.cam.cy = (double)a->cy;
-  p.hc = a->hist_coords, p.visible = a->visible, p.hv = a->hist_vis, p.hf = a->hist_conf, p.first_row = a->first_row;
-  p.ac = a->anchor_coords, p.av = a->anchor_visible;
   p.structure = a->structure, p.valid = a->valid, p.seed_pose = a->seed_pose;
   p.pose = a->pose, p.label = a->label, p.error = a->error, p.stats = a->stats;
   {
     CtkProfScope prof("fit_resection", 0.0, (double)a->G * a->F * (a->N_out * 50.0 + 100.0), s);
-    const size_t lds = (size_t)p.cap * RS_ENTRY_BYTES;
-    // (Beyond 64 KiB of LDS a kernel has to say so once; not a stream operation.  As pose.hip, from 48 KiB of dynamic LDS on: this
-    // kernel holds less than 12 KiB of static LDS beside it, 148 KiB of the CU's 160 KiB at most.)
-    if (lds > 49152) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fit_resection_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               CTK_RESECTION_LIST_MAX * RS_ENTRY_BYTES);
-    hipLaunchKernelGGL(fit_resection_kernel, dim3((unsigned)a->F, (unsigned)p.G), dim3(256), lds, s, p);
+    fit_launch(fit_resection_kernel, a->F, a->G, (size_t)p.cap * RS_ENTRY_BYTES, CTK_RESECTION_LIST_MAX * RS_ENTRY_BYTES, s, p);
   }
   CTK_HIP_CHECK_LAUNCH();
   return CTK_OK;

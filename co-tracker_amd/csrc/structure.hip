@@ -12,6 +12,7 @@
 // origin    thread 0 of the first workgroup of a group writes origin_out.
 #include "ctk_common.h"
 #include "ctk_profile.h"
+#include "fit_device.h"  // fit_scale_ok, fit_finite
 #include "structure_math.h"
 
 namespace {
@@ -127,9 +128,6 @@ __global__ __launch_bounds__(ST_BLOCK) void fit_structure_kernel(StructureParams
   so[0] = st[0], so[1] = st[1], so[2] = st[2], so[3] = st[3];
 }
 
-bool structure_scale_ok(float s) { return s > 0.0f && s <= 3.402823466e+38f; }
-bool structure_finite(float s) { return fabsf(s) <= 3.402823466e+38f; }
-
 // everything but the pointers (whether `visible` is given is looked at)
 int structure_check_shape(const ctk_fit_structure_args* a) {
   const long big = 1L << 30;
@@ -140,10 +138,10 @@ int structure_check_shape(const ctk_fit_structure_args* a) {
   if (a->source_frame < 0 || a->source_frame > big) return CTK_E_SHAPE;
   if (a->min_views < CTK_STRUCTURE_MIN_VIEWS || a->min_views > CTK_STRUCTURE_VIEWS_MAX) return CTK_E_SHAPE;
   if (a->refine < 0 || a->refine > 1) return CTK_E_SHAPE;
-  if (!structure_scale_ok(a->tol)) return CTK_E_SHAPE;
+  if (!fit_scale_ok(a->tol)) return CTK_E_SHAPE;
   if (!(a->min_sin2 > 0.0f && a->min_sin2 <= 1.0f)) return CTK_E_SHAPE;
-  if (!structure_scale_ok(a->fx) || !structure_scale_ok(a->fy) || !structure_finite(a->cx) || !structure_finite(a->cy)) return CTK_E_SHAPE;
-  if (!structure_scale_ok(a->sx) || !structure_scale_ok(a->sy)) return CTK_E_SHAPE;
+  if (!fit_scale_ok(a->fx) || !fit_scale_ok(a->fy) || !fit_finite(a->cx) || !fit_finite(a->cy)) return CTK_E_SHAPE;
+  if (!fit_scale_ok(a->sx) || !fit_scale_ok(a->sy)) return CTK_E_SHAPE;
   if (a->visible == nullptr && a->thresh != a->thresh) return CTK_E_SHAPE;
   return CTK_OK;
 }

@@ -37,6 +37,7 @@ def test_declared_bound_exported_and_abi(lib):
     makefile = open(os.path.join(ROOT, "co-tracker_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRCS = .*\bobjects\.hip\b", makefile, re.M) and re.search(r"^NOFMA = .*\bobjects\b", makefile, re.M)
     assert re.search(r"^HDRS = .*\bobjects_math\.h\b", makefile, re.M) and re.search(r"^HDRS = .*\bmotion_device\.h\b", makefile, re.M)
+    assert re.search(r"^HDRS = .*\bfit_device\.h\b", makefile, re.M)  # what the six fit kernels share
     # the release library carries no CTK_* string literal
     blob = open(L.LIB_PATH, "rb").read()
     assert not re.findall(rb"CTK_OBJECT\w*", blob)
