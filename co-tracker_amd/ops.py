@@ -26,7 +26,7 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _ptr_at(t: torch.Tensor, g0: int) -> int:
     """The address of t[g0:], without making the view."""
-    return t.data_ptr() + g0 * t.stride(0) * t.element_size()
+    return t.data_ptr() + g0 * t.stride(0) * t.element_size() if g0 else t.data_ptr()
 
 
 def _chk_f32(*ts):
@@ -317,8 +317,8 @@ def seed_points(frame: torch.Tensor, grid, bounds=None, radius: int = 3, margin:
 
 
 # ------------------------------------------------------------------------------------------
-# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks, fit_motion, track_field, fit_objects, fit_planes and fit_epipolar differ
-# in the history rows they need (`rows`) and in their own struct fields; StreamGroups has the other source, a stream's history.
+# readers of tracks: the tensor source (a finished result), stated once.  draw_tracks and the fit readers differ in the history rows
+# they need (`rows`) and in their own struct fields; StreamGroups has the other source, a stream's history.
 # ------------------------------------------------------------------------------------------
 _scratch_cache = {}
 
@@ -389,7 +389,7 @@ def _bind_tensors(a, tracks, visible, first_row, *, rows: int, f0: int, scale, F
 def _out_tuple(out, specs, device, who: str):
     """The outputs of a reader, specs = [(name, dtype, shape)]: allocated, or `out` checked against them."""
     if out is None:
-        return tuple(torch.empty(sh, device=device, dtype=dt) for _, dt, sh in specs)
+        return tuple([torch.empty(sh, device=device, dtype=dt) for _, dt, sh in specs])
     out = tuple(out)
     if len(out) != len(specs) or any(not isinstance(t_, torch.Tensor) or t_.device != device or t_.dtype != dt or tuple(t_.shape) != sh or
                                      not t_.is_contiguous() for t_, (_, dt, sh) in zip(out, specs)):
@@ -407,6 +407,201 @@ def _anchor_ptrs(anchor, G: int, N: int, device, who: str):
         raise ValueError(f"{who}: anchor must hold contiguous coords float32 [{G},{N},2] and visible uint8 [{G},{N}] on {device} and a "
                          f"frame >= 0")
     return anchor.frame, _ptr(c), _ptr(v.view(torch.uint8) if v.dtype == torch.bool else v)
+
+
+# ------------------------------------------------------------------------------------------
+# the fit readers (fit_motion, track_field, fit_objects, fit_planes, fit_epipolar, fit_pose, fit_resection, fit_structure and the
+# StreamGroups methods of the same names): the rules they share, each stated once; their two sources behind one interface; their one
+# launch.  A reader's body (_motion_fit ... _structure_fit) makes its args, applies its rules, binds its source with its own back / fwd
+# / to, and launches; the public functions build the source and call the body.
+# ------------------------------------------------------------------------------------------
+_F32, _I8, _I32, _BYTES = (torch.float32,), (torch.int8,), (torch.int32,), (torch.int8, torch.uint8, torch.bool)
+
+
+def _kinds(dtypes) -> str:
+    names = [str(d)[6:] for d in dtypes]
+    return names[0] if len(names) == 1 else ", ".join(names[:-1]) + " or " + names[-1]
+
+
+def _tensor_ptr(x, dtypes: tuple, shape: tuple, name: str, device, who: str, note: str = "") -> int:
+    """The pointer of x, checked: a contiguous tensor of one of `dtypes` and of `shape` on `device`; note: a trailing word on whose it is."""
+    if not (isinstance(x, torch.Tensor) and x.dtype in dtypes and x.device == device and tuple(x.shape) == shape and x.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous {_kinds(dtypes)} tensor {list(shape)} on {device}{note}")
+    return x.data_ptr()
+
+
+def _source_form(a, lag, to, anchor, G: int, N: int, device, who: str, flow: bool = False) -> None:
+    """Where the source frame of frame f is -- f - lag, a fixed frame `to`, or a FieldAnchor that matches G groups of N points --, as
+    the fields to, lag, anchor_frame, anchor_coords, anchor_visible of a reader's args.  `to` or `anchor` replaces the lag, which is
+    then not looked at; both at once are refused.  flow, track_field's form: exactly one of the three is given, and a negative lag
+    leads to the frame ahead."""
+    if flow and (to is not None) + (lag is not None) + (anchor is not None) != 1:
+        raise ValueError(f"{who}: exactly one of to (a frame), lag (frame f against f - lag) and anchor (FieldAnchor) says where the field leads")
+    if to is not None and anchor is not None:
+        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
+    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
+    if to is not None:
+        a.to = int(to)
+        if a.to < 0:
+            raise ValueError(f"{who}: to must be a frame >= 0")
+    elif anchor is not None:
+        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
+    else:
+        a.lag = lag = int(lag)
+        if lag == 0 or (lag < 0 and not flow):
+            raise ValueError(f"{who}: lag must " + ("not be 0 (negative: forward flow)" if flow else "be >= 1"))
+
+
+def _min_points_of(min_points, least: int, who: str) -> int:
+    min_points = int(min_points)
+    if not least <= min_points <= L.Motion.POINTS_MAX:
+        raise ValueError(f"{who}: min_points must lie in {least}..{L.Motion.POINTS_MAX}")
+    return min_points
+
+
+def _positive_tol(tol, who: str) -> float:
+    tol = float(tol)
+    if not (math.isfinite(tol) and 0.0 < tol <= 3.0e38):
+        raise ValueError(f"{who}: tol must be finite and > 0 (raw-video pixels)")
+    return tol
+
+
+def _sampling(a, hypotheses, seed, tol, min_base, who: str, resection: bool = False) -> None:
+    """The seeded hypotheses of a robust fit and its bounds.  ctk_fit_resection has a ceiling of its own, calls the count
+    `hypotheses`, takes any seed by its low 32 bits, wants a finite positive tol and has no min_base."""
+    hypotheses, seed = int(hypotheses), int(seed)
+    top = L.Resection.HYPOTHESES_MAX if resection else L.Motion.HYPOTHESES_MAX
+    if not 1 <= hypotheses <= top:
+        raise ValueError(f"{who}: hypotheses must lie in 1..{top}")
+    if resection:
+        a.hypotheses, a.seed, a.tol = hypotheses, seed & 0xffffffff, _positive_tol(tol, who)
+        return
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{who}: seed must lie in 0..2^32 - 1")
+    a.K, a.seed, a.tol, a.min_base, a.reserved = hypotheses, seed, float(tol), float(min_base), 0
+
+
+def _intrinsics(a, intrinsics, who: str) -> None:
+    if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
+        raise ValueError(f"{who}: intrinsics must be four Python floats (fx, fy, cx, cy) in raw-video pixels")
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
+    a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
+
+
+def _frame_pair(frames):
+    """frames = (first_frame, n), or None: every tracked frame -> what _frames_of takes."""
+    return (0, None) if frames is None else (frames[0], int(frames[1]))
+
+
+def _group_axis(x, dims: int):
+    """A per-group input of the tensor form given without its group axis (`dims` axes) gets it."""
+    return x[None] if isinstance(x, torch.Tensor) and x.dim() == dims else x
+
+
+class _FitSource:
+    """What the body of a fit reader asks of its source: who is called, the G groups of N points and the device that its own inputs
+    must match, the N_out points and F frames of its outputs, bind() for the source fields of its args."""
+    __slots__ = ("who", "G", "N", "N_out", "f0", "F", "device", "first_row", "scale")
+
+    def per_point_ptr(self, x, dtypes, name: str) -> Optional[int]:
+        """The pointer of a per-point list (labels, mask) [N] / [G,N] of the groups read, or None."""
+        if x is None:
+            return None
+        if not (isinstance(x, torch.Tensor) and x.dtype in dtypes and x.device == self.device and x.numel() == self.G * self.N and
+                x.shape[-1] == self.N and x.is_contiguous()):
+            raise ValueError(f"{self.who}: {name} must be a contiguous {_kinds(dtypes)} tensor [{self.N}] or [{self.G},{self.N}] on {self.device}")
+        return _ptr(x)
+
+
+class _TensorSource(_FitSource):
+    """A finished result as the source of a fit reader: tracks [T,N,2] / [G,T,N,2] and visible checked (_track_tensors), the frames
+    [f0, f0 + F) of them (_frames_of), all N points unless the reader takes an N_out (at most out_max)."""
+    __slots__ = ("tracks", "visible", "T", "kept")
+
+    def __init__(self, who: str, tracks, visible, first_frame=0, frames=None, *, first_row=None, scale=(1, 1), N_out=None,
+                 points_max: Optional[int] = L.Motion.POINTS_MAX, out_max: Optional[int] = None):
+        self.who, self.first_row, self.scale = who, first_row, scale
+        self.tracks, self.visible, self.G, self.T, self.N, self.device = _track_tensors(tracks, visible, who, points_max)
+        self.N_out = self.N if N_out is None else int(N_out)
+        if out_max is not None and not 1 <= self.N_out <= min(self.N, out_max):
+            raise ValueError(f"{who}: N_out must lie in [1, {min(self.N, out_max)}]")
+        self.f0, self.F = _frames_of(first_frame, frames, self.T, who)
+
+    def per_point_ptr(self, x, dtypes, name: str) -> Optional[int]:
+        """labels / mask [N] serve every group: the copy lives as long as the source, that is until the launch is issued."""
+        if isinstance(x, torch.Tensor) and x.dim() == 1 and self.G > 1:
+            x = self.kept = x.expand(self.G, -1).contiguous()
+        return super().per_point_ptr(x, dtypes, name)
+
+    def bind(self, a, back: int = 0, fwd: int = 0, to: int = -1, hint: str = "") -> None:
+        """The source fields of `a` for a reader that reads, besides its frames, the `back` frames before each, the frame `fwd` after
+        each and the frame `to`: the rows one call reads are kept apart (_bind_tensors), so there are at least F + back + fwd."""
+        if to >= self.T:
+            raise ValueError(f"{self.who}: to = {to} of {self.T} tracked frames")
+        _bind_tensors(a, self.tracks, self.visible, _first_row_i32(self.first_row, self.G, self.N, self.device),
+                      rows=max(self.T, self.F + back + fwd, self.f0 + self.F + fwd), f0=self.f0, F=self.F, N_out=self.N_out, scale=self.scale)
+
+
+class _HistorySource(_FitSource):
+    """A stream's history as the source of a fit reader: whom it reads (StreamGroups._reader), which frames it may (_held, with the
+    reader's back / fwd / to) and the source fields (_bind_history).  N is the stream's: labels, masks and anchors match it; outputs
+    and what an earlier reader wrote per point match N_out."""
+    __slots__ = ("gs", "g0", "thresh")
+
+    def __init__(self, gs, who: str, f0, F, N_out, group, first_row, scale, thresh, points_max: int = L.Motion.POINTS_MAX):
+        self.N_out, self.g0, self.G = gs._reader(who, N_out, group, first_row, points_max)
+        self.gs, self.who, self.first_row, self.scale, self.thresh = gs, who, first_row, scale, thresh
+        self.f0, self.F, self.N, self.device = int(f0), int(F), gs.N, gs.queries.device
+
+    def bind(self, a, back: int = 0, fwd: int = 0, to: int = -1, hint: str = "") -> None:
+        self.gs._held(self.who, self.f0, self.F, back=back, fwd=fwd, to=to, hint=hint)
+        self.gs._bind_history(a, self.g0, self.G, self.N_out, self.f0, self.F, self.scale, self.thresh, self.first_row)
+
+
+def _field_outs(G: int, F: int, H: int, W: int, cs: int):
+    gh, gw = ((H - 1) >> cs) + 2, ((W - 1) >> cs) + 2  # (field_grid's nodes)
+    return [("field", torch.int32, (G, F, gh, gw, 2)), ("level", torch.uint8, (G, F, gh, gw)), ("stats", torch.int32, (G, F, 4))]
+
+
+_Fit = namedtuple("_Fit", "args entry scratch outs")  # outs: (G, F, N_out, args) -> [(the struct field of an output = its name, dtype, shape)]
+_FITS = {
+    "motion": _Fit(L.Motion.Args, "ctk_fit_motion", "motion", lambda G, F, n, a: [
+        ("motion", torch.float32, (G, F, 2, 3)), ("inlier", torch.int8, (G, F, n)), ("stats", torch.int32, (G, F, 4))]),
+    "field": _Fit(L.Field.Args, "ctk_track_field", "field", lambda G, F, n, a: _field_outs(G, F, a.H, a.W, a.cs)),
+    "objects": _Fit(L.Objects.Args, "ctk_fit_objects", "motion", lambda G, F, n, a: [
+        ("motion", torch.float32, (G, F, a.L, 2, 3)), ("label", torch.int8, (G, F, n)), ("stats", torch.int32, (G, F, a.L, 4)),
+        ("box", torch.int32, (G, F, a.L, 4))]),
+    "planes": _Fit(L.Planes.Args, "ctk_fit_planes", "motion", lambda G, F, n, a: [
+        ("homography", torch.float32, (G, F, a.L, 3, 3)), ("label", torch.int8, (G, F, n)), ("stats", torch.int32, (G, F, a.L, 4)),
+        ("box", torch.int32, (G, F, a.L, 4))]),
+    "epipolar": _Fit(L.Epipolar.Args, "ctk_fit_epipolar", "motion", lambda G, F, n, a: [
+        ("fundamental", torch.float32, (G, F, 3, 3)), ("label", torch.int8, (G, F, n)), ("error", torch.float32, (G, F, n)),
+        ("stats", torch.int32, (G, F, 4))]),
+    "pose": _Fit(L.Pose.Args, "ctk_fit_pose", "motion", lambda G, F, n, a: [
+        ("pose", torch.float32, (G, F, 3, 4)), ("depth", torch.float32, (G, F, n, 2)), ("stats", torch.int32, (G, F, 4))]),
+    "resection": _Fit(L.Resection.Args, "ctk_fit_resection", "motion", lambda G, F, n, a: [
+        ("pose", torch.float32, (G, F, 3, 4)), ("label", torch.int8, (G, F, n)), ("error", torch.float32, (G, F, n)),
+        ("stats", torch.int32, (G, F, 4))]),
+    "structure": _Fit(L.Structure3D.Args, "ctk_fit_structure", "motion", lambda G, F, n, a: [
+        ("points", torch.float32, (G, n, 3)), ("label", torch.int8, (G, n)), ("error", torch.float32, (G, n)), ("stats", torch.int32, (G, n, 4)),
+        ("origin_out", torch.float32, (G, 3, 4))]),
+}
+
+
+def _fit_launch(kind: str, a, out, device, who: str):
+    """The launch of a fit reader, by its row of _FITS: the outputs for the G, F and N_out of `a` allocated (or `out` checked) and
+    their pointers written, the workspace asked for and taken from the scratch buffer of the row's kind, the entry point called."""
+    _, entry, scratch, outs = _FITS[kind]
+    specs = outs(a.G, a.F, a.N_out, a)
+    out = _out_tuple(out, specs, device, who)
+    for (name, _, _), t_ in zip(specs, out):
+        setattr(a, name, t_.data_ptr())
+    ref = C.byref(a)
+    ws = _scratch(scratch, _query_bytes(entry + "_workspace_bytes", ref), device)
+    L.check(getattr(L.load(), entry)(ref, ws.data_ptr(), ws.numel(), _stream()), entry)
+    return out
 
 
 # ------------------------------------------------------------------------------------------
@@ -539,23 +734,21 @@ def draw_tracks(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tenso
 MOTION_MODELS = {"translation": L.Motion.TRANSLATION, "similarity": L.Motion.SIMILARITY}
 
 
-def _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who: str) -> None:
+def _model_of(model, who: str) -> int:
     if model not in MOTION_MODELS:
         raise ValueError(f"{who}: model must be one of {sorted(MOTION_MODELS)}, got {model!r}")
-    lag, hypotheses, seed = int(lag), int(hypotheses), int(seed)
-    if lag < 1 or not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
-        raise ValueError(f"{who}: lag must be >= 1, hypotheses in 1..{L.Motion.HYPOTHESES_MAX}, seed in 0..2^32 - 1")
-    a.lag, a.model, a.K, a.seed, a.tol, a.min_base, a.reserved = lag, MOTION_MODELS[model], hypotheses, seed, float(tol), float(min_base), 0
+    return MOTION_MODELS[model]
 
 
-def _motion_launch(a, device, out, who: str):
-    """Allocates (or checks) the three outputs of ctk_fit_motion for the G, F, N_out of `a`, then the launch."""
-    out = _out_tuple(out, [("motion", torch.float32, (a.G, a.F, 2, 3)), ("inlier", torch.int8, (a.G, a.F, a.N_out)),
-                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
-    a.motion, a.inlier, a.stats = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_motion_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_motion(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_motion")
-    return out
+def _motion_fit(src, lag, model, tol, hypotheses, min_base, seed, out):
+    a, who = _FITS["motion"].args(), src.who
+    lag = int(lag)
+    if lag < 1:  # (ctk_fit_motion has the lag form alone: no `to`, no anchor, no _source_form)
+        raise ValueError(f"{who}: lag must be >= 1")
+    a.lag, a.model = lag, _model_of(model, who)
+    _sampling(a, hypotheses, seed, tol, min_base, who)
+    src.bind(a, back=lag, hint=": fit fewer frames per call")
+    return _fit_launch("motion", a, out, src.device, who)
 
 
 def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, model: str = "similarity", tol: float = 2.0,
@@ -574,13 +767,8 @@ def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, mod
     destination = motion @ (source, 1); inlier int8 [G,F,N]: -1 no correspondence, 0 outlier, 1 inlier; stats int32 [G,F,4] =
     (correspondences, inliers, best hypothesis or -1, 0)) -- `out` when given.  A frame without an admissible hypothesis (among
     them every f < lag) has the identity."""
-    who = "fit_motion"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    f0, F_ = _frames_of(first_frame, frames, T, who)
-    a = L.Motion.Args()
-    _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
-    _bind_tensors(a, tracks, visible, None, rows=F_ + a.lag, f0=f0, F=F_, scale=scale)
-    return _motion_launch(a, dev, out, who)
+    src = _TensorSource("fit_motion", tracks, visible, first_frame, frames, scale=scale)
+    return _motion_fit(src, lag, model, tol, hypotheses, min_base, seed, out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -759,36 +947,15 @@ def field_grid(size, cell: int = 16):
     return ((int(size[0]) - 1) >> cs) + 2, ((int(size[1]) - 1) >> cs) + 2
 
 
-def _field_rules(a, size, cell, radius, to, lag, anchor, G: int, N: int, device, who: str) -> None:
-    """The picture, the grid and the "to" form of ctk_track_field_args; G, N: what an anchor must match."""
+def _field_fit(src, size, cell, radius, to, lag, anchor, out):
+    a, who = _FITS["field"].args(), src.who
     H, W, radius = int(size[0]), int(size[1]), int(radius)
     if not (1 <= H <= 32768 and 1 <= W <= 32768 and 1 <= radius <= L.Field.RADIUS_MAX):
         raise ValueError(f"{who}: size = (H, W) must lie in 1..32768 and radius in 1..{L.Field.RADIUS_MAX}")
-    if (to is not None) + (lag is not None) + (anchor is not None) != 1:
-        raise ValueError(f"{who}: exactly one of to (a frame), lag (frame f against f - lag) and anchor (FieldAnchor) says where the field leads")
     a.H, a.W, a.cs, a.radius, a.reserved = H, W, _field_cs(cell, who), radius, 0
-    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
-    if to is not None:
-        a.to = int(to)
-        if a.to < 0:
-            raise ValueError(f"{who}: to must be a frame >= 0")
-    elif lag is not None:
-        a.lag = int(lag)
-        if a.lag == 0:
-            raise ValueError(f"{who}: lag must not be 0 (negative: forward flow)")
-    else:
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
-
-
-def _field_launch(a, device, out, who: str):
-    """Allocates (or checks) the three outputs of ctk_track_field for the G, F and grid of `a`, then the three launches."""
-    gh, gw = ((a.H - 1) >> a.cs) + 2, ((a.W - 1) >> a.cs) + 2
-    out = _out_tuple(out, [("field", torch.int32, (a.G, a.F, gh, gw, 2)), ("level", torch.uint8, (a.G, a.F, gh, gw)),
-                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
-    a.field, a.level, a.stats = (_ptr(t_) for t_ in out)
-    ws = _scratch("field", _query_bytes("ctk_track_field_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_track_field(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_track_field")
-    return out
+    _source_form(a, lag, to, anchor, src.G, src.N, src.device, who, flow=True)
+    src.bind(a, back=max(a.lag, 0), fwd=max(-a.lag, 0), to=a.to)  # (a negative lag reads the frame ahead)
+    return _fit_launch("field", a, out, src.device, who)
 
 
 def track_field(tracks: torch.Tensor, visible: torch.Tensor, *, size, cell: int = 16, radius: int = 2, to: Optional[int] = None,
@@ -808,19 +975,9 @@ def track_field(tracks: torch.Tensor, visible: torch.Tensor, *, size, cell: int 
     Rows are the frames first_frame .. first_frame + frames - 1 (default: to the end).  Returns (field int32 [G,F,gh,gw,2] in 1/256
     pixel, node (i, j) at pixel (i cell, j cell); level uint8 [G,F,gh,gw]: 0 own support, l filled from pyramid level l, 255 nothing;
     stats int32 [G,F,4] = (correspondences, nodes at level 0, highest level used, 0)) -- `out` when given."""
-    who = "track_field"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who)
-    N_out = N if N_out is None else int(N_out)
-    if not 1 <= N_out <= min(N, L.Field.POINTS_MAX):
-        raise ValueError(f"{who}: N_out must lie in [1, {min(N, L.Field.POINTS_MAX)}]")
-    f0, F_ = _frames_of(first_frame, frames, T, who)
-    a = L.Field.Args()
-    _field_rules(a, size, cell, radius, to, lag, anchor, G, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + abs(a.lag), f0 + F_ + max(-a.lag, 0)),
-                  f0=f0, F=F_, N_out=N_out, scale=scale)
-    return _field_launch(a, dev, out, who)
+    src = _TensorSource("track_field", tracks, visible, first_frame, frames, first_row=first_row, scale=scale, N_out=N_out, points_max=None,
+                        out_max=L.Field.POINTS_MAX)
+    return _field_fit(src, size, cell, radius, to, lag, anchor, out)
 
 
 def _field_surface(pics: torch.Tensor, layout: Optional[str], who: str):
@@ -966,41 +1123,17 @@ class ObjectSet:
         self.labels, self.anchor, self.objects = labels, anchor, int(objects)
 
 
-def _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device,
-                   who: str) -> None:
-    """The rounds, the fit and the source form of ctk_fit_objects_args; G, N: what labels and an anchor must match.  `to` or `anchor`
-    replaces the lag; both at once are refused."""
-    objects, min_points = int(objects), int(min_points)
-    if not 1 <= objects <= L.Objects.OBJECTS_MAX or not 1 <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: objects must lie in 1..{L.Objects.OBJECTS_MAX} and min_points in 1..{L.Motion.POINTS_MAX}")
-    if to is not None and anchor is not None:
-        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
-    _motion_rules(a, 1 if (to is not None or anchor is not None) else lag, model, tol, hypotheses, min_base, seed, who)
-    a.L, a.min_points = objects, min_points
-    a.to, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, None, None
-    if to is not None:
-        a.to, a.lag = int(to), 0
-        if a.to < 0:
-            raise ValueError(f"{who}: to must be a frame >= 0")
-    elif anchor is not None:
-        a.lag = 0
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
-    a.labels = None
-    if labels is not None:
-        if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int8 and labels.device == device and labels.numel() == G * N and
-                labels.shape[-1] == N and labels.is_contiguous()):
-            raise ValueError(f"{who}: labels must be a contiguous int8 tensor [{N}] or [{G},{N}] on {device}")
-        a.labels = _ptr(labels)
-
-
-def _objects_launch(a, device, who: str):
-    """Allocates the four outputs of ctk_fit_objects for the G, F, L and N_out of `a`, then the launch."""
-    out = _out_tuple(None, [("motion", torch.float32, (a.G, a.F, a.L, 2, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
-                            ("stats", torch.int32, (a.G, a.F, a.L, 4)), ("box", torch.int32, (a.G, a.F, a.L, 4))], device, who)
-    a.motion, a.label, a.stats, a.box = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_objects_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_objects(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_objects")
-    return out
+def _objects_fit(src, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed):
+    a, who = _FITS["objects"].args(), src.who
+    objects = int(objects)
+    if not 1 <= objects <= L.Objects.OBJECTS_MAX:
+        raise ValueError(f"{who}: objects must lie in 1..{L.Objects.OBJECTS_MAX}")
+    a.L, a.min_points, a.model = objects, _min_points_of(min_points, 1, who), _model_of(model, who)
+    _sampling(a, hypotheses, seed, tol, min_base, who)
+    _source_form(a, lag, to, anchor, src.G, src.N, src.device, who)
+    a.labels = src.per_point_ptr(labels, _I8, "labels")
+    src.bind(a, back=a.lag, to=a.to)  # (_source_form: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
+    return _fit_launch("objects", a, None, src.device, who)
 
 
 def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional[torch.Tensor] = None, objects: int = 4, lag: int = 1,
@@ -1025,17 +1158,8 @@ def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional
     round r, 127 (OBJECT_NONE) = no round took it; stats int32 [G,F,objects,4] = (points of the round, inliers, best hypothesis or -1,
     0); box int32 [G,F,objects,4] = (min x, min y, max x, max y) of the round's inliers on frame f in 1/16 pixel, (0, 0, -1, -1) where
     nothing was fitted)."""
-    who = "fit_objects"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    f0, F_ = _frames_of(0, None, T, who) if frames is None else _frames_of(frames[0], int(frames[1]), T, who)
-    a = L.Objects.Args()
-    if isinstance(labels, torch.Tensor) and labels.dim() == 1 and G > 1:
-        labels = labels.expand(G, -1).contiguous()
-    _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + a.lag), f0=f0, F=F_, scale=scale)
-    return _objects_launch(a, dev, who)
+    src = _TensorSource("fit_objects", tracks, visible, *_frame_pair(frames), first_row=first_row, scale=scale)
+    return _objects_fit(src, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1044,48 +1168,19 @@ def fit_objects(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional
 PLANE_BORDERS = {"fill": L.Warp.BORDER_FILL, "edge": L.Warp.BORDER_EDGE, "keep": L.Planes.BORDER_KEEP}
 
 
-def _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device,
-                  who: str) -> None:
-    """The rounds, the fit and the source form of ctk_fit_planes_args; G, N: what labels and an anchor must match.  `to` or `anchor`
-    replaces the lag; both at once are refused."""
-    planes, min_points, hypotheses, seed = int(planes), int(min_points), int(hypotheses), int(seed)
-    if not 1 <= planes <= L.Planes.PLANES_MAX or not 1 <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: planes must lie in 1..{L.Planes.PLANES_MAX} and min_points in 1..{L.Motion.POINTS_MAX}")
+def _planes_fit(src, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed):
+    a, who = _FITS["planes"].args(), src.who
+    planes = int(planes)
+    if not 1 <= planes <= L.Planes.PLANES_MAX:
+        raise ValueError(f"{who}: planes must lie in 1..{L.Planes.PLANES_MAX}")
     if labels is None and planes != 1:
         raise ValueError(f"{who}: without labels there is one list of all points: planes must be 1, got {planes}")
-    if to is not None and anchor is not None:
-        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
-    if not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
-        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Motion.HYPOTHESES_MAX} and seed in 0..2^32 - 1")
-    a.L, a.min_points, a.inverse, a.K, a.seed = planes, min_points, 1 if inverse else 0, hypotheses, seed
-    a.tol, a.min_base, a.reserved = float(tol), float(min_base), 0
-    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
-    if to is not None:
-        a.to = int(to)
-        if a.to < 0:
-            raise ValueError(f"{who}: to must be a frame >= 0")
-    elif anchor is not None:
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
-    else:
-        a.lag = int(lag)
-        if a.lag < 1:
-            raise ValueError(f"{who}: lag must be >= 1")
-    a.labels = None
-    if labels is not None:
-        if not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int8 and labels.device == device and labels.numel() == G * N and
-                labels.shape[-1] == N and labels.is_contiguous()):
-            raise ValueError(f"{who}: labels must be a contiguous int8 tensor [{N}] or [{G},{N}] on {device}")
-        a.labels = _ptr(labels)
-
-
-def _planes_launch(a, device, who: str):
-    """Allocates the four outputs of ctk_fit_planes for the G, F, L and N_out of `a`, then the launch."""
-    out = _out_tuple(None, [("homography", torch.float32, (a.G, a.F, a.L, 3, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
-                            ("stats", torch.int32, (a.G, a.F, a.L, 4)), ("box", torch.int32, (a.G, a.F, a.L, 4))], device, who)
-    a.homography, a.label, a.stats, a.box = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_planes_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_planes(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_planes")
-    return out
+    a.L, a.min_points, a.inverse = planes, _min_points_of(min_points, 1, who), 1 if inverse else 0
+    _sampling(a, hypotheses, seed, tol, min_base, who)
+    _source_form(a, lag, to, anchor, src.G, src.N, src.device, who)
+    a.labels = src.per_point_ptr(labels, _I8, "labels")
+    src.bind(a, back=a.lag, to=a.to)
+    return _fit_launch("planes", a, None, src.device, who)
 
 
 def fit_planes(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional[torch.Tensor] = None, planes: int = 1, lag: int = 1,
@@ -1109,17 +1204,8 @@ def fit_planes(tracks: torch.Tensor, visible: torch.Tensor, *, labels: Optional[
     127 = no plane took it; stats int32 [G,F,planes,4] = (points of the plane, inliers, best hypothesis or -1, 1 if the refit fell back
     to the best sample's own matrix); box int32 [G,F,planes,4] = (min x, min y, max x, max y) of the inliers on frame f in 1/16 pixel,
     (0, 0, -1, -1) where nothing was fitted)."""
-    who = "fit_planes"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    f0, F_ = _frames_of(0, None, T, who) if frames is None else _frames_of(frames[0], int(frames[1]), T, who)
-    a = L.Planes.Args()
-    if isinstance(labels, torch.Tensor) and labels.dim() == 1 and G > 1:
-        labels = labels.expand(G, -1).contiguous()
-    _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=max(T, F_ + a.lag), f0=f0, F=F_, scale=scale)
-    return _planes_launch(a, dev, who)
+    src = _TensorSource("fit_planes", tracks, visible, *_frame_pair(frames), first_row=first_row, scale=scale)
+    return _planes_fit(src, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed)
 
 
 def warp_planes(src: torch.Tensor, matrices: torch.Tensor, *, size=None, out: Optional[torch.Tensor] = None, border: str = "fill",
@@ -1380,45 +1466,14 @@ def corrblock_sample(pyr_nhwc: Sequence[torch.Tensor], targets: torch.Tensor, co
 # ------------------------------------------------------------------------------------------
 # fit epipolar (csrc/epipolar.hip; include/ctk.h, "fit epipolar")
 # ------------------------------------------------------------------------------------------
-def _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G: int, N: int, device, who: str) -> None:
-    """The fit and the source form of ctk_fit_epipolar_args; G, N: what a mask and an anchor must match.  `to` or `anchor` replaces
-    the lag; both at once are refused."""
-    min_points, hypotheses, seed = int(min_points), int(hypotheses), int(seed)
-    if not L.Epipolar.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: min_points must lie in {L.Epipolar.MIN_POINTS}..{L.Motion.POINTS_MAX}")
-    if to is not None and anchor is not None:
-        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
-    if not 1 <= hypotheses <= L.Motion.HYPOTHESES_MAX or not 0 <= seed < 2 ** 32:
-        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Motion.HYPOTHESES_MAX} and seed in 0..2^32 - 1")
-    a.min_points, a.K, a.seed = min_points, hypotheses, seed
-    a.tol, a.min_base, a.reserved = float(tol), float(min_base), 0
-    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
-    if to is not None:
-        a.to = int(to)
-        if a.to < 0:
-            raise ValueError(f"{who}: to must be a frame >= 0")
-    elif anchor is not None:
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
-    else:
-        a.lag = int(lag)
-        if a.lag < 1:
-            raise ValueError(f"{who}: lag must be >= 1")
-    a.mask = None
-    if mask is not None:
-        if not (isinstance(mask, torch.Tensor) and mask.dtype in (torch.int8, torch.uint8, torch.bool) and mask.device == device and
-                mask.numel() == G * N and mask.shape[-1] == N and mask.is_contiguous()):
-            raise ValueError(f"{who}: mask must be a contiguous int8, uint8 or bool tensor [{N}] or [{G},{N}] on {device}")
-        a.mask = _ptr(mask)
-
-
-def _epipolar_launch(a, device, out, who: str):
-    """Allocates (or checks) the four outputs of ctk_fit_epipolar for the G, F and N_out of `a`, then the launch."""
-    out = _out_tuple(out, [("fundamental", torch.float32, (a.G, a.F, 3, 3)), ("label", torch.int8, (a.G, a.F, a.N_out)),
-                           ("error", torch.float32, (a.G, a.F, a.N_out)), ("stats", torch.int32, (a.G, a.F, 4))], device, who)
-    a.fundamental, a.label, a.error, a.stats = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_epipolar_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_epipolar(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_epipolar")
-    return out
+def _epipolar_fit(src, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, out):
+    a, who = _FITS["epipolar"].args(), src.who
+    a.min_points = _min_points_of(min_points, L.Epipolar.MIN_POINTS, who)
+    _sampling(a, hypotheses, seed, tol, min_base, who)
+    _source_form(a, lag, to, anchor, src.G, src.N, src.device, who)
+    a.mask = src.per_point_ptr(mask, _BYTES, "mask")
+    src.bind(a, back=a.lag, to=a.to)
+    return _fit_launch("epipolar", a, out, src.device, who)
 
 
 def fit_epipolar(tracks: torch.Tensor, visible: torch.Tensor, *, mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None,
@@ -1443,77 +1498,23 @@ def fit_epipolar(tracks: torch.Tensor, visible: torch.Tensor, *, mask: Optional[
     that may be fitted on, inliers among them, best hypothesis or -1, bit 0 / 1: the first / second refit fell back)); `out`: such a
     tuple to write into.  F is not unique without parallax (a plane, a camera that only turns or stands): the labels then still mean
     "consistent with some camera motion"; a point that moves along its own epipolar line is not seen."""
-    who = "fit_epipolar"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    a = L.Epipolar.Args()
-    if isinstance(mask, torch.Tensor) and mask.dim() == 1 and G > 1:
-        mask = mask.expand(G, -1).contiguous()
-    _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
-    return _epipolar_launch(a, dev, out, who)
+    src = _TensorSource("fit_epipolar", tracks, visible, first_row=first_row, scale=scale)
+    return _epipolar_fit(src, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, out)
 
 
 # ------------------------------------------------------------------------------------------
 # fit pose (csrc/pose.hip; include/ctk.h, "fit pose")
 # ------------------------------------------------------------------------------------------
-def _camera_and_source(a, intrinsics, lag, to, anchor, G: int, N: int, device, who: str) -> None:
-    """The four intrinsics and the source form (lag / to / anchor) of ctk_fit_pose_args and ctk_fit_resection_args.  `to` or `anchor`
-    replaces the lag; both at once are refused.  Nothing here waits on the device."""
-    if to is not None and anchor is not None:
-        raise ValueError(f"{who}: one of to (a frame) and anchor (FieldAnchor) says where the motion starts, not both")
-    if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
-        raise ValueError(f"{who}: intrinsics must be four Python floats (fx, fy, cx, cy) in raw-video pixels")
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
-        raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
-    a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
-    a.to, a.lag, a.anchor_frame, a.anchor_coords, a.anchor_visible = -1, 0, 0, None, None
-    if to is not None:
-        a.to = int(to)
-        if a.to < 0:
-            raise ValueError(f"{who}: to must be a frame >= 0")
-    elif anchor is not None:
-        a.anchor_frame, a.anchor_coords, a.anchor_visible = _anchor_ptrs(anchor, G, N, device, who)
-    else:
-        a.lag = int(lag)
-        if a.lag < 1:
-            raise ValueError(f"{who}: lag must be >= 1")
-
-
-def _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G: int, F: int, N: int, N_out: int, device,
-                who: str) -> None:
-    """The camera, the inputs that ctk_fit_epipolar wrote and the source form of ctk_fit_pose_args; G, F, N, N_out: what they must
-    match.  `to` or `anchor` replaces the lag; both at once are refused.  Nothing here waits on the device."""
-    min_points = int(min_points)
-    if not L.Pose.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: min_points must lie in {L.Pose.MIN_POINTS}..{L.Motion.POINTS_MAX}")
-    _camera_and_source(a, intrinsics, lag, to, anchor, G, N, device, who)
-    a.min_points, a.reserved = min_points, 0
-    if not (isinstance(fundamental, torch.Tensor) and fundamental.dtype == torch.float32 and fundamental.device == device and
-            tuple(fundamental.shape) == (G, F, 3, 3) and fundamental.is_contiguous()):
-        raise ValueError(f"{who}: fundamental must be a contiguous float32 tensor [{G},{F},3,3] on {device} (fit_epipolar's)")
-    if not (isinstance(label, torch.Tensor) and label.dtype == torch.int8 and label.device == device and
-            tuple(label.shape) == (G, F, N_out) and label.is_contiguous()):
-        raise ValueError(f"{who}: label must be a contiguous int8 tensor [{G},{F},{N_out}] on {device} (fit_epipolar's)")
-    a.fundamental, a.label = _ptr(fundamental), _ptr(label)
-    a.mask = None
-    if mask is not None:
-        if not (isinstance(mask, torch.Tensor) and mask.dtype in (torch.int8, torch.uint8, torch.bool) and mask.device == device and
-                mask.numel() == G * N and mask.shape[-1] == N and mask.is_contiguous()):
-            raise ValueError(f"{who}: mask must be a contiguous int8, uint8 or bool tensor [{N}] or [{G},{N}] on {device}")
-        a.mask = _ptr(mask)
-
-
-def _pose_launch(a, device, out, who: str):
-    """Allocates (or checks) the three outputs of ctk_fit_pose for the G, F and N_out of `a`, then the launch."""
-    out = _out_tuple(out, [("pose", torch.float32, (a.G, a.F, 3, 4)), ("depth", torch.float32, (a.G, a.F, a.N_out, 2)),
-                           ("stats", torch.int32, (a.G, a.F, 4))], device, who)
-    a.pose, a.depth, a.stats = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_pose_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_pose(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_pose")
-    return out
+def _pose_fit(src, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, out):
+    a, who, dev = _FITS["pose"].args(), src.who, src.device
+    a.min_points, a.reserved = _min_points_of(min_points, L.Pose.MIN_POINTS, who), 0
+    _intrinsics(a, intrinsics, who)
+    _source_form(a, lag, to, anchor, src.G, src.N, dev, who)
+    a.fundamental = _tensor_ptr(fundamental, _F32, (src.G, src.F, 3, 3), "fundamental", dev, who, " (fit_epipolar's)")
+    a.label = _tensor_ptr(label, _I8, (src.G, src.F, src.N_out), "label", dev, who, " (fit_epipolar's)")
+    a.mask = src.per_point_ptr(mask, _BYTES, "mask")
+    src.bind(a, back=a.lag, to=a.to)
+    return _fit_launch("pose", a, out, dev, who)
 
 
 def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamental: torch.Tensor, label: torch.Tensor, *,
@@ -1535,16 +1536,8 @@ def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamenta
     the chosen candidate or -1, bit 0 / 1: the first / second round fell back, bit 2: an entry was left out of a round)); `out`: such a
     tuple to write into.  A fit needs min_points (>= 8) points labelled 1.  The scale is unknown and changes from frame to frame; no
     parallax (a camera that only turns or stands, a plane) means no pose: look at stats[..., 1] / stats[..., 0]."""
-    who = "fit_pose"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    a = L.Pose.Args()
-    if isinstance(mask, torch.Tensor) and mask.dim() == 1 and G > 1:
-        mask = mask.expand(G, -1).contiguous()
-    _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G, T, N, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
-    return _pose_launch(a, dev, out, who)
+    src = _TensorSource("fit_pose", tracks, visible, first_row=first_row, scale=scale)
+    return _pose_fit(src, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1594,39 +1587,17 @@ def structure_from_pose(tracks_row: torch.Tensor, intrinsics, depth: torch.Tenso
     return torch.where(ok[..., None], pts, torch.zeros_like(pts)), ok.to(torch.int8)
 
 
-def _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G: int, F: int, N: int,
-                     device, who: str) -> None:
-    """The camera, the structure, the seed poses, the fit and the source form of ctk_fit_resection_args; G, F, N: what they must
-    match.  Nothing here waits on the device."""
-    min_points, hypotheses, tol = int(min_points), int(hypotheses), float(tol)
-    if not L.Resection.MIN_POINTS <= min_points <= L.Motion.POINTS_MAX:
-        raise ValueError(f"{who}: min_points must lie in {L.Resection.MIN_POINTS}..{L.Motion.POINTS_MAX}")
-    if not 1 <= hypotheses <= L.Resection.HYPOTHESES_MAX:
-        raise ValueError(f"{who}: hypotheses must lie in 1..{L.Resection.HYPOTHESES_MAX}")
-    if not (math.isfinite(tol) and 0.0 < tol <= 3.0e38):
-        raise ValueError(f"{who}: tol must be finite and > 0 (raw-video pixels)")
-    _camera_and_source(a, intrinsics, lag, to, anchor, G, N, device, who)
-    a.min_points, a.hypotheses, a.seed, a.tol = min_points, hypotheses, int(seed) & 0xffffffff, tol
-    if not (isinstance(structure, torch.Tensor) and structure.dtype == torch.float32 and structure.device == device and
-            tuple(structure.shape) == (G, N, 3) and structure.is_contiguous()):
-        raise ValueError(f"{who}: structure must be a contiguous float32 tensor [{G},{N},3] on {device}")
-    if not (isinstance(valid, torch.Tensor) and valid.dtype in (torch.int8, torch.uint8, torch.bool) and valid.device == device and
-            tuple(valid.shape) == (G, N) and valid.is_contiguous()):
-        raise ValueError(f"{who}: valid must be a contiguous int8, uint8 or bool tensor [{G},{N}] on {device}")
-    if not (isinstance(seed_pose, torch.Tensor) and seed_pose.dtype == torch.float32 and seed_pose.device == device and
-            tuple(seed_pose.shape) == (G, F, 3, 4) and seed_pose.is_contiguous()):
-        raise ValueError(f"{who}: seed_pose must be a contiguous float32 tensor [{G},{F},3,4] on {device} (fit_pose's)")
-    a.structure, a.valid, a.seed_pose = _ptr(structure), _ptr(valid), _ptr(seed_pose)
-
-
-def _resection_launch(a, device, out, who: str):
-    """Allocates (or checks) the four outputs of ctk_fit_resection for the G, F and N_out of `a`, then the launch."""
-    out = _out_tuple(out, [("pose", torch.float32, (a.G, a.F, 3, 4)), ("label", torch.int8, (a.G, a.F, a.N_out)),
-                           ("error", torch.float32, (a.G, a.F, a.N_out)), ("stats", torch.int32, (a.G, a.F, 4))], device, who)
-    a.pose, a.label, a.error, a.stats = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_resection_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_resection(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_resection")
-    return out
+def _resection_fit(src, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, out):
+    a, who, dev = _FITS["resection"].args(), src.who, src.device
+    a.min_points = _min_points_of(min_points, L.Resection.MIN_POINTS, who)
+    _sampling(a, hypotheses, seed, tol, None, who, resection=True)
+    _intrinsics(a, intrinsics, who)
+    _source_form(a, lag, to, anchor, src.G, src.N, dev, who)
+    a.structure = _tensor_ptr(structure, _F32, (src.G, src.N, 3), "structure", dev, who)
+    a.valid = _tensor_ptr(valid, _BYTES, (src.G, src.N), "valid", dev, who)
+    a.seed_pose = _tensor_ptr(seed_pose, _F32, (src.G, src.F, 3, 4), "seed_pose", dev, who, " (fit_pose's)")
+    src.bind(a, back=a.lag, to=a.to)
+    return _fit_launch("resection", a, out, dev, who)
 
 
 def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, structure: torch.Tensor, valid: torch.Tensor,
@@ -1654,17 +1625,9 @@ def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, struc
     itself, the pose is exactly (I | 0))); `out`: such a tuple to write into.  A fit needs min_points (>= 6) points within tol.  The
     unit is the structure's; the seed's rotation must be close (no minimal solver); one pinhole camera without distortion; the
     structure is not refined (no bundle adjustment)."""
-    who = "fit_resection"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Motion.POINTS_MAX)
-    a = L.Resection.Args()
-    structure = structure[None] if isinstance(structure, torch.Tensor) and structure.dim() == 2 else structure
-    valid = valid[None] if isinstance(valid, torch.Tensor) and valid.dim() == 1 else valid
-    seed_pose = seed_pose[None] if isinstance(seed_pose, torch.Tensor) and seed_pose.dim() == 3 else seed_pose
-    _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G, T, N, dev, who)
-    if a.to >= T:
-        raise ValueError(f"{who}: to = {a.to} of {T} tracked frames")
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T + a.lag, f0=0, F=T, scale=scale)
-    return _resection_launch(a, dev, out, who)
+    src = _TensorSource("fit_resection", tracks, visible, first_row=first_row, scale=scale)
+    return _resection_fit(src, intrinsics, _group_axis(structure, 2), _group_axis(valid, 1), _group_axis(seed_pose, 3), lag, to, anchor, tol,
+                          hypotheses, min_points, seed, out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1681,66 +1644,34 @@ def min_sin2_of(min_parallax: float) -> float:
     return s2
 
 
-def _structure_rules(a, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax, refine,
-                     G: int, F: int, N: int, device, who: str) -> None:
-    """The camera, the views, the old structure and the fit of ctk_fit_structure_args; G, F, N: what they must match.  Nothing here
-    waits on the device."""
-    min_views, tol, into = int(min_views), float(tol), -1 if into is None else int(into)
-    if not 1 <= F <= L.Structure3D.VIEWS_MAX:
-        raise ValueError(f"{who}: between 1 and {L.Structure3D.VIEWS_MAX} frames are views, got {F}")
+def _structure_fit(src, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax, refine, out):
+    a, who, dev, G, F_ = _FITS["structure"].args(), src.who, src.device, src.G, src.F
+    min_views, into = int(min_views), -1 if into is None else int(into)
+    if not 1 <= F_ <= L.Structure3D.VIEWS_MAX:
+        raise ValueError(f"{who}: between 1 and {L.Structure3D.VIEWS_MAX} frames are views, got {F_}")
     if not L.Structure3D.MIN_VIEWS <= min_views <= L.Structure3D.VIEWS_MAX:
         raise ValueError(f"{who}: min_views must lie in {L.Structure3D.MIN_VIEWS}..{L.Structure3D.VIEWS_MAX}")
-    if not (math.isfinite(tol) and 0.0 < tol <= 3.0e38):
-        raise ValueError(f"{who}: tol must be finite and > 0 (raw-video pixels)")
-    if not -1 <= into < F:
-        raise ValueError(f"{who}: into must be one of the {F} views, or None")
+    if not -1 <= into < F_:
+        raise ValueError(f"{who}: into must be one of the {F_} views, or None")
     if int(source_frame) < 0:
         raise ValueError(f"{who}: source_frame must be a frame >= 0")
     try:
         a.min_sin2 = min_sin2_of(min_parallax)
     except ValueError as e:
         raise ValueError(f"{who}: {e}") from None
-    if isinstance(intrinsics, torch.Tensor) or len(intrinsics) != 4:
-        raise ValueError(f"{who}: intrinsics must be four Python floats (fx, fy, cx, cy) in raw-video pixels")
-    fx, fy, cx, cy = (float(v) for v in intrinsics)
-    if not (math.isfinite(fx) and math.isfinite(fy) and fx > 0.0 and fy > 0.0 and math.isfinite(cx) and math.isfinite(cy)):
-        raise ValueError(f"{who}: intrinsics (fx, fy, cx, cy): fx and fy must be finite and > 0, cx and cy finite")
-    a.fx, a.fy, a.cx, a.cy = fx, fy, cx, cy
-    a.into, a.source_frame, a.min_views, a.refine, a.tol, a.reserved = into, int(source_frame), min_views, 1 if refine else 0, tol, 0
-
-    def f32(x, shape, name, what=""):
-        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.device == device and tuple(x.shape) == shape and
-                x.is_contiguous()):
-            raise ValueError(f"{who}: {name} must be a contiguous float32 tensor {list(shape)} on {device}{what}")
-        return _ptr(x)
-    a.pose = f32(pose, (G, F, 3, 4), "pose", " (fit_resection's)")
-    a.pose_stats = None
-    if pose_stats is not None:
-        if not (isinstance(pose_stats, torch.Tensor) and pose_stats.dtype == torch.int32 and pose_stats.device == device and
-                tuple(pose_stats.shape) == (G, F, 4) and pose_stats.is_contiguous()):
-            raise ValueError(f"{who}: pose_stats must be a contiguous int32 tensor [{G},{F},4] on {device} (fit_resection's)")
-        a.pose_stats = _ptr(pose_stats)
+    _intrinsics(a, intrinsics, who)
+    a.into, a.source_frame, a.min_views, a.refine, a.tol, a.reserved = into, int(source_frame), min_views, 1 if refine else 0, _positive_tol(tol, who), 0
+    a.pose = _tensor_ptr(pose, _F32, (G, F_, 3, 4), "pose", dev, who, " (fit_resection's)")
+    a.pose_stats = None if pose_stats is None else _tensor_ptr(pose_stats, _I32, (G, F_, 4), "pose_stats", dev, who, " (fit_resection's)")
     if (structure is None) != (valid is None):
         raise ValueError(f"{who}: structure and valid come both or neither")
     a.structure_in = a.valid_in = None
     if structure is not None:
-        a.structure_in = f32(structure, (G, N, 3), "structure")
-        if not (isinstance(valid, torch.Tensor) and valid.dtype in (torch.int8, torch.uint8, torch.bool) and valid.device == device and
-                tuple(valid.shape) == (G, N) and valid.is_contiguous()):
-            raise ValueError(f"{who}: valid must be a contiguous int8, uint8 or bool tensor [{G},{N}] on {device}")
-        a.valid_in = _ptr(valid)
-    a.origin_in = None if origin is None else f32(origin, (G, 3, 4), "origin")
-
-
-def _structure_launch(a, device, out, who: str):
-    """Allocates (or checks) the five outputs of ctk_fit_structure for the G and N_out of `a`, then the launch."""
-    out = _out_tuple(out, [("points", torch.float32, (a.G, a.N_out, 3)), ("label", torch.int8, (a.G, a.N_out)),
-                           ("error", torch.float32, (a.G, a.N_out)), ("stats", torch.int32, (a.G, a.N_out, 4)),
-                           ("origin", torch.float32, (a.G, 3, 4))], device, who)
-    a.points, a.label, a.error, a.stats, a.origin_out = (_ptr(t_) for t_ in out)
-    ws = _scratch("motion", _query_bytes("ctk_fit_structure_workspace_bytes", C.byref(a)), device)
-    L.check(L.load().ctk_fit_structure(C.byref(a), _ptr(ws), ws.numel(), _stream()), "ctk_fit_structure")
-    return out
+        a.structure_in = _tensor_ptr(structure, _F32, (G, src.N, 3), "structure", dev, who)
+        a.valid_in = _tensor_ptr(valid, _BYTES, (G, src.N), "valid", dev, who)
+    a.origin_in = None if origin is None else _tensor_ptr(origin, _F32, (G, 3, 4), "origin", dev, who)
+    src.bind(a)
+    return _fit_launch("structure", a, out, dev, who)
 
 
 def fit_structure(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
@@ -1769,16 +1700,9 @@ def fit_structure(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, pose:
     counted view or -1, bits 0 / 1 / 2: round 1 / 2 / 3 fell back, bit 3: no start, bit 4: no parallax, bit 5: the `into` view is no
     view: no structure at all, bit 6: fewer than half of the observations are counted); origin float32 [G,3,4]); `out`: such a tuple to write into.  No bundle adjustment; the parallax test
     looks at the first counted view against the others only; one pinhole camera without distortion."""
-    who = "fit_structure"
-    tracks, visible, G, T, N, dev = _track_tensors(tracks, visible, who, L.Structure3D.POINTS_MAX)
-    a = L.Structure3D.Args()
-
-    def axis(x, dims):
-        return x[None] if isinstance(x, torch.Tensor) and x.dim() == dims else x
-    _structure_rules(a, intrinsics, axis(pose, 3), axis(pose_stats, 2), axis(structure, 2), axis(valid, 1), source_frame, axis(origin, 2), into,
-                     tol, min_views, min_parallax, refine, G, T, N, dev, who)
-    _bind_tensors(a, tracks, visible, _first_row_i32(first_row, G, N, dev), rows=T, f0=0, F=T, scale=scale)
-    return _structure_launch(a, dev, out, who)
+    src = _TensorSource("fit_structure", tracks, visible, first_row=first_row, scale=scale, points_max=L.Structure3D.POINTS_MAX)
+    return _structure_fit(src, intrinsics, _group_axis(pose, 3), _group_axis(pose_stats, 2), _group_axis(structure, 2), _group_axis(valid, 1),
+                          source_frame, _group_axis(origin, 2), into, tol, min_views, min_parallax, refine, out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -2266,9 +2190,9 @@ class StreamGroups:
         r0, r1 = f0 % R, f0 % R + (f1 - f0)
         return [slice(r0, r1)] if r1 <= R else [slice(r0, R), slice(0, r1 - R)]
 
-    # -- readers of the history: emit, health, draw, motion, field, objects, planes, epipolar.  What they share is stated here, once: whom a call reads
-    # (_reader), which frames it may read (_held: history_span) and the source fields of its args (_bind_history).  A reader itself
-    # holds its own options, the back / fwd / to of its span, its own struct fields and its launch. ---------------------------------
+    # -- readers of the history: emit, health, draw and the fit readers.  What they share is stated here, once: whom a call reads
+    # (_reader), which frames it may read (_held: history_span) and the source fields of its args (_bind_history).  emit, health and
+    # draw hold their own options, struct fields and launch; a fit reader is _HistorySource and the body it shares with its tensor form.
     def _reader(self, who: str, N_out, group, first_row, points_max: Optional[int] = None, need_row: bool = False):
         """Whom a reader reads -> (N_out, g0, G): the first N_out points (default: all N; at most points_max) of the G groups from g0
         on (`group` alone, or None: all), and first_row checked as what emit takes: int32 [self.G, self.N] on the device, or None."""
@@ -2307,7 +2231,7 @@ class StreamGroups:
         if F is not None:
             a.F = F
         a.sx, a.sy, a.thresh = float(scale[0]), float(scale[1]), float(thresh)
-        a.hist_coords, a.hist_vis, a.hist_conf = (_ptr_at(h_, g0) for h_ in self.hist)
+        a.hist_coords, a.hist_vis, a.hist_conf = [_ptr_at(h_, g0) for h_ in self.hist]
         a.visible = None
         a.first_row = None if first_row is None else _ptr_at(first_row, g0)
 
@@ -2416,14 +2340,8 @@ class StreamGroups:
         are history coords * scale (emit's multiplication), tol and min_base are in those pixels.  first_row int32 [G,N] (what emit
         takes) on the device.  The frames f0 - lag .. f0 + F - 1 (those >= 0) must be among the committed ones the history still
         holds: ValueError otherwise.  -> (motion [G,F,2,3], inlier [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
-        who = "motion"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        a = L.Motion.Args()
-        _motion_rules(a, lag, model, tol, hypotheses, min_base, seed, who)
-        f0, F_ = int(f0), int(F)
-        self._held(who, f0, F_, back=a.lag, hint=": fit fewer frames per call")
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _motion_launch(a, self.queries.device, out, who)
+        src = _HistorySource(self, "motion", f0, F, N_out, group, first_row, scale, thresh)
+        return _motion_fit(src, lag, model, tol, hypotheses, min_base, seed, out)
 
     def stabilize(self, frames: torch.Tensor, f0: int, *, group: int = 0, reset: bool = False, alpha: float = 0.1, zoom: float = 1.0,
                   border: str = "fill", fill=(0, 0, 0), out: Optional[torch.Tensor] = None, layout: Optional[str] = None,
@@ -2476,15 +2394,8 @@ class StreamGroups:
         emit takes) on the device.  Every frame that is read (those >= 0) must be among the committed ones the history still holds:
         ValueError otherwise; an anchor needs no frame but its own copy.  -> (field [G,F,gh,gw,2], level [G,F,gh,gw], stats [G,F,4])
         on the device.  No wait."""
-        who = "field"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Field.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Field.Args()
-        _field_rules(a, size, cell, radius, to, lag, anchor, G, self.N, dev, who)
-        f0, F_ = int(f0), int(F)
-        self._held(who, f0, F_, back=max(a.lag, 0), fwd=max(-a.lag, 0), to=a.to)  # (a negative lag reads the frame ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _field_launch(a, dev, out, who)
+        src = _HistorySource(self, "field", f0, F, N_out, group, first_row, scale, thresh, L.Field.POINTS_MAX)
+        return _field_fit(src, size, cell, radius, to, lag, anchor, out)
 
     def objects(self, f0: int, F: int, *, labels: Optional[torch.Tensor] = None, objects: int = 4, lag: int = 1, to: Optional[int] = None,
                 anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
@@ -2498,15 +2409,8 @@ class StreamGroups:
         Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError otherwise; an anchor
         needs no frame but its own copy.  -> (motion [G,F,objects,2,3], label [G,F,N_out], stats [G,F,objects,4], box
         [G,F,objects,4]) on the device.  No wait."""
-        who = "objects"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Objects.Args()
-        _objects_rules(a, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
-        f0, F_ = int(f0), int(F)
-        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_objects_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _objects_launch(a, dev, who)
+        src = _HistorySource(self, "objects", f0, F, N_out, group, first_row, scale, thresh)
+        return _objects_fit(src, labels, objects, lag, to, anchor, model, tol, hypotheses, min_base, min_points, seed)
 
     def planes(self, f0: int, F: int, *, labels: Optional[torch.Tensor] = None, planes: int = 1, lag: int = 1, to: Optional[int] = None,
                anchor: Optional[FieldAnchor] = None, inverse: bool = False, N_out: Optional[int] = None, scale=(1.0, 1.0),
@@ -2520,15 +2424,8 @@ class StreamGroups:
         Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError otherwise; an anchor
         needs no frame but its own copy.  -> (homography [G,F,planes,3,3], label [G,F,N_out], stats [G,F,planes,4], box
         [G,F,planes,4]) on the device.  No wait."""
-        who = "planes"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Planes.Args()
-        _planes_rules(a, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
-        f0, F_ = int(f0), int(F)
-        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_planes_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _planes_launch(a, dev, who)
+        src = _HistorySource(self, "planes", f0, F, N_out, group, first_row, scale, thresh)
+        return _planes_fit(src, labels, planes, lag, to, anchor, inverse, tol, hypotheses, min_base, min_points, seed)
 
     def epipolar(self, f0: int, F: int, *, mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None,
                  anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
@@ -2542,15 +2439,8 @@ class StreamGroups:
         the device.  Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError
         otherwise; an anchor needs no frame but its own copy.  -> (fundamental [G,F,3,3], label [G,F,N_out], error [G,F,N_out], stats
         [G,F,4]) on the device.  No wait."""
-        who = "epipolar"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Epipolar.Args()
-        _epipolar_rules(a, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, G, self.N, dev, who)
-        f0, F_ = int(f0), int(F)
-        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_epipolar_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _epipolar_launch(a, dev, out, who)
+        src = _HistorySource(self, "epipolar", f0, F, N_out, group, first_row, scale, thresh)
+        return _epipolar_fit(src, mask, lag, to, anchor, tol, hypotheses, min_base, min_points, seed, out)
 
     def pose(self, f0: int, F: int, intrinsics, fundamental: torch.Tensor, label: torch.Tensor, *, mask: Optional[torch.Tensor] = None,
              lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None,
@@ -2563,15 +2453,8 @@ class StreamGroups:
         picture.  mask int8 / uint8 / bool [G,N] (of the groups asked for) on the device, or None.  Every frame that is read (those
         >= 0) must be among the committed ones the history still holds: ValueError otherwise.  -> (pose [G,F,3,4], depth
         [G,F,N_out,2], stats [G,F,4]) on the device.  No wait."""
-        who = "pose"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Pose.Args()
-        f0, F_ = int(f0), int(F)
-        _pose_rules(a, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, G, F_, self.N, N_out, dev, who)
-        self._held(who, f0, F_, back=a.lag, to=a.to)  # (_pose_rules: the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _pose_launch(a, dev, out, who)
+        src = _HistorySource(self, "pose", f0, F, N_out, group, first_row, scale, thresh)
+        return _pose_fit(src, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, out)
 
     def resection(self, f0: int, F: int, intrinsics, structure: torch.Tensor, valid: torch.Tensor, seed_pose: torch.Tensor, *,
                   lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None,
@@ -2584,16 +2467,8 @@ class StreamGroups:
         intrinsics: (fx, fy, cx, cy), four Python floats, in the pixels of history coords * scale.  Every frame that is read (those
         >= 0) must be among the committed ones the history still holds: ValueError otherwise.  -> (pose [G,F,3,4], label
         [G,F,N_out], error [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
-        who = "resection"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Motion.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Resection.Args()
-        f0, F_ = int(f0), int(F)
-        _resection_rules(a, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, G, F_, self.N, dev,
-                         who)
-        self._held(who, f0, F_, back=a.lag, to=a.to)  # (the lag is >= 1, or 0 beside `to` and an anchor; never ahead)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _resection_launch(a, dev, out, who)
+        src = _HistorySource(self, "resection", f0, F, N_out, group, first_row, scale, thresh)
+        return _resection_fit(src, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, out)
 
     def structure(self, f0: int, F: int, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
                   structure: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, source_frame: int = 0,
@@ -2608,16 +2483,9 @@ class StreamGroups:
         floats, in the pixels of history coords * scale.  Every frame that is read must be among the committed ones the history still
         holds: ValueError otherwise.  -> (points [G,N_out,3], label [G,N_out], error [G,N_out], stats [G,N_out,4], origin [G,3,4]) on
         the device.  No wait."""
-        who = "structure"
-        N_out, g0, G = self._reader(who, N_out, group, first_row, L.Structure3D.POINTS_MAX)
-        dev = self.queries.device
-        a = L.Structure3D.Args()
-        f0, F_ = int(f0), int(F)
-        _structure_rules(a, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax, refine,
-                         G, F_, self.N, dev, who)
-        self._held(who, f0, F_)
-        self._bind_history(a, g0, G, N_out, f0, F_, scale, thresh, first_row)
-        return _structure_launch(a, dev, out, who)
+        src = _HistorySource(self, "structure", f0, F, N_out, group, first_row, scale, thresh, L.Structure3D.POINTS_MAX)
+        return _structure_fit(src, intrinsics, pose, pose_stats, structure, valid, source_frame, origin, into, tol, min_views, min_parallax,
+                              refine, out)
 
     def _args(self, ind: int, T_valid: int = 0, flag: bool = False) -> "L.StreamArgs":
         a = L.StreamArgs()
