@@ -57,7 +57,10 @@ class HipEncoder:
             self.units.append(us)
         self.conv2 = _Conv(fnet.conv2, device)
         self.conv3 = _Conv(fnet.conv3, device)
-        self.trace = None  # dev: a dict that receives named f32 intermediates (tools/check_encoder_hip.py)
+        # dev: a dict that receives the f32 output of every stage (conv1, norm1, layerK.J, layerK = layerK.1, fused, conv2, conv3,
+        # features = what the call returns) as [F,h,w,C] views; the launches and the bits of the call stay what they are without it
+        # (tools/check_encoder_hip.py, tests/test_gpu_encoder_stages.py)
+        self.trace = None
 
     # ---- primitives -------------------------------------------------------------------------------------------
     def _conv(self, x_sh, F, H, W, cv: _Conv):
@@ -112,11 +115,15 @@ class HipEncoder:
         if self.trace is not None:
             self.trace["conv1"] = x.view(F, Ho, Wo, 64)
         x_sh, x_f32 = self._apply(x, self._stats(x, F, Ho * Wo, 64), F, Ho * Wo, 64, want_f32=True)
+        if self.trace is not None:
+            self.trace["norm1"] = x_f32.view(F, Ho, Wo, 64)
         h, w = Ho, Wo
         stages = []
         for us in self.units:
-            for u in us:
+            for j, u in enumerate(us):
                 x_sh, x_f32, h, w = self._unit(x_sh, x_f32, F, h, w, u)
+                if self.trace is not None:
+                    self.trace[f"layer{len(stages) + 1}.{j}"] = x_f32.view(F, h, w, -1)
             stages.append((x_f32, h, w, x_f32.shape[1]))
             if self.trace is not None:
                 self.trace[f"layer{len(stages)}"] = x_f32.view(F, h, w, -1)
@@ -143,4 +150,6 @@ class HipEncoder:
             L.check(lib.ctk_enc_l2norm(_ptr(z), F * oh * ow, _ptr(out), ops._stream()), "ctk_enc_l2norm")
         else:
             out.view(F * oh * ow, 128).copy_(z)
+        if self.trace is not None:
+            self.trace["features"] = out
         return out

@@ -437,6 +437,40 @@ def host_library(tmp_path_factory, name):
     return C.CDLL(so)
 
 
+# ---- the encoder chain (tests/test_encoder_fp64_reference.py, test_gpu_encoder_stages.py) -------------------------------------------
+# name: (H, W, frames).  halo: every 3 x 3 / stride-1 layer is tile-aligned (Hout % 8 == 0 and Wout % 32 == 0: conv3x3_halo_kernel);
+# mixed: layer4 (8 x 16) falls back to conv_pp128_kernel; odd: 35 x 51, 18 x 26, 9 x 13, 5 x 7 maps, fused to 17 x 25
+ENC_CASES = {"halo": (128, 512, 2), "mixed": (128, 256, 2), "odd": (70, 102, 3)}
+# fault hooks of oracle/encoder_fp64.py: name -> (case it is planted on, the stage it must move and no other, the hook).
+# Planted where the fault means something: the tap on the map that has a halo tile seam at columns 31 | 32 (layer3 of `halo` is
+# 16 x 64), the frame statistics where frames 0 and 1 are both textured (`odd`).
+ENC_FAULTS = {
+    "dropped_tap_at_a_tile_seam": ("halo", "layer3.1", {"drop_tap": ("layer3.1.conv2", 0, 2, 31, 33)}),
+    "skip_with_main_branch_stats": ("halo", "layer2.0", {"skip_stats": "layer2.0"}),
+    "unbiased_variance": ("halo", "layer4.0", {"unbiased": "layer4.0.norm2"}),
+    "fuse_level_align_corners_false": ("halo", "fused", {"fuse_corners": 3}),
+    "norm1_stats_of_another_frame": ("odd", "norm1", {"norm1_frame": (1, 0)}),
+}
+
+
+def encoder_model():
+    """The model whose `fnet` the encoder stage tests run: fill_synthetic_(seed=3) weights, on the CPU."""
+    from cotracker_amd.model import CoTrackerThreeOnline
+    from cotracker_amd.weights import fill_synthetic_
+    m = CoTrackerThreeOnline(stride=STRIDE, corr_radius=3, window_len=16).eval()
+    fill_synthetic_(m, seed=3)
+    return m
+
+
+def encoder_frames(case):
+    """[F,3,H,W] float32 in 0..255 on the CPU: synthetic_video(seed=9) frames, then ONE CONSTANT frame of 127.5 -- 0 after
+    2 * (x / 255) - 1, so every convolution of that frame returns its bias at every pixel and every instance norm of the chain sees a
+    variance of exactly 0: the eps path, (x - mean) * 1 / sqrt(1e-5)."""
+    from cotracker_amd.synthetic import synthetic_video
+    H, W, Fn = ENC_CASES[case]
+    return torch.cat([synthetic_video(Fn - 1, H, W, seed=9)[0], torch.full((1, 3, H, W), 127.5)]).float().contiguous()
+
+
 # ---- include/ctk.h as the C compiler sees it ----------------------------------------------------------------------------------------
 def abi_structs():
     """C name -> ctypes mirror, for every struct that crosses the boundary."""

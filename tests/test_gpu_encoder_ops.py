@@ -1,7 +1,8 @@
 """The encoder's pixel kernels (co-tracker_amd/csrc/encoder.hip), one by one, against a plain reference of the same operation:
-ctk_enc_stem_im2col, ctk_enc_inorm_stats, ctk_enc_inorm_apply, ctk_enc_fuse, ctk_enc_l2norm.  The whole-encoder tests
-(test_gpu_parity.py) see them only through six more layers, at sizes that are multiples of 16 and with activations whose mean is
-about 0; here every kernel gets its own edges (odd sizes, one pixel, the 512-pixel partial-block seam, a channel count that
+ctk_enc_stem_im2col, ctk_enc_inorm_stats, ctk_enc_inorm_apply, ctk_enc_fuse, ctk_enc_l2norm.  The whole-encoder tests see them
+in the chain only: test_gpu_parity.py through six more layers and at sizes that are multiples of 16, test_gpu_encoder_stages.py
+stage by stage against float64 (also at 70 x 102 and on a constant frame), but always on the activations of a real encoder,
+whose mean is about 0; here every kernel gets its own edges (odd sizes, one pixel, the 512-pixel partial-block seam, a channel count that
 leaves threads idle, offsets that dominate the spread) and a reference in float64, or in float32 with one torch op per kernel
 operation where the kernel promises the same bits.  Every test also asserts that a second call gives the same bits and that
 frame f alone gives the bits it has inside a batch."""

@@ -26,20 +26,21 @@ with torch.no_grad():
     x = 2 * (video / 255.0) - 1.0
     ref = {}
     c1 = f.conv1(x); ref["conv1"] = c1
-    h = Fn.relu(Fn.instance_norm(c1, eps=1e-5))
+    h = Fn.relu(Fn.instance_norm(c1, eps=1e-5)); ref["norm1"] = h
     feats = []
     for i, layer in enumerate((f.layer1, f.layer2, f.layer3, f.layer4)):
-        h = layer(h); ref[f"layer{i + 1}"] = h
+        for j, unit in enumerate(layer):
+            h = unit(h); ref[f"layer{i + 1}.{j}"] = h
         feats.append(Fn.interpolate(h, (H // 4, W // 4), mode="bilinear", align_corners=True))
     cat = torch.cat(feats, 1); ref["fused"] = cat
     c2 = f.conv2(cat); ref["conv2"] = c2
     c3 = f.conv3(Fn.relu(Fn.instance_norm(c2, eps=1e-5))); ref["conv3"] = c3
     fin = c3.permute(0, 2, 3, 1)
     fin = fin / torch.sqrt(torch.maximum((fin * fin).sum(-1, keepdim=True), torch.tensor(1e-12, device=dev)))
-for k in ("conv1", "layer1", "layer2", "layer3", "layer4", "fused", "conv2", "conv3"):
+for k in ["conv1", "norm1"] + [f"layer{i}.{j}" for i in (1, 2, 3, 4) for j in (0, 1)] + ["fused", "conv2", "conv3"]:
     a, b = enc.trace[k], ref[k].permute(0, 2, 3, 1)
     d = (a.double() - b.double()).abs()
-    print(f"{k:8s} shape {tuple(a.shape)} max|ref| {float(b.abs().max()):9.3f} max err {float(d.max()):.3e} mean err {float(d.mean()):.3e}")
+    print(f"{k:9s} shape {tuple(a.shape)} max|ref| {float(b.abs().max()):9.3f} max err {float(d.max()):.3e} mean err {float(d.mean()):.3e}")
 d = (out.double() - fin.double()).abs()
 print(f"features max err {float(d.max()):.3e} mean {float(d.mean()):.3e} (|f| <= 1)")
 ours = m._encode(video, 16)
