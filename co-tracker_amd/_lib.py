@@ -37,6 +37,8 @@ PAD_ZEROS, PAD_BORDER = 0, 1  # ctk_bilinear_sampler padding_mode
 (OPT_GEMM_PP, OPT_GEMM_TAIL_PCT, OPT_CORR_VERSION, OPT_CORR_MAP, OPT_ATTENTION_VALU, OPT_ATTENTION_TIME_PERSISTENT,
  OPT_OVERLAP) = range(7)
 OPT_COUNT = 7
+LENS_TO_IDEAL, LENS_TO_SENSOR = 0, 1  # ctk_lens_*_args.direction
+LENS_ROUNDS = 8  # CTK_LENS_ROUNDS: Newton rounds of the inverse (csrc/lens_math.h)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -228,6 +230,37 @@ class Warp:
             ("G", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("reserved", C.c_int32),
             ("motion", _fp), ("post", _fp), ("state", _fp), ("warp", _fp),
         ]
+
+
+class Lens:
+    """Holder of ctk_lens, ctk_lens_frames_args and ctk_lens_points_args (include/ctk.h, "lens"), nested like Warp.Args and for the same
+    reason; their layouts are checked against the compiler by tests/test_lens_cabi.py.  The bounds mirror csrc/lens_math.h."""
+
+    FOCAL_MIN, FOCAL_MAX, REACH, COEFF_MAX, POINTS_MAX = 1.0, 1e6, 32768.0, 64.0, 1 << 20
+
+    class Camera(C.Structure):
+        """ctk_lens: sensor and ideal intrinsics (fx, fy, cx, cy) and the five Brown-Conrady coefficients (k1, k2, p1, p2, k3)."""
+        _fields_ = [("sensor", C.c_double * 4), ("ideal", C.c_double * 4), ("k", C.c_double * 5), ("reserved", C.c_double)]
+
+    class FramesArgs(C.Structure):
+        """ctk_lens_frames_args: uint8 pictures on sensor pixels -> the pinhole pictures, or back; of a size of their own."""
+
+    class PointsArgs(C.Structure):
+        """ctk_lens_points_args: positions [G,F,N,2] in sensor pixels -> ideal pixels, or back, and a label per point."""
+
+
+# (a nested class body does not see its neighbour Camera: the two structs that embed it get their fields here)
+Lens.FramesArgs._fields_ = [
+    ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("layout", C.c_int32),
+    ("border", C.c_int32), ("direction", C.c_int32), ("tol", C.c_float), ("reserved", C.c_int32), ("fill", C.c_uint8 * 4),
+    ("src_frame_stride", C.c_int64), ("src_row_stride", C.c_int64), ("dst_frame_stride", C.c_int64), ("dst_row_stride", C.c_int64),
+    ("lens", Lens.Camera), ("src", _fp), ("dst", _fp),
+]
+Lens.PointsArgs._fields_ = [
+    ("G", C.c_int32), ("F", C.c_int32), ("N", C.c_int32), ("direction", C.c_int32), ("tol", C.c_float), ("reserved", C.c_int32),
+    ("src_group_stride", C.c_int64), ("src_frame_stride", C.c_int64), ("dst_group_stride", C.c_int64), ("dst_frame_stride", C.c_int64),
+    ("lens", Lens.Camera), ("src", _fp), ("dst", _fp), ("label", _fp),
+]
 
 
 class Field:
@@ -478,6 +511,8 @@ SYMBOLS = {
     "ctk_fit_motion": (C.c_int, [_P(Motion.Args), _fp, C.c_size_t, _fp]),
     "ctk_warp_frames": (C.c_int, [_P(Warp.Args), _fp]),
     "ctk_smooth_path": (C.c_int, [_P(Warp.PathArgs), _fp]),
+    "ctk_lens_frames": (C.c_int, [_P(Lens.FramesArgs), _fp]),
+    "ctk_lens_points": (C.c_int, [_P(Lens.PointsArgs), _fp]),
     "ctk_track_field_workspace_bytes": (C.c_int, [_P(Field.Args), _P(C.c_size_t)]),
     "ctk_track_field": (C.c_int, [_P(Field.Args), _fp, C.c_size_t, _fp]),
     "ctk_warp_field": (C.c_int, [_P(Field.WarpArgs), _fp]),

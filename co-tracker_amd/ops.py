@@ -777,14 +777,20 @@ def fit_motion(tracks: torch.Tensor, visible: torch.Tensor, *, lag: int = 1, mod
 WARP_BORDERS = {"fill": L.Warp.BORDER_FILL, "edge": L.Warp.BORDER_EDGE}
 
 
-def _warp_args(frames: torch.Tensor, out: Optional[torch.Tensor], border: str, fill, layout: Optional[str], who: str):
-    """Everything of ctk_warp_args but the matrices, from `frames` and `out` (allocated dense when None) -> (args, out)."""
-    lay, F_, H, W, row, frame = _draw_surface(frames, layout, who)
+def _warp_border_fill(border: str, fill, who: str) -> List[int]:
+    """The border's name checked and the three fill values as integers (warp_frames, lens_frames)."""
     if border not in WARP_BORDERS:
         raise ValueError(f"{who}: border must be one of {sorted(WARP_BORDERS)}, got {border!r}")
     fill = [int(v) for v in fill]
     if len(fill) != 3 or any(not 0 <= v <= 255 for v in fill):
         raise ValueError(f"{who}: fill must hold three values in 0..255")
+    return fill
+
+
+def _warp_args(frames: torch.Tensor, out: Optional[torch.Tensor], border: str, fill, layout: Optional[str], who: str):
+    """Everything of ctk_warp_args but the matrices, from `frames` and `out` (allocated dense when None) -> (args, out)."""
+    lay, F_, H, W, row, frame = _draw_surface(frames, layout, who)
+    fill = _warp_border_fill(border, fill, who)
     if out is None:
         out = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
     elif out is frames or not isinstance(out, torch.Tensor) or out.device != frames.device or out.shape != frames.shape:
@@ -919,6 +925,142 @@ def stabilize(frames: torch.Tensor, tracks: torch.Tensor, visible: torch.Tensor,
     warp, state = smooth_path(motion, state, alpha=alpha, post=post)
     _warp_launch(a, warp, frames.device, who)
     return out, warp[0], state
+
+
+# ------------------------------------------------------------------------------------------
+# lens (csrc/lens.hip; include/ctk.h, "lens")
+# ------------------------------------------------------------------------------------------
+LENS_DIRECTIONS = {"ideal": L.LENS_TO_IDEAL, "sensor": L.LENS_TO_SENSOR}
+
+
+class Lens:
+    """A real camera: the pinhole part of the sensor, the five Brown-Conrady coefficients every calibration tool writes, and the ideal
+    (pinhole) camera that corrected pictures and positions are stated in (include/ctk.h, "lens"; csrc/lens_math.h has the model).
+
+    intrinsics    (fx, fy, cx, cy) of the sensor in raw-video pixels, plain Python floats
+    coefficients  (k1, k2, p1, p2, k3), the usual order
+    ideal         (fx', fy', cx', cy') of the pinhole camera; default: `intrinsics`
+    Refused (ValueError) unless all 13 numbers are finite, the focal lengths lie in [1, 1e6], |centre| <= 32768 and |coefficient| <=
+    64: an invalid lens never counts as "no lens".  .intrinsics, .coefficients and .ideal are tuples; .ideal is what a caller hands to
+    pose() / reconstruct() / ops.fit_pose as `intrinsics` once pictures or tracks have been corrected."""
+
+    def __init__(self, intrinsics, coefficients, ideal=None):
+        def floats(v, n, name):
+            if isinstance(v, torch.Tensor) or len(v) != n:
+                raise ValueError(f"Lens: {name} must be {n} Python floats")
+            return tuple(float(x) for x in v)
+        self.intrinsics = floats(intrinsics, 4, "intrinsics (fx, fy, cx, cy)")
+        self.coefficients = floats(coefficients, 5, "coefficients (k1, k2, p1, p2, k3)")
+        self.ideal = self.intrinsics if ideal is None else floats(ideal, 4, "ideal (fx', fy', cx', cy')")
+        B = L.Lens
+        for cam in (self.intrinsics, self.ideal):
+            if not (all(math.isfinite(v) for v in cam) and all(B.FOCAL_MIN <= v <= B.FOCAL_MAX for v in cam[:2]) and
+                    all(abs(v) <= B.REACH for v in cam[2:])):
+                raise ValueError(f"Lens: a camera (fx, fy, cx, cy) needs finite numbers, focal lengths in [{B.FOCAL_MIN:g}, {B.FOCAL_MAX:g}] "
+                                 f"and |centre| <= {B.REACH:g}; got {cam}")
+        if not all(math.isfinite(v) and abs(v) <= B.COEFF_MAX for v in self.coefficients):
+            raise ValueError(f"Lens: the coefficients must be finite with |k| <= {B.COEFF_MAX:g}; got {self.coefficients}")
+
+    def __repr__(self):
+        return f"Lens(intrinsics={self.intrinsics}, coefficients={self.coefficients}, ideal={self.ideal})"
+
+    def bind(self, cam) -> None:
+        """Fills a ctk_lens."""
+        for i in range(4):
+            cam.sensor[i], cam.ideal[i] = self.intrinsics[i], self.ideal[i]
+        for i in range(5):
+            cam.k[i] = self.coefficients[i]
+        cam.reserved = 0.0
+
+
+def _lens_common(a, lens, to, tol, who: str) -> None:
+    if not isinstance(lens, Lens):
+        raise ValueError(f"{who}: lens must be an ops.Lens")
+    if to not in LENS_DIRECTIONS:
+        raise ValueError(f"{who}: to must be one of {sorted(LENS_DIRECTIONS)}, got {to!r}")
+    lens.bind(a.lens)
+    a.direction, a.tol, a.reserved = LENS_DIRECTIONS[to], _positive_tol(tol, who), 0
+
+
+def lens_frames(frames: torch.Tensor, lens: Lens, *, to: str = "ideal", size=None, out: Optional[torch.Tensor] = None, border: str = "fill",
+                fill=(0, 0, 0), tol: float = 0.01, layout: Optional[str] = None) -> torch.Tensor:
+    """uint8 pictures resampled between the pixels of a real lens and those of a pinhole camera, on the device, by one launch and
+    without a wait (ctk_lens_frames; include/ctk.h and csrc/lens_math.h have the rules) -- what a caller otherwise writes as an
+    undistortion map on the host, uint8 -> float, grid_sample, round, -> uint8.  The map is made once per pixel for all pictures of the
+    call, in double.
+
+    frames   uint8 [F,H,W,3] or [F,3,H,W] on the device; strides and layout as warp_frames reads them.
+    lens     an ops.Lens.
+    to       "ideal": the pictures come from the sensor and the result is what lens.ideal sees -- straight lines are straight, and
+             every reader of tracks made on such pictures (epipolar() .. extend()) is right as it stands, given lens.ideal as the
+             intrinsics.  "sensor": pinhole pictures as the real lens would show them (eight Newton rounds per pixel).
+    size     (H, W) of the result (default: the source's); another size goes with another lens.ideal (or, to="sensor", intrinsics).
+    out      uint8 pictures of that size and the source's layout with strides of their own; must not overlap `frames`.
+    border   "fill" / "edge" as warp_frames; a pixel that has no source at all (the lens folds there, or `tol`, the residual of an
+             accepted inverse in sensor pixels, is not met) takes `fill` under both.
+    Bilinear in 1/256 pixel; Lens(K, (0, 0, 0, 0, 0)) copies bit for bit.  Returns out."""
+    who = "lens_frames"
+    lay, F_, H, W, row, frame = _draw_surface(frames, layout, who)
+    fill = _warp_border_fill(border, fill, who)
+    Ho, Wo = (H, W) if size is None else (int(size[0]), int(size[1]))
+    want = (F_, Ho, Wo, 3) if lay == "hwc" else (F_, 3, Ho, Wo)
+    if out is None:
+        if Ho < 1 or Wo < 1:
+            raise ValueError(f"{who}: size = (H, W) must be positive")
+        out = torch.empty(want, dtype=torch.uint8, device=frames.device)
+    elif out is frames or not isinstance(out, torch.Tensor) or out.device != frames.device or tuple(out.shape) != want:
+        raise ValueError(f"{who}: out must be uint8 frames {list(want)} on {frames.device}, and not `frames` itself")
+    _, _, _, _, orow, oframe = _draw_surface(out, lay, who)
+    a = L.Lens.FramesArgs()
+    _lens_common(a, lens, to, tol, who)
+    a.F, a.H, a.W, a.Ho, a.Wo, a.layout, a.border = F_, H, W, Ho, Wo, (L.INGEST_HWC if lay == "hwc" else L.INGEST_CHW), WARP_BORDERS[border]
+    for k in range(3):
+        a.fill[k] = fill[k]
+    a.src_frame_stride, a.src_row_stride, a.dst_frame_stride, a.dst_row_stride = frame, row, oframe, orow
+    a.src, a.dst = _ptr(frames), _ptr(out)
+    L.check(L.load().ctk_lens_frames(C.byref(a), _stream()), "ctk_lens_frames")  # (overlapping frames and out: refused there)
+    return out
+
+
+def lens_points(tracks: torch.Tensor, lens: Lens, *, to: str = "ideal", out: Optional[torch.Tensor] = None, labels: bool = False,
+                tol: float = 0.01):
+    """Positions carried between the pixels of a real lens and those of a pinhole camera, on the device, by one launch and without a
+    wait (ctk_lens_points; include/ctk.h and csrc/lens_math.h have the rules).
+
+    tracks   float32 [...,N,2] on the device, contiguous, any leading shape ([N,2], [T,N,2], [B,T,N,2], ...).
+    to       "ideal": sensor pixels -> the pixels of lens.ideal, by eight Newton rounds in double; a position without an inverse
+             (the lens folds there, or the residual exceeds `tol` sensor pixels) becomes NaN, which every fit reads as "not on this
+             frame".  "sensor": ideal pixels -> sensor pixels by the closed form, for drawing results onto the original frames
+             (ops.draw_tracks); NaN where the lens folds.  A position that is not finite or beyond 32768 becomes NaN either way.
+    out      float32 of the same shape; out=tracks works in place.  Default: a new tensor.
+    labels   True: also int8 [...,N]: 1 carried, 0 no image under the lens, -1 not a position.
+    This completes the offline path without further code: tracks, vis = predictor(video); ideal = ops.lens_points(tracks, lens); then
+    ops.fit_epipolar(ideal, vis, ...) -> ops.fit_pose(..., lens.ideal, ...) -> ops.fit_resection -> ops.fit_structure as today.
+    Returns out, or (out, label)."""
+    who = "lens_points"
+    if not (isinstance(tracks, torch.Tensor) and tracks.is_cuda and tracks.dtype == torch.float32 and tracks.dim() >= 2 and
+            tracks.shape[-1] == 2 and tracks.is_contiguous() and tracks.numel() > 0):
+        raise ValueError(f"{who}: tracks must be a contiguous float32 device tensor [...,N,2]")
+    if out is None:
+        out = torch.empty_like(tracks)
+    elif not (isinstance(out, torch.Tensor) and out.device == tracks.device and out.dtype == torch.float32 and out.shape == tracks.shape and
+              out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor of the shape and device of `tracks` (or `tracks` itself)")
+    N = tracks.shape[-2]
+    rows = tracks.numel() // (2 * N)  # the leading shape folded to [G,F]: F as long as the ABI allows, G the rest
+    F_ = next((f for f in range(min(rows, 65535), 0, -1) if rows % f == 0), 1)
+    G = rows // F_
+    if N > L.Lens.POINTS_MAX or G > 65535:
+        raise ValueError(f"{who}: {tuple(tracks.shape)} tracks do not fold to [G,F,N,2] with G, F <= 65535 and N <= {L.Lens.POINTS_MAX}")
+    label = torch.empty(tracks.shape[:-1], dtype=torch.int8, device=tracks.device) if labels else None
+    a = L.Lens.PointsArgs()
+    _lens_common(a, lens, to, tol, who)
+    a.G, a.F, a.N = G, F_, N
+    a.src_group_stride = a.dst_group_stride = F_ * N * 2
+    a.src_frame_stride = a.dst_frame_stride = N * 2
+    a.src, a.dst, a.label = _ptr(tracks), _ptr(out), _ptr(label)
+    L.check(L.load().ctk_lens_points(C.byref(a), _stream()), "ctk_lens_points")
+    return (out, label) if labels else out
 
 
 # ------------------------------------------------------------------------------------------

@@ -275,7 +275,63 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         # chunk -- which must hold that frame: a one-frame dummy chunk cannot serve (ValueError) --; a cell without a seed keeps the
         # lattice point of its row and column.  Built on the device without a wait, one launch per video of the batch.
         self.grid_seeds = "grid"
+        self._lens = None      # the `lens` property
+        self._lens_buf = None  # push_frames with a lens: the corrected uint8 frames of one push, kept per stream shape
         self._push_reset()
+
+    @property
+    def lens(self):
+        """Not in the reference: None (default: the frames are taken as a pinhole camera's, and nothing anywhere changes by a bit or a
+        launch), or an ops.Lens -- the real camera behind the frames given to push_frames.  With a lens set, every arriving uint8 batch
+        is first resampled into the pinhole picture of lens.ideal at raw resolution (ops.lens_frames(to="ideal", size=(H, W)): one more
+        launch per push, into a scratch buffer kept per stream shape) and then ingested as before.  The stream then lives in ideal
+        pixels: tracks, draw(), overlay(), stabilize() and every 3-D reader are right as they stand -- hand pose(), reconstruct(),
+        localize() and extend() `intrinsics=predictor.lens.ideal` --, undistort() makes the matching pictures to draw onto and
+        to_sensor() carries results back onto the original frames.  float32 frames with a lens set are refused (ValueError): the
+        resampler is a uint8 one.  Setting the property while a pushed stream has tracked a window and is not closed raises
+        RuntimeError: half a stream would be in other pixels.  forward() does not read `lens`: its chunks are the caller's float
+        tensors, which a caller corrects beforehand (ops.lens_frames on the uint8 frames) or afterwards (ops.lens_points on the tracks)."""
+        return self._lens
+
+    @lens.setter
+    def lens(self, value):
+        from . import ops
+        if value is not None and not isinstance(value, ops.Lens):
+            raise ValueError("lens must be an ops.Lens or None")
+        if self._push_tracked and not self._push_closed:
+            raise RuntimeError("lens: a pushed stream is running (it has tracked a window and is not closed): its frames so far were "
+                               "taken with the old setting; set the lens before the first push, or after final=True")
+        self._lens = value
+
+    @torch.no_grad()
+    def undistort(self, frames, out=None, border="fill", fill=(0, 0, 0)):
+        """Not in the reference: raw sensor frames -- uint8 [F,H,W,3], [F,3,H,W] or one frame, on the device -- resampled into the pinhole
+        pictures of lens.ideal at the same size, by one launch and without a wait (ops.lens_frames(to="ideal")): what push_frames did
+        to the frames it tracked, for the frames a caller wants to draw() / overlay() onto.  border "fill" / "edge" and fill as
+        ops.lens_frames; out: frames of the same shape that do not overlap `frames`.  Needs a lens (RuntimeError), no stream.
+        Returns the pictures."""
+        from . import ops
+        if self._lens is None:
+            raise RuntimeError("undistort: no lens is set (predictor.lens = ops.Lens(...))")
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() not in (3, 4):
+            raise ValueError("undistort: frames must be a uint8 device tensor [F,H,W,3], [F,3,H,W], [H,W,3] or [3,H,W]")
+        one = frames.dim() == 3
+        res = ops.lens_frames(frames[None] if one else frames, self._lens, to="ideal", out=(out[None] if one and out is not None else out),
+                              border=border, fill=fill)
+        return res[0] if one else res
+
+    @torch.no_grad()
+    def to_sensor(self, tracks, labels=False):
+        """Not in the reference: positions in the ideal pixels the stream lives in -- float32 [...,N,2] on the device, e.g. the tracks
+        push_frames returned -- carried onto the original sensor frames (ops.lens_points(to="sensor") with the predictor's lens), for
+        ops.draw_tracks on the frames as the camera delivered them.  labels=True: also int8 [...,N] (1 carried, 0 the lens folds
+        there, -1 not a position).  Needs a lens (RuntimeError).  Returns a new tensor, or (tensor, labels)."""
+        from . import ops
+        if self._lens is None:
+            raise RuntimeError("to_sensor: no lens is set (predictor.lens = ops.Lens(...))")
+        if isinstance(tracks, torch.Tensor) and not tracks.is_contiguous():
+            tracks = tracks.contiguous()
+        return ops.lens_points(tracks, self._lens, to="sensor", labels=labels)
 
     def add_queries(self, queries, group: int = 0, resident: bool = False):
         """Between two steps of a running stream (after its first tracked chunk): track queries [M,3] = (frame, x, y) -- frame
@@ -802,7 +858,9 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         pixels^2, -1 without a correspondence or a fit; stats int32 [n,4] = (points that may be fitted on, inliers among them, best
         hypothesis or -1, bit 0 / 1: the first / second refit fell back).  Without parallax -- a planar scene, a camera that only
         turns or stands -- the matrix is not unique and the labels mean "consistent with some camera motion": compare with
-        follow_planes().  A point that moves along its own epipolar line is not seen."""
+        follow_planes().  A point that moves along its own epipolar line is not seen.  One pinhole camera: a real lens is corrected in
+        front of the fit -- set `lens` before pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on
+        sensor pixels."""
         who = "epipolar"
         gs, scale = self._running(who)
         group = int(group)
@@ -831,7 +889,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         the chosen candidate or -1, bit 0 / 1: the first / second refinement round fell back, bit 2: an entry was left out of one).
         The scale is unknown and changes from frame to frame; one pinhole camera without distortion; without parallax -- a camera that
         only turns or stands, a planar scene -- there is no pose: look at stats[:, 1] / stats[:, 0] and compare with follow_planes().
-        No bundle adjustment over more than two frames."""
+        No bundle adjustment over more than two frames.  A real lens is corrected in front of the fit: set `lens` before
+        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal."""
         who = "pose"
         gs, scale = self._running(who)
         group = int(group)
@@ -860,7 +919,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         points stay tracked: points that replenish() adds later are not in it until extend() puts them there (triangulating new points
         from localised frames and restating the structure on a newer frame; refining what it holds is not built).  One pinhole camera,
         no lens distortion; the structure is never refined (no bundle adjustment); without parallax on the pair (a camera that only turns or stands, a plane) there is no structure: valid is all
-        zero."""
+        zero.  A real lens is corrected in front of the fit: set `lens` before
+        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal."""
         from . import ops
         who = "reconstruct"
         gs, scale = self._running(who)
@@ -901,7 +961,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         refining the structure is not built); the seed comes from the
         two-view pose, so a frame without parallax against the anchor that is not the anchor itself (a camera that only turned)
         relies on the fixed candidates (R0, 0) and (I, 0) -- there is no minimal P3P solver; one pinhole camera, no lens distortion;
-        no bundle adjustment.  ValueError for frames not yet tracked; NotImplementedError on a v2 predictor."""
+        no bundle adjustment.  ValueError for frames not yet tracked; NotImplementedError on a v2 predictor.  A real lens is corrected in front of the fit: set `lens` before
+        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal."""
         from . import ops
         who = "localize"
         gs, scale = self._running(who)
@@ -941,7 +1002,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         once per keyframe, not per frame, and each link carries the error of one localize(); no bundle adjustment -- neither the poses
         nor the carried points are refined; the parallax rule looks at the first counted view against the others only; a frame still
         inside the window being tracked is refined by the next step (pin()'s limit); one pinhole camera, no lens distortion.
-        ValueError for frames not yet tracked or a `frame` outside the n frames; NotImplementedError on a v2 predictor."""
+        ValueError for frames not yet tracked or a `frame` outside the n frames; NotImplementedError on a v2 predictor.  A real lens is corrected in front of the fit: set `lens` before
+        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal."""
         from . import ops
         who = "extend"
         gs, scale = self._running(who)
@@ -1220,6 +1282,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
             raise RuntimeError("push_frames: final=True has ended this stream; start the next one with a first step")
         if not isinstance(frames, torch.Tensor) or frames.dtype not in (torch.uint8, torch.float32) or frames.dim() not in (3, 4):
             raise ValueError("push_frames: frames must be a uint8 or float32 tensor [n,H,W,3], [n,3,H,W], [H,W,3] or [3,H,W]")
+        if self._lens is not None and frames.dtype != torch.uint8:
+            raise ValueError("push_frames: with a lens set the frames must be uint8 (ops.lens_frames resamples uint8 pictures)")
         if frames.dim() == 3:
             frames = frames[None]
         H, W = self._hw
@@ -1233,6 +1297,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         dev = self.queries.device
         if frames.device != dev:
             frames = frames.to(dev, non_blocking=True)  # the one copy; uint8 stays uint8
+        if self._lens is not None:
+            frames = self._undistorted(frames, layout)
         S, step = self.model.window_len, self.step
         ih, iw = self.interp_shape
         buf = self._push_buf
@@ -1255,6 +1321,15 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         if out[0] is None:  # history_frames: the last window's rows, out of the ring
             return self._emit_result(self.model.stream_window_start, self.model._gstream.committed)
         return self._user_result(*out, add_support_grid)
+
+    def _undistorted(self, frames, layout):
+        """push_frames with a lens: the arriving sensor frames as the pinhole pictures of lens.ideal at raw resolution, one launch, in a
+        scratch buffer that is allocated once per stream shape (and grows only with a longer push)."""
+        from . import ops
+        n, buf = frames.shape[0], self._lens_buf
+        if buf is None or buf.device != frames.device or tuple(buf.shape[1:]) != tuple(frames.shape[1:]) or buf.shape[0] < n:
+            buf = self._lens_buf = torch.empty(tuple(frames.shape), dtype=torch.uint8, device=frames.device)
+        return ops.lens_frames(frames, self._lens, to="ideal", size=self._hw, out=buf[:n], layout=layout)
 
     def _push_step(self, new_frames, final):
         with self._quiet():  # (a ring stream: the result is emitted by push_frames, one launch for the user points)

@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_lens_frames on the new struct ctk_lens_frames_args and
+ *       ctk_lens_points on the new struct ctk_lens_points_args, both around the new struct ctk_lens, a Brown-Conrady camera of sensor
+ *       and ideal intrinsics and five coefficients: uint8 pictures resampled from sensor pixels to pinhole pixels or back, the map made
+ *       once per pixel for all pictures of a launch, and positions carried either way by the closed form or eight Newton rounds in
+ *       double (csrc/lens_math.h); CTK_LENS_TO_IDEAL, CTK_LENS_TO_SENSOR, CTK_LENS_ROUNDS; one launch each, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_structure and ctk_fit_structure_workspace_bytes on the
  *       new struct ctk_fit_structure_args: per slot, the tracked positions on up to 256 localised frames become a 3-D point in the
  *       structure's unit (a linear midpoint start, three gated Gauss-Newton rounds on the reprojection error, a parallax test; plain
@@ -761,6 +766,106 @@ typedef struct ctk_smooth_path_args {
 } ctk_smooth_path_args;
 int ctk_smooth_path(const ctk_smooth_path_args* a, void* stream);
 
+/* ---- lens: the distortion of a real lens taken out of pictures and positions, in front of everything else ------------------------------
+ * Every fit below ("fit epipolar" .. "fit structure") assumes one pinhole camera.  A wide lens moves the corners of a 1080p picture by
+ * more than a hundred pixels, the fits' tolerances are 1 - 2.  ctk_lens_frames resamples raw sensor pictures into pinhole pictures
+ * BEFORE they enter a stream (or back); ctk_lens_points carries positions between sensor pixels and ideal pixels in either direction
+ * (tracks made on sensor pixels into the fits, results back onto the original frames).  No fit kernel changes.  The rules are stated
+ * once in csrc/lens_math.h: decisions are integers or single comparisons, everything in double is one IEEE operation per step in the
+ * order written there, and the results depend on them alone.
+ *   camera     struct ctk_lens: Brown-Conrady with k = (k1, k2, p1, p2, k3), the order every calibration tool writes.  sensor =
+ *              (fx, fy, cx, cy), the pinhole part of the real camera in raw-video pixels; ideal = (fx', fy', cx', cy'), the camera the
+ *              corrected pictures and positions are stated in (equal to `sensor` unless the caller wants another field of view or
+ *              size); pixel centres at integers.  Valid iff all 13 numbers are finite, the four focal lengths lie in [1, 1e6],
+ *              |centre| <= 32768, |coefficient| <= 64 and reserved == 0.  An invalid lens is refused; it never counts as the identity.
+ *   forward    ideal -> sensor, (x, y) normalised ideal coordinates:  r2 = x x + y y;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ *              xd = x rad + 2 p1 x y + p2 (r2 + 2 x x);  yd = y rad + p1 (r2 + 2 y y) + 2 p2 x y;
+ *              sensor pixel = (fx xd + cx, fy yd + cy), ideal pixel = (fx' x + cx', fy' y + cy').
+ *   jacobian   with dr = k1 + r2 (2 k2 + 3 k3 r2):  a = rad + 2 x x dr + 2 p1 y + 6 p2 x;  b = c = 2 x y dr + 2 p1 x + 2 p2 y;
+ *              d = rad + 2 y y dr + 6 p1 y + 2 p2 x;  det = a d - b c.
+ *   inverse    sensor -> ideal: Newton from (x, y) = (xd, yd), CTK_LENS_ROUNDS = 8 rounds, always all of them: (ex, ey) = (xd, yd) -
+ *              forward of (x, y), idet = 1 / det (the one division of a round), x += (d ex - b ey) idet, y += (a ey - c ex) idet.
+ *              Accepted iff, at the result, det > 0 and the squared residual in sensor pixels (fx ex)^2 + (fy ey)^2 <= tol2 =
+ *              (double)tol (double)tol.  A NaN fails both comparisons.  No root, no library call.  Where the polynomial folds
+ *              inside the field (det <= 0) there is no inverse, and the point is reported as such.
+ *   points     ctk_lens_points, direction CTK_LENS_TO_IDEAL: the position is read as two float32 widened to double; not finite, or
+ *              |p| > 32768 on an axis: (NaN, NaN) with the bits 0x7FC00000, label -1.  Otherwise it is normalised with 1 / fx, 1 / fy
+ *              (one division per launch, on the host) and inverted: accepted, the (float) of the ideal pixel, label 1; not accepted,
+ *              NaN, label 0.  Every fit kernel treats a NaN position as "not on this frame": a point without an inverse never
+ *              enters a fit.  CTK_LENS_TO_SENSOR: the same reading and refusal, normalised with 1 / fx', 1 / fy', forward; label 1 iff
+ *              det > 0 at that point, else label 0 and NaN.
+ *   pictures   ctk_lens_frames: for output pixel (x, y) the source position (px, py) in double -- forward for CTK_LENS_TO_IDEAL (the
+ *              output is the pinhole picture), the inverse for CTK_LENS_TO_SENSOR.  The pixel is OUTSIDE when the point rule gives a
+ *              label <= 0, or (px, py) is not finite or |p| > 32768 on an axis; an outside pixel takes fill[c] under either border.
+ *              Otherwise X = llrint(px * 256.0) (round half to even), ix = X >> 8, fx = X & 255, Y likewise, and the four taps, the
+ *              CTK_WARP_FILL / CTK_WARP_EDGE borders and the blend are exactly ctk_warp_frames'.  With all coefficients 0 and
+ *              ideal == sensor the source is copied bit for bit (the round trip through the normalised coordinate is off by 1e-10
+ *              pixel, far less than 1/512); a centre shifted by whole pixels gives a shifted copy.
+ *   frames     src uint8, F pictures of H x W; dst uint8, F pictures of Ho x Wo (another size goes with another ideal or sensor
+ *              camera); 3 channels; layouts, strides (in elements) and the whole-dword-or-byte store rule as in ctk_warp_args.  src
+ *              and dst must not overlap.  The source position of a pixel does not depend on the picture: a thread computes the
+ *              double-precision map of its 4 consecutive pixels of a row once and loops over the pictures (a slice of them per grid
+ *              z, and more than one slice only where a small picture would not fill the device); memory is read directly.
+ * One launch each on `stream`, no atomics, no host synchronisation, capture-safe; every output element is written by one plain store
+ * and the inputs are only read.  ctk_lens_points: one thread per point, a position is one 8-byte load and one 8-byte store; src and
+ * dst float32 [G,F,N,2] with group and frame strides in elements each; dst == src with equal strides is allowed (an element is read
+ * and then written by its own thread), any other overlap is not; label int8 [G,F,N] dense, or NULL.
+ * Before the launch.  ctk_lens_frames: NULL a, src or dst: CTK_E_NULL; F outside 1..65535, H, W, Ho or Wo outside
+ * 1..CTK_INGEST_MAX_SIDE, an unknown layout, border or direction, a stride smaller than its row or frame or above 2^40, an invalid
+ * lens, tol not > 0 (or not finite), overlapping byte ranges, reserved != 0: CTK_E_SHAPE.  ctk_lens_points: NULL a, src or dst:
+ * CTK_E_NULL; G or F outside 1..65535, N outside 1..2^20, an unknown direction, a frame stride below 2 N, a group stride below F frame
+ * strides, a stride above 2^40, an invalid lens, tol not > 0, reserved != 0, an overlap other than dst == src with equal strides
+ * (label included): CTK_E_SHAPE; src or dst not 8-byte aligned or an odd stride: CTK_E_ALIGN.
+ *
+ * Known limits.  Five coefficients: no thin-prism, tilt or rational (k4 .. k6) terms, no fisheye (equidistant) model.  One lens per
+ * launch.  Bilinear resampling, no prefilter: a picture shrunk by much more than 2 aliases.  The Newton start is the distorted
+ * position itself: a lens so strong that this start lies beyond the fold reports label 0 there although an inverse exists. */
+#define CTK_LENS_TO_IDEAL 0
+#define CTK_LENS_TO_SENSOR 1
+#define CTK_LENS_ROUNDS 8
+typedef struct ctk_lens {
+  double sensor[4];           /* fx, fy, cx, cy of the real camera, raw-video pixels               */
+  double ideal[4];            /* fx', fy', cx', cy' of the pinhole camera                          */
+  double k[5];                /* k1, k2, p1, p2, k3                                                */
+  double reserved;            /* 0 */
+} ctk_lens;
+
+typedef struct ctk_lens_frames_args {
+  int32_t F;                  /* pictures                                                          */
+  int32_t H, W;               /* size of a src picture in pixels                                   */
+  int32_t Ho, Wo;             /* size of a dst picture                                             */
+  int32_t layout;             /* CTK_INGEST_HWC / CTK_INGEST_CHW                                   */
+  int32_t border;             /* CTK_WARP_FILL / CTK_WARP_EDGE                                     */
+  int32_t direction;          /* CTK_LENS_TO_IDEAL: dst is the pinhole picture / CTK_LENS_TO_SENSOR */
+  float tol;                  /* residual of an accepted inverse, sensor pixels, > 0               */
+  int32_t reserved;           /* 0 */
+  uint8_t fill[4];            /* the value outside the picture, per channel; three used            */
+  int64_t src_frame_stride;   /* elements between two pictures of src                              */
+  int64_t src_row_stride;     /* elements between two pixel rows of src                            */
+  int64_t dst_frame_stride;
+  int64_t dst_row_stride;
+  ctk_lens lens;
+  const uint8_t* src;
+  uint8_t* dst;
+} ctk_lens_frames_args;
+int ctk_lens_frames(const ctk_lens_frames_args* a, void* stream);
+
+typedef struct ctk_lens_points_args {
+  int32_t G, F, N;            /* groups, frames per group, points per frame                        */
+  int32_t direction;          /* CTK_LENS_TO_IDEAL / CTK_LENS_TO_SENSOR                            */
+  float tol;                  /* residual of an accepted inverse, sensor pixels, > 0               */
+  int32_t reserved;           /* 0 */
+  int64_t src_group_stride;   /* elements (floats) between two groups of src                       */
+  int64_t src_frame_stride;   /* elements between two frames of src, >= 2 N                        */
+  int64_t dst_group_stride;
+  int64_t dst_frame_stride;
+  ctk_lens lens;
+  const float* src;           /* [G,F,N,2] */
+  float* dst;                 /* [G,F,N,2]; may be src itself                                      */
+  int8_t* label;              /* [G,F,N]: 1 carried, 0 no inverse / folded, -1 not a position; or NULL */
+} ctk_lens_points_args;
+int ctk_lens_points(const ctk_lens_points_args* a, void* stream);
+
 /* ---- track field: a dense displacement field from the tracked points, and pictures carried along it ---------------------------------
  * For a caller whose tracks are on the device and whose scene does not move as one plane: what ctk_fit_motion's single matrix cannot
  * say.  An object mask, a paint stroke or a texture known on one frame is carried onto other frames along the tracked points, or a
@@ -1027,7 +1132,8 @@ int ctk_fit_objects(const ctk_fit_objects_args* a, void* workspace, size_t works
  *
  * Known limits.  No split mode for planes, no affine model, no homography path in ctk_smooth_path; no alpha blending and no
  * anti-aliased edges where a picture is drawn, bilinear taps only (no bicubic); the refit is one algebraic least-squares step (no
- * Sampson or iterated refit); no lens distortion.                                                                                   */
+ * Sampson or iterated refit); no lens distortion. ctk_lens_frames / ctk_lens_points correct a lens in front of
+ * the fit ("lens" above). */
 typedef struct ctk_fit_planes_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
@@ -1137,7 +1243,8 @@ int ctk_warp_planes(const ctk_warp_planes_args* a, void* stream);
  * Known limits.  F is not unique without parallax -- a planar scene, a camera that only rotates, a static camera: the labels then
  * still mean "consistent with SOME camera motion", and a caller tells by comparing with ctk_fit_planes' inliers.  A point that moves
  * along its own epipolar line is not seen by any F.  No rank-2 enforcement; one algebraic refit per round (no iterated or Sampson-
- * weighted refit); no lens distortion; no essential matrix and no pose decomposition.                                                  */
+ * weighted refit); no lens distortion; no essential matrix and no pose decomposition. ctk_lens_frames / ctk_lens_points correct a lens in front of
+ * the fit ("lens" above). */
 typedef struct ctk_fit_epipolar_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
@@ -1225,7 +1332,7 @@ int ctk_fit_epipolar(const ctk_fit_epipolar_args* a, void* workspace, size_t wor
  * Known limits.  The scale is unknown: |t| = 1, depths are in baselines, and the unit changes from frame to frame.  One pinhole
  * camera, no lens distortion.  No parallax means no pose -- a camera that only turns, a planar scene, a static camera: the caller
  * tells by stats[1] / stats[0] and by comparing with ctk_fit_planes' inliers.  Two frames at a time: no bundle adjustment over more,
- * no chaining of poses.                                                                                                                */
+ * no chaining of poses.  ctk_lens_frames / ctk_lens_points correct a lens in front of the fit ("lens" above). */
 typedef struct ctk_fit_pose_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
@@ -1305,7 +1412,8 @@ int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_b
  *
  * Known limits.  The unit is the structure's (the baseline of the pair it was reconstructed from).  A structure lives as long as
  * enough of its points stay tracked; ctk_fit_structure (below) adds points to it.  The candidates come from the seed: a seed whose rotation is far off
- * finds no fit (no minimal P3P solver).  One pinhole camera, no lens distortion.  No bundle adjustment: the structure is not refined. */
+ * finds no fit (no minimal P3P solver).  One pinhole camera, no lens distortion.  No bundle adjustment: the structure is not refined. ctk_lens_frames / ctk_lens_points correct a lens in front of
+ * the fit ("lens" above). */
 typedef struct ctk_fit_resection_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
@@ -1386,7 +1494,8 @@ int ctk_fit_resection(const ctk_fit_resection_args* a, void* workspace, size_t w
  * Known limits.  A point stays in a structure's fits only while it is visible on the frame the structure is stated in.  Poses
  * chain once per restatement, not per frame.  No bundle adjustment: neither the poses nor the carried points are refined.  The
  * parallax test looks at the first counted view against the others only.  The start is not robust: the gates drop one wrong view of a
- * few tol, a grossly wrong one (tens of tol) rejects the slot.  One pinhole camera, no lens distortion. */
+ * few tol, a grossly wrong one (tens of tol) rejects the slot.  One pinhole camera, no lens distortion. ctk_lens_frames / ctk_lens_points correct a lens in front of
+ * the fit ("lens" above). */
 typedef struct ctk_fit_structure_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
