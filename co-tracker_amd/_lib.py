@@ -405,6 +405,28 @@ class Resection:
         ]
 
 
+class P3p:
+    """Holder of ctk_fit_p3p_args (include/ctk.h, "fit p3p"), nested like Resection.Args and for the same reason; its layout is checked
+    against the compiler by tests/test_p3p_cabi.py.  The constants mirror csrc/p3p_math.h; the list cap, min_points and the ceiling of
+    `hypotheses` are Resection's."""
+
+    ROUNDS = 6
+
+    class Args(C.Structure):
+        """ctk_fit_p3p_args: ctk_fit_resection_args without seed_pose -> per frame a pose (R | t) in the structure's unit, a label and
+        a reprojection error per point, and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("min_points", C.c_int32),
+            ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+            ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+            ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float), ("tol", C.c_float),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp),
+            ("structure", _fp), ("valid", _fp), ("pose", _fp), ("label", _fp), ("error", _fp), ("stats", _fp),
+        ]
+
+
 class Structure3D:
     """Holder of ctk_fit_structure_args (include/ctk.h, "fit structure"), nested like Resection.Args and for the same reason; its layout
     is checked against the compiler by tests/test_structure_cabi.py.  The constants mirror csrc/structure_math.h."""
@@ -527,6 +549,8 @@ SYMBOLS = {
     "ctk_fit_pose": (C.c_int, [_P(Pose.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_resection_workspace_bytes": (C.c_int, [_P(Resection.Args), _P(C.c_size_t)]),
     "ctk_fit_resection": (C.c_int, [_P(Resection.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_p3p_workspace_bytes": (C.c_int, [_P(P3p.Args), _P(C.c_size_t)]),
+    "ctk_fit_p3p": (C.c_int, [_P(P3p.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_structure_workspace_bytes": (C.c_int, [_P(Structure3D.Args), _P(C.c_size_t)]),
     "ctk_fit_structure": (C.c_int, [_P(Structure3D.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),

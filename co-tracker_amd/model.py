@@ -1065,6 +1065,13 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         the device, by one launch and without a wait: ops.StreamGroups.resection.  Serves a ring history and the default one alike."""
         return self._running_stream().resection(f0, F, intrinsics, structure, valid, seed_pose, **kw)
 
+    def stream_p3p(self, f0, F, intrinsics, structure, valid, **kw):
+        """One camera pose per frame [f0, f0 + F) of the running (or just closed) stream against a 3-D structure, in that structure's
+        unit and coordinates, WITHOUT a seed pose (every candidate comes from three points of the structure) -- straight from the
+        history and logits on the device, by one launch and without a wait: ops.StreamGroups.p3p.  Serves a ring history and the
+        default one alike."""
+        return self._running_stream().p3p(f0, F, intrinsics, structure, valid, **kw)
+
     def stream_structure(self, f0, F, intrinsics, pose, **kw):
         """One 3-D point per slot from the frames [f0, f0 + F) of the running (or just closed) stream under the poses stream_resection
         returned for them, the old structure carried along and everything restated in the camera of one of the frames -- straight

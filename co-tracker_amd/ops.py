@@ -410,7 +410,7 @@ def _anchor_ptrs(anchor, G: int, N: int, device, who: str):
 
 
 # ------------------------------------------------------------------------------------------
-# the fit readers (fit_motion, track_field, fit_objects, fit_planes, fit_epipolar, fit_pose, fit_resection, fit_structure and the
+# the fit readers (fit_motion, track_field, fit_objects, fit_planes, fit_epipolar, fit_pose, fit_resection, fit_p3p, fit_structure and the
 # StreamGroups methods of the same names): the rules they share, each stated once; their two sources behind one interface; their one
 # launch.  A reader's body (_motion_fit ... _structure_fit) makes its args, applies its rules, binds its source with its own back / fwd
 # / to, and launches; the public functions build the source and call the body.
@@ -582,6 +582,9 @@ _FITS = {
     "pose": _Fit(L.Pose.Args, "ctk_fit_pose", "motion", lambda G, F, n, a: [
         ("pose", torch.float32, (G, F, 3, 4)), ("depth", torch.float32, (G, F, n, 2)), ("stats", torch.int32, (G, F, 4))]),
     "resection": _Fit(L.Resection.Args, "ctk_fit_resection", "motion", lambda G, F, n, a: [
+        ("pose", torch.float32, (G, F, 3, 4)), ("label", torch.int8, (G, F, n)), ("error", torch.float32, (G, F, n)),
+        ("stats", torch.int32, (G, F, 4))]),
+    "p3p": _Fit(L.P3p.Args, "ctk_fit_p3p", "motion", lambda G, F, n, a: [
         ("pose", torch.float32, (G, F, 3, 4)), ("label", torch.int8, (G, F, n)), ("error", torch.float32, (G, F, n)),
         ("stats", torch.int32, (G, F, 4))]),
     "structure": _Fit(L.Structure3D.Args, "ctk_fit_structure", "motion", lambda G, F, n, a: [
@@ -1729,17 +1732,19 @@ def structure_from_pose(tracks_row: torch.Tensor, intrinsics, depth: torch.Tenso
     return torch.where(ok[..., None], pts, torch.zeros_like(pts)), ok.to(torch.int8)
 
 
-def _resection_fit(src, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, out):
-    a, who, dev = _FITS["resection"].args(), src.who, src.device
+def _resection_fit(src, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, out, kind="resection"):
+    """The body of fit_resection and, as kind "p3p", of fit_p3p: the same args, rules and source; ctk_fit_p3p takes no seed_pose."""
+    a, who, dev = _FITS[kind].args(), src.who, src.device
     a.min_points = _min_points_of(min_points, L.Resection.MIN_POINTS, who)
     _sampling(a, hypotheses, seed, tol, None, who, resection=True)
     _intrinsics(a, intrinsics, who)
     _source_form(a, lag, to, anchor, src.G, src.N, dev, who)
     a.structure = _tensor_ptr(structure, _F32, (src.G, src.N, 3), "structure", dev, who)
     a.valid = _tensor_ptr(valid, _BYTES, (src.G, src.N), "valid", dev, who)
-    a.seed_pose = _tensor_ptr(seed_pose, _F32, (src.G, src.F, 3, 4), "seed_pose", dev, who, " (fit_pose's)")
+    if kind == "resection":
+        a.seed_pose = _tensor_ptr(seed_pose, _F32, (src.G, src.F, 3, 4), "seed_pose", dev, who, " (fit_pose's)")
     src.bind(a, back=a.lag, to=a.to)
-    return _fit_launch("resection", a, out, dev, who)
+    return _fit_launch(kind, a, out, dev, who)
 
 
 def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, structure: torch.Tensor, valid: torch.Tensor,
@@ -1766,10 +1771,35 @@ def fit_resection(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, struc
     entry was left out of a round, bit 3: more than 4096 points, the first 4096 were fitted on, bit 5: the frame is the source frame
     itself, the pose is exactly (I | 0))); `out`: such a tuple to write into.  A fit needs min_points (>= 6) points within tol.  The
     unit is the structure's; the seed's rotation must be close (no minimal solver); one pinhole camera without distortion; the
-    structure is not refined (no bundle adjustment)."""
+    structure is not refined (no bundle adjustment).  fit_p3p asks the same question without a seed."""
     src = _TensorSource("fit_resection", tracks, visible, first_row=first_row, scale=scale)
     return _resection_fit(src, intrinsics, _group_axis(structure, 2), _group_axis(valid, 1), _group_axis(seed_pose, 3), lag, to, anchor, tol,
                           hypotheses, min_points, seed, out)
+
+
+# ------------------------------------------------------------------------------------------
+# fit p3p (csrc/p3p.hip; include/ctk.h, "fit p3p")
+# ------------------------------------------------------------------------------------------
+def fit_p3p(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, structure: torch.Tensor, valid: torch.Tensor, *, lag: int = 1,
+            to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, tol: float = 2.0, hypotheses: int = 256, min_points: int = 16,
+            seed: int = 0, first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """Where the camera is on every frame against a 3-D structure, WITHOUT a seed pose: fit_resection's question answered from the
+    structure alone, by one launch and without a wait (ctk_fit_p3p; include/ctk.h and csrc/p3p_math.h have the rules).  Each of the
+    `hypotheses` candidates is the pose that three sampled structure points fix (the scales of their rays by six Newton rounds that
+    start at the points' own distances from the structure's camera, then the rotation by the polar steps); the candidate with most
+    points within tol pixels of their reprojection wins, the lowest on ties, and is refined by fit_resection's three Gauss-Newton
+    rounds.  No two-view fit comes first, so a structure of which most points have begun to move, or a planar one, is no obstacle.
+
+    tracks, visible, intrinsics, structure, valid, lag / to / anchor, first_row, scale   as in fit_resection.
+    Returns fit_resection's tuple (pose float32 [G,T,3,4], label int8 [G,T,N], error float32 [G,T,N], stats int32 [G,T,4]) with the
+    same meaning; the winning candidate stats[..., 2] lies in 0 .. hypotheses, the last being (I | 0) -- the only one on the source
+    frame itself, whose pose is exactly (I | 0).  `out`: such a tuple to write into.  A fit needs min_points (>= 6) points within tol.
+    Limits: Newton finds the P3P root nearest the structure's own distances, one root per triple -- measured on camera displacements
+    up to the depth of the nearest point; the rest are fit_resection's (the unit is the structure's; one pinhole camera without
+    distortion; no bundle adjustment)."""
+    src = _TensorSource("fit_p3p", tracks, visible, first_row=first_row, scale=scale)
+    return _resection_fit(src, intrinsics, _group_axis(structure, 2), _group_axis(valid, 1), None, lag, to, anchor, tol, hypotheses, min_points,
+                          seed, out, kind="p3p")
 
 
 # ------------------------------------------------------------------------------------------
@@ -2611,6 +2641,19 @@ class StreamGroups:
         [G,F,N_out], error [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
         src = _HistorySource(self, "resection", f0, F, N_out, group, first_row, scale, thresh)
         return _resection_fit(src, intrinsics, structure, valid, seed_pose, lag, to, anchor, tol, hypotheses, min_points, seed, out)
+
+    def p3p(self, f0: int, F: int, intrinsics, structure: torch.Tensor, valid: torch.Tensor, *, lag: int = 1, to: Optional[int] = None,
+            anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+            first_row: Optional[torch.Tensor] = None, tol: float = 2.0, hypotheses: int = 256, min_points: int = 16, seed: int = 0,
+            group: Optional[int] = None, out=None):
+        """One camera pose per frame f0 .. f0 + F - 1 against a 3-D structure (structure float32 [G,N,3] in the source camera's
+        coordinates, valid int8 / uint8 / bool [G,N], of the groups asked for; only read) WITHOUT a seed pose, over the first N_out
+        points of every group (or of `group` alone), straight from the stream's own history and logits by the one launch of
+        ctk_fit_p3p: fit_p3p has the picture.  intrinsics: (fx, fy, cx, cy), four Python floats, in the pixels of history coords *
+        scale.  Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError
+        otherwise.  -> (pose [G,F,3,4], label [G,F,N_out], error [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
+        src = _HistorySource(self, "p3p", f0, F, N_out, group, first_row, scale, thresh)
+        return _resection_fit(src, intrinsics, structure, valid, None, lag, to, anchor, tol, hypotheses, min_points, seed, out, kind="p3p")
 
     def structure(self, f0: int, F: int, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
                   structure: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, source_frame: int = 0,

@@ -962,7 +962,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         two-view pose, so a frame without parallax against the anchor that is not the anchor itself (a camera that only turned)
         relies on the fixed candidates (R0, 0) and (I, 0) -- there is no minimal P3P solver; one pinhole camera, no lens distortion;
         no bundle adjustment.  ValueError for frames not yet tracked; NotImplementedError on a v2 predictor.  A real lens is corrected in front of the fit: set `lens` before
-        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal."""
+        pushing (ctk_lens_frames), or run ops.lens_points (ctk_lens_points) over tracks made on sensor pixels, and pass lens.ideal.
+        resect() asks the same question without a seed: its candidates come from three points of the structure each."""
         from . import ops
         who = "localize"
         gs, scale = self._running(who)
@@ -977,6 +978,34 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         seeds, _, _ = self.model.stream_pose(first_frame, n, cam, fund, label, mask=mask, min_points=two_view, **source)
         pose, label, error, stats = self.model.stream_resection(first_frame, n, cam, structure.points[None], mask, seeds, tol=tol,
                                                                 hypotheses=hypotheses, min_points=min_points, seed=seed, **source)
+        return pose[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
+    def resect(self, structure, n=None, first_frame=None, tol=2.0, hypotheses=256, min_points=16, seed=0):
+        """Not in the reference: localize()'s question -- where the camera is on the n frames from first_frame on (default: the frames
+        of the window just tracked) in the unit and coordinates of an ops.Structure -- answered from the structure alone, by ONE
+        launch against the structure's anchor and no wait: ctk_fit_p3p (include/ctk.h, "fit p3p").  Each of the `hypotheses`
+        candidates is the pose that three sampled structure points fix; the one with most points within `tol` pixels of their
+        reprojection wins and is refined by localize()'s three Gauss-Newton rounds.  No two-view fit comes first, so it holds where
+        localize()'s seed fails: when most points of the structure have begun to move (three clean points a sample instead of
+        eight), and on a planar structure.  Returns (pose, label, error, stats) exactly as localize() shapes them -- they go into
+        extend(poses=(pose, stats)) and world_pose() as they stand; stats[:, 2] lies in 0 .. hypotheses, the last being (I | 0), the
+        pose of the structure's own frame.  Limits: the Newton rounds start at the points' own distances from the structure's
+        camera and find the P3P root nearest to them, one root per triple -- measured on camera displacements up to the depth of
+        the nearest point; the rest are localize()'s (the unit is the baseline of the structure's pair; the structure lives as long
+        as enough of its points stay tracked; one pinhole camera, no lens distortion; no bundle adjustment).  ValueError for frames
+        not yet tracked; NotImplementedError on a v2 predictor."""
+        from . import ops
+        who = "resect"
+        gs, scale = self._running(who)
+        if not isinstance(structure, ops.Structure):
+            raise ValueError(f"{who}: structure must be an ops.Structure (reconstruct)")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        anchor = structure.anchor
+        pose, label, error, stats = self.model.stream_p3p(
+            first_frame, n, structure.intrinsics, structure.points[None], structure.valid[None], tol=tol, hypotheses=hypotheses,
+            min_points=min_points, seed=seed, anchor=anchor, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(),
+            group=anchor.group)
         return pose[0], label[0], error[0], stats[0]
 
     @torch.no_grad()

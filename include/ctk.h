@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_p3p and ctk_fit_p3p_workspace_bytes on the new
+ *       struct ctk_fit_p3p_args, which is ctk_fit_resection_args without seed_pose: per frame, the camera's pose against a fixed 3-D structure
+ *       WITHOUT a seed: every candidate is the pose of three sampled points (six Newton rounds on their three scales from the
+ *       structure's own distances, a cofactor solve, the polar steps), scored and refitted by ctk_fit_resection's rules
+ *       (csrc/p3p_math.h); one launch, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_lens_frames on the new struct ctk_lens_frames_args and
  *       ctk_lens_points on the new struct ctk_lens_points_args, both around the new struct ctk_lens, a Brown-Conrady camera of sensor
  *       and ideal intrinsics and five coefficients: uint8 pictures resampled from sensor pixels to pinhole pixels or back, the map made
@@ -1413,7 +1418,7 @@ int ctk_fit_pose(const ctk_fit_pose_args* a, void* workspace, size_t workspace_b
  * Known limits.  The unit is the structure's (the baseline of the pair it was reconstructed from).  A structure lives as long as
  * enough of its points stay tracked; ctk_fit_structure (below) adds points to it.  The candidates come from the seed: a seed whose rotation is far off
  * finds no fit (no minimal P3P solver).  One pinhole camera, no lens distortion.  No bundle adjustment: the structure is not refined. ctk_lens_frames / ctk_lens_points correct a lens in front of
- * the fit ("lens" above). */
+ * the fit ("lens" above).  ctk_fit_p3p (below) is the entry point without a seed: its candidates come from three points each. */
 typedef struct ctk_fit_resection_args {
   int32_t G, N;               /* query groups, points per group of the history                     */
   int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
@@ -1445,6 +1450,73 @@ typedef struct ctk_fit_resection_args {
 } ctk_fit_resection_args;
 int ctk_fit_resection_workspace_bytes(const ctk_fit_resection_args* a, size_t* out_bytes);
 int ctk_fit_resection(const ctk_fit_resection_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit p3p: the camera's pose against a fixed 3-D structure from three points a candidate, no seed ------------------------------------
+ * ctk_fit_resection scores candidates that all share the rotation of a seed pose, which a two-view fit has to find first: eight clean
+ * points a sample, and no unique matrix on a planar structure.  ctk_fit_p3p needs no seed: candidate k is the pose that THREE sampled
+ * entries of the fit list fix, and the rest of the call is ctk_fit_resection's bit for bit.  The rules are stated once in
+ * csrc/p3p_math.h, on top of csrc/resection_math.h.
+ *
+ * Unchanged from ctk_fit_resection: the frame of the call and the gather (positions in 1/16 pixel, the pair rule with its three source
+ * forms, first_row, `visible` or the logits with thresh, N_out <= 8192, the four intrinsics), the fit list (`valid` nonzero and three
+ * finite floats of `structure`, ascending n, the first 4096 take part, M of them, more set stats[3] bit 3), project and within, the
+ * `still` rule (bit 5), the score (an integer count of fit-list entries within tol; the largest wins, the lowest k on ties; fewer than
+ * min_points, 6..8192: no fit), the three fixed-point Gauss-Newton rounds (the 28 int64 sums stay below 2^61, the 8 x 8 L D L^T; bits 0 /
+ * 1 / 4 a round fell back, bit 2 an entry was left out), the outputs and no fit: pose float32 [G,F,3,4] = (R | t), (I | 0) where there
+ * is no fit; label int8 [G,F,N_out] -1 / 0 / 1; error float32 [G,F,N_out]; stats int32 [G,F,4] = (M, slots labelled 1, the winning k or
+ * -1, bits).  Every element is written by one plain store.
+ *   candidates k < hypotheses (1..1024): the first three of the four distinct indices of ctk_fit_planes' seeded sample give the entries
+ *              (X_i, Q_i) with rays y_i.  The unknowns are the scales l_i of the camera points Y_i = l_i y_i under
+ *              l_i^2 |y_i|^2 + l_j^2 |y_j|^2 - 2 l_i l_j (y_i . y_j) = |X_i - X_j|^2 for the three pairs.  Start: the point's own distance
+ *              from the structure's camera, l_i = |X_i|^2 rsqrt(|X_i|^2 |y_i|^2) (a point with |X_i|^2 not > 0 or not finite skips the
+ *              candidate).  Six Newton rounds on the 3 x 3 system by a cofactor solve; a determinant that is zero or not finite, or an
+ *              l_i that ends not finite or not > 0, skips the candidate.  A = [X_1 - X_0, X_2 - X_0, their cross product] as columns, B
+ *              likewise from the Y_i; det A not > 0 (a collinear or repeated triple) skips the candidate; R = polar(B A^-1) by
+ *              cofactors and the four polar steps, checked as ctk_fit_pose checks a rotation; t = Y_0 - R X_0.
+ *              k = hypotheses: (I, 0), the only candidate on a still frame; stats[2] is in 0 .. hypotheses.
+ * One launch on `stream`, one workgroup of 256 threads per (group, frame) with the fit list (X, Q and the slot) in min(N_out, 4096) * 34
+ * bytes of LDS; a candidate is made by ONE lane, 64 a wave at a time, kept in that lane's registers and handed to the wave lane by lane
+ * for the count by ballots; no atomics, no host synchronisation, capture-safe; `structure` and `valid` are only read.  The workspace
+ * query answers 0 and `workspace` may be NULL.  Errors before any launch: ctk_fit_resection's for the fields both structs have (NULL a,
+ * hist_coords, structure, valid, pose, label, error or stats, `visible` NULL with hist_vis or hist_conf NULL, half an anchor:
+ * CTK_E_NULL; the shapes, min_points outside 6..8192, hypotheses outside 1..1024, tol not finite or not > 0, the camera: CTK_E_SHAPE;
+ * hist_coords or anchor_coords not 8-byte aligned, structure, pose, error or stats not 4-byte aligned: CTK_E_ALIGN).
+ *
+ * Known limits.  Newton finds the P3P root nearest the structure's own distances: ONE root per triple, not the up to four of a closed
+ * form.  Measured on the CPU (noise-free, 300 points 3..12 deep, 400 clean triples a row) the share of clean triples that return the
+ * planted pose is 0.99 / 0.98 / 0.97 / 0.95 for a camera displaced by 0.3 / 1 / 2 / 3 units; a camera further from the structure's
+ * camera than the nearest point is deep was not tried.  The rest are ctk_fit_resection's: the unit is the structure's, a structure
+ * lives as long as enough of its points stay tracked, one pinhole camera without lens distortion, no bundle adjustment. */
+typedef struct ctk_fit_p3p_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the outputs is frame f0 + j, 0 <= j < F                  */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t min_points;         /* a fit needs this many entries within tol, 6..8192                 */
+  int32_t hypotheses;         /* sampled candidates, 1..1024                                       */
+  uint32_t seed;              /* of the generator                                                  */
+  float fx, fy, cx, cy;       /* the pinhole camera, raw-video pixels                              */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  float tol;                  /* reprojection tolerance in raw-video pixels, finite and > 0        */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const float* structure;     /* [G,N,3], source-camera coordinates; read only                     */
+  const int8_t* valid;        /* [G,N], nonzero: the point is in the structure; read only          */
+  float* pose;                /* [G,F,3,4] */
+  int8_t* label;              /* [G,F,N_out] */
+  float* error;               /* [G,F,N_out] */
+  int32_t* stats;             /* [G,F,4] */
+} ctk_fit_p3p_args;
+int ctk_fit_p3p_workspace_bytes(const ctk_fit_p3p_args* a, size_t* out_bytes);
+int ctk_fit_p3p(const ctk_fit_p3p_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- fit structure: points added to a 3-D structure, and the structure restated on a newer frame ---------------------------------------
  * ctk_fit_resection places cameras against a structure that only shrinks.  ctk_fit_structure turns "tracked on several localised
