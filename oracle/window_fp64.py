@@ -131,9 +131,10 @@ def tokens(coords, vis, conf, emb, p, res=(384, 512), stride=4):
     return torch.cat([vc, emb.permute(1, 0, 2), pe], dim=-1) + time_embed(p, coords.shape[0])
 
 
-def attention(x, ctx, p, pre, drop_keys=None):
+def attention(x, ctx, p, pre, drop_keys=None, mask=None):
     """Attention.forward (blocks.py:379-398): x [B,N1,384], ctx [B,N2,384].  drop_keys = (head, k0, k1): a planted fault --
-    that head ignores keys k0..k1-1."""
+    that head ignores keys k0..k1-1.  mask: attn_bias (blocks.py:392-394), added to the scaled logits; anything that
+    broadcasts to [B,8,N1,N2] (CoTracker2 only, oracle/window_v2_fp64.py)."""
     B, N1, C = x.shape
     d = C // HEADS
     q = F.linear(x, p[pre + "to_q.weight"], p[pre + "to_q.bias"]).reshape(B, N1, HEADS, d).permute(0, 2, 1, 3)
@@ -141,6 +142,8 @@ def attention(x, ctx, p, pre, drop_keys=None):
     k = k.reshape(B, -1, HEADS, d).permute(0, 2, 1, 3)
     v = v.reshape(B, -1, HEADS, d).permute(0, 2, 1, 3)
     s = (q @ k.transpose(-2, -1)) * d ** -0.5
+    if mask is not None:
+        s = s + mask
     if drop_keys is not None:
         h, k0, k1 = drop_keys
         s[:, h, :, k0:k1] = -math.inf
@@ -155,10 +158,10 @@ def self_block(x, p, pre):
     return x + mlp(F.layer_norm(x, (HID,), eps=1e-6), p, pre + "mlp.")
 
 
-def cross_block(x, ctx, p, pre, drop_keys=None):
-    """CrossAttnBlock.forward (cotracker.py:559-577)."""
+def cross_block(x, ctx, p, pre, drop_keys=None, mask=None):
+    """CrossAttnBlock.forward (cotracker.py:559-577); mask: the additive attn_bias of `attention`."""
     c = F.layer_norm(ctx, (HID,), p[pre + "norm_context.weight"], p[pre + "norm_context.bias"], eps=1e-5)
-    x = x + attention(F.layer_norm(x, (HID,), eps=1e-6), c, p, pre + "cross_attn.", drop_keys)
+    x = x + attention(F.layer_norm(x, (HID,), eps=1e-6), c, p, pre + "cross_attn.", drop_keys, mask)
     return x + mlp(F.layer_norm(x, (HID,), eps=1e-6), p, pre + "mlp.")
 
 
