@@ -427,6 +427,30 @@ class P3p:
         ]
 
 
+class Focal:
+    """Holder of ctk_fit_focal_args (include/ctk.h, "fit focal"), nested like Pose.Args and for the same reason; its layout is checked
+    against the compiler by tests/test_focal_cabi.py.  The constants mirror csrc/focal_math.h; min_points is Pose's."""
+
+    K_MAX, FRAMES_MAX, ONE = 256, 65535, 1 << 32
+    BIT_END, BIT_FLAT, BIT_CANDIDATE = 1, 2, 4
+
+    class Args(C.Structure):
+        """ctk_fit_focal_args: history rows, a principal point, what ctk_fit_epipolar wrote (fundamental, label) and K candidate focal
+        lengths -> per (frame, candidate) an integer cost, per group the summed curve, the chosen focal length and the counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("N_out", C.c_int32), ("R", C.c_int32), ("f0", C.c_int32), ("F", C.c_int32),
+            ("to", C.c_int32), ("lag", C.c_int32), ("anchor_frame", C.c_int32), ("min_points", C.c_int32),
+            ("K", C.c_int32), ("min_frames", C.c_int32),
+            ("cx", C.c_float), ("cy", C.c_float), ("sx", C.c_float), ("sy", C.c_float), ("thresh", C.c_float),
+            ("tol", C.c_float), ("contrast", C.c_float),
+            ("reserved", C.c_int32),
+            ("hist_coords", _fp), ("visible", _fp), ("hist_vis", _fp), ("hist_conf", _fp), ("first_row", _fp),
+            ("anchor_coords", _fp), ("anchor_visible", _fp), ("mask", _fp),
+            ("fundamental", _fp), ("label", _fp), ("focals", _fp), ("curve_in", _fp),
+            ("focal", _fp), ("curve", _fp), ("cost", _fp), ("stats", _fp),
+        ]
+
+
 class Structure3D:
     """Holder of ctk_fit_structure_args (include/ctk.h, "fit structure"), nested like Resection.Args and for the same reason; its layout
     is checked against the compiler by tests/test_structure_cabi.py.  The constants mirror csrc/structure_math.h."""
@@ -551,6 +575,8 @@ SYMBOLS = {
     "ctk_fit_resection": (C.c_int, [_P(Resection.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_p3p_workspace_bytes": (C.c_int, [_P(P3p.Args), _P(C.c_size_t)]),
     "ctk_fit_p3p": (C.c_int, [_P(P3p.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_focal_workspace_bytes": (C.c_int, [_P(Focal.Args), _P(C.c_size_t)]),
+    "ctk_fit_focal": (C.c_int, [_P(Focal.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_structure_workspace_bytes": (C.c_int, [_P(Structure3D.Args), _P(C.c_size_t)]),
     "ctk_fit_structure": (C.c_int, [_P(Structure3D.Args), _fp, C.c_size_t, _fp]),
     "ctk_corr_embed_workspace_bytes": (C.c_int, [_P(WindowArgs), _P(C.c_size_t)]),

@@ -1059,6 +1059,13 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         by one launch and without a wait: ops.StreamGroups.pose.  Serves a ring history and the default one alike."""
         return self._running_stream().pose(f0, F, intrinsics, fundamental, label, **kw)
 
+    def stream_focal(self, f0, F, fundamental, label, **kw):
+        """The focal length of the camera from the frames [f0, f0 + F) of the running (or just closed) stream, from what stream_epipolar
+        returned for the same frames: a sweep of candidate focal lengths through stream_pose's rules, summed over the frames (and over
+        earlier calls, curve=) -- straight from the history and logits on the device, by two launches and without a wait:
+        ops.StreamGroups.focal.  Serves a ring history and the default one alike."""
+        return self._running_stream().focal(f0, F, fundamental, label, **kw)
+
     def stream_resection(self, f0, F, intrinsics, structure, valid, seed_pose, **kw):
         """One camera pose per frame [f0, f0 + F) of the running (or just closed) stream against a 3-D structure, in that structure's
         unit and coordinates, started from what stream_pose returned for the same frames -- straight from the history and logits on

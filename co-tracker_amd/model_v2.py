@@ -202,6 +202,9 @@ class CoTracker2(TrackerBase):
     def stream_pose(self, *args, **kwargs):  # the history it reads is the CoTracker3 online model's device stream state
         raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_pose on a v2 model is not implemented")
 
+    def stream_focal(self, *args, **kwargs):  # the history it reads is the CoTracker3 online model's device stream state
+        raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_focal on a v2 model is not implemented")
+
     def stream_resection(self, *args, **kwargs):  # the history it reads is the CoTracker3 online model's device stream state
         raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_resection on a v2 model is not implemented")
 

@@ -587,6 +587,9 @@ _FITS = {
     "p3p": _Fit(L.P3p.Args, "ctk_fit_p3p", "motion", lambda G, F, n, a: [
         ("pose", torch.float32, (G, F, 3, 4)), ("label", torch.int8, (G, F, n)), ("error", torch.float32, (G, F, n)),
         ("stats", torch.int32, (G, F, 4))]),
+    "focal": _Fit(L.Focal.Args, "ctk_fit_focal", "motion", lambda G, F, n, a: [
+        ("focal", torch.float32, (G,)), ("curve", torch.int64, (G, a.K + 2)), ("cost", torch.int64, (G, F, a.K)),
+        ("stats", torch.int32, (G, 4))]),
     "structure": _Fit(L.Structure3D.Args, "ctk_fit_structure", "motion", lambda G, F, n, a: [
         ("points", torch.float32, (G, n, 3)), ("label", torch.int8, (G, n)), ("error", torch.float32, (G, n)), ("stats", torch.int32, (G, n, 4)),
         ("origin_out", torch.float32, (G, 3, 4))]),
@@ -1686,6 +1689,113 @@ def fit_pose(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, fundamenta
 
 
 # ------------------------------------------------------------------------------------------
+# fit focal (csrc/focal.hip; include/ctk.h, "fit focal")
+# ------------------------------------------------------------------------------------------
+_focal_cache = {}
+_FOCAL_CACHE_MAX = 64
+
+
+def focal_candidates(size, device, *, candidates: int = 64, span=(0.25, 4.0)) -> torch.Tensor:
+    """The default candidates of fit_focal as a float32 [candidates] constant on `device`: geometric over span * W of size = (H, W),
+    lo * (hi / lo)^(k / (K - 1)) in Python floats (one candidate: the geometric mean).  Kept per (span, K, W, device) as quad_constant
+    keeps its quads: computed and uploaded once, through pinned memory with a non-blocking copy."""
+    K, W = int(candidates), float(size[1])
+    lo, hi = float(span[0]) * W, float(span[1]) * W
+    if not 1 <= K <= L.Focal.K_MAX:
+        raise ValueError(f"fit_focal: candidates must lie in 1..{L.Focal.K_MAX}")
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 < lo <= hi <= 3.0e38):
+        raise ValueError("fit_focal: span = (lo, hi) in picture widths with 0 < lo <= hi, and size = (H, W) with W > 0")
+    device = torch.device(device)
+    key = (lo, hi, K, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    q = _focal_cache.get(key)
+    if q is None:
+        host = [(lo * hi) ** 0.5] if K == 1 else [lo * (hi / lo) ** (k / (K - 1)) for k in range(K)]
+        q = torch.tensor(host, dtype=torch.float32).pin_memory().to(device, non_blocking=True)
+        while len(_focal_cache) >= _FOCAL_CACHE_MAX:
+            _focal_cache.pop(next(iter(_focal_cache)))
+        _focal_cache[key] = q
+    return q
+
+
+def _focal_list(focals, size, candidates, span, device, who: str) -> torch.Tensor:
+    """focals: None (the cached default of `size`), a device tensor (taken as it is) or host numbers (checked) -> float32 [K] on device."""
+    if focals is None:
+        if size is None:
+            raise ValueError(f"{who}: give size = (H, W) of the picture for the default candidates, or focals")
+        return focal_candidates(size, device, candidates=candidates, span=span)
+    if isinstance(focals, torch.Tensor) and focals.is_cuda:
+        if not (focals.dtype == torch.float32 and focals.dim() == 1 and 1 <= focals.numel() <= L.Focal.K_MAX and focals.is_contiguous() and
+                focals.device == device):
+            raise ValueError(f"{who}: focals on the device must be a contiguous float32 tensor [K], K in 1..{L.Focal.K_MAX}, on {device}")
+        return focals
+    host = [float(v) for v in (focals.tolist() if isinstance(focals, torch.Tensor) else focals)]
+    if not 1 <= len(host) <= L.Focal.K_MAX or any(not (math.isfinite(v) and 0.0 < v <= 3.0e38) for v in host) or \
+            any(b <= a for a, b in zip(host, host[1:])):
+        raise ValueError(f"{who}: focals must be 1..{L.Focal.K_MAX} finite numbers > 0 in ascending order (raw-video pixels)")
+    return torch.tensor(host, dtype=torch.float32).pin_memory().to(device, non_blocking=True)
+
+
+def _focal_fit(src, fundamental, label, focals, size, candidates, span, principal, mask, lag, to, anchor, tol, min_points, min_frames,
+               contrast, curve, out):
+    a, who, dev = _FITS["focal"].args(), src.who, src.device
+    a.min_points, a.reserved = _min_points_of(min_points, L.Pose.MIN_POINTS, who), 0
+    focals = _focal_list(focals, size, candidates, span, dev, who)
+    a.focals, a.K = focals.data_ptr(), focals.numel()
+    if principal is None:
+        if size is None:
+            raise ValueError(f"{who}: give principal = (cx, cy), or size = (H, W) for the picture centre")
+        principal = ((float(size[1]) - 1.0) * 0.5, (float(size[0]) - 1.0) * 0.5)
+    cx, cy = (float(v) for v in principal)
+    if not (math.isfinite(cx) and math.isfinite(cy)):
+        raise ValueError(f"{who}: principal = (cx, cy) must be two finite numbers (raw-video pixels)")
+    a.cx, a.cy, a.tol = cx, cy, _positive_tol(tol, who)
+    a.min_frames, a.contrast = int(min_frames), float(contrast)
+    if a.min_frames < 1 or not (math.isfinite(a.contrast) and a.contrast >= 1.0):
+        raise ValueError(f"{who}: min_frames must be >= 1 and contrast finite and >= 1")
+    _source_form(a, lag, to, anchor, src.G, src.N, dev, who)
+    if src.F > L.Focal.FRAMES_MAX:
+        raise ValueError(f"{who}: at most {L.Focal.FRAMES_MAX} frames a call (accumulate through curve=)")
+    a.fundamental = _tensor_ptr(fundamental, _F32, (src.G, src.F, 3, 3), "fundamental", dev, who, " (fit_epipolar's)")
+    a.label = _tensor_ptr(label, _I8, (src.G, src.F, src.N_out), "label", dev, who, " (fit_epipolar's)")
+    a.mask = src.per_point_ptr(mask, _BYTES, "mask")
+    a.curve_in = None if curve is None else _tensor_ptr(curve, (torch.int64,), (src.G, a.K + 2), "curve", dev, who,
+                                                        " (an earlier call's, same focals)")
+    src.bind(a, back=a.lag, to=a.to)
+    return _fit_launch("focal", a, out, dev, who) + (focals,)
+
+
+def fit_focal(tracks: torch.Tensor, visible: torch.Tensor, fundamental: torch.Tensor, label: torch.Tensor, *, focals=None, size=None,
+              candidates: int = 64, span=(0.25, 4.0), principal=None, mask: Optional[torch.Tensor] = None, lag: int = 1,
+              to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, tol: float = 1.0, min_points: int = 16, min_frames: int = 1,
+              contrast: float = 1.5, curve: Optional[torch.Tensor] = None, first_row: Optional[torch.Tensor] = None, scale=(1, 1), out=None):
+    """The focal length the camera had, read off the tracks: the one of four intrinsics that fit_pose and everything behind it want and
+    a caller with a phone clip does not know.  K candidate focal lengths are swept through fit_pose's rules over the matrices and
+    labels of fit_epipolar; each (frame, candidate) gets an integer cost -- the squared Sampson distance in pixels under the
+    candidate's best rigid pose, truncated at tol^2, summed over the points labelled 1 --; the costs are summed over the frames, and
+    the candidate with the smallest total is refined by a parabola through its neighbours.  Two launches, no wait (ctk_fit_focal;
+    include/ctk.h and csrc/focal_math.h have the rules).  Works on any result of any predictor here, offline ones included.
+
+    tracks, visible, lag / to / anchor, first_row, scale, mask   what fit_epipolar and fit_pose take: they decide the fit list.
+    fundamental, label   float32 [G,T,3,3] and int8 [G,T,N] as fit_epipolar returned them; they are only read.
+    focals    None: `candidates` (1..256) focal lengths geometric over span * W of size = (H, W), cached on the device; a list of
+              ascending finite numbers > 0 (raw-video pixels); or a float32 device tensor [K], taken as it is.
+    principal (cx, cy) in raw-video pixels; None: the centre ((W - 1) / 2, (H - 1) / 2) of `size`.  It is assumed, not estimated.
+    curve     the `curve` an earlier call returned for the same focals: the new curve is the running sum, so evidence accumulates over
+              calls -- more frames, other videos of the same camera -- without a wait; two calls accumulated equal one over both.
+    A frame takes part with min_points (>= 8) points labelled 1 and a usable matrix; a fit needs min_frames such frames (earlier
+    calls' included) and a curve whose largest total is at least `contrast` times its smallest -- a camera that does not TURN between
+    the two frames of a pair leaves the curve flat (F does not depend on the focal length then) and is refused.  Rows are all T
+    frames.  Returns (focal float32 [G], 0 where there is no fit; curve int64 [G,K+2]: the totals, then the frames and entries
+    counted; cost int64 [G,T,K], in units of 2^-32 tol^2; stats int32 [G,4] = (frames counted, the chosen candidate or -1, entries
+    counted, bit 0: the minimum lies at an end of the range, bit 1: the curve is flat, bit 2: a candidate is not finite and > 0);
+    focals float32 [K]); `out`: a tuple of the first four to write into.  Known limits: square pixels, an assumed principal point, a
+    camera that must turn, one fixed focal length per accumulation (no zoom), no distortion estimate."""
+    src = _TensorSource("fit_focal", tracks, visible, first_row=first_row, scale=scale)
+    return _focal_fit(src, fundamental, label, focals, size, candidates, span, principal, mask, lag, to, anchor, tol, min_points,
+                      min_frames, contrast, curve, out)
+
+
+# ------------------------------------------------------------------------------------------
 # fit resection (csrc/resection.hip; include/ctk.h, "fit resection")
 # ------------------------------------------------------------------------------------------
 class _StructureOrigin:
@@ -2627,6 +2737,22 @@ class StreamGroups:
         [G,F,N_out,2], stats [G,F,4]) on the device.  No wait."""
         src = _HistorySource(self, "pose", f0, F, N_out, group, first_row, scale, thresh)
         return _pose_fit(src, intrinsics, fundamental, label, mask, lag, to, anchor, min_points, out)
+
+    def focal(self, f0: int, F: int, fundamental: torch.Tensor, label: torch.Tensor, *, focals=None, size=None, candidates: int = 64,
+              span=(0.25, 4.0), principal=None, mask: Optional[torch.Tensor] = None, lag: int = 1, to: Optional[int] = None,
+              anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None, scale=(1.0, 1.0), thresh: float = 0.6,
+              first_row: Optional[torch.Tensor] = None, tol: float = 1.0, min_points: int = 16, min_frames: int = 1,
+              contrast: float = 1.5, curve: Optional[torch.Tensor] = None, group: Optional[int] = None, out=None):
+        """The focal length of the camera from the frames f0 .. f0 + F - 1 over the first N_out points of every group (or of `group`
+        alone), from what epipolar() returned for the same frames, source form, N_out, scale, thresh, first_row and group (fundamental
+        [G,F,3,3], label [G,F,N_out]; only read), straight from the stream's own history and logits by the two launches of
+        ctk_fit_focal: fit_focal has the picture, the candidates (focals / size, candidates, span), the principal point (in the pixels
+        of history coords * scale; None: the centre of `size`), the contrast rule and `curve`, the running sum an earlier call
+        returned.  Every frame that is read (those >= 0) must be among the committed ones the history still holds: ValueError
+        otherwise.  -> (focal [G], curve [G,K+2], cost [G,F,K], stats [G,4], focals [K]) on the device.  No wait."""
+        src = _HistorySource(self, "focal", f0, F, N_out, group, first_row, scale, thresh)
+        return _focal_fit(src, fundamental, label, focals, size, candidates, span, principal, mask, lag, to, anchor, tol, min_points,
+                          min_frames, contrast, curve, out)
 
     def resection(self, f0: int, F: int, intrinsics, structure: torch.Tensor, valid: torch.Tensor, seed_pose: torch.Tensor, *,
                   lag: int = 1, to: Optional[int] = None, anchor: Optional[FieldAnchor] = None, N_out: Optional[int] = None,

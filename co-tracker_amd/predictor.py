@@ -10,6 +10,7 @@ the raw video width.  All tensor work stays on the GPU (the reference's per-batc
 loop, predictor.py:177-185, is a single indexed write here).
 """
 import contextlib
+import math
 
 import torch
 import torch.nn.functional as F
@@ -880,7 +881,8 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         deep each of the N (+ spare_points) user-visible points of query set `group` is, on the n frames from first_frame on (default:
         the frames of the window just tracked, as in epipolar()) -- the launch of ctk_fit_epipolar and then the launch of ctk_fit_pose
         on its matrix and labels (ops.StreamGroups.epipolar and .pose on the stream's own history and logits): two launches, no wait.
-        intrinsics: (fx, fy, cx, cy), four Python floats, one pinhole camera in raw-video pixels.  tol, hypotheses, min_base, seed and
+        intrinsics: (fx, fy, cx, cy), four Python floats, one pinhole camera in raw-video pixels (a caller who does not know them:
+        calibrate() reads the focal length off the tracks, intrinsics() makes the four floats).  tol, hypotheses, min_base, seed and
         mask are epipolar()'s; min_points holds for both: the matrix needs that many inliers, the pose that many points labelled 1.
         The range errors are epipolar()'s.  Returns, on the device: pose float32 [n,3,4] = (R | t) with X_f = R X_(f - lag) + t in
         camera coordinates and |t| = 1, (I | 0) where there is no fit; depth float32 [n,N,2] = (depth on frame f - lag, depth on frame
@@ -905,12 +907,77 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         return pose[0], depth[0], label[0], stats[0]
 
     @torch.no_grad()
+    def calibrate(self, n=None, first_frame=None, lag=8, candidates=64, span=(0.25, 4.0), focals=None, principal=None, tol=1.0,
+                  hypotheses=512, min_base=16.0, min_points=16, min_frames=1, contrast=1.5, seed=0, mask=None, group=0, state=None):
+        """Not in the reference: the focal length of the camera, for a caller who does not know the intrinsics pose() and everything
+        behind it ask for, read off the tracks of query set `group` on the n frames from first_frame on (default: the frames of the
+        window just tracked, as in epipolar()) -- the launch of ctk_fit_epipolar and then the two launches of ctk_fit_focal on its
+        matrices and labels (ops.StreamGroups.epipolar and .focal on the stream's own history and logits): three launches, no wait.
+        Each frame f is paired with frame f - lag; `candidates` focal lengths geometric over span * W of the raw video (or `focals`:
+        ascending host numbers, or a float32 device tensor) are swept through pose()'s rules, each pair scores each candidate in
+        pixels, and the scores are summed.  principal: (cx, cy) in raw-video pixels, assumed, not estimated; None: the picture centre
+        ((W - 1) / 2, (H - 1) / 2), or with `lens` set the principal point of lens.ideal -- the calibration is then of lens.ideal's
+        picture, the one the stream tracks.  tol, hypotheses, min_base, seed and mask are epipolar()'s; min_points holds for both.
+        state: what an earlier call returned: its curve is added to, so that evidence accumulates over windows (its candidates and
+        principal point are used again; candidates, span, focals and principal are then not looked at).  The range errors are
+        epipolar()'s.  Returns (focal, state): focal a float32 device scalar, 0 where there is no fit yet -- fewer than min_frames
+        pairs took part, or the curve's largest total is below `contrast` times its smallest: the camera has not TURNED between the
+        frames of the pairs (under a pure translation every focal length explains the matrices equally well) --; state = (curve int64
+        [K+2] on the device, focals float32 [K] on the device, principal).  intrinsics(focal, state[2]) makes the four floats.  Known
+        limits: square pixels, an assumed principal point, a camera that must turn, ONE fixed focal length per accumulation (start a
+        new state after a zoom), no distortion estimate, no second finer sweep, no bundle adjustment."""
+        who = "calibrate"
+        gs, scale = self._running(who)
+        group = int(group)
+        if not 0 <= group < gs.G:
+            raise ValueError(f"{who}: group must lie in [0, {gs.G})")
+        first_frame, n = self._newest_frames(gs, n, first_frame, who)
+        curve = None
+        if state is not None:
+            if not (isinstance(state, tuple) and len(state) == 3 and isinstance(state[0], torch.Tensor) and isinstance(state[1], torch.Tensor)):
+                raise ValueError(f"{who}: state must be what an earlier calibrate() returned: (curve, focals, principal)")
+            curve, focals, principal = state[0][None], state[1], state[2]
+        elif principal is None:
+            H, W = self._hw
+            principal = ((W - 1) * 0.5, (H - 1) * 0.5) if self._lens is None else tuple(float(v) for v in self._lens.ideal[2:4])
+        principal = (float(principal[0]), float(principal[1]))
+        mask = None if mask is None else mask[None]
+        source = dict(lag=lag, N_out=self.N, scale=scale, thresh=0.6, first_row=self._emit_first_row(), group=group)
+        fund, label, _, _ = self.model.stream_epipolar(first_frame, n, mask=mask, tol=tol, hypotheses=hypotheses, min_base=min_base,
+                                                       min_points=min_points, seed=seed, **source)
+        focal, curve, _, _, focals = self.model.stream_focal(first_frame, n, fund, label, focals=focals, size=self._hw, candidates=candidates,
+                                                             span=span, principal=principal, mask=mask, tol=tol, min_points=min_points,
+                                                             min_frames=min_frames, contrast=contrast, curve=curve, **source)
+        return focal[0], (curve[0], focals, principal)
+
+    def intrinsics(self, focal, principal=None):
+        """Not in the reference: (f, f, cx, cy) as four Python floats -- what pose(), reconstruct(), localize() and extend() take --
+        from calibrate()'s focal length.  THE one device-to-host copy of the calibration: it waits for the stream's work up to the
+        calibrate() call.  principal: (cx, cy), or calibrate()'s state (its principal point is used), or None: the picture centre, or
+        with `lens` set the principal point of lens.ideal (calibrate()'s own default).  ValueError when focal is 0: there is no fit
+        yet -- the camera has not turned between the paired frames, or too few frames took part; push more frames and pass the
+        state on."""
+        who = "intrinsics"
+        if isinstance(principal, tuple) and len(principal) == 3 and isinstance(principal[0], torch.Tensor):
+            principal = principal[2]
+        if principal is None:
+            if self._hw is None:
+                raise RuntimeError(f"{who}: no stream has been started, so the picture centre is unknown: pass principal")
+            H, W = self._hw
+            principal = ((W - 1) * 0.5, (H - 1) * 0.5) if self._lens is None else tuple(float(v) for v in self._lens.ideal[2:4])
+        f = float(focal.item() if isinstance(focal, torch.Tensor) else focal)  # the one wait
+        if not (math.isfinite(f) and f > 0.0):
+            raise ValueError(f"{who}: focal is {f}: calibrate() has no fit yet (the camera has not turned between the paired frames, "
+                             "or too few frames took part)")
+        return (f, f, float(principal[0]), float(principal[1]))
+
+    @torch.no_grad()
     def reconstruct(self, intrinsics, frame=None, lag=8, max_depth=64.0, group=0, tol=1.0, hypotheses=512, min_base=16.0, min_points=16,
                     seed=0, mask=None):
         """Not in the reference: the static points of query set `group` in 3-D, reconstructed ONCE from the pair (frame - lag, frame)
         (default: the newest tracked frame) -- pose() for that one pair (two launches), ops.structure_from_pose (elementwise torch: the
         depth on `frame` times the point's ray) and one pin(frame), without a wait.  intrinsics: (fx, fy, cx, cy), four Python floats,
-        one pinhole camera in raw-video pixels; tol, hypotheses, min_base, min_points, seed and mask are pose()'s; max_depth (in
+        one pinhole camera in raw-video pixels (unknown: calibrate() and intrinsics()); tol, hypotheses, min_base, min_points, seed and mask are pose()'s; max_depth (in
         baselines of the pair) drops far points, which carry no parallax: a parameter, not a measured optimum.  ValueError when
         frame - lag is negative or has left the ring (history_frames) or the frame has not been tracked, as split_scene().  Returns an
         ops.Structure: points float32 [N_model,3] on the device in the camera coordinates of `frame`, valid int8 [N_model] (labelled

@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_focal and ctk_fit_focal_workspace_bytes on the new
+ *       struct ctk_fit_focal_args, which is ctk_fit_pose_args with a principal point in place of four intrinsics: K candidate focal
+ *       lengths are swept through ctk_fit_pose's rules over ctk_fit_epipolar's matrices and labels, every (frame, candidate) gets an
+ *       int64 cost in pixels, and per group the smallest total over the frames (and over earlier calls, curve_in) is chosen and
+ *       refined, or refused where the curve is flat (csrc/focal_math.h); two launches, no atomics.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_p3p and ctk_fit_p3p_workspace_bytes on the new
  *       struct ctk_fit_p3p_args, which is ctk_fit_resection_args without seed_pose: per frame, the camera's pose against a fixed 3-D structure
  *       WITHOUT a seed: every candidate is the pose of three sampled points (six Newton rounds on their three scales from the
@@ -1517,6 +1522,84 @@ typedef struct ctk_fit_p3p_args {
 } ctk_fit_p3p_args;
 int ctk_fit_p3p_workspace_bytes(const ctk_fit_p3p_args* a, size_t* out_bytes);
 int ctk_fit_p3p(const ctk_fit_p3p_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit focal: the focal length the camera had, read off the tracks -----------------------------------------------------------------------
+ * ctk_fit_pose and everything behind it want four intrinsics.  The one a caller cannot guess is the focal length; the principal point
+ * is the picture centre to within what these fits can see.  Over a fit list there is one focal length at which a rigid pose explains
+ * the correspondences as well as the unconstrained fundamental matrix does: ctk_fit_focal sweeps K candidate focal lengths through
+ * ctk_fit_pose's rules, scores each in pixels, sums the scores over the frames of the call (and of earlier calls) in integers, and
+ * takes the minimum, per group g.  The rules are stated once in csrc/focal_math.h, on top of csrc/pose_math.h.
+ *
+ * The frame of the call is ctk_fit_pose's; everything not named here is its own bit for bit: the gather, the fit list (label 1 and
+ * mask nonzero), `fundamental` and `label` as ctk_fit_epipolar wrote them, the rays, E, the decomposition, the vote, the two rounds.
+ *   camera     of candidate k: fx = fy = focals[k] (device float32 [K]; ascending is the caller's duty), cx and cy the call's.
+ *              Square pixels only.  A candidate stands iff it is finite and > 0; one that does not sets stats[3] bit 2.
+ *   takes part a frame takes part iff its fit list has M >= min_points entries and ctk_fit_pose's E is accepted (F not all zero,
+ *              finite, E finite) under at least one standing candidate.  A frame that does not costs 0 everywhere and is not counted.
+ *   score      per (frame that takes part, candidate): the pose of ctk_fit_pose's rules under that camera; per fit-list entry under
+ *              the final pose, with r and g of the refinement: c = min(((r r) / g) (f f) / (tol tol), 1), 1 where !(g > 0) or the
+ *              quotient is a NaN -- the squared Sampson distance in pixels, truncated at tol^2, in units of tol^2;
+ *              term = llrint(c 2^32).  cost int64 [G,F,K] = the sum of the terms; M 2^32 where the candidate does not stand or no
+ *              pose comes out.  F <= 65535 keeps a call's sums below 2^61.
+ *   totals     curve int64 [G,K+2]: curve[k] = curve_in[k] + the sum of cost[.][k] over the frames; curve[K] and curve[K+1] carry the
+ *              counted frames and entries the same way.  curve_in (NULL: zeros) is the curve of an earlier call with the same focals:
+ *              evidence accumulates over calls without a wait; two calls accumulated equal one call over both frame sets.
+ *   choice     no fit when the counted frames < min_frames.  i = the smallest total (the lowest index on ties), mx = the largest.  No
+ *              fit and bit 1 when !((double)mx >= contrast * (double)total[i]): the curve is flat -- the camera did not turn
+ *              between the frames, and F does not depend on the focal length then -- or when candidate i does not stand.
+ *   refine     0 < i < K-1: a = total[i-1] - total[i], d = total[i+1] - total[i] (in integers), delta = 0.5 (a - d) / (a + d) where
+ *              a + d > 0; f = f_i + delta (f_{i+1} - f_i) for delta >= 0, f_i + delta (f_i - f_{i-1}) below; f_i where a + d is not
+ *              > 0 or that neighbour does not stand.  At either end of the range f = f_i and bit 0: the range was too narrow.
+ *   outputs    focal float32 [G], 0.0f where there is no fit; stats int32 [G,4] = (frames counted, i or -1, entries counted, bits),
+ *              the counts clamped to int32.  Every element of the four outputs is written by one plain store.
+ * Two launches on `stream`.  The sweep: grid (frame, group, four candidates), 256 threads, the fit list staged once in N_out * 18
+ * bytes of LDS, a wave per candidate (wave shuffles for the votes and sums, lane 0 solves in the wave's own LDS).  The choice: one
+ * workgroup per group adds the costs, counts the frames that took part by the sweep's own rule, chooses and refines.  No atomics, no
+ * host synchronisation, capture-safe.  The workspace query answers 0 and `workspace` may be NULL.  Before any launch: NULL a,
+ * hist_coords, fundamental, label, focals, focal, curve, cost or stats, `visible` NULL with hist_vis or hist_conf NULL, one of
+ * anchor_coords / anchor_visible without the other: CTK_E_NULL; every shape ctk_fit_pose refuses for the fields both structs have,
+ * K outside 1..256, min_frames < 1, tol not finite or not > 0, contrast not finite or < 1, cx or cy not finite: CTK_E_SHAPE;
+ * hist_coords or anchor_coords not 8-byte aligned, fundamental, focals, focal or stats not 4-byte aligned, curve_in, curve or cost not
+ * 8-byte aligned: CTK_E_ALIGN.  The query checks the same shapes and reads no pointer of the struct.
+ *
+ * Known limits.  Square pixels.  The principal point is assumed, not estimated.  The camera must TURN between the two frames of a
+ * pair: under a pure translation every focal length explains F equally well, and the contrast rule refuses the fit.  One fixed focal
+ * length per accumulation (no zoom).  No distortion estimate.  No second, finer sweep around the minimum. */
+typedef struct ctk_fit_focal_args {
+  int32_t G, N;               /* query groups, points per group of the history                     */
+  int32_t N_out;              /* points per group that are looked at (the first N_out), <= 8192    */
+  int32_t R;                  /* history rows per group                                            */
+  int32_t f0, F;              /* row j of the inputs and of cost is frame f0 + j, 0 <= j < F       */
+  int32_t to;                 /* a fixed source frame, or -1                                       */
+  int32_t lag;                /* source = f - lag (>= 1), or 0                                     */
+  int32_t anchor_frame;       /* the frame the anchor was taken on (with anchor_coords)            */
+  int32_t min_points;         /* a frame takes part with this many entries on its fit list, 8..8192 */
+  int32_t K;                  /* candidates, 1..256                                                */
+  int32_t min_frames;         /* a fit needs this many frames that took part, >= 1                 */
+  float cx, cy;               /* the principal point, raw-video pixels                             */
+  float sx, sy;               /* position = coords * (sx, sy)                                      */
+  float thresh;               /* visible from logits: sigmoid(vis) * sigmoid(conf) > thresh        */
+  float tol;                  /* the score is truncated at tol^2; raw-video pixels, finite and > 0 */
+  float contrast;             /* largest total / smallest total that a fit needs, finite and >= 1  */
+  int32_t reserved;           /* 0 */
+  const float* hist_coords;
+  const uint8_t* visible;     /* [G,R,N], or NULL: hist_vis / hist_conf and thresh                 */
+  const float* hist_vis; const float* hist_conf;
+  const int32_t* first_row;   /* optional */
+  const float* anchor_coords; /* [G,N,2], or NULL                                                  */
+  const uint8_t* anchor_visible; /* [G,N], with anchor_coords                                      */
+  const int8_t* mask;         /* [G,N], or NULL: every correspondence labelled 1 is fitted on      */
+  const float* fundamental;   /* [G,F,3,3], as ctk_fit_epipolar wrote it; read only                */
+  const int8_t* label;        /* [G,F,N_out], as ctk_fit_epipolar wrote it; read only              */
+  const float* focals;        /* [K], the candidates in raw-video pixels; read only                */
+  const int64_t* curve_in;    /* [G,K+2], or NULL: the curve of an earlier call; read only         */
+  float* focal;               /* [G] */
+  int64_t* curve;             /* [G,K+2] */
+  int64_t* cost;              /* [G,F,K] */
+  int32_t* stats;             /* [G,4] */
+} ctk_fit_focal_args;
+int ctk_fit_focal_workspace_bytes(const ctk_fit_focal_args* a, size_t* out_bytes);
+int ctk_fit_focal(const ctk_fit_focal_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- fit structure: points added to a 3-D structure, and the structure restated on a newer frame ---------------------------------------
  * ctk_fit_resection places cameras against a structure that only shrinks.  ctk_fit_structure turns "tracked on several localised
