@@ -27,8 +27,14 @@ namespace {
 
 // torch divides a tensor by a host scalar as a multiplication with the scalar's float reciprocal (queries / stride, / 2^l, history /
 // stride): the kernels take 1 / stride, rounded once on the host, and multiply.
-// float -> integer frame index as torch's .long() does it (truncation toward zero); NaN / out-of-range frames match no window
-__device__ __forceinline__ long qframe_of(float f) { return (long)f; }
+// float -> integer frame index as torch's .long() does it (truncation toward zero); NaN / out-of-range frames match no window:
+// a frame that is NaN or outside [-2^31, 2^31) becomes QFRAME_NONE, which lies beyond every ind + S (<= 2^31) and leaves room
+// for the long arithmetic of its readers.  (The bare conversion is no such rule: it takes NaN to frame 0.)
+constexpr long QFRAME_NONE = 1L << 62;
+__device__ __forceinline__ long qframe_of(float f) {
+  if (!(f >= -2147483648.0f && f < 2147483648.0f)) return QFRAME_NONE;
+  return (long)f;
+}
 
 // ---- begin: one thread per (g, t, n) of the window state ------------------------------------------------------------------
 // the history row of frame f in a ring of R rows; every use below has wave-uniform operands (block indices, kernel arguments)

@@ -350,7 +350,9 @@ int ctk_window_tokens_batch(const ctk_window_batch* batch, const ctk_model_weigh
  * `ind` is the first frame of the window (a multiple of `step`), the same number for every group; overlap = S - step.
  *   begin:   point_mask = qframe < ind + S.  A point with ind > 0 and qframe < ind + overlap takes history rows ind .. ind+overlap-1
  *            (coords / stride), the last of them repeated `step` times; any other point takes its query (x, y) / stride and zero
- *            logits.  qframe = (integer) queries[.,0], truncated as torch's .long().
+ *            logits.  qframe = (integer) queries[.,0], truncated as torch's .long().  A frame that is NaN or outside
+ *            [-2^31, 2^31) matches no window: it reads as a frame beyond every ind + S in begin, support, the resident assign and
+ *            health (point_mask 0, begun from its query, never sampled, never carried; a plain assign; a pending slot).
  *   support: per level, ONLY the points with left <= qframe < right (left = 0 at ind == 0, else ind + step; right = ind + S) are
  *            sampled at frame qframe - ind of fmaps[l] (NHWC [S,H_l,W_l,128], the window's pyramid) at (x, y) / stride / 2^l
  *            with the arithmetic of ctk_sample_support, and ADDED into support[l]; every other row is neither read nor written.
