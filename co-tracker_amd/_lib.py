@@ -451,6 +451,26 @@ class Focal:
         ]
 
 
+class Align:
+    """Holder of ctk_fit_align_args (include/ctk.h, "fit align"), nested like Resection.Args and for the same reason; its layout is
+    checked against the compiler by tests/test_align_cabi.py.  The constants mirror csrc/align_math.h; the list cap and the ceiling of
+    `hypotheses` are Resection's."""
+
+    MIN_POINTS, ROUNDS, REACH = 3, 3, 1048576.0
+    BIT_ROUND, BIT_LEFT, BIT_CAP, BIT_IDENTICAL = 2, 4, 8, 32
+
+    class Args(C.Structure):
+        """ctk_fit_align_args: two point sets with their validity bytes, a camera for the second, two tolerances -> per pair the
+        similarity (s R | t) and its scale, a label and a squared pixel distance per slot, and the fit's counts."""
+        _fields_ = [
+            ("G", C.c_int32), ("N", C.c_int32), ("min_points", C.c_int32), ("hypotheses", C.c_int32), ("seed", C.c_uint32),
+            ("reserved", C.c_int32),
+            ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("tol", C.c_float), ("depth_tol", C.c_float),
+            ("a", _fp), ("valid_a", _fp), ("b", _fp), ("valid_b", _fp), ("mask", _fp),
+            ("sim", _fp), ("scale", _fp), ("label", _fp), ("error", _fp), ("stats", _fp),
+        ]
+
+
 class Structure3D:
     """Holder of ctk_fit_structure_args (include/ctk.h, "fit structure"), nested like Resection.Args and for the same reason; its layout
     is checked against the compiler by tests/test_structure_cabi.py.  The constants mirror csrc/structure_math.h."""
@@ -575,6 +595,8 @@ SYMBOLS = {
     "ctk_fit_resection": (C.c_int, [_P(Resection.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_p3p_workspace_bytes": (C.c_int, [_P(P3p.Args), _P(C.c_size_t)]),
     "ctk_fit_p3p": (C.c_int, [_P(P3p.Args), _fp, C.c_size_t, _fp]),
+    "ctk_fit_align_workspace_bytes": (C.c_int, [_P(Align.Args), _P(C.c_size_t)]),
+    "ctk_fit_align": (C.c_int, [_P(Align.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_focal_workspace_bytes": (C.c_int, [_P(Focal.Args), _P(C.c_size_t)]),
     "ctk_fit_focal": (C.c_int, [_P(Focal.Args), _fp, C.c_size_t, _fp]),
     "ctk_fit_structure_workspace_bytes": (C.c_int, [_P(Structure3D.Args), _P(C.c_size_t)]),

@@ -1079,6 +1079,11 @@ class CoTrackerThreeOnline(CoTrackerThreeBase):
         default one alike."""
         return self._running_stream().p3p(f0, F, intrinsics, structure, valid, **kw)
 
+    def stream_align(self, a, valid_a, b, valid_b, intrinsics, **kw):
+        """The similarity between two point sets over the slots of the running (or just closed) stream, by one launch and without a
+        wait: ops.StreamGroups.align.  It reads no history and touches nothing of the stream."""
+        return self._running_stream().align(a, valid_a, b, valid_b, intrinsics, **kw)
+
     def stream_structure(self, f0, F, intrinsics, pose, **kw):
         """One 3-D point per slot from the frames [f0, f0 + F) of the running (or just closed) stream under the poses stream_resection
         returned for them, the old structure carried along and everything restated in the camera of one of the frames -- straight

@@ -211,6 +211,9 @@ class CoTracker2(TrackerBase):
     def stream_p3p(self, *args, **kwargs):  # the history it reads is the CoTracker3 online model's device stream state
         raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_p3p on a v2 model is not implemented")
 
+    def stream_align(self, *args, **kwargs):  # the slots it aligns over are the CoTracker3 online model's device stream state
+        raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_align on a v2 model is not implemented")
+
     def stream_structure(self, *args, **kwargs):  # the history it reads is the CoTracker3 online model's device stream state
         raise NotImplementedError("CoTracker2 (model_v2.py) keeps no stream state on the device; stream_structure on a v2 model is not implemented")
 

@@ -1913,6 +1913,106 @@ def fit_p3p(tracks: torch.Tensor, visible: torch.Tensor, intrinsics, structure: 
 
 
 # ------------------------------------------------------------------------------------------
+# fit align (csrc/align.hip; include/ctk.h, "fit align")
+# ------------------------------------------------------------------------------------------
+def _align_fit(a, valid_a, b, valid_b, intrinsics, mask, tol, depth_tol, hypotheses, min_points, seed, out, who: str):
+    """The body of fit_align and StreamGroups.align: the args, the rules and the one launch of ctk_fit_align.  There is no history in
+    this call, so no source is bound."""
+    if not (isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.dim() in (2, 3) and a.shape[-1] == 3):
+        raise ValueError(f"{who}: a must be a float32 device tensor [N,3] or [G,N,3]")
+    a, valid_a, b, valid_b, mask = _group_axis(a, 2), _group_axis(valid_a, 1), _group_axis(b, 2), _group_axis(valid_b, 1), _group_axis(mask, 1)
+    G, N, dev = a.shape[0], a.shape[1], a.device
+    if not (1 <= N <= L.Motion.POINTS_MAX and 1 <= G <= 65535):
+        raise ValueError(f"{who}: between 1 and {L.Motion.POINTS_MAX} slots per set and at most 65535 pairs, got {N} and {G}")
+    g = L.Align.Args()
+    g.G, g.N, g.reserved = G, N, 0
+    g.min_points = _min_points_of(min_points, L.Align.MIN_POINTS, who)
+    _sampling(g, hypotheses, seed, tol, None, who, resection=True)
+    _intrinsics(g, intrinsics, who)
+    g.depth_tol = float(depth_tol)
+    if not (math.isfinite(g.depth_tol) and 0.0 < g.depth_tol <= 3.0e38):
+        raise ValueError(f"{who}: depth_tol must be finite and > 0 (a share of the depth)")
+    g.a = _tensor_ptr(a, _F32, (G, N, 3), "a", dev, who)
+    g.valid_a = _tensor_ptr(valid_a, _BYTES, (G, N), "valid_a", dev, who)
+    g.b = _tensor_ptr(b, _F32, (G, N, 3), "b", dev, who)
+    g.valid_b = _tensor_ptr(valid_b, _BYTES, (G, N), "valid_b", dev, who)
+    g.mask = None if mask is None else _tensor_ptr(mask, _BYTES, (G, N), "mask", dev, who)
+    specs = [("sim", torch.float32, (G, 3, 4)), ("scale", torch.float32, (G,)), ("label", torch.int8, (G, N)),
+             ("error", torch.float32, (G, N)), ("stats", torch.int32, (G, 4))]
+    out = _out_tuple(out, specs, dev, who)
+    for (name, _, _), t_ in zip(specs, out):
+        setattr(g, name, t_.data_ptr())
+    L.check(L.load().ctk_fit_align(C.byref(g), None, 0, _stream()), "ctk_fit_align")  # (the workspace query answers 0)
+    return out
+
+
+def fit_align(a: torch.Tensor, valid_a: torch.Tensor, b: torch.Tensor, valid_b: torch.Tensor, intrinsics, mask: Optional[torch.Tensor] = None,
+              tol: float = 2.0, depth_tol: float = 0.1, hypotheses: int = 256, min_points: int = 8, seed: int = 0, out=None):
+    """The similarity that best maps one set of 3-D points onto another, b ~ s R a + t with s > 0, robustly: by one launch and without
+    a wait (ctk_fit_align; include/ctk.h and csrc/align_math.h have the rules).  Works on any tensors -- two structures of a stream,
+    offline results, surveyed points -- as long as slot n of both sets is the same point.
+
+    a, b         float32 [G,N,3] / [N,3]: the two sets; b in the coordinates of a camera (z forward), whose pinhole model `intrinsics` is.
+    valid_a, valid_b   int8 / uint8 / bool [G,N] / [N]: which slots hold a point.  A slot is a correspondence when both bytes are
+                 nonzero, all six numbers are finite and at most 2^20 in magnitude and b's depth is > 0.
+    intrinsics   (fx, fy, cx, cy), four Python floats: the camera of b's frame, in whose pixels tol is stated.
+    mask         int8 / uint8 / bool [G,N] / [N] or None: the correspondences that may take part in the fit; all are classified.
+    Each of the `hypotheses` candidates is the similarity that three sampled correspondences fix (the scale from the two triangles'
+    sides, the rotation from their frames); the last candidate is the identity.  A point is within tolerance when s R a + t lies in
+    front of the camera, within tol pixels of b's projection and within depth_tol of b's depth (relative); the candidate with most
+    such points wins, the lowest on ties, and is refined by three Gauss-Newton rounds on those two errors.  Returns (sim float32
+    [G,3,4]: row r = (s R[r], t[r]), apply_similarity applies it; all zero where there is no fit; scale float32 [G]: s, 0 where there
+    is no fit; label int8 [G,N]: 1 within tolerance, 0 not, -1 no correspondence; error float32 [G,N]: the squared pixel distance,
+    +inf behind the camera, -1 without a correspondence or a fit; stats int32 [G,4] = (points fitted on, points labelled 1, the
+    winning candidate or -1, bits: 1 a round kept its transform, 2 an entry was left out, 3 more than 4096 points, 5 the sets are
+    identical: exactly (1, I, 0))); `out`: such a tuple to write into.  A fit needs min_points (>= 3) points within tolerance.
+    Limits: one similarity per pair; at least three non-collinear common points; no covariance; a degenerate inlier set keeps the
+    candidate's transform (bit 1)."""
+    return _align_fit(a, valid_a, b, valid_b, intrinsics, mask, tol, depth_tol, hypotheses, min_points, seed, out, "fit_align")
+
+
+def apply_similarity(sim: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """sim [...,3,4] = (s R | t) of fit_align on points [...,N,3] -> s R X + t, [...,N,3] (elementwise torch, no wait)."""
+    return points @ sim[..., :3].transpose(-1, -2) + sim[..., None, :, 3]
+
+
+def compose_similarity(pose: torch.Tensor, sim: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """A pose [...,3,4] = (R_p | t_p) against a's world, X_f = R_p X_a + t_p in a's unit, stated against b's world and in b's unit,
+    with sim [...,3,4] = (s R | t) and scale [...] = s of fit_align(a, b) (elementwise torch, no wait).
+    X_b = s R X_a + t gives X_a = R^T (X_b - t) / s, so X_f = R_p R^T (X_b - t) / s + t_p; times s, the same camera point in b's unit:
+    s X_f = (R_p R^T) X_b + (s t_p - R_p R^T t).  Hence R' = R_p R^T and t' = s t_p - R' t.  Where there is no fit (scale 0) the
+    result is not finite."""
+    s = scale[..., None, None]
+    Rn = pose[..., :3] @ (sim[..., :3] / s).transpose(-1, -2)
+    return torch.cat([Rn, s * pose[..., 3:] - Rn @ sim[..., 3:]], dim=-1)
+
+
+def camera_centre(pose: torch.Tensor) -> torch.Tensor:
+    """Where the camera of a pose [...,3,4] = (M | t) with X_f = M X_w + t stands in the world's coordinates and unit: -M^-1 t, [...,3]
+    (a 3 x 3 solve in torch, no wait).  For a rigid pose this is -R^T t; it also holds for what world_pose() returns against a structure
+    of merge_structures, whose left block is a rotation times the scale between the two units -- there -R^T t would be off by s^2."""
+    return -torch.linalg.solve(pose[..., :3], pose[..., 3])
+
+
+def merge_structures(a: "Structure", b: "Structure", sim: torch.Tensor, label: torch.Tensor) -> "Structure":
+    """Two structures of one stream as one, on b's anchor, in b's unit and b's camera, from what fit_align(a.points, a.valid, b.points,
+    b.valid) returned for them (sim [3,4], label [N]; elementwise torch, no wait): b's points where b has one; where b has none and a
+    has one, a's point carried over by sim -- if there is a fit (a slot labelled 1) and the carried point lies in front of b's
+    camera.  origin = (s R | t) composed with a.origin, the map from the first world of a's chain into b's camera and unit, so that
+    world_pose() of a pose against the merged structure keeps answering in that first world: its left block is a rotation times s
+    (the two units differ), so the camera's centre is camera_centre(pose) = -M^-1 t, in the first world's unit -- NOT -R^T t --, and
+    (M | t) / s is the rigid pose there."""
+    if not (isinstance(a, Structure) and isinstance(b, Structure)):
+        raise ValueError("merge_structures: a and b must be ops.Structure")
+    carried = apply_similarity(sim, a.points)
+    take = (a.valid != 0) & (b.valid == 0) & (label == 1).any() & (carried[:, 2] > 0) & torch.isfinite(carried).all(dim=-1)
+    points = torch.where(take[:, None], carried, b.points)
+    valid = torch.where(take, torch.ones_like(b.valid), b.valid)
+    origin = sim if a.origin is None else torch.cat([sim[:, :3] @ a.origin[:, :3], sim[:, :3] @ a.origin[:, 3:] + sim[:, 3:]], dim=-1)
+    return Structure(points, valid, b.anchor, b.intrinsics, origin)
+
+
+# ------------------------------------------------------------------------------------------
 # fit structure (csrc/structure.hip; include/ctk.h, "fit structure")
 # ------------------------------------------------------------------------------------------
 def min_sin2_of(min_parallax: float) -> float:
@@ -2780,6 +2880,17 @@ class StreamGroups:
         otherwise.  -> (pose [G,F,3,4], label [G,F,N_out], error [G,F,N_out], stats [G,F,4]) on the device.  No wait."""
         src = _HistorySource(self, "p3p", f0, F, N_out, group, first_row, scale, thresh)
         return _resection_fit(src, intrinsics, structure, valid, None, lag, to, anchor, tol, hypotheses, min_points, seed, out, kind="p3p")
+
+    def align(self, a: torch.Tensor, valid_a: torch.Tensor, b: torch.Tensor, valid_b: torch.Tensor, intrinsics, *,
+              mask: Optional[torch.Tensor] = None, tol: float = 2.0, depth_tol: float = 0.1, hypotheses: int = 256, min_points: int = 8,
+              seed: int = 0, out=None):
+        """The similarity b ~ s R a + t between two point sets over this stream's slots (a, b float32 [G,N,3] / [N,3] with their
+        validity bytes [G,N] / [N], N the stream's slots per group, on the stream's device; only read) by the one launch of
+        ctk_fit_align: fit_align has the picture.  The call reads no history, so no frame has to be held by the ring; nothing of the
+        stream is touched.  -> (sim [G,3,4], scale [G], label [G,N], error [G,N], stats [G,4]) on the device.  No wait."""
+        if not (isinstance(a, torch.Tensor) and a.device == self.coords.device and a.shape[-2:] == (self.N, 3)):
+            raise ValueError(f"align: a must be a float32 tensor [{self.N},3] or [G,{self.N},3] on {self.coords.device}")
+        return _align_fit(a, valid_a, b, valid_b, intrinsics, mask, tol, depth_tol, hypotheses, min_points, seed, out, "align")
 
     def structure(self, f0: int, F: int, intrinsics, pose: torch.Tensor, *, pose_stats: Optional[torch.Tensor] = None,
                   structure: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, source_frame: int = 0,

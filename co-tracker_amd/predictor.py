@@ -1076,6 +1076,58 @@ class CoTrackerOnlinePredictor(torch.nn.Module):
         return pose[0], label[0], error[0], stats[0]
 
     @torch.no_grad()
+    def align(self, a, b, mask=None, tol=2.0, depth_tol=0.1, hypotheses=256, min_points=8, seed=0):
+        """Not in the reference: the similarity that maps ops.Structure `a` onto ops.Structure `b` of the running stream, over the
+        slots both hold -- what carries a trajectory over a loss (a new reconstruct() has a unit and a camera of its own), and what
+        compares an extended structure with a fresh reconstruction of the same slots.  ONE launch and no wait: ctk_fit_align
+        (include/ctk.h, "fit align").  Each of the `hypotheses` candidates is the similarity three sampled common points fix; the one
+        with most points within `tol` pixels (in b's camera, b.intrinsics) and `depth_tol` of b's depth wins and is refined by three
+        Gauss-Newton rounds.  Nothing of the stream is read, waited for, re-captured or re-allocated.  Returns, on the device: sim
+        float32 [3,4] = (s R | t) with X_b = s R X_a + t (all zero: no fit), scale float32 [] = s (0: no fit), label int8 [N_model]:
+        1 the two agree, 0 they do not (the point moved between the two, or no fit), -1 not in both; error float32 [N_model]: the
+        squared pixel distance (-1: label -1 or no fit); stats int32 [4] = (points fitted on, points labelled 1, the winning
+        candidate or -1, bits as ops.fit_align).  ops.merge_structures(a, b, sim, label) makes one structure of the two;
+        ops.compose_similarity restates a pose against a.  Limits: one similarity per pair; at least three non-collinear common
+        points; no covariance; a degenerate inlier set keeps the candidate's transform (bit 1).  ValueError for structures of
+        different slot counts; NotImplementedError on a v2 predictor."""
+        from . import ops
+        who = "align"
+        self._running(who)
+        if not (isinstance(a, ops.Structure) and isinstance(b, ops.Structure)):
+            raise ValueError(f"{who}: a and b must be ops.Structure (reconstruct, extend)")
+        sim, scale, label, error, stats = self.model.stream_align(a.points, a.valid, b.points, b.valid, b.intrinsics, mask=mask, tol=tol,
+                                                                  depth_tol=depth_tol, hypotheses=hypotheses, min_points=min_points, seed=seed)
+        return sim[0], scale[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
+    def georeference(self, structure, known, slots, intrinsics=None, tol=2.0, depth_tol=0.1, hypotheses=256, min_points=3, seed=0):
+        """Not in the reference: an ops.Structure put into a caller's metric frame from a few surveyed points.  known: float32 [M,3],
+        the points of the slots `slots` (M integers, distinct, each a slot of the structure) in the metric frame; they are scattered
+        into an [N_model,3] buffer with a validity mask (elementwise torch) and align()'s one launch finds X_metric = s R X_structure
+        + t: `scale` is metres per structure unit.  No wait.  The tolerance is in the pixels of `intrinsics` (fx, fy, cx, cy), a
+        camera of the metric frame that looks along its z axis, so the known points need z > 0 there; a caller without such a camera
+        passes None -- the structure's own intrinsics -- and states the known points in the axes of the structure's anchor camera
+        (x right, y down, z forward, in metres).  Returns align()'s tuple; ops.apply_similarity(sim, structure.points) are the
+        metric points, ops.compose_similarity(pose, sim, scale) the metric pose.  Three known points fix the similarity and leave
+        nothing to judge it by: give more where there are more (6 and min_points=4 drop one wrong survey point).  Limits: align()'s."""
+        from . import ops
+        who = "georeference"
+        self._running(who)
+        if not isinstance(structure, ops.Structure):
+            raise ValueError(f"{who}: structure must be an ops.Structure (reconstruct, extend)")
+        pts = structure.points
+        slots = torch.as_tensor(slots, dtype=torch.long, device=pts.device).reshape(-1)
+        if not (isinstance(known, torch.Tensor) and known.dtype == torch.float32 and tuple(known.shape) == (slots.numel(), 3)):
+            raise ValueError(f"{who}: known must be a float32 tensor [{slots.numel()},3], one row per slot")
+        metric = torch.zeros_like(pts)
+        valid = torch.zeros_like(structure.valid)
+        metric[slots], valid[slots] = known.to(pts.device), 1
+        cam = structure.intrinsics if intrinsics is None else intrinsics
+        sim, scale, label, error, stats = self.model.stream_align(pts, structure.valid, metric, valid, cam, tol=tol, depth_tol=depth_tol,
+                                                                  hypotheses=hypotheses, min_points=min_points, seed=seed)
+        return sim[0], scale[0], label[0], error[0], stats[0]
+
+    @torch.no_grad()
     def extend(self, structure, frame=None, n=None, first_frame=None, tol=2.0, min_views=3, min_parallax=1.0, refine=False, poses=None,
                **localize_kw):
         """Not in the reference: points added to an ops.Structure, and the structure restated on a newer frame -- the keyframe step

@@ -47,6 +47,11 @@ extern "C" {
 #endif
 
 /* ABI history (what a binding written against an older header must know):
+ *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_align and ctk_fit_align_workspace_bytes on the new
+ *       struct ctk_fit_align_args: per pair of 3-D point sets the similarity Y ~ s R X + t that maps one onto the other: every candidate
+ *       is the transform of three sampled common points (the ratio of the triangles' sides, ctk_fit_p3p's polar(B A^-1)), scored by an
+ *       integer count under a pixel and a depth tolerance and refitted by three fixed-point Gauss-Newton rounds on seven parameters
+ *       (csrc/align_math.h); one launch, no atomics, no stream history.
  *   v9, additive (number unchanged; no existing struct or symbol changed): + ctk_fit_focal and ctk_fit_focal_workspace_bytes on the new
  *       struct ctk_fit_focal_args, which is ctk_fit_pose_args with a principal point in place of four intrinsics: K candidate focal
  *       lengths are swept through ctk_fit_pose's rules over ctk_fit_epipolar's matrices and labels, every (frame, candidate) gets an
@@ -1602,6 +1607,67 @@ typedef struct ctk_fit_focal_args {
 } ctk_fit_focal_args;
 int ctk_fit_focal_workspace_bytes(const ctk_fit_focal_args* a, size_t* out_bytes);
 int ctk_fit_focal(const ctk_fit_focal_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- fit align: the similarity that maps one 3-D point set onto another ---------------------------------------------------------------------
+ * Every structure of the 3-D chain lives in a unit and a camera frame of its own.  ctk_fit_align finds, per pair g, Y ~ s R X + t with
+ * s > 0 between the points a[g] (X) and b[g] (Y) that share slots, robustly: points that moved between the two sets are labelled out.
+ * The rules are stated once in csrc/align_math.h, on top of csrc/p3p_math.h; the kernel, a g++ build and numpy agree on every bit.
+ *   correspondence  slot n with valid_a and valid_b nonzero, six finite floats of magnitude <= 2^20 and Y_z > 0.
+ *   fit list   the correspondences whose mask byte is nonzero (mask NULL: all), ascending n, the first 4096 (M of them; more: stats[3]
+ *              bit 3).  Every correspondence is classified, listed or not.
+ *   candidates k < hypotheses (1..1024): the first three indices of ctk_fit_planes' seeded sample (frame 0); with M = 3 the entries
+ *              (0, 1, 2).  s^2 = the sum of the three squared sides in b over that in a, s by ctk_fit_pose's reciprocal root;
+ *              R = polar(B A^-1) of the two triangle frames as in ctk_fit_p3p, a's sides scaled by s first; a collinear or repeated
+ *              triple in either set skips the candidate; t = Y_0 - s R X_0.  k = hypotheses: (1, I, 0).  Where every correspondence
+ *              has the same floats in both sets only that one is scored (bit 5) and the result is exactly (1, I, 0).
+ *   score      Z = s R X + t is within iff Z_z > 0, the squared pixel distance of the projections of Z and Y by (fx, fy, cx, cy) is
+ *              <= tol^2 (compared without a division) and |Z_z - Y_z| <= depth_tol Y_z.  The integer count decides; the lowest k on
+ *              ties; fewer than min_points (3..8192), M < 3 or no candidate: no fit.
+ *   refit      three Gauss-Newton rounds over the entries within 4, 2, 1 x (tol, depth_tol) under the round's transform, seven
+ *              parameters about b's camera centre: Z' = (1 + d)(I + [w]x) Z + T, so s' = s (1 + d), R' = polar(R + [w]x R),
+ *              t' = ((t + w x t) + d t) + T.  The residual is what the score judges: the two pixel differences u - ub and v - vb with
+ *              (u, v) = (Z_x, Z_y) / Z_z, (ub, vb) = (Y_x, Y_y) / Y_z, and the relative depth difference (Z_z - Y_z) / Y_z, weighted
+ *              1 : fy / fx : tol / (fx depth_tol) (each in units of its tolerance, up to tol / fx).  T is solved in units of 2^e, e the
+ *              largest frexp exponent of Y_z over the round's entries.  An entry's three rows of eight numbers (the gradient by
+ *              (w, T 2^-e, d) and the residual) are scaled by 1/16 and by their weight; an entry with one of its 24 numbers above 4
+ *              in magnitude is left out (bit 2), so the 36 int64 sums of llrint(x_i x_j 2^44) stay below 2^62; ctk_fit_planes' 8 x 8
+ *              L D L^T with one padded row.  A round that fails -- fewer than 3 entries, the solve, a rotation or translation that
+ *              ctk_fit_pose would not accept, an s that is not finite or not > 0 -- keeps its transform (bit 1).
+ *   outputs    sim float32 [G,3,4]: row r = (s R[r][0..2], t[r]), to be applied to homogeneous points; scale float32 [G];
+ *              label int8 [G,N]: 1 within tolerance, 0 not, -1 no correspondence; error float32 [G,N]: the squared pixel distance, +inf
+ *              where Z_z <= 0, -1 without a correspondence or a fit; stats int32 [G,4] = (M, slots labelled 1, the winning k or -1,
+ *              bits).  No fit: sim all zero, scale 0, every correspondence label 0 and error -1.
+ * One launch on `stream`, one workgroup of 256 threads per pair with the fit list (six floats an entry) in min(N, 4096) * 24 bytes of
+ * LDS; a candidate is made by ONE lane, 64 a wave at a time; no atomics, no host synchronisation, capture-safe; every output element
+ * is one plain store and the inputs are only read.  The workspace query answers 0 and `workspace` may be NULL.  Errors before any
+ * launch: NULL a, a, valid_a, b, valid_b, sim, scale, label, error or stats: CTK_E_NULL; G outside 1..65535, N outside 1..8192,
+ * hypotheses outside 1..1024, min_points outside 3..8192, fx or fy not finite or not > 0, cx or cy not finite, tol or depth_tol not
+ * finite or not > 0, reserved != 0: CTK_E_SHAPE; a, b, sim, scale, error or stats not 4-byte aligned: CTK_E_ALIGN.
+ *
+ * Known limits.  One similarity per pair; at least three non-collinear common points; no covariance; a degenerate inlier set keeps
+ * the candidate's transform (bit 1); the refit turns about b's camera centre, so b is expected in a camera's frame. */
+typedef struct ctk_fit_align_args {
+  int32_t G, N;               /* pairs, slots per set                                              */
+  int32_t min_points;         /* a fit needs this many entries within tolerance, 3..8192           */
+  int32_t hypotheses;         /* sampled candidates, 1..1024                                       */
+  uint32_t seed;              /* of the generator                                                  */
+  int32_t reserved;           /* 0                                                                 */
+  float fx, fy, cx, cy;       /* the pinhole camera of b's frame                                   */
+  float tol;                  /* pixel tolerance in that camera, finite and > 0                    */
+  float depth_tol;            /* relative depth tolerance, finite and > 0                          */
+  const float* a;             /* [G,N,3]; read only                                                */
+  const int8_t* valid_a;      /* [G,N], nonzero: the point exists; read only                       */
+  const float* b;             /* [G,N,3]; read only                                                */
+  const int8_t* valid_b;      /* [G,N]; read only                                                  */
+  const uint8_t* mask;        /* [G,N], nonzero: the correspondence may be on the fit list; or NULL */
+  float* sim;                 /* [G,3,4] */
+  float* scale;               /* [G] */
+  int8_t* label;              /* [G,N] */
+  float* error;               /* [G,N] */
+  int32_t* stats;             /* [G,4] */
+} ctk_fit_align_args;
+int ctk_fit_align_workspace_bytes(const ctk_fit_align_args* a, size_t* out_bytes);
+int ctk_fit_align(const ctk_fit_align_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- fit structure: points added to a 3-D structure, and the structure restated on a newer frame ---------------------------------------
  * ctk_fit_resection places cameras against a structure that only shrinks.  ctk_fit_structure turns "tracked on several localised
